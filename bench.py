@@ -20,6 +20,13 @@ Inputs (keys with shift tables, matrices, assignments) are resident in HBM befor
     python bench.py --gpus 4                      # starts 4 rank processes itself (rank r -> device r)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 2 --device 0           # rehearsal: 2 ranks on ONE GPU (gloo gathers)
+    python bench.py --full                        # + checks, end_to_end, CPU baseline, BLS12-381, with_synthesis
+    python bench.py --dump-outputs DIR            # + the last timed step's responses as DIR/*.npy
+
+A plain run sets up, warms up, times the steps and prints the headline line (with the roofline figures derived from
+the timed steps' own kernel timings).  Everything that needs work of its own after the timed region - the uncontended
+kernel run behind `roofline.alone`, the checks of the timed proofs, the `end_to_end` aggregation, the CPU baseline,
+the BLS12-381 `secondary` and the `with_synthesis` legs - runs with `--full` only (each still subject to its --no-*).
 """
 import argparse
 import hashlib
@@ -80,6 +87,12 @@ def parse():
                          "puts several ranks on one GPU)")
     ap.add_argument("--device", type=int, default=None,
                     help="force a device index for every rank (rehearsing N > 1 ranks on a 1-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement also run the uncontended kernel measurement (roofline.alone), "
+                         "the checks of the timed proofs, end_to_end, the CPU baseline and the secondary / with_synthesis "
+                         "legs (off by default: a plain run does only what the headline figure needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's gathered responses as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -571,6 +584,26 @@ def timed_run(job, steps, warmup, barrier):
     return time.time() - t0
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(job, out_dir):
+    """What a caller of the timed path receives from its last step: the gathered stage-0 (104 B) and stage-1 (328 B)
+    response records of every subcircuit, in subcircuit order, one float32 per byte (exact: the values are 0..255).
+    Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of the subcircuits is written (each record starts with its
+    subcircuit index)."""
+    import numpy as np
+    all0, all1 = (np.asarray(r, np.uint8) for r in job.last_records)
+    rows = np.arange(len(all0))
+    cap = DUMP_LIMIT_BYTES // (4 * (all0.shape[1] + all1.shape[1]))
+    if len(rows) > cap:
+        rows = np.sort(np.random.default_rng(0).choice(len(rows), cap, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, recs in (("stage0_responses", all0), ("stage1_responses", all1)):
+        np.save(os.path.join(out_dir, name + ".npy"), recs[rows].astype(np.float32))
+    log("last timed step's responses of %d subcircuits written to %s" % (len(rows), out_dir))
+
+
 def roofline_of(job, curve, ms_per_proof=None):
     """Dominant kernel = k_msm_accum0<Fq> (bucket accumulation), launched 5 times per subcircuit: H query (m-1 dense
     terms), A / B1 / L queries (n_v-1, n_v-1, n1 terms) and the stage-0 commitment.  Algorithmic bytes per launch =
@@ -693,12 +726,12 @@ def main():
     if os.environ.get("HK_BENCH_ECHO_RANK"):
         log("rank %d of %d starting (pid %d)" % (rank, world, os.getpid()))
     # host half of every job first: spawned worker processes, before this process touches HIP
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
-    want_secondary = rank == 0 and world == 1 and not args.no_secondary and args.curve == "bn254"
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_secondary = args.full and rank == 0 and world == 1 and not args.no_secondary and args.curve == "bn254"
     prep = prepare_job_host(args, args.curve, rank, world, single_class=args.single_class)
     prep2 = prepare_job_host(args, "bls12_381", 0, 1, single_class=True, witnesses=2) if want_secondary else None
     # third leg: the same job shape on REAL SHA-256 subcircuits with every stage-1 assignment generated inside the step
-    want_synth = (rank == 0 and world == 1 and not args.no_synthesis_leg and args.curve == "bn254"
+    want_synth = (args.full and rank == 0 and world == 1 and not args.no_synthesis_leg and args.curve == "bn254"
                   and args.config == "big-merkle-64x32" and not args.witness_gen and args.subcircuits == 64)
     args3 = prep3 = None
     if want_synth:
@@ -755,24 +788,24 @@ def main():
         parts = [None] * world
         dist.all_gather_object(parts, sorted(job.classes))
         rank_classes = parts
+    if args.dump_outputs and rank == 0:
+        dump_outputs(job, args.dump_outputs)
     # the dominant kernel WITHOUT other proofs sharing the chip: three proofs one after another on one lane, after the
     # timed region (reported beside the timed-region figure, never instead of it)
-    alone = []
-    try:
-        if args.no_verify:                       # the counter-collection passes keep exactly 5 launches per subcircuit
-            raise RuntimeError("skipped with --no-verify")
-        i0 = job.shard[0]
-        com0 = job.last_records[0][i0][8:8 + job.ctx.g1_bytes]
-        for _ in range(3):
-            _rec, t = job._stage1((i0, com0))
-            alone.append(t)
-        job.alone = alone[1:]
-    except Exception as e:       # noqa: BLE001
-        if not args.no_verify:
+    job.alone = []
+    if args.full and not args.no_verify:         # the counter-collection passes keep exactly 5 launches per subcircuit
+        alone = []
+        try:
+            i0 = job.shard[0]
+            com0 = job.last_records[0][i0][8:8 + job.ctx.g1_bytes]
+            for _ in range(3):
+                _rec, t = job._stage1((i0, com0))
+                alone.append(t)
+            job.alone = alone[1:]
+        except Exception as e:       # noqa: BLE001
             log("rank %d: uncontended measurement failed: %r" % (rank, e))
-        job.alone = []
     checks = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         t0 = time.time()
         checks = job.verify_last_step()              # every rank checks its own shard; raises on failure
         checks["seconds"] = time.time() - t0
@@ -780,7 +813,7 @@ def main():
     proofs = world * args.subcircuits * args.steps
     e2e = None
     n_tot = world * args.subcircuits
-    if not args.no_e2e and job.synthetic and n_tot & (n_tot - 1) == 0:
+    if args.full and not args.no_e2e and job.synthetic and n_tot & (n_tot - 1) == 0:
         try:
             e2e = end_to_end(job, use_dist, dt / args.steps)          # every rank: the verifying keys are gathered
             if rank == 0:

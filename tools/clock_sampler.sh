@@ -6,7 +6,8 @@ cd "$(dirname "$0")/.." || exit 1
 mkdir -p gpurun_out
 OUT=gpurun_out/clock_samples.txt
 : > $OUT
-timeout -k 10 300 python bench.py --no-cpu-baseline --no-secondary --steps 12 --warmup 2 > gpurun_out/clock_bench.json 2> gpurun_out/clock_bench.err &
+D=$(dirname $OUT)
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-secondary --steps 12 --warmup 2 > $D/clock_bench.json 2> $D/clock_bench.err &
 BP=$!
 t0=$(date +%s%N)
 while kill -0 $BP 2>/dev/null; do
