@@ -9,6 +9,7 @@
 //   (the coordinator's step between the rounds is not part of the worker path)
 //   round 2: for every subcircuit                       process_stage1_request_with_cb (worker.rs:150-195):
 //            hk_prove(...) with the SAME kappa re-derived from com_seed (worker.rs:236-241)  -> Stage1Response
+//            (--batch-prove: one hk_prove_batch per key class instead, compute_responses of node.rs:760-795)
 //   write every response as the reference's ark-serialize bytes: <out>/stage0_resp_<i>.bin, stage1_resp_<i>.bin
 //   (util.rs:79-91 cli_filenames), print one JSON line with the job's timing
 //
@@ -19,6 +20,7 @@
 //
 // build:  make -C apps      (g++ -O2 -std=c++17 -pthread ... -lhekaton, rpath = hekaton_system_amd/lib)
 // usage:  hk_all_in_one <job_dir> <out_dir> [--threads T] [--steps K] [--warmup W] [--device D] [--host-inputs] [--curve C]
+//                       [--no-batch-commit] [--batch-prove]
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -103,6 +105,7 @@ int main(int argc, char** argv) {
     bool host_inputs = false;
     bool bls = false;
     bool batch_commit = true;
+    bool batch_prove = false;
     for (int i = 3; i < argc; i++) {
         std::string a = argv[i];
         if (a == "--threads" && i + 1 < argc) threads = (unsigned)atoi(argv[++i]);
@@ -111,6 +114,7 @@ int main(int argc, char** argv) {
         else if (a == "--device" && i + 1 < argc) device = atoi(argv[++i]);
         else if (a == "--host-inputs") host_inputs = true;
         else if (a == "--no-batch-commit") batch_commit = false;
+        else if (a == "--batch-prove") batch_prove = true;
         else if (a == "--curve" && i + 1 < argc) { std::string c = argv[++i]; bls = c == "bls12_381"; if (!bls && c != "bn254") { fprintf(stderr, "unknown curve %s\n", c.c_str()); return 2; } }
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -191,6 +195,28 @@ int main(int argc, char** argv) {
             }
             round1.push_back(Task{c, 0, true});
         }
+        // --batch-prove: round 2 as one hk_prove_batch per key class - the members' assignments row after row (resident in
+        // one device buffer per class unless --host-inputs), r, s and kappas likewise, laid out before the timed region
+        struct ProveRows { std::vector<size_t> members; Bytes z, r, s, kappas; void* zdev = nullptr; size_t n_v = 0; };
+        std::vector<ProveRows> prow(batch_prove ? n_cls : 0);
+        for (size_t c = 0; c < prow.size(); c++) {
+            ProveRows& pr = prow[c];
+            pr.members = crow[c].members;
+            for (size_t i : pr.members) {
+                const Assignment& as = classes[c]->assigns[subs[i].assign];
+                if (pr.n_v && as.n_v != pr.n_v) throw std::runtime_error("assignments of one class differ in length");
+                pr.n_v = as.n_v;
+                pr.z.insert(pr.z.end(), as.host.begin(), as.host.end());
+                pr.r.insert(pr.r.end(), subs[i].r.begin(), subs[i].r.end());
+                pr.s.insert(pr.s.end(), subs[i].s.begin(), subs[i].s.end());
+                Bytes kappa = kappa_of(subs[i].com_seed);
+                pr.kappas.insert(pr.kappas.end(), kappa.begin(), kappa.end());
+            }
+            if (!host_inputs && !pr.z.empty()) {
+                check(hk_dev_alloc(ctx.raw(), pr.z.size(), &pr.zdev), "hk_dev_alloc");
+                check(hk_dev_upload(ctx.raw(), pr.zdev, pr.z.data(), pr.z.size()), "hk_dev_upload");
+            }
+        }
         std::vector<Stage0Response> resp0(n_sub);
         std::vector<Stage1Response> resp1(n_sub);
         auto step = [&]() {
@@ -220,6 +246,20 @@ int main(int argc, char** argv) {
                 resp0[i] = Stage0Response{(uint64_t)i, com, sc.com_seed};
             });
             // round 2 (worker.rs:150-195): kappa re-derived from the seed, the commitment travels inside the proof
+            if (batch_prove) {
+                parallel_for(n_cls, threads, [&](size_t c) {
+                    const ProveRows& pr = prow[c];
+                    if (pr.members.empty()) return;
+                    std::vector<Proof> ps = CPGroth16::prove_batch(ctx, classes[c]->pk, host_inputs ? (const void*)pr.z.data() : pr.zdev,
+                                                                   pr.n_v, pr.r, pr.s, pr.kappas, 1, pr.members.size());
+                    for (size_t k = 0; k < pr.members.size(); k++) {
+                        size_t i = pr.members[k];
+                        ps[k].ds = {resp0[i].com};
+                        resp1[i] = Stage1Response{(uint64_t)i, ps[k]};
+                    }
+                });
+                return;
+            }
             parallel_for(n_sub, threads, [&](size_t i) {
                 const Subcircuit& sc = subs[i];
                 KeyClass& kc = *classes[sc.cls];
@@ -249,11 +289,14 @@ int main(int argc, char** argv) {
         for (auto& kc : classes)
             for (auto& as : kc->assigns)
                 if (as.dev) hk_dev_free(ctx.raw(), as.dev);
+        for (auto& pr : prow)
+            if (pr.zdev) hk_dev_free(ctx.raw(), pr.zdev);
         printf("{\"driver\": \"hk_all_in_one (C++ over the C ABI)\", \"curve\": \"%s\", \"subcircuits\": %zu, \"classes\": %zu, \"threads\": %u, "
                "\"steps\": %u, \"warmup\": %u, \"ms_per_step\": %.3f, \"proofs_per_s\": %.3f, \"inputs\": \"%s\", "
-               "\"key_load_s\": %.2f}\n",
+               "\"key_load_s\": %.2f, \"prove\": \"%s\"}\n",
                bls ? "bls12_381" : "bn254", n_sub, n_cls, threads, steps, warmup, dt / steps * 1e3, n_sub * steps / dt,
-               host_inputs ? "host (PCIe per proof)" : "resident", load_s);
+               host_inputs ? "host (PCIe per proof)" : "resident", load_s,
+               batch_prove ? "hk_prove_batch per class" : "hk_prove per subcircuit");
         return 0;
     } catch (const Error& e) {
         fprintf(stderr, "hekaton error: %s\n", e.what());

@@ -67,7 +67,8 @@ EXPORTS = ["hk_status_str", "hk_version", "hk_ctx_create", "hk_ctx_destroy", "hk
            "hk_dev_upload", "hk_dev_download", "hk_msm_g1", "hk_msm_g2", "hk_ntt", "hk_witness_map",
            "hk_pk_upload", "hk_pk_free", "hk_commit", "hk_prove", "hk_fixed_base_g1", "hk_fixed_base_g2", "hk_scalar_pairing_g1", "hk_scalar_pairing_g2", "hk_field_convert", "hk_bases_upload", "hk_bases_free",
            "hk_msm_bases", "hk_multi_pairing", "hk_pairing_products", "hk_ctx_gt_bytes",
-           "hk_points_lincomb_g1", "hk_points_lincomb_g2", "hk_points_fold_g2", "hk_points_fold_g1", "hk_points_fold_many_g1", "hk_points_fold_many_g2", "hk_pairing_pairs", "hk_keccak_f1600", "hk_assignment_from_bits", "hk_wprog_upload", "hk_wprog_free", "hk_wprog_run", "hk_gt_pow", "hk_fq12_pow", "hk_gt_pow_prod", "hk_poseidon_path", "hk_assignment_scatter", "hk_commit_batch"]
+           "hk_points_lincomb_g1", "hk_points_lincomb_g2", "hk_points_fold_g2", "hk_points_fold_g1", "hk_points_fold_many_g1", "hk_points_fold_many_g2", "hk_pairing_pairs", "hk_keccak_f1600", "hk_assignment_from_bits", "hk_wprog_upload", "hk_wprog_free", "hk_wprog_run", "hk_gt_pow", "hk_fq12_pow", "hk_gt_pow_prod", "hk_poseidon_path", "hk_assignment_scatter", "hk_commit_batch",
+           "hk_prove_batch"]
 
 _lib = None
 
@@ -142,6 +143,7 @@ def load():
     lib.hk_commit.argtypes = [vp, vp, sz, vp, sz, vp, vp]
     lib.hk_commit_batch.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp]
     lib.hk_prove.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp]
+    lib.hk_prove_batch.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, sz, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -642,4 +644,22 @@ class DevicePk:
         check(ctx.lib.hk_prove(ctx.handle, self.handle, ptr(z), n_v, r.ctypes.data, s.ctypes.data,
                                kap.ctypes.data if nk else None, nk, a.ctypes.data, b.ctypes.data,
                                c.ctypes.data), "hk_prove")
+        return a, b, c
+
+    def prove_batch(self, z_rows, rs, ss, kappas, n_v, batch):
+        """hk_prove_batch: `batch` proofs of this key's class in one lock-step call.  z_rows: their assignments row after
+        row (batch x n_v Fr Montgomery; uint8 array or DeviceBuffer); rs, ss: batch Fr each; kappas: batch x n_kappas Fr
+        (uint8 arrays, Montgomery).  Returns (a, b, c) as (batch, g1 | g2 | g1 bytes) uint8 arrays; row b equals
+        prove() on row b."""
+        ctx = self.ctx
+        r = np.ascontiguousarray(rs, dtype=np.uint8).reshape(-1)
+        s = np.ascontiguousarray(ss, dtype=np.uint8).reshape(-1)
+        kap = np.ascontiguousarray(kappas, dtype=np.uint8).reshape(-1)
+        nk = len(kap) // (ctx.fr_bytes * batch) if batch else 0
+        a = np.zeros((batch, ctx.g1_bytes), dtype=np.uint8)
+        b = np.zeros((batch, ctx.g2_bytes), dtype=np.uint8)
+        c = np.zeros((batch, ctx.g1_bytes), dtype=np.uint8)
+        check(ctx.lib.hk_prove_batch(ctx.handle, self.handle, ptr(z_rows), n_v, r.ctypes.data, s.ctypes.data,
+                                     kap.ctypes.data if nk else None, nk, batch, a.ctypes.data, b.ctypes.data,
+                                     c.ctypes.data), "hk_prove_batch")
         return a, b, c

@@ -124,6 +124,8 @@ struct Ops {
     static hk_status commit_batch(hk_ctx*, const hk_pk*, size_t, const void*, size_t, const void*, size_t, void*);
     static hk_status prove(hk_ctx*, const hk_pk*, const void*, size_t, const void*, const void*,
                            const void*, size_t, void*, void*, void*);
+    static hk_status prove_batch(hk_ctx*, const hk_pk*, const void*, size_t, const void*, const void*,
+                                 const void*, size_t, size_t, void*, void*, void*);
     static void ctx_release(hk_ctx*);
     static hk_status fixed_base(hk_ctx*, int, const void*, const void*, size_t, int, void*);
     static hk_status scalar_pairing(hk_ctx*, int, const void*, const void*, size_t, void*);
@@ -157,7 +159,7 @@ struct Ops {
         b = finish_private_bytes();
         return b > m ? b : m;
     }
-    static size_t finish_private_bytes();      // prove_impl.cuh (k_finish)
+    static size_t finish_private_bytes();      // prove_impl.cuh (k_finish, k_finish_b)
     static hk_status poseidon_path(hk_ctx*, const void*, size_t, const hk_poseidon_desc*, const hk_poseidon_desc*, const void*,
                                    const void*, const uint32_t*, size_t, size_t, size_t, size_t, void*);
 
@@ -167,7 +169,8 @@ struct Ops {
                                    &ctx_release, &fixed_base, &scalar_pairing, &field_convert, &bases_upload,
                                    &bases_free, &msm_bases, &pairing_products,
                                    sizeof(Fp12<typename Fq::Params>), &points_lincomb, &points_fold_g2, &points_fold_g1, &assignment_from_bits, &wprog_upload, &wprog_free, &wprog_run, &gt_pow,
-                                   &max_private_bytes, &poseidon_path, &points_fold_many, &pairing_pairs, &assignment_scatter, &commit_batch};
+                                   &max_private_bytes, &poseidon_path, &points_fold_many, &pairing_pairs, &assignment_scatter, &commit_batch,
+                                   &prove_batch};
         return &t;
     }
 };

@@ -143,6 +143,8 @@ struct CurveOps {
                                     size_t n_v, void* z_out);
     hk_status (*commit_batch)(hk_ctx*, const hk_pk*, size_t stage, const void* w, size_t n, const void* kappas, size_t batch,
                               void* out);
+    hk_status (*prove_batch)(hk_ctx*, const hk_pk*, const void* z, size_t n_v, const void* r, const void* s,
+                             const void* kappas, size_t n_kappas, size_t batch, void* a, void* b, void* c);
 };
 const CurveOps* curve_ops_bn254();
 const CurveOps* curve_ops_bls381();

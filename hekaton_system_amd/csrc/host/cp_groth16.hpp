@@ -134,6 +134,24 @@ struct CPGroth16 {                                                     // prover
               "hk_prove");
         return p;
     }
+    // hk_prove_batch: `batch` proofs of one key class in one lock-step call (the stage-1 half of a worker's
+    // compute_responses, node.rs:760-795).  z_rows: batch x n_v Fr row after row (host, or a device pointer); rs, ss:
+    // batch Fr each; kappas: batch x n_kappas Fr.  Proof b equals prove_last_stage's on row b (ds left empty).
+    static std::vector<Proof> prove_batch(const Context& ctx, ProvingKey& pk, const void* z_rows, size_t n_v, const Bytes& rs,
+                                          const Bytes& ss, const Bytes& kappas, size_t n_kappas, size_t batch) {
+        const Sizes& sz = ctx.sizes();
+        Bytes a(sz.g1 * batch), b(sz.g2 * batch), c(sz.g1 * batch);
+        check(hk_prove_batch(ctx.raw(), pk.device, z_rows, n_v, rs.data(), ss.data(), n_kappas ? kappas.data() : nullptr,
+                             n_kappas, batch, a.data(), b.data(), c.data()),
+              "hk_prove_batch");
+        std::vector<Proof> out(batch);
+        for (size_t k = 0; k < batch; k++) {
+            out[k].a.assign(a.begin() + k * sz.g1, a.begin() + (k + 1) * sz.g1);
+            out[k].b.assign(b.begin() + k * sz.g2, b.begin() + (k + 1) * sz.g2);
+            out[k].c.assign(c.begin() + k * sz.g1, c.begin() + (k + 1) * sz.g1);
+        }
+        return out;
+    }
 };
 
 class CommitmentBuilder {                                              // committer.rs:17-123

@@ -30,6 +30,12 @@ struct MsmSort {
     // count_is_zero: the caller cleared sb.count in a kernel of its own that precedes this call in stream order
     static hk_status run(hipStream_t s, const MsmPlan& p, const u32* scalars_d, int is_mont,
                          const SortBufs& sb, bool count_is_zero = false);
+    // `batch` independent sorts in lock-step (hk_prove_batch): every buffer of `sb` holds `batch` per-proof slices one
+    // fixed stride apart (msm.cuh msm_sorted_stride / msm_digits_stride); proof b's scalars start scalar_stride
+    // elements after proof a's.  sb.count must be zero (every proof's NB counters).
+    static hk_status alloc_b(Lane* L, const MsmPlan& p, u32 batch, SortBufs* out);
+    static hk_status run_b(hipStream_t s, const MsmPlan& p, const u32* scalars_d, size_t scalar_stride, int is_mont,
+                           u32 batch, const SortBufs& sb);
 };
 
 template <class F>
@@ -47,6 +53,13 @@ struct MsmRun {
     static hk_status run(hipStream_t s, const MsmPlan& p, const Affine<F>* table, u32 n_bases, u32 idx_off,
                          const SortBufs& sb, const Bufs& b, XYZZ<F>* result_d,
                          hipEvent_t ev0, hipEvent_t ev1);
+    // `batch` MSMs over the same table in lock-step (hk_prove_batch): one launch per stage with grid.y (or grid.x for the
+    // one-workgroup stages) = proof, the sorts of MsmSort::run_b, buffers of alloc_b, result of proof b at
+    // result_d[b * res_stride].  The chip's resident lanes are split across the batch (msm_lane_plan_b).
+    static hk_status alloc_b(Lane* L, const MsmPlan& p, u32 batch, Bufs* out);
+    static hk_status run_b(hipStream_t s, const MsmPlan& p, const Affine<F>* table, u32 n_bases, u32 idx_off, u32 batch,
+                           const SortBufs& sb, const Bufs& b, XYZZ<F>* result_d, u32 res_stride,
+                           hipEvent_t ev0, hipEvent_t ev1);
     static hk_status build_tables(hipStream_t s, Affine<F>* table, u32 n, u32 groups, u32 shift_bits);
     static hk_status to_affine(hipStream_t s, const XYZZ<F>* in, Affine<F>* out, u32 n);
     // fixed-base batch scalar multiplication (fixed_base.cuh); all pointers device.

@@ -137,6 +137,41 @@ def process_stage1_request_with_cb(rng, cb, com, rand, stage1_req):
     return Stage1Response(stage1_req.subcircuit_idx, proof)
 
 
+def process_stage1_requests_batch(rngs, cbs, coms, rands, reqs):
+    """The stage-1 pass of a worker over ALL the subcircuits it holds (compute_responses, mpi-snark/src/bin/node.rs:760-795,
+    around worker.rs:150-195) with the proofs of every proving-key class in one hk_prove_batch call: the last stage of each
+    request is synthesised on the host as CPGroth16.prove_last_stage does, r and then s are drawn from the request's own
+    rng in the order of prove_last_stage_with_zk, and the responses are those of process_stage1_request_with_cb request
+    by request.  rngs, cbs, coms, rands, reqs: one entry per request.  Returns [Stage1Response] in request order."""
+    from .cp_groth16 import FrCodec
+    prepared, groups = [], {}
+    for k, (rng, cb, com, rand, req) in enumerate(zip(rngs, cbs, coms, rands, reqs)):
+        assert getattr(cb.circuit, "subcircuit_idx", req.subcircuit_idx) == req.subcircuit_idx
+        pk = cb.pk
+        if len(pk.deltas_g) // pk.device.ctx.g1_bytes != 2:
+            raise AssertionError("deltas_g.len() == comm_rands.len() + 1")      # committer.rs:112
+        cs, circuit = cb.cs, cb.circuit
+        r, s = rng.fr(cs.r), rng.fr(cs.r)                       # prover.rs:28-29
+        circuit.generate_constraints(circuit.last_stage(), cs)  # prover.rs:70-75: synthesis stays on the host
+        cs.finalize()
+        fc = FrCodec(pk.device.ctx.curve)
+        z = getattr(circuit, "full_assignment_bytes", None)
+        z = z(cs) if z else fc.enc(cs.full_assignment())
+        n_v = cs.num_instance_variables() + cs.num_witness_variables()
+        prepared.append((req, com, np.frombuffer(bytes(z), np.uint8), r, s, rand, n_v))
+        groups.setdefault(id(pk), (pk, []))[1].append(k)
+    proofs = [None] * len(prepared)
+    for pk, members in groups.values():
+        fc = FrCodec(pk.device.ctx.curve)
+        n_v = prepared[members[0]][6]
+        rows = np.concatenate([prepared[k][2] for k in members])
+        enc = lambda i: np.frombuffer(bytes(fc.enc([prepared[k][i] for k in members])), np.uint8)
+        a, b, c = pk.device.prove_batch(rows, enc(3), enc(4), enc(5), n_v, len(members))
+        for j, k in enumerate(members):
+            proofs[k] = Proof(a=a[j].copy(), b=b[j].copy(), c=c[j].copy(), ds=[prepared[k][1]])
+    return [Stage1Response(p[0].subcircuit_idx, proof) for p, proof in zip(prepared, proofs)]
+
+
 class WorkerState:
     """mpi-snark/src/worker.rs:25-87: keeps the commitment builder between the two rounds and
     re-derives the commitment randomness from `com_seed` (worker.rs:63-66)."""

@@ -346,6 +346,32 @@ hk_status hk_prove(hk_ctx* ctx, const hk_pk* pk, const void* z_mont, size_t n_v,
                    const void* kappas_mont, size_t n_kappas,
                    void* proof_a_g1, void* proof_b_g2, void* proof_c_g1);
 
+/* hk_prove for `batch` subcircuits of one proving-key class in ONE call - the stage-1 half of a worker's
+ * compute_responses (mpi-snark/src/bin/node.rs:760-795: one task per subcircuit there).  Row b of every output is
+ * byte-identical to
+ *   hk_prove(ctx, pk, z + b*n_v, n_v, r + b, s + b, kappas + b*n_kappas, n_kappas, proofs_a + b, proofs_b + b, proofs_c + b)
+ * (pointer arithmetic in elements):
+ *   z_mont         [h|d] batch x n_v Fr, row after row (the layout hk_wprog_run / hk_assignment_scatter write)
+ *   r_mont, s_mont [h]   batch Fr each
+ *   kappas_mont    [h]   batch x n_kappas Fr, row after row
+ *   proofs_a_g1 [h] batch G1, proofs_b_g2 [h] batch G2, proofs_c_g1 [h] batch G1 (packed affine)
+ * Errors, for the batch as a whole and checked in this order: HK_ERR_ARG for a key of another context or one without
+ * QAP matrices; HK_ERR_LEN when n_v or n_kappas does not match the key; batch == 0 then returns HK_OK and touches
+ * nothing; HK_ERR_ARG for a NULL pointer (kappas only when n_kappas > 0).  A failed call leaves the lane usable.
+ * The proofs run in lock-step: every stage of hk_prove (digit sorts, the bucket accumulation of each of the five
+ * queries, the level / reduction tail, k_finish) is ONE launch for a whole chunk of proofs, each proof on its own
+ * slice of the buffers, over the key's shared shift tables; the witness map runs one chain per proof.
+ * Chunks: a batch is proven in consecutive chunks of at most HK_PROVE_BATCH_CHUNK proofs, and of fewer when a chunk's
+ * scratch (hk_prove's per-proof device buffers times the chunk, DESIGN.md "Batched proving") would not fit in the
+ * device's free memory plus the lane's own arena; a chunk is never smaller than one proof.
+ * hk_timings after the call: total_ms spans the whole call, every phase figure is summed over the chunks (within a
+ * chunk the queries overlap as in hk_prove); accum_kernel_launches counts the real k_msm_accum0<Fq> launches - four per
+ * chunk (A, B1, L, H; the G2 query is not counted, as for hk_prove) - and accum_kernel_ms their summed kernel time. */
+#define HK_PROVE_BATCH_CHUNK 8
+hk_status hk_prove_batch(hk_ctx* ctx, const hk_pk* pk, const void* z_mont, size_t n_v,
+                         const void* r_mont, const void* s_mont, const void* kappas_mont, size_t n_kappas,
+                         size_t batch, void* proofs_a_g1, void* proofs_b_g2, void* proofs_c_g1);
+
 #ifdef __cplusplus
 }
 #endif
