@@ -9,18 +9,19 @@ namespace hk {
 
 inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-inline size_t msm_sort_bytes(const MsmPlan& p) {
-    return al256(4ull * p.NB) * 2 + al256(4ull * (p.NB + 1)) + al256(4ull * ((size_t)p.n * p.W + 1)) +
-           al256(2ull * ((size_t)p.n * p.W + 8)) + 1024;
+// device bytes of MsmSort::alloc / MsmRun::alloc for `nb` proofs side by side
+inline size_t msm_sort_bytes(const MsmPlan& p, size_t nb = 1) {
+    return al256(4ull * p.NB * nb) * 2 + al256(4ull * (p.NB + 1) * nb) + al256(4ull * msm_sorted_stride(p) * nb) +
+           al256(2ull * msm_digits_stride(p) * nb) + 1024;
 }
 template <class F>
-inline size_t msm_run_bytes(const MsmPlan& p0) {
+inline size_t msm_run_bytes(const MsmPlan& p0, size_t nb = 1) {
     MsmPlan p = p0;
-    msm_set_lanes(p, 4u * 65536u);             // upper bound over the per-flavour lane schedules
-    size_t n0 = 2ull * p.T[0], n1 = p.n_levels > 1 ? 2ull * p.T[1] : 2;
-    return al256(sizeof(XYZZ<F>) * (p.NB + 1)) + al256(4 * n0) + al256(sizeof(XYZZ<F>) * n0) + al256(4 * n1) +
-           al256(sizeof(XYZZ<F>) * n1) + al256(sizeof(XYZZ<F>) * p.WP * (p.B / p.K)) +
-           al256(sizeof(XYZZ<F>) * p.WP) + 2048;
+    msm_set_lanes(p, (u32)(4u * 65536u / nb));   // upper bound over the per-flavour lane schedules (msm_lane_plan)
+    size_t n0 = 2ull * p.T[0], n1 = msm_p1_stride(p);
+    return al256(sizeof(XYZZ<F>) * (p.NB + 1) * nb) + al256(4 * n0 * nb) + al256(sizeof(XYZZ<F>) * n0 * nb) +
+           al256(4 * n1 * nb) + al256(sizeof(XYZZ<F>) * n1 * nb) + al256(sizeof(XYZZ<F>) * p.WP * (p.B / p.K) * nb) +
+           al256(sizeof(XYZZ<F>) * p.WP * nb) + 2048;
 }
 
 // window size for an MSM over caller-supplied bases (no shift tables: all W windows keep their own
@@ -122,8 +123,6 @@ struct Ops {
     static void pk_free(hk_pk*);
     static hk_status commit(hk_ctx*, const hk_pk*, size_t, const void*, size_t, const void*, void*);
     static hk_status commit_batch(hk_ctx*, const hk_pk*, size_t, const void*, size_t, const void*, size_t, void*);
-    static hk_status prove(hk_ctx*, const hk_pk*, const void*, size_t, const void*, const void*,
-                           const void*, size_t, void*, void*, void*);
     static hk_status prove_batch(hk_ctx*, const hk_pk*, const void*, size_t, const void*, const void*,
                                  const void*, size_t, size_t, void*, void*, void*);
     static void ctx_release(hk_ctx*);
@@ -159,13 +158,13 @@ struct Ops {
         b = finish_private_bytes();
         return b > m ? b : m;
     }
-    static size_t finish_private_bytes();      // prove_impl.cuh (k_finish, k_finish_b)
+    static size_t finish_private_bytes();      // prove_impl.cuh (k_finish)
     static hk_status poseidon_path(hk_ctx*, const void*, size_t, const hk_poseidon_desc*, const hk_poseidon_desc*, const void*,
                                    const void*, const uint32_t*, size_t, size_t, size_t, size_t, void*);
 
     static const CurveOps* table() {
         static const CurveOps t = {sizeof(Fr), sizeof(Fq), sizeof(Affine<Fq>), sizeof(Affine<Fq2>),
-                                   &msm, &ntt, &witness_map, &pk_upload, &pk_free, &commit, &prove,
+                                   &msm, &ntt, &witness_map, &pk_upload, &pk_free, &commit,
                                    &ctx_release, &fixed_base, &scalar_pairing, &field_convert, &bases_upload,
                                    &bases_free, &msm_bases, &pairing_products,
                                    sizeof(Fp12<typename Fq::Params>), &points_lincomb, &points_fold_g2, &points_fold_g1, &assignment_from_bits, &wprog_upload, &wprog_free, &wprog_run, &gt_pow,

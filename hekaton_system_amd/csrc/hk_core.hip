@@ -538,7 +538,7 @@ hk_status hk_commit_batch(hk_ctx* ctx, const hk_pk* pk, size_t stage, const void
 hk_status hk_prove(hk_ctx* ctx, const hk_pk* pk, const void* z, size_t n_v, const void* r, const void* s,
                    const void* kappas, size_t n_kappas, void* a, void* b, void* c) {
     if (!ctx || !pk || !z || !r || !s || !a || !b || !c) return HK_ERR_ARG;
-    return ctx->ops->prove(ctx, pk, z, n_v, r, s, kappas, n_kappas, a, b, c);
+    return ctx->ops->prove_batch(ctx, pk, z, n_v, r, s, kappas, n_kappas, 1, a, b, c);   // a batch of one
 }
 hk_status hk_prove_batch(hk_ctx* ctx, const hk_pk* pk, const void* z, size_t n_v, const void* r, const void* s,
                          const void* kappas, size_t n_kappas, size_t batch, void* a, void* b, void* c) {

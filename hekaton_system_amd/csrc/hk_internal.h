@@ -101,8 +101,6 @@ struct CurveOps {
     void (*pk_free)(hk_pk*);
     hk_status (*commit)(hk_ctx*, const hk_pk*, size_t stage, const void* w, size_t n, const void* kappa,
                         void* out);
-    hk_status (*prove)(hk_ctx*, const hk_pk*, const void* z, size_t n_v, const void* r, const void* s,
-                       const void* kappas, size_t n_kappas, void* a, void* b, void* c);
     void (*ctx_release)(hk_ctx*);
     hk_status (*fixed_base)(hk_ctx*, int group, const void* base, const void* scalars, size_t n, int mont,
                             void* out);

@@ -79,6 +79,15 @@ HK_HD LevelInfo msm_level_info(const MsmPlan& p, u32 E, int k) {
     return li;
 }
 
+// The sort and bucket kernels run a batch of proofs in lock-step (hk_prove_batch; a single MSM is a batch of one): the
+// proof index is grid.y, or grid.x for the one-workgroup stages (scan, tail), and selects the proof's slice of every
+// buffer by a fixed per-proof stride - count, cursor NB; start NB + 1; sorted n W + 1; digits n W + 8; buckets NB + 1
+// (the reduction ticket rides behind them); boundary partials 2 T[0] and msm_p1_stride; reduction partials WP B / K.
+// Sorted entries index their own proof's slice and never carry the proof.
+HK_HD size_t msm_sorted_stride(const MsmPlan& p) { return (size_t)p.n * p.W + 1; }
+HK_HD size_t msm_digits_stride(const MsmPlan& p) { return (size_t)p.n * p.W + 8; }
+HK_HD size_t msm_p1_stride(const MsmPlan& p) { return p.n_levels > 1 ? 2ull * p.T[1] : 2ull; }
+
 #if defined(__HIPCC__)
 
 // ---- digit extraction -----------------------------------------------------------------------------
@@ -115,18 +124,71 @@ __device__ __forceinline__ int msm_digit(const u32 (&sp)[10], u32 w, u32 c) {
 }
 
 // ---- counting sort, pass 1: histogram ------------------------------------------------------------
+// proof blockIdx.y: its scalars start scalar_stride_words u32 after the previous proof's
 template <class Fr>
 __global__ void __launch_bounds__(MSM_SORT_THREADS)
-k_msm_hist(const u32* __restrict__ scalars, int is_mont, MsmPlan p, u32* __restrict__ count,
-           short* __restrict__ digits) {
-#include "kbody/msm_hist.inc"
+k_msm_hist(const u32* __restrict__ scalars_all, size_t scalar_stride_words, int is_mont, MsmPlan p,
+           u32* __restrict__ count_all, short* __restrict__ digits_all) {
+    const size_t pr = blockIdx.y;
+    const u32* __restrict__ scalars = scalars_all + pr * scalar_stride_words;
+    u32* __restrict__ count = count_all + pr * p.NB;
+    short* __restrict__ digits = digits_all + pr * msm_digits_stride(p);
+    __shared__ u32 h[MSM_LDS_COUNTERS];
+    for (u32 b = threadIdx.x; b < p.NB; b += blockDim.x) h[b] = 0;
+    __syncthreads();
+    size_t base = (size_t)blockIdx.x * p.chunk;
+    for (u32 k = threadIdx.x; k < p.chunk; k += blockDim.x) {
+        size_t i = base + k;
+        if (i >= p.n) break;
+        u32 sp[10];
+        msm_load_scalar<Fr>(scalars, i, is_mont, p, sp);
+        for (u32 w = 0; w < p.W; w++) {
+            int d = msm_digit(sp, w, p.c);
+            // the signed digits are computed ONCE per scalar (Montgomery reduction + split) and kept, window-major,
+            // for the two passes of k_msm_scatter: 2 bytes per digit, coalesced across the lanes of a wave
+            digits[(size_t)w * p.n + i] = (short)d;
+            if (d != 0) {
+                u32 mag = d < 0 ? (u32)(-d) : (u32)d;
+                atomicAdd(&h[(w % p.WP) * p.B + mag - 1], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (u32 b = threadIdx.x; b < p.NB; b += blockDim.x) {
+        u32 v = h[b];
+        if (v) atomicAdd(&count[b], v);
+    }
 }
 
-// ---- exclusive scan of bucket counts (single workgroup) ---------------------------------------------
+// ---- exclusive scan of bucket counts (one workgroup per proof: blockIdx.x) -----------------------------
 template <int UNUSED>
 __global__ void __launch_bounds__(1024)
-k_msm_scan(const u32* __restrict__ count, u32* __restrict__ start, u32* __restrict__ cursor, u32 NB) {
-#include "kbody/msm_scan.inc"
+k_msm_scan(const u32* __restrict__ count_all, u32* __restrict__ start_all, u32* __restrict__ cursor_all, u32 NB) {
+    const size_t pr = blockIdx.x;
+    const u32* __restrict__ count = count_all + pr * NB;
+    u32* __restrict__ start = start_all + pr * (NB + 1);
+    u32* __restrict__ cursor = cursor_all + pr * NB;
+    __shared__ u32 part[1024];
+    u32 per = (NB + 1023) / 1024;
+    u32 lo = threadIdx.x * per, hi = min(lo + per, NB);
+    u32 s = 0;
+    for (u32 b = lo; b < hi; b++) s += count[b];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    // Hillis-Steele inclusive scan over 1024 partials
+    for (u32 off = 1; off < 1024; off <<= 1) {
+        u32 v = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    u32 run = threadIdx.x ? part[threadIdx.x - 1] : 0;
+    for (u32 b = lo; b < hi; b++) {
+        start[b] = run;
+        cursor[b] = run;
+        run += count[b];
+    }
+    if (threadIdx.x == 1023) start[NB] = part[1023];
 }
 
 // ---- counting sort, pass 2: scatter entry ids ----------------------------------------------------------
@@ -135,8 +197,41 @@ k_msm_scan(const u32* __restrict__ count, u32* __restrict__ start, u32* __restri
 __device__ __forceinline__ u32 msm_mag(int d) { return d < 0 ? (u32)(-d) : (u32)d; }
 template <class Fr>
 __global__ void __launch_bounds__(MSM_SORT_THREADS)
-k_msm_scatter(const short* __restrict__ digits, MsmPlan p, u32* __restrict__ cursor, u32* __restrict__ sorted) {
-#include "kbody/msm_scatter.inc"
+k_msm_scatter(const short* __restrict__ digits_all, MsmPlan p, u32* __restrict__ cursor_all, u32* __restrict__ sorted_all) {
+    const size_t pr = blockIdx.y;
+    const short* __restrict__ digits = digits_all + pr * msm_digits_stride(p);
+    u32* __restrict__ cursor = cursor_all + pr * p.NB;
+    u32* __restrict__ sorted = sorted_all + pr * msm_sorted_stride(p);
+    __shared__ u32 h[MSM_LDS_COUNTERS];
+    for (u32 b = threadIdx.x; b < p.NB; b += blockDim.x) h[b] = 0;
+    __syncthreads();
+    size_t base = (size_t)blockIdx.x * p.chunk;
+    for (u32 k = threadIdx.x; k < p.chunk; k += blockDim.x) {
+        size_t i = base + k;
+        if (i >= p.n) break;
+        for (u32 w = 0; w < p.W; w++) {
+            int d = digits[(size_t)w * p.n + i];
+            if (d != 0) atomicAdd(&h[(w % p.WP) * p.B + msm_mag(d) - 1], 1u);
+        }
+    }
+    __syncthreads();
+    // reserve this workgroup's range in every non-empty bucket; h[b] becomes the running position
+    for (u32 b = threadIdx.x; b < p.NB; b += blockDim.x) {
+        u32 v = h[b];
+        if (v) h[b] = atomicAdd(&cursor[b], v);
+    }
+    __syncthreads();
+    for (u32 k = threadIdx.x; k < p.chunk; k += blockDim.x) {
+        size_t i = base + k;
+        if (i >= p.n) break;
+        for (u32 w = 0; w < p.W; w++) {
+            int d = digits[(size_t)w * p.n + i];
+            if (d != 0) {
+                u32 pos = atomicAdd(&h[(w % p.WP) * p.B + msm_mag(d) - 1], 1u);
+                sorted[pos] = ((w / p.WP) << p.gshift) | (u32)i | (d < 0 ? 0x80000000u : 0u);
+            }
+        }
+    }
 }
 
 // ---- point I/O -----------------------------------------------------------------------------------------
@@ -216,13 +311,99 @@ template <class P> struct AccumOcc<Fp2<P>> { static constexpr int waves = P::N <
 // ---- level 0: equal slices of the sorted entry list, mixed adds into registers ---------------------
 // The sorted list was built for `n_entries` scalars per group; this base table has `n_bases` bases per
 // group and its base j corresponds to scalar j + idx_off (the L-query is a suffix of the assignment:
-// cp-groth16/src/prover.rs:111-117 vs :78-82).
+// cp-groth16/src/prover.rs:111-117 vs :78-82).  Proof blockIdx.y; every proof reads the one base table.
 template <class F>
 __global__ void __launch_bounds__(64, AccumOcc<F>::waves)
 k_msm_accum0(const Affine<F>* __restrict__ bases, u32 n_bases, u32 idx_off,
-             const u32* __restrict__ sorted, const u32* __restrict__ start, MsmPlan p,
-             XYZZ<F>* __restrict__ buckets, u32* __restrict__ pkeys, XYZZ<F>* __restrict__ ppts) {
-#include "kbody/msm_accum0.inc"
+             const u32* __restrict__ sorted_all, const u32* __restrict__ start_all, MsmPlan p,
+             XYZZ<F>* __restrict__ buckets_all, u32* __restrict__ pkeys_all, XYZZ<F>* __restrict__ ppts_all) {
+    const size_t pr = blockIdx.y, s0 = 2ull * p.T[0];
+    const u32* __restrict__ sorted = sorted_all + pr * msm_sorted_stride(p);
+    const u32* __restrict__ start = start_all + pr * (p.NB + 1);
+    XYZZ<F>* __restrict__ buckets = buckets_all + pr * (p.NB + 1);
+    u32* __restrict__ pkeys = pkeys_all + pr * s0;
+    XYZZ<F>* __restrict__ ppts = ppts_all + pr * s0;
+    u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    u32 E = start[p.NB];
+    LevelInfo li = msm_level_info(p, E, 0);
+    // No memset precedes this launch.  The reduction's ticket (one u32 behind the buckets) is cleared here; a bucket with
+    // no entries is never read (the reductions see start[b] == start[b + 1]); every other bucket is written exactly once by
+    // the lane in whose slice it STARTS - its sum when it also ends there, the neutral element when it continues into the
+    // next slices, whose partial sums the level kernels then add to it.
+    if (t == 0) *reinterpret_cast<u32*>(buckets + p.NB) = 0u;
+    if (t >= li.active) return;
+    u32 pos = t * li.L;
+    u32 end = min(pos + li.L, E);
+    u32 b = msm_find_bucket(start, p.NB, pos);
+    bool head_partial = start[b] < pos;
+    bool first = true;
+    u32 first_key = b;
+    u32 boundary = start[b + 1];
+    XYZZ<F> acc = XYZZ<F>::inf();
+    // boundary partials go straight to memory when they become known (keeping a second XYZZ value
+    // live across the loop costs 32+ VGPRs, i.e. a wave of occupancy)
+    st_vec(&ppts[2 * t], XYZZ<F>::inf());
+    if constexpr (AccumPrefetch<F>::value) {
+        // software pipeline, two deep: the entry of step pos + 2 and the 64-byte table row of step pos + 1 are
+        // requested before the mixed add of step pos, so neither link of the dependent chain entry -> row -> add
+        // stands between two adds of this wave
+        u32 e_n = 0, e_nn = 0;
+        bool v_n = false;
+        Affine<F> P_n;
+        auto request_row = [&](u32 e) {
+            e_n = e;
+            u32 g = (e & 0x7fffffffu) >> p.gshift;
+            u32 i = e & ((1u << p.gshift) - 1u);
+            v_n = i >= idx_off && i - idx_off < n_bases;
+            if (v_n) P_n = ld_vec(&bases[(size_t)g * n_bases + (i - idx_off)]);     // never touches an empty table
+        };
+        if (pos < end) request_row(sorted[pos]);
+        if (pos + 1 < end) e_nn = sorted[pos + 1];
+        for (; pos < end; pos++) {
+            Affine<F> P = P_n;
+            u32 e = e_n;
+            bool v = v_n;
+            if (pos + 1 < end) request_row(e_nn);
+            if (pos + 2 < end) e_nn = sorted[pos + 2];
+            if (pos == boundary) {
+                if (first && head_partial) st_vec(&ppts[2 * t], acc);
+                else st_vec(&buckets[b], acc);
+                first = false;
+                acc = XYZZ<F>::inf();
+                do { b++; boundary = start[b + 1]; } while (boundary <= pos);
+            }
+            if (v) {
+                if (e >> 31) P.y = F::neg(P.y);
+                acc = ec_madd<F, AccumInlineCorner<F>::value>(acc, P);
+            }
+        }
+    } else
+    for (; pos < end; pos++) {
+        if (pos == boundary) {
+            // bucket b ended exactly here
+            if (first && head_partial) st_vec(&ppts[2 * t], acc);
+            else st_vec(&buckets[b], acc);
+            first = false;
+            acc = XYZZ<F>::inf();
+            do { b++; boundary = start[b + 1]; } while (boundary <= pos);
+        }
+        u32 e = sorted[pos];
+        u32 g = (e & 0x7fffffffu) >> p.gshift;
+        u32 i = e & ((1u << p.gshift) - 1u);
+        if (i >= idx_off && i - idx_off < n_bases) {
+            Affine<F> P = ld_vec(&bases[(size_t)g * n_bases + (i - idx_off)]);
+            if (e >> 31) P.y = F::neg(P.y);
+            acc = ec_madd<F, AccumInlineCorner<F>::value>(acc, P);
+        }
+    }
+    bool tail_partial = end < boundary;     // bucket b continues in the next lane's slice
+    bool is_tail = false;
+    if (first && head_partial) st_vec(&ppts[2 * t], acc);          // single run that began before this slice
+    else if (tail_partial) { is_tail = true; st_vec(&buckets[b], XYZZ<F>::inf()); }   // starts here, continues: neutral
+    else st_vec(&buckets[b], acc);
+    pkeys[2 * t] = first_key;
+    pkeys[2 * t + 1] = b;
+    st_vec(&ppts[2 * t + 1], is_tail ? acc : XYZZ<F>::inf());
 }
 
 // ---- levels >= 1: segmented reduction of boundary partials ---------------------------------------------
@@ -264,25 +445,48 @@ __device__ __forceinline__ void msm_accum_level(int level, u32 t, const LevelInf
     }
 }
 
+// proof blockIdx.y; s_in / s_out: per-proof strides of the partial buffers this level reads / writes (2 T[0] or
+// msm_p1_stride)
 template <class F>
 __global__ void __launch_bounds__(64)
-k_msm_accum_lvl(int level, const u32* __restrict__ keys_in, const XYZZ<F>* __restrict__ pts_in,
+k_msm_accum_lvl(int level, const u32* __restrict__ keys_in, const XYZZ<F>* __restrict__ pts_in, size_t s_in,
                 const u32* __restrict__ start, MsmPlan p, XYZZ<F>* __restrict__ buckets,
-                u32* __restrict__ keys_out, XYZZ<F>* __restrict__ pts_out) {
+                u32* __restrict__ keys_out, XYZZ<F>* __restrict__ pts_out, size_t s_out) {
+    const size_t pr = blockIdx.y;
     u32 t = blockIdx.x * blockDim.x + threadIdx.x;
-    u32 E = start[p.NB];
+    u32 E = start[pr * (p.NB + 1) + p.NB];
     LevelInfo li = msm_level_info(p, E, level);
     if (t >= li.active) return;
-    msm_accum_level<F>(level, t, li, keys_in, pts_in, p, buckets, keys_out, pts_out);
+    msm_accum_level<F>(level, t, li, keys_in + pr * s_in, pts_in + pr * s_in, p, buckets + pr * (p.NB + 1),
+                       keys_out + pr * s_out, pts_out + pr * s_out);
 }
 
 // every level from `level0` on (each at most MSM_TAIL_THREADS lanes wide) in ONE workgroup, ping-ponging the two
-// partial buffers with a workgroup barrier between levels: replaces the last 3 launches of the level chain
+// partial buffers with a workgroup barrier between levels: replaces the last 3 launches of the level chain.  One
+// workgroup per proof (blockIdx.x).
 template <class F>
 __global__ void __launch_bounds__(MSM_TAIL_THREADS)
-k_msm_accum_tail(int level0, u32* __restrict__ keys0, XYZZ<F>* __restrict__ pts0, u32* __restrict__ keys1,
-                 XYZZ<F>* __restrict__ pts1, const u32* __restrict__ start, MsmPlan p, XYZZ<F>* __restrict__ buckets) {
-#include "kbody/msm_accum_tail.inc"
+k_msm_accum_tail(int level0, u32* __restrict__ keys0_all, XYZZ<F>* __restrict__ pts0_all, u32* __restrict__ keys1_all,
+                 XYZZ<F>* __restrict__ pts1_all, const u32* __restrict__ start_all, MsmPlan p,
+                 XYZZ<F>* __restrict__ buckets_all) {
+    const size_t pr = blockIdx.x, s0 = 2ull * p.T[0], s1 = msm_p1_stride(p);
+    u32* __restrict__ keys0 = keys0_all + pr * s0;
+    XYZZ<F>* __restrict__ pts0 = pts0_all + pr * s0;
+    u32* __restrict__ keys1 = keys1_all + pr * s1;
+    XYZZ<F>* __restrict__ pts1 = pts1_all + pr * s1;
+    const u32* __restrict__ start = start_all + pr * (p.NB + 1);
+    XYZZ<F>* __restrict__ buckets = buckets_all + pr * (p.NB + 1);
+    u32 t = threadIdx.x;
+    u32 E = start[p.NB];
+    for (int level = level0; level < (int)p.n_levels; level++) {
+        LevelInfo li = msm_level_info(p, E, level);
+        bool in0 = ((level - 1) & 1) == 0;           // level k reads buffer (k-1)&1 and writes buffer k&1
+        if (t < li.active)
+            msm_accum_level<F>(level, t, li, in0 ? keys0 : keys1, in0 ? pts0 : pts1, p, buckets, in0 ? keys1 : keys0,
+                               in0 ? pts1 : pts0);
+        __threadfence_block();
+        __syncthreads();
+    }
 }
 
 // ---- bucket reduction: lane j of window w' owns K consecutive buckets ---------------------------------
@@ -318,13 +522,76 @@ k_msm_bucket_reduce(const XYZZ<F>* __restrict__ buckets, const u32* __restrict__
 
 // WP == 1 (every table-backed MSM): bucket reduction, the sum over lanes and the final result in ONE launch.
 // Every workgroup reduces its lanes' weighted bucket sums in LDS and publishes one partial; the workgroup that
-// takes the last ticket adds the partials.  `ticket` sits right behind the buckets and is cleared by k_msm_accum0.
+// takes the last ticket adds the partials.  Proof blockIdx.y: its ticket is the u32 right behind its own buckets (cleared
+// by k_msm_accum0), its result res_all[pr * res_stride].
 constexpr int MSM_REDUCE_THREADS = 128;
 template <class F>
 __global__ void __launch_bounds__(MSM_REDUCE_THREADS)
-k_msm_reduce_fused(const XYZZ<F>* __restrict__ buckets, const u32* __restrict__ start, MsmPlan p,
-                   XYZZ<F>* __restrict__ partial, u32* __restrict__ ticket, XYZZ<F>* __restrict__ res) {
-#include "kbody/msm_reduce_fused.inc"
+k_msm_reduce_fused(XYZZ<F>* __restrict__ buckets_all, const u32* __restrict__ start_all, MsmPlan p,
+                   XYZZ<F>* __restrict__ partial_all, XYZZ<F>* __restrict__ res_all, u32 res_stride) {
+    const size_t pr = blockIdx.y;
+    const XYZZ<F>* __restrict__ buckets = buckets_all + pr * (p.NB + 1);
+    const u32* __restrict__ start = start_all + pr * (p.NB + 1);
+    XYZZ<F>* __restrict__ partial = partial_all + pr * ((size_t)p.WP * (p.B / p.K));
+    u32* __restrict__ ticket = reinterpret_cast<u32*>(buckets_all + pr * (p.NB + 1) + p.NB);
+    XYZZ<F>* __restrict__ res = res_all + pr * res_stride;
+    __shared__ XYZZ<F> sh[MSM_REDUCE_THREADS];
+    __shared__ u32 last;
+    u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    u32 J = p.B / p.K;
+    XYZZ<F> tot = XYZZ<F>::inf();
+    if (t < J) {
+        const XYZZ<F>* bk = buckets + (size_t)t * p.K;
+        const u32* st = start + (size_t)t * p.K;
+        XYZZ<F> run = XYZZ<F>::inf();
+        for (int b = (int)p.K - 1; b >= 0; b--) {
+            XYZZ<F> q = st[b] == st[b + 1] ? XYZZ<F>::inf() : ld_vec(&bk[b]);      // empty bucket: never written
+            run = ec_add_ni(run, q);
+            tot = ec_add_ni(tot, run);
+        }
+        u32 wgt = t * p.K;
+        if (wgt && !run.is_inf()) {
+            XYZZ<F> acc = XYZZ<F>::inf();
+            for (int bit = 31 - __clz(wgt); bit >= 0; bit--) {
+                acc = ec_dbl_ni(acc);
+                if ((wgt >> bit) & 1) acc = ec_add_ni(acc, run);
+            }
+            tot = ec_add_ni(tot, acc);
+        }
+    }
+    sh[threadIdx.x] = tot;
+    __syncthreads();
+    for (u32 off = MSM_REDUCE_THREADS / 2; off >= 1; off >>= 1) {
+        if (threadIdx.x < off) {
+            // operands stay in LDS (the out-of-line add takes references): two private copies of 384 B each less per
+            // lane for the 12-limb G2 flavour, i.e. a smaller scratch ring on every queue that runs this kernel
+            XYZZ<F> t = ec_add_ni(sh[threadIdx.x], sh[threadIdx.x + off]);
+            sh[threadIdx.x] = t;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        st_vec(&partial[blockIdx.x], sh[0]);
+        __threadfence();
+        last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    XYZZ<F> acc = XYZZ<F>::inf();
+    for (u32 j = threadIdx.x; j < gridDim.x; j += MSM_REDUCE_THREADS) acc = ec_add_ni(acc, ld_vec(&partial[j]));
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (u32 off = MSM_REDUCE_THREADS / 2; off >= 1; off >>= 1) {
+        if (threadIdx.x < off) {
+            // operands stay in LDS (the out-of-line add takes references): two private copies of 384 B each less per
+            // lane for the 12-limb G2 flavour, i.e. a smaller scratch ring on every queue that runs this kernel
+            XYZZ<F> t = ec_add_ni(sh[threadIdx.x], sh[threadIdx.x + off]);
+            sh[threadIdx.x] = t;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) st_vec(res, sh[0]);
 }
 
 // one workgroup per window: LDS tree over the J lane results

@@ -15,6 +15,7 @@ static inline size_t hk_private_bytes_of(const void* kernel) {
     return (size_t)fa.localSizeBytes;
 }
 
+// Every buffer below holds `batch` per-proof slices one fixed stride apart (msm.cuh); a single MSM is a batch of one.
 struct SortBufs {        // device buffers produced by the counting sort
     u32* count;          // [NB]
     u32* start;          // [NB + 1]   start[NB] = number of non-zero digits E
@@ -25,17 +26,12 @@ struct SortBufs {        // device buffers produced by the counting sort
 
 template <class Fr>
 struct MsmSort {
-    static hk_status alloc(Lane* L, const MsmPlan& p, SortBufs* out);
-    // scalars_d: n field elements on the device (canonical, or Montgomery when is_mont)
+    static hk_status alloc(Lane* L, const MsmPlan& p, SortBufs* out, u32 batch = 1);
+    // scalars_d: n field elements on the device (canonical, or Montgomery when is_mont); proof b's start scalar_stride
+    // elements after proof b - 1's.
     // count_is_zero: the caller cleared sb.count in a kernel of its own that precedes this call in stream order
     static hk_status run(hipStream_t s, const MsmPlan& p, const u32* scalars_d, int is_mont,
-                         const SortBufs& sb, bool count_is_zero = false);
-    // `batch` independent sorts in lock-step (hk_prove_batch): every buffer of `sb` holds `batch` per-proof slices one
-    // fixed stride apart (msm.cuh msm_sorted_stride / msm_digits_stride); proof b's scalars start scalar_stride
-    // elements after proof a's.  sb.count must be zero (every proof's NB counters).
-    static hk_status alloc_b(Lane* L, const MsmPlan& p, u32 batch, SortBufs* out);
-    static hk_status run_b(hipStream_t s, const MsmPlan& p, const u32* scalars_d, size_t scalar_stride, int is_mont,
-                           u32 batch, const SortBufs& sb);
+                         const SortBufs& sb, bool count_is_zero = false, u32 batch = 1, size_t scalar_stride = 0);
 };
 
 template <class F>
@@ -47,19 +43,14 @@ struct MsmRun {
         XYZZ<F>* red;            // [WP * B / K]
         XYZZ<F>* wsum;           // [WP]
     };
-    static hk_status alloc(Lane* L, const MsmPlan& p, Bufs* out);
-    // table: F shift groups of n_bases affine points each.  result_d receives one XYZZ point.
-    // ev0/ev1 (optional) bracket the bucket-accumulate launches for hk_timings.
+    static hk_status alloc(Lane* L, const MsmPlan& p, Bufs* out, u32 batch = 1);
+    // table: F shift groups of n_bases affine points each.  result_d receives one XYZZ point per proof, proof b's at
+    // result_d[b * res_stride].  `batch` MSMs over the same table run in lock-step, one launch per stage; the chip's
+    // resident lanes are split across them (msm_lane_plan).  ev0/ev1 (optional) bracket the bucket-accumulate launch for
+    // hk_timings.
     static hk_status run(hipStream_t s, const MsmPlan& p, const Affine<F>* table, u32 n_bases, u32 idx_off,
                          const SortBufs& sb, const Bufs& b, XYZZ<F>* result_d,
-                         hipEvent_t ev0, hipEvent_t ev1);
-    // `batch` MSMs over the same table in lock-step (hk_prove_batch): one launch per stage with grid.y (or grid.x for the
-    // one-workgroup stages) = proof, the sorts of MsmSort::run_b, buffers of alloc_b, result of proof b at
-    // result_d[b * res_stride].  The chip's resident lanes are split across the batch (msm_lane_plan_b).
-    static hk_status alloc_b(Lane* L, const MsmPlan& p, u32 batch, Bufs* out);
-    static hk_status run_b(hipStream_t s, const MsmPlan& p, const Affine<F>* table, u32 n_bases, u32 idx_off, u32 batch,
-                           const SortBufs& sb, const Bufs& b, XYZZ<F>* result_d, u32 res_stride,
-                           hipEvent_t ev0, hipEvent_t ev1);
+                         hipEvent_t ev0, hipEvent_t ev1, u32 batch = 1, u32 res_stride = 1);
     static hk_status build_tables(hipStream_t s, Affine<F>* table, u32 n, u32 groups, u32 shift_bits);
     static hk_status to_affine(hipStream_t s, const XYZZ<F>* in, Affine<F>* out, u32 n);
     // fixed-base batch scalar multiplication (fixed_base.cuh); all pointers device.

@@ -4,7 +4,6 @@
 #include "msm_driver.cuh"
 #include "fixed_base.cuh"
 #include "endo.cuh"
-#include "msm_batch.cuh"
 
 namespace hk {
 
@@ -20,37 +19,7 @@ static inline bool hk_dbg_sync() { static const bool on = getenv("HK_DEBUG_SYNC"
     } while (0)
 
 template <class Fr>
-hk_status MsmSort<Fr>::alloc(Lane* L, const MsmPlan& p, SortBufs* out) {
-    out->count = L->alloc_n<u32>(p.NB);
-    out->start = L->alloc_n<u32>(p.NB + 1);
-    out->cursor = L->alloc_n<u32>(p.NB);
-    out->sorted = L->alloc_n<u32>((size_t)p.n * p.W + 1);
-    out->digits = L->alloc_n<short>((size_t)p.n * p.W + 8);
-    if (!out->count || !out->start || !out->cursor || !out->sorted || !out->digits) return HK_ERR_NOMEM;
-    return HK_OK;
-}
-
-template <class Fr>
-hk_status MsmSort<Fr>::run(hipStream_t s, const MsmPlan& p, const u32* scalars_d, int is_mont,
-                           const SortBufs& sb, bool count_is_zero) {
-    if (p.NB > (u32)MSM_LDS_COUNTERS || p.c > 16) return HK_ERR_ARG;       // digits are stored as int16
-    if (!count_is_zero) HK_HIP(hipMemsetAsync(sb.count, 0, sizeof(u32) * p.NB, s));
-    u32 blocks = (p.n + p.chunk - 1) / p.chunk;
-    if (blocks == 0) blocks = 1;
-    hipLaunchKernelGGL((k_msm_hist<Fr>), dim3(blocks), dim3(MSM_SORT_THREADS), 0, s,
-                       scalars_d, is_mont, p, sb.count, sb.digits);
-    HK_DBG(s, "k_msm_hist");
-    hipLaunchKernelGGL((k_msm_scan<0>), dim3(1), dim3(1024), 0, s, sb.count, sb.start, sb.cursor, p.NB);
-    HK_DBG(s, "k_msm_scan");
-    hipLaunchKernelGGL((k_msm_scatter<Fr>), dim3(blocks), dim3(MSM_SORT_THREADS), 0, s,
-                       (const short*)sb.digits, p, sb.cursor, sb.sorted);
-    HK_DBG(s, "k_msm_scatter");
-    HK_HIP(hipGetLastError());
-    return HK_OK;
-}
-
-template <class Fr>
-hk_status MsmSort<Fr>::alloc_b(Lane* L, const MsmPlan& p, u32 batch, SortBufs* out) {
+hk_status MsmSort<Fr>::alloc(Lane* L, const MsmPlan& p, SortBufs* out, u32 batch) {
     out->count = L->alloc_n<u32>((size_t)p.NB * batch);
     out->start = L->alloc_n<u32>((size_t)(p.NB + 1) * batch);
     out->cursor = L->alloc_n<u32>((size_t)p.NB * batch);
@@ -61,37 +30,31 @@ hk_status MsmSort<Fr>::alloc_b(Lane* L, const MsmPlan& p, u32 batch, SortBufs* o
 }
 
 template <class Fr>
-hk_status MsmSort<Fr>::run_b(hipStream_t s, const MsmPlan& p, const u32* scalars_d, size_t scalar_stride, int is_mont,
-                             u32 batch, const SortBufs& sb) {
-    if (p.NB > (u32)MSM_LDS_COUNTERS || p.c > 16 || batch == 0 || batch > 65535u) return HK_ERR_ARG;
+hk_status MsmSort<Fr>::run(hipStream_t s, const MsmPlan& p, const u32* scalars_d, int is_mont,
+                           const SortBufs& sb, bool count_is_zero, u32 batch, size_t scalar_stride) {
+    if (p.NB > (u32)MSM_LDS_COUNTERS || p.c > 16) return HK_ERR_ARG;       // digits are stored as int16
+    if (batch == 0 || batch > 65535u) return HK_ERR_ARG;
+    if (!count_is_zero) HK_HIP(hipMemsetAsync(sb.count, 0, sizeof(u32) * p.NB * batch, s));
     u32 blocks = (p.n + p.chunk - 1) / p.chunk;
     if (blocks == 0) blocks = 1;
     const size_t words = scalar_stride * (sizeof(Fr) / sizeof(u32));
-    hipLaunchKernelGGL((k_msm_hist_b<Fr>), dim3(blocks, batch), dim3(MSM_SORT_THREADS), 0, s,
+    hipLaunchKernelGGL((k_msm_hist<Fr>), dim3(blocks, batch), dim3(MSM_SORT_THREADS), 0, s,
                        scalars_d, words, is_mont, p, sb.count, sb.digits);
-    HK_DBG(s, "k_msm_hist_b");
-    hipLaunchKernelGGL((k_msm_scan_b<0>), dim3(batch), dim3(1024), 0, s, sb.count, sb.start, sb.cursor, p.NB);
-    HK_DBG(s, "k_msm_scan_b");
-    hipLaunchKernelGGL((k_msm_scatter_b<Fr>), dim3(blocks, batch), dim3(MSM_SORT_THREADS), 0, s,
+    HK_DBG(s, "k_msm_hist");
+    hipLaunchKernelGGL((k_msm_scan<0>), dim3(batch), dim3(1024), 0, s, sb.count, sb.start, sb.cursor, p.NB);
+    HK_DBG(s, "k_msm_scan");
+    hipLaunchKernelGGL((k_msm_scatter<Fr>), dim3(blocks, batch), dim3(MSM_SORT_THREADS), 0, s,
                        (const short*)sb.digits, p, sb.cursor, sb.sorted);
-    HK_DBG(s, "k_msm_scatter_b");
+    HK_DBG(s, "k_msm_scatter");
     HK_HIP(hipGetLastError());
     return HK_OK;
 }
 
 // accumulate schedule for this coordinate field: as many lanes as the kernel keeps resident
-// (AccumOcc<F>::waves per SIMD x 1024 SIMDs x 64), so the sorted list is consumed in ONE balanced round
+// (AccumOcc<F>::waves per SIMD x 1024 SIMDs x 64), so the sorted list is consumed in ONE balanced round; a batch of
+// proofs side by side splits those lanes (they are not multiplied by the batch)
 template <class F>
-static inline MsmPlan msm_lane_plan(const MsmPlan& p0) {
-    MsmPlan p = p0;
-    msm_set_lanes(p, (u32)AccumOcc<F>::waves * 65536u);
-    return p;
-}
-
-// the same for `batch` proofs side by side: the resident lanes split across them (not multiplied by the batch), so one
-// batched launch is one balanced round over the chip
-template <class F>
-static inline MsmPlan msm_lane_plan_b(const MsmPlan& p0, u32 batch) {
+static inline MsmPlan msm_lane_plan(const MsmPlan& p0, u32 batch = 1) {
     MsmPlan p = p0;
     u32 lanes = (u32)AccumOcc<F>::waves * 65536u / (batch ? batch : 1u);
     msm_set_lanes(p, lanes ? lanes : 1u);
@@ -99,10 +62,10 @@ static inline MsmPlan msm_lane_plan_b(const MsmPlan& p0, u32 batch) {
 }
 
 template <class F>
-hk_status MsmRun<F>::alloc_b(Lane* L, const MsmPlan& p0, u32 batch, Bufs* out) {
-    const MsmPlan p = msm_lane_plan_b<F>(p0, batch);
+hk_status MsmRun<F>::alloc(Lane* L, const MsmPlan& p0, Bufs* out, u32 batch) {
+    const MsmPlan p = msm_lane_plan<F>(p0, batch);
     const size_t n0 = 2ull * p.T[0], n1 = msm_p1_stride(p);
-    out->buckets = L->alloc_n<XYZZ<F>>((size_t)(p.NB + 1) * batch);
+    out->buckets = L->alloc_n<XYZZ<F>>((size_t)(p.NB + 1) * batch);     // + one slot: the reduction ticket
     out->pkeys[0] = L->alloc_n<u32>(n0 * batch);
     out->ppts[0] = L->alloc_n<XYZZ<F>>(n0 * batch);
     out->pkeys[1] = L->alloc_n<u32>(n1 * batch);
@@ -115,39 +78,43 @@ hk_status MsmRun<F>::alloc_b(Lane* L, const MsmPlan& p0, u32 batch, Bufs* out) {
 }
 
 template <class F>
-hk_status MsmRun<F>::run_b(hipStream_t s, const MsmPlan& p0, const Affine<F>* table, u32 n_bases, u32 idx_off, u32 batch,
-                           const SortBufs& sb, const Bufs& b, XYZZ<F>* result_d, u32 res_stride,
-                           hipEvent_t ev0, hipEvent_t ev1) {
+hk_status MsmRun<F>::run(hipStream_t s, const MsmPlan& p0, const Affine<F>* table, u32 n_bases, u32 idx_off,
+                         const SortBufs& sb, const Bufs& b, XYZZ<F>* result_d,
+                         hipEvent_t ev0, hipEvent_t ev1, u32 batch, u32 res_stride) {
     if (batch == 0 || batch > 65535u) return HK_ERR_ARG;
-    const MsmPlan p = msm_lane_plan_b<F>(p0, batch);
+    const MsmPlan p = msm_lane_plan<F>(p0, batch);
     const size_t n0 = 2ull * p.T[0], n1 = msm_p1_stride(p);
+    // no memset of the buckets (4 - 8 MB per MSM): k_msm_accum0 writes every bucket that has entries and clears the
+    // ticket, the reductions skip the empty ones
+    // with profiling on, ev0/ev1 take the kernel's own start/stop timestamps (hipExtLaunchKernelGGL), so
+    // the figure agrees with rocprofv3's kernel trace even when other lanes share the hardware queues
     dim3 g0((p.T[0] + 63) / 64, batch);
     if (ev0 && ev1)
-        hipExtLaunchKernelGGL((k_msm_accum0_b<F>), g0, dim3(64), 0, s, ev0, ev1, 0,
+        hipExtLaunchKernelGGL((k_msm_accum0<F>), g0, dim3(64), 0, s, ev0, ev1, 0,
                               table, n_bases, idx_off, sb.sorted, sb.start, p, b.buckets, b.pkeys[0], b.ppts[0]);
     else
-        hipLaunchKernelGGL((k_msm_accum0_b<F>), g0, dim3(64), 0, s,
+        hipLaunchKernelGGL((k_msm_accum0<F>), g0, dim3(64), 0, s,
                            table, n_bases, idx_off, sb.sorted, sb.start, p, b.buckets, b.pkeys[0], b.ppts[0]);
-    HK_DBG(s, "k_msm_accum0_b");
+    HK_DBG(s, "k_msm_accum0");
     u32 k = 1;
     for (; k < p.n_levels && p.T[k] > (u32)MSM_TAIL_THREADS; k++) {
         int in = (k - 1) & 1, out = k & 1;
-        hipLaunchKernelGGL((k_msm_accum_lvl_b<F>), dim3((p.T[k] + 63) / 64, batch), dim3(64), 0, s,
+        hipLaunchKernelGGL((k_msm_accum_lvl<F>), dim3((p.T[k] + 63) / 64, batch), dim3(64), 0, s,
                            (int)k, b.pkeys[in], b.ppts[in], in ? n1 : n0, sb.start, p, b.buckets, b.pkeys[out], b.ppts[out],
                            out ? n1 : n0);
-        HK_DBG(s, "k_msm_accum_lvl_b");
+        HK_DBG(s, "k_msm_accum_lvl");
     }
-    if (k < p.n_levels) {
-        hipLaunchKernelGGL((k_msm_accum_tail_b<F>), dim3(batch), dim3(MSM_TAIL_THREADS), 0, s, (int)k, b.pkeys[0], b.ppts[0],
+    if (k < p.n_levels) {                                   // the remaining levels fit one workgroup each: one launch
+        hipLaunchKernelGGL((k_msm_accum_tail<F>), dim3(batch), dim3(MSM_TAIL_THREADS), 0, s, (int)k, b.pkeys[0], b.ppts[0],
                            b.pkeys[1], b.ppts[1], sb.start, p, b.buckets);
-        HK_DBG(s, "k_msm_accum_tail_b");
+        HK_DBG(s, "k_msm_accum_tail");
     }
     u32 J = p.B / p.K;
     if (p.WP == 1) {
         u32 blocks = (J + MSM_REDUCE_THREADS - 1) / MSM_REDUCE_THREADS;
-        hipLaunchKernelGGL((k_msm_reduce_fused_b<F>), dim3(blocks, batch), dim3(MSM_REDUCE_THREADS), 0, s, b.buckets, sb.start, p,
+        hipLaunchKernelGGL((k_msm_reduce_fused<F>), dim3(blocks, batch), dim3(MSM_REDUCE_THREADS), 0, s, b.buckets, sb.start, p,
                            b.red, result_d, res_stride);
-        HK_DBG(s, "k_msm_reduce_fused_b");
+        HK_DBG(s, "k_msm_reduce_fused");
     } else {
         // several windows per group (the HK_MSM_WP experiment only): the three-launch reduction of each proof's slices
         const size_t rs = (size_t)p.WP * J;
@@ -155,78 +122,14 @@ hk_status MsmRun<F>::run_b(hipStream_t s, const MsmPlan& p0, const Affine<F>* ta
             const XYZZ<F>* bk = b.buckets + (size_t)pr * (p.NB + 1);
             const u32* st = sb.start + (size_t)pr * (p.NB + 1);
             hipLaunchKernelGGL((k_msm_bucket_reduce<F>), dim3((p.WP * J + 63) / 64), dim3(64), 0, s, bk, st, p, b.red + pr * rs);
+            HK_DBG(s, "k_msm_bucket_reduce");
             hipLaunchKernelGGL((k_msm_window_sum<F>), dim3(p.WP), dim3(MSM_WSUM_THREADS), 0, s, b.red + pr * rs, p,
                                b.wsum + (size_t)pr * p.WP);
+            HK_DBG(s, "k_msm_window_sum");
             hipLaunchKernelGGL((k_msm_final<F>), dim3(1), dim3(64), 0, s, b.wsum + (size_t)pr * p.WP, p,
                                result_d + (size_t)pr * res_stride);
+            HK_DBG(s, "k_msm_final");
         }
-        HK_DBG(s, "k_msm_final");
-    }
-    HK_HIP(hipGetLastError());
-    return HK_OK;
-}
-
-template <class F>
-hk_status MsmRun<F>::alloc(Lane* L, const MsmPlan& p0, Bufs* out) {
-    const MsmPlan p = msm_lane_plan<F>(p0);
-    out->buckets = L->alloc_n<XYZZ<F>>(p.NB + 1);          // + one slot: the reduction ticket, zeroed with the buckets
-    size_t n0 = 2ull * p.T[0];
-    size_t n1 = p.n_levels > 1 ? 2ull * p.T[1] : 2;
-    out->pkeys[0] = L->alloc_n<u32>(n0);
-    out->ppts[0] = L->alloc_n<XYZZ<F>>(n0);
-    out->pkeys[1] = L->alloc_n<u32>(n1);
-    out->ppts[1] = L->alloc_n<XYZZ<F>>(n1);
-    out->red = L->alloc_n<XYZZ<F>>((size_t)p.WP * (p.B / p.K));
-    out->wsum = L->alloc_n<XYZZ<F>>(p.WP);
-    if (!out->buckets || !out->pkeys[0] || !out->ppts[0] || !out->pkeys[1] || !out->ppts[1] ||
-        !out->red || !out->wsum)
-        return HK_ERR_NOMEM;
-    return HK_OK;
-}
-
-template <class F>
-hk_status MsmRun<F>::run(hipStream_t s, const MsmPlan& p0, const Affine<F>* table, u32 n_bases, u32 idx_off,
-                         const SortBufs& sb, const Bufs& b, XYZZ<F>* result_d,
-                         hipEvent_t ev0, hipEvent_t ev1) {
-    const MsmPlan p = msm_lane_plan<F>(p0);
-    // no memset of the buckets (4 - 8 MB per MSM): k_msm_accum0 writes every bucket that has entries and clears the
-    // ticket, the reductions skip the empty ones
-    u32* ticket = reinterpret_cast<u32*>(b.buckets + p.NB);
-    // with profiling on, ev0/ev1 take the kernel's own start/stop timestamps (hipExtLaunchKernelGGL), so
-    // the figure agrees with rocprofv3's kernel trace even when other lanes share the hardware queues
-    if (ev0 && ev1)
-        hipExtLaunchKernelGGL((k_msm_accum0<F>), dim3((p.T[0] + 63) / 64), dim3(64), 0, s, ev0, ev1, 0,
-                              table, n_bases, idx_off, sb.sorted, sb.start, p, b.buckets, b.pkeys[0], b.ppts[0]);
-    else
-        hipLaunchKernelGGL((k_msm_accum0<F>), dim3((p.T[0] + 63) / 64), dim3(64), 0, s,
-                           table, n_bases, idx_off, sb.sorted, sb.start, p, b.buckets, b.pkeys[0], b.ppts[0]);
-    HK_DBG(s, "k_msm_accum0");
-    u32 k = 1;
-    for (; k < p.n_levels && p.T[k] > (u32)MSM_TAIL_THREADS; k++) {
-        int in = (k - 1) & 1, out = k & 1;
-        hipLaunchKernelGGL((k_msm_accum_lvl<F>), dim3((p.T[k] + 63) / 64), dim3(64), 0, s,
-                           (int)k, b.pkeys[in], b.ppts[in], sb.start, p, b.buckets, b.pkeys[out], b.ppts[out]);
-        HK_DBG(s, "k_msm_accum_lvl");
-    }
-    if (k < p.n_levels) {                                   // the remaining levels fit one workgroup each: one launch
-        hipLaunchKernelGGL((k_msm_accum_tail<F>), dim3(1), dim3(MSM_TAIL_THREADS), 0, s, (int)k, b.pkeys[0], b.ppts[0],
-                           b.pkeys[1], b.ppts[1], sb.start, p, b.buckets);
-        HK_DBG(s, "k_msm_accum_tail");
-    }
-    u32 J = p.B / p.K;
-    if (p.WP == 1) {
-        u32 blocks = (J + MSM_REDUCE_THREADS - 1) / MSM_REDUCE_THREADS;
-        hipLaunchKernelGGL((k_msm_reduce_fused<F>), dim3(blocks), dim3(MSM_REDUCE_THREADS), 0, s, b.buckets, sb.start, p, b.red,
-                           ticket, result_d);
-        HK_DBG(s, "k_msm_reduce_fused");
-    } else {
-        hipLaunchKernelGGL((k_msm_bucket_reduce<F>), dim3((p.WP * J + 63) / 64), dim3(64), 0, s,
-                           b.buckets, sb.start, p, b.red);
-        HK_DBG(s, "k_msm_bucket_reduce");
-        hipLaunchKernelGGL((k_msm_window_sum<F>), dim3(p.WP), dim3(MSM_WSUM_THREADS), 0, s, b.red, p, b.wsum);
-        HK_DBG(s, "k_msm_window_sum");
-        hipLaunchKernelGGL((k_msm_final<F>), dim3(1), dim3(64), 0, s, b.wsum, p, result_d);
-        HK_DBG(s, "k_msm_final");
     }
     HK_HIP(hipGetLastError());
     return HK_OK;
@@ -237,8 +140,7 @@ template <class F>
 size_t MsmRun<F>::max_private_bytes() {
     typedef typename ScalarOf<F>::type Fr;
     const void* ks[] = {(const void*)k_msm_accum0<F>, (const void*)k_msm_accum_lvl<F>, (const void*)k_msm_accum_tail<F>,
-                        (const void*)k_msm_reduce_fused<F>, (const void*)k_msm_accum0_b<F>, (const void*)k_msm_accum_lvl_b<F>,
-                        (const void*)k_msm_accum_tail_b<F>, (const void*)k_msm_reduce_fused_b<F>, (const void*)k_msm_bucket_reduce<F>,
+                        (const void*)k_msm_reduce_fused<F>, (const void*)k_msm_bucket_reduce<F>,
                         (const void*)k_msm_window_sum<F>, (const void*)k_msm_final<F>, (const void*)k_to_affine<F>,
                         (const void*)k_msm_build_tables<F>, (const void*)k_batch_affine<F>, (const void*)k_fb_table<F>,
                         (const void*)k_fb_mul<Fr, F>, (const void*)k_scalar_mul_each<Fr, F>, (const void*)k_scalar_mul_endo<Fr, F>, (const void*)k_points_fold_endo<Fr, F>, (const void*)k_points_mul_split<Fr, F, true>, (const void*)k_points_mul_split<Fr, F, false>, (const void*)k_points_sum<F>, (const void*)k_points_sum_seg<F>,

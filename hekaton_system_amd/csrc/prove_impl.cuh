@@ -17,7 +17,6 @@
 #include "fixed_base.cuh"
 #include "witness.cuh"
 #include "endo.cuh"
-#include "msm_batch.cuh"
 
 namespace hk {
 
@@ -435,14 +434,15 @@ __global__ void k_mark_noninf(const Affine<F>* __restrict__ pts, u32* __restrict
     u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) flags[i] = ld_vec(&pts[i]).is_inf() ? 0u : 1u;
 }
-// dst[k] = src[idx[k]] for idx[k] < n_src (ext slots beyond the source stay as they are)
+// dst[k] = src[idx[k]] for idx[k] < n_src (ext slots beyond the source stay as they are), for the row of grid.y: dst rows
+// n apart, src rows n_src apart, one index list
 template <class T>
-__global__ void k_gather(T* __restrict__ dst, const T* __restrict__ src, const u32* __restrict__ idx, u32 n,
-                         u32 n_src) {
+__global__ void k_gather(T* __restrict__ dst, const T* __restrict__ src, const u32* __restrict__ idx, u32 n, u32 n_src) {
     u32 k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
+    const size_t pr = blockIdx.y;
     u32 i = idx[k];
-    if (i < n_src) st_vec(&dst[k], ld_vec(&src[i]));
+    if (i < n_src) st_vec(&dst[pr * n + k], ld_vec(&src[pr * n_src + i]));
 }
 
 // error exits of pk_upload: release everything allocated so far (fail()) and tell out-of-memory from other faults
@@ -1402,30 +1402,15 @@ void Ops<C>::ctx_release(hk_ctx* ctx) {
 }
 
 // ---- small device helpers for the fused calls -------------------------------------------------------------
-// ext[0] = r, ext[1] = s, ext[2] = r*s, ext[3+i] = kappa_i   (all Montgomery)
-// Also clears the bucket counters of the proof's digit sorts (up to three arrays of `nb` u32 each; every workgroup takes a
-// share): they are accumulated with atomics by k_msm_hist, and this kernel precedes every sort of the proof in stream
-// order (the side streams wait for the event recorded behind it) - three memset launches less per proof.
+// ext[0] = r, ext[1] = s, ext[2] = r*s, ext[3+i] = kappa_i   (all Montgomery), for each of `batch` proofs: row b of ext
+// starts ext_stride elements after row b - 1, row b of rs_kappas (r, s, kappas) rs_stride after.
+// Also clears the bucket counters of the proofs' digit sorts (up to three arrays of `nb` u32 each, every proof's counters;
+// every workgroup takes a share): they are accumulated with atomics by k_msm_hist, and this kernel precedes every sort of
+// the proofs in stream order (the side streams wait for the event recorded behind it) - three memset launches less.
 template <class Fr>
-__global__ void k_prep_ext(Fr* __restrict__ ext, const Fr* __restrict__ rs_kappas, u32 n_kappas, u32* __restrict__ c0,
-                           u32* __restrict__ c1, u32* __restrict__ c2, u32 nb0, u32 nb1, u32 nb2) {
-    u32 gt = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
-    for (u32 i = gt; i < nb0; i += stride) c0[i] = 0;
-    for (u32 i = gt; i < nb1; i += stride) c1[i] = 0;
-    for (u32 i = gt; i < nb2; i += stride) c2[i] = 0;
-    if (blockIdx.x || threadIdx.x) return;
-    Fr r = fr_load(&rs_kappas[0]), s = fr_load(&rs_kappas[1]);
-    fr_store(&ext[0], r);
-    fr_store(&ext[1], s);
-    fr_store(&ext[2], Fr::mul(r, s));
-    for (u32 i = 0; i < n_kappas; i++) fr_store(&ext[3 + i], fr_load(&rs_kappas[2 + i]));
-}
-// the same for `batch` proofs (hk_prove_batch): row b of ext starts ext_stride elements after row b - 1, row b of
-// rs_kappas (r, s, kappas) rs_stride after; nb0..nb2 count every proof's counters (batch x NB)
-template <class Fr>
-__global__ void k_prep_ext_b(Fr* __restrict__ ext, u32 ext_stride, const Fr* __restrict__ rs_kappas, u32 rs_stride,
-                             u32 n_kappas, u32 batch, u32* __restrict__ c0, u32* __restrict__ c1, u32* __restrict__ c2,
-                             u32 nb0, u32 nb1, u32 nb2) {
+__global__ void k_prep_ext(Fr* __restrict__ ext, u32 ext_stride, const Fr* __restrict__ rs_kappas, u32 rs_stride,
+                           u32 n_kappas, u32 batch, u32* __restrict__ c0, u32* __restrict__ c1, u32* __restrict__ c2,
+                           u32 nb0, u32 nb1, u32 nb2) {
     u32 gt = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
     for (u32 i = gt; i < nb0; i += stride) c0[i] = 0;
     for (u32 i = gt; i < nb1; i += stride) c1[i] = 0;
@@ -1440,35 +1425,16 @@ __global__ void k_prep_ext_b(Fr* __restrict__ ext, u32 ext_stride, const Fr* __r
     for (u32 i = 0; i < n_kappas; i++) fr_store(&e[3 + i], fr_load(&rk[2 + i]));
 }
 
-// k_gather over `batch` rows (grid.y = proof): dst rows n apart, src rows n_src apart, one index list
-template <class T>
-__global__ void k_gather_b(T* __restrict__ dst, const T* __restrict__ src, const u32* __restrict__ idx, u32 n, u32 n_src) {
-    u32 k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const size_t pr = blockIdx.y;
-    u32 i = idx[k];
-    if (i < n_src) st_vec(&dst[pr * n + k], ld_vec(&src[pr * n_src + i]));
-}
-
 // Finish: A = MA + a_g[0] + alpha_g ; B = MB2 + b_h[0] + beta_h ; B1 = MB1 + b_g[0] + beta_g ;
 //         C = s*A + r*B1 + ML' + MH   with ML' = L - rs*delta_g - sum kappa_i*delta_i   (see file header)
 // (prover.rs:135-155 "Finish C" + into_affine, committer.rs:112-114).  One lane per output point.
+// Grid (3, batch), proof = blockIdx.y: res_g1 holds 4 points per proof (MA, MB1, ML, MH), res_g2 1 (MB2), rs rs_stride Fr
+// per proof (r, s, kappas); one output point per proof in each of out_a / out_b / out_c.
 template <class Fr, class Fq, class Fq2>
-__global__ void k_finish(const XYZZ<Fq>* __restrict__ res_g1,   // MA, MB1, ML, MH
-                         const XYZZ<Fq2>* __restrict__ res_g2,  // MB2
-                         const Affine<Fq>* __restrict__ c1, const Affine<Fq2>* __restrict__ c2,
-                         const Fr* __restrict__ rs,              // r, s (Montgomery)
-                         Affine<Fq>* __restrict__ out_a, Affine<Fq2>* __restrict__ out_b,
-                         Affine<Fq>* __restrict__ out_c, EndoSplit<2> E) {
-#include "kbody/finish.inc"
-}
-// hk_prove_batch: grid (3, batch), proof = blockIdx.y.  res_g1: 4 points per proof (MA, MB1, ML, MH), res_g2: 1,
-// rs: rs_stride Fr per proof (r, s, kappas); one output point per proof in each of out_a / out_b / out_c.
-template <class Fr, class Fq, class Fq2>
-__global__ void k_finish_b(const XYZZ<Fq>* __restrict__ res_g1_all, const XYZZ<Fq2>* __restrict__ res_g2_all,
-                           const Affine<Fq>* __restrict__ c1, const Affine<Fq2>* __restrict__ c2, const Fr* __restrict__ rs_all,
-                           u32 rs_stride, Affine<Fq>* __restrict__ out_a_all, Affine<Fq2>* __restrict__ out_b_all,
-                           Affine<Fq>* __restrict__ out_c_all, EndoSplit<2> E) {
+__global__ void k_finish(const XYZZ<Fq>* __restrict__ res_g1_all, const XYZZ<Fq2>* __restrict__ res_g2_all,
+                         const Affine<Fq>* __restrict__ c1, const Affine<Fq2>* __restrict__ c2, const Fr* __restrict__ rs_all,
+                         u32 rs_stride, Affine<Fq>* __restrict__ out_a_all, Affine<Fq2>* __restrict__ out_b_all,
+                         Affine<Fq>* __restrict__ out_c_all, EndoSplit<2> E) {
     const size_t pr = blockIdx.y;
     const XYZZ<Fq>* __restrict__ res_g1 = res_g1_all + 4 * pr;
     const XYZZ<Fq2>* __restrict__ res_g2 = res_g2_all + pr;
@@ -1476,14 +1442,83 @@ __global__ void k_finish_b(const XYZZ<Fq>* __restrict__ res_g1_all, const XYZZ<F
     Affine<Fq>* __restrict__ out_a = out_a_all + pr;
     Affine<Fq2>* __restrict__ out_b = out_b_all + pr;
     Affine<Fq>* __restrict__ out_c = out_c_all + pr;
-#include "kbody/finish.inc"
+    if (blockIdx.x < 2 && threadIdx.x) return;
+    if (blockIdx.x == 0) {
+        XYZZ<Fq> A = ec_madd_ni(ec_madd_ni(ld_vec(&res_g1[0]), ld_vec(&c1[0])), ld_vec(&c1[1]));
+        st_vec(out_a, ec_to_affine(A));
+    } else if (blockIdx.x == 1) {
+        XYZZ<Fq2> B = ec_madd_ni(ec_madd_ni(ld_vec(&res_g2[0]), ld_vec(&c2[0])), ld_vec(&c2[1]));
+        st_vec(out_b, ec_to_affine(B));
+    } else {
+        // C = s*A + r*B1 + ML' + MH.  This kernel is the tail of every proof's latency, and its two variable-base products
+        // were one lane's chain of 256 doublings + <= 128 additions (Straus over a joint table: 3 ms).  They now run as
+        // the short element-wise sweeps do (endo.cuh): A and B1 are normalised by lanes 0 and 1, then FOUR lanes take one
+        // GLV half each (s = s0 + s1 lambda on A, r = r0 + r1 lambda on B1: <= 131 bits) with a signed 4-bit window over
+        // 1P .. 8P and a Jacobian chain - 34 digits x (4 doublings + 1 add) - and lane 0 joins the four partial products.
+        __shared__ Affine<Fq> base[2];
+        __shared__ Jac<Fq> tab[4][SPLIT_TABLE];
+        __shared__ Jac<Fq> part[4];
+        const u32 t = threadIdx.x;
+        if (t < 2) {
+            XYZZ<Fq> X = ec_madd_ni(ec_madd_ni(ld_vec(&res_g1[t]), ld_vec(&c1[2 * t])), ld_vec(&c1[2 * t + 1]));   // A | B1
+            base[t] = ec_to_affine(X);
+        }
+        __syncthreads();
+        if (t < 4) {
+            constexpr int ND = SplitDigits<Fq>::ND;
+            Fr k = Fr::from_mont(fr_load(&rs[(t >> 1) == 0 ? 1 : 0]));          // lanes 0, 1: s (on A);  lanes 2, 3: r (on B1)
+            u32 c[8], mag[2][6];
+            HK_UNROLL for (int l = 0; l < 8; l++) c[l] = l < Fr::N ? k.v[l] : 0u;
+            u32 neg = endo_decompose<2>(c, E, mag);
+            u32 m[6];
+            HK_UNROLL for (int l = 0; l < 6; l++) m[l] = (t & 1u) ? mag[1][l] : mag[0][l];
+            split_bias<ND>(m);
+            Affine<Fq> q = base[t >> 1];
+            Jac<Fq> acc = Jac<Fq>::inf();
+            const bool q_inf = q.is_inf();
+            if (!q_inf) {
+                if (t & 1u) q = EndoOf<Fq>::apply(q);
+                if ((neg >> (t & 1u)) & 1u) q.y = Fq::neg(q.y);
+                Jac<Fq> e = Jac<Fq>::from_affine(q);
+                tab[t][0] = e;
+                HK_NOUNROLL for (int i = 2; i <= SPLIT_TABLE; i++) {
+                    Jac<Fq> prev = (i & 1) ? tab[t][i - 2] : tab[t][i / 2 - 1];
+                    e = (i & 1) ? jac_madd_ni(prev, q) : jac_dbl_ni(prev);
+                    tab[t][i - 1] = e;
+                }
+                HK_NOUNROLL for (int d = ND - 1; d >= 0; d--) {
+                    int dig = split_digit(m, d);
+                    if (dig == 0 && acc.is_inf()) continue;
+                    HK_NOUNROLL for (int r4 = 0; r4 < 4; r4++) acc = jac_dbl_ni(acc);
+                    if (dig != 0) {
+                        Jac<Fq> e2 = tab[t][(dig < 0 ? -dig : dig) - 1];
+                        if (dig < 0) e2.y = Fq::neg(e2.y);
+                        acc = jac_add_ni(acc, e2);
+                    }
+                }
+            }
+            part[t] = acc;
+        }
+        __syncthreads();
+        if (t == 0) {
+            Jac<Fq> sum = part[0];
+            HK_NOUNROLL for (int i = 1; i < 4; i++) sum = jac_add_ni(sum, part[i]);
+            XYZZ<Fq> Cc = XYZZ<Fq>::inf();
+            if (!sum.is_inf()) {
+                Cc.x = sum.x; Cc.y = sum.y;
+                Cc.zz = Fq::sqr(sum.z);
+                Cc.zzz = Fq::mul(Cc.zz, sum.z);
+            }
+            Cc = ec_add_ni(Cc, ld_vec(&res_g1[2]));
+            Cc = ec_add_ni(Cc, ld_vec(&res_g1[3]));
+            st_vec(out_c, ec_to_affine(Cc));
+        }
+    }
 }
 
 template <class C>
 size_t Ops<C>::finish_private_bytes() {
-    size_t a = hk_private_bytes_of((const void*)k_finish<Fr, Fq, Fq2>);
-    size_t b = hk_private_bytes_of((const void*)k_finish_b<Fr, Fq, Fq2>);
-    return a > b ? a : b;
+    return hk_private_bytes_of((const void*)k_finish<Fr, Fq, Fq2>);
 }
 
 static inline float ev_ms(hipEvent_t a, hipEvent_t b) {
@@ -1591,195 +1626,9 @@ hk_status Ops<C>::commit_batch(hk_ctx* ctx, const hk_pk* h, size_t stage, const 
     return HK_OK;
 }
 
-template <class C>
-hk_status Ops<C>::prove(hk_ctx* ctx, const hk_pk* h, const void* z, size_t n_v, const void* r_m,
-                        const void* s_m, const void* kappas, size_t n_kappas, void* out_a, void* out_b,
-                        void* out_c) {
-    typedef QapHost<C> Q;
-    if (h->ctx != ctx) return HK_ERR_ARG;
-    PkImpl<C>* pk = (PkImpl<C>*)h->impl;
-    if (!pk->has_qap) return HK_ERR_ARG;
-    if (n_v != pk->n_v) return HK_ERR_LEN;
-    if (n_kappas + 1 != pk->n_stages) return HK_ERR_LEN;   // committer.rs:112 assert
-    if (n_kappas && !kappas) return HK_ERR_ARG;
-    NttTables* T;
-    HK_TRY(NttHost<C>::ensure(ctx, pk->log_m, &T));
-    LaneGuard g(ctx);
-    Lane* L = g.lane;
-    if (!L) return HK_ERR_DEVICE;
-    const MsmPlan &pz = pk->plan_z, &ph = pk->plan_h;
-    size_t m = (size_t)1 << pk->log_m;
-    const MsmPlan& pb = pk->plan_b;
-    size_t need = al256(sizeof(Fr) * pk->n_ext) + al256(sizeof(Fr) * n_v) + msm_sort_bytes(pz) +
-                  msm_sort_bytes(ph) + 2 * msm_run_bytes<Fq>(pz) + msm_run_bytes<Fq>(pb) + msm_run_bytes<Fq>(ph) +
-                  msm_run_bytes<Fq2>(pb) + al256(3 * m * sizeof(Fr)) + 16384;
-    if (pk->b_compact) need += msm_sort_bytes(pb) + al256(sizeof(Fr) * pk->b_n);
-    HK_TRY(L->reserve(need));
-    hipStream_t s = L->stream;
-    bool prof = ctx->profiling;
-    hipEvent_t* ev = L->ev;
-    int e = 0;
-    auto mark = [&]() -> hk_status { if (prof) HK_HIP(hipEventRecord(ev[e], s)); e++; return HK_OK; };
-    HK_TRY(mark());                                                            // ev0
-    // --- extended scalar vector: z[1..] | r | s | rs | kappas
-    Fr* zext = L->alloc_n<Fr>(pk->n_ext);
-    Fr* small = L->alloc_n<Fr>(2 + n_kappas);
-    if (!zext || !small) return HK_ERR_NOMEM;
-    const Fr* zd;
-    if (is_device_ptr(z)) zd = (const Fr*)z;
-    else {
-        Fr* t = L->alloc_n<Fr>(n_v);
-        if (!t) return HK_ERR_NOMEM;
-        HK_HIP(hipMemcpyAsync(t, z, n_v * sizeof(Fr), hipMemcpyHostToDevice, s));
-        zd = t;
-    }
-    if (n_v > 1) HK_HIP(hipMemcpyAsync(zext, zd + 1, (n_v - 1) * sizeof(Fr), hipMemcpyDeviceToDevice, s));
-    HK_HIP(hipMemcpyAsync(small, r_m, sizeof(Fr), hipMemcpyHostToDevice, s));
-    HK_HIP(hipMemcpyAsync(small + 1, s_m, sizeof(Fr), hipMemcpyHostToDevice, s));
-    if (n_kappas) HK_HIP(hipMemcpyAsync(small + 2, kappas, n_kappas * sizeof(Fr), hipMemcpyHostToDevice, s));
-    // --- one digit sort shared by the four assignment-indexed queries
-    SortBufs sb, sbh, sbb;
-    sbb.count = nullptr;
-    HK_TRY(MsmSort<Fr>::alloc(L, pz, &sb));
-    HK_TRY(MsmSort<Fr>::alloc(L, ph, &sbh));
-    Fr* zb = nullptr;
-    if (pk->b_compact) {
-        HK_TRY(MsmSort<Fr>::alloc(L, pb, &sbb));
-        zb = L->alloc_n<Fr>(pk->b_n);
-        if (!zb) return HK_ERR_NOMEM;
-    }
-    hipLaunchKernelGGL((k_prep_ext<Fr>), dim3(64), dim3(256), 0, s, zext + (n_v - 1), small, (u32)n_kappas, sb.count,
-                       sbh.count, sbb.count, pz.NB, ph.NB, pk->b_compact ? pb.NB : 0u);
-    typename MsmRun<Fq>::Bufs rbA, rbB1, rbL, rbh;
-    typename MsmRun<Fq2>::Bufs rb2;
-    HK_TRY(MsmRun<Fq>::alloc(L, pz, &rbA));
-    HK_TRY(MsmRun<Fq>::alloc(L, pb, &rbB1));
-    HK_TRY(MsmRun<Fq>::alloc(L, pz, &rbL));
-    HK_TRY(MsmRun<Fq>::alloc(L, ph, &rbh));
-    HK_TRY(MsmRun<Fq2>::alloc(L, pb, &rb2));
-    XYZZ<Fq>* res1 = L->alloc_n<XYZZ<Fq>>(4);
-    XYZZ<Fq2>* res2 = L->alloc_n<XYZZ<Fq2>>(1);
-    Affine<Fq>* oa = L->alloc_n<Affine<Fq>>(2);
-    Affine<Fq2>* ob = L->alloc_n<Affine<Fq2>>(1);
-    Fr* abc = L->alloc_n<Fr>(3 * m);
-    if (!res1 || !res2 || !oa || !ob || !abc) return HK_ERR_NOMEM;
-    // Fork: the five queries are independent once their scalars exist.  Side streams let the
-    // latency-bound tails (segmented levels, bucket reduction) of one query hide under the
-    // throughput-bound accumulation of another.
-    //   main  : sort(z) -> A
-    //   aux0  : B1      aux1 : B2 (G2)      aux2 : L      aux3 : witness map -> sort(h) -> H
-    // HK_SERIAL_STREAMS=1 keeps everything on the lane's own stream: clean per-kernel times for profiling, and - with
-    // 18 lanes and GPU_MAX_HW_QUEUES=18, one hardware queue per lane - the faster form for small circuits (DESIGN.md
-    // section 5).  Not the default: 18 concurrent G2 tail kernels (2-3 KB of scratch per lane each) once exhausted the
-    // runtime's scratch pool on BLS12-381 and the process aborted (HSA_STATUS_ERROR_OUT_OF_RESOURCES).
-    hipStream_t axs[4] = {L->aux[0], L->aux[1], L->aux[2], L->aux[3]};
-    static const bool serial = getenv("HK_SERIAL_STREAMS") != nullptr;
-    if (serial) for (auto& a : axs) a = s;
-    hipStream_t* ax = axs;
-    // Every exit between the fork and the join - an HK_TRY / HK_HIP return included - must leave no side stream
-    // running on this lane's arena: the next call on the lane resets the arena and would reuse live memory.
-    struct JoinGuard {
-        hipStream_t main; hipStream_t* aux; bool joined = false;
-        ~JoinGuard() {
-            if (joined) return;
-            for (int i = 0; i < 4; i++) (void)hipStreamSynchronize(aux[i]);
-            (void)hipStreamSynchronize(main);
-        }
-    } join_guard{s, axs};
-    hipEvent_t ev_z = ev[16], ev_sorted = ev[17];
-    HK_HIP(hipEventRecord(ev_z, s));                                           // z (and ext scalars) on device
-    HK_HIP(hipStreamWaitEvent(ax[3], ev_z, 0));
-    if (prof) HK_HIP(hipEventRecord(ev[5], ax[3]));
-    HK_TRY(Q::run(ax[3], T, pk->csr[0], pk->csr[1], pk->csr[2], pk->n_inst, pk->n_c, zd, abc, pk->log_m));
-    if (prof) HK_HIP(hipEventRecord(ev[6], ax[3]));                            // witness map done
-    HK_TRY(MsmSort<Fr>::run(ax[3], ph, (const u32*)abc, 1, sbh, true));
-    hipEvent_t kh0 = prof ? ev[12] : nullptr, kh1 = prof ? ev[13] : nullptr;
-    HK_TRY(MsmRun<Fq>::run(ax[3], ph, pk->h_tab, (u32)m, 0, sbh, rbh, res1 + 3, kh0, kh1));
-    HK_HIP(hipEventRecord(ev[7], ax[3]));                                      // H done
-    HK_TRY(MsmSort<Fr>::run(s, pz, (const u32*)zext, 1, sb, true));
-    HK_HIP(hipEventRecord(ev_sorted, s));
-    HK_TRY(mark());                                                            // ev1: digits done
-    HK_HIP(hipStreamWaitEvent(ax[2], ev_sorted, 0));
-    const SortBufs* sbB = &sb;
-    if (pk->b_compact) {
-        // B1 / B2 over the non-infinity bases only: gather their scalars, sort those digits on aux0
-        HK_HIP(hipStreamWaitEvent(ax[0], ev_z, 0));
-        hipLaunchKernelGGL((k_gather<Fr>), dim3((pk->b_n + 255) / 256), dim3(256), 0, ax[0], zb, (const Fr*)zext,
-                           (const u32*)pk->b_idx, pk->b_n, pk->n_ext);
-        HK_TRY(MsmSort<Fr>::run(ax[0], pb, (const u32*)zb, 1, sbb, true));
-        HK_HIP(hipEventRecord(ev[28], ax[0]));
-        HK_HIP(hipStreamWaitEvent(ax[1], ev[28], 0));
-        sbB = &sbb;
-    } else {
-        HK_HIP(hipStreamWaitEvent(ax[0], ev_sorted, 0));
-        HK_HIP(hipStreamWaitEvent(ax[1], ev_sorted, 0));
-    }
-    HK_TRY(MsmRun<Fq2>::run(ax[1], pb, pk->b2_tab, pk->b_n, 0, *sbB, rb2, res2, nullptr, nullptr));
-    HK_HIP(hipEventRecord(ev[4], ax[1]));                                      // B2 done
-    HK_TRY(MsmRun<Fq>::run(ax[0], pb, pk->b1_tab, pk->b_n, 0, *sbB, rbB1, res1 + 1, prof ? ev[22] : nullptr,
-                           prof ? ev[23] : nullptr));
-    HK_HIP(hipEventRecord(ev[3], ax[0]));                                      // B1 done
-    HK_TRY(MsmRun<Fq>::run(ax[2], pz, pk->l_tab, pk->l_n, pk->l_off, sb, rbL, res1 + 2, prof ? ev[24] : nullptr,
-                           prof ? ev[25] : nullptr));
-    HK_HIP(hipEventRecord(ev[18], ax[2]));                                     // L done
-    HK_TRY(MsmRun<Fq>::run(s, pz, pk->a_tab, pk->n_ext, 0, sb, rbA, res1 + 0, prof ? ev[26] : nullptr,
-                           prof ? ev[27] : nullptr));
-    HK_TRY(mark());                                                            // ev2: A done
-    // Join
-    HK_HIP(hipStreamWaitEvent(s, ev[3], 0));
-    HK_HIP(hipStreamWaitEvent(s, ev[4], 0));
-    HK_HIP(hipStreamWaitEvent(s, ev[18], 0));
-    HK_HIP(hipStreamWaitEvent(s, ev[7], 0));
-    join_guard.joined = true;                                                  // main now depends on every side stream
-    if (prof) HK_HIP(hipEventRecord(ev[19], s));                               // all queries done
-    static const EndoSplit<2> endo_g1 = EndoOf<Fq>::split();
-    hipLaunchKernelGGL((k_finish<Fr, Fq, Fq2>), dim3(3), dim3(64), 0, s, res1, res2, pk->consts_g1,
-                       pk->consts_g2, small, oa, ob, oa + 1, endo_g1);
-    HK_HIP(hipGetLastError());
-    HK_HIP(hipMemcpyAsync(out_a, oa, sizeof(Affine<Fq>), hipMemcpyDeviceToHost, s));
-    HK_HIP(hipMemcpyAsync(out_b, ob, sizeof(Affine<Fq2>), hipMemcpyDeviceToHost, s));
-    HK_HIP(hipMemcpyAsync(out_c, oa + 1, sizeof(Affine<Fq>), hipMemcpyDeviceToHost, s));
-    if (prof) HK_HIP(hipEventRecord(ev[8], s));
-    HK_HIP(hipStreamSynchronize(s));
-    if (prof) {
-        hk_timings& t = L->timings;
-        memset(&t, 0, sizeof(t));
-        // the five queries run concurrently on side streams: each figure is the elapsed time on the
-        // query's own stream since its fork point (they overlap, they do not add up to total_ms)
-        t.total_ms = ev_ms(ev[0], ev[8]);
-        t.digits_ms = ev_ms(ev[0], ev[1]);
-        t.msm_a_ms = ev_ms(ev[1], ev[2]);
-        t.msm_b_g1_ms = ev_ms(ev[1], ev[3]);
-        t.msm_b_g2_ms = ev_ms(ev[1], ev[4]);
-        t.msm_l_ms = ev_ms(ev[1], ev[18]);
-        t.witness_map_ms = ev_ms(ev[5], ev[6]);
-        t.msm_h_ms = ev_ms(ev[6], ev[7]);
-        t.finish_ms = ev_ms(ev[19], ev[8]);
-        // k_msm_accum0<Fq> launches of this proof: H (dense) + A, B1, L (sparse)
-        t.accum_h_ms = ev_ms(ev[12], ev[13]);
-        t.accum_kernel_ms = t.accum_h_ms + ev_ms(ev[22], ev[23]) + ev_ms(ev[24], ev[25]) + ev_ms(ev[26], ev[27]);
-        t.accum_kernel_launches = 4;
-    }
-    return HK_OK;
-}
-
-// ---- hk_prove_batch ---------------------------------------------------------------------------------------------------
-// Device bytes of one lock-step chunk of `nb` proofs: every per-proof buffer of hk_prove times nb, the bucket pipelines
-// sized by the batched lane plan (the chip's lanes split across the chunk, so the boundary partials do not grow with nb).
-inline size_t msm_sort_bytes_b(const MsmPlan& p, size_t nb) {
-    return al256(4ull * p.NB * nb) * 2 + al256(4ull * (p.NB + 1) * nb) + al256(4ull * msm_sorted_stride(p) * nb) +
-           al256(2ull * msm_digits_stride(p) * nb) + 1024;
-}
-template <class F>
-inline size_t msm_run_bytes_b(const MsmPlan& p0, size_t nb) {
-    MsmPlan p = p0;
-    msm_set_lanes(p, (u32)(4u * 65536u / nb));   // upper bound over the per-flavour lane schedules (msm_lane_plan_b)
-    size_t n0 = 2ull * p.T[0], n1 = msm_p1_stride(p);
-    return al256(sizeof(XYZZ<F>) * (p.NB + 1) * nb) + al256(4 * n0 * nb) + al256(sizeof(XYZZ<F>) * n0 * nb) +
-           al256(4 * n1 * nb) + al256(sizeof(XYZZ<F>) * n1 * nb) + al256(sizeof(XYZZ<F>) * p.WP * (p.B / p.K) * nb) +
-           al256(sizeof(XYZZ<F>) * p.WP * nb) + 2048;
-}
-
+// hk_prove is a batch of one.  A batch runs in chunks of up to HK_PROVE_BATCH_CHUNK proofs, every stage one launch for
+// the chunk (proof = grid.y, or grid.x for the one-workgroup stages), each proof on its own slice of the buffers; all
+// read the key's shared shift tables.
 template <class C>
 hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t n_v, const void* r_m, const void* s_m,
                               const void* kappas, size_t n_kappas, size_t batch, void* out_a, void* out_b, void* out_c) {
@@ -1788,7 +1637,7 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
     PkImpl<C>* pk = (PkImpl<C>*)h->impl;
     if (!pk->has_qap) return HK_ERR_ARG;
     if (n_v != pk->n_v) return HK_ERR_LEN;
-    if (n_kappas + 1 != pk->n_stages) return HK_ERR_LEN;
+    if (n_kappas + 1 != pk->n_stages) return HK_ERR_LEN;   // committer.rs:112 assert
     if (batch == 0) return HK_OK;
     if (!z || !r_m || !s_m || !out_a || !out_b || !out_c || (n_kappas && !kappas)) return HK_ERR_ARG;
     NttTables* T;
@@ -1799,26 +1648,28 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
     const MsmPlan &pz = pk->plan_z, &ph = pk->plan_h, &pb = pk->plan_b;
     const size_t m = (size_t)1 << pk->log_m, fr = sizeof(Fr), rs_stride = 2 + n_kappas;
     const bool z_dev = is_device_ptr(z);
+    // device bytes of one chunk of `nb` proofs: every per-proof buffer times nb, the bucket pipelines sized by the lane
+    // plan of the chunk (the chip's lanes split across it, so the boundary partials do not grow with nb)
     auto need_for = [&](size_t nb) -> size_t {
-        size_t need = al256(fr * pk->n_ext * nb) + al256(fr * rs_stride * nb) + msm_sort_bytes_b(pz, nb) +
-                      msm_sort_bytes_b(ph, nb) + 2 * msm_run_bytes_b<Fq>(pz, nb) + msm_run_bytes_b<Fq>(pb, nb) +
-                      msm_run_bytes_b<Fq>(ph, nb) + msm_run_bytes_b<Fq2>(pb, nb) + al256(3 * m * fr * nb) +
+        size_t need = al256(fr * pk->n_ext * nb) + al256(fr * rs_stride * nb) + msm_sort_bytes(pz, nb) +
+                      msm_sort_bytes(ph, nb) + 2 * msm_run_bytes<Fq>(pz, nb) + msm_run_bytes<Fq>(pb, nb) +
+                      msm_run_bytes<Fq>(ph, nb) + msm_run_bytes<Fq2>(pb, nb) + al256(3 * m * fr * nb) +
                       al256(4 * nb * sizeof(XYZZ<Fq>)) + al256(nb * sizeof(XYZZ<Fq2>)) + 2 * al256(nb * sizeof(Affine<Fq>)) +
                       al256(nb * sizeof(Affine<Fq2>)) + 16384;
         if (!z_dev) need += al256(fr * n_v * nb);
-        if (pk->b_compact) need += msm_sort_bytes_b(pb, nb) + al256(fr * pk->b_n * nb);
+        if (pk->b_compact) need += msm_sort_bytes(pb, nb) + al256(fr * pk->b_n * nb);
         return need;
     };
     // chunk rule (hekaton.h): at most HK_PROVE_BATCH_CHUNK proofs, fewer when that many would not fit in free device memory
     // (the lane's own arena counts as free: reserve() replaces it)
     size_t chunk = batch < (size_t)HK_PROVE_BATCH_CHUNK ? batch : (size_t)HK_PROVE_BATCH_CHUNK;
-    {
+    if (chunk > 1) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
         size_t avail = free_b + L->arena_cap;
         while (chunk > 1 && need_for(chunk) > avail) chunk--;
     }
-    // r | s | kappas of every proof, one row each (k_prep_ext_b and k_finish_b read them)
+    // r | s | kappas of every proof, one row each (k_prep_ext and k_finish read them)
     std::vector<unsigned char> rows(batch * rs_stride * fr);
     for (size_t b = 0; b < batch; b++) {
         unsigned char* row = rows.data() + b * rs_stride * fr;
@@ -1831,15 +1682,20 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
     hipEvent_t* ev = L->ev;
     hk_timings acc;
     memset(&acc, 0, sizeof(acc));
-    if (prof) HK_HIP(hipEventRecord(ev[9], s));
     static const EndoSplit<2> endo_g1 = EndoOf<Fq>::split();
+    // HK_SERIAL_STREAMS=1 keeps everything on the lane's own stream: clean per-kernel times for profiling, and - with
+    // 18 lanes and GPU_MAX_HW_QUEUES=18, one hardware queue per lane - the faster form for small circuits (DESIGN.md
+    // section 5).  Not the default: 18 concurrent G2 tail kernels (2-3 KB of scratch per lane each) once exhausted the
+    // runtime's scratch pool on BLS12-381 and the process aborted (HSA_STATUS_ERROR_OUT_OF_RESOURCES).
     static const bool serial = getenv("HK_SERIAL_STREAMS") != nullptr;
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const u32 nb = (u32)std::min(chunk, batch - b0);
         HK_TRY(L->reserve(need_for(nb)));
-        auto mark = [&](int i) -> hk_status { if (prof) HK_HIP(hipEventRecord(ev[i], s)); return HK_OK; };
-        HK_TRY(mark(0));
-        Fr* zext = L->alloc_n<Fr>((size_t)pk->n_ext * nb);                      // [nb][n_ext]: z[1..] | r | s | rs | kappas
+        // ev[0] marks the start of the call (total_ms runs from it to the last chunk's ev[8]), ev[9] that of a later chunk
+        hipEvent_t ev_start = b0 ? ev[9] : ev[0];
+        if (prof) HK_HIP(hipEventRecord(ev_start, s));
+        // --- extended scalar vectors [nb][n_ext]: z[1..] | r | s | rs | kappas
+        Fr* zext = L->alloc_n<Fr>((size_t)pk->n_ext * nb);
         Fr* small = L->alloc_n<Fr>(rs_stride * nb);                             // [nb][2 + n_kappas]
         if (!zext || !small) return HK_ERR_NOMEM;
         const Fr* zd;
@@ -1850,29 +1706,32 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
             HK_HIP(hipMemcpyAsync(t, (const Fr*)z + b0 * n_v, n_v * nb * fr, hipMemcpyHostToDevice, s));
             zd = t;
         }
-        if (n_v > 1)
+        if (n_v > 1 && nb == 1)
+            HK_HIP(hipMemcpyAsync(zext, zd + 1, (n_v - 1) * fr, hipMemcpyDeviceToDevice, s));
+        else if (n_v > 1)
             HK_HIP(hipMemcpy2DAsync(zext, pk->n_ext * fr, zd + 1, n_v * fr, (n_v - 1) * fr, nb, hipMemcpyDeviceToDevice, s));
         HK_HIP(hipMemcpyAsync(small, rows.data() + b0 * rs_stride * fr, nb * rs_stride * fr, hipMemcpyHostToDevice, s));
+        // --- one digit sort per proof shared by the four assignment-indexed queries
         SortBufs sb, sbh, sbb;
         sbb.count = nullptr;
-        HK_TRY(MsmSort<Fr>::alloc_b(L, pz, nb, &sb));
-        HK_TRY(MsmSort<Fr>::alloc_b(L, ph, nb, &sbh));
+        HK_TRY(MsmSort<Fr>::alloc(L, pz, &sb, nb));
+        HK_TRY(MsmSort<Fr>::alloc(L, ph, &sbh, nb));
         Fr* zb = nullptr;
         if (pk->b_compact) {
-            HK_TRY(MsmSort<Fr>::alloc_b(L, pb, nb, &sbb));
+            HK_TRY(MsmSort<Fr>::alloc(L, pb, &sbb, nb));
             zb = L->alloc_n<Fr>((size_t)pk->b_n * nb);
             if (!zb) return HK_ERR_NOMEM;
         }
-        hipLaunchKernelGGL((k_prep_ext_b<Fr>), dim3(64), dim3(256), 0, s, zext + (n_v - 1), pk->n_ext, (const Fr*)small,
+        hipLaunchKernelGGL((k_prep_ext<Fr>), dim3(64), dim3(256), 0, s, zext + (n_v - 1), pk->n_ext, (const Fr*)small,
                            (u32)rs_stride, (u32)n_kappas, nb, sb.count, sbh.count, sbb.count, pz.NB * nb, ph.NB * nb,
                            pk->b_compact ? pb.NB * nb : 0u);
         typename MsmRun<Fq>::Bufs rbA, rbB1, rbL, rbh;
         typename MsmRun<Fq2>::Bufs rb2;
-        HK_TRY(MsmRun<Fq>::alloc_b(L, pz, nb, &rbA));
-        HK_TRY(MsmRun<Fq>::alloc_b(L, pb, nb, &rbB1));
-        HK_TRY(MsmRun<Fq>::alloc_b(L, pz, nb, &rbL));
-        HK_TRY(MsmRun<Fq>::alloc_b(L, ph, nb, &rbh));
-        HK_TRY(MsmRun<Fq2>::alloc_b(L, pb, nb, &rb2));
+        HK_TRY(MsmRun<Fq>::alloc(L, pz, &rbA, nb));
+        HK_TRY(MsmRun<Fq>::alloc(L, pb, &rbB1, nb));
+        HK_TRY(MsmRun<Fq>::alloc(L, pz, &rbL, nb));
+        HK_TRY(MsmRun<Fq>::alloc(L, ph, &rbh, nb));
+        HK_TRY(MsmRun<Fq2>::alloc(L, pb, &rb2, nb));
         XYZZ<Fq>* res1 = L->alloc_n<XYZZ<Fq>>(4 * (size_t)nb);                  // [nb][A, B1, L, H]
         XYZZ<Fq2>* res2 = L->alloc_n<XYZZ<Fq2>>(nb);
         Affine<Fq>* oa = L->alloc_n<Affine<Fq>>(nb);
@@ -1880,10 +1739,16 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
         Affine<Fq2>* ob = L->alloc_n<Affine<Fq2>>(nb);
         Fr* abc = L->alloc_n<Fr>(3 * m * nb);                                   // [nb][a | b | c]
         if (!res1 || !res2 || !oa || !oc || !ob || !abc) return HK_ERR_NOMEM;
-        // the fork of hk_prove, one query per stream, every launch covering the whole chunk
+        // Fork: the five queries are independent once their scalars exist.  Side streams let the
+        // latency-bound tails (segmented levels, bucket reduction) of one query hide under the
+        // throughput-bound accumulation of another; every launch covers the whole chunk.
+        //   main  : sort(z) -> A
+        //   aux0  : B1      aux1 : B2 (G2)      aux2 : L      aux3 : witness map -> sort(h) -> H
         hipStream_t axs[4] = {L->aux[0], L->aux[1], L->aux[2], L->aux[3]};
         if (serial) for (auto& a : axs) a = s;
         hipStream_t* ax = axs;
+        // Every exit between the fork and the join - an HK_TRY / HK_HIP return included - must leave no side stream
+        // running on this lane's arena: the next call on the lane resets the arena and would reuse live memory.
         struct JoinGuard {
             hipStream_t main; hipStream_t* aux; bool joined = false;
             ~JoinGuard() {
@@ -1893,27 +1758,28 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
             }
         } join_guard{s, axs};
         hipEvent_t ev_z = ev[16], ev_sorted = ev[17];
-        HK_HIP(hipEventRecord(ev_z, s));
+        HK_HIP(hipEventRecord(ev_z, s));                                       // z (and ext scalars) on device
         HK_HIP(hipStreamWaitEvent(ax[3], ev_z, 0));
         if (prof) HK_HIP(hipEventRecord(ev[5], ax[3]));
         for (u32 j = 0; j < nb; j++)                                            // witness map: one chain per proof
             HK_TRY(Q::run(ax[3], T, pk->csr[0], pk->csr[1], pk->csr[2], pk->n_inst, pk->n_c, zd + (size_t)j * n_v,
                           abc + (size_t)j * 3 * m, pk->log_m));
-        if (prof) HK_HIP(hipEventRecord(ev[6], ax[3]));
-        HK_TRY(MsmSort<Fr>::run_b(ax[3], ph, (const u32*)abc, 3 * m, 1, nb, sbh));
-        HK_TRY(MsmRun<Fq>::run_b(ax[3], ph, pk->h_tab, (u32)m, 0, nb, sbh, rbh, res1 + 3, 4, prof ? ev[12] : nullptr,
-                                 prof ? ev[13] : nullptr));
-        HK_HIP(hipEventRecord(ev[7], ax[3]));
-        HK_TRY(MsmSort<Fr>::run_b(s, pz, (const u32*)zext, pk->n_ext, 1, nb, sb));
+        if (prof) HK_HIP(hipEventRecord(ev[6], ax[3]));                        // witness map done
+        HK_TRY(MsmSort<Fr>::run(ax[3], ph, (const u32*)abc, 1, sbh, true, nb, 3 * m));
+        HK_TRY(MsmRun<Fq>::run(ax[3], ph, pk->h_tab, (u32)m, 0, sbh, rbh, res1 + 3, prof ? ev[12] : nullptr,
+                               prof ? ev[13] : nullptr, nb, 4));
+        HK_HIP(hipEventRecord(ev[7], ax[3]));                                  // H done
+        HK_TRY(MsmSort<Fr>::run(s, pz, (const u32*)zext, 1, sb, true, nb, pk->n_ext));
         HK_HIP(hipEventRecord(ev_sorted, s));
-        HK_TRY(mark(1));
+        if (prof) HK_HIP(hipEventRecord(ev[1], s));                            // digits done
         HK_HIP(hipStreamWaitEvent(ax[2], ev_sorted, 0));
         const SortBufs* sbB = &sb;
         if (pk->b_compact) {
+            // B1 / B2 over the non-infinity bases only: gather their scalars, sort those digits on aux0
             HK_HIP(hipStreamWaitEvent(ax[0], ev_z, 0));
-            hipLaunchKernelGGL((k_gather_b<Fr>), dim3((pk->b_n + 255) / 256, nb), dim3(256), 0, ax[0], zb, (const Fr*)zext,
+            hipLaunchKernelGGL((k_gather<Fr>), dim3((pk->b_n + 255) / 256, nb), dim3(256), 0, ax[0], zb, (const Fr*)zext,
                                (const u32*)pk->b_idx, pk->b_n, pk->n_ext);
-            HK_TRY(MsmSort<Fr>::run_b(ax[0], pb, (const u32*)zb, pk->b_n, 1, nb, sbb));
+            HK_TRY(MsmSort<Fr>::run(ax[0], pb, (const u32*)zb, 1, sbb, true, nb, pk->b_n));
             HK_HIP(hipEventRecord(ev[28], ax[0]));
             HK_HIP(hipStreamWaitEvent(ax[1], ev[28], 0));
             sbB = &sbb;
@@ -1921,34 +1787,36 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
             HK_HIP(hipStreamWaitEvent(ax[0], ev_sorted, 0));
             HK_HIP(hipStreamWaitEvent(ax[1], ev_sorted, 0));
         }
-        HK_TRY(MsmRun<Fq2>::run_b(ax[1], pb, pk->b2_tab, pk->b_n, 0, nb, *sbB, rb2, res2, 1, nullptr, nullptr));
-        HK_HIP(hipEventRecord(ev[4], ax[1]));
-        HK_TRY(MsmRun<Fq>::run_b(ax[0], pb, pk->b1_tab, pk->b_n, 0, nb, *sbB, rbB1, res1 + 1, 4, prof ? ev[22] : nullptr,
-                                 prof ? ev[23] : nullptr));
-        HK_HIP(hipEventRecord(ev[3], ax[0]));
-        HK_TRY(MsmRun<Fq>::run_b(ax[2], pz, pk->l_tab, pk->l_n, pk->l_off, nb, sb, rbL, res1 + 2, 4, prof ? ev[24] : nullptr,
-                                 prof ? ev[25] : nullptr));
-        HK_HIP(hipEventRecord(ev[18], ax[2]));
-        HK_TRY(MsmRun<Fq>::run_b(s, pz, pk->a_tab, pk->n_ext, 0, nb, sb, rbA, res1 + 0, 4, prof ? ev[26] : nullptr,
-                                 prof ? ev[27] : nullptr));
-        HK_TRY(mark(2));
+        HK_TRY(MsmRun<Fq2>::run(ax[1], pb, pk->b2_tab, pk->b_n, 0, *sbB, rb2, res2, nullptr, nullptr, nb, 1));
+        HK_HIP(hipEventRecord(ev[4], ax[1]));                                  // B2 done
+        HK_TRY(MsmRun<Fq>::run(ax[0], pb, pk->b1_tab, pk->b_n, 0, *sbB, rbB1, res1 + 1, prof ? ev[22] : nullptr,
+                               prof ? ev[23] : nullptr, nb, 4));
+        HK_HIP(hipEventRecord(ev[3], ax[0]));                                  // B1 done
+        HK_TRY(MsmRun<Fq>::run(ax[2], pz, pk->l_tab, pk->l_n, pk->l_off, sb, rbL, res1 + 2, prof ? ev[24] : nullptr,
+                               prof ? ev[25] : nullptr, nb, 4));
+        HK_HIP(hipEventRecord(ev[18], ax[2]));                                 // L done
+        HK_TRY(MsmRun<Fq>::run(s, pz, pk->a_tab, pk->n_ext, 0, sb, rbA, res1 + 0, prof ? ev[26] : nullptr,
+                               prof ? ev[27] : nullptr, nb, 4));
+        if (prof) HK_HIP(hipEventRecord(ev[2], s));                            // A done
+        // Join
         HK_HIP(hipStreamWaitEvent(s, ev[3], 0));
         HK_HIP(hipStreamWaitEvent(s, ev[4], 0));
         HK_HIP(hipStreamWaitEvent(s, ev[18], 0));
         HK_HIP(hipStreamWaitEvent(s, ev[7], 0));
-        join_guard.joined = true;
-        if (prof) HK_HIP(hipEventRecord(ev[19], s));
-        hipLaunchKernelGGL((k_finish_b<Fr, Fq, Fq2>), dim3(3, nb), dim3(64), 0, s, res1, res2, pk->consts_g1, pk->consts_g2,
+        join_guard.joined = true;                                              // main now depends on every side stream
+        if (prof) HK_HIP(hipEventRecord(ev[19], s));                           // all queries done
+        hipLaunchKernelGGL((k_finish<Fr, Fq, Fq2>), dim3(3, nb), dim3(64), 0, s, res1, res2, pk->consts_g1, pk->consts_g2,
                            (const Fr*)small, (u32)rs_stride, oa, ob, oc, endo_g1);
         HK_HIP(hipGetLastError());
         HK_HIP(hipMemcpyAsync((char*)out_a + b0 * sizeof(Affine<Fq>), oa, nb * sizeof(Affine<Fq>), hipMemcpyDeviceToHost, s));
         HK_HIP(hipMemcpyAsync((char*)out_b + b0 * sizeof(Affine<Fq2>), ob, nb * sizeof(Affine<Fq2>), hipMemcpyDeviceToHost, s));
         HK_HIP(hipMemcpyAsync((char*)out_c + b0 * sizeof(Affine<Fq>), oc, nb * sizeof(Affine<Fq>), hipMemcpyDeviceToHost, s));
-        HK_TRY(mark(8));
+        if (prof) HK_HIP(hipEventRecord(ev[8], s));
         HK_HIP(hipStreamSynchronize(s));
         if (prof) {
-            // phase brackets summed over the chunks (within a chunk they overlap, as in hk_prove)
-            acc.digits_ms += ev_ms(ev[0], ev[1]);
+            // the five queries run concurrently on side streams: each figure is the elapsed time on the query's own
+            // stream since its fork point (they overlap, they do not add up to total_ms); summed over the chunks
+            acc.digits_ms += ev_ms(ev_start, ev[1]);
             acc.msm_a_ms += ev_ms(ev[1], ev[2]);
             acc.msm_b_g1_ms += ev_ms(ev[1], ev[3]);
             acc.msm_b_g2_ms += ev_ms(ev[1], ev[4]);
@@ -1956,16 +1824,15 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
             acc.witness_map_ms += ev_ms(ev[5], ev[6]);
             acc.msm_h_ms += ev_ms(ev[6], ev[7]);
             acc.finish_ms += ev_ms(ev[19], ev[8]);
+            // the k_msm_accum0<Fq> launches of the chunk: H (dense) + A, B1, L (sparse)
             float kh = ev_ms(ev[12], ev[13]);
             acc.accum_h_ms += kh;
             acc.accum_kernel_ms += kh + ev_ms(ev[22], ev[23]) + ev_ms(ev[24], ev[25]) + ev_ms(ev[26], ev[27]);
-            acc.accum_kernel_launches += 4;                                     // H, A, B1, L: each one launch per chunk
+            acc.accum_kernel_launches += 4;
         }
     }
     if (prof) {
-        HK_HIP(hipEventRecord(ev[10], s));
-        HK_HIP(hipEventSynchronize(ev[10]));
-        acc.total_ms = ev_ms(ev[9], ev[10]);
+        acc.total_ms = ev_ms(ev[0], ev[8]);
         L->timings = acc;
     }
     return HK_OK;
