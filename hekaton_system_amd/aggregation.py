@@ -264,3 +264,30 @@ class AggProvingKey:
         com_lr = f_lr.result()
         return dict(size=n, output=z_lr, commitment=com_lr, twist=twist, left=left, right=right, cross_terms=z,
                     com_ab=com_ab, com_c=com_c, prepared_input=prepared_input)
+
+
+def verify_subcircuit_proofs(ctx, vks, proofs, pub_inputs, batch_rng=None):
+    """Opt-in check of the stage-1 proofs a coordinator received, before agg_front: verify_proof (verifier.rs:64-71) for
+    every subcircuit, grouped by verifying key (one hk_vk_prepare + one hk_verify_batch per key class).  vks: the
+    VerifyingKey of each proof (one per proof); pub_inputs: the public inputs shared by all subcircuits (a list of ints)
+    or one list per proof.  Returns the sorted indices of the proofs that fail (rejected or carrying an invalid point)."""
+    from .cp_groth16 import prepare_verifying_key, verify_proofs
+    n = len(proofs)
+    if len(vks) != n:
+        raise ValueError("one verifying key per proof")
+    per_proof = n > 0 and isinstance(pub_inputs[0], (list, tuple))
+    if per_proof and len(pub_inputs) != n:
+        raise ValueError("one list of public inputs per proof")
+    groups = {}
+    for i, vk in enumerate(vks):
+        groups.setdefault(id(vk), (vk, []))[1].append(i)
+    bad = []
+    for vk, idx in groups.values():
+        pvk = prepare_verifying_key(ctx, vk)
+        try:
+            xs = [list(pub_inputs[i]) if per_proof else list(pub_inputs) for i in idx]
+            verdicts = verify_proofs(pvk, [proofs[i] for i in idx], xs, batch_rng=batch_rng)
+        finally:
+            pvk.free()
+        bad += [i for i, v in zip(idx, verdicts) if v != 1]
+    return sorted(bad)

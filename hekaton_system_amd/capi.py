@@ -51,6 +51,11 @@ class hk_pk_desc(C.Structure):
                 ("n_inst", C.c_size_t), ("n_constraints", C.c_size_t)]
 
 
+class hk_vk_desc(C.Structure):                # include/hekaton.h
+    _fields_ = [("alpha_g", C.c_void_p), ("beta_h", C.c_void_p), ("gamma_h", C.c_void_p), ("deltas_h", C.c_void_p),
+                ("n_deltas", C.c_size_t), ("gamma_abc_g", C.c_void_p), ("n_abc", C.c_size_t)]
+
+
 class hk_timings(C.Structure):
     _fields_ = [(n, C.c_float) for n in
                 ("total_ms", "digits_ms", "msm_a_ms", "msm_b_g1_ms", "msm_b_g2_ms", "msm_l_ms",
@@ -68,7 +73,11 @@ EXPORTS = ["hk_status_str", "hk_version", "hk_ctx_create", "hk_ctx_destroy", "hk
            "hk_pk_upload", "hk_pk_free", "hk_commit", "hk_prove", "hk_fixed_base_g1", "hk_fixed_base_g2", "hk_scalar_pairing_g1", "hk_scalar_pairing_g2", "hk_field_convert", "hk_bases_upload", "hk_bases_free",
            "hk_msm_bases", "hk_multi_pairing", "hk_pairing_products", "hk_ctx_gt_bytes",
            "hk_points_lincomb_g1", "hk_points_lincomb_g2", "hk_points_fold_g2", "hk_points_fold_g1", "hk_points_fold_many_g1", "hk_points_fold_many_g2", "hk_pairing_pairs", "hk_keccak_f1600", "hk_assignment_from_bits", "hk_wprog_upload", "hk_wprog_free", "hk_wprog_run", "hk_gt_pow", "hk_fq12_pow", "hk_gt_pow_prod", "hk_poseidon_path", "hk_assignment_scatter", "hk_commit_batch",
-           "hk_prove_batch"]
+           "hk_prove_batch", "hk_vk_prepare", "hk_vk_free", "hk_vk_alpha_beta", "hk_verify_batch", "hk_points_check_g1",
+           "hk_points_check_g2"]
+
+HK_VERIFY_CHECK_POINTS = 1
+VERDICT_REJECT, VERDICT_ACCEPT, VERDICT_BAD_POINT = 0, 1, 2
 
 _lib = None
 
@@ -144,6 +153,13 @@ def load():
     lib.hk_commit_batch.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp]
     lib.hk_prove.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp]
     lib.hk_prove_batch.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, sz, vp, vp, vp]
+    lib.hk_vk_prepare.argtypes = [vp, C.POINTER(hk_vk_desc), C.POINTER(vp)]
+    lib.hk_vk_free.argtypes = [vp]
+    lib.hk_vk_free.restype = None
+    lib.hk_vk_alpha_beta.argtypes = [vp, vp]
+    lib.hk_verify_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, C.c_uint, vp, vp]
+    lib.hk_points_check_g1.argtypes = [vp, vp, sz, vp]
+    lib.hk_points_check_g2.argtypes = [vp, vp, sz, vp]
     _lib = lib
     return lib
 
@@ -500,6 +516,30 @@ class Context:
               "hk_witness_map")
         return out, m_out.value
 
+    def points_check(self, group, pts, n=None):
+        """hk_points_check_g1 / _g2: ark's AffineRepr::check of each point (on its curve, in the prime-order subgroup;
+        infinity passes).  pts: packed affine bytes (uint8 array or DeviceBuffer).  Returns np.uint8[n] of 0 / 1."""
+        pb = self.g1_bytes if group == 1 else self.g2_bytes
+        n = n if n is not None else len(pts) // pb
+        ok = np.zeros(n, dtype=np.uint8)
+        fn = self.lib.hk_points_check_g1 if group == 1 else self.lib.hk_points_check_g2
+        check(fn(self.handle, ptr(pts) if n else None, n, ok.ctypes.data), fn.__name__)
+        return ok
+
+    def vk_prepare(self, *, alpha_g, beta_h, gamma_h, deltas_h, gamma_abc_g):
+        """hk_vk_prepare (prepare_verifying_key, verifier.rs:7-18).  deltas_h: the stage deltas then delta_last, packed G2
+        bytes; gamma_abc_g: packed G1 bytes.  Returns a DeviceVk."""
+        arrs = [np.ascontiguousarray(x, dtype=np.uint8).reshape(-1) for x in (alpha_g, beta_h, gamma_h, deltas_h, gamma_abc_g)]
+        if len(arrs[0]) != self.g1_bytes or len(arrs[1]) != self.g2_bytes or len(arrs[2]) != self.g2_bytes:
+            raise HekatonError(HK_ERR_LEN, "hk_vk_prepare")
+        if len(arrs[3]) % self.g2_bytes or len(arrs[4]) % self.g1_bytes:
+            raise HekatonError(HK_ERR_LEN, "hk_vk_prepare")
+        d = hk_vk_desc(arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[2].ctypes.data, arrs[3].ctypes.data,
+                       len(arrs[3]) // self.g2_bytes, arrs[4].ctypes.data, len(arrs[4]) // self.g1_bytes)
+        h = C.c_void_p()
+        check(self.lib.hk_vk_prepare(self.handle, C.byref(d), C.byref(h)), "hk_vk_prepare")
+        return DeviceVk(self, h, d.n_deltas, d.n_abc)
+
     def pk_upload(self, *, a_g, b_g, b_h, h_g, ck_stages, deltas_g, last_delta_h, alpha_g, beta_g, beta_h,
                   matrices=None, n_inst=0, n_constraints=0):
         """hk_pk_upload: all arguments packed-affine numpy uint8 arrays (or DeviceBuffers with explicit
@@ -595,6 +635,64 @@ class ResidentBases:
         if self.handle:
             self.ctx.lib.hk_bases_free(self.handle)
             self.handle = None
+
+
+class DeviceVk:
+    """hk_vk wrapper: a prepared verifying key (PreparedVerifyingKey, verifier.rs:7-18) resident in HBM."""
+
+    def __init__(self, ctx, handle, n_deltas, n_abc):
+        self.ctx = ctx
+        self.handle = handle
+        self.n_deltas, self.n_abc = n_deltas, n_abc
+
+    def free(self):
+        if self.handle:
+            self.ctx.lib.hk_vk_free(self.handle)
+            self.handle = None
+
+    def alpha_beta(self):
+        """e(alpha, beta) in the GT layout of Context.multi_pairing."""
+        out = np.zeros(self.ctx.gt_bytes, dtype=np.uint8)
+        check(self.ctx.lib.hk_vk_alpha_beta(self.handle, out.ctypes.data), "hk_vk_alpha_beta")
+        return out
+
+    def check_args(self, n, a, b, c, ds, inputs, rand=None):
+        """The length checks of verify(), before any device call: HekatonError(HK_ERR_LEN) for a length that does not
+        match n proofs of this key (verifier.rs:53-55 MalformedVerifyingKey for the inputs), ValueError for a zero r."""
+        ctx = self.ctx
+        nd, nk = self.n_deltas - 1, self.n_abc - 1
+        for arr, per in ((a, ctx.g1_bytes), (b, ctx.g2_bytes), (c, ctx.g1_bytes), (ds, nd * ctx.g1_bytes),
+                         (inputs, nk * ctx.fr_bytes)):
+            size = arr.nbytes if isinstance(arr, DeviceBuffer) else (0 if arr is None else np.asarray(arr).nbytes)
+            if size != n * per:
+                raise HekatonError(HK_ERR_LEN, "hk_verify_batch")
+        if rand is not None:
+            rr = np.ascontiguousarray(rand, dtype=np.uint8).reshape(-1)
+            if len(rr) != n * ctx.fr_bytes:
+                raise HekatonError(HK_ERR_LEN, "hk_verify_batch")
+            if (rr.reshape(n, ctx.fr_bytes) == 0).all(axis=1).any():
+                raise ValueError("batch verification needs nonzero r_i")
+
+    def verify(self, a, b, c, ds, inputs, n=None, check_points=True, rand=None, verdicts=None):
+        """hk_verify_batch: one verdict per proof (VERDICT_ACCEPT / _REJECT / _BAD_POINT).  a, c: n G1; b: n G2;
+        ds: n x (n_deltas - 1) G1; inputs: n x (n_abc - 1) Fr Montgomery; all packed bytes, row after row (uint8 arrays
+        or DeviceBuffers).  rand: None (per-proof mode) or n nonzero Fr Montgomery (batch mode; needs check_points).
+        verdicts: optional DeviceBuffer of n bytes to write to instead of a new host array."""
+        ctx = self.ctx
+        if n is None:
+            n = (a.nbytes if isinstance(a, DeviceBuffer) else np.asarray(a).nbytes) // ctx.g1_bytes
+        ds = ds if ds is not None else np.zeros(0, dtype=np.uint8)
+        inputs = inputs if inputs is not None else np.zeros(0, dtype=np.uint8)
+        self.check_args(n, a, b, c, ds, inputs, rand)
+        keep = [x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8) for x in (a, b, c, ds, inputs)]
+        rr = None if rand is None else np.ascontiguousarray(rand, dtype=np.uint8).reshape(-1)
+        out = verdicts if verdicts is not None else np.zeros(n, dtype=np.uint8)
+        flags = HK_VERIFY_CHECK_POINTS if check_points else 0
+        nz = lambda x: ptr(x) if n and (x.nbytes if isinstance(x, DeviceBuffer) else x.size) else None
+        check(ctx.lib.hk_verify_batch(ctx.handle, self.handle, nz(keep[0]), nz(keep[1]), nz(keep[2]), nz(keep[3]),
+                                      nz(keep[4]), n, flags, None if rr is None else rr.ctypes.data, ptr(out)),
+              "hk_verify_batch")
+        return out
 
 
 class DevicePk:

@@ -551,3 +551,68 @@ def trapdoor_verify(ctx, curve, td, n_inst, stage_ranges, z, h, comms, kappas, r
     lhs = log_a * log_b % mod
     rhs = (td.alpha * td.beta + ic * td.gamma + sum(d * dk for d, dk in zip(d_logs, td.deltas)) + log_c * dl) % mod
     assert lhs == rhs, "Groth16 verifier equation (verifier.rs:23-43) does not hold in the exponent"
+
+
+# --------------------------------------------------------------------------------------- verifier (verifier.rs)
+@dataclass
+class PreparedVerifyingKey:    # data_structures.rs PreparedVerifyingKey: the key, e(alpha, beta) and the lines of -gamma, -delta_j
+    vk: VerifyingKey
+    curve: str
+    device: object             # capi.DeviceVk
+
+    def alpha_beta_gt(self):
+        return self.device.alpha_beta()
+
+    def free(self):
+        self.device.free()
+
+
+def prepare_verifying_key(ctx, vk):
+    """verifier.rs:7-18 on the device (hk_vk_prepare).  vk.deltas_h holds the stage deltas followed by delta_last."""
+    dev = ctx.vk_prepare(alpha_g=vk.alpha_g, beta_h=vk.beta_h, gamma_h=vk.gamma_h, deltas_h=vk.deltas_h,
+                         gamma_abc_g=vk.gamma_abc_g)
+    return PreparedVerifyingKey(vk, ctx.curve, dev)
+
+
+def _draw_r(rng, r_mod):
+    """A nonzero 128-bit batching scalar from `rng` (SeededRng, random.Random or anything with getrandbits / bytes)."""
+    while True:
+        v = rng.getrandbits(128) if hasattr(rng, "getrandbits") else int.from_bytes(rng.bytes(16), "little")
+        if v % r_mod:
+            return v
+
+
+def verify_proofs(pvk, proofs, inputs, batch_rng=None):
+    """verify_proof (verifier.rs:64-71) for many proofs of one key in one call.  inputs: one list of public inputs (ints)
+    per proof.  Returns one verdict per proof: 1 accepted, 0 rejected, 2 a proof point off its curve or outside the
+    prime-order subgroup.  batch_rng: draw nonzero 128-bit r_i from it and check one randomised equation first
+    (hk_verify_batch batch mode; a failing batch is verified proof by proof)."""
+    ctx = pvk.device.ctx
+    n = len(proofs)
+    if len(inputs) != n:
+        raise ValueError("one list of public inputs per proof")
+    nk = pvk.device.n_abc - 1
+    for x in inputs:
+        if len(x) != nk:                                   # verifier.rs:53-55
+            raise capi.HekatonError(capi.HK_ERR_LEN, "verify_proof (MalformedVerifyingKey)")
+    nd = pvk.device.n_deltas - 1
+    for p in proofs:
+        if len(p.ds) != nd:
+            raise capi.HekatonError(capi.HK_ERR_LEN, "hk_verify_batch")
+    if n == 0:
+        return []
+    fc = FrCodec(pvk.curve)
+    cat = lambda xs: np.concatenate([np.asarray(x, np.uint8).reshape(-1) for x in xs]) if xs else np.zeros(0, np.uint8)
+    a, b, c = cat([p.a for p in proofs]), cat([p.b for p in proofs]), cat([p.c for p in proofs])
+    ds = cat([d for p in proofs for d in p.ds])
+    xs = fc.enc([v for x in inputs for v in x]) if nk else np.zeros(0, np.uint8)
+    rand = None
+    if batch_rng is not None:
+        rand = fc.enc([_draw_r(batch_rng, fc.r) for _ in range(n)])
+    return [int(v) for v in pvk.device.verify(a, b, c, ds, xs, n=n, check_points=True, rand=rand)]
+
+
+def verify_proof(pvk, proof, public_inputs):
+    """verifier.rs:64-71: True iff the proof satisfies the verifier's equation (a point off its curve or outside the
+    prime-order subgroup is a rejection too)."""
+    return verify_proofs(pvk, [proof], [list(public_inputs)])[0] == capi.VERDICT_ACCEPT

@@ -155,6 +155,8 @@ struct Ops {
         if (b > m) m = b;
         b = PairRun<typename Fq::Params>::max_private_bytes();
         if (b > m) m = b;
+        b = VerifyRun<typename Fq::Params>::max_private_bytes();
+        if (b > m) m = b;
         b = finish_private_bytes();
         return b > m ? b : m;
     }
@@ -169,7 +171,9 @@ struct Ops {
                                    &bases_free, &msm_bases, &pairing_products,
                                    sizeof(Fp12<typename Fq::Params>), &points_lincomb, &points_fold_g2, &points_fold_g1, &assignment_from_bits, &wprog_upload, &wprog_free, &wprog_run, &gt_pow,
                                    &max_private_bytes, &poseidon_path, &points_fold_many, &pairing_pairs, &assignment_scatter, &commit_batch,
-                                   &prove_batch};
+                                   &prove_batch, &VerifyRun<typename Fq::Params>::vk_prepare, &VerifyRun<typename Fq::Params>::vk_free,
+                                   &VerifyRun<typename Fq::Params>::vk_alpha_beta, &VerifyRun<typename Fq::Params>::verify_batch,
+                                   &VerifyRun<typename Fq::Params>::points_check};
         return &t;
     }
 };

@@ -498,6 +498,30 @@ hk_status hk_multi_pairing(hk_ctx* ctx, const void* g1, const void* g2, size_t n
     const void* r[1] = {n ? g2 : (const void*)gt_out};
     return ctx->ops->pairing_products(ctx, l, 1, r, 1, n, gt_out);
 }
+hk_status hk_vk_prepare(hk_ctx* ctx, const hk_vk_desc* desc, hk_vk** out) {
+    if (!ctx || !desc || !out) return HK_ERR_ARG;
+    return ctx->ops->vk_prepare(ctx, desc, out);
+}
+void hk_vk_free(hk_vk* vk) {
+    if (vk) vk->ops->vk_free(vk);
+}
+hk_status hk_vk_alpha_beta(const hk_vk* vk, void* gt_out) {
+    if (!vk || !gt_out) return HK_ERR_ARG;
+    return vk->ops->vk_alpha_beta(vk, gt_out);
+}
+hk_status hk_verify_batch(hk_ctx* ctx, const hk_vk* vk, const void* a_g1, const void* b_g2, const void* c_g1, const void* ds_g1,
+                          const void* inputs_mont, size_t n, unsigned flags, const void* rand_mont, uint8_t* verdicts) {
+    if (!ctx || !vk || vk->ctx != ctx) return HK_ERR_ARG;
+    return ctx->ops->verify_batch(ctx, vk, a_g1, b_g2, c_g1, ds_g1, inputs_mont, n, flags, rand_mont, verdicts);
+}
+hk_status hk_points_check_g1(hk_ctx* ctx, const void* points, size_t n, uint8_t* ok) {
+    if (!ctx || (n && (!points || !ok))) return HK_ERR_ARG;
+    return ctx->ops->points_check(ctx, 1, points, n, ok);
+}
+hk_status hk_points_check_g2(hk_ctx* ctx, const void* points, size_t n, uint8_t* ok) {
+    if (!ctx || (n && (!points || !ok))) return HK_ERR_ARG;
+    return ctx->ops->points_check(ctx, 2, points, n, ok);
+}
 hk_status hk_ctx_gt_bytes(const hk_ctx* ctx, size_t* gt) {
     if (!ctx || !gt) return HK_ERR_ARG;
     *gt = ctx->ops->gt_bytes;

@@ -143,6 +143,12 @@ struct CurveOps {
                               void* out);
     hk_status (*prove_batch)(hk_ctx*, const hk_pk*, const void* z, size_t n_v, const void* r, const void* s,
                              const void* kappas, size_t n_kappas, size_t batch, void* a, void* b, void* c);
+    hk_status (*vk_prepare)(hk_ctx*, const hk_vk_desc*, hk_vk**);
+    void (*vk_free)(hk_vk*);
+    hk_status (*vk_alpha_beta)(const hk_vk*, void*);
+    hk_status (*verify_batch)(hk_ctx*, const hk_vk*, const void* a, const void* b, const void* c, const void* ds, const void* inputs,
+                              size_t n, unsigned flags, const void* rand, unsigned char* verdicts);
+    hk_status (*points_check)(hk_ctx*, int group, const void* pts, size_t n, unsigned char* ok);
 };
 const CurveOps* curve_ops_bn254();
 const CurveOps* curve_ops_bls381();
@@ -170,6 +176,12 @@ struct hk_ctx {
 };
 
 struct hk_pk {
+    const hk::CurveOps* ops;
+    hk_ctx* ctx;
+    void* impl;
+};
+
+struct hk_vk {                     // a prepared verifying key (verify.cuh VkImpl)
     const hk::CurveOps* ops;
     hk_ctx* ctx;
     void* impl;

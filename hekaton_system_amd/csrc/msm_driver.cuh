@@ -105,4 +105,17 @@ struct PairRun {
     static hk_status gt_prod(hipStream_t s, const Fp12<P>* in, u32 len, u32 groups, Fp12<P>* out);
 };
 
+// CP-Groth16 verification (verify.cuh): the hk_vk_* / hk_verify_batch / hk_points_check_* entry points of a curve;
+// explicit instantiation in hk_<curve>_pair.hip
+template <class P>
+struct VerifyRun {
+    static hk_status vk_prepare(hk_ctx*, const hk_vk_desc*, hk_vk**);
+    static void vk_free(hk_vk*);
+    static hk_status vk_alpha_beta(const hk_vk*, void* gt_out);
+    static hk_status verify_batch(hk_ctx*, const hk_vk*, const void* a, const void* b, const void* c, const void* ds,
+                                  const void* inputs, size_t n, unsigned flags, const void* rand, unsigned char* verdicts);
+    static hk_status points_check(hk_ctx*, int group, const void* pts, size_t n, unsigned char* ok);
+    static size_t max_private_bytes();
+};
+
 }  // namespace hk

@@ -37,7 +37,8 @@ extern "C" {
 #endif
 
 typedef struct hk_ctx hk_ctx;   /* one per (process, device): lanes, twiddles, scratch */
-typedef struct hk_pk hk_pk;     /* device-resident proving-key class (+ its R1CS matrices) */
+typedef struct hk_pk hk_pk;
+typedef struct hk_vk hk_vk;     /* prepared verifying key (hk_vk_prepare) */     /* device-resident proving-key class (+ its R1CS matrices) */
 
 typedef enum { HK_BN254 = 0, HK_BLS12_381 = 1 } hk_curve;
 
@@ -371,6 +372,52 @@ hk_status hk_prove(hk_ctx* ctx, const hk_pk* pk, const void* z_mont, size_t n_v,
 hk_status hk_prove_batch(hk_ctx* ctx, const hk_pk* pk, const void* z_mont, size_t n_v,
                          const void* r_mont, const void* s_mont, const void* kappas_mont, size_t n_kappas,
                          size_t batch, void* proofs_a_g1, void* proofs_b_g2, void* proofs_c_g1);
+
+/* ---- CP-Groth16 proof verification (cp-groth16/src/verifier.rs) ------------------------------------------------- */
+
+/* A verifying key (data_structures.rs:33-46), every point [h|d] packed affine: deltas_h[n_deltas] are the stage deltas
+ * followed by delta_last; gamma_abc_g[n_abc] the input bases.  A proof of this key carries n_deltas - 1 commitments D
+ * and n_abc - 1 public inputs. */
+typedef struct {
+    const void* alpha_g;
+    const void* beta_h;
+    const void* gamma_h;
+    const void* deltas_h;
+    size_t n_deltas;
+    const void* gamma_abc_g;
+    size_t n_abc;
+} hk_vk_desc;
+
+/* prepare_verifying_key (verifier.rs:7-18): uploads the key, computes e(alpha, beta) on the device and keeps the Miller
+ * lines of -gamma and of every -delta_j (ark's G2Prepared), so that verification never runs them again.  HK_ERR_LEN for
+ * n_deltas == 0 or n_abc == 0. */
+hk_status hk_vk_prepare(hk_ctx* ctx, const hk_vk_desc* desc, hk_vk** out);
+void      hk_vk_free(hk_vk* vk);
+/* PreparedVerifyingKey.alpha_beta_gt in the GT layout of hk_multi_pairing (gt_out [h|d], hk_ctx_gt_bytes bytes) */
+hk_status hk_vk_alpha_beta(const hk_vk* vk, void* gt_out);
+
+#define HK_VERIFY_CHECK_POINTS 1u   /* validate A, B, C and every D first (ark AffineRepr::check) */
+#define HK_VERDICT_REJECT    0      /* the verifier's equation fails */
+#define HK_VERDICT_ACCEPT    1
+#define HK_VERDICT_BAD_POINT 2      /* a proof point is off its curve or outside the prime-order subgroup */
+
+/* verify_proof (verifier.rs:64-71) for n proofs of one key, one verdict byte each (HK_VERDICT_*):
+ *   a, c [h|d] n G1; b [h|d] n G2; ds [h|d] n x (n_deltas - 1) G1, row after row; inputs_mont [h|d] n x (n_abc - 1) Fr
+ *   (Montgomery), row after row; verdicts [h|d] n bytes.
+ * rand_mont == NULL: per-proof mode, the exact equation of every proof.  rand_mont [h|d]: n nonzero Fr (Montgomery),
+ * batch mode: one randomised equation
+ *   prod e(r_i A_i, B_i) e(sum r_i IC_i, -gamma) prod_j e(sum r_i D_ij, -delta_j) e(sum r_i C_i, -delta_last)
+ *     == e(alpha, beta)^(sum r_i)
+ * per chunk of proofs; all verdicts are 1 when it holds, else that chunk is verified per proof.  Batch mode requires
+ * HK_VERIFY_CHECK_POINTS (HK_ERR_ARG otherwise).  A pair with a member at infinity contributes 1; infinity passes the
+ * point check.  Returns HK_OK whatever the verdicts; n == 0 does nothing. */
+hk_status hk_verify_batch(hk_ctx* ctx, const hk_vk* vk, const void* a_g1, const void* b_g2, const void* c_g1,
+                          const void* ds_g1, const void* inputs_mont, size_t n, unsigned flags, const void* rand_mont,
+                          uint8_t* verdicts);
+/* ok[i] = 1 when points[i] is on its curve and in the prime-order subgroup (or infinity), else 0 (ark's AffineRepr::check,
+ * what deserialize_* with Validate::Yes runs).  points [h|d] n packed affine, ok [h|d] n bytes. */
+hk_status hk_points_check_g1(hk_ctx* ctx, const void* points, size_t n, uint8_t* ok);
+hk_status hk_points_check_g2(hk_ctx* ctx, const void* points, size_t n, uint8_t* ok);
 
 #ifdef __cplusplus
 }
