@@ -7,23 +7,6 @@
 
 namespace hk {
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// device bytes of MsmSort::alloc / MsmRun::alloc for `nb` proofs side by side
-inline size_t msm_sort_bytes(const MsmPlan& p, size_t nb = 1) {
-    return al256(4ull * p.NB * nb) * 2 + al256(4ull * (p.NB + 1) * nb) + al256(4ull * msm_sorted_stride(p) * nb) +
-           al256(2ull * msm_digits_stride(p) * nb) + 1024;
-}
-template <class F>
-inline size_t msm_run_bytes(const MsmPlan& p0, size_t nb = 1) {
-    MsmPlan p = p0;
-    msm_set_lanes(p, (u32)(4u * 65536u / nb));   // upper bound over the per-flavour lane schedules (msm_lane_plan)
-    size_t n0 = 2ull * p.T[0], n1 = msm_p1_stride(p);
-    return al256(sizeof(XYZZ<F>) * (p.NB + 1) * nb) + al256(4 * n0 * nb) + al256(sizeof(XYZZ<F>) * n0 * nb) +
-           al256(4 * n1 * nb) + al256(sizeof(XYZZ<F>) * n1 * nb) + al256(sizeof(XYZZ<F>) * p.WP * (p.B / p.K) * nb) +
-           al256(sizeof(XYZZ<F>) * p.WP * nb) + 2048;
-}
-
 // window size for an MSM over caller-supplied bases (no shift tables: all W windows keep their own
 // buckets, W * 2^(c-1) counters must fit the 128 KiB LDS histogram)
 inline u32 msm_pick_c_plain(size_t n, u32 fr_bits) {
@@ -56,6 +39,45 @@ struct Ops {
     typedef typename C::Fq Fq;
     typedef typename C::Fq2 Fq2;
 
+    // One MSM into the affine point `out` on the lane's stream: n element-wise products over the endomorphism and one sum
+    // (MsmRun::small_msm) when `small`, else the digit sort and the bucket pass over plan *p.  carve() lists its scratch
+    // inside the caller's Lane::carve; run() takes n scalars and n bases (group 0 of a table) on the device.
+    template <class F>
+    struct OneMsm {
+        bool small;
+        const MsmPlan* p;
+        u32 n;
+        XYZZ<F>*xy, *tab, *res;
+        Affine<F>* aff;
+        SortBufs sb;
+        typename MsmRun<F>::Bufs rb;
+
+        void carve(Carve& c) {
+            if (small) {
+                xy = c.n<XYZZ<F>>(n);
+                tab = (XYZZ<F>*)c.take(endo_tab_bytes<F>(n));
+            } else {
+                MsmSort<Fr>::alloc(c, *p, &sb);
+                MsmRun<F>::alloc(c, *p, &rb);
+            }
+            res = c.n<XYZZ<F>>(1);
+            aff = c.n<Affine<F>>(1);
+        }
+        // ev0 / ev1 (optional) bracket the bucket-accumulate launch
+        hk_status run(hipStream_t s, const Affine<F>* bases, const void* scalars, int mont, void* out, hipMemcpyKind kind,
+                      hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) const {
+            if (small) {
+                HK_TRY(MsmRun<F>::small_msm(s, bases, scalars, mont, n, tab, xy, res));
+            } else {
+                HK_TRY(MsmSort<Fr>::run(s, *p, (const u32*)scalars, mont, sb));
+                HK_TRY(MsmRun<F>::run(s, *p, bases, n, 0, sb, rb, res, ev0, ev1));
+            }
+            HK_TRY(MsmRun<F>::to_affine(s, res, aff, 1));
+            HK_HIP(hipMemcpyAsync(out, aff, sizeof(Affine<F>), kind, s));
+            return HK_OK;
+        }
+    };
+
     template <class F>
     static hk_status msm_plain(hk_ctx* ctx, const void* bases, size_t n_bases, const void* scalars,
                                size_t n_scalars, int mont, int checked, void* out) {
@@ -67,46 +89,19 @@ struct Ops {
         LaneGuard g(ctx);
         Lane* L = g.lane;
         if (!L) return HK_ERR_DEVICE;
-        if (n * EndoOf<F>::K <= SPLIT_MAX_LANES && !getenv("HK_MSM_NO_SMALL")) {
-            // short vector, no tables: a Pippenger pass would end in ~254 serial doublings (3 / 8.5 ms whatever n)
-            size_t need = al256(n * sizeof(Fr)) + al256(n * sizeof(Affine<F>)) + al256(n * sizeof(XYZZ<F>)) +
-                          al256(endo_tab_bytes<F>(n)) + al256(sizeof(XYZZ<F>)) + al256(sizeof(Affine<F>)) + 4096;
-            HK_TRY(L->reserve(need));
-            const void *sc_d, *b_d;
-            HK_TRY(to_device(L, scalars, n * sizeof(Fr), &sc_d));
-            HK_TRY(to_device(L, bases, n * sizeof(Affine<F>), &b_d));
-            XYZZ<F>* xy = L->alloc_n<XYZZ<F>>(n);
-            XYZZ<F>* tab = (XYZZ<F>*)L->alloc_n<unsigned char>(endo_tab_bytes<F>(n));
-            XYZZ<F>* res = L->alloc_n<XYZZ<F>>(1);
-            Affine<F>* aff = L->alloc_n<Affine<F>>(1);
-            if (!xy || !tab || !res || !aff) return HK_ERR_NOMEM;
-            HK_TRY(MsmRun<F>::small_msm(L->stream, (const Affine<F>*)b_d, sc_d, mont, (u32)n, tab, xy, res));
-            HK_TRY(MsmRun<F>::to_affine(L->stream, res, aff, 1));
-            HK_HIP(hipMemcpyAsync(out, aff, sizeof(Affine<F>), hipMemcpyDeviceToHost, L->stream));
-            HK_HIP(hipStreamSynchronize(L->stream));
-            return HK_OK;
-        }
-        u32 c = msm_pick_c_plain(n, C::FR_BITS);
-        MsmPlan p = msm_make_plan((u32)n, C::FR_BITS, c, 0xffffffffu, ctx->max_lanes0, C::Fr::Params::MOD, C::Fr::Params::N);
-        size_t need = al256(n * sizeof(Fr)) + al256(n * sizeof(Affine<F>)) + msm_sort_bytes(p) +
-                      msm_run_bytes<F>(p) + al256(sizeof(XYZZ<F>)) + al256(sizeof(Affine<F>)) + 4096;
-        HK_TRY(L->reserve(need));
+        // short vector, no tables: a Pippenger pass would end in ~254 serial doublings (3 / 8.5 ms whatever n)
+        const bool small = n * EndoOf<F>::K <= SPLIT_MAX_LANES && !getenv("HK_MSM_NO_SMALL");
+        MsmPlan p;
+        if (!small)
+            p = msm_make_plan((u32)n, C::FR_BITS, msm_pick_c_plain(n, C::FR_BITS), 0xffffffffu, ctx->max_lanes0, C::Fr::Params::MOD,
+                              C::Fr::Params::N);
+        OneMsm<F> msm{small, &p, (u32)n};
         const void *sc_d, *b_d;
+        HK_TRY(L->carve([&](Carve& c) { sc_d = c.take(n * sizeof(Fr)); b_d = c.take(n * sizeof(Affine<F>)); msm.carve(c); }));
         HK_TRY(to_device(L, scalars, n * sizeof(Fr), &sc_d));
         HK_TRY(to_device(L, bases, n * sizeof(Affine<F>), &b_d));
-        SortBufs sb;
-        HK_TRY(MsmSort<Fr>::alloc(L, p, &sb));
-        typename MsmRun<F>::Bufs rb;
-        HK_TRY(MsmRun<F>::alloc(L, p, &rb));
-        XYZZ<F>* res = L->alloc_n<XYZZ<F>>(1);
-        Affine<F>* aff = L->alloc_n<Affine<F>>(1);
-        if (!res || !aff) return HK_ERR_NOMEM;
-        HK_TRY(MsmSort<Fr>::run(L->stream, p, (const u32*)sc_d, mont, sb));
-        HK_TRY(MsmRun<F>::run(L->stream, p, (const Affine<F>*)b_d, (u32)n, 0, sb, rb, res, nullptr, nullptr));
-        HK_TRY(MsmRun<F>::to_affine(L->stream, res, aff, 1));
-        HK_HIP(hipMemcpyAsync(out, aff, sizeof(Affine<F>), hipMemcpyDeviceToHost, L->stream));
-        HK_HIP(hipStreamSynchronize(L->stream));
-        return HK_OK;
+        HK_TRY(msm.run(L->stream, (const Affine<F>*)b_d, sc_d, mont, out, hipMemcpyDeviceToHost));
+        return L->settle();
     }
 
     static hk_status msm(hk_ctx* ctx, int group, const void* bases, size_t n_bases, const void* scalars,

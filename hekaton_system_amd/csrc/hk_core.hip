@@ -104,13 +104,13 @@ hk_status scratch_budget_check(const CurveOps* ops, const hipDeviceProp_t& prop,
 static thread_local hk_timings tl_last_timings = {};
 
 hk_status Lane::reserve(size_t bytes) {
-    arena_off = 0;
     if (bytes <= arena_cap) return HK_OK;
     HK_HIP(hipStreamSynchronize(stream));
     if (owner) {
         // an idle lane of the context may hold an arena that is large enough (an earlier call of this size ran there):
         // trade arenas with it - the smallest that fits - instead of allocating (a hipMalloc of tens of MB takes
-        // milliseconds, and which lane a call lands on is arbitrary).  An idle lane's stream has nothing in flight.
+        // milliseconds, and which lane a call lands on is arbitrary).  An idle lane's streams have nothing in flight:
+        // ~LaneGuard drains them before it marks a lane free.
         std::lock_guard<std::mutex> lk(owner->mu);
         Lane* best = nullptr;
         for (Lane* l : owner->lanes)
@@ -196,13 +196,19 @@ LaneGuard::LaneGuard(hk_ctx* c) : ctx(c), lane(nullptr) {
         }
         ctx->cv.wait(lk);
     }
-    if (lane) { lane->busy = true; lane->owner = ctx; }
+    if (lane) { lane->busy = true; lane->settled = false; lane->owner = ctx; }
     lk.unlock();
     (void)hipSetDevice(ctx->device);
 }
 
 LaneGuard::~LaneGuard() {
     if (!lane) return;
+    if (!lane->settled) {
+        // an error return (HK_TRY / HK_HIP) may leave kernels queued on the arena: another call may take this lane, or
+        // trade arenas with it in reserve(), once it is free
+        (void)hipStreamSynchronize(lane->stream);
+        for (auto& a : lane->aux) (void)hipStreamSynchronize(a);
+    }
     std::unique_lock<std::mutex> lk(ctx->mu);
     lane->busy = false;
     ctx->last = lane->timings;
@@ -228,13 +234,9 @@ bool is_device_ptr(const void* p) {
     return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
 }
 
-hk_status to_device(Lane* L, const void* p, size_t bytes, const void** out) {
-    if (bytes == 0) { *out = p; return HK_OK; }
-    if (is_device_ptr(p)) { *out = p; return HK_OK; }
-    void* d = L->alloc(bytes);
-    if (!d) return HK_ERR_NOMEM;
-    HK_HIP(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, L->stream));
-    *out = d;
+hk_status to_device(Lane* L, const void* src, size_t bytes, const void** p) {
+    if (bytes == 0 || is_device_ptr(src)) { *p = src; return HK_OK; }
+    HK_HIP(hipMemcpyAsync((void*)*p, src, bytes, hipMemcpyHostToDevice, L->stream));
     return HK_OK;
 }
 
@@ -306,7 +308,6 @@ void hk_ctx_destroy(hk_ctx* ctx) {
     for (Lane* l : ctx->lanes) {
         if (l->arena) (void)hipFree(l->arena);
         for (void* p : l->retired) (void)hipFree(p);
-        if (l->pinned) (void)hipHostFree(l->pinned);
         for (auto& e : l->ev) (void)hipEventDestroy(e);
         for (auto& a : l->aux) if (a) (void)hipStreamDestroy(a);
         (void)hipStreamDestroy(l->stream);

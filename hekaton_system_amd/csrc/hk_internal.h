@@ -59,29 +59,56 @@ template <> struct ScalarOf<CurveBn254::Fq2> { typedef CurveBn254::Fr type; };
 template <> struct ScalarOf<CurveBls381::Fq> { typedef CurveBls381::Fr type; };
 template <> struct ScalarOf<CurveBls381::Fq2> { typedef CurveBls381::Fr type; };
 
+// ---- scratch carving -------------------------------------------------------------------------------------
+// A call lists its scratch buffers once, as a function of a Carve, and Lane::carve walks that list twice: without a base the
+// cursor only counts bytes, with one it hands out 256-B aligned slices of it.
+struct Carve {
+    char* base = nullptr;
+    size_t off = 0;
+    void* take(size_t bytes) {
+        size_t o = (off + 255) & ~(size_t)255;
+        off = o + bytes;
+        return base ? base + o : nullptr;
+    }
+    template <class T> T* n(size_t count) { return (T*)take(count * sizeof(T)); }
+};
+
 // ---- per-call lane: one stream + one grow-only scratch arena ---------------------------------------
 struct Lane {
     hipStream_t stream = nullptr;
     char* arena = nullptr;
     size_t arena_cap = 0;
-    size_t arena_off = 0;
-    void* pinned = nullptr;       // small host staging buffer
-    size_t pinned_cap = 0;
     hipEvent_t ev[32];
     hipStream_t aux[4] = {nullptr, nullptr, nullptr, nullptr};   // fork/join side streams of hk_prove
     bool busy = false;
+    bool settled = false;         // nothing queued since the last settle(): ~LaneGuard need not drain the streams
     hk_timings timings;
     std::vector<void*> retired;   // outgrown arenas: freed when no call is in flight (hipFree waits for the whole device)
     hk_ctx* owner = nullptr;      // the context the lane belongs to (reserve() may trade arenas with an idle lane of it)
 
-    hk_status reserve(size_t bytes);                 // ensure capacity (may sync + realloc), reset
-    void* alloc(size_t bytes) {                      // bump allocation, 256-B aligned
-        size_t off = (arena_off + 255) & ~(size_t)255;
-        if (off + bytes > arena_cap) return nullptr;
-        arena_off = off + bytes;
-        return arena + off;
+    hk_status reserve(size_t bytes);                 // ensure capacity (may sync + realloc)
+    // the call's scratch: fn(Carve&) runs once counting, then - after reserve(total) - once on the arena.  fn only carves
+    // (no HIP call, no getenv / is_device_ptr: decide those before and capture the result), and both passes must agree.
+    template <class Fn> hk_status carve(Fn&& fn) {
+        Carve count;
+        fn(count);
+        HK_TRY(reserve(count.off));
+        Carve real;
+        real.base = arena;
+        fn(real);
+        if (real.off != count.off) {
+            fprintf(stderr, "[hekaton] scratch carve is not deterministic (%zu bytes counted, %zu carved)\n", count.off, real.off);
+            return HK_ERR_DEVICE;
+        }
+        settled = false;                             // work on the new slices follows
+        return HK_OK;
     }
-    template <class T> T* alloc_n(size_t n) { return (T*)alloc(n * sizeof(T)); }
+    // the call's final synchronize: the lane is idle from here on
+    hk_status settle() {
+        HK_HIP(hipStreamSynchronize(stream));
+        settled = true;
+        return HK_OK;
+    }
 };
 
 struct NttTables;   // ntt.hip
@@ -216,7 +243,7 @@ struct LaneGuard {
 };
 
 bool is_device_ptr(const void* p);
-// returns a device pointer for `p` (copies host data into lane scratch when needed)
-hk_status to_device(Lane* L, const void* p, size_t bytes, const void** out);
+// *p: `bytes` of lane scratch carved for the input `src`.  A host `src` is copied there; a device `src` replaces *p.
+hk_status to_device(Lane* L, const void* src, size_t bytes, const void** p);
 
 }  // namespace hk

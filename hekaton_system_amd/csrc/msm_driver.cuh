@@ -26,7 +26,7 @@ struct SortBufs {        // device buffers produced by the counting sort
 
 template <class Fr>
 struct MsmSort {
-    static hk_status alloc(Lane* L, const MsmPlan& p, SortBufs* out, u32 batch = 1);
+    static void alloc(Carve& c, const MsmPlan& p, SortBufs* out, u32 batch = 1);
     // scalars_d: n field elements on the device (canonical, or Montgomery when is_mont); proof b's start scalar_stride
     // elements after proof b - 1's.
     // count_is_zero: the caller cleared sb.count in a kernel of its own that precedes this call in stream order
@@ -43,7 +43,7 @@ struct MsmRun {
         XYZZ<F>* red;            // [WP * B / K]
         XYZZ<F>* wsum;           // [WP]
     };
-    static hk_status alloc(Lane* L, const MsmPlan& p, Bufs* out, u32 batch = 1);
+    static void alloc(Carve& c, const MsmPlan& p, Bufs* out, u32 batch = 1);
     // table: F shift groups of n_bases affine points each.  result_d receives one XYZZ point per proof, proof b's at
     // result_d[b * res_stride].  `batch` MSMs over the same table run in lock-step, one launch per stage; the chip's
     // resident lanes are split across them (msm_lane_plan).  ev0/ev1 (optional) bracket the bucket-accumulate launch for

@@ -19,14 +19,12 @@ static inline bool hk_dbg_sync() { static const bool on = getenv("HK_DEBUG_SYNC"
     } while (0)
 
 template <class Fr>
-hk_status MsmSort<Fr>::alloc(Lane* L, const MsmPlan& p, SortBufs* out, u32 batch) {
-    out->count = L->alloc_n<u32>((size_t)p.NB * batch);
-    out->start = L->alloc_n<u32>((size_t)(p.NB + 1) * batch);
-    out->cursor = L->alloc_n<u32>((size_t)p.NB * batch);
-    out->sorted = L->alloc_n<u32>(msm_sorted_stride(p) * batch);
-    out->digits = L->alloc_n<short>(msm_digits_stride(p) * batch);
-    if (!out->count || !out->start || !out->cursor || !out->sorted || !out->digits) return HK_ERR_NOMEM;
-    return HK_OK;
+void MsmSort<Fr>::alloc(Carve& c, const MsmPlan& p, SortBufs* out, u32 batch) {
+    out->count = c.n<u32>((size_t)p.NB * batch);
+    out->start = c.n<u32>((size_t)(p.NB + 1) * batch);
+    out->cursor = c.n<u32>((size_t)p.NB * batch);
+    out->sorted = c.n<u32>(msm_sorted_stride(p) * batch);
+    out->digits = c.n<short>(msm_digits_stride(p) * batch);
 }
 
 template <class Fr>
@@ -62,19 +60,16 @@ static inline MsmPlan msm_lane_plan(const MsmPlan& p0, u32 batch = 1) {
 }
 
 template <class F>
-hk_status MsmRun<F>::alloc(Lane* L, const MsmPlan& p0, Bufs* out, u32 batch) {
+void MsmRun<F>::alloc(Carve& c, const MsmPlan& p0, Bufs* out, u32 batch) {
     const MsmPlan p = msm_lane_plan<F>(p0, batch);
     const size_t n0 = 2ull * p.T[0], n1 = msm_p1_stride(p);
-    out->buckets = L->alloc_n<XYZZ<F>>((size_t)(p.NB + 1) * batch);     // + one slot: the reduction ticket
-    out->pkeys[0] = L->alloc_n<u32>(n0 * batch);
-    out->ppts[0] = L->alloc_n<XYZZ<F>>(n0 * batch);
-    out->pkeys[1] = L->alloc_n<u32>(n1 * batch);
-    out->ppts[1] = L->alloc_n<XYZZ<F>>(n1 * batch);
-    out->red = L->alloc_n<XYZZ<F>>((size_t)p.WP * (p.B / p.K) * batch);
-    out->wsum = L->alloc_n<XYZZ<F>>((size_t)p.WP * batch);
-    if (!out->buckets || !out->pkeys[0] || !out->ppts[0] || !out->pkeys[1] || !out->ppts[1] || !out->red || !out->wsum)
-        return HK_ERR_NOMEM;
-    return HK_OK;
+    out->buckets = c.n<XYZZ<F>>((size_t)(p.NB + 1) * batch);     // + one slot: the reduction ticket
+    out->pkeys[0] = c.n<u32>(n0 * batch);
+    out->ppts[0] = c.n<XYZZ<F>>(n0 * batch);
+    out->pkeys[1] = c.n<u32>(n1 * batch);
+    out->ppts[1] = c.n<XYZZ<F>>(n1 * batch);
+    out->red = c.n<XYZZ<F>>((size_t)p.WP * (p.B / p.K) * batch);
+    out->wsum = c.n<XYZZ<F>>((size_t)p.WP * batch);
 }
 
 template <class F>

@@ -220,12 +220,12 @@ hk_status Ops<C>::ntt(hk_ctx* ctx, void* data, unsigned log_m, int inverse, int 
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
     size_t n = (size_t)1 << log_m;
-    HK_TRY(L->reserve(n * sizeof(Fr) + 4096));
+    Fr* stage;
+    HK_TRY(L->carve([&](Carve& c) { stage = c.n<Fr>(n); }));
     bool dev = is_device_ptr(data);
     Fr* d = (Fr*)data;
     if (!dev) {
-        d = L->alloc_n<Fr>(n);
-        if (!d) return HK_ERR_NOMEM;
+        d = stage;
         HK_HIP(hipMemcpyAsync(d, data, n * sizeof(Fr), hipMemcpyHostToDevice, L->stream));
     }
     hipStream_t s = L->stream;
@@ -245,8 +245,7 @@ hk_status Ops<C>::ntt(hk_ctx* ctx, void* data, unsigned log_m, int inverse, int 
         HK_TRY(N::bitrev(s, d, log_m));
     }
     if (!dev) HK_HIP(hipMemcpyAsync(data, d, n * sizeof(Fr), hipMemcpyDeviceToHost, s));
-    HK_HIP(hipStreamSynchronize(s));
-    return HK_OK;
+    return L->settle();
 }
 
 // ---- witness map on device buffers --------------------------------------------------------------------
@@ -338,31 +337,34 @@ hk_status Ops<C>::witness_map(hk_ctx* ctx, const hk_csr* A, const hk_csr* B, con
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    size_t need = 3 * m * sizeof(Fr) + n_v * sizeof(Fr) + 8192 + 256;
     const hk_csr* Ms[3] = {A, B, Cm};
-    for (auto M : Ms) need += al256(8 * (M->n_rows + 1)) + al256(4 * M->nnz) + al256(sizeof(Fr) * M->nnz);
-    HK_TRY(L->reserve(need));
+    const void *rp[3], *cl[3], *vl[3], *zd;
+    u32* flag;
+    Fr* abc;
+    HK_TRY(L->carve([&](Carve& c) {
+        for (int k = 0; k < 3; k++) {
+            rp[k] = c.take(8 * (Ms[k]->n_rows + 1));
+            cl[k] = c.take(4 * Ms[k]->nnz);
+            vl[k] = c.take(sizeof(Fr) * Ms[k]->nnz);
+        }
+        flag = c.n<u32>(1);
+        zd = c.take(n_v * sizeof(Fr));
+        abc = c.n<Fr>(3 * m);
+    }));
     CsrDev D[3];
     for (int k = 0; k < 3; k++) {
-        const void *rp, *cl, *vl;
-        HK_TRY(to_device(L, Ms[k]->row_ptr, 8 * (Ms[k]->n_rows + 1), &rp));
-        HK_TRY(to_device(L, Ms[k]->col, 4 * Ms[k]->nnz, &cl));
-        HK_TRY(to_device(L, Ms[k]->val_mont, sizeof(Fr) * Ms[k]->nnz, &vl));
-        D[k] = {(const u64*)rp, (const u32*)cl, vl, Ms[k]->n_rows, Ms[k]->nnz};
+        HK_TRY(to_device(L, Ms[k]->row_ptr, 8 * (Ms[k]->n_rows + 1), &rp[k]));
+        HK_TRY(to_device(L, Ms[k]->col, 4 * Ms[k]->nnz, &cl[k]));
+        HK_TRY(to_device(L, Ms[k]->val_mont, sizeof(Fr) * Ms[k]->nnz, &vl[k]));
+        D[k] = {(const u64*)rp[k], (const u32*)cl[k], vl[k], Ms[k]->n_rows, Ms[k]->nnz};
     }
-    u32* flag = L->alloc_n<u32>(1);
-    if (!flag) return HK_ERR_NOMEM;
     for (int k = 0; k < 3; k++) HK_TRY(csr_validate(L->stream, D[k], n_v, flag));
-    const void* zd;
     HK_TRY(to_device(L, z, n_v * sizeof(Fr), &zd));
-    Fr* abc = L->alloc_n<Fr>(3 * m);
-    if (!abc) return HK_ERR_NOMEM;
     HK_TRY(Q::run(L->stream, T, D[0], D[1], D[2], n_inst, n_c, (const Fr*)zd, abc, log_m));
     HK_TRY(NttHost<C>::bitrev(L->stream, abc, log_m));         // API returns natural order
     HK_HIP(hipMemcpyAsync(h_out, abc, m * sizeof(Fr),
                           is_device_ptr(h_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, L->stream));
-    HK_HIP(hipStreamSynchronize(L->stream));
-    return HK_OK;
+    return L->settle();
 }
 
 // ---- device-resident proving key ------------------------------------------------------------------------
@@ -744,45 +746,23 @@ hk_status Ops<C>::msm_bases(hk_ctx* ctx, const hk_bases* h, const void* scalars,
         LaneGuard g(ctx);
         Lane* L = g.lane;
         if (!L) return HK_ERR_DEVICE;
-        if (!b->has_tables || (sizeof(F) > sizeof(Fq) && n <= 2048 && !getenv("HK_MSM_NO_SMALL"))) {
-            // a short G2 MSM: even with the tables' bucket pass free of a Horner tail, n element-wise products over psi +
-            // one sum are quicker (1.9 - 2.4 ms against 2.3 - 3.0; G1 stays with the tables: 1.0 - 1.2 ms against 1.4 - 1.5)
-            HK_TRY(L->reserve(al256(n * sizeof(Fr)) + al256(n * sizeof(XYZZ<F>)) + al256(endo_tab_bytes<F>(n)) +
-                              al256(sizeof(XYZZ<F>)) + al256(sizeof(Affine<F>)) + 4096));
-            const void* sc_d;
-            HK_TRY(to_device(L, scalars, n * sizeof(Fr), &sc_d));
-            XYZZ<F>* xy = L->alloc_n<XYZZ<F>>(n);
-            XYZZ<F>* tab = (XYZZ<F>*)L->alloc_n<unsigned char>(endo_tab_bytes<F>(n));
-            XYZZ<F>* res = L->alloc_n<XYZZ<F>>(1);
-            Affine<F>* aff = L->alloc_n<Affine<F>>(1);
-            if (!xy || !tab || !res || !aff) return HK_ERR_NOMEM;
-            HK_TRY(MsmRun<F>::small_msm(L->stream, (const Affine<F>*)b->tab, sc_d, mont, (u32)n, tab, xy, res));   // group 0 of the table = the bases
-            HK_TRY(MsmRun<F>::to_affine(L->stream, res, aff, 1));
-            HK_HIP(hipMemcpyAsync(out, aff, sizeof(Affine<F>), is_device_ptr(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, L->stream));
-            HK_HIP(hipStreamSynchronize(L->stream));
-            return HK_OK;
-        }
-        const MsmPlan& p = b->plan;                                  // planned for b->n scalars; the tail reads zeros
-        size_t need = al256(b->n * sizeof(Fr)) + msm_sort_bytes(p) + msm_run_bytes<F>(p) + 8192;
-        HK_TRY(L->reserve(need));
+        // a short G2 MSM: even with the tables' bucket pass free of a Horner tail, n element-wise products over psi + one sum
+        // are quicker (1.9 - 2.4 ms against 2.3 - 3.0; G1 stays with the tables: 1.0 - 1.2 ms against 1.4 - 1.5)
+        const bool small = !b->has_tables || (sizeof(F) > sizeof(Fq) && n <= 2048 && !getenv("HK_MSM_NO_SMALL"));
+        OneMsm<F> msm{small, &b->plan, small ? (u32)n : b->n};     // the bucket pass is planned for b->n scalars
+        Fr* sc;
+        HK_TRY(L->carve([&](Carve& c) { sc = c.n<Fr>(msm.n); msm.carve(c); }));
         hipStream_t s = L->stream;
-        Fr* sc = L->alloc_n<Fr>(b->n);
-        if (!sc) return HK_ERR_NOMEM;
-        HK_HIP(hipMemcpyAsync(sc, scalars, n * sizeof(Fr), h2d_kind(scalars), s));
-        if (n < b->n) HK_HIP(hipMemsetAsync(sc + n, 0, (b->n - n) * sizeof(Fr), s));
-        SortBufs sb;
-        HK_TRY(MsmSort<Fr>::alloc(L, p, &sb));
-        typename MsmRun<F>::Bufs rb;
-        HK_TRY(MsmRun<F>::alloc(L, p, &rb));
-        XYZZ<F>* res = L->alloc_n<XYZZ<F>>(1);
-        Affine<F>* aff = L->alloc_n<Affine<F>>(1);
-        if (!res || !aff) return HK_ERR_NOMEM;
-        HK_TRY(MsmSort<Fr>::run(s, p, (const u32*)sc, mont, sb));
-        HK_TRY(MsmRun<F>::run(s, p, (const Affine<F>*)b->tab, b->n, 0, sb, rb, res, nullptr, nullptr));
-        HK_TRY(MsmRun<F>::to_affine(s, res, aff, 1));
-        HK_HIP(hipMemcpyAsync(out, aff, sizeof(Affine<F>), is_device_ptr(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-        HK_HIP(hipStreamSynchronize(s));
-        return HK_OK;
+        const void* sc_d = sc;
+        if (small)
+            HK_TRY(to_device(L, scalars, n * sizeof(Fr), &sc_d));
+        else {                                                       // the tail reads zeros
+            HK_HIP(hipMemcpyAsync(sc, scalars, n * sizeof(Fr), h2d_kind(scalars), s));
+            if (n < b->n) HK_HIP(hipMemsetAsync(sc + n, 0, (b->n - n) * sizeof(Fr), s));
+        }
+        HK_TRY(msm.run(s, (const Affine<F>*)b->tab, sc_d, mont, out,                  // group 0 of the table = the bases
+                       is_device_ptr(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+        return L->settle();
     };
     return b->group == 1 ? run(Fq()) : run(Fq2());
 }
@@ -797,9 +777,18 @@ hk_status Ops<C>::fixed_base(hk_ctx* ctx, int group, const void* base, const voi
     if (!L) return HK_ERR_DEVICE;
     auto run = [&](auto ftag) -> hk_status {
         typedef decltype(ftag) F;
-        size_t need = al256(sizeof(Affine<F>)) + al256(n * sizeof(Fr)) + al256(sizeof(Affine<F>) * FB_WINDOWS * 256) +
-                      al256(n * sizeof(XYZZ<F>)) + al256(n * sizeof(F)) + al256(n * sizeof(Affine<F>)) + 8192;
-        HK_TRY(L->reserve(need));
+        const void *bd, *sd;
+        Affine<F>*tab_s, *out_s;
+        XYZZ<F>* xy;
+        F* pref;
+        HK_TRY(L->carve([&](Carve& c) {
+            bd = c.take(sizeof(Affine<F>));
+            sd = c.take(n * sizeof(Fr));
+            tab_s = c.n<Affine<F>>(FB_WINDOWS * 256);
+            xy = c.n<XYZZ<F>>(n);
+            pref = c.n<F>(n);
+            out_s = c.n<Affine<F>>(n);
+        }));
         // the base's window table: from the context's cache when this base has been multiplied before (host bases only: the
         // key is the base's bytes), else built now - into a cache slot when one is free, into the lane's scratch otherwise
         const size_t tbytes = sizeof(Affine<F>) * FB_WINDOWS * 256;
@@ -836,18 +825,14 @@ hk_status Ops<C>::fixed_base(hk_ctx* ctx, int group, const void* base, const voi
                 }
             }
         }
-        const void *bd, *sd;
         HK_TRY(to_device(L, base, sizeof(Affine<F>), &bd));
         HK_TRY(to_device(L, scalars, n * sizeof(Fr), &sd));
-        if (!table) table = L->alloc_n<Affine<F>>(FB_WINDOWS * 256);
-        XYZZ<F>* xy = L->alloc_n<XYZZ<F>>(n);
-        F* pref = L->alloc_n<F>(n);
+        if (!table) table = tab_s;
         bool out_dev = is_device_ptr(out);
-        Affine<F>* od = out_dev ? (Affine<F>*)out : L->alloc_n<Affine<F>>(n);
-        if (!table || !xy || !pref || !od) return HK_ERR_NOMEM;
+        Affine<F>* od = out_dev ? (Affine<F>*)out : out_s;
         HK_TRY(MsmRun<F>::fixed_base(L->stream, (const Affine<F>*)bd, sd, mont, (u32)n, table, xy, pref, od, build));
         if (!out_dev) HK_HIP(hipMemcpyAsync(out, od, n * sizeof(Affine<F>), hipMemcpyDeviceToHost, L->stream));
-        HK_HIP(hipStreamSynchronize(L->stream));
+        HK_TRY(L->settle());
         if (slot >= 0) {                                         // the table is complete: later calls may read it
             std::lock_guard<std::mutex> lk(ctx->mu);
             ctx->fb_cache[slot].ready = true;
@@ -868,22 +853,25 @@ hk_status Ops<C>::scalar_pairing(hk_ctx* ctx, int group, const void* points, con
     if (!L) return HK_ERR_DEVICE;
     auto run = [&](auto ftag) -> hk_status {
         typedef decltype(ftag) F;
-        size_t need = al256(n * sizeof(Affine<F>)) * 2 + al256(n * sizeof(Fr)) + al256(n * sizeof(XYZZ<F>)) +
-                      al256(endo_tab_bytes<F>(n)) + al256(n * sizeof(F)) + 8192;
-        HK_TRY(L->reserve(need));
         const void *pd, *sd;
+        XYZZ<F>*xy, *tab;
+        F* pref;
+        Affine<F>* out_s;
+        HK_TRY(L->carve([&](Carve& c) {
+            pd = c.take(n * sizeof(Affine<F>));
+            sd = c.take(n * sizeof(Fr));
+            xy = c.n<XYZZ<F>>(n);
+            pref = c.n<F>(n);
+            tab = (XYZZ<F>*)c.take(endo_tab_bytes<F>(n));            // the chains' tables (endo.cuh)
+            out_s = c.n<Affine<F>>(n);
+        }));
         HK_TRY(to_device(L, points, n * sizeof(Affine<F>), &pd));
         HK_TRY(to_device(L, scalars, n * sizeof(Fr), &sd));
-        XYZZ<F>* xy = L->alloc_n<XYZZ<F>>(n);
-        F* pref = L->alloc_n<F>(n);
-        XYZZ<F>* tab = (XYZZ<F>*)L->alloc_n<unsigned char>(endo_tab_bytes<F>(n));   // the chains' tables (endo.cuh)
         bool out_dev = is_device_ptr(out);
-        Affine<F>* od = out_dev ? (Affine<F>*)out : L->alloc_n<Affine<F>>(n);
-        if (!xy || !pref || !od || !tab) return HK_ERR_NOMEM;
+        Affine<F>* od = out_dev ? (Affine<F>*)out : out_s;
         HK_TRY(MsmRun<F>::scalar_mul_each(L->stream, (const Affine<F>*)pd, sd, (u32)n, xy, pref, od, tab));
         if (!out_dev) HK_HIP(hipMemcpyAsync(out, od, n * sizeof(Affine<F>), hipMemcpyDeviceToHost, L->stream));
-        HK_HIP(hipStreamSynchronize(L->stream));
-        return HK_OK;
+        return L->settle();
     };
     return group == 1 ? run(Fq()) : run(Fq2());
 }
@@ -899,26 +887,29 @@ hk_status Ops<C>::points_lincomb(hk_ctx* ctx, int group, const void* const* vecs
     if (!L) return HK_ERR_DEVICE;
     auto run = [&](auto ftag) -> hk_status {
         typedef decltype(ftag) F;
-        size_t need = (k + 1) * al256(n * sizeof(Affine<F>)) + al256(k * sizeof(Fr)) + al256(n * sizeof(XYZZ<F>)) +
-                      al256(n * sizeof(F)) + 8192;
-        HK_TRY(L->reserve(need));
         const Affine<F>* dv[LINCOMB_MAX];
+        const void* cd;
+        XYZZ<F>* xy;
+        F* pref;
+        Affine<F>* out_s;
+        HK_TRY(L->carve([&](Carve& c) {
+            for (size_t j = 0; j < k; j++) dv[j] = c.n<Affine<F>>(n);
+            cd = c.take(k * sizeof(Fr));
+            xy = c.n<XYZZ<F>>(n);
+            pref = c.n<F>(n);
+            out_s = c.n<Affine<F>>(n);
+        }));
         for (size_t j = 0; j < k; j++) {
-            const void* d;
+            const void* d = dv[j];
             HK_TRY(to_device(L, vecs[j], n * sizeof(Affine<F>), &d));
             dv[j] = (const Affine<F>*)d;
         }
-        const void* cd;
         HK_TRY(to_device(L, coeffs, k * sizeof(Fr), &cd));
-        XYZZ<F>* xy = L->alloc_n<XYZZ<F>>(n);
-        F* pref = L->alloc_n<F>(n);
         bool out_dev = is_device_ptr(out);
-        Affine<F>* od = out_dev ? (Affine<F>*)out : L->alloc_n<Affine<F>>(n);
-        if (!xy || !pref || !od) return HK_ERR_NOMEM;
+        Affine<F>* od = out_dev ? (Affine<F>*)out : out_s;
         HK_TRY(MsmRun<F>::lincomb(L->stream, dv, cd, (u32)k, (u32)n, xy, pref, od));
         if (!out_dev) HK_HIP(hipMemcpyAsync(out, od, n * sizeof(Affine<F>), hipMemcpyDeviceToHost, L->stream));
-        HK_HIP(hipStreamSynchronize(L->stream));
-        return HK_OK;
+        return L->settle();
     };
     return group == 1 ? run(Fq()) : run(Fq2());
 }
@@ -953,29 +944,35 @@ hk_status Ops<C>::points_fold(hk_ctx* ctx, size_t k, const void* const* lo, cons
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    size_t need = 3 * k * al256(n * sizeof(Affine<F>)) + al256(K * sizeof(Fr)) + al256(k * n * sizeof(XYZZ<F>)) +
-                  al256(endo_tab_bytes<F>(n, k)) + al256(k * n * sizeof(F)) + 8192;
-    HK_TRY(L->reserve(need));
     const Affine<F>*lod[FOLD_MAX], *hid[FOLD_MAX];
+    Fr* cd;
+    XYZZ<F>*tab, *xy;
+    F* pref;
+    Affine<F>* out_s;
+    HK_TRY(L->carve([&](Carve& c) {
+        for (size_t y = 0; y < k; y++) {
+            lod[y] = c.n<Affine<F>>(n);
+            hid[y] = c.n<Affine<F>>(n);
+        }
+        cd = c.n<Fr>(K);
+        tab = (XYZZ<F>*)c.take(endo_tab_bytes<F>(n, k));
+        xy = c.n<XYZZ<F>>(k * n);
+        pref = c.n<F>(k * n);
+        out_s = c.n<Affine<F>>(k * n);
+    }));
     for (size_t y = 0; y < k; y++) {
-        const void* d;
-        HK_TRY(to_device(L, lo[y], n * sizeof(Affine<F>), &d));
-        lod[y] = (const Affine<F>*)d;
-        HK_TRY(to_device(L, hi[y], n * sizeof(Affine<F>), &d));
-        hid[y] = (const Affine<F>*)d;
+        const void *l = lod[y], *h = hid[y];
+        HK_TRY(to_device(L, lo[y], n * sizeof(Affine<F>), &l));
+        HK_TRY(to_device(L, hi[y], n * sizeof(Affine<F>), &h));
+        lod[y] = (const Affine<F>*)l;
+        hid[y] = (const Affine<F>*)h;
     }
-    Fr* cd = L->alloc_n<Fr>(K);
-    if (!cd) return HK_ERR_NOMEM;
     HK_HIP(hipMemcpyAsync(cd, coeffs, K * sizeof(Fr), is_device_ptr(coeffs) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                           L->stream));
     if (!is_device_ptr(coeffs)) HK_HIP(hipStreamSynchronize(L->stream));      // a pageable caller buffer: done with it now
-    XYZZ<F>* tab = (XYZZ<F>*)L->alloc_n<unsigned char>(endo_tab_bytes<F>(n, k));
-    XYZZ<F>* xy = L->alloc_n<XYZZ<F>>(k * n);
-    F* pref = L->alloc_n<F>(k * n);
     // one vector into a device buffer is normalised in place; otherwise into one array that is then handed out
     bool direct = k == 1 && is_device_ptr(out[0]);
-    Affine<F>* od = direct ? (Affine<F>*)out[0] : L->alloc_n<Affine<F>>(k * n);
-    if (!tab || !xy || !pref || !od) return HK_ERR_NOMEM;
+    Affine<F>* od = direct ? (Affine<F>*)out[0] : out_s;
     HK_TRY(MsmRun<F>::fold_endo(L->stream, (u32)k, lod, hid, cd, neg_mask, (u32)n, tab, xy, pref, od));
     if (!direct) {
         GatherRows gr;
@@ -996,8 +993,7 @@ hk_status Ops<C>::points_fold(hk_ctx* ctx, size_t k, const void* const* lo, cons
                                       is_device_ptr(out[y]) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, L->stream));
         }
     }
-    HK_HIP(hipStreamSynchronize(L->stream));
-    return HK_OK;
+    return L->settle();
 }
 
 // out[i] = lo[i] + sum_{j<4} (+-) coeffs4[j] * psi^j(hi[i]) in G2: the fold lo + c * hi of a TIPA round with c split into
@@ -1048,21 +1044,18 @@ hk_status Ops<C>::assignment_from_bits(hk_ctx* ctx, const void* bits, size_t n_v
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    HK_TRY(L->reserve(al256(n_v) + al256(4 * n_full) + al256(sizeof(Fr) * n_full) + 4096));
-    const void *bd, *cd = nullptr, *vd = nullptr;
+    const void *bd, *cd, *vd;
+    HK_TRY(L->carve([&](Carve& c) { bd = c.take(n_v); cd = c.take(4 * n_full); vd = c.take(sizeof(Fr) * n_full); }));
     HK_TRY(to_device(L, bits, n_v, &bd));
-    if (n_full) {
-        HK_TRY(to_device(L, full_cols, 4 * n_full, &cd));
-        HK_TRY(to_device(L, full_vals, sizeof(Fr) * n_full, &vd));
-    }
+    HK_TRY(to_device(L, full_cols, 4 * n_full, &cd));
+    HK_TRY(to_device(L, full_vals, sizeof(Fr) * n_full, &vd));
     hipLaunchKernelGGL((k_expand_bits<Fr>), dim3((u32)((n_v + 255) / 256)), dim3(256), 0, L->stream, (const unsigned char*)bd, n_v,
                        (Fr*)z_out);
     if (n_full)
         hipLaunchKernelGGL((k_scatter_full<Fr>), dim3((u32)((n_full + 63) / 64)), dim3(64), 0, L->stream, (const u32*)cd,
                            (const Fr*)vd, (u32)n_full, n_v, (Fr*)z_out);
     HK_HIP(hipGetLastError());
-    HK_HIP(hipStreamSynchronize(L->stream));
-    return HK_OK;
+    return L->settle();
 }
 
 // ---- word programs (witness.cuh) ---------------------------------------------------------------------------------
@@ -1141,18 +1134,18 @@ hk_status Ops<C>::wprog_run(hk_ctx* ctx, const hk_wprog* h, const uint32_t* inpu
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    size_t need = al256(4 * batch * w->n_inputs) + al256(4 * (size_t)w->n_values * batch) + al256(4 * n_full) +
-                  al256(sizeof(Fr) * n_full * batch) + 8192;
-    HK_TRY(L->reserve(need));
+    const void *in_d, *cd, *vd;
+    u32* values;
+    HK_TRY(L->carve([&](Carve& c) {
+        in_d = c.take(4 * batch * w->n_inputs);
+        cd = c.take(4 * n_full);
+        vd = c.take(sizeof(Fr) * n_full * batch);
+        values = c.n<u32>((size_t)w->n_values * batch);
+    }));
     hipStream_t s = L->stream;
-    const void *in_d, *cd = nullptr, *vd = nullptr;
     HK_TRY(to_device(L, inputs, 4 * batch * w->n_inputs, &in_d));
-    if (n_full) {
-        HK_TRY(to_device(L, full_cols, 4 * n_full, &cd));
-        HK_TRY(to_device(L, full_vals, sizeof(Fr) * n_full * batch, &vd));
-    }
-    u32* values = L->alloc_n<u32>((size_t)w->n_values * batch);
-    if (!values) return HK_ERR_NOMEM;
+    HK_TRY(to_device(L, full_cols, 4 * n_full, &cd));
+    HK_TRY(to_device(L, full_vals, sizeof(Fr) * n_full * batch, &vd));
     hipLaunchKernelGGL((k_word_program<0>), dim3((u32)((batch + 63) / 64)), dim3(64), 0, s, w->ops, w->n_ops, w->refs,
                        (const u32*)in_d, w->n_inputs, (u32)batch, values);
     hipLaunchKernelGGL((k_witness_expand<Fr>), dim3((u32)((w->n_v + 255) / 256), (u32)batch), dim3(256), 0, s, w->map, w->n_v,
@@ -1161,8 +1154,7 @@ hk_status Ops<C>::wprog_run(hk_ctx* ctx, const hk_wprog* h, const uint32_t* inpu
         hipLaunchKernelGGL((k_scatter_full_batch<Fr>), dim3((u32)((n_full + 63) / 64), (u32)batch), dim3(64), 0, s,
                            (const u32*)cd, (const Fr*)vd, (u32)n_full, w->n_v, (Fr*)z_out);
     HK_HIP(hipGetLastError());
-    HK_HIP(hipStreamSynchronize(s));
-    return HK_OK;
+    return L->settle();
 }
 
 // z_out[b][full_cols[j]] = full_vals[b][j]: the full-width values alone, for a caller that ran the class's word program
@@ -1177,15 +1169,14 @@ hk_status Ops<C>::assignment_scatter(hk_ctx* ctx, const uint32_t* full_cols, con
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    HK_TRY(L->reserve(al256(4 * n_full) + al256(sizeof(Fr) * n_full * batch) + 4096));
     const void *cd, *vd;
+    HK_TRY(L->carve([&](Carve& c) { cd = c.take(4 * n_full); vd = c.take(sizeof(Fr) * n_full * batch); }));
     HK_TRY(to_device(L, full_cols, 4 * n_full, &cd));
     HK_TRY(to_device(L, full_vals, sizeof(Fr) * n_full * batch, &vd));
     hipLaunchKernelGGL((k_scatter_full_batch<Fr>), dim3((u32)((n_full + 63) / 64), (u32)batch), dim3(64), 0, L->stream,
                        (const u32*)cd, (const Fr*)vd, (u32)n_full, n_v, (Fr*)z_out);
     HK_HIP(hipGetLastError());
-    HK_HIP(hipStreamSynchronize(L->stream));
-    return HK_OK;
+    return L->settle();
 }
 
 template <class C>
@@ -1212,20 +1203,23 @@ hk_status Ops<C>::poseidon_path(hk_ctx* ctx, const void* consts, size_t n_consts
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    HK_TRY(L->reserve(al256(n_consts * sizeof(Fr)) + al256(batch * 4 * sizeof(Fr)) + al256(batch * depth * sizeof(Fr)) +
-                      al256(4 * batch) + 4096));
-    const void *cd, *ld, *sd = nullptr, *id;
+    const void *cd, *ld, *sd, *id;
+    HK_TRY(L->carve([&](Carve& c) {
+        cd = c.take(n_consts * sizeof(Fr));
+        ld = c.take(batch * 4 * sizeof(Fr));
+        sd = c.take(batch * depth * sizeof(Fr));
+        id = c.take(4 * batch);
+    }));
     HK_TRY(to_device(L, consts, n_consts * sizeof(Fr), &cd));
     HK_TRY(to_device(L, leaf, batch * 4 * sizeof(Fr), &ld));
-    if (depth) HK_TRY(to_device(L, siblings, batch * depth * sizeof(Fr), &sd));
+    HK_TRY(to_device(L, siblings, batch * depth * sizeof(Fr), &sd));
     HK_TRY(to_device(L, index, 4 * batch, &id));
     PoseidonDesc a{lh->t, lh->alpha, lh->full_rounds, lh->partial_rounds, lh->consts_offset};
     PoseidonDesc b{nh->t, nh->alpha, nh->full_rounds, nh->partial_rounds, nh->consts_offset};
     hipLaunchKernelGGL((k_poseidon_path<Fr>), dim3((u32)((batch + 63) / 64)), dim3(64), 0, L->stream, (const Fr*)cd, a, b,
                        (const Fr*)ld, (const Fr*)sd, (const u32*)id, (u32)depth, (u32)batch, n_v, col0, (Fr*)z_out);
     HK_HIP(hipGetLastError());
-    HK_HIP(hipStreamSynchronize(L->stream));
-    return HK_OK;
+    return L->settle();
 }
 
 // ---- multi-pairings (pairing.cuh) ------------------------------------------------------------------------------
@@ -1271,16 +1265,17 @@ hk_status Ops<C>::pairing_pairs(hk_ctx* ctx, const void* const* lhs, size_t n_lh
     if (!L) return HK_ERR_DEVICE;
     size_t g1b = sizeof(Affine<Fq>), g2b = sizeof(Affine<Fq2>);
     size_t mbytes = PairRun<P>::scratch_bytes((u32)n, (u32)count, (u32)n_rhs);
-    size_t need = al256(n_lhs * n * g1b) + al256(n_rhs * n * g2b) + al256(mbytes) +
-                  2 * al256(count * sizeof(GT)) + 8192;
-    HK_TRY(L->reserve(need));
+    Affine<Fq>* d1;
+    Affine<Fq2>* d2;
+    GT *miller, *prod, *res;
+    HK_TRY(L->carve([&](Carve& c) {
+        d1 = c.n<Affine<Fq>>(n_lhs * n);
+        d2 = c.n<Affine<Fq2>>(n_rhs * n);
+        miller = (GT*)c.take(mbytes);                     // lines + per-step tree buffers (or the serial path's Miller values)
+        prod = c.n<GT>(count);
+        res = c.n<GT>(count);
+    }));
     hipStream_t s = L->stream;
-    Affine<Fq>* d1 = L->alloc_n<Affine<Fq>>(n_lhs * n);
-    Affine<Fq2>* d2 = L->alloc_n<Affine<Fq2>>(n_rhs * n);
-    GT* miller = (GT*)L->alloc(mbytes);                   // lines + per-step tree buffers (or the serial path's Miller values)
-    GT* prod = L->alloc_n<GT>(count);
-    GT* res = L->alloc_n<GT>(count);
-    if (!d1 || !d2 || !miller || !prod || !res) return HK_ERR_NOMEM;
     bool packed = false;
     if (n_lhs + n_rhs <= (size_t)GatherRows::MAX && n * g2b < ((size_t)1 << 32)) {
         GatherRows gr;
@@ -1308,8 +1303,7 @@ hk_status Ops<C>::pairing_pairs(hk_ctx* ctx, const void* const* lhs, size_t n_lh
     }
     HK_TRY(PairRun<P>::run(s, d1, d2, (u32)n, (u32)n_lhs, (u32)n_rhs, miller, prod, res, pl.n ? &pl : nullptr));
     HK_HIP(hipMemcpyAsync(out, res, count * sizeof(GT), is_device_ptr(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-    HK_HIP(hipStreamSynchronize(s));
-    return HK_OK;
+    return L->settle();
 }
 
 template <class C>
@@ -1324,23 +1318,26 @@ hk_status Ops<C>::gt_pow(hk_ctx* ctx, const void* gt_in, const void* scalars, si
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    HK_TRY(L->reserve(3 * al256(n * sizeof(GT)) + al256(n * sizeof(Fr)) + 4096));
     const void *ind, *sd;
+    GT *pw_s, *od_s;
+    HK_TRY(L->carve([&](Carve& c) {
+        ind = c.take(n * sizeof(GT));
+        sd = c.take(n * sizeof(Fr));
+        pw_s = c.n<GT>(n);
+        od_s = c.n<GT>(n_out);
+    }));
     HK_TRY(to_device(L, gt_in, n * sizeof(GT), &ind));
     HK_TRY(to_device(L, scalars, n * sizeof(Fr), &sd));
     bool out_dev = is_device_ptr(gt_out);
-    GT* pw = (out_dev && group_len == 1) ? (GT*)gt_out : L->alloc_n<GT>(n);
-    if (!pw) return HK_ERR_NOMEM;
+    GT* pw = (out_dev && group_len == 1) ? (GT*)gt_out : pw_s;
     HK_TRY(PairRun<P>::gt_pow(L->stream, (const GT*)ind, sd, (u32)n, pw, in_gt != 0));
     GT* od = pw;
     if (group_len > 1) {
-        od = out_dev ? (GT*)gt_out : L->alloc_n<GT>(n_out);
-        if (!od) return HK_ERR_NOMEM;
+        od = out_dev ? (GT*)gt_out : od_s;
         HK_TRY(PairRun<P>::gt_prod(L->stream, pw, (u32)group_len, (u32)n_out, od));
     }
     if (!out_dev) HK_HIP(hipMemcpyAsync(gt_out, od, n_out * sizeof(GT), hipMemcpyDeviceToHost, L->stream));
-    HK_HIP(hipStreamSynchronize(L->stream));
-    return HK_OK;
+    return L->settle();
 }
 
 // out[i] = in[i] * R (to_mont) or in[i] / R; memory canonical either way
@@ -1362,25 +1359,22 @@ hk_status Ops<C>::field_convert(hk_ctx* ctx, int which, const void* in, void* ou
         typedef decltype(ftag) F;
         const size_t CH = (size_t)1 << 24;                       // host buffers go through the lane in chunks
         bool in_dev = is_device_ptr(in), out_dev = is_device_ptr(out);
-        HK_TRY(L->reserve(2 * al256(std::min(n, CH) * sizeof(F)) + 4096));
         for (size_t off = 0; off < n; off += CH) {
             size_t k = std::min(CH, n - off);
-            L->arena_off = 0;
+            F *t, *u;
+            HK_TRY(L->carve([&](Carve& c) { t = c.n<F>(k); u = c.n<F>(k); }));
             const F* src = (const F*)in + off;
             F* dst = (F*)out + off;
             const F* sd = src;
             if (!in_dev) {
-                F* t = L->alloc_n<F>(k);
-                if (!t) return HK_ERR_NOMEM;
                 HK_HIP(hipMemcpyAsync(t, src, k * sizeof(F), hipMemcpyHostToDevice, L->stream));
                 sd = t;
             }
-            F* dd = out_dev ? dst : L->alloc_n<F>(k);
-            if (!dd) return HK_ERR_NOMEM;
+            F* dd = out_dev ? dst : u;
             hipLaunchKernelGGL(k_field_convert<F>, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, L->stream, sd, dd, k, to_mont);
             HK_HIP(hipGetLastError());
             if (!out_dev) HK_HIP(hipMemcpyAsync(dst, dd, k * sizeof(F), hipMemcpyDeviceToHost, L->stream));
-            HK_HIP(hipStreamSynchronize(L->stream));
+            HK_TRY(L->settle());
         }
         return HK_OK;
     };
@@ -1542,30 +1536,17 @@ hk_status Ops<C>::commit(hk_ctx* ctx, const hk_pk* h, size_t stage, const void* 
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const MsmPlan& p = pk->plan_ck[stage];
-    size_t need = al256((n + 1) * sizeof(Fr)) + msm_sort_bytes(p) + msm_run_bytes<Fq>(p) + 4096;
-    HK_TRY(L->reserve(need));
+    OneMsm<Fq> msm{false, &pk->plan_ck[stage], (u32)(n + 1)};
+    Fr* sc;
+    HK_TRY(L->carve([&](Carve& c) { sc = c.n<Fr>(n + 1); msm.carve(c); }));
     hipStream_t s = L->stream;
     bool prof = ctx->profiling;
     if (prof) HK_HIP(hipEventRecord(L->ev[0], s));
-    Fr* sc = L->alloc_n<Fr>(n + 1);
-    if (!sc) return HK_ERR_NOMEM;
     if (n) HK_HIP(hipMemcpyAsync(sc, w, n * sizeof(Fr), h2d_kind(w), s));
     HK_HIP(hipMemcpyAsync(sc + n, kappa, sizeof(Fr), hipMemcpyHostToDevice, s));
-    SortBufs sb;
-    HK_TRY(MsmSort<Fr>::alloc(L, p, &sb));
-    typename MsmRun<Fq>::Bufs rb;
-    HK_TRY(MsmRun<Fq>::alloc(L, p, &rb));
-    XYZZ<Fq>* res = L->alloc_n<XYZZ<Fq>>(1);
-    Affine<Fq>* aff = L->alloc_n<Affine<Fq>>(1);
-    if (!res || !aff) return HK_ERR_NOMEM;
-    HK_TRY(MsmSort<Fr>::run(s, p, (const u32*)sc, 1, sb));
-    HK_TRY(MsmRun<Fq>::run(s, p, pk->ck_tab[stage], (u32)(n + 1), 0, sb, rb, res, prof ? L->ev[20] : nullptr,
-                           prof ? L->ev[21] : nullptr));
-    HK_TRY(MsmRun<Fq>::to_affine(s, res, aff, 1));
-    HK_HIP(hipMemcpyAsync(out, aff, sizeof(Affine<Fq>), hipMemcpyDeviceToHost, s));
+    HK_TRY(msm.run(s, pk->ck_tab[stage], sc, 1, out, hipMemcpyDeviceToHost, prof ? L->ev[20] : nullptr, prof ? L->ev[21] : nullptr));
     if (prof) HK_HIP(hipEventRecord(L->ev[1], s));
-    HK_HIP(hipStreamSynchronize(s));
+    HK_TRY(L->settle());
     if (prof) {
         memset(&L->timings, 0, sizeof(L->timings));
         L->timings.total_ms = ev_ms(L->ev[0], L->ev[1]);
@@ -1599,26 +1580,28 @@ hk_status Ops<C>::commit_batch(hk_ctx* ctx, const hk_pk* h, size_t stage, const 
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    size_t need = al256(tot * sizeof(Fr)) + al256(tot * sizeof(XYZZ<Fq>)) + al256(endo_tab_bytes<Fq>(tot)) +
-                  al256(batch * sizeof(XYZZ<Fq>)) + al256(batch * sizeof(Fq)) + al256(batch * sizeof(Affine<Fq>)) + 8192;
-    HK_TRY(L->reserve(need));
+    Fr* sc;
+    XYZZ<Fq>*xy, *tab, *res;
+    Fq* pref;
+    Affine<Fq>* aff;
+    HK_TRY(L->carve([&](Carve& c) {
+        sc = c.n<Fr>(tot);                                     // [batch][n + 1]: a row's witnesses, then its kappa
+        xy = c.n<XYZZ<Fq>>(tot);
+        tab = (XYZZ<Fq>*)c.take(endo_tab_bytes<Fq>(tot));
+        res = c.n<XYZZ<Fq>>(batch);
+        pref = c.n<Fq>(batch);
+        aff = c.n<Affine<Fq>>(batch);
+    }));
     hipStream_t s = L->stream;
     bool prof = ctx->profiling;
     if (prof) HK_HIP(hipEventRecord(L->ev[0], s));
-    Fr* sc = L->alloc_n<Fr>(tot);                              // [batch][n + 1]: a row's witnesses, then its kappa
-    XYZZ<Fq>* xy = L->alloc_n<XYZZ<Fq>>(tot);
-    XYZZ<Fq>* tab = (XYZZ<Fq>*)L->alloc_n<unsigned char>(endo_tab_bytes<Fq>(tot));
-    XYZZ<Fq>* res = L->alloc_n<XYZZ<Fq>>(batch);
-    Fq* pref = L->alloc_n<Fq>(batch);
-    Affine<Fq>* aff = L->alloc_n<Affine<Fq>>(batch);
-    if (!sc || !xy || !tab || !res || !pref || !aff) return HK_ERR_NOMEM;
     if (n) HK_HIP(hipMemcpy2DAsync(sc, seg * sizeof(Fr), w, n * sizeof(Fr), n * sizeof(Fr), batch, h2d_kind(w), s));
     HK_HIP(hipMemcpy2DAsync(sc + n, seg * sizeof(Fr), kappas, sizeof(Fr), sizeof(Fr), batch, hipMemcpyHostToDevice, s));
     HK_TRY(MsmRun<Fq>::small_msm_rows(s, pk->ck_tab[stage], sc, (u32)seg, (u32)batch, tab, xy, res));   // group 0 of the table
     HK_TRY(MsmRun<Fq>::batch_affine(s, res, aff, pref, (u32)batch));
     HK_HIP(hipMemcpyAsync(out, aff, batch * sizeof(Affine<Fq>), is_device_ptr(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
     if (prof) HK_HIP(hipEventRecord(L->ev[1], s));
-    HK_HIP(hipStreamSynchronize(s));
+    HK_TRY(L->settle());
     if (prof) {
         memset(&L->timings, 0, sizeof(L->timings));
         L->timings.total_ms = ev_ms(L->ev[0], L->ev[1]);
@@ -1648,17 +1631,39 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
     const MsmPlan &pz = pk->plan_z, &ph = pk->plan_h, &pb = pk->plan_b;
     const size_t m = (size_t)1 << pk->log_m, fr = sizeof(Fr), rs_stride = 2 + n_kappas;
     const bool z_dev = is_device_ptr(z);
-    // device bytes of one chunk of `nb` proofs: every per-proof buffer times nb, the bucket pipelines sized by the lane
-    // plan of the chunk (the chip's lanes split across it, so the boundary partials do not grow with nb)
-    auto need_for = [&](size_t nb) -> size_t {
-        size_t need = al256(fr * pk->n_ext * nb) + al256(fr * rs_stride * nb) + msm_sort_bytes(pz, nb) +
-                      msm_sort_bytes(ph, nb) + 2 * msm_run_bytes<Fq>(pz, nb) + msm_run_bytes<Fq>(pb, nb) +
-                      msm_run_bytes<Fq>(ph, nb) + msm_run_bytes<Fq2>(pb, nb) + al256(3 * m * fr * nb) +
-                      al256(4 * nb * sizeof(XYZZ<Fq>)) + al256(nb * sizeof(XYZZ<Fq2>)) + 2 * al256(nb * sizeof(Affine<Fq>)) +
-                      al256(nb * sizeof(Affine<Fq2>)) + 16384;
-        if (!z_dev) need += al256(fr * n_v * nb);
-        if (pk->b_compact) need += msm_sort_bytes(pb, nb) + al256(fr * pk->b_n * nb);
-        return need;
+    // the scratch of one chunk of `nb` proofs: every per-proof buffer times nb, the bucket pipelines sized by the lane plan
+    // of the chunk (the chip's lanes split across it, so the boundary partials do not grow with nb)
+    Fr *zext, *small, *zt, *zb, *abc;
+    SortBufs sb, sbh, sbb;
+    typename MsmRun<Fq>::Bufs rbA, rbB1, rbL, rbh;
+    typename MsmRun<Fq2>::Bufs rb2;
+    XYZZ<Fq>* res1;
+    XYZZ<Fq2>* res2;
+    Affine<Fq> *oa, *oc;
+    Affine<Fq2>* ob;
+    auto chunk_bufs = [&](Carve& c, u32 nb) {
+        zext = c.n<Fr>((size_t)pk->n_ext * nb);                               // z[1..] | r | s | rs | kappas
+        small = c.n<Fr>(rs_stride * nb);                                      // [nb][2 + n_kappas]
+        zt = z_dev ? nullptr : c.n<Fr>(n_v * nb);                             // a host z, copied in
+        MsmSort<Fr>::alloc(c, pz, &sb, nb);
+        MsmSort<Fr>::alloc(c, ph, &sbh, nb);
+        sbb.count = nullptr;
+        zb = nullptr;
+        if (pk->b_compact) {
+            MsmSort<Fr>::alloc(c, pb, &sbb, nb);
+            zb = c.n<Fr>((size_t)pk->b_n * nb);
+        }
+        MsmRun<Fq>::alloc(c, pz, &rbA, nb);
+        MsmRun<Fq>::alloc(c, pb, &rbB1, nb);
+        MsmRun<Fq>::alloc(c, pz, &rbL, nb);
+        MsmRun<Fq>::alloc(c, ph, &rbh, nb);
+        MsmRun<Fq2>::alloc(c, pb, &rb2, nb);
+        res1 = c.n<XYZZ<Fq>>(4 * (size_t)nb);                                // [nb][A, B1, L, H]
+        res2 = c.n<XYZZ<Fq2>>(nb);
+        oa = c.n<Affine<Fq>>(nb);
+        oc = c.n<Affine<Fq>>(nb);
+        ob = c.n<Affine<Fq2>>(nb);
+        abc = c.n<Fr>(3 * m * nb);                                            // [nb][a | b | c]
     };
     // chunk rule (hekaton.h): at most HK_PROVE_BATCH_CHUNK proofs, fewer when that many would not fit in free device memory
     // (the lane's own arena counts as free: reserve() replaces it)
@@ -1667,7 +1672,8 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
         size_t avail = free_b + L->arena_cap;
-        while (chunk > 1 && need_for(chunk) > avail) chunk--;
+        auto chunk_bytes = [&](size_t nb) { Carve c; chunk_bufs(c, (u32)nb); return c.off; };
+        while (chunk > 1 && chunk_bytes(chunk) > avail) chunk--;
     }
     // r | s | kappas of every proof, one row each (k_prep_ext and k_finish read them)
     std::vector<unsigned char> rows(batch * rs_stride * fr);
@@ -1690,21 +1696,16 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
     static const bool serial = getenv("HK_SERIAL_STREAMS") != nullptr;
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const u32 nb = (u32)std::min(chunk, batch - b0);
-        HK_TRY(L->reserve(need_for(nb)));
+        HK_TRY(L->carve([&](Carve& c) { chunk_bufs(c, nb); }));
         // ev[0] marks the start of the call (total_ms runs from it to the last chunk's ev[8]), ev[9] that of a later chunk
         hipEvent_t ev_start = b0 ? ev[9] : ev[0];
         if (prof) HK_HIP(hipEventRecord(ev_start, s));
-        // --- extended scalar vectors [nb][n_ext]: z[1..] | r | s | rs | kappas
-        Fr* zext = L->alloc_n<Fr>((size_t)pk->n_ext * nb);
-        Fr* small = L->alloc_n<Fr>(rs_stride * nb);                             // [nb][2 + n_kappas]
-        if (!zext || !small) return HK_ERR_NOMEM;
+        // --- extended scalar vectors [nb][n_ext]
         const Fr* zd;
         if (z_dev) zd = (const Fr*)z + b0 * n_v;
         else {
-            Fr* t = L->alloc_n<Fr>(n_v * nb);
-            if (!t) return HK_ERR_NOMEM;
-            HK_HIP(hipMemcpyAsync(t, (const Fr*)z + b0 * n_v, n_v * nb * fr, hipMemcpyHostToDevice, s));
-            zd = t;
+            HK_HIP(hipMemcpyAsync(zt, (const Fr*)z + b0 * n_v, n_v * nb * fr, hipMemcpyHostToDevice, s));
+            zd = zt;
         }
         if (n_v > 1 && nb == 1)
             HK_HIP(hipMemcpyAsync(zext, zd + 1, (n_v - 1) * fr, hipMemcpyDeviceToDevice, s));
@@ -1712,33 +1713,9 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
             HK_HIP(hipMemcpy2DAsync(zext, pk->n_ext * fr, zd + 1, n_v * fr, (n_v - 1) * fr, nb, hipMemcpyDeviceToDevice, s));
         HK_HIP(hipMemcpyAsync(small, rows.data() + b0 * rs_stride * fr, nb * rs_stride * fr, hipMemcpyHostToDevice, s));
         // --- one digit sort per proof shared by the four assignment-indexed queries
-        SortBufs sb, sbh, sbb;
-        sbb.count = nullptr;
-        HK_TRY(MsmSort<Fr>::alloc(L, pz, &sb, nb));
-        HK_TRY(MsmSort<Fr>::alloc(L, ph, &sbh, nb));
-        Fr* zb = nullptr;
-        if (pk->b_compact) {
-            HK_TRY(MsmSort<Fr>::alloc(L, pb, &sbb, nb));
-            zb = L->alloc_n<Fr>((size_t)pk->b_n * nb);
-            if (!zb) return HK_ERR_NOMEM;
-        }
         hipLaunchKernelGGL((k_prep_ext<Fr>), dim3(64), dim3(256), 0, s, zext + (n_v - 1), pk->n_ext, (const Fr*)small,
                            (u32)rs_stride, (u32)n_kappas, nb, sb.count, sbh.count, sbb.count, pz.NB * nb, ph.NB * nb,
                            pk->b_compact ? pb.NB * nb : 0u);
-        typename MsmRun<Fq>::Bufs rbA, rbB1, rbL, rbh;
-        typename MsmRun<Fq2>::Bufs rb2;
-        HK_TRY(MsmRun<Fq>::alloc(L, pz, &rbA, nb));
-        HK_TRY(MsmRun<Fq>::alloc(L, pb, &rbB1, nb));
-        HK_TRY(MsmRun<Fq>::alloc(L, pz, &rbL, nb));
-        HK_TRY(MsmRun<Fq>::alloc(L, ph, &rbh, nb));
-        HK_TRY(MsmRun<Fq2>::alloc(L, pb, &rb2, nb));
-        XYZZ<Fq>* res1 = L->alloc_n<XYZZ<Fq>>(4 * (size_t)nb);                  // [nb][A, B1, L, H]
-        XYZZ<Fq2>* res2 = L->alloc_n<XYZZ<Fq2>>(nb);
-        Affine<Fq>* oa = L->alloc_n<Affine<Fq>>(nb);
-        Affine<Fq>* oc = L->alloc_n<Affine<Fq>>(nb);
-        Affine<Fq2>* ob = L->alloc_n<Affine<Fq2>>(nb);
-        Fr* abc = L->alloc_n<Fr>(3 * m * nb);                                   // [nb][a | b | c]
-        if (!res1 || !res2 || !oa || !oc || !ob || !abc) return HK_ERR_NOMEM;
         // Fork: the five queries are independent once their scalars exist.  Side streams let the
         // latency-bound tails (segmented levels, bucket reduction) of one query hide under the
         // throughput-bound accumulation of another; every launch covers the whole chunk.
@@ -1747,16 +1724,6 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
         hipStream_t axs[4] = {L->aux[0], L->aux[1], L->aux[2], L->aux[3]};
         if (serial) for (auto& a : axs) a = s;
         hipStream_t* ax = axs;
-        // Every exit between the fork and the join - an HK_TRY / HK_HIP return included - must leave no side stream
-        // running on this lane's arena: the next call on the lane resets the arena and would reuse live memory.
-        struct JoinGuard {
-            hipStream_t main; hipStream_t* aux; bool joined = false;
-            ~JoinGuard() {
-                if (joined) return;
-                for (int i = 0; i < 4; i++) (void)hipStreamSynchronize(aux[i]);
-                (void)hipStreamSynchronize(main);
-            }
-        } join_guard{s, axs};
         hipEvent_t ev_z = ev[16], ev_sorted = ev[17];
         HK_HIP(hipEventRecord(ev_z, s));                                       // z (and ext scalars) on device
         HK_HIP(hipStreamWaitEvent(ax[3], ev_z, 0));
@@ -1803,7 +1770,6 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
         HK_HIP(hipStreamWaitEvent(s, ev[4], 0));
         HK_HIP(hipStreamWaitEvent(s, ev[18], 0));
         HK_HIP(hipStreamWaitEvent(s, ev[7], 0));
-        join_guard.joined = true;                                              // main now depends on every side stream
         if (prof) HK_HIP(hipEventRecord(ev[19], s));                           // all queries done
         hipLaunchKernelGGL((k_finish<Fr, Fq, Fq2>), dim3(3, nb), dim3(64), 0, s, res1, res2, pk->consts_g1, pk->consts_g2,
                            (const Fr*)small, (u32)rs_stride, oa, ob, oc, endo_g1);
@@ -1812,7 +1778,7 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
         HK_HIP(hipMemcpyAsync((char*)out_b + b0 * sizeof(Affine<Fq2>), ob, nb * sizeof(Affine<Fq2>), hipMemcpyDeviceToHost, s));
         HK_HIP(hipMemcpyAsync((char*)out_c + b0 * sizeof(Affine<Fq>), oc, nb * sizeof(Affine<Fq>), hipMemcpyDeviceToHost, s));
         if (prof) HK_HIP(hipEventRecord(ev[8], s));
-        HK_HIP(hipStreamSynchronize(s));
+        HK_TRY(L->settle());
         if (prof) {
             // the five queries run concurrently on side streams: each figure is the elapsed time on the query's own
             // stream since its fork point (they overlap, they do not add up to total_ms); summed over the chunks

@@ -216,8 +216,6 @@ k_verify_verdict(const Fp12<P>* __restrict__ got, const Fp12<P>* __restrict__ wa
 #endif  // __HIPCC__
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-inline size_t vr_al(size_t b) { return (b + 255) & ~(size_t)255; }
-
 template <class P>
 struct VkImpl {
     u32 n_deltas = 0, n_abc = 0;
@@ -303,15 +301,19 @@ hk_status VerifyRun<P>::vk_prepare(hk_ctx* ctx, const hk_vk_desc* d, hk_vk** out
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
     size_t mbytes = PairRun<P>::scratch_bytes(1, 1, 1);
-    HK_TRY(L->reserve(vr_al(nst * sizeof(Affine<Fq2>)) + 2 * vr_al(sizeof(Affine<Fq2>)) + vr_al(mbytes) + 2 * vr_al(sizeof(GT)) + 8192));
-    hipStream_t s = L->stream;
-    Affine<Fq2>* g2 = L->alloc_n<Affine<Fq2>>(nst);
+    Affine<Fq2>* g2;
     const void *al, *be;
+    GT *miller, *prod;
+    HK_TRY(L->carve([&](Carve& c) {
+        g2 = c.n<Affine<Fq2>>(nst);
+        al = c.take(sizeof(Affine<Fq>));
+        be = c.take(sizeof(Affine<Fq2>));
+        miller = (GT*)c.take(mbytes);
+        prod = c.n<GT>(1);
+    }));
+    hipStream_t s = L->stream;
     HK_TRY(to_device(L, d->alpha_g, sizeof(Affine<Fq>), &al));
     HK_TRY(to_device(L, d->beta_h, sizeof(Affine<Fq2>), &be));
-    GT* miller = (GT*)L->alloc(mbytes);
-    GT* prod = L->alloc_n<GT>(1);
-    if (!g2 || !miller || !prod) return HK_ERR_NOMEM;
     VkImpl<P>* v = new VkImpl<P>();
     v->n_deltas = (u32)d->n_deltas;
     v->n_abc = (u32)d->n_abc;
@@ -327,7 +329,7 @@ hk_status VerifyRun<P>::vk_prepare(hk_ctx* ctx, const hk_vk_desc* d, hk_vk** out
     hk_status st = verify_lines<P>(s, g2, nst, v->lines);
     if (st == HK_OK)
         st = PairRun<P>::run(s, (const Affine<Fq>*)al, (const Affine<Fq2>*)be, 1, 1, 1, miller, prod, v->alpha_beta);
-    if (st == HK_OK && hipStreamSynchronize(s) != hipSuccess) st = HK_ERR_DEVICE;
+    if (st == HK_OK) st = L->settle();
     if (st != HK_OK) return fail(st);
     hk_vk* h = new hk_vk();
     h->ops = ctx->ops;
@@ -366,17 +368,16 @@ hk_status VerifyRun<P>::points_check(hk_ctx* ctx, int group, const void* pts, si
     if (!L) return HK_ERR_DEVICE;
     auto run = [&](auto ftag) -> hk_status {
         typedef decltype(ftag) F;
-        HK_TRY(L->reserve(vr_al(n * sizeof(Affine<F>)) + vr_al(n) + 4096));
         const void* pd;
+        unsigned char* out_s;
+        HK_TRY(L->carve([&](Carve& c) { pd = c.take(n * sizeof(Affine<F>)); out_s = c.n<unsigned char>(n); }));
         HK_TRY(to_device(L, pts, n * sizeof(Affine<F>), &pd));
         bool dev = is_device_ptr(ok);
-        unsigned char* od = dev ? ok : L->alloc_n<unsigned char>(n);
-        if (!od) return HK_ERR_NOMEM;
+        unsigned char* od = dev ? ok : out_s;
         hipLaunchKernelGGL((k_points_check<F>), dim3((u32)((n + 63) / 64)), dim3(64), 0, L->stream, (const Affine<F>*)pd, (u32)n, 0u, od);
         HK_HIP(hipGetLastError());
         if (!dev) HK_HIP(hipMemcpyAsync(ok, od, n, hipMemcpyDeviceToHost, L->stream));
-        HK_HIP(hipStreamSynchronize(L->stream));
-        return HK_OK;
+        return L->settle();
     };
     return group == 1 ? run(Fp<P>()) : run(Fp2<P>());
 }
@@ -405,29 +406,54 @@ hk_status VerifyRun<P>::verify_batch(hk_ctx* ctx, const hk_vk* h, const void* a,
     for (size_t o = 0; o < n; o += VERIFY_CHUNK) {
         const u32 m = (u32)(n - o < VERIFY_CHUNK ? n - o : VERIFY_CHUNK);
         const u32 gb = (m + nst + 15) / 16;                // ... of the batch product
-        size_t need = vr_al(m * 2 * g1b) + vr_al(m * g2b) + vr_al((size_t)m * (nd - 1) * g1b) + vr_al((size_t)m * nk * frb) +
-                      3 * vr_al(m) + vr_al((size_t)m * nst * g1b) + vr_al((size_t)m * S * sizeof(Line6<P>)) +
-                      2 * vr_al((size_t)m * S * gpp * sizeof(GT)) + vr_al(m * sizeof(GT)) + 16384;
-        if (rand)
-            need += vr_al(m * frb) + vr_al(m * g1b) + vr_al(m * sizeof(XYZZ<Fq>)) + vr_al(m * sizeof(Fq)) + vr_al(endo_tab_bytes<Fq>(m)) +
-                    vr_al(m * g1b) + vr_al(nst * sizeof(XYZZ<Fq>)) + vr_al(nst * g1b) + vr_al((nk + 1) * frb) +
-                    2 * vr_al((size_t)S * gb * sizeof(GT)) + 2 * vr_al(sizeof(GT)) + 256;
-        HK_TRY(L->reserve(need));
-        const void *ad, *bd, *cd, *dd = nullptr, *xd = nullptr, *rd = nullptr;
+        const void *ad, *bd, *cd, *dd, *xd, *rd;
+        unsigned char *flag, *vd_s;
+        Affine<Fq>* gst;
+        Line6<P>* lines;
+        GT *pp0, *pp1, *res;
+        // the randomised check's buffers (when `rand`)
+        Affine<Fq>*ra = nullptr, *col = nullptr, *bst = nullptr;
+        XYZZ<Fq>*xy = nullptr, *tab = nullptr, *sums = nullptr;
+        Fq* pref = nullptr;
+        Fr* coef = nullptr;
+        GT *qa = nullptr, *qb = nullptr, *one = nullptr, *want = nullptr;
+        unsigned char* eq = nullptr;
+        HK_TRY(L->carve([&](Carve& k) {
+            ad = k.take(m * g1b);
+            bd = k.take(m * g2b);
+            cd = k.take(m * g1b);
+            dd = k.take((size_t)m * (nd - 1) * g1b);
+            xd = k.take((size_t)m * nk * frb);
+            rd = k.take(rand ? m * frb : 0);
+            flag = k.n<unsigned char>(m);
+            vd_s = k.n<unsigned char>(m);
+            gst = k.n<Affine<Fq>>((size_t)m * nst);
+            lines = k.n<Line6<P>>((size_t)m * S);
+            pp0 = k.n<GT>((size_t)m * S * gpp);
+            pp1 = k.n<GT>((size_t)m * S * gpp);
+            res = k.n<GT>(m);
+            if (!rand) return;
+            ra = k.n<Affine<Fq>>(m);
+            xy = k.n<XYZZ<Fq>>(m);
+            pref = k.n<Fq>(m);
+            tab = (XYZZ<Fq>*)k.take(endo_tab_bytes<Fq>(m));
+            col = k.n<Affine<Fq>>(m);
+            sums = k.n<XYZZ<Fq>>(nst);
+            bst = k.n<Affine<Fq>>(nst);
+            coef = k.n<Fr>(nk + 1);
+            qa = k.n<GT>((size_t)S * gb);
+            qb = k.n<GT>((size_t)S * gb);
+            one = k.n<GT>(1);
+            want = k.n<GT>(1);
+            eq = k.n<unsigned char>(1);
+        }));
         HK_TRY(to_device(L, (const char*)a + o * g1b, m * g1b, &ad));
         HK_TRY(to_device(L, (const char*)b + o * g2b, m * g2b, &bd));
         HK_TRY(to_device(L, (const char*)c + o * g1b, m * g1b, &cd));
         if (nd > 1) HK_TRY(to_device(L, (const char*)ds + o * (nd - 1) * g1b, (size_t)m * (nd - 1) * g1b, &dd));
         if (nk) HK_TRY(to_device(L, (const char*)inputs + o * nk * frb, (size_t)m * nk * frb, &xd));
         if (rand) HK_TRY(to_device(L, (const char*)rand + o * frb, m * frb, &rd));
-        unsigned char* flag = L->alloc_n<unsigned char>(m);
-        unsigned char* vd = out_dev ? verdicts + o : L->alloc_n<unsigned char>(m);
-        Affine<Fq>* gst = L->alloc_n<Affine<Fq>>((size_t)m * nst);
-        Line6<P>* lines = L->alloc_n<Line6<P>>((size_t)m * S);
-        GT* pp0 = L->alloc_n<GT>((size_t)m * S * gpp);
-        GT* pp1 = L->alloc_n<GT>((size_t)m * S * gpp);
-        GT* res = L->alloc_n<GT>(m);
-        if (!flag || !vd || !gst || !lines || !pp0 || !pp1 || !res) return HK_ERR_NOMEM;
+        unsigned char* vd = out_dev ? verdicts + o : vd_s;
         HK_HIP(hipMemsetAsync(flag, 0, m, s));
         bool any_bad = false;
         if (check) {
@@ -450,20 +476,6 @@ hk_status VerifyRun<P>::verify_batch(hk_ctx* ctx, const hk_vk* h, const void* a,
             for (u32 i = 0; i < m; i++) any_bad = any_bad || fh[i];
         }
         if (rand && !any_bad) {
-            Affine<Fq>* ra = L->alloc_n<Affine<Fq>>(m);
-            XYZZ<Fq>* xy = L->alloc_n<XYZZ<Fq>>(m);
-            Fq* pref = L->alloc_n<Fq>(m);
-            XYZZ<Fq>* tab = (XYZZ<Fq>*)L->alloc_n<unsigned char>(endo_tab_bytes<Fq>(m));
-            Affine<Fq>* col = L->alloc_n<Affine<Fq>>(m);
-            XYZZ<Fq>* sums = L->alloc_n<XYZZ<Fq>>(nst);
-            Affine<Fq>* bst = L->alloc_n<Affine<Fq>>(nst);
-            Fr* coef = L->alloc_n<Fr>(nk + 1);
-            GT* qa = L->alloc_n<GT>((size_t)S * gb);
-            GT* qb = L->alloc_n<GT>((size_t)S * gb);
-            GT* one = L->alloc_n<GT>(1);
-            GT* want = L->alloc_n<GT>(1);
-            unsigned char* eq = L->alloc_n<unsigned char>(1);
-            if (!ra || !xy || !pref || !tab || !col || !sums || !bst || !coef || !qa || !qb || !one || !want || !eq) return HK_ERR_NOMEM;
             // sum r_i, sum r_i x_i -> sum r_i IC_i = (sum r_i) abc[0] + sum_k (sum_i r_i x_ik) abc[k + 1]
             hipLaunchKernelGGL((k_verify_coeffs<Fr>), dim3((nk + 1 + 63) / 64), dim3(64), 0, s, (const Fr*)rd, (const Fr*)xd, m, nk, coef);
             hipLaunchKernelGGL((k_verify_ic<P, Fr>), dim3(1), dim3(64), 0, s, (const Affine<Fq>*)v->abc, nk + 1, (const Fr*)coef,
@@ -505,7 +517,7 @@ hk_status VerifyRun<P>::verify_batch(hk_ctx* ctx, const hk_vk* h, const void* a,
             HK_HIP(hipGetLastError());
         }
         if (!out_dev) HK_HIP(hipMemcpyAsync(verdicts + o, vd, m, hipMemcpyDeviceToHost, s));
-        HK_HIP(hipStreamSynchronize(s));
+        HK_TRY(L->settle());
     }
     return HK_OK;
 }
