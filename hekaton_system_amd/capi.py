@@ -56,11 +56,27 @@ class hk_vk_desc(C.Structure):                # include/hekaton.h
                 ("n_deltas", C.c_size_t), ("gamma_abc_g", C.c_void_p), ("n_abc", C.c_size_t)]
 
 
+class hk_keygen_desc(C.Structure):            # include/hekaton.h
+    _fields_ = [("A", C.POINTER(hk_csr)), ("B", C.POINTER(hk_csr)), ("C", C.POINTER(hk_csr)),
+                ("n_inst", C.c_size_t), ("n_constraints", C.c_size_t), ("n_v", C.c_size_t),
+                ("stage_ranges", C.c_void_p), ("n_stages", C.c_size_t),
+                ("alpha", C.c_void_p), ("beta", C.c_void_p), ("gamma", C.c_void_p), ("t", C.c_void_p),
+                ("g1_scalar", C.c_void_p), ("g2_scalar", C.c_void_p), ("deltas", C.c_void_p)]
+
+
+class hk_keygen_out(C.Structure):             # include/hekaton.h
+    _fields_ = [("a_g", C.c_void_p), ("b_g", C.c_void_p), ("b_h", C.c_void_p), ("h_g", C.c_void_p),
+                ("ck_stage", C.POINTER(C.c_void_p)),
+                ("deltas_g", C.c_void_p), ("alpha_g", C.c_void_p), ("beta_g", C.c_void_p), ("gamma_abc_g", C.c_void_p),
+                ("beta_h", C.c_void_p), ("gamma_h", C.c_void_p), ("deltas_h", C.c_void_p), ("qap_abc", C.c_void_p)]
+
+
 class hk_timings(C.Structure):
     _fields_ = [(n, C.c_float) for n in
                 ("total_ms", "digits_ms", "msm_a_ms", "msm_b_g1_ms", "msm_b_g2_ms", "msm_l_ms",
                  "witness_map_ms", "msm_h_ms", "finish_ms", "accum_kernel_ms")] + \
-               [("accum_kernel_launches", C.c_uint32), ("accum_h_ms", C.c_float)]
+               [("accum_kernel_launches", C.c_uint32), ("accum_h_ms", C.c_float), ("keygen_qap_ms", C.c_float),
+                ("keygen_scalars_ms", C.c_float), ("keygen_sweeps_ms", C.c_float)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -74,7 +90,7 @@ EXPORTS = ["hk_status_str", "hk_version", "hk_ctx_create", "hk_ctx_destroy", "hk
            "hk_msm_bases", "hk_multi_pairing", "hk_pairing_products", "hk_ctx_gt_bytes",
            "hk_points_lincomb_g1", "hk_points_lincomb_g2", "hk_points_fold_g2", "hk_points_fold_g1", "hk_points_fold_many_g1", "hk_points_fold_many_g2", "hk_pairing_pairs", "hk_keccak_f1600", "hk_assignment_from_bits", "hk_wprog_upload", "hk_wprog_free", "hk_wprog_run", "hk_gt_pow", "hk_fq12_pow", "hk_gt_pow_prod", "hk_poseidon_path", "hk_assignment_scatter", "hk_commit_batch",
            "hk_prove_batch", "hk_vk_prepare", "hk_vk_free", "hk_vk_alpha_beta", "hk_verify_batch", "hk_points_check_g1",
-           "hk_points_check_g2"]
+           "hk_points_check_g2", "hk_qap_eval", "hk_keygen"]
 
 HK_VERIFY_CHECK_POINTS = 1
 VERDICT_REJECT, VERDICT_ACCEPT, VERDICT_BAD_POINT = 0, 1, 2
@@ -160,6 +176,9 @@ def load():
     lib.hk_verify_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, C.c_uint, vp, vp]
     lib.hk_points_check_g1.argtypes = [vp, vp, sz, vp]
     lib.hk_points_check_g2.argtypes = [vp, vp, sz, vp]
+    lib.hk_qap_eval.argtypes = [vp, C.POINTER(hk_csr), C.POINTER(hk_csr), C.POINTER(hk_csr), sz, sz, sz, vp, vp, vp, vp, vp,
+                                C.POINTER(sz)]
+    lib.hk_keygen.argtypes = [vp, C.POINTER(hk_keygen_desc), C.POINTER(hk_keygen_out), C.POINTER(sz)]
     _lib = lib
     return lib
 
@@ -515,6 +534,84 @@ class Context:
                                       n_inst, n_constraints, ptr(z), nv, out.ctypes.data, m, C.byref(m_out)),
               "hk_witness_map")
         return out, m_out.value
+
+    @staticmethod
+    def _csrs(matrices, keep):
+        """hk_csr structs over (row_ptr, col, val) triples; each member a numpy array (host) or a DeviceBuffer (device)."""
+        out = []
+        for (rp, col, val) in matrices:
+            arrs = [x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=dt)
+                    for x, dt in ((rp, np.uint64), (col, np.uint32), (val, np.uint8))]
+            keep += arrs
+            n_rows = arrs[0].nbytes // 8 - 1
+            nnz = arrs[1].nbytes // 4
+            out.append(hk_csr(*[ptr(x).value if (x.nbytes if isinstance(x, DeviceBuffer) else x.size) else None
+                                for x in arrs], n_rows, nnz))
+        return out
+
+    def qap_eval(self, A, B, Cm, n_inst, n_constraints, n_v, t, out=None):
+        """hk_qap_eval (instance_map_with_evaluation, generator.rs:75-76) at t (int, or Montgomery bytes).  A/B/Cm: CSR
+        triples as in witness_map (members may be DeviceBuffers).  out: optional (a, b, c) DeviceBuffers of n_v Fr each.
+        Returns (a, b, c, zt, m): a/b/c Montgomery bytes (numpy, or the given DeviceBuffers), zt Montgomery bytes."""
+        from .cp_groth16 import FrCodec
+        keep = []
+        csrs = self._csrs((A, B, Cm), keep)
+        t = FrCodec(self.curve).enc1(t) if isinstance(t, int) else np.ascontiguousarray(t, dtype=np.uint8)
+        outs = out if out is not None else [np.zeros(n_v * self.fr_bytes, dtype=np.uint8) for _ in range(3)]
+        zt = np.zeros(self.fr_bytes, dtype=np.uint8)
+        m = C.c_size_t()
+        check(self.lib.hk_qap_eval(self.handle, C.byref(csrs[0]), C.byref(csrs[1]), C.byref(csrs[2]), n_inst, n_constraints,
+                                   n_v, t.ctypes.data, ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), zt.ctypes.data, C.byref(m)),
+              "hk_qap_eval")
+        return outs[0], outs[1], outs[2], zt, m.value
+
+    def keygen(self, *, matrices, n_inst, n_constraints, n_v, stage_ranges, alpha, beta, gamma, deltas, t, g1_scalar,
+               g2_scalar, on_device=False, with_qap=False):
+        """hk_keygen: generate_parameters past synthesis (generator.rs:66-224) in one device call.  Scalars are ints (or
+        Montgomery bytes); matrices: CSR triples as in witness_map; stage_ranges: [(begin, end)] over witness indices.
+        on_device: a_g, b_g, b_h, h_g come back as DeviceBuffers (the rest on the host).  Returns a dict of packed-affine
+        arrays: a_g, b_g, b_h, h_g, ck (list per stage), deltas_g, alpha_g, beta_g, gamma_abc_g, beta_h, gamma_h, deltas_h,
+        and m; with with_qap also qap_abc (3 n_v Fr, Montgomery bytes, a | b | c)."""
+        from .cp_groth16 import FrCodec
+        fc = FrCodec(self.curve)
+        enc = lambda x: fc.enc1(x) if isinstance(x, int) else np.ascontiguousarray(x, dtype=np.uint8)
+        keep = []
+        csrs = self._csrs(matrices, keep)
+        ns = len(stage_ranges)
+        m = 1
+        while m < n_constraints + n_inst:
+            m *= 2
+        g1, g2 = self.g1_bytes, self.g2_bytes
+
+        def buf(nbytes, dev=False):
+            return DeviceBuffer(self, nbytes) if dev else np.zeros(nbytes, dtype=np.uint8)
+        res = dict(a_g=buf(n_v * g1, on_device), b_g=buf(n_v * g1, on_device), b_h=buf(n_v * g2, on_device),
+                   h_g=buf(max(m - 1, 0) * g1, on_device), ck=[buf((e - b) * g1) for b, e in stage_ranges],
+                   deltas_g=buf(ns * g1), alpha_g=buf(g1), beta_g=buf(g1), gamma_abc_g=buf(n_inst * g1), beta_h=buf(g2),
+                   gamma_h=buf(g2), deltas_h=buf(ns * g2))
+        if with_qap:
+            res["qap_abc"] = buf(3 * n_v * self.fr_bytes)
+        sr = np.array([v for be in stage_ranges for v in be], dtype=np.uint64)
+        sc = [enc(x) for x in (alpha, beta, gamma, t, g1_scalar, g2_scalar)]
+        dl = np.concatenate([enc(x) for x in deltas]) if ns else np.zeros(0, np.uint8)
+        keep += [sr, dl] + sc
+        d = hk_keygen_desc(C.pointer(csrs[0]), C.pointer(csrs[1]), C.pointer(csrs[2]), n_inst, n_constraints, n_v,
+                           sr.ctypes.data if ns else None, ns, *[x.ctypes.data for x in sc], dl.ctypes.data if ns else None)
+        ckp = (C.c_void_p * max(ns, 1))(*[ptr(x).value if x.size else None for x in res["ck"]])
+        pp = lambda x: ptr(x).value if (x.nbytes if isinstance(x, DeviceBuffer) else x.size) else None
+        o = hk_keygen_out(pp(res["a_g"]), pp(res["b_g"]), pp(res["b_h"]), pp(res["h_g"]), ckp,
+                          *[pp(res[k]) for k in ("deltas_g", "alpha_g", "beta_g", "gamma_abc_g", "beta_h", "gamma_h",
+                                                 "deltas_h")], pp(res["qap_abc"]) if with_qap else None)
+        m_out = C.c_size_t()
+        try:
+            check(self.lib.hk_keygen(self.handle, C.byref(d), C.byref(o), C.byref(m_out)), "hk_keygen")
+        except HekatonError:
+            for k in ("a_g", "b_g", "b_h", "h_g"):
+                if isinstance(res[k], DeviceBuffer):
+                    res[k].free()
+            raise
+        res["m"] = m_out.value
+        return res
 
     def points_check(self, group, pts, n=None):
         """hk_points_check_g1 / _g2: ark's AffineRepr::check of each point (on its curve, in the prime-order subgroup;

@@ -438,6 +438,51 @@ def generate_parameters(circuit, curve, rng, ctx, keep_on_device=False):
     return setup_device(setup_host(circuit, curve, rng), ctx, keep_on_device)
 
 
+def generate_parameters_device(circuit, curve, rng, ctx, keep_on_device=False, with_qap=False):
+    """generator.rs:18-238 with everything past synthesis in ONE device call (hk_keygen): the QAP at t, every scalar and
+    every fixed-base sweep.  Draws from `rng` exactly as `setup_host` does (alpha, beta, gamma, the deltas, the generator
+    scalars, synthesis, then t), so the same seed gives the same ProvingKey as `generate_parameters`, byte for byte.
+    keep_on_device: a_g, b_g, b_h, h_g stay DeviceBuffers (ProvingKey.upload takes them without a host copy).
+    Returns (ProvingKey, Trapdoor).  The trapdoor's a, b, c (the QAP evaluations at t) are filled only with
+    with_qap=True (hk_keygen's qap_abc output); otherwise they are None - zt and m are always set."""
+    p = CURVE_PARAMS[curve]
+    r = p["r"]
+    fc = FrCodec(curve)
+    alpha, beta, gamma = rng.fr(r) or 1, rng.fr(r) or 1, rng.fr(r) or 1
+    deltas = [rng.fr(r) or 1 for _ in range(circuit.total_num_stages())]
+    g1s, g2s = rng.fr(r) or 1, rng.fr(r) or 1
+    fast = hasattr(circuit, "qap_evaluate")
+    cs = MultiStageConstraintSystem(r, construct_matrices=not fast)
+    for stage in range(circuit.total_num_stages()):
+        circuit.generate_constraints(stage, cs)
+    cs.finalize()
+    n_inst, n_wit, n_c = cs.num_instance_variables(), cs.num_witness_variables(), cs.num_constraints()
+    t = rng.fr(r)
+    if fast:
+        matrices = circuit.csr(fc)
+    else:
+        matrices = tuple(csr_from_rows(fc, M) for M in cs.to_matrices())
+    ranges = list(cs.variable_range_for_stage)
+    res = ctx.keygen(matrices=matrices, n_inst=n_inst, n_constraints=n_c, n_v=n_inst + n_wit, stage_ranges=ranges,
+                     alpha=alpha, beta=beta, gamma=gamma, deltas=deltas, t=t, g1_scalar=g1s, g2_scalar=g2s,
+                     on_device=keep_on_device, with_qap=with_qap)
+    m = res["m"]
+    g1b, g2b = ctx.g1_bytes, ctx.g2_bytes
+    vk = VerifyingKey(alpha_g=res["alpha_g"], beta_h=res["beta_h"], gamma_h=res["gamma_h"],
+                      last_delta_h=res["deltas_h"][-g2b:], gamma_abc_g=res["gamma_abc_g"], deltas_h=res["deltas_h"])
+    ck = CommitterKey(last_delta_g=res["deltas_g"][-g1b:], deltas_abc_g=list(res["ck"]))
+    pk = ProvingKey(vk=vk, beta_g=res["beta_g"], a_g=res["a_g"], b_g=res["b_g"], b_h=res["b_h"], h_g=res["h_g"], ck=ck,
+                    deltas_g=res["deltas_g"], matrices=matrices, n_inst=n_inst, n_constraints=n_c)
+    a = b = c = None
+    if with_qap:
+        n_v = n_inst + n_wit
+        abc = fc.dec(res["qap_abc"])
+        a, b, c = abc[:n_v], abc[n_v:2 * n_v], abc[2 * n_v:]
+    td = Trapdoor(alpha, beta, gamma, deltas, t, g1s, g2s, a, b, c, (pow(t, m, r) - 1) % r, m,
+                  stage_ranges=ranges, n_inst=n_inst)
+    return pk, td
+
+
 # --------------------------------------------------------------------------------------- prover
 class CPGroth16:
     """prover.rs:15-171.  `cs`/`circuit` as in the reference; `pk` must be uploaded (ProvingKey.upload)."""

@@ -571,6 +571,16 @@ hk_status hk_prove_batch(hk_ctx* ctx, const hk_pk* pk, const void* z, size_t n_v
     return ctx->ops->prove_batch(ctx, pk, z, n_v, r, s, kappas, n_kappas, batch, a, b, c);
 }
 
+hk_status hk_qap_eval(hk_ctx* ctx, const hk_csr* A, const hk_csr* B, const hk_csr* C, size_t n_inst, size_t n_constraints,
+                      size_t n_v, const void* t, void* a, void* b, void* c, void* zt, size_t* m_out) {
+    if (!ctx) return HK_ERR_ARG;
+    return ctx->ops->qap_eval(ctx, A, B, C, n_inst, n_constraints, n_v, t, a, b, c, zt, m_out);
+}
+hk_status hk_keygen(hk_ctx* ctx, const hk_keygen_desc* desc, const hk_keygen_out* out, size_t* m_out) {
+    if (!ctx || !desc || !out) return HK_ERR_ARG;
+    return ctx->ops->keygen(ctx, desc, out, m_out);
+}
+
 }  // extern "C"
 
 // ---- host utility: Keccak-f[1600], the permutation under the merlin transcripts of the aggregator (STROBE-128;

@@ -176,6 +176,9 @@ struct CurveOps {
     hk_status (*verify_batch)(hk_ctx*, const hk_vk*, const void* a, const void* b, const void* c, const void* ds, const void* inputs,
                               size_t n, unsigned flags, const void* rand, unsigned char* verdicts);
     hk_status (*points_check)(hk_ctx*, int group, const void* pts, size_t n, unsigned char* ok);
+    hk_status (*qap_eval)(hk_ctx*, const hk_csr* A, const hk_csr* B, const hk_csr* C, size_t n_inst, size_t n_c, size_t n_v,
+                          const void* t, void* a, void* b, void* c, void* zt, size_t* m_out);
+    hk_status (*keygen)(hk_ctx*, const hk_keygen_desc*, const hk_keygen_out*, size_t* m_out);
 };
 const CurveOps* curve_ops_bn254();
 const CurveOps* curve_ops_bls381();

@@ -85,6 +85,48 @@ struct ProvingKey {
 
 struct Proof { Bytes a, b, c; std::vector<Bytes> ds; };          // data_structures.rs:7-16
 
+// generate_parameters past synthesis (generator.rs:66-224) in one device call (hk_keygen): the toxic waste (one Fr each,
+// Montgomery bytes; deltas: one per stage, concatenated) and the class's matrices in, the key out - pk's matrices, sizes
+// and every array it holds; the verifying-key parts it does not hold (gamma_h, gamma_abc_g, every stage's delta_h) go to
+// the optional vk_* outputs.
+struct SetupTrapdoor { Bytes alpha, beta, gamma, t, g1_scalar, g2_scalar, deltas; };
+inline void generate_parameters(const Context& ctx, const Csr& A, const Csr& B, const Csr& C, size_t n_inst, size_t n_constraints,
+                                size_t n_v, const std::vector<std::pair<uint64_t, uint64_t>>& stage_ranges,
+                                const SetupTrapdoor& td, ProvingKey& pk, Bytes* vk_gamma_h = nullptr,
+                                Bytes* vk_gamma_abc_g = nullptr, Bytes* vk_deltas_h = nullptr) {
+    const Sizes& z = ctx.sizes();
+    size_t m = 1;
+    while (m < n_constraints + n_inst) m <<= 1;
+    const size_t ns = stage_ranges.size();
+    pk.A = A; pk.B = B; pk.C = C;
+    pk.n_inst = n_inst; pk.n_constraints = n_constraints;
+    pk.a_g.assign(n_v * z.g1, 0); pk.b_g.assign(n_v * z.g1, 0); pk.b_h.assign(n_v * z.g2, 0); pk.h_g.assign((m - 1) * z.g1, 0);
+    pk.deltas_g.assign(ns * z.g1, 0); pk.alpha_g.assign(z.g1, 0); pk.beta_g.assign(z.g1, 0); pk.beta_h.assign(z.g2, 0);
+    pk.ck_deltas_abc_g.assign(ns, Bytes());
+    std::vector<void*> ckp(ns);
+    std::vector<uint64_t> sr;
+    for (size_t k = 0; k < ns; k++) {
+        pk.ck_deltas_abc_g[k].assign((stage_ranges[k].second - stage_ranges[k].first) * z.g1, 0);
+        ckp[k] = pk.ck_deltas_abc_g[k].data();
+        sr.push_back(stage_ranges[k].first);
+        sr.push_back(stage_ranges[k].second);
+    }
+    Bytes gamma_h(z.g2), gamma_abc_g(n_inst * z.g1), deltas_h(ns * z.g2);
+    hk_csr a{A.row_ptr.data(), A.col.data(), A.val_mont.data(), A.row_ptr.size() - 1, A.col.size()};
+    hk_csr b{B.row_ptr.data(), B.col.data(), B.val_mont.data(), B.row_ptr.size() - 1, B.col.size()};
+    hk_csr c{C.row_ptr.data(), C.col.data(), C.val_mont.data(), C.row_ptr.size() - 1, C.col.size()};
+    hk_keygen_desc d{&a, &b, &c, n_inst, n_constraints, n_v, sr.data(), ns, td.alpha.data(), td.beta.data(), td.gamma.data(),
+                     td.t.data(), td.g1_scalar.data(), td.g2_scalar.data(), td.deltas.data()};
+    hk_keygen_out o{pk.a_g.data(), pk.b_g.data(), pk.b_h.data(), pk.h_g.data(), ckp.data(), pk.deltas_g.data(), pk.alpha_g.data(),
+                    pk.beta_g.data(), gamma_abc_g.data(), pk.beta_h.data(), gamma_h.data(), deltas_h.data(), nullptr};
+    check(hk_keygen(ctx.raw(), &d, &o, nullptr), "hk_keygen");
+    pk.last_delta_h.assign(deltas_h.end() - z.g2, deltas_h.end());
+    if (vk_gamma_h) *vk_gamma_h = gamma_h;
+    if (vk_gamma_abc_g) *vk_gamma_abc_g = gamma_abc_g;
+    if (vk_deltas_h) *vk_deltas_h = deltas_h;
+}
+
+
 // constraint_synthesizer.rs:14-117 — assignments only (matrices are static per class and live with the key)
 struct MultiStageConstraintSystem {
     size_t fr_bytes;

@@ -767,6 +767,52 @@ hk_status Ops<C>::msm_bases(hk_ctx* ctx, const hk_bases* h, const void* scalars,
     return b->group == 1 ? run(Fq()) : run(Fq2());
 }
 
+// The window table of a fixed-base call's base, from the context's cache (hk_fixed_base): `base` (host bytes, or nullptr for a
+// device base, which is never cached) found there ready -> table, build = false; found while another call builds it, or
+// no free slot -> table = nullptr (the call builds into its own scratch); else a new slot is claimed -> table, build = true,
+// and publish() after the call's settle marks it ready.  A call that fails after claiming a slot retires it: the entry
+// never matches again (its base may claim another).
+struct FbCacheUse {
+    hk_ctx* c;
+    int slot = -1;
+    bool done = false;
+    void* table = nullptr;
+    bool build = true;
+    FbCacheUse(hk_ctx* ctx, int group, const void* base, size_t base_bytes, size_t tbytes) : c(ctx) {
+        if (!base || getenv("HK_FB_NO_CACHE")) return;
+        std::string key((const char*)base, base_bytes);
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        for (auto& e : ctx->fb_cache)
+            if (e.group == group && e.base == key) {
+                if (e.ready) { table = e.table; build = false; }
+                slot = -2;                                       // present (ready, or being built by another call)
+                break;
+            }
+        if (slot == -1 && ctx->fb_cache.size() < (size_t)hk_ctx::FB_CACHE_MAX) {
+            void* t = nullptr;
+            if (hipMalloc(&t, tbytes) == hipSuccess) {
+                ctx->fb_cache.push_back({group, key, t, false});
+                slot = (int)ctx->fb_cache.size() - 1;
+                table = t;
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+    }
+    void publish() {
+        if (slot >= 0) {
+            std::lock_guard<std::mutex> lk(c->mu);
+            c->fb_cache[slot].ready = true;
+        }
+        done = true;
+    }
+    ~FbCacheUse() {
+        if (slot < 0 || done) return;
+        std::lock_guard<std::mutex> lk(c->mu);
+        c->fb_cache[slot].group = -1;
+    }
+};
+
 template <class C>
 hk_status Ops<C>::fixed_base(hk_ctx* ctx, int group, const void* base, const void* scalars, size_t n, int mont,
                              void* out) {
@@ -792,39 +838,9 @@ hk_status Ops<C>::fixed_base(hk_ctx* ctx, int group, const void* base, const voi
         // the base's window table: from the context's cache when this base has been multiplied before (host bases only: the
         // key is the base's bytes), else built now - into a cache slot when one is free, into the lane's scratch otherwise
         const size_t tbytes = sizeof(Affine<F>) * FB_WINDOWS * 256;
-        Affine<F>* table = nullptr;
-        bool build = true;
-        int slot = -1;
-        struct SlotGuard {                                       // a call that fails after claiming a slot retires it: the
-            hk_ctx* c;                                           // entry never matches again (its base may claim another)
-            int* slot;
-            bool done;
-            ~SlotGuard() {
-                if (*slot < 0 || done) return;
-                std::lock_guard<std::mutex> lk(c->mu);
-                c->fb_cache[*slot].group = -1;
-            }
-        } claimed{ctx, &slot, false};
-        if (!is_device_ptr(base) && !getenv("HK_FB_NO_CACHE")) {
-            std::string key((const char*)base, sizeof(Affine<F>));
-            std::lock_guard<std::mutex> lk(ctx->mu);
-            for (auto& e : ctx->fb_cache)
-                if (e.group == group && e.base == key) {
-                    if (e.ready) { table = (Affine<F>*)e.table; build = false; }
-                    slot = -2;                                   // present (ready, or being built by another call)
-                    break;
-                }
-            if (slot == -1 && ctx->fb_cache.size() < (size_t)hk_ctx::FB_CACHE_MAX) {
-                void* t = nullptr;
-                if (hipMalloc(&t, tbytes) == hipSuccess) {
-                    ctx->fb_cache.push_back({group, key, t, false});
-                    slot = (int)ctx->fb_cache.size() - 1;
-                    table = (Affine<F>*)t;
-                } else {
-                    (void)hipGetLastError();
-                }
-            }
-        }
+        FbCacheUse claimed(ctx, group, is_device_ptr(base) ? nullptr : base, sizeof(Affine<F>), tbytes);
+        Affine<F>* table = (Affine<F>*)claimed.table;
+        bool build = claimed.build;
         HK_TRY(to_device(L, base, sizeof(Affine<F>), &bd));
         HK_TRY(to_device(L, scalars, n * sizeof(Fr), &sd));
         if (!table) table = tab_s;
@@ -833,11 +849,7 @@ hk_status Ops<C>::fixed_base(hk_ctx* ctx, int group, const void* base, const voi
         HK_TRY(MsmRun<F>::fixed_base(L->stream, (const Affine<F>*)bd, sd, mont, (u32)n, table, xy, pref, od, build));
         if (!out_dev) HK_HIP(hipMemcpyAsync(out, od, n * sizeof(Affine<F>), hipMemcpyDeviceToHost, L->stream));
         HK_TRY(L->settle());
-        if (slot >= 0) {                                         // the table is complete: later calls may read it
-            std::lock_guard<std::mutex> lk(ctx->mu);
-            ctx->fb_cache[slot].ready = true;
-        }
-        claimed.done = true;
+        claimed.publish();                                       // the table is complete: later calls may read it
         return HK_OK;
     };
     return group == 1 ? run(Fq()) : run(Fq2());
@@ -1805,3 +1817,5 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
 }
 
 }  // namespace hk
+
+#include "keygen.cuh"

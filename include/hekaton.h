@@ -98,6 +98,9 @@ typedef struct {
     float accum_kernel_ms; /* sum over this call's k_msm_accum0<Fq> launches (dominant kernel),  */
     uint32_t accum_kernel_launches;  /* timed on the kernel itself; and how many launches that was */
     float accum_h_ms;      /* the H-query launch alone (the dense one)                             */
+    float keygen_qap_ms;      /* hk_keygen only (total_ms spans the call): the QAP at t (Lagrange coefficients +   */
+    float keygen_scalars_ms;  /* column sums), the scalar assembly, and every fixed-base sweep with its copy-out    */
+    float keygen_sweeps_ms;
 } hk_timings;
 
 const char* hk_status_str(hk_status s);
@@ -418,6 +421,50 @@ hk_status hk_verify_batch(hk_ctx* ctx, const hk_vk* vk, const void* a_g1, const 
  * what deserialize_* with Validate::Yes runs).  points [h|d] n packed affine, ok [h|d] n bytes. */
 hk_status hk_points_check_g1(hk_ctx* ctx, const void* points, size_t n, uint8_t* ok);
 hk_status hk_points_check_g2(hk_ctx* ctx, const void* points, size_t n, uint8_t* ok);
+
+/* ---- trusted setup past synthesis (cp-groth16/src/generator.rs:66-224) ---------------------------------------------
+ * Both entries take the class's matrices in the hk_csr form of hk_witness_map / hk_pk_upload ([h|d]).  Errors, checked in
+ * this order: HK_ERR_DOMAIN_TOO_LARGE when log2(m) exceeds the curve's two-adicity (from the sizes alone, before any array
+ * is read); HK_ERR_ARG for a NULL required pointer, a matrix with n_rows != n_constraints, n_v, an nnz or m >= 2^32,
+ * n_inst == 0 or > n_v (hk_keygen also: stage ranges that do not tile [0, n_v - n_inst) in order, a zero gamma or delta);
+ * then, found on the device: HK_ERR_ARG for a column index >= n_v or a row_ptr that decreases or does not end at nnz, and
+ * HK_ERR_ARG for t in the domain (zt = 0; generator.rs:68 never draws one).  hk_keygen writes no point output unless all
+ * of these pass; the contents of hk_qap_eval's outputs after a failed call are undefined.  A failed call leaves the lane
+ * usable. */
+
+/* LibsnarkReduction::instance_map_with_evaluation (cp-groth16/src/generator.rs:75-76): a_j = sum_i A_ij u_i(t) + u_(n_c+j)(t)
+ * for j < n_inst, b_j and c_j likewise without the instance rows, u_i the Lagrange coefficients of the domain of size m
+ * (the next power of two >= n_constraints + n_inst) at t.  t_mont [h]: 1 Fr; a/b/c_out [h|d]: n_v Fr (Montgomery);
+ * zt_out [h]: t^m - 1 (1 Fr, Montgomery); *m_out = m (m_out may be NULL). */
+hk_status hk_qap_eval(hk_ctx* ctx, const hk_csr* A, const hk_csr* B, const hk_csr* C, size_t n_inst,
+                      size_t n_constraints, size_t n_v, const void* t_mont,
+                      void* a_out, void* b_out, void* c_out, void* zt_out, size_t* m_out);
+
+/* The toxic waste and the class: every Fr [h], 1 element each, Montgomery. */
+typedef struct {
+    const hk_csr *A, *B, *C;
+    size_t n_inst, n_constraints, n_v;
+    const uint64_t* stage_ranges; size_t n_stages;   /* [h] [begin, end) per stage over witness indices, in order */
+    const void *alpha, *beta, *gamma, *t, *g1_scalar, *g2_scalar;
+    const void* deltas;                               /* n_stages Fr */
+} hk_keygen_desc;
+
+/* Where the key goes: every pointer [h|d], packed affine; layouts = ProvingKey (cp-groth16/src/data_structures.rs:66-83). */
+typedef struct {
+    void *a_g, *b_g, *b_h, *h_g;      /* n_v G1, n_v G1, n_v G2, m - 1 G1 (h_g may be NULL when m == 1) */
+    void* const* ck_stage;            /* [h] n_stages pointers; stage k: (end - begin) G1 (NULL allowed for an empty stage) */
+    void *deltas_g, *alpha_g, *beta_g, *gamma_abc_g;   /* n_stages, 1, 1, n_inst G1 */
+    void *beta_h, *gamma_h, *deltas_h;                 /* 1, 1, n_stages G2 */
+    void* qap_abc;                    /* optional (NULL: not written): 3 n_v Fr, a | b | c at t, Montgomery */
+} hk_keygen_out;
+
+/* generate_parameters past synthesis (generator.rs:66-224): the QAP at t (as hk_qap_eval), every scalar of the key -
+ * (beta a_i + alpha b_i + c_i) / delta_k over stage k's witness range, / gamma over the instance, zt t^i / delta_last for
+ * i < m - 1 - and every fixed-base sweep over the standard generators times g1_scalar / g2_scalar, without a host round
+ * trip: a_g = a_i g1s G1, b_g = b_i g1s G1, b_h = b_i g2s G2, h_g, ck, gamma_abc_g, alpha_g = alpha g1s G1, beta_g,
+ * deltas_g = delta_k g1s G1, beta_h = beta g2s G2, gamma_h, deltas_h.  *m_out = m (may be NULL).  The sweeps share the
+ * context's window-table cache with hk_fixed_base_g1 / _g2.  Errors: see above. */
+hk_status hk_keygen(hk_ctx* ctx, const hk_keygen_desc* desc, const hk_keygen_out* out, size_t* m_out);
 
 #ifdef __cplusplus
 }
