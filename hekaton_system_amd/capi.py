@@ -76,7 +76,7 @@ class hk_timings(C.Structure):
                 ("total_ms", "digits_ms", "msm_a_ms", "msm_b_g1_ms", "msm_b_g2_ms", "msm_l_ms",
                  "witness_map_ms", "msm_h_ms", "finish_ms", "accum_kernel_ms")] + \
                [("accum_kernel_launches", C.c_uint32), ("accum_h_ms", C.c_float), ("keygen_qap_ms", C.c_float),
-                ("keygen_scalars_ms", C.c_float), ("keygen_sweeps_ms", C.c_float)]
+                ("keygen_scalars_ms", C.c_float), ("keygen_sweeps_ms", C.c_float), ("batch_proofs", C.c_uint32)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}

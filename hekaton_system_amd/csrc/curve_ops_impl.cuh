@@ -118,8 +118,7 @@ struct Ops {
     static void pk_free(hk_pk*);
     static hk_status commit(hk_ctx*, const hk_pk*, size_t, const void*, size_t, const void*, void*);
     static hk_status commit_batch(hk_ctx*, const hk_pk*, size_t, const void*, size_t, const void*, size_t, void*);
-    static hk_status prove_batch(hk_ctx*, const hk_pk*, const void*, size_t, const void*, const void*,
-                                 const void*, size_t, size_t, void*, void*, void*);
+    static hk_status prove_batch(hk_ctx*, const hk_pk*, size_t, size_t, const ProveRow*, size_t);
     static void ctx_release(hk_ctx*);
     static hk_status fixed_base(hk_ctx*, int, const void*, const void*, size_t, int, void*);
     static hk_status scalar_pairing(hk_ctx*, int, const void*, const void*, size_t, void*);

@@ -563,12 +563,46 @@ hk_status hk_commit_batch(hk_ctx* ctx, const hk_pk* pk, size_t stage, const void
 hk_status hk_prove(hk_ctx* ctx, const hk_pk* pk, const void* z, size_t n_v, const void* r, const void* s,
                    const void* kappas, size_t n_kappas, void* a, void* b, void* c) {
     if (!ctx || !pk || !z || !r || !s || !a || !b || !c) return HK_ERR_ARG;
-    return ctx->ops->prove_batch(ctx, pk, z, n_v, r, s, kappas, n_kappas, 1, a, b, c);   // a batch of one
+    // a bad call fails on its own thread and never joins a batch: key and lengths (a batch of none only validates), kappas
+    HK_TRY(ctx->ops->prove_batch(ctx, pk, n_v, n_kappas, nullptr, 0));
+    if (n_kappas && !kappas) return HK_ERR_ARG;
+    // concurrent calls of this key meet in the context's coalescer and run as one lock-step batch;
+    // a lone call leads at once, a batch of one
+    const hk::ProveCall call = {{z, r, s, kappas, a, b, c}, n_v, n_kappas};
+    hk::ProveResult res = ctx->prove_q.submit(pk, call, [&](const hk_pk* key, hk::ProveCoalescer::Member* const* ms, size_t n) {
+        std::vector<hk::ProveRow> rows(n);
+        for (size_t i = 0; i < n; i++) rows[i] = ms[i]->item->row;
+        // the key's lengths, from its own calls: the leader's n_v / n_kappas belong to the leader's key
+        hk_status st = ctx->ops->prove_batch(ctx, key, ms[0]->item->n_v, ms[0]->item->n_kappas, rows.data(), n);
+        // every member's share of the chunk: each *_ms figure over the chunk's proofs, four accumulate launches as for
+        // one proof (bench.py and the roofline divide per-proof bytes by accum_kernel_ms / accum_kernel_launches)
+        hk_timings t = tl_last_timings;      // the lane's timings, published by prove_batch's LaneGuard on this thread
+        const float f = 1.0f / (float)n;
+        for (float* x : {&t.total_ms, &t.digits_ms, &t.msm_a_ms, &t.msm_b_g1_ms, &t.msm_b_g2_ms, &t.msm_l_ms, &t.witness_map_ms,
+                         &t.msm_h_ms, &t.finish_ms, &t.accum_kernel_ms, &t.accum_h_ms, &t.keygen_qap_ms, &t.keygen_scalars_ms,
+                         &t.keygen_sweeps_ms})
+            *x *= f;
+        if (t.accum_kernel_launches) t.accum_kernel_launches = 4;
+        t.batch_proofs = (uint32_t)n;
+        for (size_t i = 0; i < n; i++) ms[i]->result = hk::ProveResult{st, t};
+    });
+    tl_last_timings = res.timings;
+    return res.status;
 }
 hk_status hk_prove_batch(hk_ctx* ctx, const hk_pk* pk, const void* z, size_t n_v, const void* r, const void* s,
                          const void* kappas, size_t n_kappas, size_t batch, void* a, void* b, void* c) {
     if (!ctx || !pk) return HK_ERR_ARG;
-    return ctx->ops->prove_batch(ctx, pk, z, n_v, r, s, kappas, n_kappas, batch, a, b, c);
+    HK_TRY(ctx->ops->prove_batch(ctx, pk, n_v, n_kappas, nullptr, 0));      // key and lengths first, as documented
+    if (batch == 0) return HK_OK;
+    if (!z || !r || !s || !a || !b || !c || (n_kappas && !kappas)) return HK_ERR_ARG;
+    // row b of the arrays, row after row
+    const size_t fr = ctx->ops->fr_bytes, g1 = ctx->ops->g1_bytes, g2 = ctx->ops->g2_bytes;
+    std::vector<hk::ProveRow> rows(batch);
+    for (size_t i = 0; i < batch; i++)
+        rows[i] = {(const char*)z + i * n_v * fr, (const char*)r + i * fr, (const char*)s + i * fr,
+                   n_kappas ? (const char*)kappas + i * n_kappas * fr : nullptr, (char*)a + i * g1, (char*)b + i * g2,
+                   (char*)c + i * g1};
+    return ctx->ops->prove_batch(ctx, pk, n_v, n_kappas, rows.data(), batch);
 }
 
 hk_status hk_qap_eval(hk_ctx* ctx, const hk_csr* A, const hk_csr* B, const hk_csr* C, size_t n_inst, size_t n_constraints,

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/hekaton.h"
+#include "coalesce.h"
 #include "msm.cuh"
 
 #define HK_HIP(expr)                                                                         \
@@ -113,6 +114,32 @@ struct Lane {
 
 struct NttTables;   // ntt.hip
 
+// one proof of a prove_batch call: its own assignment (host or device), blinders, kappas and host outputs
+struct ProveRow {
+    const void* z;                // n_v Fr, Montgomery [h|d]
+    const void* r;                // 1 Fr [h]
+    const void* s;                // 1 Fr [h]
+    const void* kappas;           // n_kappas Fr [h]
+    void *a, *b, *c;              // proof.a (G1), proof.b (G2), proof.c (G1) [h]
+};
+
+// what the coalescer hands each member of a batch: the batch's status and this proof's share of its timings
+struct ProveResult {
+    hk_status status;
+    hk_timings timings;
+};
+
+// a queued hk_prove call: its row and the lengths it was validated with (those of its key - a leader may run another
+// key's calls than its own)
+struct ProveCall {
+    ProveRow row;
+    size_t n_v, n_kappas;
+};
+
+// hk_prove's coalescer: at most PROVE_COALESCE_RUNNING coalesced batches of a context run at once
+enum { PROVE_COALESCE_RUNNING = 2 };
+typedef Coalescer<const hk_pk*, ProveCall, ProveResult> ProveCoalescer;
+
 }  // namespace hk
 
 namespace hk {
@@ -168,8 +195,8 @@ struct CurveOps {
                                     size_t n_v, void* z_out);
     hk_status (*commit_batch)(hk_ctx*, const hk_pk*, size_t stage, const void* w, size_t n, const void* kappas, size_t batch,
                               void* out);
-    hk_status (*prove_batch)(hk_ctx*, const hk_pk*, const void* z, size_t n_v, const void* r, const void* s,
-                             const void* kappas, size_t n_kappas, size_t batch, void* a, void* b, void* c);
+    // `batch` proofs of one key, row b from rows[b]; batch == 0 only validates (key, n_v, n_kappas) and touches nothing
+    hk_status (*prove_batch)(hk_ctx*, const hk_pk*, size_t n_v, size_t n_kappas, const ProveRow* rows, size_t batch);
     hk_status (*vk_prepare)(hk_ctx*, const hk_vk_desc*, hk_vk**);
     void (*vk_free)(hk_vk*);
     hk_status (*vk_alpha_beta)(const hk_vk*, void*);
@@ -203,6 +230,8 @@ struct hk_ctx {
     struct FbTable { int group; std::string base; void* table; bool ready; };
     enum { FB_CACHE_MAX = 8 };
     std::vector<FbTable> fb_cache;
+    // concurrent hk_prove calls of one key meet here and run as one lock-step batch (hk_core.hip)
+    hk::ProveCoalescer prove_q{hk::PROVE_COALESCE_RUNNING, HK_PROVE_BATCH_CHUNK, hk::ProveResult{HK_ERR_NOMEM, {}}};
 };
 
 struct hk_pk {

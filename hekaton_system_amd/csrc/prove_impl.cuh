@@ -1621,12 +1621,12 @@ hk_status Ops<C>::commit_batch(hk_ctx* ctx, const hk_pk* h, size_t stage, const 
     return HK_OK;
 }
 
-// hk_prove is a batch of one.  A batch runs in chunks of up to HK_PROVE_BATCH_CHUNK proofs, every stage one launch for
-// the chunk (proof = grid.y, or grid.x for the one-workgroup stages), each proof on its own slice of the buffers; all
-// read the key's shared shift tables.
+// hk_prove_batch and hk_prove's coalesced batches (a lone hk_prove is a batch of one).  A batch runs in chunks of up to
+// HK_PROVE_BATCH_CHUNK proofs, every stage one launch for the chunk (proof = grid.y, or grid.x for the one-workgroup
+// stages), each proof on its own slice of the buffers; all read the key's shared shift tables.  Row b's inputs and outputs
+// live wherever rows[b] points: a chunk may mix host and device assignments.
 template <class C>
-hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t n_v, const void* r_m, const void* s_m,
-                              const void* kappas, size_t n_kappas, size_t batch, void* out_a, void* out_b, void* out_c) {
+hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_kappas, const ProveRow* rows, size_t batch) {
     typedef QapHost<C> Q;
     if (h->ctx != ctx) return HK_ERR_ARG;
     PkImpl<C>* pk = (PkImpl<C>*)h->impl;
@@ -1634,7 +1634,11 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
     if (n_v != pk->n_v) return HK_ERR_LEN;
     if (n_kappas + 1 != pk->n_stages) return HK_ERR_LEN;   // committer.rs:112 assert
     if (batch == 0) return HK_OK;
-    if (!z || !r_m || !s_m || !out_a || !out_b || !out_c || (n_kappas && !kappas)) return HK_ERR_ARG;
+    if (!rows) return HK_ERR_ARG;
+    for (size_t b = 0; b < batch; b++) {
+        const ProveRow& w = rows[b];
+        if (!w.z || !w.r || !w.s || !w.a || !w.b || !w.c || (n_kappas && !w.kappas)) return HK_ERR_ARG;
+    }
     NttTables* T;
     HK_TRY(NttHost<C>::ensure(ctx, pk->log_m, &T));
     LaneGuard g(ctx);
@@ -1642,7 +1646,12 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
     if (!L) return HK_ERR_DEVICE;
     const MsmPlan &pz = pk->plan_z, &ph = pk->plan_h, &pb = pk->plan_b;
     const size_t m = (size_t)1 << pk->log_m, fr = sizeof(Fr), rs_stride = 2 + n_kappas;
-    const bool z_dev = is_device_ptr(z);
+    std::vector<char> z_dev(batch);
+    bool any_host = false;
+    for (size_t b = 0; b < batch; b++) {
+        z_dev[b] = is_device_ptr(rows[b].z);
+        any_host = any_host || !z_dev[b];
+    }
     // the scratch of one chunk of `nb` proofs: every per-proof buffer times nb, the bucket pipelines sized by the lane plan
     // of the chunk (the chip's lanes split across it, so the boundary partials do not grow with nb)
     Fr *zext, *small, *zt, *zb, *abc;
@@ -1656,7 +1665,7 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
     auto chunk_bufs = [&](Carve& c, u32 nb) {
         zext = c.n<Fr>((size_t)pk->n_ext * nb);                               // z[1..] | r | s | rs | kappas
         small = c.n<Fr>(rs_stride * nb);                                      // [nb][2 + n_kappas]
-        zt = z_dev ? nullptr : c.n<Fr>(n_v * nb);                             // a host z, copied in
+        zt = any_host ? c.n<Fr>(n_v * nb) : nullptr;                          // host rows of z, copied in (slot = row)
         MsmSort<Fr>::alloc(c, pz, &sb, nb);
         MsmSort<Fr>::alloc(c, ph, &sbh, nb);
         sbb.count = nullptr;
@@ -1688,13 +1697,17 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
         while (chunk > 1 && chunk_bytes(chunk) > avail) chunk--;
     }
     // r | s | kappas of every proof, one row each (k_prep_ext and k_finish read them)
-    std::vector<unsigned char> rows(batch * rs_stride * fr);
+    std::vector<unsigned char> rsk(batch * rs_stride * fr);
     for (size_t b = 0; b < batch; b++) {
-        unsigned char* row = rows.data() + b * rs_stride * fr;
-        memcpy(row, (const char*)r_m + b * fr, fr);
-        memcpy(row + fr, (const char*)s_m + b * fr, fr);
-        if (n_kappas) memcpy(row + 2 * fr, (const char*)kappas + b * n_kappas * fr, n_kappas * fr);
+        unsigned char* row = rsk.data() + b * rs_stride * fr;
+        memcpy(row, rows[b].r, fr);
+        memcpy(row + fr, rows[b].s, fr);
+        if (n_kappas) memcpy(row + 2 * fr, rows[b].kappas, n_kappas * fr);
     }
+    // the chunk's proofs land here and go out row by row once the chunk has settled
+    std::vector<Affine<Fq>> ha(chunk), hc(chunk);
+    std::vector<Affine<Fq2>> hb(chunk);
+    std::vector<const Fr*> zd(chunk);
     hipStream_t s = L->stream;
     const bool prof = ctx->profiling;
     hipEvent_t* ev = L->ev;
@@ -1712,18 +1725,17 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
         // ev[0] marks the start of the call (total_ms runs from it to the last chunk's ev[8]), ev[9] that of a later chunk
         hipEvent_t ev_start = b0 ? ev[9] : ev[0];
         if (prof) HK_HIP(hipEventRecord(ev_start, s));
-        // --- extended scalar vectors [nb][n_ext]
-        const Fr* zd;
-        if (z_dev) zd = (const Fr*)z + b0 * n_v;
-        else {
-            HK_HIP(hipMemcpyAsync(zt, (const Fr*)z + b0 * n_v, n_v * nb * fr, hipMemcpyHostToDevice, s));
-            zd = zt;
+        // --- extended scalar vectors [nb][n_ext]: row j's z on the device (a host row through its zt slot), then z[1..]
+        for (u32 j = 0; j < nb; j++) {
+            if (z_dev[b0 + j]) zd[j] = (const Fr*)rows[b0 + j].z;
+            else {
+                HK_HIP(hipMemcpyAsync(zt + (size_t)j * n_v, rows[b0 + j].z, n_v * fr, hipMemcpyHostToDevice, s));
+                zd[j] = zt + (size_t)j * n_v;
+            }
+            if (n_v > 1)
+                HK_HIP(hipMemcpyAsync(zext + (size_t)j * pk->n_ext, zd[j] + 1, (n_v - 1) * fr, hipMemcpyDeviceToDevice, s));
         }
-        if (n_v > 1 && nb == 1)
-            HK_HIP(hipMemcpyAsync(zext, zd + 1, (n_v - 1) * fr, hipMemcpyDeviceToDevice, s));
-        else if (n_v > 1)
-            HK_HIP(hipMemcpy2DAsync(zext, pk->n_ext * fr, zd + 1, n_v * fr, (n_v - 1) * fr, nb, hipMemcpyDeviceToDevice, s));
-        HK_HIP(hipMemcpyAsync(small, rows.data() + b0 * rs_stride * fr, nb * rs_stride * fr, hipMemcpyHostToDevice, s));
+        HK_HIP(hipMemcpyAsync(small, rsk.data() + b0 * rs_stride * fr, nb * rs_stride * fr, hipMemcpyHostToDevice, s));
         // --- one digit sort per proof shared by the four assignment-indexed queries
         hipLaunchKernelGGL((k_prep_ext<Fr>), dim3(64), dim3(256), 0, s, zext + (n_v - 1), pk->n_ext, (const Fr*)small,
                            (u32)rs_stride, (u32)n_kappas, nb, sb.count, sbh.count, sbb.count, pz.NB * nb, ph.NB * nb,
@@ -1741,7 +1753,7 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
         HK_HIP(hipStreamWaitEvent(ax[3], ev_z, 0));
         if (prof) HK_HIP(hipEventRecord(ev[5], ax[3]));
         for (u32 j = 0; j < nb; j++)                                            // witness map: one chain per proof
-            HK_TRY(Q::run(ax[3], T, pk->csr[0], pk->csr[1], pk->csr[2], pk->n_inst, pk->n_c, zd + (size_t)j * n_v,
+            HK_TRY(Q::run(ax[3], T, pk->csr[0], pk->csr[1], pk->csr[2], pk->n_inst, pk->n_c, zd[j],
                           abc + (size_t)j * 3 * m, pk->log_m));
         if (prof) HK_HIP(hipEventRecord(ev[6], ax[3]));                        // witness map done
         HK_TRY(MsmSort<Fr>::run(ax[3], ph, (const u32*)abc, 1, sbh, true, nb, 3 * m));
@@ -1786,18 +1798,25 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
         hipLaunchKernelGGL((k_finish<Fr, Fq, Fq2>), dim3(3, nb), dim3(64), 0, s, res1, res2, pk->consts_g1, pk->consts_g2,
                            (const Fr*)small, (u32)rs_stride, oa, ob, oc, endo_g1);
         HK_HIP(hipGetLastError());
-        HK_HIP(hipMemcpyAsync((char*)out_a + b0 * sizeof(Affine<Fq>), oa, nb * sizeof(Affine<Fq>), hipMemcpyDeviceToHost, s));
-        HK_HIP(hipMemcpyAsync((char*)out_b + b0 * sizeof(Affine<Fq2>), ob, nb * sizeof(Affine<Fq2>), hipMemcpyDeviceToHost, s));
-        HK_HIP(hipMemcpyAsync((char*)out_c + b0 * sizeof(Affine<Fq>), oc, nb * sizeof(Affine<Fq>), hipMemcpyDeviceToHost, s));
+        HK_HIP(hipMemcpyAsync(ha.data(), oa, nb * sizeof(Affine<Fq>), hipMemcpyDeviceToHost, s));
+        HK_HIP(hipMemcpyAsync(hb.data(), ob, nb * sizeof(Affine<Fq2>), hipMemcpyDeviceToHost, s));
+        HK_HIP(hipMemcpyAsync(hc.data(), oc, nb * sizeof(Affine<Fq>), hipMemcpyDeviceToHost, s));
         if (prof) HK_HIP(hipEventRecord(ev[8], s));
         HK_TRY(L->settle());
+        for (u32 j = 0; j < nb; j++) {
+            memcpy(rows[b0 + j].a, &ha[j], sizeof(Affine<Fq>));
+            memcpy(rows[b0 + j].b, &hb[j], sizeof(Affine<Fq2>));
+            memcpy(rows[b0 + j].c, &hc[j], sizeof(Affine<Fq>));
+        }
         if (prof) {
             // the five queries run concurrently on side streams: each figure is the elapsed time on the query's own
             // stream since its fork point (they overlap, they do not add up to total_ms); summed over the chunks
             acc.digits_ms += ev_ms(ev_start, ev[1]);
             acc.msm_a_ms += ev_ms(ev[1], ev[2]);
-            acc.msm_b_g1_ms += ev_ms(ev[1], ev[3]);
-            acc.msm_b_g2_ms += ev_ms(ev[1], ev[4]);
+            // a compact B forks from z (its own gather and sort on aux0), not from the shared sort: it may finish before ev[1]
+            hipEvent_t fork_b = pk->b_compact ? ev_z : ev[1];
+            acc.msm_b_g1_ms += ev_ms(fork_b, ev[3]);
+            acc.msm_b_g2_ms += ev_ms(fork_b, ev[4]);
             acc.msm_l_ms += ev_ms(ev[1], ev[18]);
             acc.witness_map_ms += ev_ms(ev[5], ev[6]);
             acc.msm_h_ms += ev_ms(ev[6], ev[7]);
@@ -1811,6 +1830,7 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, const void* z, size_t
     }
     if (prof) {
         acc.total_ms = ev_ms(ev[0], ev[8]);
+        acc.batch_proofs = (uint32_t)chunk;
         L->timings = acc;
     }
     return HK_OK;

@@ -84,7 +84,10 @@ typedef struct {
 
 /* Per-phase device timings of the last hk_prove / hk_commit on the calling thread's lane,
  * measured with HIP events on the lane's stream (milliseconds). Replaces the reference's
- * start_timer!/end_timer! brackets (cp-groth16/src/prover.rs:65-150). */
+ * start_timer!/end_timer! brackets (cp-groth16/src/prover.rs:65-150).
+ * After an hk_prove that ran in a coalesced chunk of batch_proofs proofs, every *_ms field is this proof's share of the
+ * chunk (the chunk's figure / batch_proofs) and accum_kernel_launches is 4, as for a proof that ran alone.
+ * The struct grew: batch_proofs was appended after keygen_sweeps_ms; a host that mirrors it must add the field. */
 typedef struct {
     float total_ms;
     float digits_ms;       /* scalar from-Montgomery + signed-digit split + bucket sort   */
@@ -101,6 +104,7 @@ typedef struct {
     float keygen_qap_ms;      /* hk_keygen only (total_ms spans the call): the QAP at t (Lagrange coefficients +   */
     float keygen_scalars_ms;  /* column sums), the scalar assembly, and every fixed-base sweep with its copy-out    */
     float keygen_sweeps_ms;
+    uint32_t batch_proofs;    /* hk_prove / hk_prove_batch: proofs in the chunk the call ran in (1: it ran alone)       */
 } hk_timings;
 
 const char* hk_status_str(hk_status s);
@@ -344,7 +348,14 @@ hk_status hk_commit_batch(hk_ctx* ctx, const hk_pk* pk, size_t stage, const void
  *   z_mont [h|d]  full assignment instance||witness, n_v Fr Montgomery, z[0] = 1
  *   r_mont,s_mont [h] the two blinders (prover.rs:28-29)
  *   kappas_mont [h]   n_kappas = n_stages-1 commitment randomizers (committer.rs:110-113)
- * Outputs [h]: proof.a (G1), proof.b (G2), proof.c (G1), packed affine. */
+ * Outputs [h]: proof.a (G1), proof.b (G2), proof.c (G1), packed affine.
+ * Concurrent calls coalesce: a call that passes the checks (HK_ERR_ARG for a NULL pointer, a key of another context or
+ * one without QAP matrices; HK_ERR_LEN for n_v / n_kappas) queues behind the other calls of its context.  While fewer
+ * than two coalesced chunks of the context run, a caller at once leads the oldest queued key's calls - up to
+ * HK_PROVE_BATCH_CHUNK of them, its own among the candidates - through hk_prove_batch's lock-step pipeline; the others
+ * wait without holding a lane and get their own outputs, the chunk's status and their share of its hk_timings
+ * (batch_proofs tells how many proofs the chunk held).  A lone caller runs at once as a batch of one.  Every output is
+ * byte-identical to the proof the call would get alone. */
 hk_status hk_prove(hk_ctx* ctx, const hk_pk* pk, const void* z_mont, size_t n_v,
                    const void* r_mont, const void* s_mont,
                    const void* kappas_mont, size_t n_kappas,
@@ -370,7 +381,8 @@ hk_status hk_prove(hk_ctx* ctx, const hk_pk* pk, const void* z_mont, size_t n_v,
  * device's free memory plus the lane's own arena; a chunk is never smaller than one proof.
  * hk_timings after the call: total_ms spans the whole call, every phase figure is summed over the chunks (within a
  * chunk the queries overlap as in hk_prove); accum_kernel_launches counts the real k_msm_accum0<Fq> launches - four per
- * chunk (A, B1, L, H; the G2 query is not counted, as for hk_prove) - and accum_kernel_ms their summed kernel time. */
+ * chunk (A, B1, L, H; the G2 query is not counted, as for hk_prove) - and accum_kernel_ms their summed kernel time;
+ * batch_proofs is the chunk size.  hk_prove_batch does not pass through hk_prove's coalescer. */
 #define HK_PROVE_BATCH_CHUNK 8
 hk_status hk_prove_batch(hk_ctx* ctx, const hk_pk* pk, const void* z_mont, size_t n_v,
                          const void* r_mont, const void* s_mont, const void* kappas_mont, size_t n_kappas,
