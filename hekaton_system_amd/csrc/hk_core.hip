@@ -69,6 +69,12 @@ static presize_fn presize_kernel_for(size_t frame, size_t* actual) {
     return nullptr;
 }
 
+// the hardware queues the runtime gives the process: GPU_MAX_HW_QUEUES as the host set it, or the HIP runtime's default of 4
+static unsigned hw_queues() {
+    const char* q = getenv("GPU_MAX_HW_QUEUES");
+    return q && atoi(q) > 0 ? (unsigned)atoi(q) : 4u;
+}
+
 hk_status scratch_budget_check(const CurveOps* ops, const hipDeviceProp_t& prop, void** presize_out) {
     // the deepest frame of EVERY curve the library carries, not only this context's: a process that opens a context of the
     // other curve later (the bench's BLS12-381 leg after its BN254 leg) then finds every queue's ring already at its final
@@ -83,8 +89,7 @@ hk_status scratch_budget_check(const CurveOps* ops, const hipDeviceProp_t& prop,
     size_t presized = frame;
     *presize_out = (void*)presize_kernel_for(frame, &presized);
     if (presized > frame) frame = presized;                 // the ring every queue will actually hold
-    const char* q = getenv("GPU_MAX_HW_QUEUES");
-    uint64_t queues = q && atoi(q) > 0 ? (uint64_t)atoi(q) : 4;          // the HIP runtime's default
+    uint64_t queues = hw_queues();
     uint64_t slots = (uint64_t)prop.multiProcessorCount * (uint64_t)(prop.maxThreadsPerMultiProcessor / 64);
     uint64_t ring = (uint64_t)frame * 64 * slots;
     uint64_t limit = scratch_limit_bytes();
@@ -111,9 +116,10 @@ hk_status Lane::reserve(size_t bytes) {
         // trade arenas with it - the smallest that fits - instead of allocating (a hipMalloc of tens of MB takes
         // milliseconds, and which lane a call lands on is arbitrary).  An idle lane's streams have nothing in flight:
         // ~LaneGuard drains them before it marks a lane free.
+        // (within its own kind: a prove lane's arena stays with the prove lanes, which reuse it chunk after chunk)
         std::lock_guard<std::mutex> lk(owner->mu);
         Lane* best = nullptr;
-        for (Lane* l : owner->lanes)
+        for (Lane* l : prove ? owner->prove_lanes : owner->lanes)
             if (l != this && !l->busy && l->arena_cap >= bytes && (!best || l->arena_cap < best->arena_cap)) best = l;
         if (best) {
             std::swap(arena, best->arena);
@@ -135,6 +141,47 @@ hk_status Lane::reserve(size_t bytes) {
     return HK_OK;
 }
 
+// A new lane with n streams (its events, its streams, each stream's scratch ring pre-sized); nullptr when the runtime
+// refuses a stream or an event: a half-built lane would run on the legacy default stream / null events.
+static Lane* new_lane(hk_ctx* ctx, unsigned n, bool prove) {
+    Lane* l = new Lane();
+    (void)hipSetDevice(ctx->device);
+    for (auto& e : l->ev) e = nullptr;
+    l->n_streams = n;
+    l->prove = prove;
+    bool ok = true;
+    for (auto& e : l->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    for (unsigned i = 0; i < n; i++)
+        ok = ok && hipStreamCreateWithFlags(i ? &l->side[i - 1] : &l->stream, hipStreamNonBlocking) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        fprintf(stderr, "[hekaton] could not create the streams / events of a lane\n");
+        for (auto& e : l->ev) if (e) (void)hipEventDestroy(e);
+        for (unsigned i = 0; i < n; i++) if (l->stream_at(i)) (void)hipStreamDestroy(l->stream_at(i));
+        delete l;
+        return nullptr;
+    }
+    if (ctx->presize_kernel && !getenv("HK_NO_SCRATCH_PRESIZE")) {
+        // one wave of the deepest frame on each of the lane's streams, in creation order (see k_scratch_presize)
+        presize_fn k = (presize_fn)ctx->presize_kernel;
+        for (unsigned i = 0; i < n; i++) hipLaunchKernelGGL(k, dim3(1), dim3(64), 0, l->stream_at(i), (unsigned*)nullptr, 1u);
+        bool okp = true;
+        for (unsigned i = 0; i < n; i++) okp = okp && hipStreamSynchronize(l->stream_at(i)) == hipSuccess;
+        if (!okp) { (void)hipGetLastError(); fprintf(stderr, "[hekaton] scratch pre-sizing of a lane failed\n"); }
+    }
+    memset(&l->timings, 0, sizeof(l->timings));
+    l->owner = ctx;
+    return l;
+}
+
+static void free_lane(Lane* l) {
+    if (l->arena) (void)hipFree(l->arena);
+    for (void* p : l->retired) (void)hipFree(p);
+    for (auto& e : l->ev) (void)hipEventDestroy(e);
+    for (unsigned i = 0; i < l->n_streams; i++) (void)hipStreamDestroy(l->stream_at(i));
+    delete l;
+}
+
 LaneGuard::LaneGuard(hk_ctx* c) : ctx(c), lane(nullptr) {
     std::unique_lock<std::mutex> lk(ctx->mu);
     for (;;) {
@@ -145,53 +192,9 @@ LaneGuard::LaneGuard(hk_ctx* c) : ctx(c), lane(nullptr) {
             if (!l->busy && (!lane || l->arena_cap > lane->arena_cap)) lane = l;
         if (lane) break;
         if (ctx->lanes.size() < ctx->max_lanes) {
-            Lane* l = new Lane();
-            (void)hipSetDevice(ctx->device);
-            for (auto& e : l->ev) e = nullptr;
-            bool ok = hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking) == hipSuccess;
-            for (auto& e : l->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-            for (auto& a : l->aux) ok = ok && hipStreamCreateWithFlags(&a, hipStreamNonBlocking) == hipSuccess;
-            if (!ok) {                       // a half-built lane would run on the legacy default stream / null events
-                (void)hipGetLastError();
-                fprintf(stderr, "[hekaton] could not create the streams / events of a lane\n");
-                for (auto& e : l->ev) if (e) (void)hipEventDestroy(e);
-                for (auto& a : l->aux) if (a) (void)hipStreamDestroy(a);
-                if (l->stream) (void)hipStreamDestroy(l->stream);
-                delete l;
-                break;
-            }
-            // The runtime hands hardware queues to streams round robin in creation order; with 20 queues and five streams
-            // per lane the FIRST stream of lane k and of lane k + 4 share a queue, and two concurrent single-kernel calls
-            // (the aggregator's sweeps and pairings, the witness programs) on those lanes run one after the other.  Lanes
-            // 4 .. 7 therefore work on their second stream, lanes 8 .. 11 on their third, ...: queues 0, 5, 10, 15, then
-            // 1, 6, 11, 16, then 2, 7, ...  (the five streams of a lane are interchangeable for hk_prove's fork / join).
-            // Streams stay lazily created, lane by lane: creating all of them at once made a second context of the
-            // process abort with HSA_STATUS_ERROR_OUT_OF_RESOURCES in its first scratch pre-sizing (twenty new queues
-            // wanting their rings while the previous context's were still held).
-            {
-                // all five roles rotate (HK_LANE_ROT positions per group of four lanes, default 1): not only the working
-                // stream of single-kernel calls moves to another queue, hk_prove's heavy side streams of lanes k and
-                // k + 4 stop sharing queues role by role
-                static const size_t step = [] { const char* e = getenv("HK_LANE_ROT"); return e ? (size_t)atoi(e) % 5 : (size_t)1; }();
-                size_t rot = ((ctx->lanes.size() / 4) * step) % 5;
-                if (rot) {
-                    hipStream_t all[5] = {l->stream, l->aux[0], l->aux[1], l->aux[2], l->aux[3]};
-                    l->stream = all[rot % 5];
-                    for (size_t j = 0; j < 4; j++) l->aux[j] = all[(rot + 1 + j) % 5];
-                }
-            }
-            if (ctx->presize_kernel && !getenv("HK_NO_SCRATCH_PRESIZE")) {
-                // one wave of the deepest frame on each of the lane's streams, in creation order (see k_scratch_presize)
-                presize_fn k = (presize_fn)ctx->presize_kernel;
-                hipLaunchKernelGGL(k, dim3(1), dim3(64), 0, l->stream, (unsigned*)nullptr, 1u);
-                for (auto& a : l->aux) hipLaunchKernelGGL(k, dim3(1), dim3(64), 0, a, (unsigned*)nullptr, 1u);
-                bool okp = hipStreamSynchronize(l->stream) == hipSuccess;
-                for (auto& a : l->aux) okp = okp && hipStreamSynchronize(a) == hipSuccess;
-                if (!okp) { (void)hipGetLastError(); fprintf(stderr, "[hekaton] scratch pre-sizing of a lane failed\n"); }
-            }
-            memset(&l->timings, 0, sizeof(l->timings));
-            ctx->lanes.push_back(l);
-            lane = l;
+            // one stream: the runtime hands it the least-used hardware queue.  Lanes stay lazily created, one by one.
+            lane = new_lane(ctx, 1, false);
+            if (lane) ctx->lanes.push_back(lane);
             break;
         }
         ctx->cv.wait(lk);
@@ -201,13 +204,27 @@ LaneGuard::LaneGuard(hk_ctx* c) : ctx(c), lane(nullptr) {
     (void)hipSetDevice(ctx->device);
 }
 
+LaneGuard::LaneGuard(hk_ctx* c, ProveLaneTag) : ctx(c), lane(nullptr) {
+    std::unique_lock<std::mutex> lk(ctx->mu);
+    if (ctx->prove_lanes.empty()) return;              // hk_ctx_create made them; none means it could not
+    for (;;) {
+        for (Lane* l : ctx->prove_lanes)
+            if (!l->busy && (!lane || l->arena_cap > lane->arena_cap)) lane = l;
+        if (lane) break;
+        ctx->prove_cv.wait(lk);
+    }
+    lane->busy = true;
+    lane->settled = false;
+    lk.unlock();
+    (void)hipSetDevice(ctx->device);
+}
+
 LaneGuard::~LaneGuard() {
     if (!lane) return;
     if (!lane->settled) {
-        // an error return (HK_TRY / HK_HIP) may leave kernels queued on the arena: another call may take this lane, or
-        // trade arenas with it in reserve(), once it is free
-        (void)hipStreamSynchronize(lane->stream);
-        for (auto& a : lane->aux) (void)hipStreamSynchronize(a);
+        // an error return (HK_TRY / HK_HIP) may leave kernels queued on the arena, on any of the lane's streams: another
+        // call may take this lane, or trade arenas with it in reserve(), once it is free
+        for (unsigned i = 0; i < lane->n_streams; i++) (void)hipStreamSynchronize(lane->stream_at(i));
     }
     std::unique_lock<std::mutex> lk(ctx->mu);
     lane->busy = false;
@@ -215,15 +232,19 @@ LaneGuard::~LaneGuard() {
     tl_last_timings = lane->timings;
     bool idle = true;
     for (Lane* l : ctx->lanes) idle = idle && !l->busy;
+    for (Lane* l : ctx->prove_lanes) idle = idle && !l->busy;
     if (idle)                                      // nothing of this context is on the GPU: outgrown arenas go now
-        for (Lane* l : ctx->lanes) {
-            if (l->retired.empty()) continue;
-            (void)hipSetDevice(ctx->device);
-            for (void* p : l->retired) (void)hipFree(p);
-            l->retired.clear();
-        }
+        for (auto* v : {&ctx->lanes, &ctx->prove_lanes})
+            for (Lane* l : *v) {
+                if (l->retired.empty()) continue;
+                (void)hipSetDevice(ctx->device);
+                for (void* p : l->retired) (void)hipFree(p);
+                l->retired.clear();
+            }
+    const bool prove = lane->prove;
     lk.unlock();
-    ctx->cv.notify_one();
+    if (prove) ctx->prove_cv.notify_one();
+    else ctx->cv.notify_one();
 }
 
 bool is_device_ptr(const void* p) {
@@ -264,11 +285,9 @@ hk_status hk_ctx_create(hk_curve curve, int device_id, hk_ctx** out) {
     if (!out) return HK_ERR_ARG;
     *out = nullptr;
     if (curve != HK_BN254 && curve != HK_BLS12_381) return HK_ERR_ARG;
-    // Concurrent proofs want more hardware queues than the HIP runtime's default of 4 (GPU_MAX_HW_QUEUES=20: DESIGN.md
-    // section 5).  The runtime reads that variable when it initialises and the library does NOT touch the process
-    // environment (setenv is not safe against another thread's getenv in a multi-threaded host): the host exports it
-    // before its first HIP call - the bindings and drivers of this repository do (capi.py, apps/hk_all_in_one.cpp,
-    // INTEGRATION.md section 3).
+    // The library plans its streams within the hardware queues the process has (GPU_MAX_HW_QUEUES as the host set it
+    // before its first HIP call, or the runtime's default of 4) and does NOT touch the process environment (setenv is
+    // not safe against another thread's getenv in a multi-threaded host): DESIGN.md section 5, INTEGRATION.md section 3.
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
         (void)hipGetLastError();
@@ -296,6 +315,19 @@ hk_status hk_ctx_create(hk_curve curve, int device_id, hk_ctx** out) {
     memset(&c->last, 0, sizeof(c->last));
     const char* ml = getenv("HK_MAX_LANES");
     if (ml && atoi(ml) > 0) c->max_lanes = (size_t)atoi(ml);
+    // the prove lanes, before any general lane of the context: PROVE_COALESCE_RUNNING lanes of s = Q / K streams (at most
+    // five, the roles of a chunk), created in a row so that the runtime's least-used assignment gives each stream its own
+    // hardware queue while the Q queues go round.  HK_SERIAL_STREAMS=1: one stream per prove lane.
+    c->prove_streams = getenv("HK_SERIAL_STREAMS") ? 1u : hk::prove_lane_streams(hw_queues(), hk::PROVE_COALESCE_RUNNING);
+    for (int i = 0; i < hk::PROVE_COALESCE_RUNNING; i++) {
+        hk::Lane* l = new_lane(c, c->prove_streams, true);
+        if (!l) {
+            for (hk::Lane* p : c->prove_lanes) free_lane(p);
+            delete c;
+            return HK_ERR_DEVICE;
+        }
+        c->prove_lanes.push_back(l);
+    }
     *out = c;
     return HK_OK;
 }
@@ -305,14 +337,8 @@ void hk_ctx_destroy(hk_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     if (ctx->ops && ctx->ops->ctx_release) ctx->ops->ctx_release(ctx);
-    for (Lane* l : ctx->lanes) {
-        if (l->arena) (void)hipFree(l->arena);
-        for (void* p : l->retired) (void)hipFree(p);
-        for (auto& e : l->ev) (void)hipEventDestroy(e);
-        for (auto& a : l->aux) if (a) (void)hipStreamDestroy(a);
-        (void)hipStreamDestroy(l->stream);
-        delete l;
-    }
+    for (Lane* l : ctx->lanes) free_lane(l);
+    for (Lane* l : ctx->prove_lanes) free_lane(l);
     delete ctx;
 }
 
@@ -320,10 +346,9 @@ hk_status hk_ctx_sync(hk_ctx* ctx) {
     if (!ctx) return HK_ERR_ARG;
     HK_HIP(hipSetDevice(ctx->device));
     std::unique_lock<std::mutex> lk(ctx->mu);
-    for (Lane* l : ctx->lanes) {
-        HK_HIP(hipStreamSynchronize(l->stream));
-        for (auto& a : l->aux) if (a) HK_HIP(hipStreamSynchronize(a));
-    }
+    for (auto* v : {&ctx->lanes, &ctx->prove_lanes})
+        for (Lane* l : *v)
+            for (unsigned i = 0; i < l->n_streams; i++) HK_HIP(hipStreamSynchronize(l->stream_at(i)));
     return HK_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "../../include/hekaton.h"
 #include "coalesce.h"
 #include "msm.cuh"
+#include "stream_plan.h"
 
 #define HK_HIP(expr)                                                                         \
     do {                                                                                     \
@@ -75,12 +76,16 @@ struct Carve {
 };
 
 // ---- per-call lane: one stream + one grow-only scratch arena ---------------------------------------
+// A general lane has one stream.  A prove lane (hk_ctx::prove_lanes) has n_streams: `stream` and side[0 .. n_streams - 2],
+// over which prove_batch spreads its five roles (stream_plan.h).
 struct Lane {
     hipStream_t stream = nullptr;
     char* arena = nullptr;
     size_t arena_cap = 0;
     hipEvent_t ev[32];
-    hipStream_t aux[4] = {nullptr, nullptr, nullptr, nullptr};   // fork/join side streams of hk_prove
+    hipStream_t side[PROVE_MAX_STREAMS - 1] = {};
+    unsigned n_streams = 1;
+    bool prove = false;
     bool busy = false;
     bool settled = false;         // nothing queued since the last settle(): ~LaneGuard need not drain the streams
     hk_timings timings;
@@ -104,9 +109,11 @@ struct Lane {
         settled = false;                             // work on the new slices follows
         return HK_OK;
     }
-    // the call's final synchronize: the lane is idle from here on
+    hipStream_t stream_at(unsigned i) const { return i ? side[i - 1] : stream; }
+    // the call's final synchronize, over every stream of the lane (kernels on any of them use the arena): the lane is idle
+    // from here on
     hk_status settle() {
-        HK_HIP(hipStreamSynchronize(stream));
+        for (unsigned i = 0; i < n_streams; i++) HK_HIP(hipStreamSynchronize(stream_at(i)));
         settled = true;
         return HK_OK;
     }
@@ -220,6 +227,11 @@ struct hk_ctx {
     std::condition_variable cv;
     std::vector<hk::Lane*> lanes;
     size_t max_lanes = 8;           // concurrent calls beyond this wait for a lane (HK_MAX_LANES)
+    // every prove_batch runs on one of these PROVE_COALESCE_RUNNING lanes of prove_streams streams each, created with the
+    // context before any general lane (hk_core.hip); their waiters wait on prove_cv
+    std::vector<hk::Lane*> prove_lanes;
+    unsigned prove_streams = 1;
+    std::condition_variable prove_cv;
     hk::NttTables* ntt = nullptr;
     hk_timings last;
     uint32_t max_lanes0 = 262144;   // level-0 accumulate lanes: 4 waves/SIMD x 1024 SIMDs x 64
@@ -267,10 +279,12 @@ struct hk_wprog {
 
 namespace hk {
 
+struct ProveLaneTag {};
 struct LaneGuard {
     hk_ctx* ctx;
     Lane* lane;
-    LaneGuard(hk_ctx* c);
+    LaneGuard(hk_ctx* c);                  // a general lane
+    LaneGuard(hk_ctx* c, ProveLaneTag);    // a prove lane: waits for one of the context's prove lanes to be free
     ~LaneGuard();
 };
 

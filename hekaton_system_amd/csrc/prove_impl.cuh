@@ -1433,21 +1433,24 @@ __global__ void k_prep_ext(Fr* __restrict__ ext, u32 ext_stride, const Fr* __res
 
 // Finish: A = MA + a_g[0] + alpha_g ; B = MB2 + b_h[0] + beta_h ; B1 = MB1 + b_g[0] + beta_g ;
 //         C = s*A + r*B1 + ML' + MH   with ML' = L - rs*delta_g - sum kappa_i*delta_i   (see file header)
-// (prover.rs:135-155 "Finish C" + into_affine, committer.rs:112-114).  One lane per output point.
-// Grid (3, batch), proof = blockIdx.y: res_g1 holds 4 points per proof (MA, MB1, ML, MH), res_g2 1 (MB2), rs rs_stride Fr
-// per proof (r, s, kappas); one output point per proof in each of out_a / out_b / out_c.
+// (prover.rs:135-155 "Finish C" + into_affine, committer.rs:112-114).  Two kernels, so that the variable-base products
+// do not wait for H: k_finish_ab needs only A, B1, B2 and L and leaves C without MH in part_c; k_finish_c adds MH once H is
+// done and normalises C.  The sum is the one the single kernel formed, in the same order, and an affine point is unique.
+// k_finish_ab: one lane per output point.  Grid (3, batch), proof = blockIdx.y: res_g1 holds 4 points per proof (MA, MB1,
+// ML, MH; MH is not read here), res_g2 1 (MB2), rs rs_stride Fr per proof (r, s, kappas); one point per proof in each of
+// out_a / out_b / part_c.
 template <class Fr, class Fq, class Fq2>
-__global__ void k_finish(const XYZZ<Fq>* __restrict__ res_g1_all, const XYZZ<Fq2>* __restrict__ res_g2_all,
-                         const Affine<Fq>* __restrict__ c1, const Affine<Fq2>* __restrict__ c2, const Fr* __restrict__ rs_all,
-                         u32 rs_stride, Affine<Fq>* __restrict__ out_a_all, Affine<Fq2>* __restrict__ out_b_all,
-                         Affine<Fq>* __restrict__ out_c_all, EndoSplit<2> E) {
+__global__ void k_finish_ab(const XYZZ<Fq>* __restrict__ res_g1_all, const XYZZ<Fq2>* __restrict__ res_g2_all,
+                            const Affine<Fq>* __restrict__ c1, const Affine<Fq2>* __restrict__ c2, const Fr* __restrict__ rs_all,
+                            u32 rs_stride, Affine<Fq>* __restrict__ out_a_all, Affine<Fq2>* __restrict__ out_b_all,
+                            XYZZ<Fq>* __restrict__ part_c_all, EndoSplit<2> E) {
     const size_t pr = blockIdx.y;
     const XYZZ<Fq>* __restrict__ res_g1 = res_g1_all + 4 * pr;
     const XYZZ<Fq2>* __restrict__ res_g2 = res_g2_all + pr;
     const Fr* __restrict__ rs = rs_all + pr * rs_stride;
     Affine<Fq>* __restrict__ out_a = out_a_all + pr;
     Affine<Fq2>* __restrict__ out_b = out_b_all + pr;
-    Affine<Fq>* __restrict__ out_c = out_c_all + pr;
+    XYZZ<Fq>* __restrict__ part_c = part_c_all + pr;
     if (blockIdx.x < 2 && threadIdx.x) return;
     if (blockIdx.x == 0) {
         XYZZ<Fq> A = ec_madd_ni(ec_madd_ni(ld_vec(&res_g1[0]), ld_vec(&c1[0])), ld_vec(&c1[1]));
@@ -1515,16 +1518,27 @@ __global__ void k_finish(const XYZZ<Fq>* __restrict__ res_g1_all, const XYZZ<Fq2
                 Cc.zz = Fq::sqr(sum.z);
                 Cc.zzz = Fq::mul(Cc.zz, sum.z);
             }
-            Cc = ec_add_ni(Cc, ld_vec(&res_g1[2]));
-            Cc = ec_add_ni(Cc, ld_vec(&res_g1[3]));
-            st_vec(out_c, ec_to_affine(Cc));
+            st_vec(part_c, ec_add_ni(Cc, ld_vec(&res_g1[2])));
         }
     }
 }
 
+// k_finish_c: C = part_c + MH, to affine.  One lane per proof of the chunk, one wave.
+static_assert(HK_PROVE_BATCH_CHUNK <= 64, "k_finish_c covers a chunk with one wave");
+template <class Fq>
+__global__ void __launch_bounds__(64) k_finish_c(const XYZZ<Fq>* __restrict__ part_c, const XYZZ<Fq>* __restrict__ res_g1_all,
+                                                 Affine<Fq>* __restrict__ out_c, u32 batch) {
+    const u32 pr = threadIdx.x;
+    if (pr >= batch) return;
+    XYZZ<Fq> Cc = ec_add_ni(ld_vec(&part_c[pr]), ld_vec(&res_g1_all[4 * (size_t)pr + 3]));
+    st_vec(&out_c[pr], ec_to_affine(Cc));
+}
+
 template <class C>
 size_t Ops<C>::finish_private_bytes() {
-    return hk_private_bytes_of((const void*)k_finish<Fr, Fq, Fq2>);
+    size_t ab = hk_private_bytes_of((const void*)k_finish_ab<Fr, Fq, Fq2>);
+    size_t c = hk_private_bytes_of((const void*)k_finish_c<Fq>);
+    return ab > c ? ab : c;
 }
 
 static inline float ev_ms(hipEvent_t a, hipEvent_t b) {
@@ -1639,11 +1653,12 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
         const ProveRow& w = rows[b];
         if (!w.z || !w.r || !w.s || !w.a || !w.b || !w.c || (n_kappas && !w.kappas)) return HK_ERR_ARG;
     }
-    NttTables* T;
-    HK_TRY(NttHost<C>::ensure(ctx, pk->log_m, &T));
-    LaneGuard g(ctx);
+    // a prove lane first, before anything else that might wait: its holder never waits for a general lane
+    LaneGuard g(ctx, ProveLaneTag{});
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
+    NttTables* T;
+    HK_TRY(NttHost<C>::ensure(ctx, pk->log_m, &T));
     const MsmPlan &pz = pk->plan_z, &ph = pk->plan_h, &pb = pk->plan_b;
     const size_t m = (size_t)1 << pk->log_m, fr = sizeof(Fr), rs_stride = 2 + n_kappas;
     std::vector<char> z_dev(batch);
@@ -1662,6 +1677,7 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
     XYZZ<Fq2>* res2;
     Affine<Fq> *oa, *oc;
     Affine<Fq2>* ob;
+    XYZZ<Fq>* pc;
     auto chunk_bufs = [&](Carve& c, u32 nb) {
         zext = c.n<Fr>((size_t)pk->n_ext * nb);                               // z[1..] | r | s | rs | kappas
         small = c.n<Fr>(rs_stride * nb);                                      // [nb][2 + n_kappas]
@@ -1684,6 +1700,7 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
         oa = c.n<Affine<Fq>>(nb);
         oc = c.n<Affine<Fq>>(nb);
         ob = c.n<Affine<Fq2>>(nb);
+        pc = c.n<XYZZ<Fq>>(nb);                                               // C without MH (k_finish_ab -> k_finish_c)
         abc = c.n<Fr>(3 * m * nb);                                            // [nb][a | b | c]
     };
     // chunk rule (hekaton.h): at most HK_PROVE_BATCH_CHUNK proofs, fewer when that many would not fit in free device memory
@@ -1696,7 +1713,7 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
         auto chunk_bytes = [&](size_t nb) { Carve c; chunk_bufs(c, (u32)nb); return c.off; };
         while (chunk > 1 && chunk_bytes(chunk) > avail) chunk--;
     }
-    // r | s | kappas of every proof, one row each (k_prep_ext and k_finish read them)
+    // r | s | kappas of every proof, one row each (k_prep_ext and k_finish_ab read them)
     std::vector<unsigned char> rsk(batch * rs_stride * fr);
     for (size_t b = 0; b < batch; b++) {
         unsigned char* row = rsk.data() + b * rs_stride * fr;
@@ -1708,17 +1725,21 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
     std::vector<Affine<Fq>> ha(chunk), hc(chunk);
     std::vector<Affine<Fq2>> hb(chunk);
     std::vector<const Fr*> zd(chunk);
-    hipStream_t s = L->stream;
     const bool prof = ctx->profiling;
     hipEvent_t* ev = L->ev;
     hk_timings acc;
     memset(&acc, 0, sizeof(acc));
     static const EndoSplit<2> endo_g1 = EndoOf<Fq>::split();
-    // HK_SERIAL_STREAMS=1 keeps everything on the lane's own stream: clean per-kernel times for profiling, and - with
-    // 18 lanes and GPU_MAX_HW_QUEUES=18, one hardware queue per lane - the faster form for small circuits (DESIGN.md
-    // section 5).  Not the default: 18 concurrent G2 tail kernels (2-3 KB of scratch per lane each) once exhausted the
-    // runtime's scratch pool on BLS12-381 and the process aborted (HSA_STATUS_ERROR_OUT_OF_RESOURCES).
-    static const bool serial = getenv("HK_SERIAL_STREAMS") != nullptr;
+    // the five roles on the lane's streams (stream_plan.h): main on L->stream, the others where the role map puts them.
+    // One stream (HK_SERIAL_STREAMS=1, or one hardware queue per lane) runs everything in submission order: clean
+    // per-kernel times for profiling.  A fork or join between two roles on one stream is no event wait at all.
+    hipStream_t rs[PROVE_ROLES];
+    for (int r = 0; r < PROVE_ROLES; r++) rs[r] = L->stream_at(prove_role_stream(L->n_streams, (ProveRole)r));
+    hipStream_t s = rs[ROLE_MAIN];
+    auto wait = [](hipStream_t to, hipEvent_t e, hipStream_t from) -> hk_status {
+        if (to != from) HK_HIP(hipStreamWaitEvent(to, e, 0));
+        return HK_OK;
+    };
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
         const u32 nb = (u32)std::min(chunk, batch - b0);
         HK_TRY(L->carve([&](Carve& c) { chunk_bufs(c, nb); }));
@@ -1740,63 +1761,72 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
         hipLaunchKernelGGL((k_prep_ext<Fr>), dim3(64), dim3(256), 0, s, zext + (n_v - 1), pk->n_ext, (const Fr*)small,
                            (u32)rs_stride, (u32)n_kappas, nb, sb.count, sbh.count, sbb.count, pz.NB * nb, ph.NB * nb,
                            pk->b_compact ? pb.NB * nb : 0u);
-        // Fork: the five queries are independent once their scalars exist.  Side streams let the
-        // latency-bound tails (segmented levels, bucket reduction) of one query hide under the
-        // throughput-bound accumulation of another; every launch covers the whole chunk.
-        //   main  : sort(z) -> A
-        //   aux0  : B1      aux1 : B2 (G2)      aux2 : L      aux3 : witness map -> sort(h) -> H
-        hipStream_t axs[4] = {L->aux[0], L->aux[1], L->aux[2], L->aux[3]};
-        if (serial) for (auto& a : axs) a = s;
-        hipStream_t* ax = axs;
+        // Fork: the five queries are independent once their scalars exist.  Streams let the latency-bound tails
+        // (segmented levels, bucket reduction) of one query hide under the throughput-bound accumulation of another;
+        // every launch covers the whole chunk.
+        //   main : sort(z) -> A -> finish_ab -> finish_c     B1      B2 (G2)      L      H : witness map -> sort(h) -> H
+        hipStream_t sB1 = rs[ROLE_B1], sB2 = rs[ROLE_B2], sL = rs[ROLE_L], sH = rs[ROLE_H];
         hipEvent_t ev_z = ev[16], ev_sorted = ev[17];
         HK_HIP(hipEventRecord(ev_z, s));                                       // z (and ext scalars) on device
-        HK_HIP(hipStreamWaitEvent(ax[3], ev_z, 0));
-        if (prof) HK_HIP(hipEventRecord(ev[5], ax[3]));
-        for (u32 j = 0; j < nb; j++)                                            // witness map: one chain per proof
-            HK_TRY(Q::run(ax[3], T, pk->csr[0], pk->csr[1], pk->csr[2], pk->n_inst, pk->n_c, zd[j],
-                          abc + (size_t)j * 3 * m, pk->log_m));
-        if (prof) HK_HIP(hipEventRecord(ev[6], ax[3]));                        // witness map done
-        HK_TRY(MsmSort<Fr>::run(ax[3], ph, (const u32*)abc, 1, sbh, true, nb, 3 * m));
-        HK_TRY(MsmRun<Fq>::run(ax[3], ph, pk->h_tab, (u32)m, 0, sbh, rbh, res1 + 3, prof ? ev[12] : nullptr,
-                               prof ? ev[13] : nullptr, nb, 4));
-        HK_HIP(hipEventRecord(ev[7], ax[3]));                                  // H done
+        auto submit_h = [&]() -> hk_status {
+            HK_TRY(wait(sH, ev_z, s));
+            if (prof) HK_HIP(hipEventRecord(ev[5], sH));
+            for (u32 j = 0; j < nb; j++)                                        // witness map: one chain per proof
+                HK_TRY(Q::run(sH, T, pk->csr[0], pk->csr[1], pk->csr[2], pk->n_inst, pk->n_c, zd[j],
+                              abc + (size_t)j * 3 * m, pk->log_m));
+            if (prof) HK_HIP(hipEventRecord(ev[6], sH));                       // witness map done
+            HK_TRY(MsmSort<Fr>::run(sH, ph, (const u32*)abc, 1, sbh, true, nb, 3 * m));
+            HK_TRY(MsmRun<Fq>::run(sH, ph, pk->h_tab, (u32)m, 0, sbh, rbh, res1 + 3, prof ? ev[12] : nullptr,
+                                   prof ? ev[13] : nullptr, nb, 4));
+            HK_HIP(hipEventRecord(ev[7], sH));                                 // H done
+            return HK_OK;
+        };
+        // Submitting the H chain's hundred-odd launches takes the host milliseconds, and a stream starts only once its
+        // work is submitted.  H is the longest role when the queries have streams of their own, so it goes first; on
+        // two streams the four queries in a row are longer than H (profiles/queues_*), so they go first there.
+        const bool h_first = L->n_streams >= 3;
+        if (h_first) HK_TRY(submit_h());
         HK_TRY(MsmSort<Fr>::run(s, pz, (const u32*)zext, 1, sb, true, nb, pk->n_ext));
         HK_HIP(hipEventRecord(ev_sorted, s));
         if (prof) HK_HIP(hipEventRecord(ev[1], s));                            // digits done
-        HK_HIP(hipStreamWaitEvent(ax[2], ev_sorted, 0));
+        HK_TRY(wait(sL, ev_sorted, s));
         const SortBufs* sbB = &sb;
         if (pk->b_compact) {
-            // B1 / B2 over the non-infinity bases only: gather their scalars, sort those digits on aux0
-            HK_HIP(hipStreamWaitEvent(ax[0], ev_z, 0));
-            hipLaunchKernelGGL((k_gather<Fr>), dim3((pk->b_n + 255) / 256, nb), dim3(256), 0, ax[0], zb, (const Fr*)zext,
+            // B1 / B2 over the non-infinity bases only: gather their scalars, sort those digits on B1's stream
+            HK_TRY(wait(sB1, ev_z, s));
+            hipLaunchKernelGGL((k_gather<Fr>), dim3((pk->b_n + 255) / 256, nb), dim3(256), 0, sB1, zb, (const Fr*)zext,
                                (const u32*)pk->b_idx, pk->b_n, pk->n_ext);
-            HK_TRY(MsmSort<Fr>::run(ax[0], pb, (const u32*)zb, 1, sbb, true, nb, pk->b_n));
-            HK_HIP(hipEventRecord(ev[28], ax[0]));
-            HK_HIP(hipStreamWaitEvent(ax[1], ev[28], 0));
+            HK_TRY(MsmSort<Fr>::run(sB1, pb, (const u32*)zb, 1, sbb, true, nb, pk->b_n));
+            HK_HIP(hipEventRecord(ev[28], sB1));
+            HK_TRY(wait(sB2, ev[28], sB1));
             sbB = &sbb;
         } else {
-            HK_HIP(hipStreamWaitEvent(ax[0], ev_sorted, 0));
-            HK_HIP(hipStreamWaitEvent(ax[1], ev_sorted, 0));
+            HK_TRY(wait(sB1, ev_sorted, s));
+            HK_TRY(wait(sB2, ev_sorted, s));
         }
-        HK_TRY(MsmRun<Fq2>::run(ax[1], pb, pk->b2_tab, pk->b_n, 0, *sbB, rb2, res2, nullptr, nullptr, nb, 1));
-        HK_HIP(hipEventRecord(ev[4], ax[1]));                                  // B2 done
-        HK_TRY(MsmRun<Fq>::run(ax[0], pb, pk->b1_tab, pk->b_n, 0, *sbB, rbB1, res1 + 1, prof ? ev[22] : nullptr,
+        HK_TRY(MsmRun<Fq2>::run(sB2, pb, pk->b2_tab, pk->b_n, 0, *sbB, rb2, res2, nullptr, nullptr, nb, 1));
+        HK_HIP(hipEventRecord(ev[4], sB2));                                    // B2 done
+        HK_TRY(MsmRun<Fq>::run(sB1, pb, pk->b1_tab, pk->b_n, 0, *sbB, rbB1, res1 + 1, prof ? ev[22] : nullptr,
                                prof ? ev[23] : nullptr, nb, 4));
-        HK_HIP(hipEventRecord(ev[3], ax[0]));                                  // B1 done
-        HK_TRY(MsmRun<Fq>::run(ax[2], pz, pk->l_tab, pk->l_n, pk->l_off, sb, rbL, res1 + 2, prof ? ev[24] : nullptr,
+        HK_HIP(hipEventRecord(ev[3], sB1));                                    // B1 done
+        HK_TRY(MsmRun<Fq>::run(sL, pz, pk->l_tab, pk->l_n, pk->l_off, sb, rbL, res1 + 2, prof ? ev[24] : nullptr,
                                prof ? ev[25] : nullptr, nb, 4));
-        HK_HIP(hipEventRecord(ev[18], ax[2]));                                 // L done
+        HK_HIP(hipEventRecord(ev[18], sL));                                    // L done
         HK_TRY(MsmRun<Fq>::run(s, pz, pk->a_tab, pk->n_ext, 0, sb, rbA, res1 + 0, prof ? ev[26] : nullptr,
                                prof ? ev[27] : nullptr, nb, 4));
         if (prof) HK_HIP(hipEventRecord(ev[2], s));                            // A done
-        // Join
-        HK_HIP(hipStreamWaitEvent(s, ev[3], 0));
-        HK_HIP(hipStreamWaitEvent(s, ev[4], 0));
-        HK_HIP(hipStreamWaitEvent(s, ev[18], 0));
-        HK_HIP(hipStreamWaitEvent(s, ev[7], 0));
-        if (prof) HK_HIP(hipEventRecord(ev[19], s));                           // all queries done
-        hipLaunchKernelGGL((k_finish<Fr, Fq, Fq2>), dim3(3, nb), dim3(64), 0, s, res1, res2, pk->consts_g1, pk->consts_g2,
-                           (const Fr*)small, (u32)rs_stride, oa, ob, oc, endo_g1);
+        // Join the queries: A, B, and C without MH need nothing of H, so they no longer wait for it
+        HK_TRY(wait(s, ev[3], sB1));
+        HK_TRY(wait(s, ev[4], sB2));
+        HK_TRY(wait(s, ev[18], sL));
+        hipLaunchKernelGGL((k_finish_ab<Fr, Fq, Fq2>), dim3(3, nb), dim3(64), 0, s, res1, res2, pk->consts_g1, pk->consts_g2,
+                           (const Fr*)small, (u32)rs_stride, oa, ob, pc, endo_g1);
+        HK_HIP(hipGetLastError());
+        if (!h_first) HK_TRY(submit_h());
+        // Join H
+        HK_TRY(wait(s, ev[7], sH));
+        if (prof) HK_HIP(hipEventRecord(ev[19], s));                           // all queries and finish_ab done
+        hipLaunchKernelGGL((k_finish_c<Fq>), dim3(1), dim3(64), 0, s, (const XYZZ<Fq>*)pc, (const XYZZ<Fq>*)res1, oc, nb);
         HK_HIP(hipGetLastError());
         HK_HIP(hipMemcpyAsync(ha.data(), oa, nb * sizeof(Affine<Fq>), hipMemcpyDeviceToHost, s));
         HK_HIP(hipMemcpyAsync(hb.data(), ob, nb * sizeof(Affine<Fq2>), hipMemcpyDeviceToHost, s));
@@ -1809,11 +1839,13 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
             memcpy(rows[b0 + j].c, &hc[j], sizeof(Affine<Fq>));
         }
         if (prof) {
-            // the five queries run concurrently on side streams: each figure is the elapsed time on the query's own
-            // stream since its fork point (they overlap, they do not add up to total_ms); summed over the chunks
+            // the five queries run concurrently where they have streams of their own: each figure is the elapsed time on
+            // the query's stream since its fork point (they overlap, they do not add up to total_ms; roles that share a
+            // stream include the work queued before them there); summed over the chunks.  finish_ms: k_finish_c and the
+            // copies, from the moment H and k_finish_ab are both done.
             acc.digits_ms += ev_ms(ev_start, ev[1]);
             acc.msm_a_ms += ev_ms(ev[1], ev[2]);
-            // a compact B forks from z (its own gather and sort on aux0), not from the shared sort: it may finish before ev[1]
+            // a compact B forks from z (its own gather and sort on B1's stream), not from the shared sort: it may finish before ev[1]
             hipEvent_t fork_b = pk->b_compact ? ev_z : ev[1];
             acc.msm_b_g1_ms += ev_ms(fork_b, ev[3]);
             acc.msm_b_g2_ms += ev_ms(fork_b, ev[4]);
