@@ -108,6 +108,16 @@ hk_status scratch_budget_check(const CurveOps* ops, const hipDeviceProp_t& prop,
 
 static thread_local hk_timings tl_last_timings = {};
 
+// HK_PROVE_GATHER_TRACE=1 (read once, off by default): one stderr line per hk_prove arrival - how long after the end of the
+// chunk that held this thread's previous call it re-entered - and one per chunk end, with the number of arena allocations of
+// the process so far.  The figures behind PROVE_GATHER_US.
+static bool gather_trace() { static const bool on = getenv("HK_PROVE_GATHER_TRACE") != nullptr; return on; }
+static int64_t now_us() {
+    return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+static std::atomic<unsigned> g_arena_allocs{0};
+static thread_local int64_t tl_prev_chunk_end_us = 0;
+
 hk_status Lane::reserve(size_t bytes) {
     if (bytes <= arena_cap) return HK_OK;
     HK_HIP(hipStreamSynchronize(stream));
@@ -131,6 +141,7 @@ hk_status Lane::reserve(size_t bytes) {
     arena = nullptr;
     arena_cap = 0;
     size_t want = bytes + bytes / 8 + (1u << 20);
+    g_arena_allocs++;
     hipError_t e = hipMalloc((void**)&arena, want);
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -307,7 +318,9 @@ hk_status hk_ctx_create(hk_curve curve, int device_id, hk_ctx** out) {
     // no environment setting may be able to exhaust the runtime's scratch pool (the abort of round 2): refuse here
     void* presize = nullptr;
     HK_TRY(hk::scratch_budget_check(ops, prop, &presize));
-    hk_ctx* c = new hk_ctx();
+    // read once per context, before any thread can be inside hk_prove
+    const char* gu = getenv("HK_PROVE_GATHER_US");
+    hk_ctx* c = new hk_ctx(gu ? atol(gu) : (long)hk::PROVE_GATHER_US);
     c->presize_kernel = presize;
     c->curve = curve;
     c->device = device_id;
@@ -594,6 +607,8 @@ hk_status hk_prove(hk_ctx* ctx, const hk_pk* pk, const void* z, size_t n_v, cons
     // concurrent calls of this key meet in the context's coalescer and run as one lock-step batch;
     // a lone call leads at once, a batch of one
     const hk::ProveCall call = {{z, r, s, kappas, a, b, c}, n_v, n_kappas};
+    if (hk::gather_trace() && hk::tl_prev_chunk_end_us)
+        fprintf(stderr, "[hekaton] gather arrive gap_us=%lld\n", (long long)(hk::now_us() - hk::tl_prev_chunk_end_us));
     hk::ProveResult res = ctx->prove_q.submit(pk, call, [&](const hk_pk* key, hk::ProveCoalescer::Member* const* ms, size_t n) {
         std::vector<hk::ProveRow> rows(n);
         for (size_t i = 0; i < n; i++) rows[i] = ms[i]->item->row;
@@ -609,8 +624,14 @@ hk_status hk_prove(hk_ctx* ctx, const hk_pk* pk, const void* z, size_t n_v, cons
             *x *= f;
         if (t.accum_kernel_launches) t.accum_kernel_launches = 4;
         t.batch_proofs = (uint32_t)n;
-        for (size_t i = 0; i < n; i++) ms[i]->result = hk::ProveResult{st, t};
+        int64_t end_us = 0;
+        if (hk::gather_trace()) {
+            end_us = hk::now_us();
+            fprintf(stderr, "[hekaton] gather chunk n=%zu arena_allocs=%u\n", n, hk::g_arena_allocs.load());
+        }
+        for (size_t i = 0; i < n; i++) ms[i]->result = hk::ProveResult{st, t, end_us};
     });
+    hk::tl_prev_chunk_end_us = res.end_us;
     tl_last_timings = res.timings;
     return res.status;
 }

@@ -134,7 +134,12 @@ struct ProveRow {
 struct ProveResult {
     hk_status status;
     hk_timings timings;
+    int64_t end_us;               // when the chunk ended (steady clock; HK_PROVE_GATHER_TRACE only, else 0)
 };
+
+// how long a leader of hk_prove's coalescer gathers the callers a finished chunk released before it runs a chunk below its
+// balanced size (coalesce.h).  Measured in the default bench on MI355X; HK_PROVE_GATHER_US overrides.
+enum { PROVE_GATHER_US = 1000 };
 
 // a queued hk_prove call: its row and the lengths it was validated with (those of its key - a leader may run another
 // key's calls than its own)
@@ -242,8 +247,11 @@ struct hk_ctx {
     struct FbTable { int group; std::string base; void* table; bool ready; };
     enum { FB_CACHE_MAX = 8 };
     std::vector<FbTable> fb_cache;
-    // concurrent hk_prove calls of one key meet here and run as one lock-step batch (hk_core.hip)
-    hk::ProveCoalescer prove_q{hk::PROVE_COALESCE_RUNNING, HK_PROVE_BATCH_CHUNK, hk::ProveResult{HK_ERR_NOMEM, {}}};
+    // concurrent hk_prove calls of one key meet here and run as one lock-step batch (hk_core.hip); gather_us: how long a
+    // leader waits for the callers a finished chunk released (HK_PROVE_GATHER_US, 0 = no waiting and no balancing)
+    hk::ProveCoalescer prove_q;
+    explicit hk_ctx(long gather_us)
+        : prove_q(hk::PROVE_COALESCE_RUNNING, HK_PROVE_BATCH_CHUNK, hk::ProveResult{HK_ERR_NOMEM, {}, 0}, gather_us) {}
 };
 
 struct hk_pk {
