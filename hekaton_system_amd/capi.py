@@ -71,6 +71,18 @@ class hk_keygen_out(C.Structure):             # include/hekaton.h
                 ("beta_h", C.c_void_p), ("gamma_h", C.c_void_p), ("deltas_h", C.c_void_p), ("qap_abc", C.c_void_p)]
 
 
+class hk_exec_tree_desc(C.Structure):         # include/hekaton.h
+    _fields_ = [("n_sub", C.c_uint32), ("entry_fields", C.c_uint32), ("offsets", C.c_void_p),
+                ("time_entries_mont", C.c_void_p), ("addr_entries_mont", C.c_void_p), ("challenges_mont", C.c_void_p),
+                ("consts_mont", C.c_void_p), ("n_consts", C.c_size_t),
+                ("leaf_hash", C.POINTER(hk_poseidon_desc)), ("node_hash", C.POINTER(hk_poseidon_desc))]
+
+
+class hk_exec_tree_out(C.Structure):          # include/hekaton.h
+    _fields_ = [("evals_mont", C.c_void_p), ("leaves_mont", C.c_void_p), ("nodes_mont", C.c_void_p),
+                ("siblings_mont", C.c_void_p), ("root_mont", C.c_void_p)]
+
+
 class hk_timings(C.Structure):
     _fields_ = [(n, C.c_float) for n in
                 ("total_ms", "digits_ms", "msm_a_ms", "msm_b_g1_ms", "msm_b_g2_ms", "msm_l_ms",
@@ -90,7 +102,7 @@ EXPORTS = ["hk_status_str", "hk_version", "hk_ctx_create", "hk_ctx_destroy", "hk
            "hk_msm_bases", "hk_multi_pairing", "hk_pairing_products", "hk_ctx_gt_bytes",
            "hk_points_lincomb_g1", "hk_points_lincomb_g2", "hk_points_fold_g2", "hk_points_fold_g1", "hk_points_fold_many_g1", "hk_points_fold_many_g2", "hk_pairing_pairs", "hk_keccak_f1600", "hk_assignment_from_bits", "hk_wprog_upload", "hk_wprog_free", "hk_wprog_run", "hk_gt_pow", "hk_fq12_pow", "hk_gt_pow_prod", "hk_poseidon_path", "hk_assignment_scatter", "hk_commit_batch",
            "hk_prove_batch", "hk_vk_prepare", "hk_vk_free", "hk_vk_alpha_beta", "hk_verify_batch", "hk_points_check_g1",
-           "hk_points_check_g2", "hk_qap_eval", "hk_keygen"]
+           "hk_points_check_g2", "hk_qap_eval", "hk_keygen", "hk_exec_tree"]
 
 HK_VERIFY_CHECK_POINTS = 1
 VERDICT_REJECT, VERDICT_ACCEPT, VERDICT_BAD_POINT = 0, 1, 2
@@ -179,6 +191,7 @@ def load():
     lib.hk_qap_eval.argtypes = [vp, C.POINTER(hk_csr), C.POINTER(hk_csr), C.POINTER(hk_csr), sz, sz, sz, vp, vp, vp, vp, vp,
                                 C.POINTER(sz)]
     lib.hk_keygen.argtypes = [vp, C.POINTER(hk_keygen_desc), C.POINTER(hk_keygen_out), C.POINTER(sz)]
+    lib.hk_exec_tree.argtypes = [vp, C.POINTER(hk_exec_tree_desc), C.POINTER(hk_exec_tree_out)]
     _lib = lib
     return lib
 
@@ -465,17 +478,22 @@ class Context:
         """hk_poseidon_path: the membership block of `batch` assignments, written on the device.  params:
         (consts DeviceBuffer or Montgomery bytes, n_consts, (t, alpha, rf, rp, off) of the leaf hash, same of the node hash)
         - poseidon.device_params(curve); leaf: Montgomery bytes (batch, 4 Fr); siblings: (batch, depth Fr); index: uint32
-        (batch); z_out: DeviceBuffer (or raw device address) of batch x n_v Fr."""
+        (batch); z_out: DeviceBuffer (or raw device address) of batch x n_v Fr.  leaf and siblings may also be the
+        DeviceBuffers hk_exec_tree left on the device (both then; batch = len(index))."""
         consts, n_consts, ld, nd = params
-        leaf = np.ascontiguousarray(leaf, dtype=np.uint8)
-        batch = leaf.shape[0]
-        siblings = np.ascontiguousarray(siblings, dtype=np.uint8).reshape(batch, -1)
-        depth = siblings.shape[1] // self.fr_bytes
         index = np.ascontiguousarray(index, dtype=np.uint32)
+        if isinstance(leaf, DeviceBuffer):
+            batch = index.size
+            depth = siblings.nbytes // (batch * self.fr_bytes)
+        else:
+            leaf = np.ascontiguousarray(leaf, dtype=np.uint8)
+            batch = leaf.shape[0]
+            siblings = np.ascontiguousarray(siblings, dtype=np.uint8).reshape(batch, -1)
+            depth = siblings.shape[1] // self.fr_bytes
         a, b = hk_poseidon_desc(*ld), hk_poseidon_desc(*nd)
         zp = z_out.ptr if isinstance(z_out, DeviceBuffer) else int(z_out)
-        check(self.lib.hk_poseidon_path(self.handle, ptr(consts), int(n_consts), C.byref(a), C.byref(b), leaf.ctypes.data,
-                                        siblings.ctypes.data if depth else None, index.ctypes.data, depth, batch, int(n_v),
+        check(self.lib.hk_poseidon_path(self.handle, ptr(consts), int(n_consts), C.byref(a), C.byref(b), ptr(leaf),
+                                        ptr(siblings) if depth else None, index.ctypes.data, depth, batch, int(n_v),
                                         int(col0), zp), "hk_poseidon_path")
 
     def wprog_upload(self, ops, refs, vmap, n_values, n_inputs):
@@ -612,6 +630,47 @@ class Context:
             raise
         res["m"] = m_out.value
         return res
+
+    def exec_tree(self, params, entry_fields, offsets, time_entries, addr_entries, challenges, device_out=False, out=None):
+        """hk_exec_tree: the coordinator's step between the rounds (coordinator.rs:125-174, 425-466) in one device call.
+        params: poseidon.device_params(curve), as poseidon_path takes it; entry_fields: 2 (ROM) or 4 (RAM); offsets:
+        n_sub + 1 uint32, subtrace i = entries [offsets[i], offsets[i + 1]) of both orders; time_entries / addr_entries:
+        Montgomery bytes (or DeviceBuffers) of offsets[-1] x entry_fields Fr; challenges: entry_fields ints (or their
+        Montgomery bytes) in the reference's challenges() order, tr_chal last.  Returns (evals [n_sub x 2 Fr], leaves
+        [n_sub x (2 + entry_fields)], nodes [2 n_sub - 1: leaf digests, each level, root last], siblings [n_sub x depth,
+        bottom-up], root) as Montgomery bytes, or as DeviceBuffers when device_out is set; out: five buffers of those
+        sizes to fill and return instead (numpy arrays or DeviceBuffers)."""
+        from .cp_groth16 import FrCodec
+        consts, n_consts, ld, nd = params
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+        n_sub = offsets.size - 1
+        keep = [x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8)
+                for x in (time_entries, addr_entries)]
+        if isinstance(challenges, np.ndarray):
+            ch = np.ascontiguousarray(challenges, dtype=np.uint8)
+        else:
+            ch = FrCodec(self.curve).enc(list(challenges))
+        depth = max(n_sub, 1).bit_length() - 1
+        fr = self.fr_bytes
+        sizes = [2 * n_sub, (2 + entry_fields) * n_sub, 2 * n_sub - 1, n_sub * depth, 1]
+        if out is not None:
+            outs = list(out)
+            assert [x.nbytes >= k * fr for x, k in zip(outs, sizes)] == [True] * 5
+        else:
+            outs = [DeviceBuffer(self, max(k, 1) * fr) if device_out else np.zeros(max(k, 0) * fr, dtype=np.uint8) for k in sizes]
+        a, b = hk_poseidon_desc(*ld), hk_poseidon_desc(*nd)
+        pp = lambda x: ptr(x).value if (x.nbytes if isinstance(x, DeviceBuffer) else x.size) else None
+        d = hk_exec_tree_desc(n_sub, int(entry_fields), offsets.ctypes.data, pp(keep[0]), pp(keep[1]), ch.ctypes.data,
+                              ptr(consts), int(n_consts), C.pointer(a), C.pointer(b))
+        o = hk_exec_tree_out(*[ptr(x) for x in outs])
+        try:
+            check(self.lib.hk_exec_tree(self.handle, C.byref(d), C.byref(o)), "hk_exec_tree")
+        except HekatonError:
+            if device_out and out is None:
+                for x in outs:
+                    x.free()
+            raise
+        return tuple(outs)
 
     def points_check(self, group, pts, n=None):
         """hk_points_check_g1 / _g2: ark's AffineRepr::check of each point (on its curve, in the prime-order subgroup;

@@ -660,6 +660,10 @@ hk_status hk_keygen(hk_ctx* ctx, const hk_keygen_desc* desc, const hk_keygen_out
     if (!ctx || !desc || !out) return HK_ERR_ARG;
     return ctx->ops->keygen(ctx, desc, out, m_out);
 }
+hk_status hk_exec_tree(hk_ctx* ctx, const hk_exec_tree_desc* desc, const hk_exec_tree_out* out) {
+    if (!ctx || !desc || !out) return HK_ERR_ARG;
+    return ctx->ops->exec_tree(ctx, desc, out);
+}
 
 }  // extern "C"
 

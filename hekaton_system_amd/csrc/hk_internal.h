@@ -218,6 +218,7 @@ struct CurveOps {
     hk_status (*qap_eval)(hk_ctx*, const hk_csr* A, const hk_csr* B, const hk_csr* C, size_t n_inst, size_t n_c, size_t n_v,
                           const void* t, void* a, void* b, void* c, void* zt, size_t* m_out);
     hk_status (*keygen)(hk_ctx*, const hk_keygen_desc*, const hk_keygen_out*, size_t* m_out);
+    hk_status (*exec_tree)(hk_ctx*, const hk_exec_tree_desc*, const hk_exec_tree_out*);
 };
 const CurveOps* curve_ops_bn254();
 const CurveOps* curve_ops_bls381();

@@ -1871,3 +1871,4 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
 }  // namespace hk
 
 #include "keygen.cuh"
+#include "exec_tree.cuh"

@@ -192,6 +192,21 @@ class ExecTree:
         self.root = level[0]
         self.depth = len(self.levels) - 1
 
+    @classmethod
+    def from_levels(cls, curve, leaves, levels):
+        """A tree whose digests were computed elsewhere (hk_exec_tree): levels[0] the leaf digests, then each level, the
+        root's last.  Offers the same root / depth / path / verify as a tree built here; nothing is re-hashed."""
+        n = len(leaves)
+        assert n >= 2 and n & (n - 1) == 0
+        assert [len(l) for l in levels] == [n >> k for k in range(n.bit_length())]
+        t = cls.__new__(cls)
+        t.leaf_cfg, t.node_cfg = merkle_params(curve)
+        t.leaves = [list(l) for l in leaves]
+        t.levels = [list(l) for l in levels]
+        t.root = t.levels[-1][0]
+        t.depth = len(t.levels) - 1
+        return t
+
     def path(self, i):
         sib, k = [], i
         for lvl in self.levels[:-1]:

@@ -947,10 +947,13 @@ class ShaMerkleJob:
         its time-ordered then its address-ordered entries, the variable order of `ShaMerkleSubcircuit._program`."""
         return [x for e in self.time[idx] for x in e] + [x for e in self.addr[idx] for x in e]
 
-    def set_challenges(self, entry_chal, tr_chal):
-        """Running evaluations entering every subcircuit (coordinator.rs:125-160 `generate_exec_tree`)."""
+    def set_challenges(self, entry_chal, tr_chal, ctx=None):
+        """Running evaluations entering every subcircuit (coordinator.rs:125-160 `generate_exec_tree`).  ctx (a
+        capi.Context of the job's curve): evaluations, tree and root come from one hk_exec_tree call instead."""
         n = self.n
         self.entry_chal, self.tr_chal = entry_chal % self.r, tr_chal % self.r
+        if ctx is not None:
+            return self._set_challenges_device(ctx)
         r, ech, tr = self.r, self.entry_chal, self.tr_chal
         step = lambda cur, e: cur * ((tr - (e[1] + ech * e[0])) % r) % r
         self.time_eval0, self.addr_eval0 = [1], [1]
@@ -969,6 +972,25 @@ class ShaMerkleJob:
         leaves = [[self.time_eval0[i + 1], self.addr_eval0[i + 1], self.addr[i][-1][0] % r, self.addr[i][-1][1] % r]
                   for i in range(n)]
         self.tree = ExecTree(self.curve, leaves)
+        self.root = self.tree.root
+
+    def _set_challenges_device(self, ctx):
+        from .poseidon import ExecTree, device_params
+        fc = FrCodec(self.curve)
+        n, k = self.n, self.np_
+        offsets = np.arange(n + 1, dtype=np.uint32) * k
+        flat = lambda tr: fc.enc([x for ops in tr for e in ops for x in e])
+        evals, leaves, nodes, _, _ = ctx.exec_tree(device_params(self.curve, fc), 2, offsets, flat(self.time), flat(self.addr),
+                                                   (self.entry_chal, self.tr_chal))
+        ev, lf, nd = fc.dec(evals), fc.dec(leaves), fc.dec(nodes)
+        self.time_eval0, self.addr_eval0 = [1] + ev[0::2], [1] + ev[1::2]
+        assert self.time_eval0[-1] == self.addr_eval0[-1]          # same multiset: the permutation check will hold
+        levels, at, w = [], 0, n
+        while w >= 1:
+            levels.append(nd[at:at + w])
+            at += w
+            w //= 2
+        self.tree = ExecTree.from_levels(self.curve, [lf[4 * i:4 * i + 4] for i in range(n)], levels)
         self.root = self.tree.root
 
     def class_of(self, idx):

@@ -10,6 +10,7 @@ rom_transcript.rs, ram_transcript.rs; coordinator.rs:92-160):
     running_evaluations                         the evals after every subcircuit = the leaves of `generate_exec_tree`
                                                 (coordinator.rs:125-160) without its Merkle tree (ark-crypto-primitives
                                                 `TreeConfig`, third-party, out of scope)
+    exec_tree_device                            the same leaves AND the tree (poseidon.ExecTree) from one hk_exec_tree call
 
 Plain Python ints; field arithmetic is a handful of products per entry.  The ark-serialize layouts are those the derives
 produce (field order of the structs; `RunningEvaluation` / `TranscriptEntry` enums carry a one-byte tag, mod.rs:47-66,
@@ -185,3 +186,51 @@ def running_evaluations(mem_type, super_com, r, time_ordered_subtraces, addr_ord
             last = ae
         leaves.append((evals.copy(), last))
     return leaves
+
+
+def flatten_subtraces(fc, subtraces):
+    """(offsets uint32 [n + 1], Montgomery bytes of the entries' to_field_elements(), row after row) of a list of
+    subtraces - the layout hk_exec_tree reads."""
+    import numpy as np
+    offsets = np.zeros(len(subtraces) + 1, dtype=np.uint32)
+    offsets[1:] = np.cumsum([len(st) for st in subtraces])
+    return offsets, fc.enc([x for st in subtraces for e in st for x in e.to_field_elements()])
+
+
+def exec_tree_device(ctx, mem_type, challenges_or_super_com, time_ordered_subtraces, addr_ordered_subtraces):
+    """`generate_exec_tree` (coordinator.rs:125-174) on the device: (leaves, tree).  leaves is exactly what
+    `running_evaluations` returns; tree is a poseidon.ExecTree over (time eval, addr eval, last entry's fields) built
+    from the digests hk_exec_tree computed.  challenges_or_super_com: the challenges in `RunningEvaluation.challenges`
+    order, or the super commitment (an aggregation.IppCom or its uncompressed bytes) they are hashed from."""
+    from .cp_groth16 import CURVE_PARAMS, FrCodec
+    from .poseidon import ExecTree, device_params
+    fc = FrCodec(ctx.curve)
+    r = CURVE_PARAMS[ctx.curve]["r"]
+    c = challenges_or_super_com
+    if isinstance(c, (bytes, bytearray)) or hasattr(c, "serialize_uncompressed"):
+        chal = RunningEvaluation.new(mem_type, c, r).challenges
+    else:
+        chal = tuple(x % r for x in c)
+    k = 2 if mem_type == ROM else 4
+    assert len(chal) == k and len(time_ordered_subtraces) == len(addr_ordered_subtraces)
+    offsets, time_b = flatten_subtraces(fc, time_ordered_subtraces)
+    offsets_a, addr_b = flatten_subtraces(fc, addr_ordered_subtraces)
+    assert (offsets == offsets_a).all()
+    n = len(time_ordered_subtraces)
+    evals, leaves_b, nodes, _, _ = ctx.exec_tree(device_params(ctx.curve, fc), k, offsets, time_b, addr_b, chal)
+    ev = fc.dec(evals)
+    pad = (RomTranscriptEntry if mem_type == ROM else RamTranscriptEntry).padding()
+    leaves, last = [], pad
+    for i, st in enumerate(addr_ordered_subtraces):
+        if st:
+            last = st[-1]
+        leaves.append((RunningEvaluation(mem_type, r, chal, ev[2 * i], ev[2 * i + 1]), last))
+    fields = fc.dec(leaves_b)
+    nd = fc.dec(nodes)
+    levels, at, w = [], 0, n
+    while w >= 1:
+        levels.append(nd[at:at + w])
+        at += w
+        w //= 2
+    tree = ExecTree.from_levels(ctx.curve, [fields[i * (2 + k):(i + 1) * (2 + k)] for i in range(n)], levels)
+    return leaves, tree

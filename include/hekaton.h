@@ -478,6 +478,41 @@ typedef struct {
  * context's window-table cache with hk_fixed_base_g1 / _g2.  Errors: see above. */
 hk_status hk_keygen(hk_ctx* ctx, const hk_keygen_desc* desc, const hk_keygen_out* out, size_t* m_out);
 
+/* ---- the coordinator between the two rounds (distributed-prover/src/coordinator.rs:125-174, 425-466) ---------------
+ * Once the stage-0 commitments are hashed to the challenges, `generate_exec_tree` threads the running evaluations through
+ * every subtrace (transcript/mod.rs:85-132: eval *= tr_chal - repr(entry)), forms one leaf per subcircuit
+ * (eval_tree.rs:53-101) and builds the Poseidon Merkle tree over them; `CoordinatorStage1State::new` then takes one
+ * `generate_proof` path per subcircuit.  hk_exec_tree does all of it in one call from the two flattened traces:
+ *   factor of an entry f     tr_chal - (f[1] + c0 f[0] [+ c1 f[2] + c2 f[3]])   (rom_transcript.rs:84-86, ram :109-112)
+ *   evaluation i             product of the factors of entries [0, offsets[i + 1]), from 1, per order
+ *   leaf i                   (time eval, addr eval, last entry): the last entry is entry offsets[i + 1] - 1 of the address
+ *                            order, all zero when offsets[i + 1] == 0 (`padding()`); an empty subtrace carries the previous
+ *                            one over (coordinator.rs:137-160)
+ *   leaf digest              the rate-3 sponge over the 2 + entry_fields leaf fields (two permutations), inner node = the
+ *                            two-to-one hash of its children (poseidon_util.rs:26-107)
+ * The address sort (coordinator.rs:92-123) does not depend on the challenges and stays with the caller.  siblings_mont and
+ * leaves_mont are what hk_poseidon_path takes as they are (ROM).  HK_ERR_ARG, before any device work and with the outputs
+ * untouched: n_sub not a power of two or 1, entry_fields not 2 / 4, offsets[0] != 0 or decreasing offsets, a descriptor
+ * other than the compiled (t 4, alpha 5) leaf / (t 3, alpha 17) node pair, constants that end before its tables do. */
+typedef struct {
+    uint32_t n_sub;                 /* leaves = subcircuits; a power of two >= 2 (ark MerkleTree::new) */
+    uint32_t entry_fields;          /* 2 = ROM (addr, val); 4 = RAM (addr, val, timestamp, is_read): to_field_elements() order */
+    const uint32_t* offsets;        /* [h] n_sub + 1; offsets[0] = 0, non-decreasing: subtrace i = entries [offsets[i], offsets[i+1]) of BOTH orders */
+    const void* time_entries_mont;  /* [h|d] offsets[n_sub] x entry_fields Fr */
+    const void* addr_entries_mont;  /* [h|d] same shape, address-ordered */
+    const void* challenges_mont;    /* [h] entry_fields Fr in the reference's challenges() order: entry challenge(s), then tr_chal */
+    const void* consts_mont; size_t n_consts;             /* as hk_poseidon_path */
+    const hk_poseidon_desc* leaf_hash; const hk_poseidon_desc* node_hash;
+} hk_exec_tree_desc;
+typedef struct {                    /* every pointer [h|d]; evals / nodes may be NULL */
+    void* evals_mont;               /* n_sub x 2 Fr: (time, addr) evaluation AFTER subcircuit i */
+    void* leaves_mont;              /* n_sub x (2 + entry_fields) Fr: ExecTreeLeaf::to_field_elements (eval_tree.rs:81-94) */
+    void* nodes_mont;               /* 2 n_sub - 1 Fr: leaf digests, then each level, root last */
+    void* siblings_mont;            /* n_sub x depth Fr, bottom-up: hk_poseidon_path's `siblings_mont` as is */
+    void* root_mont;                /* 1 Fr */
+} hk_exec_tree_out;
+hk_status hk_exec_tree(hk_ctx* ctx, const hk_exec_tree_desc* desc, const hk_exec_tree_out* out);
+
 #ifdef __cplusplus
 }
 #endif
