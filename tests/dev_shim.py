@@ -1,5 +1,6 @@
-"""Loader and integer packing for the test-only device shim (tests/device_shim/field_dev_shim.hip): plain helper of
-tests/test_field_device_gpu.py and tests/test_wave_f12_gpu.py.  The shim runs in the calling process."""
+"""Loaders and integer packing for the test-only device shims: tests/device_shim/field_dev_shim.hip (plain helper of
+tests/test_field_device_gpu.py and tests/test_wave_f12_gpu.py) and tests/device_shim/ec_dev_shim.hip (of
+tests/test_ec_device_gpu.py and tests/test_msm_plan_device_gpu.py).  The shims run in the calling process."""
 import ctypes
 import os
 
@@ -11,7 +12,21 @@ ADD, SUB, MUL, SQR, NEG, DBL, HALVE, CANON, TO_MONT, FROM_MONT, INV, IS_ZERO, EQ
 W_MUL, W_SQR, W_CYC_SQR, W_CONJ, W_FROB1, W_FROB2, W_FROB3, W_INV = range(8)
 ALIAS_NONE, ALIAS_A, ALIAS_B, ALIAS_ALL = range(4)
 
+# ec_dev_shim.hip
+EC_VARIANTS = {"asm": "libec_dev_shim.so", "noasm": "libec_dev_shim_noasm.so"}
+(G_MADD, G_MADD_NI, G_ADD, G_ADD_NI, G_DBL, G_DBL_NI, G_DBL_AFFINE, G_NEG, G_TO_AFFINE, G_MUL_SMALL, G_MUL_LIMBS,
+ G_MADD_CHAIN) = range(12)
+HIP_NOT_SUPPORTED = 801
+# what the -DHK_NO_ASM_MUL build leaves out, by group id: with the C++ product these forms outgrow the code-object bounds
+# (see op_built in ec_dev_shim.hip); the shim answers hipErrorNotSupported for them.  EcShim.built asserts that this table
+# and the shim's op_built agree
+EC_NOASM_NOT_BUILT = {
+    1: {G_MADD, G_MADD_NI, G_ADD, G_ADD_NI, G_MUL_SMALL, G_MUL_LIMBS, G_MADD_CHAIN},
+    2: {G_MADD, G_MADD_CHAIN},
+}
+
 _loaded = {}
+_loaded_ec = {}
 
 
 def pack(elems, nbytes):
@@ -64,3 +79,74 @@ def load(variant):
     if variant not in _loaded:
         _loaded[variant] = DevShim(variant)
     return _loaded[variant]
+
+
+class EcShim:
+    """Points travel as slots of four coordinate-field elements (x, y, zz, zzz; an affine point fills the first two), each an
+    int (G1) or a (c0, c1) tuple (G2) of RAW limbs: Montgomery values, possibly non-canonical representatives."""
+
+    def __init__(self, variant):
+        path = os.path.join(ROOT, "hekaton_system_amd", "lib", EC_VARIANTS[variant])
+        assert os.path.exists(path), "build the device shim first (python __graft_entry__.py)"
+        self.variant = variant
+        self.lib = ctypes.CDLL(path)
+        self.lib.dshim_group_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+                                            ctypes.c_size_t, ctypes.c_int, ctypes.c_uint]
+        self.lib.dshim_batch_affine.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint]
+        self.lib.dshim_msm.argtypes = [ctypes.c_int] + [ctypes.c_uint] * 6 + [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int,
+                                                                               ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint)]
+        assert self.lib.dshim_ec_uses_asm() == (1 if variant == "asm" else 0)
+        assert self.lib.dshim_ec_has_msm() == (1 if variant == "asm" else 0)
+
+    def built(self, gid, op):
+        """whether this build holds `op` for group `gid`: the table above, which must agree with the shim's own op_built"""
+        want = self.variant == "asm" or op not in EC_NOASM_NOT_BUILT.get(gid, ())
+        assert bool(self.lib.dshim_ec_op_built(gid, op)) == want, "EC_NOASM_NOT_BUILT and op_built differ: g%d op %d" % (gid, op)
+        return want
+
+    def group_op_status(self, gid, op, nbytes, a, b=None, raw=0, k=0):
+        """-> (status, slots): status 0, or minus the hipError_t"""
+        width = 1 if isinstance(a[0][0], int) else len(a[0][0])
+        abuf = b"".join(pack(list(slot), nbytes) for slot in a)
+        bbuf = None if b is None else b"".join(pack(list(slot), nbytes) for slot in b)
+        assert bbuf is None or len(bbuf) == len(abuf)
+        out = ctypes.create_string_buffer(len(abuf))
+        st = self.lib.dshim_group_op(gid, op, abuf, bbuf, out, len(a), raw, k)
+        if st != 0:
+            return st, None
+        elems = unpack(out.raw, nbytes, width)
+        return 0, [tuple(elems[i:i + 4]) for i in range(0, len(elems), 4)]
+
+    def group_op(self, gid, op, nbytes, a, b=None, raw=0, k=0):
+        st, slots = self.group_op_status(gid, op, nbytes, a, b, raw, k)
+        assert st == 0, "dshim_group_op(group %d, op %d): HIP error %d" % (gid, op, -st)
+        return slots
+
+    def batch_affine(self, gid, nbytes, pts, chunk):
+        """pts: XYZZ slots as they lie in memory -> list of (x, y)"""
+        width = 1 if isinstance(pts[0][0], int) else len(pts[0][0])
+        buf = b"".join(pack(list(slot), nbytes) for slot in pts)
+        out = ctypes.create_string_buffer(len(buf) // 2)
+        st = self.lib.dshim_batch_affine(gid, buf, out, len(pts), chunk)
+        assert st == 0, "dshim_batch_affine(group %d, n %d, chunk %d): HIP error %d" % (gid, len(pts), chunk, -st)
+        elems = unpack(out.raw, nbytes, width)
+        return [tuple(elems[i:i + 2]) for i in range(0, len(elems), 2)]
+
+    def msm(self, gid, c, WP, n, bases, scalars, mont, batch=1, n_bases=None, idx_off=0, point_bytes=0):
+        """bases: bytes of n_bases affine points (memory form), scalars: bytes of batch x n Fr -> (status, bytes of batch
+        affine points or None, plan words W, F, NB, n_levels, T[0], T[1], Lmin0, K, lanes).  status: 0, the product's hk_status
+        (> 0), or minus a hipError_t."""
+        if n_bases is None:
+            n_bases = n
+        assert len(bases) == n_bases * point_bytes and len(scalars) == batch * n * 32
+        out = ctypes.create_string_buffer(batch * point_bytes)
+        plan = (ctypes.c_uint * 9)()
+        st = self.lib.dshim_msm(gid, c, WP, batch, n, n_bases, idx_off, bytes(bases) if n_bases else None, bytes(scalars),
+                                1 if mont else 0, out, plan)
+        return st, (out.raw if st == 0 else None), list(plan)
+
+
+def load_ec(variant):
+    if variant not in _loaded_ec:
+        _loaded_ec[variant] = EcShim(variant)
+    return _loaded_ec[variant]
