@@ -83,6 +83,15 @@ class hk_exec_tree_out(C.Structure):          # include/hekaton.h
                 ("siblings_mont", C.c_void_p), ("root_mont", C.c_void_p)]
 
 
+class hk_stage1_desc(C.Structure):            # include/hekaton.h
+    _fields_ = [("n_sub", C.c_uint32), ("n_portals", C.c_uint32), ("depth", C.c_uint32), ("offsets", C.c_void_p),
+                ("time_entries_mont", C.c_void_p), ("addr_entries_mont", C.c_void_p), ("challenges_mont", C.c_void_p),
+                ("evals_mont", C.c_void_p), ("leaves_mont", C.c_void_p), ("siblings_mont", C.c_void_p),
+                ("root_mont", C.c_void_p), ("consts_mont", C.c_void_p), ("n_consts", C.c_size_t),
+                ("leaf_hash", C.POINTER(hk_poseidon_desc)), ("node_hash", C.POINTER(hk_poseidon_desc)),
+                ("inst_col0", C.c_uint32), ("col0", C.c_uint32), ("pos_col0", C.c_uint32)]
+
+
 class hk_timings(C.Structure):
     _fields_ = [(n, C.c_float) for n in
                 ("total_ms", "digits_ms", "msm_a_ms", "msm_b_g1_ms", "msm_b_g2_ms", "msm_l_ms",
@@ -102,7 +111,7 @@ EXPORTS = ["hk_status_str", "hk_version", "hk_ctx_create", "hk_ctx_destroy", "hk
            "hk_msm_bases", "hk_multi_pairing", "hk_pairing_products", "hk_ctx_gt_bytes",
            "hk_points_lincomb_g1", "hk_points_lincomb_g2", "hk_points_fold_g2", "hk_points_fold_g1", "hk_points_fold_many_g1", "hk_points_fold_many_g2", "hk_pairing_pairs", "hk_keccak_f1600", "hk_assignment_from_bits", "hk_wprog_upload", "hk_wprog_free", "hk_wprog_run", "hk_gt_pow", "hk_fq12_pow", "hk_gt_pow_prod", "hk_poseidon_path", "hk_assignment_scatter", "hk_commit_batch",
            "hk_prove_batch", "hk_vk_prepare", "hk_vk_free", "hk_vk_alpha_beta", "hk_verify_batch", "hk_points_check_g1",
-           "hk_points_check_g2", "hk_qap_eval", "hk_keygen", "hk_exec_tree"]
+           "hk_points_check_g2", "hk_qap_eval", "hk_keygen", "hk_exec_tree", "hk_stage1_witness"]
 
 HK_VERIFY_CHECK_POINTS = 1
 VERDICT_REJECT, VERDICT_ACCEPT, VERDICT_BAD_POINT = 0, 1, 2
@@ -192,6 +201,7 @@ def load():
                                 C.POINTER(sz)]
     lib.hk_keygen.argtypes = [vp, C.POINTER(hk_keygen_desc), C.POINTER(hk_keygen_out), C.POINTER(sz)]
     lib.hk_exec_tree.argtypes = [vp, C.POINTER(hk_exec_tree_desc), C.POINTER(hk_exec_tree_out)]
+    lib.hk_stage1_witness.argtypes = [vp, C.POINTER(hk_stage1_desc), vp, sz, sz, vp]
     _lib = lib
     return lib
 
@@ -671,6 +681,38 @@ class Context:
                     x.free()
             raise
         return tuple(outs)
+
+    def stage1_witness(self, params, n_portals, offsets, time_entries, addr_entries, challenges, exec_outs, sub_index, n_v,
+                       layout, z_out):
+        """hk_stage1_witness: every challenge-dependent column of the assignments of the subcircuits `sub_index` (any order,
+        repeats allowed; row b of z_out = subcircuit sub_index[b]), from what exec_tree took and returned.  params, offsets,
+        time_entries, addr_entries, challenges: as exec_tree takes them (ROM entries: 2 Fr each; challenges = entry_chal,
+        tr_chal); exec_outs: exec_tree's return value (evals, leaves, nodes, siblings, root), numpy arrays or DeviceBuffers;
+        n_portals: the entries each selected subcircuit owns per order; layout: (inst_col0, col0, pos_col0) - the first
+        column of the three instance values, of the 10 n_portals + 4 portal columns and of the membership block; z_out:
+        DeviceBuffer (or raw device address) of len(sub_index) x n_v Fr.  Every other column keeps its bytes."""
+        from .cp_groth16 import FrCodec
+        consts, n_consts, ld, nd = params
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+        n_sub = offsets.size - 1
+        sub_index = np.ascontiguousarray(sub_index, dtype=np.uint32)
+        evals, leaves, _nodes, siblings, root = exec_outs
+        keep = [x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8)
+                for x in (time_entries, addr_entries, evals, leaves, siblings, root)]
+        if isinstance(challenges, np.ndarray):
+            ch = np.ascontiguousarray(challenges, dtype=np.uint8)
+        else:
+            ch = FrCodec(self.curve).enc(list(challenges))
+        a, b = hk_poseidon_desc(*ld), hk_poseidon_desc(*nd)
+        pp = lambda x: ptr(x).value if (x.nbytes if isinstance(x, DeviceBuffer) else x.size) else None
+        inst_col0, col0, pos_col0 = layout
+        d = hk_stage1_desc(n_sub, int(n_portals), max(n_sub, 1).bit_length() - 1, offsets.ctypes.data, pp(keep[0]), pp(keep[1]),
+                           ch.ctypes.data, pp(keep[2]), pp(keep[3]), pp(keep[4]), pp(keep[5]), ptr(consts), int(n_consts),
+                           C.pointer(a), C.pointer(b), int(inst_col0), int(col0), int(pos_col0))
+        zp = z_out.ptr if isinstance(z_out, DeviceBuffer) else int(z_out)
+        check(self.lib.hk_stage1_witness(self.handle, C.byref(d), sub_index.ctypes.data if sub_index.size else None,
+                                         sub_index.size, int(n_v), zp), "hk_stage1_witness")
+        return z_out
 
     def points_check(self, group, pts, n=None):
         """hk_points_check_g1 / _g2: ark's AffineRepr::check of each point (on its curve, in the prime-order subgroup;

@@ -27,15 +27,20 @@ constexpr u32 ET_WG_STATES = 64;       // Poseidon states of one 256-lane workgr
 // the challenges in the reference's challenges() order: c[0 .. K - 2] the entry challenges, c[K - 1] = tr_chal
 template <class Fr> struct EtChal { Fr c[4]; };
 
-// tr_chal - (f[1] + c0 f[0] [+ c1 f[2] + c2 f[3]]) of one entry (rom_transcript.rs:84-86, ram_transcript.rs:109-112)
+// f[1] + c0 f[0] [+ c1 f[2] + c2 f[3]]: the representation of one entry, and its factor tr_chal - repr
+// (rom_transcript.rs:84-86, ram_transcript.rs:109-112)
 template <class Fr, int K>
-__device__ __forceinline__ Fr et_factor(const Fr* __restrict__ e, const EtChal<Fr>& ch) {
+__device__ __forceinline__ Fr et_repr(const Fr* __restrict__ e, const EtChal<Fr>& ch) {
     Fr r = Fr::add(fr_load(&e[1]), Fr::mul(ch.c[0], fr_load(&e[0])));
     if constexpr (K == 4) {
         r = Fr::add(r, Fr::mul(ch.c[1], fr_load(&e[2])));
         r = Fr::add(r, Fr::mul(ch.c[2], fr_load(&e[3])));
     }
-    return Fr::sub(ch.c[K - 1], r);
+    return r;
+}
+template <class Fr, int K>
+__device__ __forceinline__ Fr et_factor(const Fr* __restrict__ e, const EtChal<Fr>& ch) {
+    return Fr::sub(ch.c[K - 1], et_repr<Fr, K>(e, ch));
 }
 template <class Fr>
 __device__ __forceinline__ Fr et_select(bool take, const Fr& a, const Fr& b) {

@@ -664,6 +664,11 @@ hk_status hk_exec_tree(hk_ctx* ctx, const hk_exec_tree_desc* desc, const hk_exec
     if (!ctx || !desc || !out) return HK_ERR_ARG;
     return ctx->ops->exec_tree(ctx, desc, out);
 }
+hk_status hk_stage1_witness(hk_ctx* ctx, const hk_stage1_desc* desc, const uint32_t* sub_index, size_t batch, size_t n_v,
+                            void* z_out) {
+    if (!ctx || !desc) return HK_ERR_ARG;
+    return ctx->ops->stage1_witness(ctx, desc, sub_index, batch, n_v, z_out);
+}
 
 }  // extern "C"
 

@@ -219,6 +219,7 @@ struct CurveOps {
                           const void* t, void* a, void* b, void* c, void* zt, size_t* m_out);
     hk_status (*keygen)(hk_ctx*, const hk_keygen_desc*, const hk_keygen_out*, size_t* m_out);
     hk_status (*exec_tree)(hk_ctx*, const hk_exec_tree_desc*, const hk_exec_tree_out*);
+    hk_status (*stage1_witness)(hk_ctx*, const hk_stage1_desc*, const uint32_t* sub_index, size_t batch, size_t n_v, void* z_out);
 };
 const CurveOps* curve_ops_bn254();
 const CurveOps* curve_ops_bls381();

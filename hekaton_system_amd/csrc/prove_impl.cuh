@@ -1198,10 +1198,6 @@ hk_status Ops<C>::poseidon_path(hk_ctx* ctx, const void* consts, size_t n_consts
     if (batch == 0) return HK_OK;
     if (!consts || !lh || !nh || !leaf || !index || (depth && !siblings) || !is_device_ptr(z_out)) return HK_ERR_ARG;
     if (batch >= (1u << 20) || depth > 32) return HK_ERR_ARG;
-    auto per_perm = [](const hk_poseidon_desc* d) -> size_t {          // witnesses of one permutation
-        size_t chain = d->alpha == 5 ? 3 : 5;
-        return (size_t)d->full_rounds * (d->t * chain + d->t) + (size_t)d->partial_rounds * (chain + d->t);
-    };
     for (const hk_poseidon_desc* d : {lh, nh}) {
         if (d->t < 2 || d->t > 4 || (d->alpha != 5 && d->alpha != 17) || (d->full_rounds & 1) ||
             (size_t)d->consts_offset + (size_t)(d->full_rounds + d->partial_rounds) * d->t + (size_t)d->t * d->t > n_consts)
@@ -1210,7 +1206,7 @@ hk_status Ops<C>::poseidon_path(hk_ctx* ctx, const void* consts, size_t n_consts
     // the kernel is compiled for the reference's two instances (poseidon_util.rs:53-62): rate 3 / x^5 over the 4 leaf
     // fields, rate 2 / x^17 for two-to-one; round counts and constants stay run-time data
     if (lh->t != 4 || nh->t != 3 || lh->alpha != 5 || nh->alpha != 17) return HK_ERR_ARG;
-    size_t block = 2 * per_perm(lh) + depth * (3 + per_perm(nh));
+    size_t block = 2 * poseidon_trace_len(lh) + depth * (3 + poseidon_trace_len(nh));
     if (col0 > n_v || block > n_v - col0) return HK_ERR_ARG;
     LaneGuard g(ctx);
     Lane* L = g.lane;
@@ -1872,3 +1868,4 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
 
 #include "keygen.cuh"
 #include "exec_tree.cuh"
+#include "stage1.cuh"

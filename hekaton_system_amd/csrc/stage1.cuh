@@ -1,0 +1,234 @@
+// stage1.cuh — the challenge-dependent columns of a subcircuit's stage-1 assignment on the device (hk_stage1_witness,
+// DESIGN.md section 4i): what distributed-prover/src/subcircuit_circuit.rs:206-252 witnesses from the Stage1Request of
+// coordinator.rs:569-604, taken from hk_exec_tree's outputs where they lie.  Included at the end of prove_impl.cuh.
+//
+//   k_s1_values      the three instance values and the portal block (10 k + 4 columns for k entries per order): copies, the two
+//                    running-evaluation chains, the address-step (inv, same) pairs.  One lane per (role, row), role-major, so
+//                    the lanes of a wave share a role: 4 k + 5 copies, 2 chains of k products, k inversions.
+//   k_s1_membership  the Poseidon membership block on a quad of lanes per row: poseidon_permute_quad with every S-box chain and
+//                    round state stored where k_poseidon_path's one lane stores them.
+#pragma once
+#include "exec_tree.cuh"
+
+namespace hk {
+
+constexpr u32 S1_WG_ROWS = 64;         // rows of one 256-lane workgroup of k_s1_membership (a quad each)
+
+#if defined(__HIPCC__)
+
+// Row b of z is subcircuit i = rows[2 b], whose entries start at off = rows[2 b + 1] in both orders.  Lane g: role g / batch,
+// row g % batch.  Roles, with K = n_portals:
+//   [0, 3)               instance: entry_chal, tr_chal, root                          -> inst_col0 + role
+//   [3, 3 + 4 K)         (addr, val) of the K time-ordered then the K address-ordered entries -> col0 + (role - 3)
+//   [3 + 4 K, 5 + 4 K)   the previous leaf's last address-ordered entry, zero in front of entry 0    -> col0 + 8 K + 2 + f
+//   [5 + 4 K, 7 + 4 K)   chain of order y: evals[i - 1][y] (1 for i = 0), then per entry e = val + entry_chal addr and
+//                        cur <- cur (tr_chal - e)                                     -> col0 + 4 K + y (1 + 2 K) ...
+//   [7 + 4 K, 7 + 5 K)   step j: d = addr[off + j] - addr[off + j - 1] (minus 0 at entry 0), inv = 1 / d or 0, same = [d == 0]
+//                                                                                    -> col0 + 8 K + 4 + 2 j, + 1
+template <class Fr>
+__global__ void __launch_bounds__(256)
+k_s1_values(const Fr* __restrict__ time_e, const Fr* __restrict__ addr_e, const u32* __restrict__ rows, u32 batch, u32 K,
+            EtChal<Fr> ch, const Fr* __restrict__ evals, const Fr* __restrict__ root, size_t n_v, size_t inst_col0, size_t col0,
+            Fr* __restrict__ z_out) {
+    const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
+    const u32 role = g / batch, b = g % batch;
+    if (role >= 7 + 5 * K) return;
+    const u32 i = rows[2 * b];
+    const u64 off = rows[2 * b + 1];
+    Fr* z = z_out + (size_t)b * n_v;
+    if (role < 3) {
+        fr_store(&z[inst_col0 + role], role == 2 ? fr_load(root) : ch.c[role]);
+    } else if (role < 3 + 4 * K) {
+        const u32 c = role - 3;                                    // 2 K Fr of the time order, then 2 K of the address order
+        const Fr* src = c < 2 * K ? time_e + off * 2 + c : addr_e + off * 2 + (c - 2 * K);
+        fr_store(&z[col0 + c], fr_load(src));
+    } else if (role < 5 + 4 * K) {
+        const u32 f = role - (3 + 4 * K);
+        Fr x = Fr::zero();
+        if (off) x = fr_load(&addr_e[(off - 1) * 2 + f]);
+        fr_store(&z[col0 + 8 * K + 2 + f], x);
+    } else if (role < 7 + 4 * K) {
+        const u32 y = role - (5 + 4 * K);
+        const Fr* e = (y ? addr_e : time_e) + off * 2;
+        Fr* w = z + col0 + 4 * K + y * (1 + 2 * K);
+        Fr cur = Fr::one();
+        if (i) cur = fr_load(&evals[(size_t)(i - 1) * 2 + y]);
+        fr_store(w++, cur);
+        HK_NOUNROLL for (u32 j = 0; j < K; j++) {
+            Fr r = et_repr<Fr, 2>(e + 2 * (size_t)j, ch);
+            cur = Fr::mul(cur, Fr::sub(ch.c[1], r));
+            fr_store(w++, r);
+            fr_store(w++, cur);
+        }
+    } else {
+        const u32 j = role - (7 + 4 * K);
+        const u64 at = off + j;
+        Fr d = fr_load(&addr_e[at * 2]);
+        if (at) d = Fr::sub(d, fr_load(&addr_e[(at - 1) * 2]));
+        d = Fr::canon(d);
+        Fr* w = z + col0 + 8 * K + 4 + 2 * j;
+        fr_store(&w[0], fp_inv(d));                                // maps 0 to 0
+        fr_store(&w[1], d.is_zero() ? Fr::one() : Fr::zero());
+    }
+}
+
+// poseidon_permute_quad with the trace of poseidon_permute_trace: in a round that starts at w, lane i < T stores its S-box
+// chain (L = 3 values at ALPHA 5, 5 at 17) at w + i L + step when the round is full or i = 0, and its new state element at
+// w + (full ? T : 1) L + i; w advances by the same amount on every lane.  `store` is false on the lanes of a quad past the
+// batch and on the fourth lane at T = 3: they compute along (every lane of a quad is in every DPP exchange) and write nothing.
+template <class Fr, int T, int ALPHA>
+__device__ __forceinline__ Fr s1_permute_quad_trace(const Fr* __restrict__ consts, const PoseidonDesc& d, Fr s, bool store,
+                                                    Fr*& w) {
+    static_assert(T == 3 || T == 4, "one state element per lane of a quad");
+    constexpr u32 L = ALPHA == 5 ? 3 : 5;
+    const u32 q = threadIdx.x & 3u;
+    const u32 qc = q < (u32)T ? q : 0u;
+    const Fr* ark = consts + d.off;
+    const Fr* mds = ark + (size_t)(d.rf + d.rp) * T;
+    const u32 rounds = d.rf + d.rp, half = d.rf / 2;
+    const bool mine = store && q < (u32)T;
+    Fr m[T];
+    HK_UNROLL for (int j = 0; j < T; j++) m[j] = fr_load(&mds[qc * T + j]);
+    Fr k = fr_load(&ark[qc]);
+    HK_NOUNROLL for (u32 r = 0; r < rounds; r++) {
+        const bool full = r < half || r >= half + d.rp;
+        const bool keep = full || q == 0;
+        const bool trace = mine && keep;
+        Fr* c = w + qc * L;
+        Fr y = Fr::add(s, k);
+        k = fr_load(&ark[(r + 1 < rounds ? r + 1 : r) * T + qc]);       // the next round's constant, under this round's products
+        Fr x = Fr::mul(y, y);
+        if (trace) fr_store(c++, x);
+        HK_UNROLL for (int e = 0; e < (ALPHA == 5 ? 1 : 3); e++) {
+            x = Fr::mul(x, x);
+            if (trace) fr_store(c++, x);
+        }
+        x = Fr::mul(x, y);
+        if (trace) fr_store(c, x);
+        x = et_select(keep, x, y);
+        s = Fr::mul(m[0], et_quad_bcast<Fr, 0x00>(x));
+        s = Fr::add(s, Fr::mul(m[1], et_quad_bcast<Fr, 0x55>(x)));
+        s = Fr::add(s, Fr::mul(m[2], et_quad_bcast<Fr, 0xAA>(x)));
+        if constexpr (T == 4) s = Fr::add(s, Fr::mul(m[3], et_quad_bcast<Fr, 0xFF>(x)));
+        w += (full ? (u32)T : 1u) * L;
+        if (mine) fr_store(&w[qc], s);
+        w += T;
+    }
+    return s;
+}
+
+// One quad per row: the membership block of subcircuit i = rows[2 b] - leaf leaves[i], path siblings[i], index i - in the order
+// of k_poseidon_path / sha_circuit.poseidon_path_trace, at column pos_col0 of row b.  A quad past the batch recomputes the last
+// row and stores nothing: no lane leaves in front of a DPP read.
+template <class Fr>
+__global__ void __launch_bounds__(256)
+k_s1_membership(const Fr* __restrict__ consts, PoseidonDesc leaf_d, PoseidonDesc node_d, const Fr* __restrict__ leaves,
+                const Fr* __restrict__ siblings, const u32* __restrict__ rows, u32 depth, u32 batch, size_t n_v, size_t pos_col0,
+                Fr* __restrict__ z_out) {
+    const u32 t = (blockIdx.x * blockDim.x + threadIdx.x) >> 2;
+    const u32 q = threadIdx.x & 3u;
+    const bool store = t < batch;
+    const u32 b = store ? t : batch - 1;
+    const u32 i = rows[2 * b];
+    const Fr* leaf = leaves + (size_t)i * 4;
+    Fr* w = z_out + (size_t)b * n_v + pos_col0;
+    // the rate-3 sponge over the 4 leaf fields (et_leaf_digest with the trace): every lane loads an index it may read
+    Fr s = et_select(q != 0, fr_load(&leaf[q ? q - 1 : 0]), Fr::zero());
+    s = s1_permute_quad_trace<Fr, 4, 5>(consts, leaf_d, s, store, w);
+    s = Fr::add(s, et_select(q == 1, fr_load(&leaf[3]), Fr::zero()));
+    s = s1_permute_quad_trace<Fr, 4, 5>(consts, leaf_d, s, store, w);
+    Fr cur = et_quad_bcast<Fr, 0x55>(s);
+    HK_NOUNROLL for (u32 l = 0; l < depth; l++) {
+        const Fr sib = fr_load(&siblings[(size_t)i * depth + l]);
+        const bool bit = (i >> l) & 1u;
+        const Fr left = et_select(bit, sib, cur), right = et_select(bit, cur, sib);
+        // bit / sibling / left: lane 0, 1, 2 one each
+        Fr v = et_select(q == 1, sib, left);
+        v = et_select(q == 0, bit ? Fr::one() : Fr::zero(), v);
+        if (store && q < 3) fr_store(&w[q], v);
+        w += 3;
+        s = et_select(q == 1, left, et_select(q == 2, right, Fr::zero()));
+        s = s1_permute_quad_trace<Fr, 3, 17>(consts, node_d, s, store, w);
+        cur = et_quad_bcast<Fr, 0x55>(s);
+    }
+}
+
+#endif  // __HIPCC__
+
+template <class C>
+hk_status Ops<C>::stage1_witness(hk_ctx* ctx, const hk_stage1_desc* d, const uint32_t* sub_index, size_t batch, size_t n_v,
+                                 void* z_out) {
+    if (!d->offsets || !d->time_entries_mont || !d->addr_entries_mont || !d->challenges_mont || !d->evals_mont ||
+        !d->leaves_mont || !d->siblings_mont || !d->root_mont || !d->consts_mont || !d->leaf_hash || !d->node_hash ||
+        (batch && (!sub_index || !z_out)))
+        return HK_ERR_ARG;
+    const size_t n_sub = d->n_sub, K = d->n_portals, depth = d->depth;
+    if (n_sub < 2 || (n_sub & (n_sub - 1)) || n_sub > ((size_t)1 << 24) || depth > 24 || ((size_t)1 << depth) != n_sub)
+        return HK_ERR_ARG;
+    if (K == 0 || K > (1u << 16) || batch >= (1u << 20) || (7 + 5 * K) * batch >= ((size_t)1 << 31)) return HK_ERR_ARG;   // lanes of k_s1_values
+    if (d->offsets[0] != 0) return HK_ERR_ARG;
+    for (size_t i = 0; i < n_sub; i++)
+        if (d->offsets[i + 1] < d->offsets[i]) return HK_ERR_ARG;
+    std::vector<u32> rows(2 * batch);                      // (subcircuit, its first entry) per row; outlives the lane's copies
+    for (size_t b = 0; b < batch; b++) {
+        const u32 i = sub_index[b];
+        if (i >= n_sub || d->offsets[i + 1] - d->offsets[i] != K) return HK_ERR_ARG;
+        rows[2 * b] = i;
+        rows[2 * b + 1] = d->offsets[i];
+    }
+    const hk_poseidon_desc *lh = d->leaf_hash, *nh = d->node_hash;
+    for (const hk_poseidon_desc* p : {lh, nh}) {
+        if ((p->full_rounds & 1) || p->full_rounds + p->partial_rounds == 0 ||
+            (size_t)p->consts_offset + (size_t)(p->full_rounds + p->partial_rounds) * p->t + (size_t)p->t * p->t > d->n_consts)
+            return HK_ERR_ARG;
+    }
+    // compiled for the reference's two instances (poseidon_util.rs:53-62), as hk_poseidon_path and hk_exec_tree are
+    if (lh->t != 4 || nh->t != 3 || lh->alpha != 5 || nh->alpha != 17) return HK_ERR_ARG;
+    // the three column ranges: inside [1, n_v), no two overlapping
+    const size_t lo[3] = {d->inst_col0, d->col0, d->pos_col0};
+    const size_t len[3] = {3, 10 * K + 4, 2 * poseidon_trace_len(lh) + depth * (3 + poseidon_trace_len(nh))};   // as hk_poseidon_path
+    for (int a = 0; a < 3; a++) {
+        if (lo[a] < 1 || lo[a] > n_v || len[a] > n_v - lo[a]) return HK_ERR_ARG;
+        for (int b = 0; b < a; b++)
+            if (lo[a] < lo[b] + len[b] && lo[b] < lo[a] + len[a]) return HK_ERR_ARG;
+    }
+    if (batch == 0) return HK_OK;
+    if (!is_device_ptr(z_out)) return HK_ERR_ARG;
+
+    const size_t n = d->offsets[n_sub], fr = sizeof(Fr);
+    struct In { const void* src; size_t bytes; const void* p; };
+    In in[] = {{d->time_entries_mont, n * 2 * fr, nullptr}, {d->addr_entries_mont, n * 2 * fr, nullptr},
+               {d->consts_mont, d->n_consts * fr, nullptr}, {d->evals_mont, n_sub * 2 * fr, nullptr},
+               {d->leaves_mont, n_sub * 4 * fr, nullptr},   {d->siblings_mont, n_sub * depth * fr, nullptr},
+               {d->root_mont, fr, nullptr}};
+    size_t staged[7];                                      // bytes of lane scratch per input: none for a device-resident one
+    for (int k = 0; k < 7; k++) staged[k] = is_device_ptr(in[k].src) ? 0 : in[k].bytes;
+    EtChal<Fr> ch;
+    for (size_t k = 0; k < 4; k++) {
+        ch.c[k] = Fr::zero();
+        if (k < 2) memcpy(&ch.c[k], (const char*)d->challenges_mont + k * fr, fr);
+    }
+    LaneGuard g(ctx);
+    Lane* L = g.lane;
+    if (!L) return HK_ERR_DEVICE;
+    u32* rows_d;
+    HK_TRY(L->carve([&](Carve& c) {
+        for (int k = 0; k < 7; k++) in[k].p = c.take(staged[k]);
+        rows_d = c.n<u32>(2 * batch);
+    }));
+    hipStream_t s = L->stream;
+    for (int k = 0; k < 7; k++) HK_TRY(to_device(L, in[k].src, in[k].bytes, &in[k].p));
+    HK_HIP(hipMemcpyAsync(rows_d, rows.data(), 4 * rows.size(), hipMemcpyHostToDevice, s));
+    const Fr *tp = (const Fr*)in[0].p, *ap = (const Fr*)in[1].p, *cp = (const Fr*)in[2].p;
+    const u32 nb = (u32)batch, lanes = (u32)((7 + 5 * K) * batch);
+    hipLaunchKernelGGL((k_s1_values<Fr>), dim3((lanes + 255) / 256), dim3(256), 0, s, tp, ap, (const u32*)rows_d, nb, (u32)K, ch,
+                       (const Fr*)in[3].p, (const Fr*)in[6].p, n_v, (size_t)d->inst_col0, (size_t)d->col0, (Fr*)z_out);
+    PoseidonDesc a{lh->t, lh->alpha, lh->full_rounds, lh->partial_rounds, lh->consts_offset};
+    PoseidonDesc b{nh->t, nh->alpha, nh->full_rounds, nh->partial_rounds, nh->consts_offset};
+    hipLaunchKernelGGL((k_s1_membership<Fr>), dim3((nb + S1_WG_ROWS - 1) / S1_WG_ROWS), dim3(256), 0, s, cp, a, b,
+                       (const Fr*)in[4].p, (const Fr*)in[5].p, (const u32*)rows_d, (u32)depth, nb, n_v, (size_t)d->pos_col0, (Fr*)z_out);
+    HK_HIP(hipGetLastError());
+    return L->settle();
+}
+
+}  // namespace hk

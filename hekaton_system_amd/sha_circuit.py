@@ -993,6 +993,13 @@ class ShaMerkleJob:
         self.tree = ExecTree.from_levels(self.curve, [lf[4 * i:4 * i + 4] for i in range(n)], levels)
         self.root = self.tree.root
 
+    def stage1_device(self, ctx):
+        """The job's challenge-dependent witness on the device: one hk_exec_tree call over the two traces, uploaded once,
+        whose outputs stay where hk_stage1_witness reads them.  Needs the challenges (`set_challenges`, or the constructor's);
+        the job itself is left as it is.  Returns a `Stage1Device`: `.fill(circ, members, z)` per class, `.root`, `.free()`."""
+        assert self.entry_chal is not None, "stage1_device needs the round's challenges"
+        return Stage1Device(self, ctx)
+
     def class_of(self, idx):
         """(kind, first, last) - the proving-key class a subcircuit needs (5 classes, tree_hash_circuit.rs:192-216)."""
         return self.kind[idx], idx == 0, idx == self.n - 1
@@ -1012,6 +1019,52 @@ class ShaMerkleJob:
         elif self.kind[idx] == "padding":
             w["leaf"] = bytes(64)
         return w
+
+
+class Stage1Device:
+    """What `ShaMerkleJob.stage1_device` returns: the job's traces and hk_exec_tree's outputs (evaluations, leaves, nodes,
+    siblings, root) as DeviceBuffers, from which `fill` writes the challenge-dependent columns of a class's assignments
+    (hk_stage1_witness) without a host value in between.  `root` is the one value read back (an int)."""
+
+    def __init__(self, job, ctx):
+        from .capi import DeviceBuffer
+        from .poseidon import device_params
+        fc = FrCodec(job.curve)
+        self.job, self.ctx = job, ctx
+        self.offsets = np.arange(job.n + 1, dtype=np.uint32) * job.np_
+        flat = lambda tr: fc.enc([x for ops in tr for e in ops for x in e])
+        consts, n_consts, ld, nd = device_params(job.curve, fc)
+        self.traces = [DeviceBuffer.from_host(ctx, flat(job.time)), DeviceBuffer.from_host(ctx, flat(job.addr))]
+        self.params = (DeviceBuffer.from_host(ctx, consts), n_consts, ld, nd)
+        self.challenges = fc.enc([job.entry_chal, job.tr_chal])
+        try:
+            self.outs = ctx.exec_tree(self.params, 2, self.offsets, self.traces[0], self.traces[1], self.challenges,
+                                      device_out=True)
+        except Exception:
+            self.outs = ()
+            self.free()
+            raise
+        self.root = fc.dec(self.outs[4].to_host())[0]
+
+    def fill(self, circ, members, z):
+        """The challenge-dependent columns of the assignments of `members` (subcircuit indices of ONE class, `circ`), row b
+        of the DeviceBuffer z = members[b]; the root class's data-tree root (`sha_root_col`) goes in by hk_assignment_scatter.
+        The bit columns are the word program's (hk_wprog_run), before or after."""
+        members = np.ascontiguousarray(members, dtype=np.uint32)
+        self.ctx.stage1_witness(self.params, self.job.np_, self.offsets, self.traces[0], self.traces[1], self.challenges,
+                                self.outs, members, circ.n_v, (1, circ.N_INST, circ.pos_col0), z)
+        if circ.kind == "root" and members.size:
+            from .capi import check
+            cols = np.array([circ.sha_root_col], np.uint32)
+            vals = np.ascontiguousarray(np.tile(circ.fc.enc([self.job.sha_root]), members.size))
+            check(self.ctx.lib.hk_assignment_scatter(self.ctx.handle, cols.ctypes.data, vals.ctypes.data, 1, members.size,
+                                                     circ.n_v, z.ptr), "hk_assignment_scatter")
+        return z
+
+    def free(self):
+        for x in list(self.traces) + [self.params[0]] + list(self.outs):
+            x.free()
+        self.traces, self.outs = [], ()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -513,6 +513,53 @@ typedef struct {                    /* every pointer [h|d]; evals / nodes may be
 } hk_exec_tree_out;
 hk_status hk_exec_tree(hk_ctx* ctx, const hk_exec_tree_desc* desc, const hk_exec_tree_out* out);
 
+/* ---- a subcircuit's challenge-dependent witness (distributed-prover/src/subcircuit_circuit.rs:206-252) -------------
+ * A stage-1 assignment has the bit columns of its gadgets (hk_wprog_run; no challenge in them) and the columns that wait for
+ * the round's challenges: what `generate_constraints` witnesses from its Stage1Request (coordinator.rs:569-604: the
+ * challenges, the previous leaf's evaluations and last entry, the membership path of its own leaf, the root).  hk_exec_tree
+ * computes every one of those values; hk_stage1_witness writes them into the assignments of any subset of the job's
+ * subcircuits, from hk_exec_tree's inputs and outputs where they lie (ROM entries).  Row b of z_out is the assignment of
+ * subcircuit i = sub_index[b]; indices may come in any order and may repeat.  With k = n_portals:
+ *   inst_col0 + 0 .. 2     entry_chal, tr_chal, root
+ *   col0 ..                (addr, val) of the k time-ordered entries, then of the k address-ordered ones        4 k
+ *                          time chain: evals[i - 1][0] (1 for i = 0), then per entry e = val + entry_chal addr
+ *                          and cur <- cur (tr_chal - e)                                                         1 + 2 k
+ *                          address chain, the same from evals[i - 1][1]                                         1 + 2 k
+ *                          the previous leaf's last address-ordered entry: entry offsets[i] - 1, (0, 0) when
+ *                          offsets[i] == 0                                                                      2
+ *                          per consecutive pair of [previous] + address entries, d = addr' - addr: inv = 1 / d
+ *                          (0 when d = 0), same = [d == 0]                                                      2 k
+ *   pos_col0 ..            the membership block of leaf leaves[i], path siblings[i], index i: the values and order of
+ *                          hk_poseidon_path
+ * - the columns hekaton_system_amd/sha_circuit.py `ShaMerkleSubcircuit._program` allocates.  Every other column of z_out keeps
+ * its bytes, column 0 included.  The call runs on the caller's lane; host-resident inputs are staged in lane scratch, device-
+ * resident ones are read in place.  batch == 0: HK_OK, nothing done.  HK_ERR_ARG, before any device work and with z_out
+ * untouched: a NULL pointer; n_sub not a power of two >= 2 or depth != log2(n_sub); n_portals == 0; offsets[0] != 0 or
+ * decreasing offsets; sub_index[b] >= n_sub; a selected subcircuit that does not own exactly n_portals entries; a descriptor
+ * pair other than the compiled (t 4, alpha 5) / (t 3, alpha 17), constants that end before its tables do; one of the three
+ * column ranges not inside [1, n_v) or two of them overlapping (the membership block's length as hk_poseidon_path computes
+ * it); batch >= 2^20 or (7 + 5 k) batch >= 2^31. */
+typedef struct {
+    uint32_t n_sub;                 /* subcircuits of the job = rows of evals / leaves / siblings; power of two >= 2 */
+    uint32_t n_portals;             /* k >= 1: entries a subcircuit of this class owns in EACH order */
+    uint32_t depth;                 /* log2(n_sub) */
+    const uint32_t* offsets;        /* [h] n_sub + 1, as hk_exec_tree */
+    const void* time_entries_mont;  /* [h|d] offsets[n_sub] x 2 Fr (addr, val): hk_exec_tree's inputs, entry_fields = 2 */
+    const void* addr_entries_mont;  /* [h|d] same shape, address order */
+    const void* challenges_mont;    /* [h] 2 Fr: entry_chal, tr_chal */
+    const void* evals_mont;         /* [h|d] n_sub x 2 Fr      } */
+    const void* leaves_mont;        /* [h|d] n_sub x 4 Fr      } exactly what hk_exec_tree wrote */
+    const void* siblings_mont;      /* [h|d] n_sub x depth Fr  } */
+    const void* root_mont;          /* [h|d] 1 Fr              } */
+    const void* consts_mont; size_t n_consts;
+    const hk_poseidon_desc* leaf_hash; const hk_poseidon_desc* node_hash;   /* as hk_poseidon_path / hk_exec_tree */
+    uint32_t inst_col0;             /* columns inst_col0 .. +2 <- entry_chal, tr_chal, root */
+    uint32_t col0;                  /* first column of the portal block (10 k + 4 columns, order above) */
+    uint32_t pos_col0;              /* first column of the membership block (hk_poseidon_path's col0) */
+} hk_stage1_desc;
+hk_status hk_stage1_witness(hk_ctx* ctx, const hk_stage1_desc* desc, const uint32_t* sub_index /* [h] batch */,
+                            size_t batch, size_t n_v, void* z_out /* [d] batch x n_v Fr */);
+
 #ifdef __cplusplus
 }
 #endif
