@@ -111,7 +111,8 @@ EXPORTS = ["hk_status_str", "hk_version", "hk_ctx_create", "hk_ctx_destroy", "hk
            "hk_msm_bases", "hk_multi_pairing", "hk_pairing_products", "hk_ctx_gt_bytes",
            "hk_points_lincomb_g1", "hk_points_lincomb_g2", "hk_points_fold_g2", "hk_points_fold_g1", "hk_points_fold_many_g1", "hk_points_fold_many_g2", "hk_pairing_pairs", "hk_keccak_f1600", "hk_assignment_from_bits", "hk_wprog_upload", "hk_wprog_free", "hk_wprog_run", "hk_gt_pow", "hk_fq12_pow", "hk_gt_pow_prod", "hk_poseidon_path", "hk_assignment_scatter", "hk_commit_batch",
            "hk_prove_batch", "hk_vk_prepare", "hk_vk_free", "hk_vk_alpha_beta", "hk_verify_batch", "hk_points_check_g1",
-           "hk_points_check_g2", "hk_qap_eval", "hk_keygen", "hk_exec_tree", "hk_stage1_witness"]
+           "hk_points_check_g2", "hk_qap_eval", "hk_keygen", "hk_exec_tree", "hk_stage1_witness",
+           "hk_trace_sort", "hk_stage0_witness"]
 
 HK_VERIFY_CHECK_POINTS = 1
 VERDICT_REJECT, VERDICT_ACCEPT, VERDICT_BAD_POINT = 0, 1, 2
@@ -202,6 +203,8 @@ def load():
     lib.hk_keygen.argtypes = [vp, C.POINTER(hk_keygen_desc), C.POINTER(hk_keygen_out), C.POINTER(sz)]
     lib.hk_exec_tree.argtypes = [vp, C.POINTER(hk_exec_tree_desc), C.POINTER(hk_exec_tree_out)]
     lib.hk_stage1_witness.argtypes = [vp, C.POINTER(hk_stage1_desc), vp, sz, sz, vp]
+    lib.hk_trace_sort.argtypes = [vp, C.c_uint32, vp, sz, vp, vp]
+    lib.hk_stage0_witness.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, sz, vp]
     _lib = lib
     return lib
 
@@ -713,6 +716,48 @@ class Context:
         check(self.lib.hk_stage1_witness(self.handle, C.byref(d), sub_index.ctypes.data if sub_index.size else None,
                                          sub_index.size, int(n_v), zp), "hk_stage1_witness")
         return z_out
+
+    def trace_sort(self, entry_fields, time_entries, n_entries=None, device_out=False, want_perm=False):
+        """hk_trace_sort: the address-ordered trace (coordinator.rs:92-123) from the flattened time-ordered one - the stable
+        sort by addr (entry_fields 2, ROM) or (addr, timestamp) (entry_fields 4, RAM).  time_entries: Montgomery bytes or a
+        DeviceBuffer of n_entries x entry_fields Fr (n_entries defaults to all of it).  Returns the sorted entries in the
+        same layout - Montgomery bytes, or a DeviceBuffer when device_out is set - and with want_perm the pair (entries,
+        perm): sorted entry j = time entry perm[j], uint32 (a numpy array, or a DeviceBuffer when device_out is set)."""
+        k, fr = int(entry_fields), self.fr_bytes
+        src = time_entries if isinstance(time_entries, DeviceBuffer) else np.ascontiguousarray(time_entries, dtype=np.uint8)
+        if n_entries is None:
+            n_entries = (src.nbytes if isinstance(src, DeviceBuffer) else src.size) // (max(k, 1) * fr)
+        n = int(n_entries)
+        if device_out:
+            out = DeviceBuffer(self, max(n * k * fr, 1))
+            perm = DeviceBuffer(self, max(4 * n, 1)) if want_perm else None
+        else:
+            out = np.zeros(n * k * fr, dtype=np.uint8)
+            perm = np.zeros(n, dtype=np.uint32) if want_perm else None
+        try:
+            check(self.lib.hk_trace_sort(self.handle, k, ptr(src) if n else None, n, ptr(out) if n else None,
+                                         ptr(perm) if n else None), "hk_trace_sort")
+        except HekatonError:
+            if device_out:
+                out.free()
+                if perm is not None:
+                    perm.free()
+            raise
+        return (out, perm) if want_perm else out
+
+    def stage0_witness(self, offsets, n_portals, time_entries, addr_entries, sub_index, w_out):
+        """hk_stage0_witness: row b of w_out (a DeviceBuffer or raw device address of len(sub_index) x 4 n_portals Fr) = the
+        stage-0 witness of subcircuit sub_index[b]: (addr, val) of its n_portals time-ordered, then of its n_portals address-
+        ordered entries.  offsets: n_sub + 1 uint32 as exec_tree takes them; time_entries / addr_entries: Montgomery bytes or
+        DeviceBuffers of offsets[-1] x 2 Fr (ROM).  w_out is what ProvingKey.commit_batch / hk_commit_batch read."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+        sub_index = np.ascontiguousarray(sub_index, dtype=np.uint32)
+        keep = [x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8) for x in (time_entries, addr_entries)]
+        wp = w_out.ptr if isinstance(w_out, DeviceBuffer) else int(w_out)
+        check(self.lib.hk_stage0_witness(self.handle, offsets.ctypes.data, offsets.size - 1, int(n_portals), ptr(keep[0]),
+                                         ptr(keep[1]), sub_index.ctypes.data if sub_index.size else None, sub_index.size, wp),
+              "hk_stage0_witness")
+        return w_out
 
     def points_check(self, group, pts, n=None):
         """hk_points_check_g1 / _g2: ark's AffineRepr::check of each point (on its curve, in the prime-order subgroup;

@@ -147,6 +147,8 @@ struct Ops {
     static hk_status keygen(hk_ctx*, const hk_keygen_desc*, const hk_keygen_out*, size_t*);
     static hk_status exec_tree(hk_ctx*, const hk_exec_tree_desc*, const hk_exec_tree_out*);     // exec_tree.cuh
     static hk_status stage1_witness(hk_ctx*, const hk_stage1_desc*, const uint32_t*, size_t, size_t, void*);     // stage1.cuh
+    static hk_status trace_sort(hk_ctx*, uint32_t, const void*, size_t, void*, uint32_t*);     // trace_sort.cuh
+    static hk_status stage0_witness(hk_ctx*, const uint32_t*, uint32_t, uint32_t, const void*, const void*, const uint32_t*, size_t, void*);
 
     static size_t max_private_bytes() {
         size_t m = MsmRun<Fq>::max_private_bytes();
@@ -172,7 +174,8 @@ struct Ops {
                                    &max_private_bytes, &poseidon_path, &points_fold_many, &pairing_pairs, &assignment_scatter, &commit_batch,
                                    &prove_batch, &VerifyRun<typename Fq::Params>::vk_prepare, &VerifyRun<typename Fq::Params>::vk_free,
                                    &VerifyRun<typename Fq::Params>::vk_alpha_beta, &VerifyRun<typename Fq::Params>::verify_batch,
-                                   &VerifyRun<typename Fq::Params>::points_check, &qap_eval, &keygen, &exec_tree, &stage1_witness};
+                                   &VerifyRun<typename Fq::Params>::points_check, &qap_eval, &keygen, &exec_tree, &stage1_witness,
+                                   &trace_sort, &stage0_witness};
         return &t;
     }
 };

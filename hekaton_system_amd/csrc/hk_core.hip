@@ -669,6 +669,16 @@ hk_status hk_stage1_witness(hk_ctx* ctx, const hk_stage1_desc* desc, const uint3
     if (!ctx || !desc) return HK_ERR_ARG;
     return ctx->ops->stage1_witness(ctx, desc, sub_index, batch, n_v, z_out);
 }
+hk_status hk_trace_sort(hk_ctx* ctx, uint32_t entry_fields, const void* time_entries_mont, size_t n_entries,
+                        void* addr_entries_mont_out, uint32_t* perm_out) {
+    if (!ctx) return HK_ERR_ARG;
+    return ctx->ops->trace_sort(ctx, entry_fields, time_entries_mont, n_entries, addr_entries_mont_out, perm_out);
+}
+hk_status hk_stage0_witness(hk_ctx* ctx, const uint32_t* offsets, uint32_t n_sub, uint32_t n_portals, const void* time_entries_mont,
+                            const void* addr_entries_mont, const uint32_t* sub_index, size_t batch, void* w_out) {
+    if (!ctx) return HK_ERR_ARG;
+    return ctx->ops->stage0_witness(ctx, offsets, n_sub, n_portals, time_entries_mont, addr_entries_mont, sub_index, batch, w_out);
+}
 
 }  // extern "C"
 

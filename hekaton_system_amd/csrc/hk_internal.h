@@ -220,6 +220,10 @@ struct CurveOps {
     hk_status (*keygen)(hk_ctx*, const hk_keygen_desc*, const hk_keygen_out*, size_t* m_out);
     hk_status (*exec_tree)(hk_ctx*, const hk_exec_tree_desc*, const hk_exec_tree_out*);
     hk_status (*stage1_witness)(hk_ctx*, const hk_stage1_desc*, const uint32_t* sub_index, size_t batch, size_t n_v, void* z_out);
+    hk_status (*trace_sort)(hk_ctx*, uint32_t entry_fields, const void* time_entries, size_t n_entries, void* addr_entries_out,
+                            uint32_t* perm_out);
+    hk_status (*stage0_witness)(hk_ctx*, const uint32_t* offsets, uint32_t n_sub, uint32_t n_portals, const void* time_entries,
+                                const void* addr_entries, const uint32_t* sub_index, size_t batch, void* w_out);
 };
 const CurveOps* curve_ops_bn254();
 const CurveOps* curve_ops_bls381();

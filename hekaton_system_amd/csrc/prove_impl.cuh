@@ -1869,3 +1869,4 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
 #include "keygen.cuh"
 #include "exec_tree.cuh"
 #include "stage1.cuh"
+#include "trace_sort.cuh"

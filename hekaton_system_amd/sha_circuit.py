@@ -993,12 +993,19 @@ class ShaMerkleJob:
         self.tree = ExecTree.from_levels(self.curve, [lf[4 * i:4 * i + 4] for i in range(n)], levels)
         self.root = self.tree.root
 
-    def stage1_device(self, ctx):
+    def stage1_device(self, ctx, traces=None):
         """The job's challenge-dependent witness on the device: one hk_exec_tree call over the two traces, uploaded once,
         whose outputs stay where hk_stage1_witness reads them.  Needs the challenges (`set_challenges`, or the constructor's);
-        the job itself is left as it is.  Returns a `Stage1Device`: `.fill(circ, members, z)` per class, `.root`, `.free()`."""
+        the job itself is left as it is.  traces: `stage0_device(ctx).traces`, to read the two traces already on the device
+        instead of uploading them again.  Returns a `Stage1Device`: `.fill(circ, members, z)` per class, `.root`, `.free()`."""
         assert self.entry_chal is not None, "stage1_device needs the round's challenges"
-        return Stage1Device(self, ctx)
+        return Stage1Device(self, ctx, traces=traces)
+
+    def stage0_device(self, ctx):
+        """The job's stage-0 side on the device: the time-ordered trace uploaded once, the address-ordered one made from it
+        by hk_trace_sort.  Needs no challenges; the job itself (`time`, `addr`) is left as it is.  Returns a `Stage0Device`:
+        `.rows(members)` for `ProvingKey.commit_batch`, `.traces` for `Stage1Device(job, ctx, traces=...)`, `.free()`."""
+        return Stage0Device(self, ctx)
 
     def class_of(self, idx):
         """(kind, first, last) - the proving-key class a subcircuit needs (5 classes, tree_hash_circuit.rs:192-216)."""
@@ -1021,12 +1028,52 @@ class ShaMerkleJob:
         return w
 
 
+class Stage0Device:
+    """What `ShaMerkleJob.stage0_device` returns: `offsets`, and `traces = [time, addr]` as DeviceBuffers - the time-ordered
+    trace uploaded once, the address-ordered one sorted from it on the device (hk_trace_sort).  `rows(members)` cuts the
+    stage-0 witnesses of any subcircuits out of them (hk_stage0_witness) for `ProvingKey.commit_batch`; the traces are what
+    hk_exec_tree and hk_stage1_witness read next (`Stage1Device(job, ctx, traces=dev0.traces)`)."""
+
+    def __init__(self, job, ctx):
+        from .capi import DeviceBuffer
+        fc = FrCodec(job.curve)
+        self.job, self.ctx = job, ctx
+        self.offsets = np.arange(job.n + 1, dtype=np.uint32) * job.np_
+        time = DeviceBuffer.from_host(ctx, fc.enc([x for ops in job.time for e in ops for x in e]))
+        self.traces = [time]
+        try:
+            self.traces.append(ctx.trace_sort(2, time, job.n * job.np_, device_out=True))
+        except Exception:
+            self.free()
+            raise
+
+    def rows(self, members):
+        """DeviceBuffer of len(members) x 4 n_portals Fr: row b = `job.stage0_ints(members[b])` in Montgomery form.  The
+        caller frees it."""
+        from .capi import DeviceBuffer
+        members = np.ascontiguousarray(members, dtype=np.uint32)
+        w = DeviceBuffer(self.ctx, max(members.size * 4 * self.job.np_ * self.ctx.fr_bytes, 1))
+        try:
+            self.ctx.stage0_witness(self.offsets, self.job.np_, self.traces[0], self.traces[1], members, w)
+        except Exception:
+            w.free()
+            raise
+        return w
+
+    def free(self):
+        for x in self.traces:
+            x.free()
+        self.traces = []
+
+
 class Stage1Device:
     """What `ShaMerkleJob.stage1_device` returns: the job's traces and hk_exec_tree's outputs (evaluations, leaves, nodes,
     siblings, root) as DeviceBuffers, from which `fill` writes the challenge-dependent columns of a class's assignments
-    (hk_stage1_witness) without a host value in between.  `root` is the one value read back (an int)."""
+    (hk_stage1_witness) without a host value in between.  `root` is the one value read back (an int).  traces: the
+    [time, addr] DeviceBuffers of a `Stage0Device` to read instead of encoding and uploading both again; they stay their
+    owner's (`free` leaves them)."""
 
-    def __init__(self, job, ctx):
+    def __init__(self, job, ctx, traces=None):
         from .capi import DeviceBuffer
         from .poseidon import device_params
         fc = FrCodec(job.curve)
@@ -1034,7 +1081,11 @@ class Stage1Device:
         self.offsets = np.arange(job.n + 1, dtype=np.uint32) * job.np_
         flat = lambda tr: fc.enc([x for ops in tr for e in ops for x in e])
         consts, n_consts, ld, nd = device_params(job.curve, fc)
-        self.traces = [DeviceBuffer.from_host(ctx, flat(job.time)), DeviceBuffer.from_host(ctx, flat(job.addr))]
+        self._adopted = traces is not None
+        if traces is not None:
+            self.traces = list(traces)
+        else:
+            self.traces = [DeviceBuffer.from_host(ctx, flat(job.time)), DeviceBuffer.from_host(ctx, flat(job.addr))]
         self.params = (DeviceBuffer.from_host(ctx, consts), n_consts, ld, nd)
         self.challenges = fc.enc([job.entry_chal, job.tr_chal])
         try:
@@ -1062,7 +1113,7 @@ class Stage1Device:
         return z
 
     def free(self):
-        for x in list(self.traces) + [self.params[0]] + list(self.outs):
+        for x in ([] if self._adopted else list(self.traces)) + [self.params[0]] + list(self.outs):
             x.free()
         self.traces, self.outs = [], ()
 

@@ -7,6 +7,7 @@ rom_transcript.rs, ram_transcript.rs; coordinator.rs:92-160):
                                                 little-endian mod r (rom_transcript.rs:42-75, ram_transcript.rs:50-98)
     update_time_ordered / update_addr_ordered   eval *= tr_chal - repr(entry)       (rom :78-107, ram :101-135)
     sort_subtraces_by_addr                      flatten, stable sort by addr (ROM) / (addr, timestamp) (RAM), re-chunk
+    sort_subtraces_by_addr_device               the same lists from one hk_trace_sort call
     running_evaluations                         the evals after every subcircuit = the leaves of `generate_exec_tree`
                                                 (coordinator.rs:125-160) without its Merkle tree (ark-crypto-primitives
                                                 `TreeConfig`, third-party, out of scope)
@@ -170,6 +171,29 @@ def sort_subtraces_by_addr(time_ordered_subtraces):
     out, pos = [], 0
     for st in time_ordered_subtraces:
         out.append(flat[pos:pos + len(st)])
+        pos += len(st)
+    return out
+
+
+def sort_subtraces_by_addr_device(ctx, time_ordered_subtraces):
+    """`sort_subtraces_by_addr` on the device: the flattened trace goes through one hk_trace_sort call (ctx.trace_sort), the
+    entries are decoded from its result and re-chunked by the input lengths.  Returns what `sort_subtraces_by_addr` does."""
+    from .cp_groth16 import FrCodec
+    flat = [e for st in time_ordered_subtraces for e in st]
+    if not flat:
+        return [[] for _ in time_ordered_subtraces]
+    ram = isinstance(flat[0], RamTranscriptEntry)
+    k = 4 if ram else 2
+    fc = FrCodec(ctx.curve)
+    _, time_b = flatten_subtraces(fc, time_ordered_subtraces)
+    vals = fc.dec(ctx.trace_sort(k, time_b, len(flat)))
+    if ram:
+        srt = [RamTranscriptEntry(vals[i], vals[i + 1], vals[i + 2], bool(vals[i + 3])) for i in range(0, len(vals), 4)]
+    else:
+        srt = [RomTranscriptEntry(vals[i], vals[i + 1]) for i in range(0, len(vals), 2)]
+    out, pos = [], 0
+    for st in time_ordered_subtraces:
+        out.append(srt[pos:pos + len(st)])
         pos += len(st)
     return out
 

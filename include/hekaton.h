@@ -490,7 +490,8 @@ hk_status hk_keygen(hk_ctx* ctx, const hk_keygen_desc* desc, const hk_keygen_out
  *                            one over (coordinator.rs:137-160)
  *   leaf digest              the rate-3 sponge over the 2 + entry_fields leaf fields (two permutations), inner node = the
  *                            two-to-one hash of its children (poseidon_util.rs:26-107)
- * The address sort (coordinator.rs:92-123) does not depend on the challenges and stays with the caller.  siblings_mont and
+ * The address sort (coordinator.rs:92-123) does not depend on the challenges: hk_trace_sort (below) makes the address-ordered
+ * trace on the device from the time-ordered one, before or without this call.  siblings_mont and
  * leaves_mont are what hk_poseidon_path takes as they are (ROM).  HK_ERR_ARG, before any device work and with the outputs
  * untouched: n_sub not a power of two or 1, entry_fields not 2 / 4, offsets[0] != 0 or decreasing offsets, a descriptor
  * other than the compiled (t 4, alpha 5) leaf / (t 3, alpha 17) node pair, constants that end before its tables do. */
@@ -559,6 +560,39 @@ typedef struct {
 } hk_stage1_desc;
 hk_status hk_stage1_witness(hk_ctx* ctx, const hk_stage1_desc* desc, const uint32_t* sub_index /* [h] batch */,
                             size_t batch, size_t n_v, void* z_out /* [d] batch x n_v Fr */);
+
+/* ---- the address-ordered trace (distributed-prover/src/coordinator.rs:92-123 `sort_subtraces_by_addr`) ---------------
+ * The coordinator flattens the time-ordered subtraces, sorts them with Rust's stable sort_by_key - by addr as a u64 for ROM
+ * (coordinator.rs:104), by (addr u64, timestamp u32) compared lexicographically for RAM (coordinator.rs:107) - and cuts the
+ * result into chunks of the same lengths.  Both orders share one `offsets`, so re-chunking is the identity on the flat
+ * array and hk_trace_sort takes no offsets: addr_entries_mont_out is the stable sort of the n_entries flattened entries by
+ * that key, in hk_exec_tree's layout (entry_fields Montgomery Fr per entry, to_field_elements() order: field 0 the address,
+ * for RAM field 2 the timestamp).  Entries of equal key keep their time order; val and is_read are payload and never
+ * compared.  perm_out (may be NULL): address-ordered entry j = time-ordered entry perm_out[j].  The result is the same from
+ * run to run, byte for byte.  The call runs on the caller's lane; a host-resident input is staged in lane scratch, a device-
+ * resident one is read in place; the outputs are copied out of scratch last, so a refused or failed call leaves them
+ * untouched.  n_entries == 0: HK_OK, nothing done.  HK_ERR_ARG before any device work: entry_fields not 2 / 4,
+ * n_entries >= 2^31, a NULL input or addr_entries_mont_out, an output range that overlaps the input range.  HK_ERR_ARG found
+ * on the device, outputs untouched: an address >= 2^64 or a timestamp >= 2^32 (neither is a value of the reference's
+ * types). */
+hk_status hk_trace_sort(hk_ctx* ctx, uint32_t entry_fields,             /* 2 = ROM (addr, val); 4 = RAM (addr, val, timestamp, is_read) */
+                        const void* time_entries_mont, size_t n_entries, /* [h|d] n_entries x entry_fields Fr */
+                        void* addr_entries_mont_out,                     /* [h|d] same shape */
+                        uint32_t* perm_out);                             /* [h|d] n_entries, or NULL */
+
+/* ---- a subcircuit's stage-0 witness (distributed-prover/src/worker.rs:91-146 `process_stage0_request`) ----------------
+ * Row b of w_out is the stage-0 witness of subcircuit i = sub_index[b] (any order, repeats allowed): (addr, val) of its
+ * n_portals time-ordered entries, then of its n_portals address-ordered entries - entries [offsets[i], offsets[i + 1]) of
+ * each trace, two contiguous copies; the variable order of hekaton_system_amd/sha_circuit.py `ShaMerkleJob.stage0_ints` /
+ * `ShaMerkleSubcircuit._program`.  w_out is what hk_commit_batch takes as w_mont [d].  ROM entries only, as
+ * hk_stage1_witness.  Host-resident traces are staged in lane scratch, device-resident ones are read in place.
+ * batch == 0: HK_OK, nothing done.  HK_ERR_ARG, before any device work and with w_out untouched: a NULL pointer;
+ * n_portals == 0; offsets[0] != 0 or decreasing offsets; sub_index[b] >= n_sub; a selected subcircuit that does not own
+ * exactly n_portals entries; w_out not in device memory; batch >= 2^20 or batch x n_portals >= 2^28. */
+hk_status hk_stage0_witness(hk_ctx* ctx, const uint32_t* offsets /* [h] n_sub + 1 */, uint32_t n_sub, uint32_t n_portals,
+                            const void* time_entries_mont, const void* addr_entries_mont,   /* [h|d] offsets[n_sub] x 2 Fr */
+                            const uint32_t* sub_index /* [h] batch */, size_t batch,
+                            void* w_out /* [d] batch x 4 n_portals Fr */);
 
 #ifdef __cplusplus
 }
