@@ -34,10 +34,13 @@ inline u32 msm_pick_c_tables(size_t n, u32 fr_bits) {
 }
 
 template <class C>
-struct Ops {
+struct Ops final : CurveOps {
     typedef typename C::Fr Fr;
     typedef typename C::Fq Fq;
     typedef typename C::Fq2 Fq2;
+    typedef VerifyRun<typename Fq::Params> Verify;
+
+    Ops() : CurveOps(sizeof(Fr), sizeof(Fq), sizeof(Affine<Fq>), sizeof(Affine<Fq2>), sizeof(Fp12<typename Fq::Params>)) {}
 
     // One MSM into the affine point `out` on the lane's stream: n element-wise products over the endomorphism and one sum
     // (MsmRun::small_msm) when `small`, else the digit sort and the bucket pass over plan *p.  carve() lists its scratch
@@ -104,80 +107,87 @@ struct Ops {
         return L->settle();
     }
 
-    static hk_status msm(hk_ctx* ctx, int group, const void* bases, size_t n_bases, const void* scalars,
-                         size_t n_scalars, int mont, int checked, void* out) {
+    hk_status msm(hk_ctx* ctx, int group, const void* bases, size_t n_bases, const void* scalars,
+                  size_t n_scalars, int mont, int checked, void* out) override {
         if (group == 1) return msm_plain<Fq>(ctx, bases, n_bases, scalars, n_scalars, mont, checked, out);
         return msm_plain<Fq2>(ctx, bases, n_bases, scalars, n_scalars, mont, checked, out);
     }
 
-    // ---- filled in by later includes (ntt / qap / prove) -------------------------------------------
-    static hk_status ntt(hk_ctx*, void*, unsigned, int, int);
-    static hk_status witness_map(hk_ctx*, const hk_csr*, const hk_csr*, const hk_csr*, size_t, size_t,
-                                 const void*, size_t, void*, size_t, size_t*);
-    static hk_status pk_upload(hk_ctx*, const hk_pk_desc*, hk_pk**);
-    static void pk_free(hk_pk*);
-    static hk_status commit(hk_ctx*, const hk_pk*, size_t, const void*, size_t, const void*, void*);
-    static hk_status commit_batch(hk_ctx*, const hk_pk*, size_t, const void*, size_t, const void*, size_t, void*);
-    static hk_status prove_batch(hk_ctx*, const hk_pk*, size_t, size_t, const ProveRow*, size_t);
-    static void ctx_release(hk_ctx*);
-    static hk_status fixed_base(hk_ctx*, int, const void*, const void*, size_t, int, void*);
-    static hk_status scalar_pairing(hk_ctx*, int, const void*, const void*, size_t, void*);
-    static hk_status field_convert(hk_ctx*, int, const void*, void*, size_t, int);
-    static hk_status bases_upload(hk_ctx*, int, const void*, size_t, hk_bases**);
-    static void bases_free(hk_bases*);
-    static hk_status msm_bases(hk_ctx*, const hk_bases*, const void*, size_t, int, int, void*);
-    static hk_status pairing_products(hk_ctx*, const void* const*, size_t, const void* const*, size_t, size_t, void*);
-    static hk_status points_lincomb(hk_ctx*, int, const void* const*, const void*, size_t, size_t, void*);
-    template <class F>
-    static hk_status points_fold(hk_ctx*, size_t, const void* const*, const void* const*, const void*, unsigned, size_t, void* const*);
-    static hk_status assignment_scatter(hk_ctx*, const uint32_t*, const void*, size_t, size_t, size_t, void*);
-    static hk_status pairing_pairs(hk_ctx*, const void* const*, size_t, const void* const*, size_t, const uint32_t*, const uint32_t*, size_t,
-                                   size_t, void*);
-    static hk_status points_fold_many(hk_ctx*, int, size_t, const void* const*, const void* const*, const void*, unsigned, size_t, void* const*);
-    static hk_status points_fold_g2(hk_ctx*, const void*, const void*, const void*, unsigned, size_t, void*);
-    static hk_status points_fold_g1(hk_ctx*, const void*, const void*, const void*, unsigned, size_t, void*);
-    static hk_status assignment_from_bits(hk_ctx*, const void*, size_t, const uint32_t*, const void*, size_t, void*);
-    static hk_status wprog_upload(hk_ctx*, const uint32_t*, size_t, const uint32_t*, size_t, const uint32_t*, size_t, size_t,
-                                  size_t, hk_wprog**);
-    static void wprog_free(hk_wprog*);
-    static hk_status gt_pow(hk_ctx*, const void*, const void*, size_t, void*, int, size_t);
-    static hk_status wprog_run(hk_ctx*, const hk_wprog*, const uint32_t*, size_t, const uint32_t*, const void*, size_t, void*);
-    static hk_status qap_eval(hk_ctx*, const hk_csr*, const hk_csr*, const hk_csr*, size_t, size_t, size_t, const void*, void*,
-                              void*, void*, void*, size_t*);     // keygen.cuh
-    static hk_status keygen(hk_ctx*, const hk_keygen_desc*, const hk_keygen_out*, size_t*);
-    static hk_status exec_tree(hk_ctx*, const hk_exec_tree_desc*, const hk_exec_tree_out*);     // exec_tree.cuh
-    static hk_status stage1_witness(hk_ctx*, const hk_stage1_desc*, const uint32_t*, size_t, size_t, void*);     // stage1.cuh
-    static hk_status trace_sort(hk_ctx*, uint32_t, const void*, size_t, void*, uint32_t*);     // trace_sort.cuh
-    static hk_status stage0_witness(hk_ctx*, const uint32_t*, uint32_t, uint32_t, const void*, const void*, const uint32_t*, size_t, void*);
-
-    static size_t max_private_bytes() {
+    size_t max_private_bytes() override {
         size_t m = MsmRun<Fq>::max_private_bytes();
         size_t b = MsmRun<Fq2>::max_private_bytes();
         if (b > m) m = b;
         b = PairRun<typename Fq::Params>::max_private_bytes();
         if (b > m) m = b;
-        b = VerifyRun<typename Fq::Params>::max_private_bytes();
+        b = Verify::max_private_bytes();
         if (b > m) m = b;
         b = finish_private_bytes();
         return b > m ? b : m;
     }
-    static size_t finish_private_bytes();      // prove_impl.cuh (k_finish)
-    static hk_status poseidon_path(hk_ctx*, const void*, size_t, const hk_poseidon_desc*, const hk_poseidon_desc*, const void*,
-                                   const void*, const uint32_t*, size_t, size_t, size_t, size_t, void*);
 
-    static const CurveOps* table() {
-        static const CurveOps t = {sizeof(Fr), sizeof(Fq), sizeof(Affine<Fq>), sizeof(Affine<Fq2>),
-                                   &msm, &ntt, &witness_map, &pk_upload, &pk_free, &commit,
-                                   &ctx_release, &fixed_base, &scalar_pairing, &field_convert, &bases_upload,
-                                   &bases_free, &msm_bases, &pairing_products,
-                                   sizeof(Fp12<typename Fq::Params>), &points_lincomb, &points_fold_g2, &points_fold_g1, &assignment_from_bits, &wprog_upload, &wprog_free, &wprog_run, &gt_pow,
-                                   &max_private_bytes, &poseidon_path, &points_fold_many, &pairing_pairs, &assignment_scatter, &commit_batch,
-                                   &prove_batch, &VerifyRun<typename Fq::Params>::vk_prepare, &VerifyRun<typename Fq::Params>::vk_free,
-                                   &VerifyRun<typename Fq::Params>::vk_alpha_beta, &VerifyRun<typename Fq::Params>::verify_batch,
-                                   &VerifyRun<typename Fq::Params>::points_check, &qap_eval, &keygen, &exec_tree, &stage1_witness,
-                                   &trace_sort, &stage0_witness};
-        return &t;
+    // ---- defined by the headers named here, in CurveOps's order ----------------------------------------
+    // ntt_host.cuh
+    hk_status ntt(hk_ctx*, void*, unsigned, int, int) override;
+    hk_status witness_map(hk_ctx*, const hk_csr*, const hk_csr*, const hk_csr*, size_t, size_t,
+                          const void*, size_t, void*, size_t, size_t*) override;
+    void ctx_release(hk_ctx*) override;
+    // pk.cuh
+    hk_status pk_upload(hk_ctx*, const hk_pk_desc*, hk_pk**) override;
+    void pk_free(hk_pk*) override;
+    // group_ops.cuh
+    hk_status bases_upload(hk_ctx*, int, const void*, size_t, hk_bases**) override;
+    void bases_free(hk_bases*) override;
+    hk_status msm_bases(hk_ctx*, const hk_bases*, const void*, size_t, int, int, void*) override;
+    hk_status fixed_base(hk_ctx*, int, const void*, const void*, size_t, int, void*) override;
+    hk_status scalar_pairing(hk_ctx*, int, const void*, const void*, size_t, void*) override;
+    hk_status points_lincomb(hk_ctx*, int, const void* const*, const void*, size_t, size_t, void*) override;
+    template <class F>
+    static hk_status points_fold(hk_ctx*, size_t, const void* const*, const void* const*, const void*, unsigned, size_t, void* const*);
+    hk_status points_fold_many(hk_ctx*, int, size_t, const void* const*, const void* const*, const void*, unsigned, size_t,
+                               void* const*) override;
+    hk_status field_convert(hk_ctx*, int, const void*, void*, size_t, int) override;
+    // witness_host.cuh
+    hk_status assignment_from_bits(hk_ctx*, const void*, size_t, const uint32_t*, const void*, size_t, void*) override;
+    hk_status wprog_upload(hk_ctx*, const uint32_t*, size_t, const uint32_t*, size_t, const uint32_t*, size_t, size_t,
+                           size_t, hk_wprog**) override;
+    void wprog_free(hk_wprog*) override;
+    hk_status wprog_run(hk_ctx*, const hk_wprog*, const uint32_t*, size_t, const uint32_t*, const void*, size_t, void*) override;
+    hk_status assignment_scatter(hk_ctx*, const uint32_t*, const void*, size_t, size_t, size_t, void*) override;
+    hk_status poseidon_path(hk_ctx*, const void*, size_t, const hk_poseidon_desc*, const hk_poseidon_desc*, const void*,
+                            const void*, const uint32_t*, size_t, size_t, size_t, size_t, void*) override;
+    // pairing_ops.cuh
+    hk_status pairing_products(hk_ctx*, const void* const*, size_t, const void* const*, size_t, size_t, void*) override;
+    hk_status pairing_pairs(hk_ctx*, const void* const*, size_t, const void* const*, size_t, const uint32_t*, const uint32_t*, size_t,
+                            size_t, void*) override;
+    hk_status gt_pow(hk_ctx*, const void*, const void*, size_t, void*, int, size_t) override;
+    // prove_impl.cuh
+    hk_status commit(hk_ctx*, const hk_pk*, size_t, const void*, size_t, const void*, void*) override;
+    hk_status commit_batch(hk_ctx*, const hk_pk*, size_t, const void*, size_t, const void*, size_t, void*) override;
+    hk_status prove_batch(hk_ctx*, const hk_pk*, size_t, size_t, const ProveRow*, size_t) override;
+    static size_t finish_private_bytes();      // k_finish_ab / k_finish_c
+    // verify.cuh
+    hk_status vk_prepare(hk_ctx* ctx, const hk_vk_desc* d, hk_vk** out) override { return Verify::vk_prepare(ctx, d, out); }
+    void vk_free(hk_vk* vk) override { Verify::vk_free(vk); }
+    hk_status vk_alpha_beta(const hk_vk* vk, void* out) override { return Verify::vk_alpha_beta(vk, out); }
+    hk_status verify_batch(hk_ctx* ctx, const hk_vk* vk, const void* a, const void* b, const void* c, const void* ds,
+                           const void* inputs, size_t n, unsigned flags, const void* rand, unsigned char* verdicts) override {
+        return Verify::verify_batch(ctx, vk, a, b, c, ds, inputs, n, flags, rand, verdicts);
     }
+    hk_status points_check(hk_ctx* ctx, int group, const void* pts, size_t n, unsigned char* ok) override {
+        return Verify::points_check(ctx, group, pts, n, ok);
+    }
+    // keygen.cuh
+    hk_status qap_eval(hk_ctx*, const hk_csr*, const hk_csr*, const hk_csr*, size_t, size_t, size_t, const void*, void*,
+                       void*, void*, void*, size_t*) override;
+    hk_status keygen(hk_ctx*, const hk_keygen_desc*, const hk_keygen_out*, size_t*) override;
+    // exec_tree.cuh
+    hk_status exec_tree(hk_ctx*, const hk_exec_tree_desc*, const hk_exec_tree_out*) override;
+    // stage1.cuh
+    hk_status stage1_witness(hk_ctx*, const hk_stage1_desc*, const uint32_t*, size_t, size_t, void*) override;
+    // trace_sort.cuh
+    hk_status trace_sort(hk_ctx*, uint32_t, const void*, size_t, void*, uint32_t*) override;
+    hk_status stage0_witness(hk_ctx*, const uint32_t*, uint32_t, uint32_t, const void*, const void*, const uint32_t*, size_t,
+                             void*) override;
 };
 
 }  // namespace hk

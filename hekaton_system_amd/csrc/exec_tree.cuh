@@ -1,7 +1,7 @@
 // exec_tree.cuh — the coordinator's work between the two rounds of a job on the device (hk_exec_tree):
 // the running evaluations after every subcircuit, the execution leaves, their Poseidon Merkle tree and one authentication
 // path per subcircuit (distributed-prover/src/coordinator.rs:125-174 `generate_exec_tree`, 425-466 the `generate_proof` loop
-// of CoordinatorStage1State::new; eval_tree.rs:53-101).  Included at the end of prove_impl.cuh.
+// of CoordinatorStage1State::new; eval_tree.rs:53-101).
 //
 //   (a) evaluations   a product scan: one lane per chunk of ET_CHUNK consecutive entries of the flattened trace (factors and
 //                     their product, subtrace boundaries ignored), a tiled exclusive scan of the chunk products (the shape of
@@ -12,6 +12,7 @@
 //                     levels of <= ET_WG_STATES states (and the leaf level too when it fits).
 //   (c) paths         siblings[i][l] = level_l[(i >> l) ^ 1], one lane per (i, l).
 #pragma once
+#include "curve_ops_impl.cuh"
 #include "ntt.cuh"
 #include "witness.cuh"
 

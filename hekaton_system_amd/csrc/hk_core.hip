@@ -75,14 +75,14 @@ static unsigned hw_queues() {
     return q && atoi(q) > 0 ? (unsigned)atoi(q) : 4u;
 }
 
-hk_status scratch_budget_check(const CurveOps* ops, const hipDeviceProp_t& prop, void** presize_out) {
+hk_status scratch_budget_check(CurveOps* ops, const hipDeviceProp_t& prop, void** presize_out) {
     // the deepest frame of EVERY curve the library carries, not only this context's: a process that opens a context of the
     // other curve later (the bench's BLS12-381 leg after its BN254 leg) then finds every queue's ring already at its final
     // size - no ring ever grows, and the moment the round-3 experiment aborted in (twenty rings wanted at once while the
     // previous context's were still held) does not arise
-    size_t frame = ops->max_private_bytes ? ops->max_private_bytes() : 0;
-    for (const CurveOps* o : {curve_ops_bn254(), curve_ops_bls381()})
-        if (o && o->max_private_bytes && o->max_private_bytes() > frame) frame = o->max_private_bytes();
+    size_t frame = ops->max_private_bytes();
+    for (CurveOps* o : {curve_ops_bn254(), curve_ops_bls381()})
+        if (o->max_private_bytes() > frame) frame = o->max_private_bytes();
     size_t prev = g_deepest_frame.load();
     while (frame > prev && !g_deepest_frame.compare_exchange_weak(prev, frame)) {}
     frame = g_deepest_frame.load();
@@ -314,7 +314,7 @@ hk_status hk_ctx_create(hk_curve curve, int device_id, hk_ctx** out) {
                 prop.gcnArchName);
         return HK_ERR_DEVICE;
     }
-    const hk::CurveOps* ops = curve == HK_BN254 ? curve_ops_bn254() : curve_ops_bls381();
+    hk::CurveOps* ops = curve == HK_BN254 ? curve_ops_bn254() : curve_ops_bls381();
     // no environment setting may be able to exhaust the runtime's scratch pool (the abort of round 2): refuse here
     void* presize = nullptr;
     HK_TRY(hk::scratch_budget_check(ops, prop, &presize));
@@ -349,7 +349,7 @@ void hk_ctx_destroy(hk_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
-    if (ctx->ops && ctx->ops->ctx_release) ctx->ops->ctx_release(ctx);
+    if (ctx->ops) ctx->ops->ctx_release(ctx);
     for (Lane* l : ctx->lanes) free_lane(l);
     for (Lane* l : ctx->prove_lanes) free_lane(l);
     delete ctx;
@@ -501,15 +501,20 @@ hk_status hk_points_lincomb_g2(hk_ctx* ctx, const void* const* vecs, const void*
     if (!ctx || !vecs || !coeffs_mont || (n && !out)) return HK_ERR_ARG;
     return ctx->ops->points_lincomb(ctx, 2, vecs, coeffs_mont, k, n, out);
 }
+// out[i] = lo[i] + (+-) coeffs2[0] * hi[i] + (+-) coeffs2[1] * phi(hi[i]) in G1: the G1 fold lo + c * hi with c split along the
+// GLV endomorphism phi(x, y) = (BETA x, y) into two ~128-bit parts on the host (128 doubling steps instead of 254)
 hk_status hk_points_fold_g1(hk_ctx* ctx, const void* lo, const void* hi, const void* coeffs2_mont, unsigned neg_mask, size_t n,
                             void* out) {
     if (!ctx || !ctx->ops) return HK_ERR_ARG;
-    return ctx->ops->points_fold_g1(ctx, lo, hi, coeffs2_mont, neg_mask, n, out);
+    return ctx->ops->points_fold_many(ctx, 1, 1, &lo, &hi, coeffs2_mont, neg_mask, n, &out);
 }
+// out[i] = lo[i] + sum_{j<4} (+-) coeffs4[j] * psi^j(hi[i]) in G2: the fold lo + c * hi of a TIPA round with c split into
+// four ~64-bit parts on the host (c = sum +-coeffs4[j] lambda^j mod r, lambda = psi's eigenvalue), so the shared doubling
+// chain of the element-wise combination is ~66 steps instead of 254; one table add per step (endo.cuh)
 hk_status hk_points_fold_g2(hk_ctx* ctx, const void* lo, const void* hi, const void* coeffs4_mont, unsigned neg_mask, size_t n,
                             void* out) {
     if (!ctx || !ctx->ops) return HK_ERR_ARG;
-    return ctx->ops->points_fold_g2(ctx, lo, hi, coeffs4_mont, neg_mask, n, out);
+    return ctx->ops->points_fold_many(ctx, 2, 1, &lo, &hi, coeffs4_mont, neg_mask, n, &out);
 }
 hk_status hk_points_fold_many_g1(hk_ctx* ctx, size_t k, const void* const* lo, const void* const* hi, const void* coeffs2_mont,
                                  unsigned neg_mask, size_t n, void* const* out) {

@@ -155,83 +155,99 @@ typedef Coalescer<const hk_pk*, ProveCall, ProveResult> ProveCoalescer;
 }  // namespace hk
 
 namespace hk {
-// per-curve entry points; each curve's translation unit fills one table
+// per-curve entry points: each curve's translation unit (hk_<curve>_ops.hip) instantiates Ops<C> (curve_ops_impl.cuh), which
+// overrides every one of them.  Grouped by the header that defines them, in the order of Ops<C>'s declarations.
 struct CurveOps {
-    size_t fr_bytes, fq_bytes, g1_bytes, g2_bytes;
-    hk_status (*msm)(hk_ctx*, int group, const void* bases, size_t n_bases, const void* scalars,
-                     size_t n_scalars, int mont, int checked, void* out);
-    hk_status (*ntt)(hk_ctx*, void* data, unsigned log_m, int inverse, int coset);
-    hk_status (*witness_map)(hk_ctx*, const hk_csr* A, const hk_csr* B, const hk_csr* C, size_t n_inst,
-                             size_t n_c, const void* z, size_t n_v, void* h_out, size_t h_cap, size_t* m_out);
-    hk_status (*pk_upload)(hk_ctx*, const hk_pk_desc*, hk_pk**);
-    void (*pk_free)(hk_pk*);
-    hk_status (*commit)(hk_ctx*, const hk_pk*, size_t stage, const void* w, size_t n, const void* kappa,
-                        void* out);
-    void (*ctx_release)(hk_ctx*);
-    hk_status (*fixed_base)(hk_ctx*, int group, const void* base, const void* scalars, size_t n, int mont,
-                            void* out);
-    hk_status (*scalar_pairing)(hk_ctx*, int group, const void* points, const void* scalars, size_t n, void* out);
-    hk_status (*field_convert)(hk_ctx*, int which, const void* in, void* out, size_t n, int to_mont);
-    hk_status (*bases_upload)(hk_ctx*, int group, const void* bases, size_t n, hk_bases** out);
-    void (*bases_free)(hk_bases*);
-    hk_status (*msm_bases)(hk_ctx*, const hk_bases*, const void* scalars, size_t n_scalars, int mont, int checked,
-                           void* out);
-    hk_status (*pairing_products)(hk_ctx*, const void* const* lhs, size_t n_lhs, const void* const* rhs, size_t n_rhs,
-                                  size_t n, void* out);
-    size_t gt_bytes;
-    hk_status (*points_lincomb)(hk_ctx*, int group, const void* const* vecs, const void* coeffs, size_t k, size_t n,
-                                void* out);
-    hk_status (*points_fold_g2)(hk_ctx*, const void* lo, const void* hi, const void* coeffs4, unsigned neg_mask, size_t n,
-                                void* out);
-    hk_status (*points_fold_g1)(hk_ctx*, const void* lo, const void* hi, const void* coeffs2, unsigned neg_mask, size_t n,
-                                void* out);
-    hk_status (*assignment_from_bits)(hk_ctx*, const void* bits, size_t n_v, const uint32_t* full_cols,
-                                      const void* full_vals, size_t n_full, void* z_out);
-    hk_status (*wprog_upload)(hk_ctx*, const uint32_t* ops, size_t n_ops, const uint32_t* refs, size_t n_refs,
-                              const uint32_t* map, size_t n_v, size_t n_values, size_t n_inputs, hk_wprog** out);
-    void (*wprog_free)(hk_wprog*);
-    hk_status (*wprog_run)(hk_ctx*, const hk_wprog*, const uint32_t* inputs, size_t batch, const uint32_t* full_cols,
-                           const void* full_vals, size_t n_full, void* z_out);
-    hk_status (*gt_pow)(hk_ctx*, const void* gt_in, const void* scalars, size_t n, void* gt_out, int in_gt, size_t group_len);
+    const size_t fr_bytes, fq_bytes, g1_bytes, g2_bytes, gt_bytes;
+
+    // curve_ops_impl.cuh
+    virtual hk_status msm(hk_ctx*, int group, const void* bases, size_t n_bases, const void* scalars,
+                          size_t n_scalars, int mont, int checked, void* out) = 0;
     // largest private-memory frame (bytes per lane) among the curve's kernels: sizes the scratch ring the runtime
     // pins to every hardware queue that ever runs one of them
-    size_t (*max_private_bytes)();
-    hk_status (*poseidon_path)(hk_ctx*, const void* consts, size_t n_consts, const hk_poseidon_desc* leaf_hash,
-                               const hk_poseidon_desc* node_hash, const void* leaf, const void* siblings,
-                               const uint32_t* index, size_t depth, size_t batch, size_t n_v, size_t col0, void* z_out);
-    hk_status (*points_fold_many)(hk_ctx*, int group, size_t k, const void* const* lo, const void* const* hi,
-                                  const void* coeffs, unsigned neg_mask, size_t n, void* const* out);
-    hk_status (*pairing_pairs)(hk_ctx*, const void* const* lhs, size_t n_lhs, const void* const* rhs, size_t n_rhs,
-                               const uint32_t* pair_lhs, const uint32_t* pair_rhs, size_t n_pairs, size_t n, void* out);
-    hk_status (*assignment_scatter)(hk_ctx*, const uint32_t* full_cols, const void* full_vals, size_t n_full, size_t batch,
-                                    size_t n_v, void* z_out);
-    hk_status (*commit_batch)(hk_ctx*, const hk_pk*, size_t stage, const void* w, size_t n, const void* kappas, size_t batch,
-                              void* out);
+    virtual size_t max_private_bytes() = 0;
+    // ntt_host.cuh
+    virtual hk_status ntt(hk_ctx*, void* data, unsigned log_m, int inverse, int coset) = 0;
+    virtual hk_status witness_map(hk_ctx*, const hk_csr* A, const hk_csr* B, const hk_csr* C, size_t n_inst,
+                                  size_t n_c, const void* z, size_t n_v, void* h_out, size_t h_cap, size_t* m_out) = 0;
+    virtual void ctx_release(hk_ctx*) = 0;
+    // pk.cuh
+    virtual hk_status pk_upload(hk_ctx*, const hk_pk_desc*, hk_pk**) = 0;
+    virtual void pk_free(hk_pk*) = 0;
+    // group_ops.cuh
+    virtual hk_status bases_upload(hk_ctx*, int group, const void* bases, size_t n, hk_bases** out) = 0;
+    virtual void bases_free(hk_bases*) = 0;
+    virtual hk_status msm_bases(hk_ctx*, const hk_bases*, const void* scalars, size_t n_scalars, int mont, int checked,
+                                void* out) = 0;
+    virtual hk_status fixed_base(hk_ctx*, int group, const void* base, const void* scalars, size_t n, int mont,
+                                 void* out) = 0;
+    virtual hk_status scalar_pairing(hk_ctx*, int group, const void* points, const void* scalars, size_t n, void* out) = 0;
+    virtual hk_status points_lincomb(hk_ctx*, int group, const void* const* vecs, const void* coeffs, size_t k, size_t n,
+                                     void* out) = 0;
+    virtual hk_status points_fold_many(hk_ctx*, int group, size_t k, const void* const* lo, const void* const* hi,
+                                       const void* coeffs, unsigned neg_mask, size_t n, void* const* out) = 0;
+    virtual hk_status field_convert(hk_ctx*, int which, const void* in, void* out, size_t n, int to_mont) = 0;
+    // witness_host.cuh
+    virtual hk_status assignment_from_bits(hk_ctx*, const void* bits, size_t n_v, const uint32_t* full_cols,
+                                           const void* full_vals, size_t n_full, void* z_out) = 0;
+    virtual hk_status wprog_upload(hk_ctx*, const uint32_t* ops, size_t n_ops, const uint32_t* refs, size_t n_refs,
+                                   const uint32_t* map, size_t n_v, size_t n_values, size_t n_inputs, hk_wprog** out) = 0;
+    virtual void wprog_free(hk_wprog*) = 0;
+    virtual hk_status wprog_run(hk_ctx*, const hk_wprog*, const uint32_t* inputs, size_t batch, const uint32_t* full_cols,
+                                const void* full_vals, size_t n_full, void* z_out) = 0;
+    virtual hk_status assignment_scatter(hk_ctx*, const uint32_t* full_cols, const void* full_vals, size_t n_full, size_t batch,
+                                         size_t n_v, void* z_out) = 0;
+    virtual hk_status poseidon_path(hk_ctx*, const void* consts, size_t n_consts, const hk_poseidon_desc* leaf_hash,
+                                    const hk_poseidon_desc* node_hash, const void* leaf, const void* siblings,
+                                    const uint32_t* index, size_t depth, size_t batch, size_t n_v, size_t col0, void* z_out) = 0;
+    // pairing_ops.cuh
+    virtual hk_status pairing_products(hk_ctx*, const void* const* lhs, size_t n_lhs, const void* const* rhs, size_t n_rhs,
+                                       size_t n, void* out) = 0;
+    virtual hk_status pairing_pairs(hk_ctx*, const void* const* lhs, size_t n_lhs, const void* const* rhs, size_t n_rhs,
+                                    const uint32_t* pair_lhs, const uint32_t* pair_rhs, size_t n_pairs, size_t n, void* out) = 0;
+    virtual hk_status gt_pow(hk_ctx*, const void* gt_in, const void* scalars, size_t n, void* gt_out, int in_gt,
+                             size_t group_len) = 0;
+    // prove_impl.cuh
+    virtual hk_status commit(hk_ctx*, const hk_pk*, size_t stage, const void* w, size_t n, const void* kappa,
+                             void* out) = 0;
+    virtual hk_status commit_batch(hk_ctx*, const hk_pk*, size_t stage, const void* w, size_t n, const void* kappas, size_t batch,
+                                   void* out) = 0;
     // `batch` proofs of one key, row b from rows[b]; batch == 0 only validates (key, n_v, n_kappas) and touches nothing
-    hk_status (*prove_batch)(hk_ctx*, const hk_pk*, size_t n_v, size_t n_kappas, const ProveRow* rows, size_t batch);
-    hk_status (*vk_prepare)(hk_ctx*, const hk_vk_desc*, hk_vk**);
-    void (*vk_free)(hk_vk*);
-    hk_status (*vk_alpha_beta)(const hk_vk*, void*);
-    hk_status (*verify_batch)(hk_ctx*, const hk_vk*, const void* a, const void* b, const void* c, const void* ds, const void* inputs,
-                              size_t n, unsigned flags, const void* rand, unsigned char* verdicts);
-    hk_status (*points_check)(hk_ctx*, int group, const void* pts, size_t n, unsigned char* ok);
-    hk_status (*qap_eval)(hk_ctx*, const hk_csr* A, const hk_csr* B, const hk_csr* C, size_t n_inst, size_t n_c, size_t n_v,
-                          const void* t, void* a, void* b, void* c, void* zt, size_t* m_out);
-    hk_status (*keygen)(hk_ctx*, const hk_keygen_desc*, const hk_keygen_out*, size_t* m_out);
-    hk_status (*exec_tree)(hk_ctx*, const hk_exec_tree_desc*, const hk_exec_tree_out*);
-    hk_status (*stage1_witness)(hk_ctx*, const hk_stage1_desc*, const uint32_t* sub_index, size_t batch, size_t n_v, void* z_out);
-    hk_status (*trace_sort)(hk_ctx*, uint32_t entry_fields, const void* time_entries, size_t n_entries, void* addr_entries_out,
-                            uint32_t* perm_out);
-    hk_status (*stage0_witness)(hk_ctx*, const uint32_t* offsets, uint32_t n_sub, uint32_t n_portals, const void* time_entries,
-                                const void* addr_entries, const uint32_t* sub_index, size_t batch, void* w_out);
+    virtual hk_status prove_batch(hk_ctx*, const hk_pk*, size_t n_v, size_t n_kappas, const ProveRow* rows, size_t batch) = 0;
+    // verify.cuh
+    virtual hk_status vk_prepare(hk_ctx*, const hk_vk_desc*, hk_vk**) = 0;
+    virtual void vk_free(hk_vk*) = 0;
+    virtual hk_status vk_alpha_beta(const hk_vk*, void*) = 0;
+    virtual hk_status verify_batch(hk_ctx*, const hk_vk*, const void* a, const void* b, const void* c, const void* ds,
+                                   const void* inputs, size_t n, unsigned flags, const void* rand, unsigned char* verdicts) = 0;
+    virtual hk_status points_check(hk_ctx*, int group, const void* pts, size_t n, unsigned char* ok) = 0;
+    // keygen.cuh
+    virtual hk_status qap_eval(hk_ctx*, const hk_csr* A, const hk_csr* B, const hk_csr* C, size_t n_inst, size_t n_c, size_t n_v,
+                               const void* t, void* a, void* b, void* c, void* zt, size_t* m_out) = 0;
+    virtual hk_status keygen(hk_ctx*, const hk_keygen_desc*, const hk_keygen_out*, size_t* m_out) = 0;
+    // exec_tree.cuh
+    virtual hk_status exec_tree(hk_ctx*, const hk_exec_tree_desc*, const hk_exec_tree_out*) = 0;
+    // stage1.cuh
+    virtual hk_status stage1_witness(hk_ctx*, const hk_stage1_desc*, const uint32_t* sub_index, size_t batch, size_t n_v,
+                                     void* z_out) = 0;
+    // trace_sort.cuh
+    virtual hk_status trace_sort(hk_ctx*, uint32_t entry_fields, const void* time_entries, size_t n_entries, void* addr_entries_out,
+                                 uint32_t* perm_out) = 0;
+    virtual hk_status stage0_witness(hk_ctx*, const uint32_t* offsets, uint32_t n_sub, uint32_t n_portals, const void* time_entries,
+                                     const void* addr_entries, const uint32_t* sub_index, size_t batch, void* w_out) = 0;
+
+protected:
+    CurveOps(size_t fr, size_t fq, size_t g1, size_t g2, size_t gt)
+        : fr_bytes(fr), fq_bytes(fq), g1_bytes(g1), g2_bytes(g2), gt_bytes(gt) {}
+    ~CurveOps() = default;
 };
-const CurveOps* curve_ops_bn254();
-const CurveOps* curve_ops_bls381();
+CurveOps* curve_ops_bn254();
+CurveOps* curve_ops_bls381();
 }  // namespace hk
 
 struct hk_ctx {
     hk_curve curve;
-    const hk::CurveOps* ops = nullptr;
+    hk::CurveOps* ops = nullptr;
     int device;
     int profiling = 0;
     std::mutex mu;
@@ -261,19 +277,19 @@ struct hk_ctx {
 };
 
 struct hk_pk {
-    const hk::CurveOps* ops;
+    hk::CurveOps* ops;
     hk_ctx* ctx;
     void* impl;
 };
 
 struct hk_vk {                     // a prepared verifying key (verify.cuh VkImpl)
-    const hk::CurveOps* ops;
+    hk::CurveOps* ops;
     hk_ctx* ctx;
     void* impl;
 };
 
 struct hk_bases {
-    const hk::CurveOps* ops;
+    hk::CurveOps* ops;
     hk_ctx* ctx;
     void* impl;
 };
@@ -286,7 +302,7 @@ struct WprogImpl {                 // a class's word program on the device (witn
 };
 }  // namespace hk
 struct hk_wprog {
-    const hk::CurveOps* ops;
+    hk::CurveOps* ops;
     hk_ctx* ctx;
     hk::WprogImpl* impl;
 };
@@ -303,6 +319,14 @@ struct LaneGuard {
 };
 
 bool is_device_ptr(const void* p);
+static inline hipMemcpyKind h2d_kind(const void* src) {
+    return is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+}
+static inline float ev_ms(hipEvent_t a, hipEvent_t b) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); return 0.f; }
+    return ms;
+}
 // *p: `bytes` of lane scratch carved for the input `src`.  A host `src` is copied there; a device `src` replaces *p.
 hk_status to_device(Lane* L, const void* src, size_t bytes, const void** p);
 

@@ -19,6 +19,8 @@
 //   (d) the fixed-base sweeps of fixed_base.cuh over those device-resident scalars, one per output, each written into
 //       the caller's buffer (device) or copied there (host).
 #pragma once
+#include "ntt_host.cuh"
+#include "group_ops.cuh"
 
 namespace hk {
 

@@ -1,0 +1,371 @@
+// ntt_host.cuh — host side of the scalar-field transforms: the context's twiddle / coset tables, the launch sequences of
+// ntt.cuh's kernels (NttHost), the witness map over device-resident CSR matrices (QapHost), and the release of what a
+// context caches on the device.  Defines Ops<C>::ntt (hk_ntt), Ops<C>::witness_map (hk_witness_map), Ops<C>::ctx_release.
+#pragma once
+#include "curve_ops_impl.cuh"
+#include "ntt.cuh"
+
+namespace hk {
+
+// ---- small host helpers on Montgomery values (setup constants only) -------------------------------
+template <class Fr>
+static Fr host_halve(const Fr& a) {          // a/2 in the field (works on Montgomery residues too)
+    u32 t[Fr::N + 1];
+    u64 c = 0;
+    bool odd = a.v[0] & 1;
+    for (int i = 0; i < Fr::N; i++) {
+        c += (u64)a.v[i] + (odd ? Fr::Params::MOD[i] : 0u);
+        t[i] = (u32)c;
+        c >>= 32;
+    }
+    t[Fr::N] = (u32)c;
+    Fr r;
+    for (int i = 0; i < Fr::N; i++) r.v[i] = (t[i] >> 1) | (t[i + 1] << 31);
+    return r;
+}
+template <class Fr>
+static Fr host_from_limbs(const u32* l) {
+    Fr r;
+    for (int i = 0; i < Fr::N; i++) r.v[i] = l[i];
+    return r;
+}
+
+// ---- twiddle / coset tables (one set per context) ---------------------------------------------------
+struct NttTables {
+    std::mutex mu;
+    u32 log_table = 0;
+    void* tw_fwd = nullptr;      // per-stage tables of w (k_stage_tables), 2^log_table - 1 entries; stage s always uses the
+                                 // 2^(s+1)-th roots, so every transform size <= 2^log_table shares them
+    void* tw_inv = nullptr;      // same for w^-1
+    void* pw_g = nullptr;        // 3 x POW_TABLE_SIZE powers of F::GENERATOR
+    void* pw_ginv = nullptr;
+    std::vector<void*> retired;  // superseded tables stay alive until the context dies
+};
+
+template <class C>
+struct NttHost {
+    typedef typename C::Fr Fr;
+
+    static hk_status ensure(hk_ctx* ctx, u32 log_m, NttTables** out) {
+        if (log_m > C::TWO_ADICITY) return HK_ERR_DOMAIN_TOO_LARGE;
+        std::unique_lock<std::mutex> lk(ctx->mu);
+        if (!ctx->ntt) ctx->ntt = new NttTables();
+        NttTables* T = ctx->ntt;
+        lk.unlock();
+        std::unique_lock<std::mutex> tl(T->mu);
+        *out = T;
+        if (T->log_table >= log_m && T->tw_fwd) return HK_OK;
+        u32 L = log_m < 16 ? 16 : log_m;
+        if (L > C::TWO_ADICITY) L = C::TWO_ADICITY;
+        HK_HIP(hipSetDevice(ctx->device));
+        // host: w_M = ROOT^(2^(s-L)); sq[k] = w_M^(2^k); w_M^-1 = prod_k sq[k]
+        std::vector<Fr> sq(32), sqi(32);
+        Fr w = host_from_limbs<Fr>(C::ROOT);
+        for (u32 k = 0; k < C::TWO_ADICITY - L; k++) w = Fr::sqr(w);
+        Fr winv = Fr::one();
+        for (u32 k = 0; k < L; k++) {
+            sq[k] = w;
+            winv = Fr::mul(winv, w);
+            w = Fr::sqr(w);
+        }
+        Fr t = winv;
+        for (u32 k = 0; k < L; k++) { sqi[k] = t; t = Fr::sqr(t); }
+        const u32 NG = 3 * POW_TABLE_BITS;
+        std::vector<Fr> gs(NG), gis(NG);
+        Fr g = host_from_limbs<Fr>(C::GEN), gi = host_from_limbs<Fr>(C::GEN_INV);
+        for (u32 k = 0; k < NG; k++) { gs[k] = g; gis[k] = gi; g = Fr::sqr(g); gi = Fr::sqr(gi); }
+        Fr *d_sq = nullptr, *tmp = nullptr, *tf = nullptr, *ti = nullptr, *pg = nullptr, *pgi = nullptr;
+        size_t half = (size_t)1 << (L - 1), full = (size_t)1 << L;
+        HK_HIP(hipMalloc((void**)&d_sq, sizeof(Fr) * (64 + 2 * NG)));
+        HK_HIP(hipMalloc((void**)&tmp, sizeof(Fr) * half));
+        HK_HIP(hipMalloc((void**)&tf, sizeof(Fr) * full));
+        HK_HIP(hipMalloc((void**)&ti, sizeof(Fr) * full));
+        HK_HIP(hipMalloc((void**)&pg, sizeof(Fr) * 3 * POW_TABLE_SIZE));
+        HK_HIP(hipMalloc((void**)&pgi, sizeof(Fr) * 3 * POW_TABLE_SIZE));
+        HK_HIP(hipMemcpy(d_sq, sq.data(), sizeof(Fr) * 32, hipMemcpyHostToDevice));
+        HK_HIP(hipMemcpy(d_sq + 32, sqi.data(), sizeof(Fr) * 32, hipMemcpyHostToDevice));
+        HK_HIP(hipMemcpy(d_sq + 64, gs.data(), sizeof(Fr) * NG, hipMemcpyHostToDevice));
+        HK_HIP(hipMemcpy(d_sq + 64 + NG, gis.data(), sizeof(Fr) * NG, hipMemcpyHostToDevice));
+        u32 blocks = (u32)((half + 255) / 256), blocks_full = (u32)((full + 255) / 256);
+        // w_M^i for i < M/2 (scratch), regrouped into one contiguous table per butterfly stage
+        hipLaunchKernelGGL((k_pow_table<Fr>), dim3(blocks), dim3(256), 0, 0, tmp, d_sq, (u32)half, L - 1);
+        hipLaunchKernelGGL((k_stage_tables<Fr>), dim3(blocks_full), dim3(256), 0, 0, tf, tmp, L);
+        hipLaunchKernelGGL((k_pow_table<Fr>), dim3(blocks), dim3(256), 0, 0, tmp, d_sq + 32, (u32)half, L - 1);
+        hipLaunchKernelGGL((k_stage_tables<Fr>), dim3(blocks_full), dim3(256), 0, 0, ti, tmp, L);
+        for (u32 lvl = 0; lvl < 3; lvl++) {
+            hipLaunchKernelGGL((k_pow_table<Fr>), dim3(POW_TABLE_SIZE / 256), dim3(256), 0, 0, pg + POW_TABLE_SIZE * lvl,
+                               d_sq + 64 + POW_TABLE_BITS * lvl, (u32)POW_TABLE_SIZE, (u32)POW_TABLE_BITS);
+            hipLaunchKernelGGL((k_pow_table<Fr>), dim3(POW_TABLE_SIZE / 256), dim3(256), 0, 0, pgi + POW_TABLE_SIZE * lvl,
+                               d_sq + 64 + NG + POW_TABLE_BITS * lvl, (u32)POW_TABLE_SIZE, (u32)POW_TABLE_BITS);
+        }
+        HK_HIP(hipGetLastError());
+        HK_HIP(hipDeviceSynchronize());
+        HK_HIP(hipFree(d_sq));
+        HK_HIP(hipFree(tmp));
+        for (void* p : {T->tw_fwd, T->tw_inv, T->pw_g, T->pw_ginv})
+            if (p) T->retired.push_back(p);
+        T->tw_fwd = tf; T->tw_inv = ti; T->pw_g = pg; T->pw_ginv = pgi;
+        T->log_table = L;
+        return HK_OK;
+    }
+
+    static Fr size_inv(u32 log_m) {               // (2^log_m)^-1, Montgomery
+        Fr x = Fr::one();
+        for (u32 k = 0; k < log_m; k++) x = host_halve(x);
+        return x;
+    }
+    static Fr vanishing_inv_on_coset(u32 log_m) {  // (g^m - 1)^-1  (SURVEY.md A.1 `zinv`)
+        Fr g = host_from_limbs<Fr>(C::GEN);
+        for (u32 k = 0; k < log_m; k++) g = Fr::sqr(g);
+        return fp_inv(Fr::sub(g, Fr::one()));
+    }
+
+    // fused epilogue of the last pass (k_ntt_pass4): which steps, on how many of the batched vectors, operands
+    struct Post {
+        int post = 0;
+        u32 nvec = 0xffffffffu;
+        const Fr* scale = nullptr;    // post & 1
+        const Fr* pw = nullptr;       // post & 2
+        const Fr* sub = nullptr;      // post & 4
+        const Fr* kc = nullptr;
+    };
+
+    // all butterfly stages of a size-2^logn transform, `batch` vectors `stride` elements apart.
+    // tws: per-stage twiddle tables.
+    static hk_status passes(hipStream_t s, Fr* data, size_t stride, u32 batch, u32 logn, const Fr* tws, int dit,
+                            const Post& ep = Post()) {
+        if (logn == 0) return HK_OK;
+        // bottom pass: the low min(logn, 11) stages on contiguous tiles; the rest in passes of at most
+        // `upper_max` stages whose tiles are 2^nst rows of 2^(11 - nst) contiguous elements
+        static const u32 upper_max = [] {
+            const char* e = getenv("HK_NTT_UPPER_MAX");
+            u32 v = e ? (u32)atoi(e) : 6u;      // 2^21: 11+5+5, 2^22: 11+6+5 (a single 10-stage upper pass with
+                                                // 64-B rows measured the same alone and less steady under load)
+            return v < 1 ? 1u : (v > 10 ? 10u : v);
+        }();
+        static const u32 tile_log = [] {
+            const char* e = getenv("HK_NTT_TILE_LOG");
+            u32 v = e ? (u32)atoi(e) : (u32)NTT_TILE_LOG;
+            return v < 8 ? 8u : (v > (u32)NTT_TILE_LOG ? (u32)NTT_TILE_LOG : v);
+        }();
+        const u32 threads = 1u << (tile_log - 2);                    // one radix-4 quad per thread
+        u32 bottom = logn < tile_log ? logn : tile_log;
+        u32 rest = logn - bottom;
+        u32 npass = (rest + upper_max - 1) / upper_max;
+        struct P { u32 lo, nst, cols_bits; } ps[34];
+        int np = 0;
+        ps[np++] = {0, bottom, 0};
+        u32 lo = bottom;
+        for (u32 i = 0; i < npass; i++) {
+            u32 nst = (rest - (lo - bottom) + (npass - i) - 1) / (npass - i);
+            ps[np++] = {lo, nst, tile_log - nst};
+            lo += nst;
+        }
+        Fr one = Fr::one();
+        for (int k = 0; k < np; k++) {
+            const P& p = dit ? ps[k] : ps[np - 1 - k];
+            u32 tile_log = p.nst + p.cols_bits;
+            dim3 grid(1u << (logn - tile_log), batch);
+            size_t lds = sizeof(Fr) << tile_log;
+            bool last = k == np - 1;
+            int pp = last ? ep.post : 0;
+            const Fr& sc = (pp & 1) ? *ep.scale : one;
+            const Fr& kc = (pp & 4) ? *ep.kc : one;
+            if (dit)
+                hipLaunchKernelGGL((k_ntt_pass4<Fr, 1>), grid, dim3(threads), lds, s, data, stride, tws, logn, p.lo,
+                                   p.nst, p.cols_bits, pp, ep.nvec, sc, ep.pw, ep.sub, kc);
+            else
+                hipLaunchKernelGGL((k_ntt_pass4<Fr, 0>), grid, dim3(threads), lds, s, data, stride, tws, logn, p.lo,
+                                   p.nst, p.cols_bits, pp, ep.nvec, sc, ep.pw, ep.sub, kc);
+        }
+        HK_HIP(hipGetLastError());
+        return HK_OK;
+    }
+
+    static hk_status scale(hipStream_t s, Fr* data, size_t stride, u32 batch, u32 logn, const Fr* pw,
+                           const Fr& sc, int bitrev_index, int use_pow) {
+        size_t n = (size_t)1 << logn;
+        hipLaunchKernelGGL((k_scale_pow<Fr>), dim3((u32)((n + 255) / 256), batch), dim3(256), 0, s, data,
+                           stride, pw, sc, logn, bitrev_index, use_pow);
+        HK_HIP(hipGetLastError());
+        return HK_OK;
+    }
+    static hk_status bitrev(hipStream_t s, Fr* data, u32 logn) {
+        size_t n = (size_t)1 << logn;
+        hipLaunchKernelGGL((k_bitrev<Fr>), dim3((u32)((n + 255) / 256)), dim3(256), 0, s, data, logn);
+        HK_HIP(hipGetLastError());
+        return HK_OK;
+    }
+};
+
+template <class C>
+hk_status Ops<C>::ntt(hk_ctx* ctx, void* data, unsigned log_m, int inverse, int coset) {
+    typedef NttHost<C> N;
+    NttTables* T;
+    HK_TRY(N::ensure(ctx, log_m, &T));
+    LaneGuard g(ctx);
+    Lane* L = g.lane;
+    if (!L) return HK_ERR_DEVICE;
+    size_t n = (size_t)1 << log_m;
+    Fr* stage;
+    HK_TRY(L->carve([&](Carve& c) { stage = c.n<Fr>(n); }));
+    bool dev = is_device_ptr(data);
+    Fr* d = (Fr*)data;
+    if (!dev) {
+        d = stage;
+        HK_HIP(hipMemcpyAsync(d, data, n * sizeof(Fr), hipMemcpyHostToDevice, L->stream));
+    }
+    hipStream_t s = L->stream;
+    if (!inverse) {
+        // coset FFT: coeff j *= g^j, then FFT (A.2).  DIF then un-permute.
+        if (coset) HK_TRY(N::scale(s, d, n, 1, log_m, (const Fr*)T->pw_g, Fr::one(), 0, 1));
+        HK_TRY(N::passes(s, d, n, 1, log_m, (const Fr*)T->tw_fwd, 0));
+        HK_TRY(N::bitrev(s, d, log_m));
+    } else {
+        // iFFT: DIF with w^-1, scale by 1/m (and g^-j for the coset form), un-permute
+        Fr minv = N::size_inv(log_m);
+        typename N::Post ep;
+        ep.post = coset ? 3 : 1;
+        ep.scale = &minv;
+        ep.pw = (const Fr*)T->pw_ginv;
+        HK_TRY(N::passes(s, d, n, 1, log_m, (const Fr*)T->tw_inv, 0, ep));
+        HK_TRY(N::bitrev(s, d, log_m));
+    }
+    if (!dev) HK_HIP(hipMemcpyAsync(data, d, n * sizeof(Fr), hipMemcpyDeviceToHost, s));
+    return L->settle();
+}
+
+// ---- witness map on device buffers --------------------------------------------------------------------
+struct CsrDev { const u64* row_ptr; const u32* col; const void* val; size_t n_rows, nnz; };
+
+// HK_ERR_ARG unless the (device-resident) matrix is structurally sound for n_cols variables: a malformed matrix
+// must come back as an error (the reference returns an ark error), never as an out-of-bounds device read.
+// `flag`: one u32 of device scratch.  Synchronises `s`.
+static hk_status csr_validate(hipStream_t s, const CsrDev& M, size_t n_cols, u32* flag) {
+    if (n_cols >= ((size_t)1 << 32)) return HK_ERR_ARG;
+    HK_HIP(hipMemsetAsync(flag, 0, sizeof(u32), s));
+    size_t work = M.n_rows > M.nnz ? M.n_rows : M.nnz;
+    u32 blocks = (u32)std::min<size_t>((work + 255) / 256, 2048);
+    if (blocks == 0) blocks = 1;
+    hipLaunchKernelGGL((k_csr_check<0>), dim3(blocks), dim3(256), 0, s, M.row_ptr, M.col, (u64)M.n_rows, (u64)M.nnz,
+                       (u32)n_cols, flag);
+    u32 h = 0;
+    HK_HIP(hipMemcpyAsync(&h, flag, sizeof(u32), hipMemcpyDeviceToHost, s));
+    HK_HIP(hipStreamSynchronize(s));
+    return h ? HK_ERR_ARG : HK_OK;
+}
+
+template <class C>
+struct QapHost {
+    typedef typename C::Fr Fr;
+    typedef NttHost<C> N;
+
+    static u32 domain_log(size_t n_c, size_t n_inst) {
+        size_t need = n_c + n_inst;
+        u32 lg = 0;
+        while (((size_t)1 << lg) < need) lg++;
+        return lg;
+    }
+    // abc: 3*m Fr scratch (a | b | c).  On return a[0..m) = h in BIT-REVERSED order.
+    static hk_status run(hipStream_t s, NttTables* T, const CsrDev& A, const CsrDev& B, const CsrDev& Cm,
+                         size_t n_inst, size_t n_c, const Fr* z, Fr* abc, u32 log_m) {
+        size_t m = (size_t)1 << log_m;
+        const CsrDev* Ms[3] = {&A, &B, &Cm};
+        for (int k = 0; k < 3; k++) {
+            // every row of the m-element vector is written: matrix rows, the instance copy behind them (a only:
+            // a[n_c + j] = z[j]), zeros - no memset of the 3 m x 32 B (a 201 MB fill at m = 2^21)
+            hipLaunchKernelGGL((k_spmv<Fr>), dim3((u32)((m + 255) / 256)), dim3(256), 0, s,
+                               Ms[k]->row_ptr, Ms[k]->col, (const Fr*)Ms[k]->val, z, abc + k * m,
+                               (u32)n_c, k == 0 ? (u32)n_inst : 0u, (u32)m);
+        }
+        // With Z constant on the coset (Z(g w^i) = g^m - 1) and the transforms linear,
+        //     h = zinv * (coset_ifft(a_coset o b_coset) - ifft(c))
+        // which is bit for bit what A.1 computes with its seventh transform (c's coset fft) left out.
+        // Every inverse transform here is UNSCALED (m times too large); the powers of 1/m are folded into k, kc.
+        const Fr* tinv = (const Fr*)T->tw_inv;
+        const Fr* tfwd = (const Fr*)T->tw_fwd;
+        typename N::Post e1;                                   // ifft (DIF) of a, b, c; "* g^j" on a and b only
+        e1.post = 2;
+        e1.nvec = 2;
+        e1.pw = (const Fr*)T->pw_g;
+        HK_TRY(N::passes(s, abc, m, 3, log_m, tinv, 0, e1));
+        HK_TRY(N::passes(s, abc, m, 2, log_m, tfwd, 1));       // coset fft (DIT) of a, b
+        hipLaunchKernelGGL((k_mul_pointwise<Fr>), dim3((u32)((m + 255) / 256)), dim3(256), 0, s, abc, abc + m, m);
+        Fr minv = N::size_inv(log_m);
+        Fr mm = fp_inv(Fr::mul(minv, minv));                                                    // m^2
+        Fr k = Fr::mul(N::vanishing_inv_on_coset(log_m), Fr::mul(minv, Fr::mul(minv, minv)));   // zinv / m^3
+        typename N::Post e2;                                   // coset ifft (DIF): (x * g^-j - c' * m^2) * zinv/m^3
+        e2.post = 2 | 4 | 1;
+        e2.pw = (const Fr*)T->pw_ginv;
+        e2.sub = abc + 2 * m;
+        e2.kc = &mm;
+        e2.scale = &k;
+        HK_TRY(N::passes(s, abc, m, 1, log_m, tinv, 0, e2));
+        HK_HIP(hipGetLastError());
+        return HK_OK;
+    }
+};
+
+template <class C>
+hk_status Ops<C>::witness_map(hk_ctx* ctx, const hk_csr* A, const hk_csr* B, const hk_csr* Cm, size_t n_inst,
+                              size_t n_c, const void* z, size_t n_v, void* h_out, size_t h_cap,
+                              size_t* m_out) {
+    typedef QapHost<C> Q;
+    if (A->n_rows != n_c || B->n_rows != n_c || Cm->n_rows != n_c || n_inst > n_v || n_inst < 1) return HK_ERR_ARG;
+    for (auto M : {A, B, Cm})
+        if (!M->row_ptr || (M->nnz && (!M->col || !M->val_mont))) return HK_ERR_ARG;
+    u32 log_m = Q::domain_log(n_c, n_inst);
+    if (log_m > C::TWO_ADICITY) return HK_ERR_DOMAIN_TOO_LARGE;
+    size_t m = (size_t)1 << log_m;
+    if (m_out) *m_out = m;
+    if (h_cap < m) return HK_ERR_LEN;
+    NttTables* T;
+    HK_TRY(NttHost<C>::ensure(ctx, log_m, &T));
+    LaneGuard g(ctx);
+    Lane* L = g.lane;
+    if (!L) return HK_ERR_DEVICE;
+    const hk_csr* Ms[3] = {A, B, Cm};
+    const void *rp[3], *cl[3], *vl[3], *zd;
+    u32* flag;
+    Fr* abc;
+    HK_TRY(L->carve([&](Carve& c) {
+        for (int k = 0; k < 3; k++) {
+            rp[k] = c.take(8 * (Ms[k]->n_rows + 1));
+            cl[k] = c.take(4 * Ms[k]->nnz);
+            vl[k] = c.take(sizeof(Fr) * Ms[k]->nnz);
+        }
+        flag = c.n<u32>(1);
+        zd = c.take(n_v * sizeof(Fr));
+        abc = c.n<Fr>(3 * m);
+    }));
+    CsrDev D[3];
+    for (int k = 0; k < 3; k++) {
+        HK_TRY(to_device(L, Ms[k]->row_ptr, 8 * (Ms[k]->n_rows + 1), &rp[k]));
+        HK_TRY(to_device(L, Ms[k]->col, 4 * Ms[k]->nnz, &cl[k]));
+        HK_TRY(to_device(L, Ms[k]->val_mont, sizeof(Fr) * Ms[k]->nnz, &vl[k]));
+        D[k] = {(const u64*)rp[k], (const u32*)cl[k], vl[k], Ms[k]->n_rows, Ms[k]->nnz};
+    }
+    for (int k = 0; k < 3; k++) HK_TRY(csr_validate(L->stream, D[k], n_v, flag));
+    HK_TRY(to_device(L, z, n_v * sizeof(Fr), &zd));
+    HK_TRY(Q::run(L->stream, T, D[0], D[1], D[2], n_inst, n_c, (const Fr*)zd, abc, log_m));
+    HK_TRY(NttHost<C>::bitrev(L->stream, abc, log_m));         // API returns natural order
+    HK_HIP(hipMemcpyAsync(h_out, abc, m * sizeof(Fr),
+                          is_device_ptr(h_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, L->stream));
+    return L->settle();
+}
+
+template <class C>
+void Ops<C>::ctx_release(hk_ctx* ctx) {
+    for (auto& e : ctx->fb_cache)
+        if (e.table) (void)hipFree(e.table);
+    ctx->fb_cache.clear();
+    if (!ctx->ntt) return;
+    NttTables* T = ctx->ntt;
+    for (void* p : {T->tw_fwd, T->tw_inv, T->pw_g, T->pw_ginv})
+        if (p) (void)hipFree(p);
+    for (void* p : T->retired) (void)hipFree(p);
+    delete T;
+    ctx->ntt = nullptr;
+}
+
+}  // namespace hk

@@ -10,6 +10,8 @@
 // Tables: gen_tower_params.py (derived symbolically from the tower formulas and self-checked numerically).
 #pragma once
 #include "pairing.cuh"
+#include "endo.cuh"            // EndoSplit, LanesPerValue
+#include "msm_driver.cuh"      // PairList
 #include "hk_wave_f12.h"
 
 namespace hk {

@@ -1,6 +1,6 @@
 // stage1.cuh — the challenge-dependent columns of a subcircuit's stage-1 assignment on the device (hk_stage1_witness,
 // DESIGN.md section 4i): what distributed-prover/src/subcircuit_circuit.rs:206-252 witnesses from the Stage1Request of
-// coordinator.rs:569-604, taken from hk_exec_tree's outputs where they lie.  Included at the end of prove_impl.cuh.
+// coordinator.rs:569-604, taken from hk_exec_tree's outputs where they lie.
 //
 //   k_s1_values      the three instance values and the portal block (10 k + 4 columns for k entries per order): copies, the two
 //                    running-evaluation chains, the address-step (inv, same) pairs.  One lane per (role, row), role-major, so

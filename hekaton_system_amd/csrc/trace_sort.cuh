@@ -1,7 +1,7 @@
 // trace_sort.cuh — the coordinator's address-ordered trace on the device (hk_trace_sort): the stable
 // sort of the flattened time-ordered entries by addr (ROM) / (addr, timestamp) (RAM) that
 // distributed-prover/src/coordinator.rs:92-123 `sort_subtraces_by_addr` does with sort_by_key, and the stage-0 witness rows
-// (hk_stage0_witness) cut from the two traces where they lie.  Included at the end of prove_impl.cuh.
+// (hk_stage0_witness) cut from the two traces where they lie.
 //
 //   keys     one lane per entry: the key fields out of Montgomery form, packed as W = 2 (ROM) or 3 (RAM) u32 planes, least
 //            significant first (RAM: timestamp, addr low, addr high), next to the entry's index; a word of flags: an error bit
@@ -14,6 +14,7 @@
 //   gather   the 64-B or 128-B entries by the final index vector, which is also perm_out.
 // A trace of at most TS_TILE entries runs keys, every pass and the gather in one launch of one workgroup (k_ts_small).
 #pragma once
+#include "curve_ops_impl.cuh"
 #include "keygen.cuh"
 
 namespace hk {

@@ -7,8 +7,6 @@
 // Operands enter as raw limbs (that is how representatives in [p, 2p) get into registers); every HIP status is returned
 // to the caller; the shim allocates and frees its own buffers and never touches an hk_ctx.
 #include "../../hekaton_system_amd/csrc/ec.cuh"
-#include "../../hekaton_system_amd/csrc/endo.cuh"            // EndoSplit, LanesPerValue: named by kernels of pairing_wave.cuh
-#include "../../hekaton_system_amd/csrc/msm_driver.cuh"      // PairList (declarations only; nothing of the drivers is linked)
 #include "../../hekaton_system_amd/csrc/pairing_wave.cuh"
 using namespace hk;
 

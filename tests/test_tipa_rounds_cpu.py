@@ -108,7 +108,7 @@ def test_a_round_pair_fits_the_batched_pairing_call():
     import re
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "hekaton_system_amd", "csrc")
     drv = open(os.path.join(root, "msm_driver.cuh")).read()
-    impl = open(os.path.join(root, "prove_impl.cuh")).read()
+    impl = open(os.path.join(root, "group_ops.cuh")).read()
     pair_max = int(re.search(r"PAIR_LIST_MAX\s*=\s*(\d+)", drv).group(1))
     rows_max = int(re.search(r"struct GatherRows \{\s*enum \{ MAX = (\d+) \}", impl).group(1))
     assert len(tipa._NAME_PAIRS) * len(tipa._QUARTERS) == 60 <= pair_max
