@@ -92,6 +92,10 @@ class hk_stage1_desc(C.Structure):            # include/hekaton.h
                 ("inst_col0", C.c_uint32), ("col0", C.c_uint32), ("pos_col0", C.c_uint32)]
 
 
+class hk_r1cs_verdict(C.Structure):           # include/hekaton.h
+    _fields_ = [("n_bad", C.c_uint32), ("first_bad", C.c_uint32)]
+
+
 class hk_timings(C.Structure):
     _fields_ = [(n, C.c_float) for n in
                 ("total_ms", "digits_ms", "msm_a_ms", "msm_b_g1_ms", "msm_b_g2_ms", "msm_l_ms",
@@ -112,7 +116,7 @@ EXPORTS = ["hk_status_str", "hk_version", "hk_ctx_create", "hk_ctx_destroy", "hk
            "hk_points_lincomb_g1", "hk_points_lincomb_g2", "hk_points_fold_g2", "hk_points_fold_g1", "hk_points_fold_many_g1", "hk_points_fold_many_g2", "hk_pairing_pairs", "hk_keccak_f1600", "hk_assignment_from_bits", "hk_wprog_upload", "hk_wprog_free", "hk_wprog_run", "hk_gt_pow", "hk_fq12_pow", "hk_gt_pow_prod", "hk_poseidon_path", "hk_assignment_scatter", "hk_commit_batch",
            "hk_prove_batch", "hk_vk_prepare", "hk_vk_free", "hk_vk_alpha_beta", "hk_verify_batch", "hk_points_check_g1",
            "hk_points_check_g2", "hk_qap_eval", "hk_keygen", "hk_exec_tree", "hk_stage1_witness",
-           "hk_trace_sort", "hk_stage0_witness"]
+           "hk_trace_sort", "hk_stage0_witness", "hk_r1cs_check", "hk_pk_r1cs_check"]
 
 HK_VERIFY_CHECK_POINTS = 1
 VERDICT_REJECT, VERDICT_ACCEPT, VERDICT_BAD_POINT = 0, 1, 2
@@ -205,6 +209,8 @@ def load():
     lib.hk_stage1_witness.argtypes = [vp, C.POINTER(hk_stage1_desc), vp, sz, sz, vp]
     lib.hk_trace_sort.argtypes = [vp, C.c_uint32, vp, sz, vp, vp]
     lib.hk_stage0_witness.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, sz, vp]
+    lib.hk_r1cs_check.argtypes = [vp, C.POINTER(hk_csr), C.POINTER(hk_csr), C.POINTER(hk_csr), vp, sz, sz, vp, vp, vp, sz]
+    lib.hk_pk_r1cs_check.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, sz]
     _lib = lib
     return lib
 
@@ -759,6 +765,33 @@ class Context:
               "hk_stage0_witness")
         return w_out
 
+    def _r1cs_call(self, fn, head, z, n_v, batch, cap, want_vals):
+        """The shared tail of Context.r1cs_check / DevicePk.r1cs_check: `fn(*head, z, n_v, batch, verdicts, rows, vals, cap)`."""
+        fr, batch, cap = self.fr_bytes, int(batch), int(cap)
+        zz = z if isinstance(z, DeviceBuffer) else np.ascontiguousarray(z, dtype=np.uint8).reshape(-1)
+        if n_v is None:
+            n_v = (zz.nbytes if isinstance(zz, DeviceBuffer) else zz.size) // (fr * max(batch, 1))
+        verdicts = np.zeros((batch, 2), dtype=np.uint32)               # hk_r1cs_verdict: n_bad, first_bad
+        rows = np.zeros((batch, cap), dtype=np.uint32) if cap else None
+        vals = np.zeros((batch, cap, 3 * fr), dtype=np.uint8) if cap and want_vals else None
+        check(fn(*head, ptr(zz) if batch else None, int(n_v), batch, verdicts.ctypes.data if batch else None, ptr(rows),
+                 ptr(vals), cap), fn.__name__)
+        res = [(int(n), None if n == 0 else int(f)) for n, f in verdicts]
+        if not cap:
+            return res
+        return (res, rows, vals) if want_vals else (res, rows)
+
+    def r1cs_check(self, A, B, C_, z, n_v=None, batch=1, cap=0, want_vals=False):
+        """hk_r1cs_check: ark's cs.is_satisfied() / which_is_unsatisfied() for `batch` assignments of one class.  A / B / C_:
+        (row_ptr, col, val) triples as witness_map takes them (members may be DeviceBuffers); z: Montgomery bytes or a
+        DeviceBuffer of batch x n_v Fr (n_v defaults to the buffer's size / batch).  Returns [(n_bad, first_bad)] per
+        assignment, first_bad None when it is satisfied; with cap also bad_rows, uint32 (batch, cap): the first failing rows in
+        ascending order, 0xFFFFFFFF beyond; with want_vals also uint8 (batch, cap, 3 Fr): (a, b, c) of those rows, Montgomery."""
+        keep = []
+        csrs = self._csrs((A, B, C_), keep)
+        return self._r1cs_call(self.lib.hk_r1cs_check, (self.handle, C.byref(csrs[0]), C.byref(csrs[1]), C.byref(csrs[2])), z, n_v,
+                               batch, cap, want_vals)
+
     def points_check(self, group, pts, n=None):
         """hk_points_check_g1 / _g2: ark's AffineRepr::check of each point (on its curve, in the prime-order subgroup;
         infinity passes).  pts: packed affine bytes (uint8 array or DeviceBuffer).  Returns np.uint8[n] of 0 / 1."""
@@ -949,6 +982,11 @@ class DevicePk:
         if self.handle:
             self.ctx.lib.hk_pk_free(self.handle)
             self.handle = None
+
+    def r1cs_check(self, z, n_v=None, batch=1, cap=0, want_vals=False):
+        """hk_pk_r1cs_check: Context.r1cs_check against the matrices this key was uploaded with (nothing goes up again)."""
+        ctx = self.ctx
+        return ctx._r1cs_call(ctx.lib.hk_pk_r1cs_check, (ctx.handle, self.handle), z, n_v, batch, cap, want_vals)
 
     def commit(self, stage, w_stage, kappa, n=None):
         """committer.rs:87-91 — msm(ck[stage], w) + kappa * last_delta_g; returns packed G1 bytes."""

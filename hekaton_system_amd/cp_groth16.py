@@ -183,6 +183,18 @@ class MultiStageConstraintSystem:
         ev = lambda row: sum(c * z[j] for c, j in row) % self.r
         return all(ev(a) * ev(b) % self.r == ev(c) for a, b, c in zip(A, B, C))
 
+    def which_is_unsatisfied(self):
+        """ark `which_is_unsatisfied`: the first row whose constraint fails, or None."""
+        bad = r1cs_bad_rows(*self.to_matrices(), self.full_assignment(), self.r)
+        return bad[0] if bad else None
+
+
+def r1cs_bad_rows(A_rows, B_rows, C_rows, z, r):
+    """The host mirror of hk_r1cs_check: the rows i with <A_i,z> <B_i,z> != <C_i,z> (mod r), ascending, over ark-style
+    [(coeff, col)] rows and the full assignment z (ints)."""
+    ev = lambda row: sum(c * z[j] for c, j in row) % r
+    return [i for i, (a, b, c) in enumerate(zip(A_rows, B_rows, C_rows)) if ev(a) * ev(b) % r != ev(c)]
+
 
 class MultiStageConstraintSynthesizer:
     """constraint_synthesizer.rs:119-134."""

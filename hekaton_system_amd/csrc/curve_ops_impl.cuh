@@ -188,6 +188,10 @@ struct Ops final : CurveOps {
     hk_status trace_sort(hk_ctx*, uint32_t, const void*, size_t, void*, uint32_t*) override;
     hk_status stage0_witness(hk_ctx*, const uint32_t*, uint32_t, uint32_t, const void*, const void*, const uint32_t*, size_t,
                              void*) override;
+    // r1cs_check.cuh
+    hk_status r1cs_check(hk_ctx*, const hk_csr*, const hk_csr*, const hk_csr*, const void*, size_t, size_t, hk_r1cs_verdict*,
+                         uint32_t*, void*, size_t) override;
+    hk_status pk_r1cs_check(hk_ctx*, const hk_pk*, const void*, size_t, size_t, hk_r1cs_verdict*, uint32_t*, void*, size_t) override;
 };
 
 }  // namespace hk

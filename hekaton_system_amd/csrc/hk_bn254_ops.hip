@@ -10,6 +10,7 @@
 #include "exec_tree.cuh"
 #include "stage1.cuh"
 #include "trace_sort.cuh"
+#include "r1cs_check.cuh"
 namespace hk {
 extern template struct MsmRun<CurveBn254::Fq>;
 extern template struct MsmRun<CurveBn254::Fq2>;

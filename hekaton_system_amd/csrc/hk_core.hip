@@ -684,6 +684,16 @@ hk_status hk_stage0_witness(hk_ctx* ctx, const uint32_t* offsets, uint32_t n_sub
     if (!ctx) return HK_ERR_ARG;
     return ctx->ops->stage0_witness(ctx, offsets, n_sub, n_portals, time_entries_mont, addr_entries_mont, sub_index, batch, w_out);
 }
+hk_status hk_r1cs_check(hk_ctx* ctx, const hk_csr* A, const hk_csr* B, const hk_csr* C, const void* z_mont, size_t n_v, size_t batch,
+                        hk_r1cs_verdict* verdicts, uint32_t* bad_rows, void* bad_vals, size_t cap) {
+    if (!ctx || !A || !B || !C) return HK_ERR_ARG;
+    return ctx->ops->r1cs_check(ctx, A, B, C, z_mont, n_v, batch, verdicts, bad_rows, bad_vals, cap);
+}
+hk_status hk_pk_r1cs_check(hk_ctx* ctx, const hk_pk* pk, const void* z_mont, size_t n_v, size_t batch, hk_r1cs_verdict* verdicts,
+                           uint32_t* bad_rows, void* bad_vals, size_t cap) {
+    if (!ctx || !pk) return HK_ERR_ARG;
+    return ctx->ops->pk_r1cs_check(ctx, pk, z_mont, n_v, batch, verdicts, bad_rows, bad_vals, cap);
+}
 
 }  // extern "C"
 

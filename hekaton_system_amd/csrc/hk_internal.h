@@ -235,6 +235,11 @@ struct CurveOps {
                                  uint32_t* perm_out) = 0;
     virtual hk_status stage0_witness(hk_ctx*, const uint32_t* offsets, uint32_t n_sub, uint32_t n_portals, const void* time_entries,
                                      const void* addr_entries, const uint32_t* sub_index, size_t batch, void* w_out) = 0;
+    // r1cs_check.cuh
+    virtual hk_status r1cs_check(hk_ctx*, const hk_csr* A, const hk_csr* B, const hk_csr* C, const void* z, size_t n_v, size_t batch,
+                                 hk_r1cs_verdict* verdicts, uint32_t* bad_rows, void* bad_vals, size_t cap) = 0;
+    virtual hk_status pk_r1cs_check(hk_ctx*, const hk_pk*, const void* z, size_t n_v, size_t batch, hk_r1cs_verdict* verdicts,
+                                    uint32_t* bad_rows, void* bad_vals, size_t cap) = 0;
 
 protected:
     CurveOps(size_t fr, size_t fq, size_t g1, size_t g2, size_t gt)

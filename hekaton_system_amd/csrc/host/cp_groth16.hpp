@@ -126,6 +126,28 @@ inline void generate_parameters(const Context& ctx, const Csr& A, const Csr& B, 
     if (vk_deltas_h) *vk_deltas_h = deltas_h;
 }
 
+// ark `cs.which_is_unsatisfied()` for `batch` assignments of one class, where they lie (hk_pk_r1cs_check / hk_r1cs_check): z
+// is host or device memory, batch x n_v Fr Montgomery.  Returns per assignment the first failing row, or -1 when it is
+// satisfied (`cs.is_satisfied()`).  The first form uses the matrices an uploaded key carries, the second takes them directly.
+inline std::vector<int64_t> which_is_unsatisfied(const Context& ctx, const ProvingKey& pk, const void* z, size_t n_v, size_t batch) {
+    std::vector<hk_r1cs_verdict> v(batch);
+    check(hk_pk_r1cs_check(ctx.raw(), pk.device, z, n_v, batch, v.data(), nullptr, nullptr, 0), "hk_pk_r1cs_check");
+    std::vector<int64_t> out(batch);
+    for (size_t b = 0; b < batch; b++) out[b] = v[b].n_bad ? (int64_t)v[b].first_bad : -1;
+    return out;
+}
+inline std::vector<int64_t> which_is_unsatisfied(const Context& ctx, const Csr& A, const Csr& B, const Csr& C, const void* z, size_t n_v,
+                                                 size_t batch) {
+    hk_csr a{A.row_ptr.data(), A.col.data(), A.val_mont.data(), A.row_ptr.size() - 1, A.col.size()};
+    hk_csr b{B.row_ptr.data(), B.col.data(), B.val_mont.data(), B.row_ptr.size() - 1, B.col.size()};
+    hk_csr c{C.row_ptr.data(), C.col.data(), C.val_mont.data(), C.row_ptr.size() - 1, C.col.size()};
+    std::vector<hk_r1cs_verdict> v(batch);
+    check(hk_r1cs_check(ctx.raw(), &a, &b, &c, z, n_v, batch, v.data(), nullptr, nullptr, 0), "hk_r1cs_check");
+    std::vector<int64_t> out(batch);
+    for (size_t i = 0; i < batch; i++) out[i] = v[i].n_bad ? (int64_t)v[i].first_bad : -1;
+    return out;
+}
+
 
 // constraint_synthesizer.rs:14-117 — assignments only (matrices are static per class and live with the key)
 struct MultiStageConstraintSystem {

@@ -1066,6 +1066,17 @@ class Stage0Device:
         self.traces = []
 
 
+class R1csUnsatisfied(AssertionError):
+    """An assignment on the device fails its class's R1CS (Stage1Device.check).  failures: [(subcircuit, n_bad, first_bad,
+    [the first failing rows])] of every failing subcircuit of the call, in the order of `members`."""
+
+    def __init__(self, failures):
+        self.failures = failures
+        self.subcircuit, self.n_bad, self.row, _ = failures[0]
+        super().__init__("subcircuit %d: constraint %d is unsatisfied (%d failing rows in it; %d failing subcircuits in the call)"
+                         % (self.subcircuit, self.row, self.n_bad, len(failures)))
+
+
 class Stage1Device:
     """What `ShaMerkleJob.stage1_device` returns: the job's traces and hk_exec_tree's outputs (evaluations, leaves, nodes,
     siblings, root) as DeviceBuffers, from which `fill` writes the challenge-dependent columns of a class's assignments
@@ -1111,6 +1122,21 @@ class Stage1Device:
             check(self.ctx.lib.hk_assignment_scatter(self.ctx.handle, cols.ctypes.data, vals.ctypes.data, 1, members.size,
                                                      circ.n_v, z.ptr), "hk_assignment_scatter")
         return z
+
+    def check(self, pk, z, members, cap=8):
+        """ark's `assert!(cs.is_satisfied())` on the filled rows (subcircuit_circuit.rs:311-399), where they lie: one
+        hk_pk_r1cs_check over the DeviceBuffer z (row b = members[b]) against the matrices of the class's key `pk` (a
+        capi.DevicePk, or anything with its r1cs_check).  Raises R1csUnsatisfied naming the first failing (subcircuit, row);
+        its `failures` lists up to `cap` rows per failing subcircuit.  Nothing calls this unless asked to."""
+        members = [int(i) for i in members]
+        if not members:
+            return
+        res = pk.r1cs_check(z, batch=len(members), cap=cap)
+        verdicts, rows = res if cap else (res, None)
+        failures = [(i, n_bad, first, [] if rows is None else [int(x) for x in rows[b] if x != 0xffffffff])
+                    for b, (i, (n_bad, first)) in enumerate(zip(members, verdicts)) if n_bad]
+        if failures:
+            raise R1csUnsatisfied(failures)
 
     def free(self):
         for x in ([] if self._adopted else list(self.traces)) + [self.params[0]] + list(self.outs):

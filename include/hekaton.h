@@ -594,6 +594,33 @@ hk_status hk_stage0_witness(hk_ctx* ctx, const uint32_t* offsets /* [h] n_sub + 
                             const uint32_t* sub_index /* [h] batch */, size_t batch,
                             void* w_out /* [d] batch x 4 n_portals Fr */);
 
+/* ---- R1CS satisfaction of device-resident assignments (ark `cs.is_satisfied()` / `which_is_unsatisfied()`:
+ * cp-groth16/src/lib.rs:158,291; distributed-prover/src/subcircuit_circuit.rs:311-399) -------------------------------------
+ * For each of `batch` assignments (row b at z_mont + b * n_v Fr, host or device; a device one is read in place) every row i of
+ * the class's matrices is tested: <A_i,z> * <B_i,z> == <C_i,z> on canonical values.  verdicts[b] says how many rows fail and
+ * which is the first.  With bad_rows and cap > 0, bad_rows[b] holds the first min(n_bad, cap) failing rows in ascending order
+ * and 0xFFFFFFFF in every further slot; with bad_vals as well, the three dot products (a, b, c) of exactly those rows,
+ * canonical Montgomery, and zeros in the unused slots.  cap == 0 or bad_rows == NULL: verdicts only.  Every byte of every
+ * output is defined and a function of the inputs alone (no value depends on the order in which anything lands).
+ * batch == 0: HK_OK, nothing done.  HK_ERR_ARG, before any launch and with the outputs untouched: a NULL context or matrix;
+ * NULL z_mont or verdicts with batch > 0; unequal n_rows; n_rows >= 2^32 or n_v >= 2^32; bad_vals without bad_rows;
+ * n_v == 0 (a row of z has column 0); batch >= 2^31 or batch x cap >= 2^31.  hk_r1cs_check validates the matrices against n_v
+ * as hk_witness_map does (a malformed one: HK_ERR_ARG, outputs untouched).  hk_pk_r1cs_check uses the matrices the key was
+ * uploaded with, nothing re-uploaded or re-validated: HK_ERR_ARG for a key of another context or one uploaded without matrices,
+ * HK_ERR_LEN (as hk_prove) when n_v is not the key's. */
+typedef struct {
+    uint32_t n_bad;      /* rows i with <A_i,z> * <B_i,z> != <C_i,z>                          */
+    uint32_t first_bad;  /* the smallest such i; 0xFFFFFFFF when n_bad == 0                   */
+} hk_r1cs_verdict;       /* cs.is_satisfied() <=> n_bad == 0; which_is_unsatisfied() <=> first_bad */
+hk_status hk_r1cs_check(hk_ctx* ctx, const hk_csr* A, const hk_csr* B, const hk_csr* C,
+                        const void* z_mont /* [h|d] batch x n_v Fr */, size_t n_v, size_t batch,
+                        hk_r1cs_verdict* verdicts /* [h] batch */,
+                        uint32_t* bad_rows /* [h|d] batch x cap, may be NULL */,
+                        void* bad_vals    /* [h|d] batch x cap x 3 Fr (a, b, c; Montgomery), may be NULL */,
+                        size_t cap);
+hk_status hk_pk_r1cs_check(hk_ctx* ctx, const hk_pk* pk, const void* z_mont, size_t n_v, size_t batch,
+                           hk_r1cs_verdict* verdicts, uint32_t* bad_rows, void* bad_vals, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif
