@@ -5,7 +5,7 @@
 //
 //   (a) evaluations   a product scan: one lane per chunk of ET_CHUNK consecutive entries of the flattened trace (factors and
 //                     their product, subtrace boundaries ignored), a tiled exclusive scan of the chunk products (the shape of
-//                     keygen.cuh's k_kg_scan_*, with Fr::mul), one lane per subcircuit boundary: prefix of its chunk times
+//                     scan.cuh's k_scan_u32_*, with Fr::mul), one lane per subcircuit boundary: prefix of its chunk times
 //                     the < ET_CHUNK factors left of the boundary.  Time and address order share every launch (grid.y).
 //   (b) tree          Poseidon with the state spread over the four lanes of a quad (poseidon_permute_quad): one launch hashes
 //                     the leaves, one launch per level wider than a workgroup, one launch with workgroup barriers for all

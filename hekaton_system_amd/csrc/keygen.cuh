@@ -21,12 +21,13 @@
 #pragma once
 #include "ntt_host.cuh"
 #include "group_ops.cuh"
+#include "csr.cuh"
+#include "scan.cuh"
 
 namespace hk {
 
 constexpr u32 KG_CHUNK = 64;                 // consecutive powers per lane (Lagrange coefficients, h query)
 constexpr u32 KG_SEG = 256;                  // longest run of one column a lane sums
-constexpr u32 KG_SCAN_TILE = 256 * 16;       // u32 elements per block of the exclusive scan
 
 // indices into the Fr constants a keygen / QAP call uploads (Montgomery)
 enum { KC_ALPHA, KC_BETA, KC_G1S, KC_G2S, KC_GAMMA_INV_G1S, KC_H0, KC_T, KC_K, KC_WSQ, KC_TSQ = KC_WSQ + 32, KC_N = KC_TSQ + 32 };
@@ -74,63 +75,6 @@ template <int UNUSED>
 __global__ void __launch_bounds__(256) k_kg_col_count(const u32* __restrict__ col, u32 nnz, u32* __restrict__ cnt) {
     u32 e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < nnz) atomicAdd(&cnt[col[e]], 1u);
-}
-
-// exclusive scan of n u32 in three launches: per tile (prefix within the tile into out, the tile's total into tops), over
-// the tops (one block), then the tops added back
-template <int UNUSED>
-__global__ void __launch_bounds__(256) k_kg_scan_tile(const u32* __restrict__ in, u32* __restrict__ out, u32* __restrict__ tops,
-                                                      u32 n) {
-    __shared__ u32 s[256];
-    const u32 tid = threadIdx.x;
-    const u64 base = (u64)blockIdx.x * KG_SCAN_TILE + (u64)tid * 16;
-    u32 v[16], sum = 0;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        v[j] = base + j < n ? in[base + j] : 0u;
-        sum += v[j];
-    }
-    s[tid] = sum;
-    __syncthreads();
-    for (u32 off = 1; off < 256; off <<= 1) {
-        u32 x = tid >= off ? s[tid - off] : 0u;
-        __syncthreads();
-        s[tid] += x;
-        __syncthreads();
-    }
-    u32 run = s[tid] - sum;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        if (base + j < n) out[base + j] = run;
-        run += v[j];
-    }
-    if (tid == 255) tops[blockIdx.x] = s[255];
-}
-template <int UNUSED>
-__global__ void __launch_bounds__(256) k_kg_scan_tops(u32* __restrict__ tops, u32 nt) {
-    __shared__ u32 s[256];
-    const u32 tid = threadIdx.x;
-    u32 carry = 0;
-    for (u32 b = 0; b < nt; b += 256) {
-        u32 i = b + tid;
-        u32 v = i < nt ? tops[i] : 0u;
-        s[tid] = v;
-        __syncthreads();
-        for (u32 off = 1; off < 256; off <<= 1) {
-            u32 x = tid >= off ? s[tid - off] : 0u;
-            __syncthreads();
-            s[tid] += x;
-            __syncthreads();
-        }
-        if (i < nt) tops[i] = carry + s[tid] - v;
-        carry += s[255];
-        __syncthreads();
-    }
-}
-template <int UNUSED>
-__global__ void __launch_bounds__(256) k_kg_scan_add(u32* __restrict__ out, const u32* __restrict__ tops, u32 n) {
-    u32 k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n) out[k] += tops[k / KG_SCAN_TILE];
 }
 
 // sorted[cursor[col]++] = val * u[row] for every entry; the row of entry e is found by bisection over row_ptr (validated:
@@ -304,8 +248,7 @@ struct KgHost {
         if ((u64)1 << *log_m >= lim || n_v >= lim || n_inst < 1 || n_inst > n_v) return HK_ERR_ARG;
         for (int k = 0; k < 3; k++) {
             const hk_csr* M = Ms[k];
-            if (!M || !M->row_ptr || (M->nnz && (!M->col || !M->val_mont))) return HK_ERR_ARG;
-            if (M->n_rows != n_c || M->nnz >= lim) return HK_ERR_ARG;
+            if (!csr_host_ok(M) || M->n_rows != n_c || M->nnz >= lim) return HK_ERR_ARG;
         }
         return HK_OK;
     }
@@ -341,50 +284,32 @@ struct KgQap {
     const hk_csr* Ms[3];
     size_t n_inst, n_c, n_v, nnz_max = 0, n_y = 0;
     u32 log_m;
-    const void *rp[3], *cl[3], *vl[3];
-    u32 *flag, *cnt, *st[2], *cursor, *tops;
+    R1csStage stage;
+    u32 *cnt, *st[2], *cursor, *tops;
     Fr *u, *pref, *X, *Y;
 
-    void init() {
+    void init() {                                // after KgHost::check_sizes
+        stage = R1csStage(Ms[0], Ms[1], Ms[2], n_v, sizeof(Fr));
         for (int k = 0; k < 3; k++) nnz_max = std::max(nnz_max, Ms[k]->nnz);
         n_y = std::min(nnz_max, nnz_max / KG_SEG + n_v);
     }
     void carve(Carve& c) {
-        for (int k = 0; k < 3; k++) {
-            rp[k] = c.take(8 * (Ms[k]->n_rows + 1));
-            cl[k] = c.take(4 * Ms[k]->nnz);
-            vl[k] = c.take(sizeof(Fr) * Ms[k]->nnz);
-        }
-        flag = c.n<u32>(1);
+        stage.carve(c);
         u = c.n<Fr>(n_c + n_inst);
         pref = c.n<Fr>(n_c + n_inst);
         cnt = c.n<u32>(n_v + 1);
         st[0] = c.n<u32>(n_v + 1);
         st[1] = c.n<u32>(n_v + 1);
         cursor = c.n<u32>(n_v + 1);
-        tops = c.n<u32>((n_v + 1) / KG_SCAN_TILE + 1);
+        tops = c.n<u32>(scan_u32_tops_len(n_v + 1));
         X = c.n<Fr>(nnz_max);
         Y = c.n<Fr>(n_y);
-    }
-    static hk_status scan(hipStream_t s, const u32* in, u32* out, u32* tops, u32 n) {
-        u32 nt = (n + KG_SCAN_TILE - 1) / KG_SCAN_TILE;
-        hipLaunchKernelGGL((k_kg_scan_tile<0>), dim3(nt), dim3(256), 0, s, in, out, tops, n);
-        hipLaunchKernelGGL((k_kg_scan_tops<0>), dim3(1), dim3(256), 0, s, tops, nt);
-        hipLaunchKernelGGL((k_kg_scan_add<0>), dim3((n + 255) / 256), dim3(256), 0, s, out, (const u32*)tops, n);
-        HK_HIP(hipGetLastError());
-        return HK_OK;
     }
     // kc_d: the call's constants on the device (KC_*)
     hk_status run(Lane* L, const Fr* kc_d, bool zt_zero, Fr* abc) {
         hipStream_t s = L->stream;
         CsrDev D[3];
-        for (int k = 0; k < 3; k++) {
-            HK_TRY(to_device(L, Ms[k]->row_ptr, 8 * (Ms[k]->n_rows + 1), &rp[k]));
-            HK_TRY(to_device(L, Ms[k]->col, 4 * Ms[k]->nnz, &cl[k]));
-            HK_TRY(to_device(L, Ms[k]->val_mont, sizeof(Fr) * Ms[k]->nnz, &vl[k]));
-            D[k] = {(const u64*)rp[k], (const u32*)cl[k], vl[k], Ms[k]->n_rows, Ms[k]->nnz};
-        }
-        for (int k = 0; k < 3; k++) HK_TRY(csr_validate(s, D[k], n_v, flag));
+        HK_TRY(stage.upload(L, D));
         if (zt_zero) return HK_ERR_ARG;                                  // t in the domain (generator.rs:68 never draws one)
         const u32 nu = (u32)(n_c + n_inst), nv = (u32)n_v;
         hipLaunchKernelGGL((k_kg_lagrange<Fr>), dim3((nu / KG_CHUNK + 1 + 63) / 64), dim3(64), 0, s, kc_d, nu, u, pref);
@@ -392,7 +317,7 @@ struct KgQap {
             const u32 nnz = (u32)D[k].nnz;
             HK_HIP(hipMemsetAsync(cnt, 0, sizeof(u32) * (n_v + 1), s));
             if (nnz) hipLaunchKernelGGL((k_kg_col_count<0>), dim3((nnz + 255) / 256), dim3(256), 0, s, D[k].col, nnz, cnt);
-            HK_TRY(scan(s, cnt, st[0], tops, nv + 1));
+            HK_TRY(scan_u32(s, cnt, st[0], tops, nv + 1));
             HK_HIP(hipMemcpyAsync(cursor, st[0], sizeof(u32) * (n_v + 1), hipMemcpyDeviceToDevice, s));
             if (nnz)
                 hipLaunchKernelGGL((k_kg_scatter<Fr>), dim3((nnz + 255) / 256), dim3(256), 0, s, D[k].row_ptr, (u32)n_c, D[k].col,
@@ -405,7 +330,7 @@ struct KgQap {
                 u32* next_start = st[(lvl + 1) & 1];
                 Fr* next = (lvl & 1) ? X : Y;
                 hipLaunchKernelGGL((k_kg_chunk_count<0>), dim3((nv + 1 + 255) / 256), dim3(256), 0, s, start, nv, cnt);
-                HK_TRY(scan(s, cnt, next_start, tops, nv + 1));
+                HK_TRY(scan_u32(s, cnt, next_start, tops, nv + 1));
                 entries = std::min<u64>(entries, entries / KG_SEG + n_v);     // chunks <= entries / KG_SEG + non-empty columns
                 hipLaunchKernelGGL((k_kg_chunk_sum<Fr>), dim3((u32)((entries + 255) / 256)), dim3(256), 0, s, start,
                                    (const u32*)next_start, nv, vals, next);

@@ -205,55 +205,6 @@ __global__ void k_bitrev(Fr* __restrict__ data, u32 logn) {
 }
 
 // ---- R1CS -> QAP --------------------------------------------------------------------------------
-// out[row] = <M_row, z>   (ark-groth16 `evaluate_constraint`), one lane per row of the WHOLE domain vector: rows past
-// the matrix are written too - z[row - n_rows] for the n_copy instance rows of a ("a[start..end] =
-// full_assignment[..num_inputs]"), zero for the rest - so the 3 m-element vectors need no memset before the transforms
-template <class Fr>
-__global__ void k_spmv(const u64* __restrict__ row_ptr, const u32* __restrict__ col,
-                       const Fr* __restrict__ val, const Fr* __restrict__ z, Fr* __restrict__ out,
-                       u32 n_rows, u32 n_copy, u32 m) {
-    u32 row = blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= m) return;
-    if (row >= n_rows) {
-        fr_store(&out[row], row - n_rows < n_copy ? fr_load(&z[row - n_rows]) : Fr::zero());
-        return;
-    }
-    u64 b = row_ptr[row], e = row_ptr[row + 1];
-    Fr acc = Fr::zero();
-    Fr one = Fr::one();
-    for (u64 k = b; k < e; k++) {
-        Fr c = fr_load(&val[k]);
-        Fr x = fr_load(&z[col[k]]);
-        if (!(c == one)) x = Fr::mul(x, c);
-        acc = Fr::add(acc, x);
-    }
-    fr_store(&out[row], acc);
-}
-
-// Structural validation of a CSR matrix before any kernel indexes with it: row_ptr non-decreasing and within nnz,
-// every column < n_cols.  *bad becomes non-zero on the first violation (grid-stride over rows and non-zeros).
-template <int UNUSED>
-__global__ void k_csr_check(const u64* __restrict__ row_ptr, const u32* __restrict__ col, u64 n_rows, u64 nnz,
-                            u32 n_cols, u32* __restrict__ bad) {
-    u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x, stride = (u64)gridDim.x * blockDim.x;
-    u32 f = 0;
-    for (u64 i = t; i < n_rows; i += stride) {
-        u64 b = row_ptr[i], e = row_ptr[i + 1];
-        if (b > e || e > nnz) f = 1;
-    }
-    for (u64 k = t; k < nnz; k += stride)
-        if (col[k] >= n_cols) f = 2;
-    if (t == 0 && (row_ptr[0] != 0 || row_ptr[n_rows] != nnz)) f = 3;
-    if (f) atomicOr(bad, f);
-}
-
-// a[n_c + j] = z[j] for j < n_inst  (witness_map_from_matrices: "a[start..end] = full_assignment[..num_inputs]")
-template <class Fr>
-__global__ void k_copy_inputs(Fr* __restrict__ a, const Fr* __restrict__ z, u32 n_c, u32 n_inst) {
-    u32 j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n_inst) fr_store(&a[n_c + j], fr_load(&z[j]));
-}
-
 // a[i] *= b[i]   (the product of the coset evaluations; everything else of the quotient step is the epilogue
 // of the inverse transform that follows, see QapHost::run)
 template <class Fr>

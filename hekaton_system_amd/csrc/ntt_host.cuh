@@ -4,6 +4,7 @@
 #pragma once
 #include "curve_ops_impl.cuh"
 #include "ntt.cuh"
+#include "csr.cuh"
 
 namespace hk {
 
@@ -236,25 +237,6 @@ hk_status Ops<C>::ntt(hk_ctx* ctx, void* data, unsigned log_m, int inverse, int 
 }
 
 // ---- witness map on device buffers --------------------------------------------------------------------
-struct CsrDev { const u64* row_ptr; const u32* col; const void* val; size_t n_rows, nnz; };
-
-// HK_ERR_ARG unless the (device-resident) matrix is structurally sound for n_cols variables: a malformed matrix
-// must come back as an error (the reference returns an ark error), never as an out-of-bounds device read.
-// `flag`: one u32 of device scratch.  Synchronises `s`.
-static hk_status csr_validate(hipStream_t s, const CsrDev& M, size_t n_cols, u32* flag) {
-    if (n_cols >= ((size_t)1 << 32)) return HK_ERR_ARG;
-    HK_HIP(hipMemsetAsync(flag, 0, sizeof(u32), s));
-    size_t work = M.n_rows > M.nnz ? M.n_rows : M.nnz;
-    u32 blocks = (u32)std::min<size_t>((work + 255) / 256, 2048);
-    if (blocks == 0) blocks = 1;
-    hipLaunchKernelGGL((k_csr_check<0>), dim3(blocks), dim3(256), 0, s, M.row_ptr, M.col, (u64)M.n_rows, (u64)M.nnz,
-                       (u32)n_cols, flag);
-    u32 h = 0;
-    HK_HIP(hipMemcpyAsync(&h, flag, sizeof(u32), hipMemcpyDeviceToHost, s));
-    HK_HIP(hipStreamSynchronize(s));
-    return h ? HK_ERR_ARG : HK_OK;
-}
-
 template <class C>
 struct QapHost {
     typedef typename C::Fr Fr;
@@ -312,8 +294,7 @@ hk_status Ops<C>::witness_map(hk_ctx* ctx, const hk_csr* A, const hk_csr* B, con
                               size_t* m_out) {
     typedef QapHost<C> Q;
     if (A->n_rows != n_c || B->n_rows != n_c || Cm->n_rows != n_c || n_inst > n_v || n_inst < 1) return HK_ERR_ARG;
-    for (auto M : {A, B, Cm})
-        if (!M->row_ptr || (M->nnz && (!M->col || !M->val_mont))) return HK_ERR_ARG;
+    if (!csr_host_ok(A) || !csr_host_ok(B) || !csr_host_ok(Cm)) return HK_ERR_ARG;
     u32 log_m = Q::domain_log(n_c, n_inst);
     if (log_m > C::TWO_ADICITY) return HK_ERR_DOMAIN_TOO_LARGE;
     size_t m = (size_t)1 << log_m;
@@ -321,31 +302,19 @@ hk_status Ops<C>::witness_map(hk_ctx* ctx, const hk_csr* A, const hk_csr* B, con
     if (h_cap < m) return HK_ERR_LEN;
     NttTables* T;
     HK_TRY(NttHost<C>::ensure(ctx, log_m, &T));
+    R1csStage stage(A, B, Cm, n_v, sizeof(Fr));
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const hk_csr* Ms[3] = {A, B, Cm};
-    const void *rp[3], *cl[3], *vl[3], *zd;
-    u32* flag;
+    const void* zd;
     Fr* abc;
     HK_TRY(L->carve([&](Carve& c) {
-        for (int k = 0; k < 3; k++) {
-            rp[k] = c.take(8 * (Ms[k]->n_rows + 1));
-            cl[k] = c.take(4 * Ms[k]->nnz);
-            vl[k] = c.take(sizeof(Fr) * Ms[k]->nnz);
-        }
-        flag = c.n<u32>(1);
+        stage.carve(c);
         zd = c.take(n_v * sizeof(Fr));
         abc = c.n<Fr>(3 * m);
     }));
     CsrDev D[3];
-    for (int k = 0; k < 3; k++) {
-        HK_TRY(to_device(L, Ms[k]->row_ptr, 8 * (Ms[k]->n_rows + 1), &rp[k]));
-        HK_TRY(to_device(L, Ms[k]->col, 4 * Ms[k]->nnz, &cl[k]));
-        HK_TRY(to_device(L, Ms[k]->val_mont, sizeof(Fr) * Ms[k]->nnz, &vl[k]));
-        D[k] = {(const u64*)rp[k], (const u32*)cl[k], vl[k], Ms[k]->n_rows, Ms[k]->nnz};
-    }
-    for (int k = 0; k < 3; k++) HK_TRY(csr_validate(L->stream, D[k], n_v, flag));
+    HK_TRY(stage.upload(L, D));
     HK_TRY(to_device(L, z, n_v * sizeof(Fr), &zd));
     HK_TRY(Q::run(L->stream, T, D[0], D[1], D[2], n_inst, n_c, (const Fr*)zd, abc, log_m));
     HK_TRY(NttHost<C>::bitrev(L->stream, abc, log_m));         // API returns natural order

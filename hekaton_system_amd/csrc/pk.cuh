@@ -3,6 +3,7 @@
 // Ops<C>::pk_free (hk_pk_free).
 #pragma once
 #include "ntt_host.cuh"
+#include "csr.cuh"
 
 namespace hk {
 
@@ -255,13 +256,13 @@ hk_status Ops<C>::pk_upload(hk_ctx* ctx, const hk_pk_desc* d, hk_pk** out) {
         size_t m = (size_t)1 << pk->log_m;
         if (d->h_len + 1 != m) return fail(HK_ERR_LEN);                 // prover.rs:128 assert
         const hk_csr* Ms[3] = {d->A, d->B, d->C};
+        if (!csr_host_ok(d->A) || !csr_host_ok(d->B) || !csr_host_ok(d->C)) return fail(HK_ERR_ARG);
         for (int i = 0; i < 3; i++) {
             void *rp, *cl, *vl;
             PK_HIP(hipMalloc(&rp, 8 * (Ms[i]->n_rows + 1))); pk->owned.push_back(rp);
             PK_HIP(hipMalloc(&cl, 4 * Ms[i]->nnz + 16)); pk->owned.push_back(cl);
             PK_HIP(hipMalloc(&vl, sizeof(Fr) * Ms[i]->nnz + 16)); pk->owned.push_back(vl);
             PK_HIP(hipMemcpy(rp, Ms[i]->row_ptr, 8 * (Ms[i]->n_rows + 1), h2d_kind(Ms[i]->row_ptr)));
-            if (!Ms[i]->row_ptr || (Ms[i]->nnz && (!Ms[i]->col || !Ms[i]->val_mont))) return fail(HK_ERR_ARG);
             if (Ms[i]->nnz) {
                 PK_HIP(hipMemcpy(cl, Ms[i]->col, 4 * Ms[i]->nnz, h2d_kind(Ms[i]->col)));
                 PK_HIP(hipMemcpy(vl, Ms[i]->val_mont, sizeof(Fr) * Ms[i]->nnz, h2d_kind(Ms[i]->val_mont)));
@@ -274,7 +275,7 @@ hk_status Ops<C>::pk_upload(hk_ctx* ctx, const hk_pk_desc* d, hk_pk** out) {
             // not an out-of-bounds read in every later hk_prove
             void* flag = nullptr;
             PK_HIP(hipMalloc(&flag, 256)); pk->owned.push_back(flag);
-            for (int i = 0; i < 3; i++) PK_TRY(csr_validate(s0, pk->csr[i], n_v, (u32*)flag));
+            PK_TRY(r1cs_validate(s0, pk->csr, n_v, (u32*)flag));
         }
         pk->plan_h = make_plan(m);
         if ((st = pk_alloc_table(pk->owned, pk->bytes, pk->plan_h.F, m, &pk->h_tab)) != HK_OK) return fail(st);

@@ -3,16 +3,18 @@
 // distributed-prover/src/subcircuit_circuit.rs:311-399) on assignments that never exist on the host.
 //
 //   rows     k_r1cs_rows: one lane per (row, assignment): the three dot products <A_i,z>, <B_i,z>, <C_i,z> in one pass
-//            (k_spmv's loop), the test a b == c on canonical values, and the verdicts of 64 consecutive rows leave the wave as
+//            (csr_dot), the test a b == c on canonical values, and the verdicts of 64 consecutive rows leave the wave as
 //            one __ballot word that lane 0 stores into the assignment's bitmap of ceil(n_rows / 64) u64.  No m-element
 //            vectors, no transforms.
-//   compact  k_r1cs_compact: one workgroup per assignment walks its bitmap: popcounts, an exclusive scan in LDS (the shape of
-//            k_kg_scan_tile), n_bad, first_bad and the failing rows of rank < cap, then the 0xFFFFFFFF padding.  The rank
+//   compact  k_r1cs_compact: one workgroup per assignment walks its bitmap: popcounts, an exclusive scan in LDS
+//            (wg_scan_u32), n_bad, first_bad and the failing rows of rank < cap, then the 0xFFFFFFFF padding.  The rank
 //            of a failing row is the number of set bits in front of it: no atomics, nothing depends on an arrival order.
 //   vals     k_r1cs_vals (only with bad_vals): one lane per (assignment, slot) recomputes the three sides of its listed row and
 //            stores them canonical; empty slots store zeros.
 #pragma once
 #include "pk.cuh"
+#include "csr.cuh"
+#include "scan.cuh"
 
 namespace hk {
 
@@ -21,20 +23,6 @@ constexpr u32 R1_TILE_WORDS = 256 * R1_WORDS_PER_LANE;                 // = 32 7
 constexpr u32 R1_NONE = 0xffffffffu;
 
 #if defined(__HIPCC__)
-
-// <M_row, z> over the non-zeros [b, e) of the row, k_spmv's loop; empty (a lane past n_rows): zero
-template <class Fr>
-__device__ __forceinline__ Fr r1_dot(const u32* __restrict__ col, const Fr* __restrict__ val, u64 b, u64 e, const Fr* __restrict__ z) {
-    const Fr one = Fr::one();
-    Fr acc = Fr::zero();
-    HK_NOUNROLL for (u64 k = b; k < e; k++) {
-        const Fr c = fr_load(&val[k]);
-        Fr x = fr_load(&z[col[k]]);
-        if (!(c == one)) x = Fr::mul(x, c);
-        acc = Fr::add(acc, x);
-    }
-    return acc;
-}
 
 // bitmap[y words + w] bit l = row 64 w + l of assignment y fails.  Lanes past n_rows run empty rows and vote 0: every lane of
 // a wave reaches the ballot.  grid = (ceil(n_rows / 256), batch).
@@ -48,9 +36,9 @@ k_r1cs_rows(const u64* __restrict__ rpa, const u32* __restrict__ ca, const Fr* _
     const bool valid = row < n_rows;
     const u32 rr = valid ? row : 0u;                                   // row_ptr has n_rows + 1 >= 1 entries
     const Fr* zb = z + (size_t)blockIdx.y * n_v;
-    const Fr a = r1_dot<Fr>(ca, va, rpa[rr], valid ? rpa[rr + 1] : rpa[rr], zb);
-    const Fr b = r1_dot<Fr>(cb, vb, rpb[rr], valid ? rpb[rr + 1] : rpb[rr], zb);
-    const Fr c = r1_dot<Fr>(cc, vc, rpc[rr], valid ? rpc[rr + 1] : rpc[rr], zb);
+    const Fr a = csr_dot<Fr>(ca, va, rpa[rr], valid ? rpa[rr + 1] : rpa[rr], zb);
+    const Fr b = csr_dot<Fr>(cb, vb, rpb[rr], valid ? rpb[rr + 1] : rpb[rr], zb);
+    const Fr c = csr_dot<Fr>(cc, vc, rpc[rr], valid ? rpc[rr + 1] : rpc[rr], zb);
     const bool bad = valid && !(Fr::mul(a, b) == c);                   // operator== compares canonical representatives
     const u64 m = __ballot(bad);
     const u32 w = row >> 6;
@@ -77,15 +65,7 @@ k_r1cs_compact(const u64* __restrict__ bitmap, u32 words, R1Verdict* __restrict_
             v[j] = w0 + j < words ? bm[w0 + j] : 0ull;
             sum += (u32)__popcll(v[j]);
         }
-        s[tid] = sum;
-        __syncthreads();
-        HK_NOUNROLL for (u32 off = 1; off < 256; off <<= 1) {
-            const u32 x = tid >= off ? s[tid - off] : 0u;
-            __syncthreads();
-            s[tid] += x;
-            __syncthreads();
-        }
-        u32 rank = carry + s[tid] - sum;
+        u32 rank = carry + wg_scan_u32(s, tid, sum) - sum;
         const u32 total = s[255];
         HK_UNROLL for (u32 j = 0; j < R1_WORDS_PER_LANE; j++) {
             u64 m = v[j];
@@ -122,9 +102,9 @@ k_r1cs_vals(const u64* __restrict__ rpa, const u32* __restrict__ ca, const Fr* _
     const bool listed = live && row != R1_NONE;
     const u32 rr = listed ? row : 0u;
     const Fr* zb = z + (size_t)(gg / cap) * n_v;
-    const Fr a = r1_dot<Fr>(ca, va, rpa[rr], listed ? rpa[rr + 1] : rpa[rr], zb);
-    const Fr b = r1_dot<Fr>(cb, vb, rpb[rr], listed ? rpb[rr + 1] : rpb[rr], zb);
-    const Fr c = r1_dot<Fr>(cc, vc, rpc[rr], listed ? rpc[rr + 1] : rpc[rr], zb);
+    const Fr a = csr_dot<Fr>(ca, va, rpa[rr], listed ? rpa[rr + 1] : rpa[rr], zb);
+    const Fr b = csr_dot<Fr>(cb, vb, rpb[rr], listed ? rpb[rr + 1] : rpb[rr], zb);
+    const Fr c = csr_dot<Fr>(cc, vc, rpc[rr], listed ? rpc[rr + 1] : rpc[rr], zb);
     if (live) {                                                        // only the stores are guarded
         fr_store(&vals[(size_t)g * 3 + 0], a);
         fr_store(&vals[(size_t)g * 3 + 1], b);
@@ -202,40 +182,20 @@ template <class C>
 hk_status Ops<C>::r1cs_check(hk_ctx* ctx, const hk_csr* A, const hk_csr* B, const hk_csr* Cm, const void* z, size_t n_v, size_t batch,
                              hk_r1cs_verdict* verdicts, uint32_t* bad_rows, void* bad_vals, size_t cap) {
     if (A->n_rows != B->n_rows || A->n_rows != Cm->n_rows) return HK_ERR_ARG;
-    const hk_csr* Ms[3] = {A, B, Cm};
-    for (auto M : Ms)
-        if (!M->row_ptr || (M->nnz && (!M->col || !M->val_mont))) return HK_ERR_ARG;
+    if (!csr_host_ok(A) || !csr_host_ok(B) || !csr_host_ok(Cm)) return HK_ERR_ARG;
     bool done;
     HK_TRY(r1cs_check_args(A->n_rows, n_v, batch, z, verdicts, bad_rows, bad_vals, cap, &done));
     if (done) return HK_OK;
     R1csRun<C> run(A->n_rows, n_v, batch, bad_rows, bad_vals, cap);
-    size_t staged[3][3];
-    for (int k = 0; k < 3; k++) {
-        staged[k][0] = is_device_ptr(Ms[k]->row_ptr) ? 0 : 8 * (Ms[k]->n_rows + 1);
-        staged[k][1] = is_device_ptr(Ms[k]->col) ? 0 : 4 * Ms[k]->nnz;
-        staged[k][2] = is_device_ptr(Ms[k]->val_mont) ? 0 : sizeof(Fr) * Ms[k]->nnz;
-    }
+    R1csStage stage(A, B, Cm, n_v, sizeof(Fr));
     const size_t z_bytes = batch * n_v * sizeof(Fr), z_staged = is_device_ptr(z) ? 0 : z_bytes;
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void *p[3][3], *zd;
-    u32* flag;
-    HK_TRY(L->carve([&](Carve& c) {
-        for (int k = 0; k < 3; k++)
-            for (int j = 0; j < 3; j++) p[k][j] = c.take(staged[k][j]);
-        flag = c.n<u32>(1);
-        zd = c.take(z_staged);
-        run.carve(c);
-    }));
+    const void* zd;
+    HK_TRY(L->carve([&](Carve& c) { stage.carve(c); zd = c.take(z_staged); run.carve(c); }));
     CsrDev D[3];
-    for (int k = 0; k < 3; k++) {
-        HK_TRY(to_device(L, Ms[k]->row_ptr, 8 * (Ms[k]->n_rows + 1), &p[k][0]));
-        HK_TRY(to_device(L, Ms[k]->col, 4 * Ms[k]->nnz, &p[k][1]));
-        HK_TRY(to_device(L, Ms[k]->val_mont, sizeof(Fr) * Ms[k]->nnz, &p[k][2]));
-        D[k] = {(const u64*)p[k][0], (const u32*)p[k][1], p[k][2], Ms[k]->n_rows, Ms[k]->nnz};
-    }
-    for (int k = 0; k < 3; k++) HK_TRY(csr_validate(L->stream, D[k], n_v, flag));
+    HK_TRY(stage.upload(L, D));
     HK_TRY(to_device(L, z, z_bytes, &zd));
     HK_TRY(run.run(L->stream, D, (const Fr*)zd, verdicts, bad_rows, bad_vals));
     return L->settle();

@@ -15,7 +15,8 @@
 // A trace of at most TS_TILE entries runs keys, every pass and the gather in one launch of one workgroup (k_ts_small).
 #pragma once
 #include "curve_ops_impl.cuh"
-#include "keygen.cuh"
+#include "ntt.cuh"           // fr_load
+#include "scan.cuh"
 
 namespace hk {
 
@@ -135,15 +136,7 @@ __device__ __forceinline__ void ts_tile_pass(const u32* kin, const u32* iin, u32
         start = gbase[(size_t)tid * n_tiles + tile];
     } else {
         const u32 tot = c0 + c1 + c2 + c3;
-        sc[tid] = tot;
-        __syncthreads();
-        HK_NOUNROLL for (u32 off = 1; off < 256; off <<= 1) {
-            u32 x = tid >= off ? sc[tid - off] : 0u;
-            __syncthreads();
-            sc[tid] += x;
-            __syncthreads();
-        }
-        start = sc[tid] - tot;
+        start = wg_scan_u32(sc, tid, tot) - tot;       // gbase is the kernel's argument: the branch is uniform
     }
     woff[tid] = start;
     woff[256 + tid] = start + c0;
@@ -262,7 +255,7 @@ hk_status Ops<C>::trace_sort(hk_ctx* ctx, uint32_t entry_fields, const void* tim
         for (int k = 0; k < 2; k++) idx[k] = c.n<u32>(n + (k ? n : 0));     // the second one: + the small form's perm
         hist = c.n<u32>(n_hist);
         gbase = c.n<u32>(n_hist);
-        tops = c.n<u32>(n_hist / KG_SCAN_TILE + 1);
+        tops = c.n<u32>(scan_u32_tops_len(n_hist));
         flags = c.n<u32>(TS_FLAG_WORDS);
         sorted = c.n<Fr>(n * K);
     }));
@@ -298,10 +291,7 @@ hk_status Ops<C>::trace_sort(hk_ctx* ctx, uint32_t entry_fields, const void* tim
             if ((((fl[1 + word] & ~fl[4 + word]) >> shift) & 255u) == 0) continue;        // this digit is the same in every key
             const u32 *kin = keys[cur], *iin = idx[cur];
             hipLaunchKernelGGL((k_ts_hist<0>), dim3(n_tiles), dim3(256), 0, s, kin + (size_t)word * n, nn, shift, n_tiles, hist);
-            const u32 nt = (n_hist + KG_SCAN_TILE - 1) / KG_SCAN_TILE;
-            hipLaunchKernelGGL((k_kg_scan_tile<0>), dim3(nt), dim3(256), 0, s, (const u32*)hist, gbase, tops, n_hist);
-            hipLaunchKernelGGL((k_kg_scan_tops<0>), dim3(1), dim3(256), 0, s, tops, nt);
-            hipLaunchKernelGGL((k_kg_scan_add<0>), dim3((n_hist + 255) / 256), dim3(256), 0, s, gbase, (const u32*)tops, n_hist);
+            HK_TRY(scan_u32(s, hist, gbase, tops, n_hist));
             if (W == 2)
                 hipLaunchKernelGGL((k_ts_scatter<2>), dim3(n_tiles), dim3(256), 0, s, kin, iin, keys[cur ^ 1], idx[cur ^ 1], nn, word,
                                    shift, (const u32*)gbase, n_tiles);
