@@ -92,6 +92,10 @@ class hk_stage1_desc(C.Structure):            # include/hekaton.h
                 ("inst_col0", C.c_uint32), ("col0", C.c_uint32), ("pos_col0", C.c_uint32)]
 
 
+class hk_sha_tree_out(C.Structure):           # include/hekaton.h
+    _fields_ = [("digests_out", C.c_void_p), ("time_entries_mont_out", C.c_void_p), ("sha_root_mont_out", C.c_void_p)]
+
+
 class hk_r1cs_verdict(C.Structure):           # include/hekaton.h
     _fields_ = [("n_bad", C.c_uint32), ("first_bad", C.c_uint32)]
 
@@ -116,7 +120,8 @@ EXPORTS = ["hk_status_str", "hk_version", "hk_ctx_create", "hk_ctx_destroy", "hk
            "hk_points_lincomb_g1", "hk_points_lincomb_g2", "hk_points_fold_g2", "hk_points_fold_g1", "hk_points_fold_many_g1", "hk_points_fold_many_g2", "hk_pairing_pairs", "hk_keccak_f1600", "hk_assignment_from_bits", "hk_wprog_upload", "hk_wprog_free", "hk_wprog_run", "hk_gt_pow", "hk_fq12_pow", "hk_gt_pow_prod", "hk_poseidon_path", "hk_assignment_scatter", "hk_commit_batch",
            "hk_prove_batch", "hk_vk_prepare", "hk_vk_free", "hk_vk_alpha_beta", "hk_verify_batch", "hk_points_check_g1",
            "hk_points_check_g2", "hk_qap_eval", "hk_keygen", "hk_exec_tree", "hk_stage1_witness",
-           "hk_trace_sort", "hk_stage0_witness", "hk_r1cs_check", "hk_pk_r1cs_check"]
+           "hk_trace_sort", "hk_stage0_witness", "hk_r1cs_check", "hk_pk_r1cs_check",
+           "hk_sha_tree", "hk_sha_tree_inputs"]
 
 HK_VERIFY_CHECK_POINTS = 1
 VERDICT_REJECT, VERDICT_ACCEPT, VERDICT_BAD_POINT = 0, 1, 2
@@ -211,6 +216,8 @@ def load():
     lib.hk_stage0_witness.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, sz, vp]
     lib.hk_r1cs_check.argtypes = [vp, C.POINTER(hk_csr), C.POINTER(hk_csr), C.POINTER(hk_csr), vp, sz, sz, vp, vp, vp, sz]
     lib.hk_pk_r1cs_check.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, sz]
+    lib.hk_sha_tree.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(hk_sha_tree_out)]
+    lib.hk_sha_tree_inputs.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, sz, vp]
     _lib = lib
     return lib
 
@@ -765,6 +772,46 @@ class Context:
               "hk_stage0_witness")
         return w_out
 
+    def sha_tree(self, leaves, n_sub, ns, n_portals, device_out=False):
+        """hk_sha_tree: the data tree and the time-ordered trace of a big-merkle job (tree_hash_circuit.rs:313-470) from its
+        leaves.  leaves: n_sub / 2 x 64 bytes - a list of bytes, a uint8 array or a DeviceBuffer.  Returns (digests [n_sub x
+        32 B, subcircuit order, padding last], time_entries [n_sub x n_portals x 2 Fr, Montgomery: what trace_sort / exec_tree
+        / stage0_witness take], sha_root [1 Fr]) as uint8 arrays, or as DeviceBuffers when device_out is set."""
+        n, k, fr = int(n_sub), int(n_portals), self.fr_bytes
+        if isinstance(leaves, (list, tuple)):
+            leaves = np.frombuffer(b"".join(leaves), np.uint8)
+        src = leaves if isinstance(leaves, DeviceBuffer) else np.ascontiguousarray(leaves, dtype=np.uint8).reshape(-1)
+        sizes = [32 * n, 2 * n * k * fr, fr]
+        outs = [DeviceBuffer(self, max(b, 1)) if device_out else np.zeros(b, dtype=np.uint8) for b in sizes]
+        o = hk_sha_tree_out(*[ptr(x) for x in outs])
+        try:
+            check(self.lib.hk_sha_tree(self.handle, ptr(src), n, int(ns), k, C.byref(o)), "hk_sha_tree")
+        except HekatonError:
+            if device_out:
+                for x in outs:
+                    x.free()
+            raise
+        return tuple(outs)
+
+    def sha_tree_inputs(self, leaves, digests, n_sub, n_inputs, sub_index, device_out=False):
+        """hk_sha_tree_inputs: the word-program inputs (sha_circuit.program_inputs) of the subcircuits `sub_index` of one
+        kind - n_inputs 16: leaves and the padding subcircuit, from `leaves`; 54: parents and the root, from `digests`
+        (sha_tree's).  leaves / digests: uint8 arrays, DeviceBuffers, or None for the one the kind does not read.  Returns
+        uint32 (len(sub_index), n_inputs), or a DeviceBuffer of it when device_out is set."""
+        keep = [x if x is None or isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
+                for x in (leaves, digests)]
+        sub_index = np.ascontiguousarray(sub_index, dtype=np.uint32)
+        batch, k = sub_index.size, int(n_inputs)
+        out = DeviceBuffer(self, max(4 * batch * k, 1)) if device_out else np.zeros((batch, k), dtype=np.uint32)
+        try:
+            check(self.lib.hk_sha_tree_inputs(self.handle, ptr(keep[0]), ptr(keep[1]), int(n_sub), k,
+                                              sub_index.ctypes.data if batch else None, batch, ptr(out)), "hk_sha_tree_inputs")
+        except HekatonError:
+            if device_out:
+                out.free()
+            raise
+        return out
+
     def _r1cs_call(self, fn, head, z, n_v, batch, cap, want_vals):
         """The shared tail of Context.r1cs_check / DevicePk.r1cs_check: `fn(*head, z, n_v, batch, verdicts, rows, vals, cap)`."""
         fr, batch, cap = self.fr_bytes, int(batch), int(cap)
@@ -865,15 +912,19 @@ class WordProgram:
     def __init__(self, ctx, handle, n_v, n_inputs):
         self.ctx, self.handle, self.n_v, self.n_inputs = ctx, handle, n_v, n_inputs
 
-    def run(self, inputs, full_cols, full_vals, out=None):
-        """inputs: uint32 (batch, n_inputs); full_cols: uint32 (k); full_vals: Montgomery bytes (batch, k * fr_bytes).
-        Returns a DeviceBuffer holding batch x n_v Fr (or fills `out`)."""
-        inputs = np.ascontiguousarray(inputs, dtype=np.uint32)
-        batch = inputs.shape[0]
+    def run(self, inputs, full_cols, full_vals, out=None, batch=None):
+        """inputs: uint32 (batch, n_inputs), or a DeviceBuffer of it with an explicit batch=; full_cols: uint32 (k);
+        full_vals: Montgomery bytes (batch, k * fr_bytes).  Returns a DeviceBuffer holding batch x n_v Fr (or fills `out`)."""
+        if isinstance(inputs, DeviceBuffer):
+            assert batch is not None and inputs.nbytes >= 4 * int(batch) * self.n_inputs, "a DeviceBuffer of inputs needs batch="
+            batch, in_ptr = int(batch), inputs.ptr
+        else:
+            inputs = np.ascontiguousarray(inputs, dtype=np.uint32)
+            batch, in_ptr = inputs.shape[0], inputs.ctypes.data
         cols = np.ascontiguousarray(full_cols, dtype=np.uint32)
         vals = np.ascontiguousarray(full_vals, dtype=np.uint8)
         buf = out if out is not None else DeviceBuffer(self.ctx, batch * self.n_v * self.ctx.fr_bytes)
-        check(self.ctx.lib.hk_wprog_run(self.ctx.handle, self.handle, inputs.ctypes.data, batch,
+        check(self.ctx.lib.hk_wprog_run(self.ctx.handle, self.handle, in_ptr, batch,
                                         cols.ctypes.data if cols.size else None, vals.ctypes.data if cols.size else None,
                                         cols.size, buf.ptr), "hk_wprog_run")
         return buf

@@ -192,6 +192,9 @@ struct Ops final : CurveOps {
     hk_status r1cs_check(hk_ctx*, const hk_csr*, const hk_csr*, const hk_csr*, const void*, size_t, size_t, hk_r1cs_verdict*,
                          uint32_t*, void*, size_t) override;
     hk_status pk_r1cs_check(hk_ctx*, const hk_pk*, const void*, size_t, size_t, hk_r1cs_verdict*, uint32_t*, void*, size_t) override;
+    // sha_tree.cuh
+    hk_status sha_tree(hk_ctx*, const void*, uint32_t, uint32_t, uint32_t, const hk_sha_tree_out*) override;
+    hk_status sha_tree_inputs(hk_ctx*, const void*, const void*, uint32_t, uint32_t, const uint32_t*, size_t, uint32_t*) override;
 };
 
 }  // namespace hk

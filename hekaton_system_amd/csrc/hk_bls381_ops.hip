@@ -11,6 +11,7 @@
 #include "stage1.cuh"
 #include "trace_sort.cuh"
 #include "r1cs_check.cuh"
+#include "sha_tree.cuh"
 namespace hk {
 extern template struct MsmRun<CurveBls381::Fq>;
 extern template struct MsmRun<CurveBls381::Fq2>;

@@ -694,6 +694,15 @@ hk_status hk_pk_r1cs_check(hk_ctx* ctx, const hk_pk* pk, const void* z_mont, siz
     if (!ctx || !pk) return HK_ERR_ARG;
     return ctx->ops->pk_r1cs_check(ctx, pk, z_mont, n_v, batch, verdicts, bad_rows, bad_vals, cap);
 }
+hk_status hk_sha_tree(hk_ctx* ctx, const void* leaves, uint32_t n_sub, uint32_t ns, uint32_t n_portals, const hk_sha_tree_out* out) {
+    if (!ctx || !leaves || !out) return HK_ERR_ARG;
+    return ctx->ops->sha_tree(ctx, leaves, n_sub, ns, n_portals, out);
+}
+hk_status hk_sha_tree_inputs(hk_ctx* ctx, const void* leaves, const void* digests, uint32_t n_sub, uint32_t n_inputs,
+                             const uint32_t* sub_index, size_t batch, uint32_t* inputs_out) {
+    if (!ctx) return HK_ERR_ARG;
+    return ctx->ops->sha_tree_inputs(ctx, leaves, digests, n_sub, n_inputs, sub_index, batch, inputs_out);
+}
 
 }  // extern "C"
 

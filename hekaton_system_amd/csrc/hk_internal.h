@@ -240,6 +240,11 @@ struct CurveOps {
                                  hk_r1cs_verdict* verdicts, uint32_t* bad_rows, void* bad_vals, size_t cap) = 0;
     virtual hk_status pk_r1cs_check(hk_ctx*, const hk_pk*, const void* z, size_t n_v, size_t batch, hk_r1cs_verdict* verdicts,
                                     uint32_t* bad_rows, void* bad_vals, size_t cap) = 0;
+    // sha_tree.cuh
+    virtual hk_status sha_tree(hk_ctx*, const void* leaves, uint32_t n_sub, uint32_t ns, uint32_t n_portals,
+                               const hk_sha_tree_out* out) = 0;
+    virtual hk_status sha_tree_inputs(hk_ctx*, const void* leaves, const void* digests, uint32_t n_sub, uint32_t n_inputs,
+                                      const uint32_t* sub_index, size_t batch, uint32_t* inputs_out) = 0;
 
 protected:
     CurveOps(size_t fr, size_t fq, size_t g1, size_t g2, size_t gt)

@@ -894,22 +894,8 @@ class ShaMerkleJob:
         """Without challenges only the stage-0 side exists (traces, `stage0_ints`); `set_challenges` - called by the
         coordinator once the stage-0 commitments are in (coordinator.rs:315-352) - adds the running evaluations."""
         n = n_subcircuits
-        assert n >= 4 and n & (n - 1) == 0 and len(leaves) == n // 2 and n_portals >= 3
-        self.curve, self.n, self.ns, self.np_ = curve, n, ns, n_portals
-        self.r = CURVE_PARAMS[curve]["r"]
+        self._set_shape(curve, n, ns, n_portals, leaves)
         nl = n // 2
-        # node j (subcircuit order) -> children; hashes
-        self.kind = ["leaf"] * nl + ["parent"] * (n - 2 - nl) + ["root", "padding"]
-        self.children = {}
-        level_start, width, j = 0, nl, nl
-        while width > 1:
-            for k in range(width // 2):
-                self.children[j] = (level_start + 2 * k, level_start + 2 * k + 1)
-                j += 1
-            level_start += width
-            width //= 2
-        assert j == n - 1
-        self.leaves = list(leaves)
         self.digest = [None] * n
         for i in range(nl):
             self.digest[i] = iterated_sha256(self.leaves[i], ns)
@@ -918,8 +904,6 @@ class ShaMerkleJob:
             self.digest[jj] = iterated_sha256(self.digest[l][:INNER_HASH_SIZE] + self.digest[rr][:INNER_HASH_SIZE], ns)
         self.digest[n - 1] = iterated_sha256(bytes(64), ns)
         self.sha_root = node_hash_field(self.digest[n - 2])            # the data tree's root hash (a witness of the root class)
-        self.root = None                                               # the EXECUTION tree's root: known after `set_challenges`
-        self.depth = n.bit_length() - 1
         val = lambda jj: node_hash_field(self.digest[jj])
         # time-ordered trace
         self.time = []
@@ -942,6 +926,47 @@ class ShaMerkleJob:
         if entry_chal is not None:
             self.set_challenges(entry_chal, tr_chal)
 
+    def _set_shape(self, curve, n, ns, n_portals, leaves):
+        """What does not depend on a hash: the parameters, the kind of every subcircuit and node j -> children."""
+        assert n >= 4 and n & (n - 1) == 0 and len(leaves) == n // 2 and n_portals >= 3
+        self.curve, self.n, self.ns, self.np_ = curve, n, ns, n_portals
+        self.r = CURVE_PARAMS[curve]["r"]
+        nl = n // 2
+        self.kind = ["leaf"] * nl + ["parent"] * (n - 2 - nl) + ["root", "padding"]
+        self.children = {}
+        level_start, width, j = 0, nl, nl
+        while width > 1:
+            for k in range(width // 2):
+                self.children[j] = (level_start + 2 * k, level_start + 2 * k + 1)
+                j += 1
+            level_start += width
+            width //= 2
+        assert j == n - 1
+        self.leaves = list(leaves)
+        self.root = None                                               # the EXECUTION tree's root: known after `set_challenges`
+        self.depth = n.bit_length() - 1
+
+    @classmethod
+    def on_device(cls, ctx, curve, n_subcircuits, ns, n_portals, leaves):
+        """The job from its leaves with everything hashed on the device (hk_sha_tree): the same `kind`, `children`,
+        `class_of`, `make_class`, `depth`, and `tree`, a `TreeDevice` (leaves, digests, the time-ordered trace and sha_root as
+        DeviceBuffers) in place of the host `time` / `addr` / `digest`, which are never built.  `stage0_device` adopts the
+        tree's trace; `set_challenges(e, t, ctx)` only records the challenges - `stage1_device(ctx, traces=...)` does the
+        rest.  `free()` releases the tree."""
+        job = cls.__new__(cls)
+        job._set_shape(curve, n_subcircuits, ns, n_portals, leaves)
+        job.entry_chal = job.tr_chal = None
+        job.tree = TreeDevice(job, ctx)
+        return job
+
+    def tree_device(self, ctx):
+        """This job's leaves hashed on the device: a `TreeDevice` (the caller frees it)."""
+        return TreeDevice(self, ctx)
+
+    def free(self):
+        if isinstance(getattr(self, "tree", None), TreeDevice):
+            self.tree.free()
+
     def stage0_ints(self, idx):
         """The subcircuit's stage-0 witness (what `process_stage0_request` commits to, worker.rs:91-146): (addr, val) of
         its time-ordered then its address-ordered entries, the variable order of `ShaMerkleSubcircuit._program`."""
@@ -952,6 +977,8 @@ class ShaMerkleJob:
         capi.Context of the job's curve): evaluations, tree and root come from one hk_exec_tree call instead."""
         n = self.n
         self.entry_chal, self.tr_chal = entry_chal % self.r, tr_chal % self.r
+        if isinstance(getattr(self, "tree", None), TreeDevice):
+            return                                                 # an on_device job: stage1_device computes from them
         if ctx is not None:
             return self._set_challenges_device(ctx)
         r, ech, tr = self.r, self.entry_chal, self.tr_chal
@@ -1005,7 +1032,8 @@ class ShaMerkleJob:
         """The job's stage-0 side on the device: the time-ordered trace uploaded once, the address-ordered one made from it
         by hk_trace_sort.  Needs no challenges; the job itself (`time`, `addr`) is left as it is.  Returns a `Stage0Device`:
         `.rows(members)` for `ProvingKey.commit_batch`, `.traces` for `Stage1Device(job, ctx, traces=...)`, `.free()`."""
-        return Stage0Device(self, ctx)
+        tree = getattr(self, "tree", None)
+        return Stage0Device(self, ctx, tree=tree if isinstance(tree, TreeDevice) else None)
 
     def class_of(self, idx):
         """(kind, first, last) - the proving-key class a subcircuit needs (5 classes, tree_hash_circuit.rs:192-216)."""
@@ -1028,18 +1056,54 @@ class ShaMerkleJob:
         return w
 
 
-class Stage0Device:
-    """What `ShaMerkleJob.stage0_device` returns: `offsets`, and `traces = [time, addr]` as DeviceBuffers - the time-ordered
-    trace uploaded once, the address-ordered one sorted from it on the device (hk_trace_sort).  `rows(members)` cuts the
-    stage-0 witnesses of any subcircuits out of them (hk_stage0_witness) for `ProvingKey.commit_batch`; the traces are what
-    hk_exec_tree and hk_stage1_witness read next (`Stage1Device(job, ctx, traces=dev0.traces)`)."""
+class TreeDevice:
+    """The head of a job on the device (hk_sha_tree): `leaves` (n / 2 x 64 B), `digests` (n x 32 B, subcircuit order),
+    `time` (the flattened time-ordered trace, n x n_portals x 2 Fr) and `sha_root` (1 Fr) as DeviceBuffers.  `inputs(circ,
+    members)` makes the word-program inputs of members of the class `circ` (hk_sha_tree_inputs) for `WordProgram.run(...,
+    batch=len(members))`; `Stage0Device(job, ctx, tree=...)` reads `time`; `Stage1Device.fill(..., sha_root=tree.sha_root)`
+    the root."""
 
     def __init__(self, job, ctx):
         from .capi import DeviceBuffer
-        fc = FrCodec(job.curve)
+        self.job, self.ctx = job, ctx
+        self.leaves = DeviceBuffer.from_host(ctx, np.frombuffer(b"".join(job.leaves), np.uint8))
+        self.digests = self.time = self.sha_root = None
+        try:
+            self.digests, self.time, self.sha_root = ctx.sha_tree(self.leaves, job.n, job.ns, job.np_, device_out=True)
+        except Exception:
+            self.free()
+            raise
+
+    def inputs(self, circ, members):
+        """DeviceBuffer of len(members) x circ.n_inputs uint32: row b = `program_inputs` of subcircuit members[b].  The
+        caller frees it."""
+        n_inputs = 16 if circ.kind in ("leaf", "padding") else 2 * INNER_HASH_SIZE
+        return self.ctx.sha_tree_inputs(self.leaves, self.digests, self.job.n, n_inputs, members, device_out=True)
+
+    def free(self):
+        for x in (self.leaves, self.digests, self.time, self.sha_root):
+            if x is not None:
+                x.free()
+        self.leaves = self.digests = self.time = self.sha_root = None
+
+
+class Stage0Device:
+    """What `ShaMerkleJob.stage0_device` returns: `offsets`, and `traces = [time, addr]` as DeviceBuffers - the time-ordered
+    trace uploaded once (or, with tree=, the `TreeDevice`'s, which stays its owner's), the address-ordered one sorted from
+    it on the device (hk_trace_sort).  `rows(members)` cuts the stage-0 witnesses of any subcircuits out of them
+    (hk_stage0_witness) for `ProvingKey.commit_batch`; the traces are what hk_exec_tree and hk_stage1_witness read next
+    (`Stage1Device(job, ctx, traces=dev0.traces)`)."""
+
+    def __init__(self, job, ctx, tree=None):
+        from .capi import DeviceBuffer
         self.job, self.ctx = job, ctx
         self.offsets = np.arange(job.n + 1, dtype=np.uint32) * job.np_
-        time = DeviceBuffer.from_host(ctx, fc.enc([x for ops in job.time for e in ops for x in e]))
+        self._adopted = tree is not None
+        if tree is not None:
+            time = tree.time
+        else:
+            fc = FrCodec(job.curve)
+            time = DeviceBuffer.from_host(ctx, fc.enc([x for ops in job.time for e in ops for x in e]))
         self.traces = [time]
         try:
             self.traces.append(ctx.trace_sort(2, time, job.n * job.np_, device_out=True))
@@ -1061,7 +1125,7 @@ class Stage0Device:
         return w
 
     def free(self):
-        for x in self.traces:
+        for x in self.traces[1 if self._adopted else 0:]:
             x.free()
         self.traces = []
 
@@ -1082,7 +1146,8 @@ class Stage1Device:
     siblings, root) as DeviceBuffers, from which `fill` writes the challenge-dependent columns of a class's assignments
     (hk_stage1_witness) without a host value in between.  `root` is the one value read back (an int).  traces: the
     [time, addr] DeviceBuffers of a `Stage0Device` to read instead of encoding and uploading both again; they stay their
-    owner's (`free` leaves them)."""
+    owner's (`free` leaves them).  A job made by `ShaMerkleJob.on_device` has no host traces: without traces= its tree's
+    time-ordered trace is sorted here (a `Stage0Device` this object owns)."""
 
     def __init__(self, job, ctx, traces=None):
         from .capi import DeviceBuffer
@@ -1092,6 +1157,10 @@ class Stage1Device:
         self.offsets = np.arange(job.n + 1, dtype=np.uint32) * job.np_
         flat = lambda tr: fc.enc([x for ops in tr for e in ops for x in e])
         consts, n_consts, ld, nd = device_params(job.curve, fc)
+        self._dev0 = None
+        if traces is None and isinstance(getattr(job, "tree", None), TreeDevice):
+            self._dev0 = Stage0Device(job, ctx, tree=job.tree)     # an on_device job: its trace, sorted here and owned here
+            traces = self._dev0.traces
         self._adopted = traces is not None
         if traces is not None:
             self.traces = list(traces)
@@ -1108,9 +1177,10 @@ class Stage1Device:
             raise
         self.root = fc.dec(self.outs[4].to_host())[0]
 
-    def fill(self, circ, members, z):
+    def fill(self, circ, members, z, sha_root=None):
         """The challenge-dependent columns of the assignments of `members` (subcircuit indices of ONE class, `circ`), row b
-        of the DeviceBuffer z = members[b]; the root class's data-tree root (`sha_root_col`) goes in by hk_assignment_scatter.
+        of the DeviceBuffer z = members[b]; the root class's data-tree root (`sha_root_col`) goes in by hk_assignment_scatter
+        - the job's `sha_root`, or with sha_root= (a DeviceBuffer of 1 Fr: `TreeDevice.sha_root`) the value on the device.
         The bit columns are the word program's (hk_wprog_run), before or after."""
         members = np.ascontiguousarray(members, dtype=np.uint32)
         self.ctx.stage1_witness(self.params, self.job.np_, self.offsets, self.traces[0], self.traces[1], self.challenges,
@@ -1118,6 +1188,12 @@ class Stage1Device:
         if circ.kind == "root" and members.size:
             from .capi import check
             cols = np.array([circ.sha_root_col], np.uint32)
+            if sha_root is not None:
+                row = circ.n_v * self.ctx.fr_bytes                 # one value on the device: a row at a time
+                for b in range(members.size):
+                    check(self.ctx.lib.hk_assignment_scatter(self.ctx.handle, cols.ctypes.data, sha_root.ptr, 1, 1, circ.n_v,
+                                                             z.ptr + b * row), "hk_assignment_scatter")
+                return z
             vals = np.ascontiguousarray(np.tile(circ.fc.enc([self.job.sha_root]), members.size))
             check(self.ctx.lib.hk_assignment_scatter(self.ctx.handle, cols.ctypes.data, vals.ctypes.data, 1, members.size,
                                                      circ.n_v, z.ptr), "hk_assignment_scatter")
@@ -1141,6 +1217,9 @@ class Stage1Device:
     def free(self):
         for x in ([] if self._adopted else list(self.traces)) + [self.params[0]] + list(self.outs):
             x.free()
+        if self._dev0 is not None:
+            self._dev0.free()
+            self._dev0 = None
         self.traces, self.outs = [], ()
 
 
