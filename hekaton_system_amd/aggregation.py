@@ -151,7 +151,8 @@ class TIPPCommitment:
 
 class AggProvingKey:
     """distributed-prover/src/aggregation.rs:23-135.  `vks[i]`: the Groth16 verifying-key parts of subcircuit i's class
-    (cp_groth16.VerifyingKey): gamma_abc_g (4 G1), gamma_h, deltas_h (2 G2), alpha_g, beta_h."""
+    (cp_groth16.VerifyingKey): gamma_abc_g (1 + the number of public inputs G1, the same count in every key: 4 for the ROM
+    circuits, 6 for the RAM ones; at most 7, hk_points_lincomb takes 8 vectors), gamma_h, deltas_h (2 G2), alpha_g, beta_h."""
 
     def __init__(self, ctx, curve, ck, vks):
         self.ctx, self.curve, self.ck = ctx, curve, ck
@@ -162,18 +163,22 @@ class AggProvingKey:
         cat = lambda xs: np.concatenate([np.asarray(x, np.uint8) for x in xs])
         self.n = len(vks)
         assert self.n == ck.n
-        self.s = [cat([vk.gamma_abc_g[j * g1b:(j + 1) * g1b] for vk in vks]) for j in range(4)]      # :84-87
+        self.n_s = k = len(np.asarray(vks[0].gamma_abc_g, np.uint8)) // g1b
+        assert 1 <= k <= 7 and all(len(np.asarray(vk.gamma_abc_g, np.uint8)) == k * g1b for vk in vks)
+        self.s = [cat([vk.gamma_abc_g[j * g1b:(j + 1) * g1b] for vk in vks]) for j in range(k)]      # :84-87
         self.h = cat([vk.gamma_h for vk in vks])                                                    # :88
         self.delta0 = cat([vk.deltas_h[:g2b] for vk in vks])                                        # :89
         self.delta1 = cat([vk.deltas_h[g2b:2 * g2b] for vk in vks])                                 # :90
         self.alpha = cat([vk.alpha_g for vk in vks])                                                # :91
         self.beta = cat([vk.beta_h for vk in vks])                                                  # :92
-        # the seven commitments (:97-103) are fourteen inner products between six G1 and five G2 vectors: one batched call
+        # the k + 3 commitments (:97-103; seven at k = 4) are 2 k + 6 inner products between k + 2 G1 and five G2 vectors:
+        # one batched call
         o = ctx.pairing_pairs(self.s + [ck.w1, ck.w2], [ck.v1, ck.v2, self.h, self.delta0, self.delta1],
-                              [(j, k) for j in range(4) for k in range(2)] + [(4 + j, 2 + k) for k in range(3) for j in range(2)], n=ck.n)
+                              [(j, c) for j in range(k) for c in range(2)] + [(k + j, 2 + c) for c in range(3) for j in range(2)], n=ck.n)
         D = self.F.decode
-        self.com_s = [IppCom(self.F, D(o[2 * j]), D(o[2 * j + 1]), ctx=ctx) for j in range(4)]
-        self.com_h, self.com_delta0, self.com_delta1 = (IppCom(self.F, D(o[8 + 2 * k]), D(o[9 + 2 * k]), ctx=ctx) for k in range(3))
+        self.com_s = [IppCom(self.F, D(o[2 * j]), D(o[2 * j + 1]), ctx=ctx) for j in range(k)]
+        self.com_h, self.com_delta0, self.com_delta1 = (IppCom(self.F, D(o[2 * k + 2 * c]), D(o[2 * k + 1 + 2 * c]), ctx=ctx)
+                                                        for c in range(3))
 
     def agg_subcircuit_proofs(self, pt, super_com, proofs, pub_inputs, srs, tipp=None, check=True):
         """aggregation.rs:138-345 whole: the challenges come from the merlin transcript `pt` (merlin.Transcript) exactly
@@ -190,7 +195,8 @@ class AggProvingKey:
 
     def agg_front(self, super_com, proofs, pub_inputs, twist=None, s=None, t=None, pt=None):
         """aggregation.rs:138-330 up to the `TIPA::prove` call.  proofs: [cp_groth16.Proof] with one stage-0
-        commitment each; pub_inputs: 3 ints; the Fiat-Shamir challenges either as ints (twist, s, t) or drawn from the
+        commitment each; pub_inputs: one int per public input
+        of the keys (3 for the ROM circuits, 5 for the RAM ones); the Fiat-Shamir challenges either as ints (twist, s, t) or drawn from the
         merlin transcript `pt` at the reference's points.  Returns a dict with the
         TIPA instance (`output` = z_lr, `commitment` = com_lr, `twist`), the witness (`left`, `right`) and the 4 x 4
         `cross_terms`; raises AssertionError if the pairing-product equation of :265-269 fails."""
@@ -204,10 +210,11 @@ class AggProvingKey:
         # independent GPU calls of a phase go out together (one lane each), as in tipa.Tipp
         go = self.pool.submit
         x = [v % r_mod for v in pub_inputs]
+        assert len(x) == self.n_s - 1, "one public input per gamma_abc_g element after the first"
         f_ab = go(self.com.commit_with_ip, ck, a_vals, b_vals)                                      # :167
         f_c = go(self.com.commit_only_left, ck, c_vals)                                             # :168
         f_in = go(ctx.points_lincomb, 1, self.s, fc.enc([1] + x), n)                                # :192-205
-        f_cin = go(IppCom.lincomb, [(self.com_s[0], None), (self.com_s[1], x[0]), (self.com_s[2], x[1]), (self.com_s[3], x[2])])  # :171-174
+        f_cin = go(IppCom.lincomb, [(self.com_s[0], None)] + [(self.com_s[1 + j], x[j]) for j in range(len(x))])                  # :171-174
         com_ab, com_c, com_d = f_ab.result(), f_c.result(), super_com
         if pt is not None:                                                                          # :219-222
             pt.append_serializable(b"AB-commitment", com_ab.serialize_uncompressed())

@@ -92,6 +92,16 @@ class hk_stage1_desc(C.Structure):            # include/hekaton.h
                 ("inst_col0", C.c_uint32), ("col0", C.c_uint32), ("pos_col0", C.c_uint32)]
 
 
+class hk_ram_stage1_desc(C.Structure):        # include/hekaton.h
+    _fields_ = [("n_sub", C.c_uint32), ("n_portals", C.c_uint32), ("depth", C.c_uint32), ("offsets", C.c_void_p),
+                ("time_entries_mont", C.c_void_p), ("addr_entries_mont", C.c_void_p), ("challenges_mont", C.c_void_p),
+                ("evals_mont", C.c_void_p), ("leaves_mont", C.c_void_p), ("siblings_mont", C.c_void_p),
+                ("root_mont", C.c_void_p), ("consts_mont", C.c_void_p), ("n_consts", C.c_size_t),
+                ("leaf_hash", C.POINTER(hk_poseidon_desc)), ("node_hash", C.POINTER(hk_poseidon_desc)),
+                ("template_mont", C.c_void_p),
+                ("inst_col0", C.c_uint32), ("stage0_col0", C.c_uint32), ("col0", C.c_uint32), ("pos_col0", C.c_uint32)]
+
+
 class hk_sha_tree_out(C.Structure):           # include/hekaton.h
     _fields_ = [("digests_out", C.c_void_p), ("time_entries_mont_out", C.c_void_p), ("sha_root_mont_out", C.c_void_p)]
 
@@ -121,7 +131,7 @@ EXPORTS = ["hk_status_str", "hk_version", "hk_ctx_create", "hk_ctx_destroy", "hk
            "hk_prove_batch", "hk_vk_prepare", "hk_vk_free", "hk_vk_alpha_beta", "hk_verify_batch", "hk_points_check_g1",
            "hk_points_check_g2", "hk_qap_eval", "hk_keygen", "hk_exec_tree", "hk_stage1_witness",
            "hk_trace_sort", "hk_stage0_witness", "hk_r1cs_check", "hk_pk_r1cs_check",
-           "hk_sha_tree", "hk_sha_tree_inputs"]
+           "hk_sha_tree", "hk_sha_tree_inputs", "hk_ram_stage0_witness", "hk_ram_stage1_witness"]
 
 HK_VERIFY_CHECK_POINTS = 1
 VERDICT_REJECT, VERDICT_ACCEPT, VERDICT_BAD_POINT = 0, 1, 2
@@ -218,6 +228,8 @@ def load():
     lib.hk_pk_r1cs_check.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, sz]
     lib.hk_sha_tree.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(hk_sha_tree_out)]
     lib.hk_sha_tree_inputs.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, sz, vp]
+    lib.hk_ram_stage0_witness.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, sz, vp]
+    lib.hk_ram_stage1_witness.argtypes = [vp, C.POINTER(hk_ram_stage1_desc), vp, sz, sz, vp]
     _lib = lib
     return lib
 
@@ -811,6 +823,51 @@ class Context:
                 out.free()
             raise
         return out
+
+    def ram_stage0_witness(self, offsets, n_portals, time_entries, addr_entries, sub_index, w_out):
+        """hk_ram_stage0_witness: row b of w_out (a DeviceBuffer or raw device address of len(sub_index) x 70 n_portals Fr) =
+        the stage-0 witness of the RAM subcircuit sub_index[b]: 35 columns (val, addr, 32 timestamp bits, read) per entry, its
+        n_portals time-ordered then its n_portals address-ordered entries.  offsets: n_sub + 1 uint32; time_entries /
+        addr_entries: Montgomery bytes or DeviceBuffers of offsets[-1] x 4 Fr (RAM: what trace_sort(4, ...) takes and gives)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+        sub_index = np.ascontiguousarray(sub_index, dtype=np.uint32)
+        keep = [x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8) for x in (time_entries, addr_entries)]
+        wp = w_out.ptr if isinstance(w_out, DeviceBuffer) else int(w_out)
+        check(self.lib.hk_ram_stage0_witness(self.handle, offsets.ctypes.data, offsets.size - 1, int(n_portals), ptr(keep[0]),
+                                             ptr(keep[1]), sub_index.ctypes.data if sub_index.size else None, sub_index.size, wp),
+              "hk_ram_stage0_witness")
+        return w_out
+
+    def ram_stage1_witness(self, params, n_portals, offsets, time_entries, addr_entries, challenges, exec_outs, sub_index, n_v,
+                           layout, z_out, template=None):
+        """hk_ram_stage1_witness: whole assignment rows of the RAM subcircuits `sub_index` (any order, repeats allowed), from
+        what exec_tree(params, 4, ...) took and returned.  challenges: entry_chal_1..3, tr_chal (ints or Montgomery bytes);
+        layout: (inst_col0, stage0_col0, col0, pos_col0) - the first column of the five instance values, of the 70 n_portals
+        stage-0 columns, of the 43 n_portals + 37 portal columns and of the membership block; template: Montgomery bytes or
+        a DeviceBuffer of n_v Fr every row starts from, or None: every column the call does not own keeps its bytes."""
+        from .cp_groth16 import FrCodec
+        consts, n_consts, ld, nd = params
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+        n_sub = offsets.size - 1
+        sub_index = np.ascontiguousarray(sub_index, dtype=np.uint32)
+        evals, leaves, _nodes, siblings, root = exec_outs
+        keep = [x if x is None or isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8)
+                for x in (time_entries, addr_entries, evals, leaves, siblings, root, template)]
+        if isinstance(challenges, np.ndarray):
+            ch = np.ascontiguousarray(challenges, dtype=np.uint8)
+        else:
+            ch = FrCodec(self.curve).enc(list(challenges))
+        a, b = hk_poseidon_desc(*ld), hk_poseidon_desc(*nd)
+        pp = lambda x: None if x is None else ptr(x).value if (x.nbytes if isinstance(x, DeviceBuffer) else x.size) else None
+        inst_col0, stage0_col0, col0, pos_col0 = layout
+        d = hk_ram_stage1_desc(n_sub, int(n_portals), max(n_sub, 1).bit_length() - 1, offsets.ctypes.data, pp(keep[0]),
+                               pp(keep[1]), ch.ctypes.data, pp(keep[2]), pp(keep[3]), pp(keep[4]), pp(keep[5]), ptr(consts),
+                               int(n_consts), C.pointer(a), C.pointer(b), pp(keep[6]), int(inst_col0), int(stage0_col0),
+                               int(col0), int(pos_col0))
+        zp = z_out.ptr if isinstance(z_out, DeviceBuffer) else int(z_out)
+        check(self.lib.hk_ram_stage1_witness(self.handle, C.byref(d), sub_index.ctypes.data if sub_index.size else None,
+                                             sub_index.size, int(n_v), zp), "hk_ram_stage1_witness")
+        return z_out
 
     def _r1cs_call(self, fn, head, z, n_v, batch, cap, want_vals):
         """The shared tail of Context.r1cs_check / DevicePk.r1cs_check: `fn(*head, z, n_v, batch, verdicts, rows, vals, cap)`."""

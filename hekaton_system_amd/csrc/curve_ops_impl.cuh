@@ -195,6 +195,10 @@ struct Ops final : CurveOps {
     // sha_tree.cuh
     hk_status sha_tree(hk_ctx*, const void*, uint32_t, uint32_t, uint32_t, const hk_sha_tree_out*) override;
     hk_status sha_tree_inputs(hk_ctx*, const void*, const void*, uint32_t, uint32_t, const uint32_t*, size_t, uint32_t*) override;
+    // ram_witness.cuh
+    hk_status ram_stage0_witness(hk_ctx*, const uint32_t*, uint32_t, uint32_t, const void*, const void*, const uint32_t*, size_t,
+                                 void*) override;
+    hk_status ram_stage1_witness(hk_ctx*, const hk_ram_stage1_desc*, const uint32_t*, size_t, size_t, void*) override;
 };
 
 }  // namespace hk

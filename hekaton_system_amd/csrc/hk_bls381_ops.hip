@@ -12,6 +12,7 @@
 #include "trace_sort.cuh"
 #include "r1cs_check.cuh"
 #include "sha_tree.cuh"
+#include "ram_witness.cuh"
 namespace hk {
 extern template struct MsmRun<CurveBls381::Fq>;
 extern template struct MsmRun<CurveBls381::Fq2>;

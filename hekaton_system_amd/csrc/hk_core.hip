@@ -703,6 +703,17 @@ hk_status hk_sha_tree_inputs(hk_ctx* ctx, const void* leaves, const void* digest
     if (!ctx) return HK_ERR_ARG;
     return ctx->ops->sha_tree_inputs(ctx, leaves, digests, n_sub, n_inputs, sub_index, batch, inputs_out);
 }
+hk_status hk_ram_stage0_witness(hk_ctx* ctx, const uint32_t* offsets, uint32_t n_sub, uint32_t n_portals,
+                                const void* time_entries_mont, const void* addr_entries_mont, const uint32_t* sub_index, size_t batch,
+                                void* w_out) {
+    if (!ctx) return HK_ERR_ARG;
+    return ctx->ops->ram_stage0_witness(ctx, offsets, n_sub, n_portals, time_entries_mont, addr_entries_mont, sub_index, batch, w_out);
+}
+hk_status hk_ram_stage1_witness(hk_ctx* ctx, const hk_ram_stage1_desc* desc, const uint32_t* sub_index, size_t batch, size_t n_v,
+                                void* z_out) {
+    if (!ctx || !desc) return HK_ERR_ARG;
+    return ctx->ops->ram_stage1_witness(ctx, desc, sub_index, batch, n_v, z_out);
+}
 
 }  // extern "C"
 

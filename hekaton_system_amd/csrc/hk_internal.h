@@ -246,6 +246,13 @@ struct CurveOps {
     virtual hk_status sha_tree_inputs(hk_ctx*, const void* leaves, const void* digests, uint32_t n_sub, uint32_t n_inputs,
                                       const uint32_t* sub_index, size_t batch, uint32_t* inputs_out) = 0;
 
+    // ram_witness.cuh
+    virtual hk_status ram_stage0_witness(hk_ctx*, const uint32_t* offsets, uint32_t n_sub, uint32_t n_portals,
+                                         const void* time_entries, const void* addr_entries, const uint32_t* sub_index,
+                                         size_t batch, void* w_out) = 0;
+    virtual hk_status ram_stage1_witness(hk_ctx*, const hk_ram_stage1_desc*, const uint32_t* sub_index, size_t batch, size_t n_v,
+                                         void* z_out) = 0;
+
 protected:
     CurveOps(size_t fr, size_t fq, size_t g1, size_t g2, size_t gt)
         : fr_bytes(fr), fq_bytes(fq), g1_bytes(g1), g2_bytes(g2), gt_bytes(gt) {}

@@ -120,7 +120,8 @@ __device__ __forceinline__ Fr s1_permute_quad_trace(const Fr* __restrict__ const
 // One quad per row: the membership block of subcircuit i = rows[2 b] - leaf leaves[i], path siblings[i], index i - in the order
 // of k_poseidon_path / sha_circuit.poseidon_path_trace, at column pos_col0 of row b.  A quad past the batch recomputes the last
 // row and stores nothing: no lane leaves in front of a DPP read.
-template <class Fr>
+// NF = 4 (a ROM leaf) or 6 (a RAM leaf: hk_ram_stage1_witness): the second absorption adds leaf[3 .. NF) to lanes 1 .. NF - 3.
+template <class Fr, int NF>
 __global__ void __launch_bounds__(256)
 k_s1_membership(const Fr* __restrict__ consts, PoseidonDesc leaf_d, PoseidonDesc node_d, const Fr* __restrict__ leaves,
                 const Fr* __restrict__ siblings, const u32* __restrict__ rows, u32 depth, u32 batch, size_t n_v, size_t pos_col0,
@@ -130,12 +131,16 @@ k_s1_membership(const Fr* __restrict__ consts, PoseidonDesc leaf_d, PoseidonDesc
     const bool store = t < batch;
     const u32 b = store ? t : batch - 1;
     const u32 i = rows[2 * b];
-    const Fr* leaf = leaves + (size_t)i * 4;
+    static_assert(NF == 4 || NF == 6, "an execution leaf has 2 + entry_fields fields");
+    const Fr* leaf = leaves + (size_t)i * NF;
     Fr* w = z_out + (size_t)b * n_v + pos_col0;
-    // the rate-3 sponge over the 4 leaf fields (et_leaf_digest with the trace): every lane loads an index it may read
+    // the rate-3 sponge over the NF leaf fields (et_leaf_digest with the trace): every lane loads an index it may read
     Fr s = et_select(q != 0, fr_load(&leaf[q ? q - 1 : 0]), Fr::zero());
     s = s1_permute_quad_trace<Fr, 4, 5>(consts, leaf_d, s, store, w);
-    s = Fr::add(s, et_select(q == 1, fr_load(&leaf[3]), Fr::zero()));
+    if constexpr (NF == 4)
+        s = Fr::add(s, et_select(q == 1, fr_load(&leaf[3]), Fr::zero()));
+    else
+        s = Fr::add(s, et_select(q != 0, fr_load(&leaf[q ? 2 + q : 3]), Fr::zero()));
     s = s1_permute_quad_trace<Fr, 4, 5>(consts, leaf_d, s, store, w);
     Fr cur = et_quad_bcast<Fr, 0x55>(s);
     HK_NOUNROLL for (u32 l = 0; l < depth; l++) {
@@ -225,7 +230,7 @@ hk_status Ops<C>::stage1_witness(hk_ctx* ctx, const hk_stage1_desc* d, const uin
                        (const Fr*)in[3].p, (const Fr*)in[6].p, n_v, (size_t)d->inst_col0, (size_t)d->col0, (Fr*)z_out);
     PoseidonDesc a{lh->t, lh->alpha, lh->full_rounds, lh->partial_rounds, lh->consts_offset};
     PoseidonDesc b{nh->t, nh->alpha, nh->full_rounds, nh->partial_rounds, nh->consts_offset};
-    hipLaunchKernelGGL((k_s1_membership<Fr>), dim3((nb + S1_WG_ROWS - 1) / S1_WG_ROWS), dim3(256), 0, s, cp, a, b,
+    hipLaunchKernelGGL((k_s1_membership<Fr, 4>), dim3((nb + S1_WG_ROWS - 1) / S1_WG_ROWS), dim3(256), 0, s, cp, a, b,
                        (const Fr*)in[4].p, (const Fr*)in[5].p, (const u32*)rows_d, (u32)depth, nb, n_v, (size_t)d->pos_col0, (Fr*)z_out);
     HK_HIP(hipGetLastError());
     return L->settle();

@@ -519,7 +519,7 @@ hk_status hk_exec_tree(hk_ctx* ctx, const hk_exec_tree_desc* desc, const hk_exec
  * the round's challenges: what `generate_constraints` witnesses from its Stage1Request (coordinator.rs:569-604: the
  * challenges, the previous leaf's evaluations and last entry, the membership path of its own leaf, the root).  hk_exec_tree
  * computes every one of those values; hk_stage1_witness writes them into the assignments of any subset of the job's
- * subcircuits, from hk_exec_tree's inputs and outputs where they lie (ROM entries).  Row b of z_out is the assignment of
+ * subcircuits, from hk_exec_tree's inputs and outputs where they lie (ROM entries; hk_ram_stage1_witness below is the RAM form).  Row b of z_out is the assignment of
  * subcircuit i = sub_index[b]; indices may come in any order and may repeat.  With k = n_portals:
  *   inst_col0 + 0 .. 2     entry_chal, tr_chal, root
  *   col0 ..                (addr, val) of the k time-ordered entries, then of the k address-ordered ones        4 k
@@ -585,7 +585,7 @@ hk_status hk_trace_sort(hk_ctx* ctx, uint32_t entry_fields,             /* 2 = R
  * n_portals time-ordered entries, then of its n_portals address-ordered entries - entries [offsets[i], offsets[i + 1]) of
  * each trace, two contiguous copies; the variable order of hekaton_system_amd/sha_circuit.py `ShaMerkleJob.stage0_ints` /
  * `ShaMerkleSubcircuit._program`.  w_out is what hk_commit_batch takes as w_mont [d].  ROM entries only, as
- * hk_stage1_witness.  Host-resident traces are staged in lane scratch, device-resident ones are read in place.
+ * hk_stage1_witness (RAM: hk_ram_stage0_witness).  Host-resident traces are staged in lane scratch, device-resident ones are read in place.
  * batch == 0: HK_OK, nothing done.  HK_ERR_ARG, before any device work and with w_out untouched: a NULL pointer;
  * n_portals == 0; offsets[0] != 0 or decreasing offsets; sub_index[b] >= n_sub; a selected subcircuit that does not own
  * exactly n_portals entries; w_out not in device memory; batch >= 2^20 or batch x n_portals >= 2^28. */
@@ -664,6 +664,66 @@ hk_status hk_sha_tree_inputs(hk_ctx* ctx, const void* leaves /* [h|d], may be NU
                              uint32_t n_sub, uint32_t n_inputs /* 16 | 54 */,
                              const uint32_t* sub_index /* [h] batch */, size_t batch,
                              uint32_t* inputs_out /* [h|d] batch x n_inputs */);
+
+/* ---- the witness of a RAM portal subcircuit (distributed-prover/src/portal_manager/ram_portal_manager.rs:150-230,
+ * transcript/ram_transcript.rs:260-390, subcircuit_circuit.rs:166-273; the VM job of vm/vm_constraints.rs) ------------------
+ * The RAM siblings of hk_stage0_witness and hk_stage1_witness: they read hk_trace_sort's and hk_exec_tree's entry_fields = 4
+ * layout (addr, val, timestamp, is_read per entry) and write the columns hekaton_system_amd/vm_circuit.py
+ * `RamSubcircuit._program` allocates.  An entry takes 35 columns: val, addr, timestamp bit 0 .. 31 (least significant
+ * first), read.  Row b is subcircuit i = sub_index[b]; indices may come in any order and may repeat.  With k = n_portals:
+ *   stage 0                the k time-ordered entries, then the k address-ordered ones                          70 k
+ *   inst_col0 + 0 .. 4     entry_chal_1, entry_chal_2, entry_chal_3, tr_chal, root
+ *   col0 ..                the previous leaf's last address-ordered entry: entry offsets[i] - 1, all zero when
+ *                          offsets[i] == 0                                                                      35
+ *                          time chain: evals[i - 1][0] (1 for i = 0), then per entry p1 = c1 addr, p2 = c2 ts,
+ *                          e = val + p1 + p2 + c3 read and cur <- cur (tr_chal - e)                              1 + 4 k
+ *                          address chain, the same from evals[i - 1][1]                                         1 + 4 k
+ *                          per consecutive pair of [previous] + address entries, d = addr' - addr: inv = 1 / d
+ *                          (0 when d = 0), same = [d == 0], sr = same read', then bit 0 .. 31 of
+ *                          ts' - ts - 1 (mod 2^32) when same, else 32 zeros                                     35 k
+ *   pos_col0 ..            the membership block of leaf leaves[i] (six fields), path siblings[i], index i: the values and
+ *                          order of hk_poseidon_path
+ * hk_ram_stage0_witness writes the 70 k stage-0 columns alone, as rows of 70 k Fr: what hk_commit_batch takes as w_mont [d].
+ * hk_ram_stage1_witness writes a whole assignment row in one call: when template_mont is non-NULL every row of z_out is first
+ * set to it (n_v Fr: column 0 and whatever is the same for every subcircuit of the class); then the instance values, the
+ * stage-0 columns at stage0_col0, the portal block and the membership block.  Every other column keeps its bytes, or the
+ * template's.  Both calls run on the caller's lane; host-resident inputs are staged in lane scratch, device-resident ones are
+ * read in place.  batch == 0: HK_OK, nothing done.  HK_ERR_ARG, before any device work and with the output untouched: a NULL
+ * pointer (template_mont excepted); n_portals == 0; offsets[0] != 0 or decreasing offsets; sub_index[b] >= n_sub; a selected
+ * subcircuit that does not own exactly n_portals entries; the output not in device memory; hk_ram_stage1_witness also:
+ * n_sub not a power of two >= 2 or depth != log2(n_sub); a descriptor pair other than the compiled (t 4, alpha 5) /
+ * (t 3, alpha 17), constants that end before its tables do; one of the four column ranges not inside [1, n_v) or two of
+ * them overlapping.  Lane counts: every kernel of the two calls indexes its lanes with 64 bits and is launched as
+ * ceil(lanes / 256) blocks, at most batch x max(40 + 105 k, n_v) lanes, so the calls refuse k > 2^16, batch >= 2^20,
+ * batch x (40 + 105 k) >= 2^38 and batch x n_v >= 2^38 (below 2^30 blocks).  HK_ERR_ARG found on the device, the output
+ * untouched: in a SELECTED subcircuit a timestamp >= 2^32 or a read flag other than 0 / 1 (neither is a value of the
+ * reference's types); such a value elsewhere in the traces is not looked at. */
+hk_status hk_ram_stage0_witness(hk_ctx* ctx, const uint32_t* offsets /* [h] n_sub + 1 */, uint32_t n_sub, uint32_t n_portals,
+                                const void* time_entries_mont, const void* addr_entries_mont,   /* [h|d] offsets[n_sub] x 4 Fr */
+                                const uint32_t* sub_index /* [h] batch */, size_t batch,
+                                void* w_out /* [d] batch x 70 n_portals Fr */);
+typedef struct {
+    uint32_t n_sub;                 /* subcircuits of the job = rows of evals / leaves / siblings; power of two >= 2 */
+    uint32_t n_portals;             /* k >= 1: entries a subcircuit of this class owns in EACH order */
+    uint32_t depth;                 /* log2(n_sub) */
+    const uint32_t* offsets;        /* [h] n_sub + 1, as hk_exec_tree */
+    const void* time_entries_mont;  /* [h|d] offsets[n_sub] x 4 Fr (addr, val, timestamp, is_read): hk_exec_tree's inputs */
+    const void* addr_entries_mont;  /* [h|d] same shape, address order */
+    const void* challenges_mont;    /* [h] 4 Fr: entry_chal_1, entry_chal_2, entry_chal_3, tr_chal */
+    const void* evals_mont;         /* [h|d] n_sub x 2 Fr      } */
+    const void* leaves_mont;        /* [h|d] n_sub x 6 Fr      } exactly what hk_exec_tree wrote with entry_fields = 4 */
+    const void* siblings_mont;      /* [h|d] n_sub x depth Fr  } */
+    const void* root_mont;          /* [h|d] 1 Fr              } */
+    const void* consts_mont; size_t n_consts;
+    const hk_poseidon_desc* leaf_hash; const hk_poseidon_desc* node_hash;   /* as hk_poseidon_path / hk_exec_tree */
+    const void* template_mont;      /* [h|d] n_v Fr, or NULL: every row of z_out starts as a copy of it */
+    uint32_t inst_col0;             /* columns inst_col0 .. +4 <- the four challenges, root */
+    uint32_t stage0_col0;           /* first of the 70 k stage-0 columns */
+    uint32_t col0;                  /* first column of the portal block (43 k + 37 columns, order above) */
+    uint32_t pos_col0;              /* first column of the membership block (hk_poseidon_path's col0) */
+} hk_ram_stage1_desc;
+hk_status hk_ram_stage1_witness(hk_ctx* ctx, const hk_ram_stage1_desc* desc, const uint32_t* sub_index /* [h] batch */,
+                                size_t batch, size_t n_v, void* z_out /* [d] batch x n_v Fr */);
 
 #ifdef __cplusplus
 }
