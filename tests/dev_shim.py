@@ -1,6 +1,7 @@
 """Loaders and integer packing for the test-only device shims: tests/device_shim/field_dev_shim.hip (plain helper of
-tests/test_field_device_gpu.py and tests/test_wave_f12_gpu.py) and tests/device_shim/ec_dev_shim.hip (of
-tests/test_ec_device_gpu.py and tests/test_msm_plan_device_gpu.py).  The shims run in the calling process."""
+tests/test_field_device_gpu.py and tests/test_wave_f12_gpu.py), tests/device_shim/ec_dev_shim.hip (of
+tests/test_ec_device_gpu.py and tests/test_msm_plan_device_gpu.py) and tests/device_shim/pair_dev_shim.hip (of
+tests/test_pair_device_gpu.py).  The shims run in the calling process."""
 import ctypes
 import os
 
@@ -25,8 +26,15 @@ EC_NOASM_NOT_BUILT = {
     2: {G_MADD, G_MADD_CHAIN},
 }
 
+# pair_dev_shim.hip: built as shipped only (its -DHK_NO_ASM_MUL twin outgrows the code-object bounds: see the header of
+# tests/device_shim/Makefile)
+PAIR_VARIANTS = {"asm": "libpair_dev_shim.so"}
+Q_MUL, Q_SQR, Q_MUL_BY_CHAR, Q_PSI = range(4)
+FORM_LANE, FORM_QUAD = 0, 1
+
 _loaded = {}
 _loaded_ec = {}
+_loaded_pair = {}
 
 
 def pack(elems, nbytes):
@@ -150,3 +158,86 @@ def load_ec(variant):
     if variant not in _loaded_ec:
         _loaded_ec[variant] = EcShim(variant)
     return _loaded_ec[variant]
+
+
+class PairShim:
+    """The stages of the multi-pairing pipeline.  f2q_op takes and gives integers (raw limbs in, canonical Montgomery values
+    out); the pipeline stages take and give the bytes the kernels read and write (Montgomery, little-endian; nb bytes per Fq):
+    an affine G1 point is 2 Fq, a G2 point 4, a raw line 6 (c0, c1, c2 in Fq2), an Fq12 value 12."""
+
+    def __init__(self, variant):
+        path = os.path.join(ROOT, "hekaton_system_amd", "lib", PAIR_VARIANTS[variant])
+        assert os.path.exists(path), "build the device shim first (python __graft_entry__.py)"
+        self.variant = variant
+        self.lib = ctypes.CDLL(path)
+        vp, ui, up = ctypes.c_char_p, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint)
+        self.lib.dshim_f2q_op.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_size_t]
+        self.lib.dshim_pair_lines.argtypes = [ctypes.c_int, ctypes.c_int, vp, ui, ui, vp, up]
+        self.lib.dshim_pair_tree_lines.argtypes = [ctypes.c_int, vp, vp, ui, ui, ui, ui, ui, up, up, ui, vp]
+        self.lib.dshim_pair_tree.argtypes = [ctypes.c_int, vp, ui, ui, ui, vp]
+        self.lib.dshim_pair_horner.argtypes = [ctypes.c_int, vp, ui, vp]
+        self.lib.dshim_pair_steps.restype = ctypes.c_uint
+        assert self.lib.dshim_pair_uses_asm() == (1 if variant == "asm" else 0)
+
+    def steps(self, cid):
+        return self.lib.dshim_pair_steps(cid)
+
+    def f2q_op(self, cid, op, nbytes, a, b=None):
+        """a, b: lists of (c0, c1) raw limb values -> per element the four lanes' results: (c0, c1) each, or for the point ops
+        (a = the x, b = the y of the points) ((x0, x1), (y0, y1)) each"""
+        per = 2 if op in (Q_MUL_BY_CHAR, Q_PSI) else 1
+        abuf = pack(a, nbytes)
+        bbuf = None if b is None else pack(b, nbytes)
+        out = ctypes.create_string_buffer(len(a) * 4 * per * 2 * nbytes)
+        st = self.lib.dshim_f2q_op(cid, op, abuf, bbuf, out, len(a))
+        assert st == 0, "dshim_f2q_op(curve %d, op %d): HIP error %d" % (cid, op, -st)
+        f2 = unpack(out.raw, nbytes, 2)
+        if per == 2:
+            f2 = [tuple(f2[i:i + 2]) for i in range(0, len(f2), 2)]
+        return [f2[4 * i:4 * i + 4] for i in range(len(a))]
+
+    def pair_lines(self, cid, form, nb, g2, n, n_r):
+        """g2: bytes of n_r x n affine G2 points -> (bytes of the n_r x S x n raw lines, S)"""
+        assert len(g2) == n_r * n * 4 * nb
+        S = self.steps(cid)
+        out = ctypes.create_string_buffer(n_r * S * n * 6 * nb)
+        got_S = ctypes.c_uint(0)
+        st = self.lib.dshim_pair_lines(cid, form, bytes(g2), n, n_r, out, ctypes.byref(got_S))
+        assert st == 0, "dshim_pair_lines(curve %d, form %d, n %d, n_r %d): HIP error %d" % (cid, form, n, n_r, -st)
+        assert got_S.value == S
+        return out.raw, S
+
+    def pair_tree_lines(self, cid, nb, lines, g1, n, c, n_l, n_r, S, pairs=None):
+        """lines: bytes of n_r x S x n raw lines, g1: bytes of n_l x n affine G1 points, pairs: [(lhs, rhs)] or None for
+        the n_l x n_r grid -> bytes of count x S x ceil(n / c) Fq12"""
+        assert len(lines) == n_r * S * n * 6 * nb and len(g1) == n_l * n * 2 * nb
+        count = len(pairs) if pairs else n_l * n_r
+        pa = (ctypes.c_uint * count)(*[a for a, _ in pairs]) if pairs else None
+        pb = (ctypes.c_uint * count)(*[b for _, b in pairs]) if pairs else None
+        out = ctypes.create_string_buffer(count * S * ((n + c - 1) // c) * 12 * nb)
+        st = self.lib.dshim_pair_tree_lines(cid, bytes(lines), bytes(g1), n, c, n_l, n_r, S, pa, pb, len(pairs) if pairs else 0,
+                                            out)
+        assert st == 0, "dshim_pair_tree_lines(curve %d, n %d): HIP error %d" % (cid, n, -st)
+        return out.raw
+
+    def pair_tree(self, cid, nb, vals, n, c, count):
+        """vals: bytes of count x n Fq12 -> bytes of count x ceil(n / c) Fq12"""
+        assert len(vals) == count * n * 12 * nb
+        out = ctypes.create_string_buffer(count * ((n + c - 1) // c) * 12 * nb)
+        st = self.lib.dshim_pair_tree(cid, bytes(vals), n, c, count, out)
+        assert st == 0, "dshim_pair_tree(curve %d, n %d, c %d): HIP error %d" % (cid, n, c, -st)
+        return out.raw
+
+    def pair_horner(self, cid, nb, L, count):
+        """L: bytes of count x S Fq12 -> bytes of count Fq12"""
+        assert len(L) == count * self.steps(cid) * 12 * nb
+        out = ctypes.create_string_buffer(count * 12 * nb)
+        st = self.lib.dshim_pair_horner(cid, bytes(L), count, out)
+        assert st == 0, "dshim_pair_horner(curve %d, count %d): HIP error %d" % (cid, count, -st)
+        return out.raw
+
+
+def load_pair(variant):
+    if variant not in _loaded_pair:
+        _loaded_pair[variant] = PairShim(variant)
+    return _loaded_pair[variant]
