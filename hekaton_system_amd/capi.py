@@ -102,6 +102,12 @@ class hk_ram_stage1_desc(C.Structure):        # include/hekaton.h
                 ("inst_col0", C.c_uint32), ("stage0_col0", C.c_uint32), ("col0", C.c_uint32), ("pos_col0", C.c_uint32)]
 
 
+class hk_r1cs_job_desc(C.Structure):          # include/hekaton.h
+    _fields_ = [("n_parts", C.c_uint32), ("n_txs", C.c_uint32), ("slot_offsets", C.c_void_p), ("slot_rank", C.c_void_p),
+                ("slot_src", C.c_void_p), ("sets_per_tx", C.c_uint32), ("tx_len", C.c_uint32), ("tx_stride", C.c_uint32),
+                ("wit_offsets", C.c_void_p), ("body_len", C.c_void_p), ("witness_mont", C.c_void_p)]
+
+
 class hk_sha_tree_out(C.Structure):           # include/hekaton.h
     _fields_ = [("digests_out", C.c_void_p), ("time_entries_mont_out", C.c_void_p), ("sha_root_mont_out", C.c_void_p)]
 
@@ -131,7 +137,8 @@ EXPORTS = ["hk_status_str", "hk_version", "hk_ctx_create", "hk_ctx_destroy", "hk
            "hk_prove_batch", "hk_vk_prepare", "hk_vk_free", "hk_vk_alpha_beta", "hk_verify_batch", "hk_points_check_g1",
            "hk_points_check_g2", "hk_qap_eval", "hk_keygen", "hk_exec_tree", "hk_stage1_witness",
            "hk_trace_sort", "hk_stage0_witness", "hk_r1cs_check", "hk_pk_r1cs_check",
-           "hk_sha_tree", "hk_sha_tree_inputs", "hk_ram_stage0_witness", "hk_ram_stage1_witness"]
+           "hk_sha_tree", "hk_sha_tree_inputs", "hk_ram_stage0_witness", "hk_ram_stage1_witness",
+           "hk_r1cs_job_trace", "hk_r1cs_job_witness"]
 
 HK_VERIFY_CHECK_POINTS = 1
 VERDICT_REJECT, VERDICT_ACCEPT, VERDICT_BAD_POINT = 0, 1, 2
@@ -230,6 +237,8 @@ def load():
     lib.hk_sha_tree_inputs.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, sz, vp]
     lib.hk_ram_stage0_witness.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, sz, vp]
     lib.hk_ram_stage1_witness.argtypes = [vp, C.POINTER(hk_ram_stage1_desc), vp, sz, sz, vp]
+    lib.hk_r1cs_job_trace.argtypes = [vp, C.POINTER(hk_r1cs_job_desc), vp]
+    lib.hk_r1cs_job_witness.argtypes = [vp, C.POINTER(hk_r1cs_job_desc), vp, sz, sz, sz, vp]
     _lib = lib
     return lib
 
@@ -867,6 +876,51 @@ class Context:
         zp = z_out.ptr if isinstance(z_out, DeviceBuffer) else int(z_out)
         check(self.lib.hk_ram_stage1_witness(self.handle, C.byref(d), sub_index.ctypes.data if sub_index.size else None,
                                              sub_index.size, int(n_v), zp), "hk_ram_stage1_witness")
+        return z_out
+
+    def _r1cs_job_desc(self, tables, witness):
+        """(hk_r1cs_job_desc, what must stay alive beside it) from `PartitionedR1csJob.tables()` and the witness blocks."""
+        arr = {k: np.ascontiguousarray(tables[k], dtype=np.uint32)
+               for k in ("slot_offsets", "slot_rank", "slot_src", "wit_offsets", "body_len")}
+        wit = witness if isinstance(witness, DeviceBuffer) else np.ascontiguousarray(witness, dtype=np.uint8)
+        # a NULL table reaches the library as NULL: an empty numpy array has a data pointer all the same
+        p = lambda a: a.ctypes.data if a.size else None
+        d = hk_r1cs_job_desc(int(tables["n_parts"]), int(tables["n_txs"]), arr["slot_offsets"].ctypes.data, p(arr["slot_rank"]),
+                             p(arr["slot_src"]), int(tables["sets_per_tx"]), int(tables["tx_len"]), int(tables["tx_stride"]),
+                             p(arr["wit_offsets"]), p(arr["body_len"]), ptr(wit))
+        return d, (arr, wit)
+
+    def r1cs_job_trace(self, tables, witness, device_out=False, out=None):
+        """hk_r1cs_job_trace: the flattened time-ordered ROM trace of a partitioned R1CS job
+        (partitioned_r1cs_circuit.rs:182-220 `get_portal_subtraces`) - what trace_sort(2, ...), exec_tree and stage0_witness
+        take.  tables: `PartitionedR1csJob.tables()`; witness: Montgomery bytes or a DeviceBuffer of the job's witness blocks
+        (`witness_bytes()`).  Returns n_txs x slots (addr, val) pairs as Montgomery bytes, or as a DeviceBuffer when
+        device_out is set; out: a buffer of that size (numpy array or DeviceBuffer) to fill and return instead."""
+        d, keep = self._r1cs_job_desc(tables, witness)
+        n = int(tables["n_txs"]) * int(np.asarray(tables["slot_offsets"])[-1]) * 2 * self.fr_bytes
+        if out is None:
+            out = DeviceBuffer(self, max(n, 1)) if device_out else np.zeros(n, dtype=np.uint8)
+            own = device_out
+        else:
+            own = False
+        try:
+            check(self.lib.hk_r1cs_job_trace(self.handle, C.byref(d), ptr(out)), "hk_r1cs_job_trace")
+        except HekatonError:
+            if own:
+                out.free()
+            raise
+        return out
+
+    def r1cs_job_witness(self, tables, witness, sub_index, n_v, body_col0, z_out):
+        """hk_r1cs_job_witness: column 0 and the body columns of the assignments of the subcircuits `sub_index` of ONE
+        partition (any order, repeats allowed; row b of z_out = subcircuit sub_index[b]): columns body_col0 .. <- wires 1 ..
+        of the subcircuit's witness.  tables, witness: as r1cs_job_trace takes them; z_out: DeviceBuffer (or raw device
+        address) of len(sub_index) x n_v Fr.  Every other column keeps its bytes (stage1_witness writes those)."""
+        d, keep = self._r1cs_job_desc(tables, witness)
+        sub_index = np.ascontiguousarray(sub_index, dtype=np.uint32)
+        zp = z_out.ptr if isinstance(z_out, DeviceBuffer) else int(z_out)
+        check(self.lib.hk_r1cs_job_witness(self.handle, C.byref(d), sub_index.ctypes.data if sub_index.size else None,
+                                           sub_index.size, int(n_v), int(body_col0), zp), "hk_r1cs_job_witness")
         return z_out
 
     def _r1cs_call(self, fn, head, z, n_v, batch, cap, want_vals):

@@ -199,6 +199,9 @@ struct Ops final : CurveOps {
     hk_status ram_stage0_witness(hk_ctx*, const uint32_t*, uint32_t, uint32_t, const void*, const void*, const uint32_t*, size_t,
                                  void*) override;
     hk_status ram_stage1_witness(hk_ctx*, const hk_ram_stage1_desc*, const uint32_t*, size_t, size_t, void*) override;
+    // r1cs_job.cuh
+    hk_status r1cs_job_trace(hk_ctx*, const hk_r1cs_job_desc*, void*) override;
+    hk_status r1cs_job_witness(hk_ctx*, const hk_r1cs_job_desc*, const uint32_t*, size_t, size_t, size_t, void*) override;
 };
 
 }  // namespace hk

@@ -13,6 +13,7 @@
 #include "r1cs_check.cuh"
 #include "sha_tree.cuh"
 #include "ram_witness.cuh"
+#include "r1cs_job.cuh"
 namespace hk {
 extern template struct MsmRun<CurveBn254::Fq>;
 extern template struct MsmRun<CurveBn254::Fq2>;

@@ -714,6 +714,15 @@ hk_status hk_ram_stage1_witness(hk_ctx* ctx, const hk_ram_stage1_desc* desc, con
     if (!ctx || !desc) return HK_ERR_ARG;
     return ctx->ops->ram_stage1_witness(ctx, desc, sub_index, batch, n_v, z_out);
 }
+hk_status hk_r1cs_job_trace(hk_ctx* ctx, const hk_r1cs_job_desc* desc, void* time_entries_mont_out) {
+    if (!ctx || !desc) return HK_ERR_ARG;
+    return ctx->ops->r1cs_job_trace(ctx, desc, time_entries_mont_out);
+}
+hk_status hk_r1cs_job_witness(hk_ctx* ctx, const hk_r1cs_job_desc* desc, const uint32_t* sub_index, size_t batch, size_t n_v,
+                              size_t body_col0, void* z_out) {
+    if (!ctx || !desc) return HK_ERR_ARG;
+    return ctx->ops->r1cs_job_witness(ctx, desc, sub_index, batch, n_v, body_col0, z_out);
+}
 
 }  // extern "C"
 

@@ -725,6 +725,50 @@ typedef struct {
 hk_status hk_ram_stage1_witness(hk_ctx* ctx, const hk_ram_stage1_desc* desc, const uint32_t* sub_index /* [h] batch */,
                                 size_t batch, size_t n_v, void* z_out /* [d] batch x n_v Fr */);
 
+/* ---- the partitioned R1CS job (distributed-prover/src/partitioned_r1cs_circuit.rs:116-220; portal_manager/
+ * rom_portal_manager.rs:34-117 `SetupRomPortalManager`) ----------------------------------------------------------------------
+ * A circom R1CS cut into P partitions that exchange their shared wires through ROM portals, repeated over T transactions
+ * (hekaton_system_amd/r1cs_circuit.py `PartitionedR1csJob`): subcircuit i is partition i % P of transaction i / P.  The
+ * descriptor states the job once.  A transaction's witness block is the P partitions' witnesses back to back, wire order as
+ * the reference's (wire 0 the constant, the partition's own wires, its owned ones, its borrowed ones); transaction g reads
+ * the block at g * tx_stride Fr of witness_mont, or block 0 when tx_stride == 0.  A partition's portal slots are, in time
+ * order, its owned `set`s, its borrowed `get`s and, in a one-partition job, the dummy `set`; slot s carries the value at
+ * index slot_src[s] of the block - for a borrowed slot the OWNER's wire - or 0 for HK_R1CS_SRC_ZERO, at address
+ * 1 + g * sets_per_tx + slot_rank[s]: addresses are handed out from 1 in the order of the `set`s.
+ * hk_r1cs_job_trace writes `get_portal_subtraces`: the flattened time-ordered trace, n_txs * slot_offsets[n_parts] entries of
+ * (addr, val) in subcircuit order - what hk_trace_sort(2, ...), hk_exec_tree and hk_stage0_witness take, with
+ * offsets[i + 1] - offsets[i] = the slots of partition i % P.
+ * hk_r1cs_job_witness writes, into row b of z_out for subcircuit i = sub_index[b] (any order, repeats allowed, all of ONE
+ * partition p): column 0 <- 1 and columns body_col0 .. body_col0 + body_len[p] - 1 <- wires 1 .. body_len[p] of that
+ * subcircuit's witness (body_len = own wires + owned wires; a borrowed wire is the `val` column of its trace entry and has no
+ * column here).  Every other column keeps its bytes: hk_stage1_witness on the same rows completes the assignment.
+ * Both calls run on the caller's lane; a host-resident witness is staged in lane scratch, a device-resident one is read in
+ * place.  batch == 0 or a job without slots: HK_OK, nothing done.  HK_ERR_ARG, before any device work and with the output
+ * untouched: a NULL pointer; n_parts, n_txs or tx_len 0, or n_parts x n_txs > 2^24; slot_offsets[0] != 0 or decreasing; a
+ * slot_rank >= sets_per_tx; a slot_src that is neither HK_R1CS_SRC_ZERO nor < tx_len; 1 + n_txs x sets_per_tx >= 2^32;
+ * 2^31 entries or more; 0 < tx_stride < tx_len; an output range that overlaps the witness.  hk_r1cs_job_witness also:
+ * wit_offsets[0] != 0, not increasing or not ending at tx_len; body_len[p] not below partition p's wires; sub_index[b] >=
+ * n_parts x n_txs; selected subcircuits of different partitions; the body range not inside [1, n_v); z_out not in device
+ * memory; batch >= 2^20, n_v >= 2^31 or batch x n_v >= 2^38. */
+#define HK_R1CS_SRC_ZERO 0xFFFFFFFFu
+typedef struct {
+    uint32_t n_parts;               /* P >= 1 */
+    uint32_t n_txs;                 /* T >= 1 */
+    const uint32_t* slot_offsets;   /* [h] P + 1: partition p owns slots [slot_offsets[p], slot_offsets[p + 1]) of a transaction */
+    const uint32_t* slot_rank;      /* [h] slot_offsets[P]: the slot's wire is the rank-th `set` of its transaction */
+    const uint32_t* slot_src;       /* [h] slot_offsets[P]: index of its value in the witness block, or HK_R1CS_SRC_ZERO */
+    uint32_t sets_per_tx;           /* O: `set`s of one transaction */
+    uint32_t tx_len;                /* Fr of one witness block */
+    uint32_t tx_stride;             /* Fr from one transaction's block to the next; 0: every transaction reads block 0 */
+    const uint32_t* wit_offsets;    /* [h] P + 1: partition p's witness is [wit_offsets[p], wit_offsets[p + 1]) of a block */
+    const uint32_t* body_len;       /* [h] P: own + owned wires of partition p, wire 0 not counted */
+    const void* witness_mont;       /* [h|d] (n_txs - 1) x tx_stride + tx_len Fr */
+} hk_r1cs_job_desc;                 /* wit_offsets / body_len: read by hk_r1cs_job_witness only */
+hk_status hk_r1cs_job_trace(hk_ctx* ctx, const hk_r1cs_job_desc* desc,
+                            void* time_entries_mont_out /* [h|d] n_txs * slot_offsets[n_parts] x 2 Fr */);
+hk_status hk_r1cs_job_witness(hk_ctx* ctx, const hk_r1cs_job_desc* desc, const uint32_t* sub_index /* [h] batch */,
+                              size_t batch, size_t n_v, size_t body_col0, void* z_out /* [d] batch x n_v Fr */);
+
 #ifdef __cplusplus
 }
 #endif
