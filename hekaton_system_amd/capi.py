@@ -108,6 +108,18 @@ class hk_r1cs_job_desc(C.Structure):          # include/hekaton.h
                 ("wit_offsets", C.c_void_p), ("body_len", C.c_void_p), ("witness_mont", C.c_void_p)]
 
 
+class hk_vkd_desc(C.Structure):               # include/hekaton.h
+    _fields_ = [("depth", C.c_uint32), ("split", C.c_uint32), ("n_updates", C.c_uint32), ("kinds", C.c_void_p),
+                ("leaves", C.c_void_p), ("siblings_mont", C.c_void_p), ("consts_mont", C.c_void_p), ("n_consts", C.c_size_t),
+                ("leaf_hash", C.POINTER(hk_poseidon_desc)), ("node_hash", C.POINTER(hk_poseidon_desc)),
+                ("roots_mont", C.c_void_p), ("n_slots", C.c_uint32), ("slot_addr", C.c_void_p), ("slot_src", C.c_void_p),
+                ("values_mont", C.c_void_p)]
+
+
+class hk_vkd_cols(C.Structure):               # include/hekaton.h
+    _fields_ = [("kind", C.c_uint32), ("hash_col0", C.c_uint32), ("index_col0", C.c_uint32), ("path_col0", C.c_uint32)]
+
+
 class hk_sha_tree_out(C.Structure):           # include/hekaton.h
     _fields_ = [("digests_out", C.c_void_p), ("time_entries_mont_out", C.c_void_p), ("sha_root_mont_out", C.c_void_p)]
 
@@ -138,7 +150,7 @@ EXPORTS = ["hk_status_str", "hk_version", "hk_ctx_create", "hk_ctx_destroy", "hk
            "hk_points_check_g2", "hk_qap_eval", "hk_keygen", "hk_exec_tree", "hk_stage1_witness",
            "hk_trace_sort", "hk_stage0_witness", "hk_r1cs_check", "hk_pk_r1cs_check",
            "hk_sha_tree", "hk_sha_tree_inputs", "hk_ram_stage0_witness", "hk_ram_stage1_witness",
-           "hk_r1cs_job_trace", "hk_r1cs_job_witness"]
+           "hk_r1cs_job_trace", "hk_r1cs_job_witness", "hk_vkd_trace", "hk_vkd_witness"]
 
 HK_VERIFY_CHECK_POINTS = 1
 VERDICT_REJECT, VERDICT_ACCEPT, VERDICT_BAD_POINT = 0, 1, 2
@@ -239,6 +251,8 @@ def load():
     lib.hk_ram_stage1_witness.argtypes = [vp, C.POINTER(hk_ram_stage1_desc), vp, sz, sz, vp]
     lib.hk_r1cs_job_trace.argtypes = [vp, C.POINTER(hk_r1cs_job_desc), vp]
     lib.hk_r1cs_job_witness.argtypes = [vp, C.POINTER(hk_r1cs_job_desc), vp, sz, sz, sz, vp]
+    lib.hk_vkd_trace.argtypes = [vp, C.POINTER(hk_vkd_desc), vp, vp]
+    lib.hk_vkd_witness.argtypes = [vp, C.POINTER(hk_vkd_desc), vp, sz, sz, C.POINTER(hk_vkd_cols), vp]
     _lib = lib
     return lib
 
@@ -921,6 +935,57 @@ class Context:
         zp = z_out.ptr if isinstance(z_out, DeviceBuffer) else int(z_out)
         check(self.lib.hk_r1cs_job_witness(self.handle, C.byref(d), sub_index.ctypes.data if sub_index.size else None,
                                            sub_index.size, int(n_v), int(body_col0), zp), "hk_r1cs_job_witness")
+        return z_out
+
+    def _vkd_desc(self, tables, params, values=None):
+        """(hk_vkd_desc, what must stay alive beside it) from `VkdJob.tables()`, the Poseidon constants
+        (`poseidon.device_params`, the bytes or a DeviceBuffer first) and, for vkd_witness, the value table."""
+        consts, n_consts, ld, nd = params
+        arr = {k: np.ascontiguousarray(tables[k], dtype=np.uint32) for k in ("kinds", "slot_addr", "slot_src")}
+        dev = lambda x: x if x is None or isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
+        keep = [dev(tables["leaves"]), dev(tables["siblings"]), dev(consts), dev(tables["roots"]), dev(values)]
+        a, b = hk_poseidon_desc(*ld), hk_poseidon_desc(*nd)
+        # a NULL table reaches the library as NULL: an empty numpy array has a data pointer all the same
+        p = lambda x: None if x is None else ptr(x).value if (x.nbytes if isinstance(x, DeviceBuffer) else x.size) else None
+        q = lambda x: x.ctypes.data if x.size else None
+        d = hk_vkd_desc(int(tables["depth"]), int(tables["split"]), int(tables["n_updates"]), q(arr["kinds"]), p(keep[0]),
+                        p(keep[1]), p(keep[2]), int(n_consts), C.pointer(a), C.pointer(b), p(keep[3]), arr["slot_addr"].size,
+                        q(arr["slot_addr"]), q(arr["slot_src"]), p(keep[4]))
+        return d, (arr, keep, a, b)
+
+    def vkd_trace(self, tables, params, device_out=False, out=None):
+        """hk_vkd_trace: the value table and the flattened time-ordered ROM trace of a VKD job (vkd_constraints.rs:70-193
+        `get_portal_subtraces`), every hash computed on the device.  tables: `VkdJob.tables()` (leaves / siblings may be
+        DeviceBuffers); params: `poseidon.device_params` with the constants as bytes or a DeviceBuffer.  Returns (values
+        [3 + U (2 + 3 split) Fr], time_entries [n_slots x 2 Fr: what trace_sort(2, ...) / exec_tree / stage0_witness take]) as
+        Montgomery bytes, or as DeviceBuffers when device_out is set; out: a pair of buffers of those sizes to fill instead."""
+        d, keep = self._vkd_desc(tables, params)
+        fr = self.fr_bytes
+        sizes = [(3 + int(tables["n_updates"]) * (2 + 3 * int(tables["split"]))) * fr, 2 * int(d.n_slots) * fr]
+        own = out is None and device_out
+        if out is None:
+            out = tuple(DeviceBuffer(self, max(b, 1)) if device_out else np.zeros(b, dtype=np.uint8) for b in sizes)
+        try:
+            check(self.lib.hk_vkd_trace(self.handle, C.byref(d), ptr(out[0]), ptr(out[1])), "hk_vkd_trace")
+        except HekatonError:
+            if own:
+                for x in out:
+                    x.free()
+            raise
+        return out
+
+    def vkd_witness(self, tables, params, values, sub_index, n_v, cols, z_out):
+        """hk_vkd_witness: column 0 and the body columns of the assignments of the subcircuits `sub_index` of ONE class (any order, repeats
+        allowed; row b of z_out = subcircuit sub_index[b]).  tables, params: as vkd_trace takes them; values: vkd_trace's
+        value table (bytes or a DeviceBuffer); cols: (kind, hash_col0, index_col0, path_col0) - `VkdSubcircuit.device_cols`;
+        z_out: DeviceBuffer (or raw device address) of len(sub_index) x n_v Fr.  Every other column keeps its bytes
+        (stage1_witness writes those)."""
+        d, keep = self._vkd_desc(tables, params, values)
+        sub_index = np.ascontiguousarray(sub_index, dtype=np.uint32)
+        c = cols if isinstance(cols, hk_vkd_cols) else hk_vkd_cols(*[int(x) for x in cols])
+        zp = z_out.ptr if isinstance(z_out, DeviceBuffer) else None if z_out is None else int(z_out)
+        check(self.lib.hk_vkd_witness(self.handle, C.byref(d), sub_index.ctypes.data if sub_index.size else None,
+                                      sub_index.size, int(n_v), C.byref(c), zp), "hk_vkd_witness")
         return z_out
 
     def _r1cs_call(self, fn, head, z, n_v, batch, cap, want_vals):

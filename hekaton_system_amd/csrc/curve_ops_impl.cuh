@@ -202,6 +202,9 @@ struct Ops final : CurveOps {
     // r1cs_job.cuh
     hk_status r1cs_job_trace(hk_ctx*, const hk_r1cs_job_desc*, void*) override;
     hk_status r1cs_job_witness(hk_ctx*, const hk_r1cs_job_desc*, const uint32_t*, size_t, size_t, size_t, void*) override;
+    // vkd.cuh
+    hk_status vkd_trace(hk_ctx*, const hk_vkd_desc*, void*, void*) override;
+    hk_status vkd_witness(hk_ctx*, const hk_vkd_desc*, const uint32_t*, size_t, size_t, const hk_vkd_cols*, void*) override;
 };
 
 }  // namespace hk

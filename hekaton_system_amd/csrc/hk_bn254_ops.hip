@@ -14,6 +14,7 @@
 #include "sha_tree.cuh"
 #include "ram_witness.cuh"
 #include "r1cs_job.cuh"
+#include "vkd.cuh"
 namespace hk {
 extern template struct MsmRun<CurveBn254::Fq>;
 extern template struct MsmRun<CurveBn254::Fq2>;

@@ -723,6 +723,15 @@ hk_status hk_r1cs_job_witness(hk_ctx* ctx, const hk_r1cs_job_desc* desc, const u
     if (!ctx || !desc) return HK_ERR_ARG;
     return ctx->ops->r1cs_job_witness(ctx, desc, sub_index, batch, n_v, body_col0, z_out);
 }
+hk_status hk_vkd_trace(hk_ctx* ctx, const hk_vkd_desc* desc, void* values_mont_out, void* time_entries_mont_out) {
+    if (!ctx || !desc) return HK_ERR_ARG;
+    return ctx->ops->vkd_trace(ctx, desc, values_mont_out, time_entries_mont_out);
+}
+hk_status hk_vkd_witness(hk_ctx* ctx, const hk_vkd_desc* desc, const uint32_t* sub_index, size_t batch, size_t n_v,
+                         const hk_vkd_cols* cols, void* z_out) {
+    if (!ctx || !desc) return HK_ERR_ARG;
+    return ctx->ops->vkd_witness(ctx, desc, sub_index, batch, n_v, cols, z_out);
+}
 
 }  // extern "C"
 

@@ -256,6 +256,10 @@ struct CurveOps {
     virtual hk_status r1cs_job_trace(hk_ctx*, const hk_r1cs_job_desc*, void* time_entries_out) = 0;
     virtual hk_status r1cs_job_witness(hk_ctx*, const hk_r1cs_job_desc*, const uint32_t* sub_index, size_t batch, size_t n_v,
                                        size_t body_col0, void* z_out) = 0;
+    // vkd.cuh
+    virtual hk_status vkd_trace(hk_ctx*, const hk_vkd_desc*, void* values_out, void* time_entries_out) = 0;
+    virtual hk_status vkd_witness(hk_ctx*, const hk_vkd_desc*, const uint32_t* sub_index, size_t batch, size_t n_v,
+                                  const hk_vkd_cols* cols, void* z_out) = 0;
 
 protected:
     CurveOps(size_t fr, size_t fq, size_t g1, size_t g2, size_t gt)

@@ -769,6 +769,69 @@ hk_status hk_r1cs_job_trace(hk_ctx* ctx, const hk_r1cs_job_desc* desc,
 hk_status hk_r1cs_job_witness(hk_ctx* ctx, const hk_r1cs_job_desc* desc, const uint32_t* sub_index /* [h] batch */,
                               size_t batch, size_t n_v, size_t body_col0, void* z_out /* [d] batch x n_v Fr */);
 
+/* ---- the verifiable key directory job (distributed-prover/src/vkd/vkd.rs:362-617 `vkd_update_to_subcircuit`,
+ * vkd_constraints.rs:70-193 `get_portal_subtraces`, :237-342 `generate_constraints`; vkd/hash.rs) --------------------------------
+ * A batch of U directory updates over a sparse Merkle tree of `depth` levels (hekaton_system_amd/vkd_circuit.py `VkdJob`): a
+ * leaf is 66 bytes, hashed at rate 3 over its 27-byte chunks; a node is the low 216 bits of a digest; an update is two paths of
+ * `depth` two-to-one hashes cut into `split` segments of L = depth / split levels, level l from the leaf using bit l of the
+ * user's index (bit 1: the current node is the right child).  N = 8 + 2 split U subcircuits: 6 paddings, write-pp, 2 split per
+ * update, the final equality.  The descriptor states the job once; every traced value lives once in the VALUE TABLE of
+ * V = 3 + U (2 + 3 split) Fr:
+ *     0 initial root   1 final root   2 null leaf (the leaf hash of 32 zero bytes)
+ *     base(u) = 3 + u (2 + 3 split):  + 0 hash of leaf_old (0 for an append)  + 1 hash of leaf_new  + 2 + s index word s
+ *                                     + 2 + split + p split + s the node after segment s of path p (p = 0 old, 1 new)
+ * and time-ordered slot e of the whole job is (slot_addr[e], value[slot_src[e]]), or 0 for HK_VKD_SRC_ZERO (the paddings'
+ * dummies): the host resolves names to addresses and sources, as `SetupRomPortalManager` does.
+ * hk_vkd_trace computes the value table (roots copied from roots_mont; every hash on the device: one quad of lanes per leaf /
+ * username hash, one quad per (update, path) for the chain of `depth` dependent hashes - path 0 of an append starts from the
+ * null leaf) and the flattened trace: n_slots (addr, val) pairs, what hk_trace_sort(2, ...), hk_exec_tree and hk_stage0_witness
+ * take.  values_mont is not read.
+ * hk_vkd_witness writes, into row b of z_out for subcircuit i = sub_index[b] (any order, repeats allowed, all of the ONE class
+ * cols->kind), column 0 <- 1 and the BODY columns of VkdSubcircuit: at hash_col0 the "hash leaf" part (528 leaf bit columns, the permutation's
+ * trace in hk_poseidon_path's order, the digest's bits, the canon columns), at index_col0 the "get index" part (trace, bits,
+ * canon), at path_col0 the "compute path" part (L index bits; per level sibling, left, trace, bits, canon and - but for the
+ * last level - the next node).  A segment starts from the value its `get` slot names in values_mont.  Every other column
+ * keeps its bytes: hk_stage1_witness on the same rows completes the assignment.  A class without body columns (padding, write
+ * pp, equality) gets its column 0 only.
+ * Both calls run on the caller's lane; host-resident arrays are staged in lane scratch, device-resident ones read in place.
+ * One lane per Fr of the trace and four lanes per hash chain: 2 n_slots and 4 batch lanes stay below 2^31.
+ * HK_ERR_ARG / HK_ERR_LEN, before any device work and with the outputs untouched: a NULL pointer; split < 2, depth 0, above
+ * 256, no multiple of 8 split, or L < 8; n_updates 0 or above 2^20; a kind that is neither HK_VKD_APPEND nor HK_VKD_UPDATE;
+ * N above 2^24; n_slots 0 or >= 2^30 (LEN); a slot_src that is neither HK_VKD_SRC_ZERO nor < V; Poseidon descriptors other
+ * than the two instances hk_exec_tree takes; an output range that overlaps an input or the other output.  hk_vkd_witness
+ * also: values_mont NULL; cols->kind no class; batch >= 2^20, n_v 0 or >= 2^31 or batch x n_v >= 2^38 (LEN); a part of the class
+ * that does not fit [1, n_v) or overlaps the part before it (LEN); n_slots other than the layout's; sub_index[b] >= N or of
+ * another class than cols->kind; z_out not in device memory. */
+#define HK_VKD_SRC_ZERO 0xFFFFFFFFu
+#define HK_VKD_APPEND 0u
+#define HK_VKD_UPDATE 1u
+typedef struct {
+    uint32_t depth;                 /* levels of the sparse tree */
+    uint32_t split;                 /* segments of a path */
+    uint32_t n_updates;             /* U */
+    const uint32_t* kinds;          /* [h] U: HK_VKD_APPEND / HK_VKD_UPDATE */
+    const uint8_t* leaves;          /* [h|d] U x 2 x 66 bytes: leaf_old (zeros for an append), leaf_new */
+    const void* siblings_mont;      /* [h|d] U x depth Fr: the update's siblings, the leaf's first */
+    const void* consts_mont; size_t n_consts;                               /* [h|d] as hk_poseidon_path / hk_exec_tree */
+    const hk_poseidon_desc* leaf_hash; const hk_poseidon_desc* node_hash;
+    const void* roots_mont;         /* [h] 2 Fr: initial root, final root */
+    uint32_t n_slots;               /* time-ordered entries of the whole job */
+    const uint32_t* slot_addr;      /* [h] n_slots */
+    const uint32_t* slot_src;       /* [h] n_slots: index into the value table, or HK_VKD_SRC_ZERO */
+    const void* values_mont;        /* [h|d] V Fr: hk_vkd_trace's values_mont_out; read by hk_vkd_witness only */
+} hk_vkd_desc;
+typedef struct {
+    uint32_t kind;                  /* 0 padding, 1 write pp, 2 hash leaf + get index + compute path, 3 compute path,
+                                       4 compute path + equality, 5 equality + hash leaf + compute path, 6 equality */
+    uint32_t hash_col0;             /* first column of the "hash leaf" part (kinds 2, 5) */
+    uint32_t index_col0;            /* first column of the "get index" part (kind 2) */
+    uint32_t path_col0;             /* first column of the "compute path" part (kinds 2 .. 5) */
+} hk_vkd_cols;
+hk_status hk_vkd_trace(hk_ctx* ctx, const hk_vkd_desc* desc, void* values_mont_out /* [h|d] V Fr */,
+                       void* time_entries_mont_out /* [h|d] n_slots x 2 Fr */);
+hk_status hk_vkd_witness(hk_ctx* ctx, const hk_vkd_desc* desc, const uint32_t* sub_index /* [h] batch */, size_t batch,
+                         size_t n_v, const hk_vkd_cols* cols, void* z_out /* [d] batch x n_v Fr */);
+
 #ifdef __cplusplus
 }
 #endif
