@@ -10,7 +10,8 @@
                                     terms, the s/t combination, com_lr, z_lr - i.e. the TIPA instance and witness
 
 All group arithmetic runs on the GPU: multi-pairings (hk_pairing_products), element-wise scalar multiplications
-(hk_scalar_pairing), element-wise linear combinations (hk_points_lincomb).  GT products / powers of commitments
+(hk_scalar_pairing), element-wise linear combinations (hk_points_lincomb); so do the twist powers they sweep with
+(hk_scalar_powers; HK_AGG_HOST_SCALARS=1 in the environment keeps the Python loop).  GT products / powers of commitments
 (three per job) are host arithmetic (gt.py).  The Fiat-Shamir challenges r (twist), s, t come from a merlin transcript
 (merlin.py, pinned by merlin's known-answer test) when `pt` is given, else they are arguments.  `TIPA::prove / verify`
 (the GIPA recursion of the third-party `ripp` crate, absent from /root/reference) are tipa.py; `agg_subcircuit_proofs`
@@ -18,6 +19,7 @@ joins the two as aggregation.rs:138-345 does.  PARITY UNPINNED for the snarkpack
 restated from the SnarkPack paper); what the tests pin is the reference's own debug assertions
 (aggregation.rs:208-216,246-253,265-269) holding on proofs made by this prover.
 """
+import os
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
 
@@ -50,6 +52,31 @@ def tipa_commitment_key(ctx, curve, n, a, b):
     G1, G2 = fc.g1(p["g1"]), fc.g2(p["g2"])
     return IPCommKey(v1=np.asarray(ctx.fixed_base(2, G2, fc.enc(pa[:n]))), v2=np.asarray(ctx.fixed_base(2, G2, fc.enc(pb[:n]))),
                      w1=np.asarray(ctx.fixed_base(1, G1, fc.enc(pa[n:]))), w2=np.asarray(ctx.fixed_base(1, G1, fc.enc(pb[n:]))), n=n)
+
+
+def host_scalars():
+    """HK_AGG_HOST_SCALARS=1: the aggregator's scalar vectors (twist / trapdoor powers, KZG quotients) are built by the Python
+    loops and uploaded, instead of hk_scalar_powers / hk_ipa_quotient - the A/B switch of tools/agg_scalars_bench.py and the
+    in-process reference of the tests.  The outputs are the same bytes either way.  Read at every call."""
+    return bool(os.environ.get("HK_AGG_HOST_SCALARS"))
+
+
+def twist_powers(ctx, fc, twist, n, reps=1):
+    """`structured_scalar_power` (pairing_ops.rs:42-48) as the element-wise sweeps take it: the Montgomery bytes of
+    twist^0 .. twist^(n - 1), `reps` times back to back.  A DeviceBuffer (hk_scalar_powers; the caller frees it), or host
+    bytes under HK_AGG_HOST_SCALARS."""
+    if host_scalars():
+        tw = [fc.R % fc.r] * n                                # R * twist^i: Montgomery values as they come
+        for i in range(1, n):
+            tw[i] = tw[i - 1] * twist % fc.r
+        return np.tile(fc.enc_canon(tw), reps)
+    from .capi import DeviceBuffer
+    buf = DeviceBuffer(ctx, reps * n * ctx.fr_bytes)
+    try:
+        return ctx.scalar_powers(twist, n, reps, out=buf)
+    except Exception:
+        buf.free()
+        raise
 
 
 class IppCom:
@@ -222,15 +249,17 @@ class AggProvingKey:
             pt.append_serializable(b"D-commitment", com_d.serialize_uncompressed())
             twist = pt.challenge_scalar(b"r-random-fiatshamir", r_mod)
         prepared_input, com_prepared_input = f_in.result(), f_cin.result()
-        tw = [fc.R % r_mod] * n                               # :224 structured_scalar_power, as Montgomery values R * twist^i
-        for i in range(1, n):
-            tw[i] = tw[i - 1] * twist % r_mod
-        twb = fc.enc_canon(tw)
         # the five twisted G1 vectors (:236-242: five `scalar_pairing` sweeps with the same powers) as ONE sweep of 5 n
-        # elements: one launch and one normalisation instead of five side by side
+        # elements: one launch and one normalisation instead of five side by side; the powers (:224
+        # structured_scalar_power) five times back to back, left where the sweep reads them
         g1b = ctx.g1_bytes
-        swept = ctx.scalar_pairing(1, np.concatenate([a_vals, c_vals, d_vals, self.alpha, np.asarray(prepared_input, np.uint8)]),
-                                   np.tile(twb, 5), 5 * n)
+        tw5 = twist_powers(ctx, fc, twist, n, 5)
+        try:
+            swept = ctx.scalar_pairing(1, np.concatenate([a_vals, c_vals, d_vals, self.alpha, np.asarray(prepared_input, np.uint8)]),
+                                       tw5, 5 * n)
+        finally:
+            if hasattr(tw5, "free"):
+                tw5.free()
         a_r, c_r, d_r, alpha_r, input_r = (swept[j * n * g1b:(j + 1) * n * g1b] for j in range(5))
         f_cross = go(ctx.pairing_products, [a_r, input_r, d_r, c_r], [b_vals, self.h, self.delta0, self.delta1], n)   # :255-263
         f_ab_z = go(ctx.multi_pairing, alpha_r, self.beta, n)

@@ -150,7 +150,8 @@ EXPORTS = ["hk_status_str", "hk_version", "hk_ctx_create", "hk_ctx_destroy", "hk
            "hk_points_check_g2", "hk_qap_eval", "hk_keygen", "hk_exec_tree", "hk_stage1_witness",
            "hk_trace_sort", "hk_stage0_witness", "hk_r1cs_check", "hk_pk_r1cs_check",
            "hk_sha_tree", "hk_sha_tree_inputs", "hk_ram_stage0_witness", "hk_ram_stage1_witness",
-           "hk_r1cs_job_trace", "hk_r1cs_job_witness", "hk_vkd_trace", "hk_vkd_witness"]
+           "hk_r1cs_job_trace", "hk_r1cs_job_witness", "hk_vkd_trace", "hk_vkd_witness",
+           "hk_scalar_powers", "hk_ipa_quotient"]
 
 HK_VERIFY_CHECK_POINTS = 1
 VERDICT_REJECT, VERDICT_ACCEPT, VERDICT_BAD_POINT = 0, 1, 2
@@ -253,6 +254,8 @@ def load():
     lib.hk_r1cs_job_witness.argtypes = [vp, C.POINTER(hk_r1cs_job_desc), vp, sz, sz, sz, vp]
     lib.hk_vkd_trace.argtypes = [vp, C.POINTER(hk_vkd_desc), vp, vp]
     lib.hk_vkd_witness.argtypes = [vp, C.POINTER(hk_vkd_desc), vp, sz, sz, C.POINTER(hk_vkd_cols), vp]
+    lib.hk_scalar_powers.argtypes = [vp, vp, sz, sz, vp]
+    lib.hk_ipa_quotient.argtypes = [vp, vp, sz, vp, vp, sz, vp]
     _lib = lib
     return lib
 
@@ -399,6 +402,30 @@ class Context:
         fn = self.lib.hk_scalar_pairing_g1 if group == 1 else self.lib.hk_scalar_pairing_g2
         res = out if out is not None else np.zeros(n * pb, dtype=np.uint8)
         check(fn(self.handle, ptr(points), ptr(scalars), n, ptr(res)), fn.__name__)
+        return res
+
+    def scalar_powers(self, x, n, reps=1, out=None):
+        """hk_scalar_powers: `structured_scalar_power` (distributed-prover/src/pairing_ops.rs:42-48) - the Montgomery bytes of
+        x^0 .. x^(n - 1) (x an int), `reps` times back to back.  `out` may be a DeviceBuffer / DeviceView of reps * n Fr (the
+        result stays in HBM); otherwise a numpy array is returned."""
+        from .cp_groth16 import FrCodec
+        xb = FrCodec(self.curve).enc1(x)
+        res = out if out is not None else np.zeros(reps * n * self.fr_bytes, dtype=np.uint8)
+        check(self.lib.hk_scalar_powers(self.handle, xb.ctypes.data, int(n), int(reps), ptr(res)), "hk_scalar_powers")
+        return res
+
+    def ipa_quotient(self, challenges, rho, z, shift=0, out=None):
+        """hk_ipa_quotient: the Montgomery bytes of the quotient of X^shift prod_k (1 + challenges[k] (rho X)^(2^k)) by
+        (X - z), one zero appended: shift + 2^len(challenges) Fr (kzg.rs:122-141).  challenges, rho, z: ints.  `out` may be
+        a DeviceBuffer / DeviceView of that size (the result stays in HBM); otherwise a numpy array is returned."""
+        from .cp_groth16 import FrCodec
+        fc = FrCodec(self.curve)
+        challenges = list(challenges)
+        l = len(challenges)
+        ch, rb, zb = fc.enc(challenges), fc.enc1(rho), fc.enc1(z)
+        res = out if out is not None else np.zeros((shift + (1 << l)) * self.fr_bytes, dtype=np.uint8)
+        check(self.lib.hk_ipa_quotient(self.handle, ch.ctypes.data if l else None, l, rb.ctypes.data, zb.ctypes.data, int(shift),
+                                       ptr(res)), "hk_ipa_quotient")
         return res
 
     def gt_pow(self, gts, scalars, in_gt=True):

@@ -732,6 +732,15 @@ hk_status hk_vkd_witness(hk_ctx* ctx, const hk_vkd_desc* desc, const uint32_t* s
     if (!ctx || !desc) return HK_ERR_ARG;
     return ctx->ops->vkd_witness(ctx, desc, sub_index, batch, n_v, cols, z_out);
 }
+hk_status hk_scalar_powers(hk_ctx* ctx, const void* x_mont, size_t n, size_t reps, void* out) {
+    if (!ctx) return HK_ERR_ARG;
+    return ctx->ops->scalar_powers(ctx, x_mont, n, reps, out);
+}
+hk_status hk_ipa_quotient(hk_ctx* ctx, const void* challenges_mont, size_t l, const void* rho_mont, const void* z_mont,
+                          size_t shift, void* q_out) {
+    if (!ctx) return HK_ERR_ARG;
+    return ctx->ops->ipa_quotient(ctx, challenges_mont, l, rho_mont, z_mont, shift, q_out);
+}
 
 }  // extern "C"
 

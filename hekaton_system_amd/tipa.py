@@ -20,17 +20,19 @@ Prover: B' = B^(r^i), w' = w^(r^-i) (so the commitment of (A, B') under (v, w') 
     finally KZG openings of the folded keys at a random point against
         f_v(X) = prod_k (1 + c_(l-1-k)^-1 X^(2^k)),     f_w(X) = X^n prod_k (1 + c_(l-1-k) (X / r)^(2^k)).
 GPU work per round: 10 multi-pairings of n/2 pairs (two hk_pairing_products calls), 6 element-wise folds
-(hk_points_lincomb); at the end four MSMs over the resident SRS (hk_msm_bases).
+(hk_points_lincomb); at the end four MSMs over the resident SRS (hk_msm_bases).  The scalar vectors - the trapdoor powers
+of `setup`, the twist powers and the two KZG quotients of `prove` - are built on the device too (hk_scalar_powers,
+hk_ipa_quotient) and read where they lie; HK_AGG_HOST_SCALARS=1 in the environment keeps the Python loops.
 """
 import hashlib
 import os
 import time
-from concurrent.futures import ThreadPoolExecutor
+from concurrent.futures import ThreadPoolExecutor, wait
 from dataclasses import dataclass, field
 
 import numpy as np
 
-from .aggregation import IPCommKey, TIPPCommitment
+from .aggregation import IPCommKey, TIPPCommitment, host_scalars
 from .cp_groth16 import CURVE_PARAMS, FrCodec
 from .gt import GtField
 
@@ -54,16 +56,37 @@ def setup(ctx, curve, n, alpha, beta):
     p = CURVE_PARAMS[curve]
     fc = FrCodec(curve)
     r = p["r"]
-    pa, pb = [fc.R % r] * (2 * n), [fc.R % r] * (2 * n)              # R * alpha^i: Montgomery values as they come
-    for i in range(1, 2 * n):
-        pa[i] = pa[i - 1] * alpha % r
-        pb[i] = pb[i - 1] * beta % r
     G1, G2 = fc.g1(p["g1"]), fc.g2(p["g2"])
+    fr = ctx.fr_bytes
+    scalars = None
+    if host_scalars():
+        pa, pb = [fc.R % r] * (2 * n), [fc.R % r] * (2 * n)          # R * alpha^i: Montgomery values as they come
+        for i in range(1, 2 * n):
+            pa[i] = pa[i - 1] * alpha % r
+            pb[i] = pb[i - 1] * beta % r
+        sc1, sc2 = fc.enc_canon(pa + pb), fc.enc_canon(pa[:n] + pb[:n])
+    else:
+        # alpha^i | beta^i, 2 n each for G1 and n each for G2, written where the two sweeps read them
+        from .capi import DeviceBuffer
+        scalars = DeviceBuffer(ctx, 6 * n * fr)
+        sc1, sc2 = scalars.view(0, 4 * n * fr), scalars.view(4 * n * fr, 2 * n * fr)
+    try:
+        return _setup(ctx, n, alpha, beta, G1, G2, sc1, sc2)
+    finally:
+        if scalars is not None:                                       # every call that read it has returned
+            scalars.free()
+
+
+def _setup(ctx, n, alpha, beta, G1, G2, sc1, sc2):
+    fr = ctx.fr_bytes
+    if not isinstance(sc1, np.ndarray):
+        for buf, m, x, off in ((sc1, 2 * n, alpha, 0), (sc1, 2 * n, beta, 2 * n), (sc2, n, alpha, 0), (sc2, n, beta, n)):
+            ctx.scalar_powers(x, m, 1, buf.view(off * fr, m * fr))
     # two fixed-base sweeps (one per generator: its window table is built once, or comes from the context's cache), then
     # four uploads: issued together (one lane each)
     with ThreadPoolExecutor(max_workers=4) as pool:
-        f1 = pool.submit(ctx.fixed_base, 1, G1, fc.enc_canon(pa + pb))
-        f2 = pool.submit(ctx.fixed_base, 2, G2, fc.enc_canon(pa[:n] + pb[:n]))
+        f1 = pool.submit(ctx.fixed_base, 1, G1, sc1, 4 * n)
+        f2 = pool.submit(ctx.fixed_base, 2, G2, sc2, 2 * n)
         g1b, g2b = ctx.g1_bytes, ctx.g2_bytes
         g_ab, h_ab = np.asarray(f1.result()), np.asarray(f2.result())
         g_a, g_b = g_ab[:2 * n * g1b], g_ab[2 * n * g1b:]
@@ -129,6 +152,40 @@ def _divide_by_linear(coeffs, z, mod):
         acc = (coeffs[i] + acc * z) % mod
         q[i - 1] = acc
     return q                      # q[n-1] = 0: same length as the SRS slice, as kzg.rs:133-135 resizes it
+
+
+def twist_vectors(ctx, fc, twist, twist_inv, n, out=None):
+    """(twist^i, twist^-i), i < n, as Montgomery bytes: what `prove` sweeps B and the w-keys with.  On the device
+    (hk_scalar_powers) into the two windows `out` of n Fr each, which are returned; under HK_AGG_HOST_SCALARS the Python
+    loop's host bytes.  The two calls go out one after the other: each is shorter than a hand-over to the pool."""
+    if host_scalars():
+        r = fc.r
+        vecs = []
+        for x in (twist, twist_inv):
+            pw = [fc.R % r] * n                   # R * x^i: the Montgomery bytes with no product beyond the power itself
+            for i in range(1, n):
+                pw[i] = pw[i - 1] * x % r
+            vecs.append(fc.enc_canon(pw))
+        return tuple(vecs)
+    ctx.scalar_powers(twist, n, 1, out[0])
+    ctx.scalar_powers(twist_inv, n, 1, out[1])
+    return tuple(out)
+
+
+def opening_quotients(ctx, fc, challenges, twist_inv, z, n, out=None):
+    """The KZG witness polynomials of the folded keys (kzg.rs:122-141) as Montgomery bytes: q_v = f_v / (X - z) (n Fr) and
+    q_w = f_w / (X - z) (2 n Fr), from the rounds' challenges in the order they were drawn.  On the device (hk_ipa_quotient)
+    into the two windows `out`, which are returned; under HK_AGG_HOST_SCALARS the Python loops' host bytes."""
+    r = fc.r
+    ch_rev = challenges[::-1]
+    chi_rev = [pow(c, -1, r) for c in ch_rev]
+    if host_scalars():
+        fv = ipa_polynomial_coeffs(chi_rev, 1, r, fc.R)                    # R f(X): the quotients are Montgomery values
+        fw = [0] * n + ipa_polynomial_coeffs(ch_rev, twist_inv, r, fc.R)
+        return fc.enc_canon(_divide_by_linear(fv, z, r)), fc.enc_canon(_divide_by_linear(fw, z, r))
+    ctx.ipa_quotient(chi_rev, 1, z, 0, out[0])
+    ctx.ipa_quotient(ch_rev, twist_inv, z, n, out[1])
+    return tuple(out)
 
 
 # vectors of the recursion, by their index in the arena: G1 vectors fold with the challenge c, G2 vectors with 1 / c
@@ -265,67 +322,67 @@ class Tipp:
         h = len(buf) // 2
         return buf[:h], buf[h:]
 
-    def _powers(self, x, n, first=1):
-        out = [first % self.r] * n
-        for i in range(1, n):
-            out[i] = out[i - 1] * x % self.r
-        return out
-
     # ---- prove ------------------------------------------------------------------------------------------
     def prove(self, srs, A, B, twist, com, z_ab):
         """A: n G1, B: n G2 (packed affine bytes); com: IppCom (T, U[, ip]) of (A, B) under srs.ck; z_ab: the twisted
         inner product (GT tuple).  Returns the proof dict."""
         ctx, fc, F, r = self.ctx, self.fc, self.F, self.r
         n = srs.n
-        g1b, g2b = ctx.g1_bytes, ctx.g2_bytes
-        from .capi import DeviceBuffer
+        g1b, g2b, frb = ctx.g1_bytes, ctx.g2_bytes, ctx.fr_bytes
+        from .capi import DeviceBuffer, check, load
         t_start = time.perf_counter()
         r_inv = pow(twist, -1, r)
-        # R * twist^i: the Montgomery bytes of the powers with no product per element beyond the power itself
-        twb, twib = fc.enc_canon(self._powers(twist, n, fc.R)), fc.enc_canon(self._powers(r_inv, n, fc.R))
+        host = host_scalars()
         # The six vectors of the recursion live in HBM from here to the last round (one allocation, carved up front: a
         # vector of m elements is followed by its folds of m/2, m/4, ... elements): a round's calls take windows of it and
-        # write the folded halves next to them, nothing is downloaded until the single final elements.
+        # write the folded halves next to them, nothing is downloaded until the single final elements.  Behind them the
+        # scalar vectors of the device path: twist^i, twist^-i (n Fr each), the quotients q_v (n) and q_w (2 n).
         sizes = [g1b, g2b, g2b, g2b, g1b, g1b]                              # a, b', v1, v2, w1', w2'
-        arena = DeviceBuffer(ctx, sum(2 * n * sz for sz in sizes))
-        base, off = [], 0
-        for sz in sizes:
-            base.append(off)
-            off += 2 * n * sz
-        win = lambda k, start, count: arena.view(base[k] + start * sizes[k], count * sizes[k])
-        go = self.pool.submit
-        # B' = B^(r^i), w' = w^(r^-i): three independent element-wise sweeps, issued together; A, v1, v2 are copied in
-        first = [go(ctx.scalar_pairing, 2, B, twb, n, win(1, 0, n)),
-                 go(ctx.scalar_pairing, 1, srs.ck.w1, twib, n, win(4, 0, n)),
-                 go(ctx.scalar_pairing, 1, srs.ck.w2, twib, n, win(5, 0, n))]
-        for k, src in ((0, np.asarray(A)), (2, srs.ck.v1), (3, srs.ck.v2)):
-            src = np.ascontiguousarray(src, dtype=np.uint8)
-            from .capi import check, load
-            check(load().hk_dev_upload(ctx.handle, win(k, 0, n).ptr, src.ctypes.data, src.nbytes), "hk_dev_upload")
-        for f in first:
-            f.result()
-        tr = Transcript(r)
-        tr.absorb(b"instance", F.encode(com.t), F.encode(com.u), F.encode(z_ab), twist.to_bytes(32, "little"), n.to_bytes(8, "little"))
-        rounds, challenges = [], []
-        self.round_times = []                                               # (m, pairings s, host s, folds s) per round
-        t_rounds = time.perf_counter()
-        paired = not os.environ.get("HK_TIPP_SINGLE_ROUNDS")
-        pos = gipa_rounds(ctx, F, fc, r, win, n, tr, go, rounds, challenges, self.round_times, paired)
-        t_open = time.perf_counter()
-        a, b, v1, v2, w1, w2 = (win(k, pos, 1).to_host() for k in range(6))
-        arena.free()
-        tr.absorb(b"final", a, b, v1, v2, w1, w2)
-        z = tr.challenge(b"kzg-point")
-        ch_rev = challenges[::-1]
-        chi_rev = [pow(c, -1, r) for c in ch_rev]
-        # KZG openings of the folded keys (kzg.rs:46-70): quotient polynomials, MSMs over the resident SRS powers
-        fv = ipa_polynomial_coeffs(chi_rev, 1, r, fc.R)                    # R f(X): the quotients are Montgomery values
-        qv = fc.enc_canon(_divide_by_linear(fv, z, r))
-        fw = [0] * n + ipa_polynomial_coeffs(ch_rev, r_inv, r, fc.R)
-        qw = fc.enc_canon(_divide_by_linear(fw, z, r))
-        res = srs.resident
-        opens = [self.pool.submit(res[k].msm, q) for k, q in (("h_alpha", qv), ("h_beta", qv), ("g_alpha", qw), ("g_beta", qw))]
-        ov1, ov2, ow1, ow2 = (f.result() for f in opens)                   # four independent MSMs, issued together
+        vec_bytes = sum(2 * n * sz for sz in sizes)
+        arena = DeviceBuffer(ctx, vec_bytes + (0 if host else 5 * n * frb))
+        pending = []                                                        # every call handed to the pool
+
+        def go(fn, *args):
+            pending.append(self.pool.submit(fn, *args))
+            return pending[-1]
+        try:
+            base, off = [], 0
+            for sz in sizes:
+                base.append(off)
+                off += 2 * n * sz
+            win = lambda k, start, count: arena.view(base[k] + start * sizes[k], count * sizes[k])
+            scal = lambda start, count: arena.view(vec_bytes + start * n * frb, count * n * frb)
+            twb, twib = twist_vectors(ctx, fc, twist, r_inv, n, None if host else (scal(0, 1), scal(1, 1)))
+            # B' = B^(r^i), w' = w^(r^-i): three independent element-wise sweeps, issued together; A, v1, v2 are copied in
+            first = [go(ctx.scalar_pairing, 2, B, twb, n, win(1, 0, n)),
+                     go(ctx.scalar_pairing, 1, srs.ck.w1, twib, n, win(4, 0, n)),
+                     go(ctx.scalar_pairing, 1, srs.ck.w2, twib, n, win(5, 0, n))]
+            for k, src in ((0, np.asarray(A)), (2, srs.ck.v1), (3, srs.ck.v2)):
+                src = np.ascontiguousarray(src, dtype=np.uint8)
+                check(load().hk_dev_upload(ctx.handle, win(k, 0, n).ptr, src.ctypes.data, src.nbytes), "hk_dev_upload")
+            for f in first:
+                f.result()
+            tr = Transcript(r)
+            tr.absorb(b"instance", F.encode(com.t), F.encode(com.u), F.encode(z_ab), twist.to_bytes(32, "little"), n.to_bytes(8, "little"))
+            rounds, challenges = [], []
+            self.round_times = []                                           # (m, pairings s, host s, folds s) per round
+            t_rounds = time.perf_counter()
+            paired = not os.environ.get("HK_TIPP_SINGLE_ROUNDS")
+            pos = gipa_rounds(ctx, F, fc, r, win, n, tr, go, rounds, challenges, self.round_times, paired)
+            t_open = time.perf_counter()
+            a, b, v1, v2, w1, w2 = (win(k, pos, 1).to_host() for k in range(6))
+            tr.absorb(b"final", a, b, v1, v2, w1, w2)
+            z = tr.challenge(b"kzg-point")
+            # KZG openings of the folded keys (kzg.rs:46-70): quotient polynomials, MSMs over the resident SRS powers, which
+            # read the quotients where they lie
+            qv, qw = opening_quotients(ctx, fc, challenges, r_inv, z, n, None if host else (scal(2, 1), scal(3, 2)))
+            res = srs.resident
+            opens = [go(res[k].msm, q, m) for k, q, m in (("h_alpha", qv, n), ("h_beta", qv, n), ("g_alpha", qw, 2 * n),
+                                                          ("g_beta", qw, 2 * n))]
+            ov1, ov2, ow1, ow2 = (f.result() for f in opens)               # four independent MSMs, issued together
+        finally:
+            wait(pending)                                                   # no call may outlive the memory it works on
+            arena.free()
         self.phase_times = (t_rounds - t_start, t_open - t_rounds, time.perf_counter() - t_open)   # setup, rounds, openings
         proof = dict(rounds=rounds, final_a=a, final_b=b, final_v=(v1, v2), final_w=(w1, w2),
                      open_v=(ov1, ov2), open_w=(ow1, ow2))

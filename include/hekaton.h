@@ -832,6 +832,25 @@ hk_status hk_vkd_trace(hk_ctx* ctx, const hk_vkd_desc* desc, void* values_mont_o
 hk_status hk_vkd_witness(hk_ctx* ctx, const hk_vkd_desc* desc, const uint32_t* sub_index /* [h] batch */, size_t batch,
                          size_t n_v, const hk_vkd_cols* cols, void* z_out /* [d] batch x n_v Fr */);
 
+/* ---- the aggregator's scalar vectors ------------------------------------------------------------
+ * What `TIPA::setup`, `agg_subcircuit_proofs` and `TIPA::prove` build one field product at a time on the host: the powers of
+ * a trapdoor or of the twist, and the two KZG witness polynomials of the folded keys.  Both results may stay on the device,
+ * where hk_fixed_base_*, hk_scalar_pairing_* and hk_msm_bases read them.
+ *
+ * out[j * n + i] = x^i (Fr, Montgomery), i < n, j < reps - `structured_scalar_power` (pairing_ops.rs:42-48); reps > 1
+ * repeats the vector back to back (agg_front sweeps five G1 vectors with the same powers).
+ * x_mont [h]: one Fr; out [h|d]: reps * n Fr.  n == 0 or reps == 0: HK_OK, nothing written.
+ * HK_ERR_ARG (nothing written): a null pointer, n > 2^27, reps > 65535, reps * n > 2^27. */
+hk_status hk_scalar_powers(hk_ctx* ctx, const void* x_mont, size_t n, size_t reps, void* out);
+
+/* Quotient of f(X) = X^shift * prod_{k < l} (1 + c_k (rho X)^(2^k)) by (X - z), remainder dropped, padded with one zero to
+ * f's own length shift + 2^l - the witness polynomial of kzg.rs:122-141 for f_v (rho = 1, shift = 0, inverse challenges
+ * reversed) and f_w (rho = 1 / twist, shift = n).  challenges_mont [h]: l Fr; rho_mont, z_mont [h]: one Fr each;
+ * q_out [h|d]: shift + 2^l Fr, Montgomery: what hk_msm_bases takes with mont = 1.
+ * HK_ERR_ARG (nothing written): a null pointer, l > 26, shift + 2^l > 2^27. */
+hk_status hk_ipa_quotient(hk_ctx* ctx, const void* challenges_mont, size_t l, const void* rho_mont, const void* z_mont,
+                          size_t shift, void* q_out);
+
 #ifdef __cplusplus
 }
 #endif
