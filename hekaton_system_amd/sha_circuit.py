@@ -38,7 +38,11 @@ import os
 
 import numpy as np
 
-from .cp_groth16 import CURVE_PARAMS, FrCodec, MultiStageConstraintSynthesizer
+from . import capi
+from .cp_groth16 import CURVE_PARAMS, FrCodec
+from .poseidon import ExecTree, device_params
+from .portal_circuit import (ONE, PortalStage0Device, PortalStage1Device, PortalSubcircuit, R1csUnsatisfied,      # noqa: F401
+                             poseidon_path_root, poseidon_path_trace, rom_inputs)
 
 K256 = [
     0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01,
@@ -50,7 +54,6 @@ K256 = [
     0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2]
 IV256 = [0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19]
 INNER_HASH_SIZE = 27          # bytes of the digest that become the node hash (vkd/sparse_tree.rs:42)
-ONE = 0                       # column of the constant 1
 
 
 class Word:
@@ -391,135 +394,25 @@ class Tape:
         return out
 
 
-def poseidon_path_trace(leaf_cfg, node_cfg, leaf, siblings, index):
-    """Every witness of the membership block of one subcircuit, in allocation order (= what `k_poseidon_path` writes):
-    the leaf hash's permutation traces, then per level (bit, sibling, left, the two-to-one hash's trace).  The last
-    value is the root the path leads to."""
-    out = []
-    cur = leaf_cfg.crh(leaf, out)
-    for lvl, sib in enumerate(siblings):
-        bit = (index >> lvl) & 1
-        left, right = (sib, cur) if bit else (cur, sib)
-        out += [bit, sib % leaf_cfg.p, left]
-        cur = node_cfg.crh([left, right], out)
-    return out
-
-
-def poseidon_path_root(leaf_cfg, node_cfg, leaf, siblings, index):
-    cur = leaf_cfg.crh(leaf)
-    for lvl, sib in enumerate(siblings):
-        cur = node_cfg.crh([sib, cur] if (index >> lvl) & 1 else [cur, sib])
-    return cur
-
-
 # ---------------------------------------------------------------------------------------------------------------------
-class ShaMerkleSubcircuit(MultiStageConstraintSynthesizer):
+class ShaMerkleSubcircuit(PortalSubcircuit):
     """One proving-key class of the re-implemented big-merkle circuit.  kind: "leaf" | "parent" | "root" | "padding";
     `first` marks subcircuit 0 (evals pinned to 1), `last` the final subcircuit (time eval == addr eval)."""
-    N_INST = 4
 
     def __init__(self, curve, kind, ns, n_portals, first=False, last=False, depth=3):
         """depth = log2(number of subcircuits): the length of the execution tree's membership path."""
         assert kind in ("leaf", "parent", "root", "padding")
-        self.curve, self.kind, self.ns, self.np_, self.first, self.last = curve, kind, ns, n_portals, first, last
-        self.depth = depth
-        from .poseidon import merkle_params
-        self.leaf_cfg, self.node_cfg = merkle_params(curve)
-        self.r = CURVE_PARAMS[curve]["r"]
-        self.fc = FrCodec(curve)
+        self.kind, self.ns, self.np_, self.first, self.last, self.depth = kind, ns, n_portals, first, last, depth
         self.n_time = self.n_addr = n_portals
-        self.n0 = 2 * (self.n_time + self.n_addr)
-        t = Tape(self.N_INST)
-        self._program(t, None)
-        self.tape = t
-        self.n_c = t.n_rows
-        self.n_wit = t.n_wit
-        self.n_v = self.N_INST + t.n_wit
-        self._csr = None
-        self._batch = None
+        self._build(curve, 4 * n_portals)
 
     # ---- the program: identical in BUILD and EVAL --------------------------------------------------------
     def _program(self, t, inp):
         """inp (EVAL): dict with numpy / int inputs for the batch, see `witness_batch`."""
         ev = not t.build
-        B = t.batch
-        ni = self.N_INST
-        ENTRY, TR, ROOT = 1, 2, 3
-        # ---- stage 0: (addr, val) of every time-ordered and address-ordered entry
-        time_e = [(t.alloc_full(inp["time"][k][0] if ev else None), t.alloc_full(inp["time"][k][1] if ev else None))
-                  for k in range(self.n_time)]
-        addr_e = [(t.alloc_full(inp["addr"][k][0] if ev else None), t.alloc_full(inp["addr"][k][1] if ev else None))
-                  for k in range(self.n_addr)]
-        assert t.n_wit == self.n0
-        r_mod = self.r
-        # ---- stage 1
-        # running evaluations (rom_transcript.rs:77-107): eval' = eval * (tr_chal - (val + entry_chal * addr))
-        def running(entries, start_vals, key):
-            ev_col = t.alloc_full(start_vals if ev else None)
-            cur = start_vals
-            if self.first:
-                t.big_row([(1, ev_col)], [(1, ONE)], [(1, ONE)])                    # subcircuit 0: eval = 1
-            for k, (a_col, v_col) in enumerate(entries):
-                if ev:
-                    ech, tr = inp["entry_chal"], inp["tr_chal"]
-                    e_vals = [(int(v) + ech * int(a)) % r_mod for a, v in zip(inp[key][k][0], inp[key][k][1])]
-                    nxt = [c * ((tr - e) % r_mod) % r_mod for c, e in zip(cur, e_vals)]
-                else:
-                    e_vals = nxt = None
-                e_col = t.alloc_full(e_vals)
-                n_col = t.alloc_full(nxt)
-                t.big_row([(1, ENTRY)], [(1, a_col)], [(1, e_col), (r_mod - 1, v_col)])
-                t.big_row([(1, ev_col)], [(1, TR), (r_mod - 1, e_col)], [(1, n_col)])
-                ev_col, cur = n_col, nxt
-            return ev_col, cur
-        t_final, t_vals = running(time_e, inp["time_eval0"] if ev else None, "time")
-        a_final, a_vals = running(addr_e, inp["addr_eval0"] if ev else None, "addr")
-        if self.last:
-            t.big_row([(1, t_final), (r_mod - 1, a_final)], [(1, ONE)], [])
-        # the previous leaf's last address-ordered entry (subcircuit_circuit.rs:167, 209-216): witnessed; padding - address
-        # 0 - in front of subcircuit 0 (:199-203; `is_padding` compares the address only, rom_transcript.rs:249-253)
-        prev = (t.alloc_full(inp["prev"][0] if ev else None), t.alloc_full(inp["prev"][1] if ev else None))
-        if self.first:
-            t.big_row([(1, prev[0])], [(1, ONE)], [])
-        # address-step check of every consecutive pair of [previous entry] + slice (rom_portal_manager.rs:151-165):
-        #   d = addr' - addr;  d * inv = 1 - same;  same * d = 0          (same = [d == 0], `is_eq`)
-        #   (1 - same) * (d - 1) = 0                                     (not the same address -> exactly one larger)
-        #   same * (val' - val) = 0                                      (`conditional_enforce_equal`)
-        chain = [prev] + addr_e
-        for k in range(1, len(chain)):
-            (a0, v0), (a1, v1) = chain[k - 1], chain[k]
-            if ev:
-                prev_a = inp["prev"][0] if k == 1 else inp["addr"][k - 2][0]
-                d = [(int(x) - int(y)) % r_mod for x, y in zip(inp["addr"][k - 1][0], prev_a)]
-                inv = [pow(x, -1, r_mod) if x else 0 for x in d]
-                same = [0 if x else 1 for x in d]
-            else:
-                inv = same = None
-            inv_c, same_c = t.alloc_full(inv), t.alloc_full(same)
-            t.big_row([(1, a1), (r_mod - 1, a0)], [(1, inv_c)], [(1, ONE), (r_mod - 1, same_c)])
-            t.big_row([(1, same_c)], [(1, a1), (r_mod - 1, a0)], [])
-            t.big_row([(1, ONE), (r_mod - 1, same_c)], [(1, a1), (r_mod - 1, a0), (r_mod - 1, ONE)], [])
-            t.big_row([(1, same_c)], [(1, v1), (r_mod - 1, v0)], [])
-        # ---- the subcircuit's own execution leaf is in the tree (subcircuit_circuit.rs:233-252)
-        self.pos_col0 = ni + t.n_wit
-        leaf_lcs = [[(1, t_final)], [(1, a_final)], [(1, addr_e[-1][0])], [(1, addr_e[-1][1])]]
-        if ev:
-            leaf_vals = [[t_vals[b], a_vals[b], int(inp["addr"][-1][0][b]) % r_mod, int(inp["addr"][-1][1][b]) % r_mod]
-                         for b in range(B)]
-            traces = [poseidon_path_trace(self.leaf_cfg, self.node_cfg, leaf_vals[b], inp["path_sib"][b], inp["path_idx"][b])
-                      for b in range(B)]
-            cols_vals = list(zip(*traces))                       # per witness of the block: its value per batch element
-            self._pos_iter = iter(cols_vals)
-        nxt = (lambda: t.alloc_full(list(next(self._pos_iter)))) if ev else (lambda: t.alloc_full(None))
-        cur = self._poseidon_crh(t, self.leaf_cfg, leaf_lcs, nxt)
-        for _lvl in range(self.depth):
-            bit, sib, left = nxt(), nxt(), nxt()
-            t.big_row([(1, bit)], [(1, ONE), (r_mod - 1, bit)], [])                               # boolean
-            t.big_row([(1, bit)], [(1, sib), (r_mod - 1, cur)], [(1, left), (r_mod - 1, cur)])    # left = bit ? sib : cur
-            right = [(1, sib), (1, cur), (r_mod - 1, left)]                                        # the other one
-            cur = self._poseidon_crh(t, self.node_cfg, [[(1, left)], right], nxt)
-        t.big_row([(1, cur), (r_mod - 1, ROOT)], [(1, ONE)], [])                                   # the public root
-        self.pos_cols = ni + t.n_wit - self.pos_col0
+        portal = self.rom_portal_block(t, inp)
+        self.rom_membership_block(t, inp, portal)
+        time_e = portal[0]
         # ---- the hash chain
         if self.kind in ("leaf", "padding"):
             # 64 witnessed bytes as 16 big-endian words (bits boolean)
@@ -546,52 +439,6 @@ class ShaMerkleSubcircuit(MultiStageConstraintSynthesizer):
             self.sha_root_col = sha_root
             t.big_row(terms, [(1, ONE)], [(1, sha_root)])
         return digest
-
-    def _poseidon_crh(self, t, cfg, inputs, nxt):
-        """`poseidon::constraints::CRHGadget::evaluate` with an own layout: inputs = linear combinations [(coef, col)];
-        per round the S-box chain of every S-boxed element and the new state are witnesses (`nxt()` allocates the next
-        one, in the order poseidon.PoseidonConfig.permute traces them); returns the digest's column."""
-        p, tt = cfg.p, cfg.t
-        state = [[] for _ in range(tt)]                      # linear combinations; [] = 0
-        k = 0
-        while True:
-            blk = inputs[k:k + cfg.rate]
-            for i, lc in enumerate(blk):
-                state[1 + i] = state[1 + i] + lc
-            k += len(blk)
-            if k >= len(inputs):
-                break
-            state = self._poseidon_permute(t, cfg, state, nxt)
-        state = self._poseidon_permute(t, cfg, state, nxt)
-        return state[1][0][1]
-
-    def _poseidon_permute(self, t, cfg, state, nxt):
-        half = cfg.rf // 2
-        for r in range(cfg.rf + cfg.rp):
-            full = r < half or r >= half + cfg.rp
-            y = [state[i] + [(cfg.ark[r][i], ONE)] for i in range(cfg.t)]
-            for i in range(cfg.t if full else 1):
-                u = y[i]
-                prev_col = None
-                n_chain = 3 if cfg.alpha == 5 else 5
-                for step in range(n_chain):
-                    c = nxt()
-                    if step == 0:
-                        t.big_row(u, u, [(1, c)])                                  # u^2
-                    elif step < n_chain - 1:
-                        t.big_row([(1, prev_col)], [(1, prev_col)], [(1, c)])      # squarings
-                    else:
-                        t.big_row([(1, prev_col)], u, [(1, c)])                    # x^(alpha-1) * u
-                    prev_col = c
-                y[i] = [(1, prev_col)]
-            new = []
-            for i in range(cfg.t):
-                c = nxt()
-                lc = [(cfg.mds[i][j] * coef % cfg.p, col) for j in range(cfg.t) for coef, col in y[j]]
-                t.big_row(lc, [(1, ONE)], [(1, c)])
-                new.append([(1, c)])
-            state = new
-        return state
 
     @staticmethod
     def _enforce_word_eq(t, w, z):
@@ -660,63 +507,12 @@ class ShaMerkleSubcircuit(MultiStageConstraintSynthesizer):
             words.append(Word(cols, val, t._value(OP_PACK4, first_ref, 4, 0, marker)))
         return words
 
-    # ---- MultiStageConstraintSynthesizer -------------------------------------------------------------------
-    def total_num_stages(self):
-        return 2
-
-    def generate_constraints(self, stage, cs):
-        z = self._setup_assignment()
-        ni = self.N_INST
-        cs.initialize_stage()
-        if stage == 0:
-            cs.witness_assignment.extend(z[ni:ni + self.n0])
-        else:
-            cs.instance_assignment.extend(z[1:ni])
-            cs.witness_assignment.extend(z[ni + self.n0:])
-            cs._n_constraints += self.n_c
-        cs.finalize_stage()
-
+    # ---- MultiStageConstraintSynthesizer: setup over an example witness -----------------------------------------
     def _setup_assignment(self):
         if getattr(self, "_setup_z", None) is None:
             w = example_witness(self, seed=0)
             self._setup_z = self.assignment_ints(w)[0]
         return self._setup_z
-
-    def csr(self, fc):
-        if self._csr is None:
-            self._csr = self.tape.csr(fc)
-        return tuple((rp, col, val) for rp, col, val, _vi, _tab in self._csr)
-
-    def qap_evaluate(self, t_pt):
-        """instance_map_with_evaluation over the tape's rows (generator.rs:75-76)."""
-        p = CURVE_PARAMS[self.curve]
-        r, ni, n_c = self.r, self.N_INST, self.n_c
-        m, log_m = 1, 0
-        while m < n_c + ni:
-            m *= 2
-            log_m += 1
-        w = pow(pow(p["gen"], (r - 1) >> p["two_adicity"], r), 1 << (p["two_adicity"] - log_m), r)
-        zt = (pow(t_pt, m, r) - 1) % r
-        from .cp_groth16 import _batch_inverse
-        wi = [1] * m
-        for i in range(1, m):
-            wi[i] = wi[i - 1] * w % r
-        den = _batch_inverse([m * (t_pt - x) % r for x in wi], r)
-        u = [zt * x % r * d % r for x, d in zip(wi, den)]
-        self.csr(self.fc)
-        outs = []
-        for (rp, col, _val, vidx, table) in self._csr:
-            acc = [0] * self.n_v
-            rp_l, col_l, vi_l = rp.tolist(), col.tolist(), vidx.tolist()
-            for i in range(n_c):
-                ui = u[i]
-                for k in range(rp_l[i], rp_l[i + 1]):
-                    acc[col_l[k]] += ui * table[vi_l[k]]
-            outs.append([x % r for x in acc])
-        a, b, c = outs
-        for j in range(ni):
-            a[j] = (a[j] + u[n_c + j]) % r
-        return a, b, c, zt, m
 
     # ---- the workload interface bench.py / tests use for synthetic classes (workload.SyntheticSubcircuit) ----------
     def set_witness_seed(self, seed):
@@ -732,6 +528,7 @@ class ShaMerkleSubcircuit(MultiStageConstraintSynthesizer):
         return self.assignment_bytes(self._cur)[0]
 
     def stage0_witness_bytes(self):
+        """Of the current witness (`set_witness_seed`), not of given inputs: the workload interface's signature."""
         z = self.assignment_ints_current()
         return self.fc.enc(z[self.N_INST:self.N_INST + self.n0])
 
@@ -740,21 +537,12 @@ class ShaMerkleSubcircuit(MultiStageConstraintSynthesizer):
         """inputs: list of per-subcircuit dicts (see `example_witness`).  Runs the program in EVAL mode over the whole
         batch.  Returns (bits uint8 (batch, n_v), full-width {column: [ints]}, digests list of 32-byte strings)."""
         B = len(inputs)
-        inp = dict(entry_chal=None, tr_chal=None)
-        inp["entry_chal"], inp["tr_chal"] = inputs[0]["entry_chal"], inputs[0]["tr_chal"]
-        assert all(i["entry_chal"] == inp["entry_chal"] and i["tr_chal"] == inp["tr_chal"] for i in inputs)
-        for key, n in (("time", self.n_time), ("addr", self.n_addr)):
-            inp[key] = [([i[key][k][0] for i in inputs], [i[key][k][1] for i in inputs]) for k in range(n)]
-        inp["time_eval0"] = [i["time_eval0"] for i in inputs]
-        inp["addr_eval0"] = [i["addr_eval0"] for i in inputs]
-        inp["prev"] = ([i["prev"][0] for i in inputs], [i["prev"][1] for i in inputs])
-        inp["path_sib"] = [i["path"][0] for i in inputs]
-        inp["path_idx"] = [i["path"][1] for i in inputs]
+        inp = rom_inputs(inputs, self.np_)                          # values as they came: the children are unpacked from them
         inp["sha_root"] = [i.get("sha_root", 0) for i in inputs]
         if self.kind in ("leaf", "padding"):
             leaves = np.frombuffer(b"".join(i["leaf"] for i in inputs), np.uint8).reshape(B, 64)
             inp["leaf_words"] = leaves.reshape(B, 16, 4).astype(np.uint32) @ np.array([1 << 24, 1 << 16, 1 << 8, 1], np.uint32)
-        t = Tape(self.N_INST, batch=B)
+        t = self._tape(batch=B)
         digest = self._program(t, inp)
         assert t.n_wit == self.n_wit
         bits = t.assignment_bits(self.n_v)
@@ -764,7 +552,7 @@ class ShaMerkleSubcircuit(MultiStageConstraintSynthesizer):
         return bits, full, digests
 
     def assignment_ints(self, inputs):
-        """Full assignments as Python ints (tests / setup)."""
+        """Full assignments as Python ints (tests / setup), from this class's (bits, full-width) `witness_batch`."""
         inputs = inputs if isinstance(inputs, list) else [inputs]
         bits, full, _ = self.witness_batch(inputs)
         out = []
@@ -777,7 +565,8 @@ class ShaMerkleSubcircuit(MultiStageConstraintSynthesizer):
         return out
 
     def assignment_bytes(self, inputs):
-        """Montgomery bytes of the full assignments, (batch, n_v * 32): bits through a two-entry table."""
+        """Montgomery bytes of the full assignments, (batch, n_v * 32): the bit columns go through a two-entry table
+        instead of one encoding per variable."""
         inputs = inputs if isinstance(inputs, list) else [inputs]
         bits, full, _ = self.witness_batch(inputs)
         fc = self.fc
@@ -931,6 +720,7 @@ class ShaMerkleJob:
         assert n >= 4 and n & (n - 1) == 0 and len(leaves) == n // 2 and n_portals >= 3
         self.curve, self.n, self.ns, self.np_ = curve, n, ns, n_portals
         self.r = CURVE_PARAMS[curve]["r"]
+        self.offsets = np.arange(n + 1, dtype=np.uint32) * n_portals
         nl = n // 2
         self.kind = ["leaf"] * nl + ["parent"] * (n - 2 - nl) + ["root", "padding"]
         self.children = {}
@@ -972,6 +762,10 @@ class ShaMerkleJob:
         its time-ordered then its address-ordered entries, the variable order of `ShaMerkleSubcircuit._program`."""
         return [x for e in self.time[idx] for x in e] + [x for e in self.addr[idx] for x in e]
 
+    def flat(self, which):
+        """Montgomery bytes of one flattened trace, (addr, val) per entry: hk_trace_sort's / hk_exec_tree's layout."""
+        return FrCodec(self.curve).enc([x for ops in (self.time if which == "time" else self.addr) for e in ops for x in e])
+
     def set_challenges(self, entry_chal, tr_chal, ctx=None):
         """Running evaluations entering every subcircuit (coordinator.rs:125-160 `generate_exec_tree`).  ctx (a
         capi.Context of the job's curve): evaluations, tree and root come from one hk_exec_tree call instead."""
@@ -995,20 +789,15 @@ class ShaMerkleJob:
         assert self.time_eval0[-1] == self.addr_eval0[-1]          # same multiset: the permutation check will hold
         # the execution tree (coordinator.rs:125-174): leaf i = (evals after subcircuit i, last entry of its address-ordered
         # slice); every subcircuit gets the membership path of its own leaf (coordinator.rs:446-452)
-        from .poseidon import ExecTree
         leaves = [[self.time_eval0[i + 1], self.addr_eval0[i + 1], self.addr[i][-1][0] % r, self.addr[i][-1][1] % r]
                   for i in range(n)]
         self.tree = ExecTree(self.curve, leaves)
         self.root = self.tree.root
 
     def _set_challenges_device(self, ctx):
-        from .poseidon import ExecTree, device_params
-        fc = FrCodec(self.curve)
-        n, k = self.n, self.np_
-        offsets = np.arange(n + 1, dtype=np.uint32) * k
-        flat = lambda tr: fc.enc([x for ops in tr for e in ops for x in e])
-        evals, leaves, nodes, _, _ = ctx.exec_tree(device_params(self.curve, fc), 2, offsets, flat(self.time), flat(self.addr),
-                                                   (self.entry_chal, self.tr_chal))
+        fc, n = FrCodec(self.curve), self.n
+        evals, leaves, nodes, _, _ = ctx.exec_tree(device_params(self.curve, fc), 2, self.offsets, self.flat("time"),
+                                                   self.flat("addr"), (self.entry_chal, self.tr_chal))
         ev, lf, nd = fc.dec(evals), fc.dec(leaves), fc.dec(nodes)
         self.time_eval0, self.addr_eval0 = [1] + ev[0::2], [1] + ev[1::2]
         assert self.time_eval0[-1] == self.addr_eval0[-1]          # same multiset: the permutation check will hold
@@ -1064,9 +853,8 @@ class TreeDevice:
     the root."""
 
     def __init__(self, job, ctx):
-        from .capi import DeviceBuffer
         self.job, self.ctx = job, ctx
-        self.leaves = DeviceBuffer.from_host(ctx, np.frombuffer(b"".join(job.leaves), np.uint8))
+        self.leaves = capi.DeviceBuffer.from_host(ctx, np.frombuffer(b"".join(job.leaves), np.uint8))
         self.digests = self.time = self.sha_root = None
         try:
             self.digests, self.time, self.sha_root = ctx.sha_tree(self.leaves, job.n, job.ns, job.np_, device_out=True)
@@ -1087,7 +875,7 @@ class TreeDevice:
         self.leaves = self.digests = self.time = self.sha_root = None
 
 
-class Stage0Device:
+class Stage0Device(PortalStage0Device):
     """What `ShaMerkleJob.stage0_device` returns: `offsets`, and `traces = [time, addr]` as DeviceBuffers - the time-ordered
     trace uploaded once (or, with tree=, the `TreeDevice`'s, which stays its owner's), the address-ordered one sorted from
     it on the device (hk_trace_sort).  `rows(members)` cuts the stage-0 witnesses of any subcircuits out of them
@@ -1095,87 +883,28 @@ class Stage0Device:
     (`Stage1Device(job, ctx, traces=dev0.traces)`)."""
 
     def __init__(self, job, ctx, tree=None):
-        from .capi import DeviceBuffer
-        self.job, self.ctx = job, ctx
-        self.offsets = np.arange(job.n + 1, dtype=np.uint32) * job.np_
-        self._adopted = tree is not None
-        if tree is not None:
-            time = tree.time
-        else:
-            fc = FrCodec(job.curve)
-            time = DeviceBuffer.from_host(ctx, fc.enc([x for ops in job.time for e in ops for x in e]))
-        self.traces = [time]
-        try:
-            self.traces.append(ctx.trace_sort(2, time, job.n * job.np_, device_out=True))
-        except Exception:
-            self.free()
-            raise
+        self.tree = tree
+        super().__init__(job, ctx)
 
-    def rows(self, members):
-        """DeviceBuffer of len(members) x 4 n_portals Fr: row b = `job.stage0_ints(members[b])` in Montgomery form.  The
-        caller frees it."""
-        from .capi import DeviceBuffer
-        members = np.ascontiguousarray(members, dtype=np.uint32)
-        w = DeviceBuffer(self.ctx, max(members.size * 4 * self.job.np_ * self.ctx.fr_bytes, 1))
-        try:
-            self.ctx.stage0_witness(self.offsets, self.job.np_, self.traces[0], self.traces[1], members, w)
-        except Exception:
-            w.free()
-            raise
-        return w
-
-    def free(self):
-        for x in self.traces[1 if self._adopted else 0:]:
-            x.free()
-        self.traces = []
+    def _time_trace(self):
+        return self.tree.time if self.tree is not None else super()._time_trace()
 
 
-class R1csUnsatisfied(AssertionError):
-    """An assignment on the device fails its class's R1CS (Stage1Device.check).  failures: [(subcircuit, n_bad, first_bad,
-    [the first failing rows])] of every failing subcircuit of the call, in the order of `members`."""
-
-    def __init__(self, failures):
-        self.failures = failures
-        self.subcircuit, self.n_bad, self.row, _ = failures[0]
-        super().__init__("subcircuit %d: constraint %d is unsatisfied (%d failing rows in it; %d failing subcircuits in the call)"
-                         % (self.subcircuit, self.row, self.n_bad, len(failures)))
-
-
-class Stage1Device:
-    """What `ShaMerkleJob.stage1_device` returns: the job's traces and hk_exec_tree's outputs (evaluations, leaves, nodes,
-    siblings, root) as DeviceBuffers, from which `fill` writes the challenge-dependent columns of a class's assignments
-    (hk_stage1_witness) without a host value in between.  `root` is the one value read back (an int).  traces: the
-    [time, addr] DeviceBuffers of a `Stage0Device` to read instead of encoding and uploading both again; they stay their
-    owner's (`free` leaves them).  A job made by `ShaMerkleJob.on_device` has no host traces: without traces= its tree's
-    time-ordered trace is sorted here (a `Stage0Device` this object owns)."""
+class Stage1Device(PortalStage1Device):
+    """What `ShaMerkleJob.stage1_device` returns; `fill` writes the challenge-dependent columns of a class's assignments
+    (hk_stage1_witness).  traces: the [time, addr] DeviceBuffers of a `Stage0Device` to read instead of encoding and
+    uploading both again; they stay their owner's (`free` leaves them).  A job made by `ShaMerkleJob.on_device` has no host
+    traces: without traces= its tree's time-ordered trace is sorted here (a `Stage0Device` this object owns)."""
 
     def __init__(self, job, ctx, traces=None):
-        from .capi import DeviceBuffer
-        from .poseidon import device_params
-        fc = FrCodec(job.curve)
-        self.job, self.ctx = job, ctx
-        self.offsets = np.arange(job.n + 1, dtype=np.uint32) * job.np_
-        flat = lambda tr: fc.enc([x for ops in tr for e in ops for x in e])
-        consts, n_consts, ld, nd = device_params(job.curve, fc)
-        self._dev0 = None
-        if traces is None and isinstance(getattr(job, "tree", None), TreeDevice):
-            self._dev0 = Stage0Device(job, ctx, tree=job.tree)     # an on_device job: its trace, sorted here and owned here
-            traces = self._dev0.traces
-        self._adopted = traces is not None
+        super().__init__(job, ctx, (job.entry_chal, job.tr_chal), traces=traces)
+
+    def _traces(self, traces=None):
         if traces is not None:
-            self.traces = list(traces)
-        else:
-            self.traces = [DeviceBuffer.from_host(ctx, flat(job.time)), DeviceBuffer.from_host(ctx, flat(job.addr))]
-        self.params = (DeviceBuffer.from_host(ctx, consts), n_consts, ld, nd)
-        self.challenges = fc.enc([job.entry_chal, job.tr_chal])
-        try:
-            self.outs = ctx.exec_tree(self.params, 2, self.offsets, self.traces[0], self.traces[1], self.challenges,
-                                      device_out=True)
-        except Exception:
-            self.outs = ()
-            self.free()
-            raise
-        self.root = fc.dec(self.outs[4].to_host())[0]
+            return traces
+        if isinstance(getattr(self.job, "tree", None), TreeDevice):
+            return self._own(Stage0Device(self.job, self.ctx, tree=self.job.tree)).traces
+        return [self._own(capi.DeviceBuffer.from_host(self.ctx, self.job.flat(which))) for which in ("time", "addr")]
 
     def fill(self, circ, members, z, sha_root=None):
         """The challenge-dependent columns of the assignments of `members` (subcircuit indices of ONE class, `circ`), row b
@@ -1183,44 +912,19 @@ class Stage1Device:
         - the job's `sha_root`, or with sha_root= (a DeviceBuffer of 1 Fr: `TreeDevice.sha_root`) the value on the device.
         The bit columns are the word program's (hk_wprog_run), before or after."""
         members = np.ascontiguousarray(members, dtype=np.uint32)
-        self.ctx.stage1_witness(self.params, self.job.np_, self.offsets, self.traces[0], self.traces[1], self.challenges,
-                                self.outs, members, circ.n_v, (1, circ.N_INST, circ.pos_col0), z)
+        self._stage1_witness(circ, members, z)
         if circ.kind == "root" and members.size:
-            from .capi import check
             cols = np.array([circ.sha_root_col], np.uint32)
             if sha_root is not None:
                 row = circ.n_v * self.ctx.fr_bytes                 # one value on the device: a row at a time
                 for b in range(members.size):
-                    check(self.ctx.lib.hk_assignment_scatter(self.ctx.handle, cols.ctypes.data, sha_root.ptr, 1, 1, circ.n_v,
-                                                             z.ptr + b * row), "hk_assignment_scatter")
+                    capi.check(self.ctx.lib.hk_assignment_scatter(self.ctx.handle, cols.ctypes.data, sha_root.ptr, 1, 1,
+                                                                  circ.n_v, z.ptr + b * row), "hk_assignment_scatter")
                 return z
             vals = np.ascontiguousarray(np.tile(circ.fc.enc([self.job.sha_root]), members.size))
-            check(self.ctx.lib.hk_assignment_scatter(self.ctx.handle, cols.ctypes.data, vals.ctypes.data, 1, members.size,
-                                                     circ.n_v, z.ptr), "hk_assignment_scatter")
+            capi.check(self.ctx.lib.hk_assignment_scatter(self.ctx.handle, cols.ctypes.data, vals.ctypes.data, 1, members.size,
+                                                          circ.n_v, z.ptr), "hk_assignment_scatter")
         return z
-
-    def check(self, pk, z, members, cap=8):
-        """ark's `assert!(cs.is_satisfied())` on the filled rows (subcircuit_circuit.rs:311-399), where they lie: one
-        hk_pk_r1cs_check over the DeviceBuffer z (row b = members[b]) against the matrices of the class's key `pk` (a
-        capi.DevicePk, or anything with its r1cs_check).  Raises R1csUnsatisfied naming the first failing (subcircuit, row);
-        its `failures` lists up to `cap` rows per failing subcircuit.  Nothing calls this unless asked to."""
-        members = [int(i) for i in members]
-        if not members:
-            return
-        res = pk.r1cs_check(z, batch=len(members), cap=cap)
-        verdicts, rows = res if cap else (res, None)
-        failures = [(i, n_bad, first, [] if rows is None else [int(x) for x in rows[b] if x != 0xffffffff])
-                    for b, (i, (n_bad, first)) in enumerate(zip(members, verdicts)) if n_bad]
-        if failures:
-            raise R1csUnsatisfied(failures)
-
-    def free(self):
-        for x in ([] if self._adopted else list(self.traces)) + [self.params[0]] + list(self.outs):
-            x.free()
-        if self._dev0 is not None:
-            self._dev0.free()
-            self._dev0 = None
-        self.traces, self.outs = [], ()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -10,9 +10,9 @@ hashes, the index words and the roots talk through ROM portals (vkd.rs:362-617 `
 vkd_constraints.rs:70-193 `get_portal_subtraces`, :237-342 `generate_constraints`).
 
 The SEMANTICS are the reference's; tests/test_vkd_circuit_cpu.py pins the trace against a name-keyed restatement of
-`SetupRomPortalManager`.  The constraint LAYOUT is this build's own: `VkdSubcircuit` is its own class on
-`sha_circuit.Tape` with the stage-0 block, the ROM portal block and the membership block in the columns and order of
-`ShaMerkleSubcircuit._program`, then one body per primitive (the table in section 4o).  Three deliberate deviations:
+`SetupRomPortalManager`.  The constraint LAYOUT is this build's own: `VkdSubcircuit` is a
+`portal_circuit.PortalSubcircuit` - the stage-0 block, the ROM portal block and the membership block are the base's
+(`rom_portal_block`, `rom_membership_block`) - then one body per primitive (the table in section 4o).  Three deliberate deviations:
 
   1. the truncation to 27 bytes is CONSTRAINED (`bits` / `canon` / `trunc`); hash.rs:146-151 re-witnesses it without a row;
   2. ONE bit convention: level l counts from the leaf and uses bit l of the index, bit 1 = the current node is the right
@@ -26,10 +26,11 @@ import functools
 
 import numpy as np
 
-from .cp_groth16 import CURVE_PARAMS, FrCodec, MultiStageConstraintSynthesizer
-from .poseidon import merkle_params
-from .sha_circuit import ONE, ShaMerkleSubcircuit, Stage1Device, Tape, poseidon_path_trace
-from .transcript import ROM, RomTranscriptEntry, RunningEvaluation, running_evaluations, sort_subtraces_by_addr
+from . import capi
+from .cp_groth16 import CURVE_PARAMS, FrCodec
+from .poseidon import device_params, merkle_params
+from .portal_circuit import ONE, PortalJob, PortalStage0Device, PortalStage1Device, PortalSubcircuit
+from .transcript import RomTranscriptEntry
 
 INNER_HASH_SIZE = 27                                   # vkd/sparse_tree.rs:42
 NODE_BITS = 8 * INNER_HASH_SIZE
@@ -146,115 +147,35 @@ class Update:
 
 
 # ---- one proving-key class ---------------------------------------------------------------------------------------------
-class VkdSubcircuit(MultiStageConstraintSynthesizer):
+class VkdSubcircuit(PortalSubcircuit):
     """kind: the reference's `get_type()` string, its primitives in order; n_levels = L; `first` / `last` as in every class
-    here; depth_exec = log2(number of subcircuits).  `blocks` maps a block's name to its row ranges."""
-    N_INST = 4
-    _poseidon_crh = ShaMerkleSubcircuit._poseidon_crh
-    _poseidon_permute = ShaMerkleSubcircuit._poseidon_permute
-    csr = ShaMerkleSubcircuit.csr
-    qap_evaluate = ShaMerkleSubcircuit.qap_evaluate
-    total_num_stages = ShaMerkleSubcircuit.total_num_stages
+    here; depth_exec = log2(number of subcircuits).  `blocks` maps a block's name to its row ranges: a name recurs once per
+    primitive and level."""
+    block_ranges = True
 
     def __init__(self, curve, kind, n_levels, split, first=False, last=False, depth_exec=4):
-        self.curve, self.kind, self.L, self.split, self.first, self.last = curve, kind, int(n_levels), int(split), first, last
+        self.kind, self.L, self.split, self.first, self.last = kind, int(n_levels), int(split), first, last
         self.depth = depth_exec
         self.prims = kind.split(", ")
         assert all(p in PORTALS or p == "get index" for p in self.prims) and depth_exec >= 1
         assert "get index" not in self.prims or self.prims[:2] == ["hash leaf", "get index"]
         self.np_ = sum(self.split if p == "get index" else PORTALS[p] for p in self.prims)
-        self.leaf_cfg, self.node_cfg = merkle_params(curve)
-        self.r = CURVE_PARAMS[curve]["r"]
-        self.nbits = self.r.bit_length()
-        self.fc = FrCodec(curve)
-        self.n0 = 4 * self.np_
+        self.nbits = CURVE_PARAMS[curve]["r"].bit_length()
         self.blocks, self.cols = {}, {}
-        t = Tape(self.N_INST)
-        self._program(t, None)
-        self.tape = t
-        self.n_c, self.n_wit, self.n_v = t.n_rows, t.n_wit, self.N_INST + t.n_wit
-        self._csr = None
+        self._build(curve, 4 * self.np_)
 
     def _program(self, t, inp):
         ev = not t.build
         B, r, k, ni = t.batch, self.r, self.np_, self.N_INST
-        ENTRY, TR, ROOT = 1, 2, 3
         neg = r - 1
         col = lambda vals: t.alloc_full(vals if ev else None)
-        start = [0]
-
-        def block(name):
-            if t.build and t.n_rows > start[0]:
-                self.blocks.setdefault(name, []).append((start[0], t.n_rows))
-            start[0] = t.n_rows
-
-        # ---- stage 0 and the ROM portal block: `R1csSubcircuit._program`'s, column for column
-        time_e = [(col(ev and inp["time"][j][0]), col(ev and inp["time"][j][1])) for j in range(k)]
-        addr_e = [(col(ev and inp["addr"][j][0]), col(ev and inp["addr"][j][1])) for j in range(k)]
-        assert t.n_wit == self.n0
-
-        def running(entries, start_vals, key):
-            ev_col, cur = col(start_vals), start_vals
-            if self.first:
-                t.big_row([(1, ev_col)], [(1, ONE)], [(1, ONE)])
-            for j, (a_col, v_col) in enumerate(entries):
-                if ev:
-                    ech, tr = inp["entry_chal"], inp["tr_chal"]
-                    e_vals = [(v + ech * a) % r for a, v in zip(inp[key][j][0], inp[key][j][1])]
-                    nxt = [c * ((tr - e) % r) % r for c, e in zip(cur, e_vals)]
-                else:
-                    e_vals = nxt = None
-                e_col, n_col = col(e_vals), col(nxt)
-                t.big_row([(1, ENTRY)], [(1, a_col)], [(1, e_col), (neg, v_col)])
-                t.big_row([(1, ev_col)], [(1, TR), (neg, e_col)], [(1, n_col)])
-                ev_col, cur = n_col, nxt
-            return ev_col, cur
-        t_final, t_vals = running(time_e, inp["time_eval0"] if ev else None, "time")
-        a_final, a_vals = running(addr_e, inp["addr_eval0"] if ev else None, "addr")
-        if self.last:
-            t.big_row([(1, t_final), (neg, a_final)], [(1, ONE)], [])
-        prev = (col(ev and inp["prev"][0]), col(ev and inp["prev"][1]))
-        if self.first:
-            t.big_row([(1, prev[0])], [(1, ONE)], [])
-        chain = [prev] + addr_e
-        for j in range(1, len(chain)):
-            (a0, v0), (a1, v1) = chain[j - 1], chain[j]
-            if ev:
-                prev_a = inp["prev"][0] if j == 1 else inp["addr"][j - 2][0]
-                d = [(x - y) % r for x, y in zip(inp["addr"][j - 1][0], prev_a)]
-                inv = [pow(x, -1, r) if x else 0 for x in d]
-                same = [0 if x else 1 for x in d]
-            else:
-                inv = same = None
-            inv_c, same_c = col(inv), col(same)
-            t.big_row([(1, a1), (neg, a0)], [(1, inv_c)], [(1, ONE), (neg, same_c)])
-            t.big_row([(1, same_c)], [(1, a1), (neg, a0)], [])
-            t.big_row([(1, ONE), (neg, same_c)], [(1, a1), (neg, a0), (neg, ONE)], [])
-            t.big_row([(1, same_c)], [(1, v1), (neg, v0)], [])
-        assert ni + t.n_wit == ni + 10 * k + 4
+        seq = lambda traces: self.trace_columns(t, traces)
+        block = self._block_recorder(t)
+        portal = self.rom_portal_block(t, inp)
         block("portal")
-        # ---- the subcircuit's own execution leaf is in the tree
-        self.pos_col0 = ni + t.n_wit
-
-        def seq(traces):
-            """Allocates the next witness of a Poseidon trace; traces: one list per batch element (EVAL)."""
-            if not ev:
-                return lambda: t.alloc_full(None)
-            it = iter(zip(*traces))
-            return lambda: t.alloc_full(list(next(it)))
-        leaf_lcs = [[(1, t_final)], [(1, a_final)], [(1, addr_e[-1][0])], [(1, addr_e[-1][1])]]
-        nxt = seq(ev and [poseidon_path_trace(self.leaf_cfg, self.node_cfg,
-                                              [t_vals[b], a_vals[b], inp["addr"][-1][0][b], inp["addr"][-1][1][b]],
-                                              inp["path_sib"][b], inp["path_idx"][b]) for b in range(B)])
-        cur = self._poseidon_crh(t, self.leaf_cfg, leaf_lcs, nxt)
-        for _lvl in range(self.depth):
-            bit, sib, left = nxt(), nxt(), nxt()
-            t.big_row([(1, bit)], [(1, ONE), (neg, bit)], [])
-            t.big_row([(1, bit)], [(1, sib), (neg, cur)], [(1, left), (neg, cur)])
-            cur = self._poseidon_crh(t, self.node_cfg, [[(1, left)], [(1, sib), (1, cur), (neg, left)]], nxt)
-        t.big_row([(1, cur), (neg, ROOT)], [(1, ONE)], [])
-        self.pos_cols = ni + t.n_wit - self.pos_col0
+        self.rom_membership_block(t, inp, portal)
         block("membership")
+        time_e = portal[0]
 
         # ---- the body, one part per primitive ---------------------------------------------------------------------
         self.body_col0 = ni + t.n_wit
@@ -359,73 +280,20 @@ class VkdSubcircuit(MultiStageConstraintSynthesizer):
         assert j == k
         self.body_cols = ni + t.n_wit - self.body_col0
 
-    # ---- what the tests and the host mirror of hk_r1cs_check read ------------------------------------------
-    def rows(self):
-        big = self.tape.big
-        assert [e[0] for e in big] == list(range(self.n_c))
-        return [e[1] for e in big], [e[2] for e in big], [e[3] for e in big]
-
     @property
     def device_cols(self):
         """(kind, hash_col0, index_col0, path_col0): what hk_vkd_witness takes as `cols`."""
         return (KINDS.index(self.kind), self.cols.get("hash leaf", 0), self.cols.get("get index", 0),
                 self.cols.get("compute path", 0))
 
-    def block_of(self, row):
-        for name, ranges in self.blocks.items():
-            if any(lo <= row < hi for lo, hi in ranges):
-                return name
-        raise IndexError(row)
-
-    def generate_constraints(self, stage, cs):
-        z = [1] + [0] * (self.n_v - 1)                     # setup mode: only the counts matter
-        ni = self.N_INST
-        cs.initialize_stage()
-        if stage == 0:
-            cs.witness_assignment.extend(z[ni:ni + self.n0])
-        else:
-            cs.instance_assignment.extend(z[1:ni])
-            cs.witness_assignment.extend(z[ni + self.n0:])
-            cs._n_constraints += self.n_c
-        cs.finalize_stage()
-
-    def witness_batch(self, inputs):
-        """inputs: per-subcircuit dicts (`VkdJob.inputs`): the keys every class here takes (entry_chal, tr_chal, root, time,
-        addr, prev, time_eval0, addr_eval0, path) and the primitives' own: leaf (66 bytes; "hash leaf"), sibs (L nodes;
-        "compute path").  What a path starts from and its index word are read from the time-ordered entries."""
-        B, k, r = len(inputs), self.np_, self.r
-        assert all(i["entry_chal"] == inputs[0]["entry_chal"] and i["tr_chal"] == inputs[0]["tr_chal"] for i in inputs)
-        inp = dict(entry_chal=inputs[0]["entry_chal"] % r, tr_chal=inputs[0]["tr_chal"] % r)
-        for key in ("time", "addr"):
-            assert all(len(i[key]) == k for i in inputs)
-            inp[key] = [([i[key][j][0] % r for i in inputs], [i[key][j][1] % r for i in inputs]) for j in range(k)]
-        inp["prev"] = ([i["prev"][0] % r for i in inputs], [i["prev"][1] % r for i in inputs])
-        inp["time_eval0"] = [i["time_eval0"] for i in inputs]
-        inp["addr_eval0"] = [i["addr_eval0"] for i in inputs]
-        inp["path_sib"] = [i["path"][0] for i in inputs]
-        inp["path_idx"] = [i["path"][1] for i in inputs]
+    def _batch_inputs(self, inputs):
+        """inputs: per-subcircuit dicts (`VkdJob.inputs`): what `rom_inputs` takes and the primitives' own: leaf (66 bytes;
+        "hash leaf"), sibs (L nodes; "compute path").  What a path starts from and its index word are read from the
+        time-ordered entries."""
+        inp = super()._batch_inputs(inputs)
         inp["leaf"] = [i.get("leaf") for i in inputs]
         inp["sibs"] = [i.get("sibs") for i in inputs]
-        t = Tape(self.N_INST, batch=B)
-        self._program(t, inp)
-        assert t.n_wit == self.n_wit
-        out = []
-        for b in range(B):
-            z = [0] * self.n_v
-            z[:self.N_INST] = [1, inp["entry_chal"], inp["tr_chal"], inputs[b]["root"] % r]
-            for c, vals in t.full_records:
-                z[c] = int(vals[b]) % r
-            out.append(z)
-        return out
-
-    def assignment_ints(self, inputs):
-        return self.witness_batch(inputs if isinstance(inputs, list) else [inputs])
-
-    def assignment_bytes(self, inputs):
-        return np.stack([self.fc.enc(z) for z in self.assignment_ints(inputs)])
-
-    def stage0_witness_bytes(self, inputs):
-        return np.stack([self.fc.enc(z[self.N_INST:self.N_INST + self.n0]) for z in self.assignment_ints(inputs)])
+        return inp
 
 
 @functools.lru_cache(maxsize=None)
@@ -434,7 +302,7 @@ def vkd_class(curve, kind, n_levels, split, first, last, depth_exec):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-class VkdJob:
+class VkdJob(PortalJob):
     """A whole VKD job: N = 8 + 2 split U subcircuits over U updates (6 paddings, write-pp, 2 split per update, the final
     equality), the addresses `SetupRomPortalManager` hands out, the VALUE TABLE every traced value is read from, the
     time-ordered trace, its address order and - once the round's challenges are in - the running evaluations, the
@@ -449,8 +317,7 @@ class VkdJob:
     set twice; a name read before it is set (where the reference panics)."""
 
     def __init__(self, curve, initial_root, final_root, updates, depth=128, split=4, host_values=True):
-        self.curve, self.depth_tree, self.split, self.updates = curve, int(depth), int(split), list(updates)
-        self.r = CURVE_PARAMS[curve]["r"]
+        self.depth_tree, self.split, self.updates = int(depth), int(split), list(updates)
         S, U = self.split, len(self.updates)
         if S < 2 or depth % (8 * S) or depth // S < 8:
             raise ValueError("depth %d over %d segments: L must be a multiple of 8, at least 8, and split >= 2" % (depth, S))
@@ -460,7 +327,7 @@ class VkdJob:
             raise ValueError("8 + 2 x %d x %d updates = %d subcircuits: not a power of two >= 16" % (S, U, n))
         if any(len(u.path) != depth for u in self.updates):
             raise ValueError("every update carries its %d siblings" % depth)
-        self.n, self.depth = n, n.bit_length() - 1
+        self._set_shape(curve, n)
         self.initial_root, self.final_root = int(initial_root) & NODE_MASK, int(final_root) & NODE_MASK
         self.null_leaf = hash_leaf(curve, bytes(32)) if host_values else None
         self.stride = 2 + 3 * S
@@ -513,13 +380,8 @@ class VkdJob:
         self.types = [", ".join(p[0] for p in ps) for ps in self.prims]
         self.slot_addr = np.array([a for ops in self.ops for a, _ in ops], np.uint32)
         self.slot_src = np.array([s for ops in self.ops for _, s in ops], np.uint32)
-        self.time = self.addr = None
-        if host_values:
-            self.time = [[RomTranscriptEntry(a, 0 if s == SRC_ZERO else vals[s]) for a, s in ops] for ops in self.ops]
-            self.addr = sort_subtraces_by_addr(self.time)
-        self.offsets = np.zeros(n + 1, np.uint32)
-        self.offsets[1:] = np.cumsum([len(ops) for ops in self.ops])
-        self.chal = self.entry_chal = self.tr_chal = self.root = self.tree = None
+        self._set_traces([[RomTranscriptEntry(a, 0 if s == SRC_ZERO else vals[s]) for a, s in ops] for ops in self.ops]
+                         if host_values else None, lengths=[len(ops) for ops in self.ops])
 
     def _sub(self, prims):
         """One subcircuit: its portal operations resolved as `SetupRomPortalManager` does (rom_portal_manager.rs:34-117)."""
@@ -612,52 +474,17 @@ class VkdJob:
         return vkd_class(self.curve, kind, self.L, self.split, first, last, self.depth)
 
     # ---- the round --------------------------------------------------------------------------------------------------------
-    def stage0_ints(self, idx):
-        return [x % self.r for e in self.time[idx] + self.addr[idx] for x in (e.addr, e.val)]
-
     def set_challenges(self, chals, tr_chal=None, ctx=None):
-        """As `PartitionedR1csJob.set_challenges`: (entry_chal, tr_chal), or the super commitment they are hashed from; with
-        ctx the evaluations and the execution tree come from one hk_exec_tree call."""
-        from .poseidon import ExecTree
-        r = self.r
-        com = chals if isinstance(chals, (bytes, bytearray)) or hasattr(chals, "serialize_uncompressed") else None
-        if com is not None:
-            chals = RunningEvaluation.new(ROM, com, r).challenges
-        elif tr_chal is not None:
-            chals = (chals, tr_chal)
-        self.chal = tuple(c % r for c in chals)
-        assert len(self.chal) == 2
-        self.entry_chal, self.tr_chal = self.chal
-        if ctx is not None and self.time is None:                 # an `on_device` job: hk_exec_tree over the device's traces
-            self.dev1 = VkdStage1Device(self, ctx, dev0=self.dev0)
-            self.root = self.dev1.root
-            return
-        if ctx is not None:
-            from .transcript import exec_tree_device
-            leaves, self.tree = exec_tree_device(ctx, ROM, self.chal, self.time, self.addr)
-        elif com is not None:
-            leaves = running_evaluations(ROM, com, r, self.time, self.addr)
-        else:
-            run, last, leaves = RunningEvaluation(ROM, r, self.chal), RomTranscriptEntry.padding(), []
-            for ts, as_ in zip(self.time, self.addr):
-                for te, ae in zip(ts, as_):
-                    run.update_time_ordered(te)
-                    run.update_addr_ordered(ae)
-                    last = ae
-                leaves.append((run.copy(), last))
-        if ctx is None:
-            self.tree = ExecTree(self.curve, [[e.time_ordered_eval, e.addr_ordered_eval, last.addr % r, last.val % r]
-                                              for e, last in leaves])
-        self.time_eval0 = [1] + [e.time_ordered_eval for e, _ in leaves]
-        self.addr_eval0 = [1] + [e.addr_ordered_eval for e, _ in leaves]
-        self.root = self.tree.root
+        """`PortalJob.set_challenges`; an `on_device` job runs hk_exec_tree over the device's traces instead."""
+        if ctx is None or self.time is not None:
+            return super().set_challenges(chals, tr_chal, ctx)
+        self._take_challenges(chals, tr_chal)
+        self.dev1 = VkdStage1Device(self, ctx, dev0=self.dev0)
+        self.root = self.dev1.root
 
     def inputs(self, idx):
-        """What the subcircuit's Stage1Request carries, and its primitives' own witnesses."""
-        pair = lambda e: (e.addr, e.val)
-        w = dict(entry_chal=self.entry_chal, tr_chal=self.tr_chal, root=self.root, time=[pair(e) for e in self.time[idx]],
-                 addr=[pair(e) for e in self.addr[idx]], prev=pair(self.addr[idx - 1][-1]) if idx else (0, 0),
-                 time_eval0=self.time_eval0[idx], addr_eval0=self.addr_eval0[idx], path=self.tree.path(idx))
+        """The common inputs (`PortalJob.inputs`), and its primitives' own witnesses."""
+        w = super().inputs(idx)
         for prim in self.prims[idx]:
             if prim[0] == "hash leaf":
                 w["leaf"] = prim[1][1][1]
@@ -666,19 +493,6 @@ class VkdJob:
                 s = s[0] if s else self.split - 1
                 w["sibs"] = self.updates[ui].path[s * self.L:(s + 1) * self.L]
         return w
-
-    def assignment_ints(self, idx, **override):
-        w = self.inputs(idx)
-        w.update(override)
-        return self.make_class(idx).assignment_ints(w)[0]
-
-    def assignment_bytes(self, idx):
-        return self.make_class(idx).fc.enc(self.assignment_ints(idx))
-
-    def flat(self, which):
-        """Montgomery bytes of one flattened trace, (addr, val) per entry: hk_trace_sort's / hk_exec_tree's layout."""
-        tr = self.time if which == "time" else self.addr
-        return FrCodec(self.curve).enc([x % self.r for st in tr for e in st for x in (e.addr, e.val)])
 
     def values_bytes(self):
         """Montgomery bytes of the value table: what hk_vkd_trace writes as `values_out`."""
@@ -703,7 +517,6 @@ class VkdJob:
         from hk_trace_sort.  Returns a `VkdStage0Device`."""
         return VkdStage0Device(self, ctx)
 
-
     def stage1_device(self, ctx, dev0=None):
         """The job's stage-1 witness on the device: hk_exec_tree over the two traces, then per class hk_vkd_witness +
         hk_stage1_witness.  Needs `chal`.  dev0: the `stage0_device(ctx)` to read instead of running hk_vkd_trace again."""
@@ -711,80 +524,37 @@ class VkdJob:
         return VkdStage1Device(self, ctx, dev0=dev0 if dev0 is not None else getattr(self, "dev0", None))
 
 
-class VkdStage0Device:
-    """`values` (the value table), `traces = [time, addr]` as DeviceBuffers; `rows(members)` cuts the stage-0 witnesses of
-    subcircuits of ONE class out of the traces (hk_stage0_witness)."""
+class VkdStage0Device(PortalStage0Device):
+    """`values` (the value table) and `traces = [time, addr]` - value table and time-ordered trace computed by hk_vkd_trace -
+    and `params`, the Poseidon parameters on the device."""
 
-    def __init__(self, job, ctx):
-        from .capi import DeviceBuffer
-        from .poseidon import device_params
-        self.job, self.ctx, self.traces, self.values, self.params = job, ctx, [], None, None
-        try:
-            consts, n_consts, ld, nd = device_params(job.curve, FrCodec(job.curve))
-            self.params = (DeviceBuffer.from_host(ctx, consts), n_consts, ld, nd)
-            self.values, time = ctx.vkd_trace(job.tables(), self.params, device_out=True)
-            self.traces.append(time)
-            self.traces.append(ctx.trace_sort(2, time, int(job.offsets[-1]), device_out=True))
-        except Exception:
-            self.free()
-            raise
-
-    def rows(self, members):
-        """DeviceBuffer of len(members) x 4 k Fr: row b = `job.stage0_ints(members[b])`.  The caller frees it."""
-        from .capi import DeviceBuffer
-        members = np.ascontiguousarray(members, dtype=np.uint32)
-        k = int(self.job.offsets[int(members[0]) + 1] - self.job.offsets[int(members[0])]) if members.size else 1
-        w = DeviceBuffer(self.ctx, max(members.size * 4 * k * self.ctx.fr_bytes, 1))
-        try:
-            self.ctx.stage0_witness(self.job.offsets, k, self.traces[0], self.traces[1], members, w)
-        except Exception:
-            w.free()
-            raise
-        return w
-
-    def free(self):
-        for x in self.traces + [self.values] + ([self.params[0]] if self.params else []):
-            if x is not None:
-                x.free()
-        self.traces, self.values, self.params = [], None, None
+    def _time_trace(self):
+        consts, n_consts, ld, nd = device_params(self.job.curve, FrCodec(self.job.curve))
+        self.params = (self._own(capi.DeviceBuffer.from_host(self.ctx, consts)), n_consts, ld, nd)
+        self.values, time = (self._own(x) for x in self.ctx.vkd_trace(self.job.tables(), self.params, device_out=True))
+        return time
 
 
-class VkdStage1Device:
+class VkdStage1Device(PortalStage1Device):
     """The job's value table, traces and hk_exec_tree's outputs as DeviceBuffers; `fill(circ, members, z)` writes whole
     assignment rows of one class from them (hk_vkd_witness + hk_stage1_witness) and `check(pk, z, members)` tests them where
-    they lie (hk_pk_r1cs_check).  `root` is the one value read back."""
-    check = Stage1Device.check
+    they lie (hk_pk_r1cs_check).  dev0: the `VkdStage0Device` to read instead of making one here."""
 
     def __init__(self, job, ctx, dev0=None):
-        fc = FrCodec(job.curve)
-        self.job, self.ctx, self._own0, self.outs = job, ctx, None, ()
-        try:
-            if dev0 is None:
-                dev0 = self._own0 = VkdStage0Device(job, ctx)
-            self.dev0, self.params = dev0, dev0.params
-            self.tables = job.tables()
-            self.challenges = fc.enc(list(job.chal))
-            self.outs = ctx.exec_tree(self.params, 2, job.offsets, dev0.traces[0], dev0.traces[1], self.challenges,
-                                      device_out=True)
-        except Exception:
-            self.free()
-            raise
-        self.root = fc.dec(self.outs[4].to_host())[0]
+        self.tables = job.tables()
+        super().__init__(job, ctx, job.chal, dev0=dev0)
+
+    def _traces(self, dev0=None):
+        self.dev0 = dev0 if dev0 is not None else self._own(VkdStage0Device(self.job, self.ctx))
+        return self.dev0.traces
+
+    def _params(self):
+        return self.dev0.params                            # the stage-0 device's, which stay its own
 
     def fill(self, circ, members, z):
         """Row b of the DeviceBuffer z (len(members) x circ.n_v Fr) <- the assignment of subcircuit members[b], all of class
         `circ`: every column of the row is written by one of the two calls."""
         members = np.ascontiguousarray(members, dtype=np.uint32)
-        d = self.dev0
-        self.ctx.vkd_witness(self.tables, self.params, d.values, members, circ.n_v, circ.device_cols, z)
-        self.ctx.stage1_witness(self.params, circ.np_, self.job.offsets, d.traces[0], d.traces[1], self.challenges, self.outs,
-                                members, circ.n_v, (1, circ.N_INST, circ.pos_col0), z)
+        self.ctx.vkd_witness(self.tables, self.params, self.dev0.values, members, circ.n_v, circ.device_cols, z)
+        self._stage1_witness(circ, members, z)
         return z
-
-    def free(self):
-        for x in self.outs:
-            x.free()
-        if self._own0 is not None:
-            self._own0.free()
-            self._own0 = None
-        self.outs = ()

@@ -8,8 +8,8 @@ address -> larger timestamp; and over consecutive time-ordered entries: next tim
 (ark-r1cs-std `UInt32`, `FpVar`) are third-party and absent, so the constraint LAYOUT is this build's own (parity unpinned,
 DESIGN section 3); the FUNCTION is pinned by tests/test_vm_circuit_cpu.py.
 
-One program, two interpreters, on `sha_circuit.Tape` as `ShaMerkleSubcircuit._program`: BUILD records the rows, EVAL emits
-the assignment.  Instance: ONE, entry_chal_1..3, tr_chal, root (N_INST = 6).  An ENTRY takes 35 columns: val, addr,
+`RamSubcircuit` is a `portal_circuit.PortalSubcircuit` (one program, two interpreters on `sha_circuit.Tape`: BUILD records the
+rows, EVAL emits the assignment) with a portal block of its own and the base's membership block over six leaf fields.  Instance: ONE, entry_chal_1..3, tr_chal, root (N_INST = 6).  An ENTRY takes 35 columns: val, addr,
 timestamp bit 0 .. 31 (little-endian), read.  With k entries per order, the witness columns in order (the device calls
 hk_ram_stage0_witness / hk_ram_stage1_witness write the same order; csrc/ram_witness.cuh restates it):
 
@@ -21,7 +21,7 @@ hk_ram_stage0_witness / hk_ram_stage1_witness write the same order; csrc/ram_wit
         1 + 4 k                       address chain, the same
         35 k                          per consecutive pair of [previous] + address-ordered entries, d = addr' - addr:
                                       inv, same, sr, delta_0 .. delta_31
-    stage 1, membership block         Poseidon CRH over the six leaf fields, then the path (sha_circuit.poseidon_path_trace)
+    stage 1, membership block         `PortalSubcircuit.membership_block` over the six leaf fields
     stage 1, dummy products  3 n      (12, 12, 144) triples, one row each: the VM's `dummy_constraint_num / 2` products
 
 e needs three products of a challenge and a witness, and one R1CS row holds one: p1 and p2 carry the other two.
@@ -32,9 +32,9 @@ import functools
 
 import numpy as np
 
-from .cp_groth16 import CURVE_PARAMS, FrCodec, MultiStageConstraintSynthesizer
-from .sha_circuit import ONE, ShaMerkleSubcircuit, Tape, poseidon_path_trace
-from .transcript import RAM, RamTranscriptEntry, RunningEvaluation, sort_subtraces_by_addr
+from . import capi
+from .portal_circuit import ONE, PortalJob, PortalStage0Device, PortalStage1Device, PortalSubcircuit
+from .transcript import RAM, RamTranscriptEntry
 
 REGISTER_NUM = 16                  # vm/mod.rs
 ENTRY_COLS = 35                    # val, addr, 32 timestamp bits, read
@@ -77,48 +77,28 @@ class _Entry:
         return [(sign * (1 << j), c) for j, c in enumerate(self.bits)]
 
 
-class RamSubcircuit(MultiStageConstraintSynthesizer):
+class RamSubcircuit(PortalSubcircuit):
     """One proving-key class of a RAM job: a subcircuit that owns `n_portals` entries in each order.  `first` marks
     subcircuit 0 (evals pinned to 1, previous entry pinned to padding), `last` the final one (time eval == addr eval);
     depth = log2(number of subcircuits); dummy_products: the (12, 12, 144) triples after the membership block."""
-    N_INST = 6
-    # the Poseidon gadget, the CSR export and the QAP evaluation are the big-merkle class's, unchanged
-    _poseidon_crh = ShaMerkleSubcircuit._poseidon_crh
-    _poseidon_permute = ShaMerkleSubcircuit._poseidon_permute
-    csr = ShaMerkleSubcircuit.csr
-    qap_evaluate = ShaMerkleSubcircuit.qap_evaluate
-    total_num_stages = ShaMerkleSubcircuit.total_num_stages
+    N_INST = 6                                         # ONE, entry_chal_1..3, tr_chal, root
 
     def __init__(self, curve, n_portals, first=False, last=False, depth=3, dummy_products=0):
         assert n_portals >= 1 and depth >= 1
-        self.curve, self.np_, self.first, self.last, self.depth = curve, n_portals, first, last, depth
+        self.np_, self.first, self.last, self.depth = n_portals, first, last, depth
         self.dummy_products = dummy_products
-        from .poseidon import merkle_params
-        self.leaf_cfg, self.node_cfg = merkle_params(curve)
-        self.r = CURVE_PARAMS[curve]["r"]
-        self.fc = FrCodec(curve)
-        self.n0 = 2 * ENTRY_COLS * n_portals
         self.blocks = {}
-        t = Tape(self.N_INST)
-        self._program(t, None)
-        self.tape = t
-        self.n_c, self.n_wit, self.n_v = t.n_rows, t.n_wit, self.N_INST + t.n_wit
-        self._csr = None
+        self._build(curve, 2 * ENTRY_COLS * n_portals)
 
     # ---- the program: identical in BUILD and EVAL --------------------------------------------------------
     def _program(self, t, inp):
         """inp (EVAL): dict of per-batch lists, see `witness_batch`."""
         ev = not t.build
         B, r, k, ni = t.batch, self.r, self.np_, self.N_INST
-        C1, C2, C3, TR, ROOT = 1, 2, 3, 4, 5
+        C1, C2, C3, TR = 1, 2, 3, 4
         neg = r - 1
         col = lambda vals: t.alloc_full(vals if ev else None)
-        start = [0]
-
-        def block(name):
-            if t.build:
-                self.blocks[name] = (start[0], t.n_rows)
-            start[0] = t.n_rows
+        block = self._block_recorder(t)
 
         def entry(es):
             val = col(ev and [e.val % r for e in es])
@@ -211,25 +191,10 @@ class RamSubcircuit(MultiStageConstraintSynthesizer):
         block("last")
         assert ni + t.n_wit == self.col0 + 43 * k + 37
         # ---- the subcircuit's own execution leaf is in the tree (subcircuit_circuit.rs:233-260)
-        self.pos_col0 = ni + t.n_wit
         le = addr_e[-1]
         leaf_lcs = [[(1, t_final)], [(1, a_final)], [(1, le.addr)], [(1, le.val)], le.ts(), [(1, le.read)]]
-        if ev:
-            traces = []
-            for b in range(B):
-                x = le.es[b]
-                leaf = [t_vals[b], a_vals[b], x.addr % r, x.val % r, x.i % r, int(x.read) % r]
-                traces.append(poseidon_path_trace(self.leaf_cfg, self.node_cfg, leaf, inp["path_sib"][b], inp["path_idx"][b]))
-            it = iter(zip(*traces))
-        nxt = (lambda: t.alloc_full(list(next(it)))) if ev else (lambda: t.alloc_full(None))
-        cur = self._poseidon_crh(t, self.leaf_cfg, leaf_lcs, nxt)
-        for _lvl in range(self.depth):
-            bit, sib, left = nxt(), nxt(), nxt()
-            t.big_row([(1, bit)], [(1, ONE), (neg, bit)], [])
-            t.big_row([(1, bit)], [(1, sib), (neg, cur)], [(1, left), (neg, cur)])
-            cur = self._poseidon_crh(t, self.node_cfg, [[(1, left)], [(1, sib), (1, cur), (neg, left)]], nxt)
-        t.big_row([(1, cur), (neg, ROOT)], [(1, ONE)], [])
-        self.pos_cols = ni + t.n_wit - self.pos_col0
+        self.membership_block(t, leaf_lcs, ev and [[te, ae, x.addr % r, x.val % r, x.i % r, int(x.read) % r]
+                                                   for te, ae, x in zip(t_vals, a_vals, le.es)], inp)
         block("membership")
         # ---- the VM's dummy products (vm_constraints.rs:186-190): the same in every subcircuit of the class
         self.dummy_col0 = ni + t.n_wit
@@ -237,19 +202,6 @@ class RamSubcircuit(MultiStageConstraintSynthesizer):
             a, b, c = col(ev and [12] * B), col(ev and [12] * B), col(ev and [144] * B)
             t.big_row([(1, a)], [(1, b)], [(1, c)])
         block("dummy")
-
-    # ---- what the tests and the host mirror of hk_r1cs_check read ------------------------------------------
-    def rows(self):
-        """(A, B, C) as ark-style rows [(coeff, col)] - what cp_groth16.r1cs_bad_rows takes."""
-        big = self.tape.big
-        assert [e[0] for e in big] == list(range(self.n_c))
-        return [e[1] for e in big], [e[2] for e in big], [e[3] for e in big]
-
-    def block_of(self, row):
-        for name, (lo, hi) in self.blocks.items():
-            if lo <= row < hi:
-                return name
-        raise IndexError(row)
 
     def pair_rule_of(self, row):
         """(pair j, rule) of a row of the `pairs` block: rule one of same, step, first_write, sr, read_value, delta_boolean,
@@ -268,24 +220,14 @@ class RamSubcircuit(MultiStageConstraintSynthesizer):
             z[self.dummy_col0 + 3 * j:self.dummy_col0 + 3 * j + 3] = [12, 12, 144]
         return z
 
-    # ---- MultiStageConstraintSynthesizer -------------------------------------------------------------------
-    def generate_constraints(self, stage, cs):
-        z = self.template_ints()                           # setup mode: only the counts matter
-        ni = self.N_INST
-        cs.initialize_stage()
-        if stage == 0:
-            cs.witness_assignment.extend(z[ni:ni + self.n0])
-        else:
-            cs.instance_assignment.extend(z[1:ni])
-            cs.witness_assignment.extend(z[ni + self.n0:])
-            cs._n_constraints += self.n_c
-        cs.finalize_stage()
+    def _setup_assignment(self):
+        return self.template_ints()                        # setup mode: only the counts matter
 
     # ---- witness generation --------------------------------------------------------------------------------
-    def witness_batch(self, inputs):
+    def _batch_inputs(self, inputs):
         """inputs: per-subcircuit dicts (`RamJob.inputs`): chal (4 ints), root, time / addr (k entries each), prev (an entry),
-        time_eval0, addr_eval0, path (siblings, index).  Returns the full assignments as lists of ints."""
-        B, k = len(inputs), self.np_
+        time_eval0, addr_eval0, path (siblings, index)."""
+        k = self.np_
         assert all(i["chal"] == inputs[0]["chal"] for i in inputs)
         inp = dict(chal=inputs[0]["chal"])
         for key in ("time", "addr"):
@@ -296,25 +238,10 @@ class RamSubcircuit(MultiStageConstraintSynthesizer):
         inp["addr_eval0"] = [i["addr_eval0"] for i in inputs]
         inp["path_sib"] = [i["path"][0] for i in inputs]
         inp["path_idx"] = [i["path"][1] for i in inputs]
-        t = Tape(self.N_INST, batch=B)
-        self._program(t, inp)
-        assert t.n_wit == self.n_wit
-        out = []
-        for b in range(B):
-            z = [0] * self.n_v
-            z[:self.N_INST] = [1] + [c % self.r for c in inputs[b]["chal"]] + [inputs[b]["root"] % self.r]
-            for c, vals in t.full_records:
-                z[c] = int(vals[b]) % self.r
-            out.append(z)
-        return out
+        return inp
 
-    def assignment_ints(self, inputs):
-        return self.witness_batch(inputs if isinstance(inputs, list) else [inputs])
-
-    def assignment_bytes(self, inputs):
-        """Montgomery bytes of the full assignments, (batch, n_v * 32)."""
-        zs = self.assignment_ints(inputs)
-        return np.stack([self.fc.enc(z) for z in zs])
+    def _instance(self, w):
+        return list(w["chal"]) + [w["root"]]
 
 
 @functools.lru_cache(maxsize=None)
@@ -324,23 +251,17 @@ def ram_class(curve, n_portals, first, last, depth, dummy_products):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-class RamJob:
-    """A whole RAM job from its time-ordered subtraces (lists of `RamTranscriptEntry`): the address order
-    (coordinator.rs:92-123), the slices each subcircuit commits to in stage 0, and - once the round's four challenges are
-    in - the running evaluations, the execution tree and every subcircuit's inputs.  A class is (entries owned, first,
-    last); `time` / `addr` may be edited in place before `set_challenges` (the tests tamper with them)."""
+class RamJob(PortalJob):
+    """A whole RAM job from its time-ordered subtraces (lists of `RamTranscriptEntry`): a `PortalJob` over four-field
+    entries and four challenges.  A class is (entries owned, first, last)."""
+    MEM, ENTRY = RAM, RamTranscriptEntry
 
     def __init__(self, curve, time_subtraces, dummy_products=0):
         n = len(time_subtraces)
         assert n >= 2 and n & (n - 1) == 0 and all(len(st) for st in time_subtraces)
-        self.curve, self.n, self.depth = curve, n, n.bit_length() - 1
-        self.r = CURVE_PARAMS[curve]["r"]
+        self._set_shape(curve, n)
         self.dummy_products = dummy_products
-        self.time = [list(st) for st in time_subtraces]
-        self.addr = sort_subtraces_by_addr(self.time)
-        self.offsets = np.zeros(n + 1, np.uint32)
-        self.offsets[1:] = np.cumsum([len(st) for st in self.time])
-        self.chal = self.root = self.tree = None
+        self._set_traces(time_subtraces)
 
     def class_of(self, idx):
         """(entries owned, first, last): the proving-key class a subcircuit needs."""
@@ -357,55 +278,12 @@ class RamJob:
             out += [e.val % self.r, e.addr % self.r] + [(e.i >> j) & 1 for j in range(32)] + [int(e.read) % self.r]
         return out
 
+    def entry_input(self, e):
+        return e                                           # `RamSubcircuit` reads the entries themselves
+
     def set_challenges(self, chals, ctx=None):
-        """chals: (entry_chal_1, entry_chal_2, entry_chal_3, tr_chal), or the super commitment they are hashed from
-        (`RunningEvaluation.new(RAM, ...)`).  Running evaluations after every subcircuit and the execution tree
-        (coordinator.rs:125-174); with ctx (a capi.Context of the job's curve) from one hk_exec_tree call."""
-        from .poseidon import ExecTree
-        r = self.r
-        if isinstance(chals, (bytes, bytearray)) or hasattr(chals, "serialize_uncompressed"):
-            chals = RunningEvaluation.new(RAM, chals, r).challenges
-        self.chal = tuple(c % r for c in chals)
-        assert len(self.chal) == 4
-        if ctx is not None:
-            from .transcript import exec_tree_device
-            leaves, self.tree = exec_tree_device(ctx, RAM, self.chal, self.time, self.addr)
-            evs = [(e.time_ordered_eval, e.addr_ordered_eval) for e, _ in leaves]
-        else:
-            run = RunningEvaluation(RAM, r, self.chal)
-            evs, fields, last = [], [], RamTranscriptEntry.padding()
-            for ts, as_ in zip(self.time, self.addr):
-                for te, ae in zip(ts, as_):
-                    run.update_time_ordered(te)
-                    run.update_addr_ordered(ae)
-                    last = ae
-                evs.append((run.time_ordered_eval, run.addr_ordered_eval))
-                fields.append(list(evs[-1]) + [x % r for x in last.to_field_elements()])
-            self.tree = ExecTree(self.curve, fields)
-        self.time_eval0 = [1] + [e[0] for e in evs]
-        self.addr_eval0 = [1] + [e[1] for e in evs]
-        self.root = self.tree.root
-
-    def inputs(self, idx):
-        """What the subcircuit's Stage1Request carries (coordinator.rs:569-604)."""
-        return dict(chal=self.chal, root=self.root, time=self.time[idx], addr=self.addr[idx],
-                    prev=self.addr[idx - 1][-1] if idx else RamTranscriptEntry.padding(),
-                    time_eval0=self.time_eval0[idx], addr_eval0=self.addr_eval0[idx], path=self.tree.path(idx))
-
-    def assignment_ints(self, idx, **override):
-        """The subcircuit's full assignment (the host witness); override: inputs to replace (tests)."""
-        w = self.inputs(idx)
-        w.update(override)
-        return self.make_class(idx).assignment_ints(w)[0]
-
-    def assignment_bytes(self, idx):
-        return self.make_class(idx).fc.enc(self.assignment_ints(idx))
-
-    def flat(self, which):
-        """Montgomery bytes of one flattened trace, `to_field_elements()` order: hk_trace_sort's / hk_exec_tree's layout."""
-        fc = FrCodec(self.curve)
-        tr = self.time if which == "time" else self.addr
-        return fc.enc([x % self.r for st in tr for e in st for x in e.to_field_elements()])
+        """chals: (entry_chal_1, entry_chal_2, entry_chal_3, tr_chal), or the super commitment they are hashed from."""
+        super().set_challenges(chals, ctx=ctx)
 
     def stage0_device(self, ctx):
         """The job's stage-0 side on the device: the time-ordered trace uploaded once, the address-ordered one made from it
@@ -432,84 +310,42 @@ class VmJob(RamJob):
                          dummy_products=ops_per_chunk * (dummy_constraint_num // 2))
 
 
-class RamStage0Device:
+class RamStage0Device(PortalStage0Device):
     """`traces = [time, addr]` as DeviceBuffers (4 Fr per entry), the second sorted from the first on the device;
-    `rows(members)` cuts the stage-0 witnesses of subcircuits of ONE class out of them (hk_ram_stage0_witness)."""
+    `rows(members)`: 70 k Fr per subcircuit (hk_ram_stage0_witness)."""
+    ENTRY_FR, ENTRY_COLS = 4, ENTRY_COLS
 
-    def __init__(self, job, ctx):
-        from .capi import DeviceBuffer
-        self.job, self.ctx = job, ctx
-        time = DeviceBuffer.from_host(ctx, job.flat("time"))
-        self.traces = [time]
-        try:
-            self.traces.append(ctx.trace_sort(4, time, int(job.offsets[-1]), device_out=True))
-        except Exception:
-            self.free()
-            raise
-
-    def rows(self, members):
-        """DeviceBuffer of len(members) x 70 k Fr: row b = `job.stage0_ints(members[b])`.  The caller frees it."""
-        from .capi import DeviceBuffer
-        members = np.ascontiguousarray(members, dtype=np.uint32)
-        k = len(self.job.time[int(members[0])]) if members.size else 1
-        w = DeviceBuffer(self.ctx, max(members.size * 2 * ENTRY_COLS * k * self.ctx.fr_bytes, 1))
-        try:
-            self.ctx.ram_stage0_witness(self.job.offsets, k, self.traces[0], self.traces[1], members, w)
-        except Exception:
-            w.free()
-            raise
-        return w
-
-    def free(self):
-        for x in self.traces:
-            x.free()
-        self.traces = []
+    def _cut(self, k, members, w):
+        self.ctx.ram_stage0_witness(self.offsets, k, self.traces[0], self.traces[1], members, w)
 
 
-class RamStage1Device:
+class RamStage1Device(PortalStage1Device):
     """The job's traces and hk_exec_tree's RAM outputs as DeviceBuffers; `fill(circ, members, z)` writes whole assignment
-    rows of one class from them (hk_ram_stage1_witness).  `root` is the one value read back."""
+    rows of one class from them (hk_ram_stage1_witness).  traces: a `RamStage0Device`'s, to read instead of uploading and
+    sorting again."""
+    ENTRY_FR = 4
 
     def __init__(self, job, ctx, traces=None):
-        from .capi import DeviceBuffer
-        from .poseidon import device_params
-        fc = FrCodec(job.curve)
-        self.job, self.ctx, self._dev0, self.outs, self.params = job, ctx, None, (), None
-        try:
-            if traces is None:
-                self._dev0 = RamStage0Device(job, ctx)
-                traces = self._dev0.traces
-            self.traces = list(traces)
-            consts, n_consts, ld, nd = device_params(job.curve, fc)
-            self.params = (DeviceBuffer.from_host(ctx, consts), n_consts, ld, nd)
-            self.challenges = fc.enc(list(job.chal))
-            self.outs = ctx.exec_tree(self.params, 4, job.offsets, self.traces[0], self.traces[1], self.challenges,
-                                      device_out=True)
-        except Exception:
-            self.free()
-            raise
-        self.root = fc.dec(self.outs[4].to_host())[0]
-        self._templates = {}
+        self._templates = {}                               # per class: its constant row on the device
+        super().__init__(job, ctx, job.chal, traces=traces)
+
+    def _traces(self, traces=None):
+        return traces if traces is not None else self._own(RamStage0Device(self.job, self.ctx)).traces
 
     def fill(self, circ, members, z, template=True):
         """Row b of the DeviceBuffer z (len(members) x circ.n_v Fr) <- the assignment of subcircuit members[b], all of class
         `circ`.  template: start every row from the class's constant row (`circ.template_ints()`); False keeps the bytes
         of every column the call does not own."""
-        from .capi import DeviceBuffer
         members = np.ascontiguousarray(members, dtype=np.uint32)
         tm = None
         if template:
             if circ not in self._templates:
-                self._templates[circ] = DeviceBuffer.from_host(self.ctx, circ.fc.enc(circ.template_ints()))
+                self._templates[circ] = self._own(capi.DeviceBuffer.from_host(self.ctx, circ.fc.enc(circ.template_ints())))
             tm = self._templates[circ]
-        self.ctx.ram_stage1_witness(self.params, circ.np_, self.job.offsets, self.traces[0], self.traces[1], self.challenges,
+        self.ctx.ram_stage1_witness(self.params, circ.np_, self.offsets, self.traces[0], self.traces[1], self.challenges,
                                     self.outs, members, circ.n_v, (1, circ.N_INST, circ.col0, circ.pos_col0), z, template=tm)
         return z
 
     def free(self):
-        for x in ([self.params[0]] if self.params else []) + list(self.outs) + list(getattr(self, "_templates", {}).values()):
-            x.free()
-        if self._dev0 is not None:
-            self._dev0.free()
-            self._dev0 = None
-        self.traces, self.outs, self.params, self._templates = [], (), None, {}
+        super().free()
+        self._templates = {}
