@@ -3,6 +3,7 @@
 There is no CPU path: importing works anywhere (so host logic can be tested), but creating a
 `Context` without a gfx950 device raises, and a missing libhekaton.so raises at load time.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -323,6 +324,48 @@ class DeviceView(DeviceBuffer):
 
     def free(self):
         pass
+
+
+# ---- what the job entries' wrappers share -------------------------------------------------------------------------------
+def _hd(x):
+    """A host-or-device operand as the library reads it: a DeviceBuffer (or None, an absent one) as it is, anything else as
+    contiguous bytes.  The caller keeps the result alive over the call."""
+    return x if x is None or isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8)
+
+
+def _nullable(x):
+    """The address of a numpy array or DeviceBuffer, or None - NULL - for an absent or empty one: an empty numpy array has
+    a data pointer all the same."""
+    if x is None:
+        return None
+    if isinstance(x, DeviceBuffer):
+        return x.ptr if x.nbytes else None
+    return x.ctypes.data if x.size else None
+
+
+def _device_addr(z):
+    """A device output: a DeviceBuffer or its raw address."""
+    return z.ptr if isinstance(z, DeviceBuffer) else int(z)
+
+
+def _challenge_bytes(curve, challenges):
+    """Challenges given as ints or as their Montgomery bytes."""
+    if isinstance(challenges, np.ndarray):
+        return np.ascontiguousarray(challenges, dtype=np.uint8)
+    from .cp_groth16 import FrCodec
+    return FrCodec(curve).enc(list(challenges))
+
+
+@contextlib.contextmanager
+def _owned(outs, own=True):
+    """The outputs a wrapper allocated itself (`own`) are freed when the call under it raises; a caller's never are."""
+    try:
+        yield
+    except HekatonError:
+        for x in outs if own else ():
+            if isinstance(x, DeviceBuffer):
+                x.free()
+        raise
 
 
 class Context:
@@ -728,16 +771,11 @@ class Context:
         [n_sub x (2 + entry_fields)], nodes [2 n_sub - 1: leaf digests, each level, root last], siblings [n_sub x depth,
         bottom-up], root) as Montgomery bytes, or as DeviceBuffers when device_out is set; out: five buffers of those
         sizes to fill and return instead (numpy arrays or DeviceBuffers)."""
-        from .cp_groth16 import FrCodec
         consts, n_consts, ld, nd = params
         offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
         n_sub = offsets.size - 1
-        keep = [x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8)
-                for x in (time_entries, addr_entries)]
-        if isinstance(challenges, np.ndarray):
-            ch = np.ascontiguousarray(challenges, dtype=np.uint8)
-        else:
-            ch = FrCodec(self.curve).enc(list(challenges))
+        keep = [_hd(time_entries), _hd(addr_entries)]
+        ch = _challenge_bytes(self.curve, challenges)
         depth = max(n_sub, 1).bit_length() - 1
         fr = self.fr_bytes
         sizes = [2 * n_sub, (2 + entry_fields) * n_sub, 2 * n_sub - 1, n_sub * depth, 1]
@@ -747,17 +785,11 @@ class Context:
         else:
             outs = [DeviceBuffer(self, max(k, 1) * fr) if device_out else np.zeros(max(k, 0) * fr, dtype=np.uint8) for k in sizes]
         a, b = hk_poseidon_desc(*ld), hk_poseidon_desc(*nd)
-        pp = lambda x: ptr(x).value if (x.nbytes if isinstance(x, DeviceBuffer) else x.size) else None
-        d = hk_exec_tree_desc(n_sub, int(entry_fields), offsets.ctypes.data, pp(keep[0]), pp(keep[1]), ch.ctypes.data,
-                              ptr(consts), int(n_consts), C.pointer(a), C.pointer(b))
+        d = hk_exec_tree_desc(n_sub, int(entry_fields), offsets.ctypes.data, _nullable(keep[0]), _nullable(keep[1]),
+                              ch.ctypes.data, ptr(consts), int(n_consts), C.pointer(a), C.pointer(b))
         o = hk_exec_tree_out(*[ptr(x) for x in outs])
-        try:
+        with _owned(outs, out is None):
             check(self.lib.hk_exec_tree(self.handle, C.byref(d), C.byref(o)), "hk_exec_tree")
-        except HekatonError:
-            if device_out and out is None:
-                for x in outs:
-                    x.free()
-            raise
         return tuple(outs)
 
     def stage1_witness(self, params, n_portals, offsets, time_entries, addr_entries, challenges, exec_outs, sub_index, n_v,
@@ -769,27 +801,26 @@ class Context:
         n_portals: the entries each selected subcircuit owns per order; layout: (inst_col0, col0, pos_col0) - the first
         column of the three instance values, of the 10 n_portals + 4 portal columns and of the membership block; z_out:
         DeviceBuffer (or raw device address) of len(sub_index) x n_v Fr.  Every other column keeps its bytes."""
-        from .cp_groth16 import FrCodec
+        return self._stage1_witness("hk_stage1_witness", hk_stage1_desc, params, n_portals, offsets, time_entries, addr_entries,
+                                    challenges, exec_outs, sub_index, n_v, (), layout, z_out)
+
+    def _stage1_witness(self, symbol, desc, params, n_portals, offsets, time_entries, addr_entries, challenges, exec_outs,
+                        sub_index, n_v, extra, layout, z_out):
+        """stage1_witness / ram_stage1_witness: the two descriptors share their fields up to node_hash; `extra`: the
+        host-or-device operands the descriptor `desc` has between those and the columns of `layout`."""
         consts, n_consts, ld, nd = params
         offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
         n_sub = offsets.size - 1
         sub_index = np.ascontiguousarray(sub_index, dtype=np.uint32)
         evals, leaves, _nodes, siblings, root = exec_outs
-        keep = [x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8)
-                for x in (time_entries, addr_entries, evals, leaves, siblings, root)]
-        if isinstance(challenges, np.ndarray):
-            ch = np.ascontiguousarray(challenges, dtype=np.uint8)
-        else:
-            ch = FrCodec(self.curve).enc(list(challenges))
+        keep = [_hd(x) for x in (time_entries, addr_entries, evals, leaves, siblings, root) + tuple(extra)]
+        ch = _challenge_bytes(self.curve, challenges)
         a, b = hk_poseidon_desc(*ld), hk_poseidon_desc(*nd)
-        pp = lambda x: ptr(x).value if (x.nbytes if isinstance(x, DeviceBuffer) else x.size) else None
-        inst_col0, col0, pos_col0 = layout
-        d = hk_stage1_desc(n_sub, int(n_portals), max(n_sub, 1).bit_length() - 1, offsets.ctypes.data, pp(keep[0]), pp(keep[1]),
-                           ch.ctypes.data, pp(keep[2]), pp(keep[3]), pp(keep[4]), pp(keep[5]), ptr(consts), int(n_consts),
-                           C.pointer(a), C.pointer(b), int(inst_col0), int(col0), int(pos_col0))
-        zp = z_out.ptr if isinstance(z_out, DeviceBuffer) else int(z_out)
-        check(self.lib.hk_stage1_witness(self.handle, C.byref(d), sub_index.ctypes.data if sub_index.size else None,
-                                         sub_index.size, int(n_v), zp), "hk_stage1_witness")
+        d = desc(n_sub, int(n_portals), max(n_sub, 1).bit_length() - 1, offsets.ctypes.data, _nullable(keep[0]),
+                 _nullable(keep[1]), ch.ctypes.data, *[_nullable(x) for x in keep[2:6]], ptr(consts), int(n_consts),
+                 C.pointer(a), C.pointer(b), *[_nullable(x) for x in keep[6:]], *[int(c) for c in layout])
+        check(getattr(self.lib, symbol)(self.handle, C.byref(d), _nullable(sub_index), sub_index.size, int(n_v),
+                                        _device_addr(z_out)), symbol)
         return z_out
 
     def trace_sort(self, entry_fields, time_entries, n_entries=None, device_out=False, want_perm=False):
@@ -799,7 +830,7 @@ class Context:
         same layout - Montgomery bytes, or a DeviceBuffer when device_out is set - and with want_perm the pair (entries,
         perm): sorted entry j = time entry perm[j], uint32 (a numpy array, or a DeviceBuffer when device_out is set)."""
         k, fr = int(entry_fields), self.fr_bytes
-        src = time_entries if isinstance(time_entries, DeviceBuffer) else np.ascontiguousarray(time_entries, dtype=np.uint8)
+        src = _hd(time_entries)
         if n_entries is None:
             n_entries = (src.nbytes if isinstance(src, DeviceBuffer) else src.size) // (max(k, 1) * fr)
         n = int(n_entries)
@@ -809,15 +840,9 @@ class Context:
         else:
             out = np.zeros(n * k * fr, dtype=np.uint8)
             perm = np.zeros(n, dtype=np.uint32) if want_perm else None
-        try:
+        with _owned((out, perm)):
             check(self.lib.hk_trace_sort(self.handle, k, ptr(src) if n else None, n, ptr(out) if n else None,
                                          ptr(perm) if n else None), "hk_trace_sort")
-        except HekatonError:
-            if device_out:
-                out.free()
-                if perm is not None:
-                    perm.free()
-            raise
         return (out, perm) if want_perm else out
 
     def stage0_witness(self, offsets, n_portals, time_entries, addr_entries, sub_index, w_out):
@@ -825,13 +850,15 @@ class Context:
         stage-0 witness of subcircuit sub_index[b]: (addr, val) of its n_portals time-ordered, then of its n_portals address-
         ordered entries.  offsets: n_sub + 1 uint32 as exec_tree takes them; time_entries / addr_entries: Montgomery bytes or
         DeviceBuffers of offsets[-1] x 2 Fr (ROM).  w_out is what ProvingKey.commit_batch / hk_commit_batch read."""
+        return self._stage0_witness("hk_stage0_witness", offsets, n_portals, time_entries, addr_entries, sub_index, w_out)
+
+    def _stage0_witness(self, symbol, offsets, n_portals, time_entries, addr_entries, sub_index, w_out):
+        """stage0_witness / ram_stage0_witness: the two entries take the same arguments."""
         offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
         sub_index = np.ascontiguousarray(sub_index, dtype=np.uint32)
-        keep = [x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8) for x in (time_entries, addr_entries)]
-        wp = w_out.ptr if isinstance(w_out, DeviceBuffer) else int(w_out)
-        check(self.lib.hk_stage0_witness(self.handle, offsets.ctypes.data, offsets.size - 1, int(n_portals), ptr(keep[0]),
-                                         ptr(keep[1]), sub_index.ctypes.data if sub_index.size else None, sub_index.size, wp),
-              "hk_stage0_witness")
+        keep = [_hd(time_entries), _hd(addr_entries)]
+        check(getattr(self.lib, symbol)(self.handle, offsets.ctypes.data, offsets.size - 1, int(n_portals), ptr(keep[0]),
+                                        ptr(keep[1]), _nullable(sub_index), sub_index.size, _device_addr(w_out)), symbol)
         return w_out
 
     def sha_tree(self, leaves, n_sub, ns, n_portals, device_out=False):
@@ -842,17 +869,12 @@ class Context:
         n, k, fr = int(n_sub), int(n_portals), self.fr_bytes
         if isinstance(leaves, (list, tuple)):
             leaves = np.frombuffer(b"".join(leaves), np.uint8)
-        src = leaves if isinstance(leaves, DeviceBuffer) else np.ascontiguousarray(leaves, dtype=np.uint8).reshape(-1)
+        src = _hd(leaves)
         sizes = [32 * n, 2 * n * k * fr, fr]
         outs = [DeviceBuffer(self, max(b, 1)) if device_out else np.zeros(b, dtype=np.uint8) for b in sizes]
         o = hk_sha_tree_out(*[ptr(x) for x in outs])
-        try:
+        with _owned(outs):
             check(self.lib.hk_sha_tree(self.handle, ptr(src), n, int(ns), k, C.byref(o)), "hk_sha_tree")
-        except HekatonError:
-            if device_out:
-                for x in outs:
-                    x.free()
-            raise
         return tuple(outs)
 
     def sha_tree_inputs(self, leaves, digests, n_sub, n_inputs, sub_index, device_out=False):
@@ -860,18 +882,13 @@ class Context:
         kind - n_inputs 16: leaves and the padding subcircuit, from `leaves`; 54: parents and the root, from `digests`
         (sha_tree's).  leaves / digests: uint8 arrays, DeviceBuffers, or None for the one the kind does not read.  Returns
         uint32 (len(sub_index), n_inputs), or a DeviceBuffer of it when device_out is set."""
-        keep = [x if x is None or isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
-                for x in (leaves, digests)]
+        keep = [_hd(leaves), _hd(digests)]
         sub_index = np.ascontiguousarray(sub_index, dtype=np.uint32)
         batch, k = sub_index.size, int(n_inputs)
         out = DeviceBuffer(self, max(4 * batch * k, 1)) if device_out else np.zeros((batch, k), dtype=np.uint32)
-        try:
-            check(self.lib.hk_sha_tree_inputs(self.handle, ptr(keep[0]), ptr(keep[1]), int(n_sub), k,
-                                              sub_index.ctypes.data if batch else None, batch, ptr(out)), "hk_sha_tree_inputs")
-        except HekatonError:
-            if device_out:
-                out.free()
-            raise
+        with _owned((out,)):
+            check(self.lib.hk_sha_tree_inputs(self.handle, ptr(keep[0]), ptr(keep[1]), int(n_sub), k, _nullable(sub_index), batch,
+                                              ptr(out)), "hk_sha_tree_inputs")
         return out
 
     def ram_stage0_witness(self, offsets, n_portals, time_entries, addr_entries, sub_index, w_out):
@@ -879,14 +896,7 @@ class Context:
         the stage-0 witness of the RAM subcircuit sub_index[b]: 35 columns (val, addr, 32 timestamp bits, read) per entry, its
         n_portals time-ordered then its n_portals address-ordered entries.  offsets: n_sub + 1 uint32; time_entries /
         addr_entries: Montgomery bytes or DeviceBuffers of offsets[-1] x 4 Fr (RAM: what trace_sort(4, ...) takes and gives)."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
-        sub_index = np.ascontiguousarray(sub_index, dtype=np.uint32)
-        keep = [x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8) for x in (time_entries, addr_entries)]
-        wp = w_out.ptr if isinstance(w_out, DeviceBuffer) else int(w_out)
-        check(self.lib.hk_ram_stage0_witness(self.handle, offsets.ctypes.data, offsets.size - 1, int(n_portals), ptr(keep[0]),
-                                             ptr(keep[1]), sub_index.ctypes.data if sub_index.size else None, sub_index.size, wp),
-              "hk_ram_stage0_witness")
-        return w_out
+        return self._stage0_witness("hk_ram_stage0_witness", offsets, n_portals, time_entries, addr_entries, sub_index, w_out)
 
     def ram_stage1_witness(self, params, n_portals, offsets, time_entries, addr_entries, challenges, exec_outs, sub_index, n_v,
                            layout, z_out, template=None):
@@ -895,37 +905,15 @@ class Context:
         layout: (inst_col0, stage0_col0, col0, pos_col0) - the first column of the five instance values, of the 70 n_portals
         stage-0 columns, of the 43 n_portals + 37 portal columns and of the membership block; template: Montgomery bytes or
         a DeviceBuffer of n_v Fr every row starts from, or None: every column the call does not own keeps its bytes."""
-        from .cp_groth16 import FrCodec
-        consts, n_consts, ld, nd = params
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
-        n_sub = offsets.size - 1
-        sub_index = np.ascontiguousarray(sub_index, dtype=np.uint32)
-        evals, leaves, _nodes, siblings, root = exec_outs
-        keep = [x if x is None or isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8)
-                for x in (time_entries, addr_entries, evals, leaves, siblings, root, template)]
-        if isinstance(challenges, np.ndarray):
-            ch = np.ascontiguousarray(challenges, dtype=np.uint8)
-        else:
-            ch = FrCodec(self.curve).enc(list(challenges))
-        a, b = hk_poseidon_desc(*ld), hk_poseidon_desc(*nd)
-        pp = lambda x: None if x is None else ptr(x).value if (x.nbytes if isinstance(x, DeviceBuffer) else x.size) else None
-        inst_col0, stage0_col0, col0, pos_col0 = layout
-        d = hk_ram_stage1_desc(n_sub, int(n_portals), max(n_sub, 1).bit_length() - 1, offsets.ctypes.data, pp(keep[0]),
-                               pp(keep[1]), ch.ctypes.data, pp(keep[2]), pp(keep[3]), pp(keep[4]), pp(keep[5]), ptr(consts),
-                               int(n_consts), C.pointer(a), C.pointer(b), pp(keep[6]), int(inst_col0), int(stage0_col0),
-                               int(col0), int(pos_col0))
-        zp = z_out.ptr if isinstance(z_out, DeviceBuffer) else int(z_out)
-        check(self.lib.hk_ram_stage1_witness(self.handle, C.byref(d), sub_index.ctypes.data if sub_index.size else None,
-                                             sub_index.size, int(n_v), zp), "hk_ram_stage1_witness")
-        return z_out
+        return self._stage1_witness("hk_ram_stage1_witness", hk_ram_stage1_desc, params, n_portals, offsets, time_entries,
+                                    addr_entries, challenges, exec_outs, sub_index, n_v, (template,), layout, z_out)
 
     def _r1cs_job_desc(self, tables, witness):
         """(hk_r1cs_job_desc, what must stay alive beside it) from `PartitionedR1csJob.tables()` and the witness blocks."""
         arr = {k: np.ascontiguousarray(tables[k], dtype=np.uint32)
                for k in ("slot_offsets", "slot_rank", "slot_src", "wit_offsets", "body_len")}
-        wit = witness if isinstance(witness, DeviceBuffer) else np.ascontiguousarray(witness, dtype=np.uint8)
-        # a NULL table reaches the library as NULL: an empty numpy array has a data pointer all the same
-        p = lambda a: a.ctypes.data if a.size else None
+        wit = _hd(witness)
+        p = _nullable
         d = hk_r1cs_job_desc(int(tables["n_parts"]), int(tables["n_txs"]), arr["slot_offsets"].ctypes.data, p(arr["slot_rank"]),
                              p(arr["slot_src"]), int(tables["sets_per_tx"]), int(tables["tx_len"]), int(tables["tx_stride"]),
                              p(arr["wit_offsets"]), p(arr["body_len"]), ptr(wit))
@@ -939,17 +927,11 @@ class Context:
         device_out is set; out: a buffer of that size (numpy array or DeviceBuffer) to fill and return instead."""
         d, keep = self._r1cs_job_desc(tables, witness)
         n = int(tables["n_txs"]) * int(np.asarray(tables["slot_offsets"])[-1]) * 2 * self.fr_bytes
-        if out is None:
+        own = out is None
+        if own:
             out = DeviceBuffer(self, max(n, 1)) if device_out else np.zeros(n, dtype=np.uint8)
-            own = device_out
-        else:
-            own = False
-        try:
+        with _owned((out,), own):
             check(self.lib.hk_r1cs_job_trace(self.handle, C.byref(d), ptr(out)), "hk_r1cs_job_trace")
-        except HekatonError:
-            if own:
-                out.free()
-            raise
         return out
 
     def r1cs_job_witness(self, tables, witness, sub_index, n_v, body_col0, z_out):
@@ -959,9 +941,8 @@ class Context:
         address) of len(sub_index) x n_v Fr.  Every other column keeps its bytes (stage1_witness writes those)."""
         d, keep = self._r1cs_job_desc(tables, witness)
         sub_index = np.ascontiguousarray(sub_index, dtype=np.uint32)
-        zp = z_out.ptr if isinstance(z_out, DeviceBuffer) else int(z_out)
-        check(self.lib.hk_r1cs_job_witness(self.handle, C.byref(d), sub_index.ctypes.data if sub_index.size else None,
-                                           sub_index.size, int(n_v), int(body_col0), zp), "hk_r1cs_job_witness")
+        check(self.lib.hk_r1cs_job_witness(self.handle, C.byref(d), _nullable(sub_index), sub_index.size, int(n_v),
+                                           int(body_col0), _device_addr(z_out)), "hk_r1cs_job_witness")
         return z_out
 
     def _vkd_desc(self, tables, params, values=None):
@@ -969,15 +950,12 @@ class Context:
         (`poseidon.device_params`, the bytes or a DeviceBuffer first) and, for vkd_witness, the value table."""
         consts, n_consts, ld, nd = params
         arr = {k: np.ascontiguousarray(tables[k], dtype=np.uint32) for k in ("kinds", "slot_addr", "slot_src")}
-        dev = lambda x: x if x is None or isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8).reshape(-1)
-        keep = [dev(tables["leaves"]), dev(tables["siblings"]), dev(consts), dev(tables["roots"]), dev(values)]
+        keep = [_hd(x) for x in (tables["leaves"], tables["siblings"], consts, tables["roots"], values)]
         a, b = hk_poseidon_desc(*ld), hk_poseidon_desc(*nd)
-        # a NULL table reaches the library as NULL: an empty numpy array has a data pointer all the same
-        p = lambda x: None if x is None else ptr(x).value if (x.nbytes if isinstance(x, DeviceBuffer) else x.size) else None
-        q = lambda x: x.ctypes.data if x.size else None
-        d = hk_vkd_desc(int(tables["depth"]), int(tables["split"]), int(tables["n_updates"]), q(arr["kinds"]), p(keep[0]),
+        p = _nullable
+        d = hk_vkd_desc(int(tables["depth"]), int(tables["split"]), int(tables["n_updates"]), p(arr["kinds"]), p(keep[0]),
                         p(keep[1]), p(keep[2]), int(n_consts), C.pointer(a), C.pointer(b), p(keep[3]), arr["slot_addr"].size,
-                        q(arr["slot_addr"]), q(arr["slot_src"]), p(keep[4]))
+                        p(arr["slot_addr"]), p(arr["slot_src"]), p(keep[4]))
         return d, (arr, keep, a, b)
 
     def vkd_trace(self, tables, params, device_out=False, out=None):
@@ -989,16 +967,11 @@ class Context:
         d, keep = self._vkd_desc(tables, params)
         fr = self.fr_bytes
         sizes = [(3 + int(tables["n_updates"]) * (2 + 3 * int(tables["split"]))) * fr, 2 * int(d.n_slots) * fr]
-        own = out is None and device_out
-        if out is None:
+        own = out is None
+        if own:
             out = tuple(DeviceBuffer(self, max(b, 1)) if device_out else np.zeros(b, dtype=np.uint8) for b in sizes)
-        try:
+        with _owned(out, own):
             check(self.lib.hk_vkd_trace(self.handle, C.byref(d), ptr(out[0]), ptr(out[1])), "hk_vkd_trace")
-        except HekatonError:
-            if own:
-                for x in out:
-                    x.free()
-            raise
         return out
 
     def vkd_witness(self, tables, params, values, sub_index, n_v, cols, z_out):
@@ -1010,9 +983,8 @@ class Context:
         d, keep = self._vkd_desc(tables, params, values)
         sub_index = np.ascontiguousarray(sub_index, dtype=np.uint32)
         c = cols if isinstance(cols, hk_vkd_cols) else hk_vkd_cols(*[int(x) for x in cols])
-        zp = z_out.ptr if isinstance(z_out, DeviceBuffer) else None if z_out is None else int(z_out)
-        check(self.lib.hk_vkd_witness(self.handle, C.byref(d), sub_index.ctypes.data if sub_index.size else None,
-                                      sub_index.size, int(n_v), C.byref(c), zp), "hk_vkd_witness")
+        check(self.lib.hk_vkd_witness(self.handle, C.byref(d), _nullable(sub_index), sub_index.size, int(n_v), C.byref(c),
+                                      None if z_out is None else _device_addr(z_out)), "hk_vkd_witness")
         return z_out
 
     def _r1cs_call(self, fn, head, z, n_v, batch, cap, want_vals):

@@ -279,44 +279,33 @@ k_et_paths(const Fr* __restrict__ nodes, u32 n_sub, u32 depth, Fr* __restrict__ 
 template <class C>
 hk_status Ops<C>::exec_tree(hk_ctx* ctx, const hk_exec_tree_desc* d, const hk_exec_tree_out* o) {
     const size_t n_sub = d->n_sub, K = d->entry_fields;
-    if (n_sub < 2 || (n_sub & (n_sub - 1)) || n_sub > ((size_t)1 << 24)) return HK_ERR_ARG;   // ark MerkleTree::new: 2^k >= 2 leaves
+    u32 depth = 0;
+    while (((size_t)1 << depth) < n_sub) depth++;
+    HK_TRY(tree_shape_check(n_sub, depth));                 // n_sub itself: depth is derived from it
     if (K != 2 && K != 4) return HK_ERR_ARG;
     if (!d->offsets || !d->challenges_mont || !d->consts_mont || !d->leaf_hash || !d->node_hash || !o->leaves_mont ||
         !o->siblings_mont || !o->root_mont)
         return HK_ERR_ARG;
-    if (d->offsets[0] != 0) return HK_ERR_ARG;
-    for (size_t i = 0; i < n_sub; i++)
-        if (d->offsets[i + 1] < d->offsets[i]) return HK_ERR_ARG;
-    const size_t n = d->offsets[n_sub];
+    HK_TRY(offsets_check(d->offsets, n_sub));
+    const size_t n = d->offsets[n_sub], nf = 2 + K;
     if (n && (!d->time_entries_mont || !d->addr_entries_mont)) return HK_ERR_ARG;
-    const hk_poseidon_desc *lh = d->leaf_hash, *nh = d->node_hash;
-    for (const hk_poseidon_desc* p : {lh, nh}) {
-        if ((p->full_rounds & 1) || p->full_rounds + p->partial_rounds == 0 ||
-            (size_t)p->consts_offset + (size_t)(p->full_rounds + p->partial_rounds) * p->t + (size_t)p->t * p->t > d->n_consts)
-            return HK_ERR_ARG;
-    }
-    // compiled for the reference's two instances (poseidon_util.rs:53-62), as hk_poseidon_path is
-    if (lh->t != 4 || nh->t != 3 || lh->alpha != 5 || nh->alpha != 17) return HK_ERR_ARG;
+    HK_TRY(poseidon_pair_check(d->leaf_hash, d->node_hash, d->n_consts));
 
-    const size_t nf = 2 + K;
-    u32 depth = 0;
-    while (((size_t)1 << depth) < n_sub) depth++;
     const u32 n_chunks = (u32)(n / ET_CHUNK + 1), n_tiles = (n_chunks + ET_SCAN_TILE - 1) / ET_SCAN_TILE;
     EtChal<Fr> ch;
     for (size_t k = 0; k < 4; k++) {
         ch.c[k] = Fr::zero();
         if (k < K) memcpy(&ch.c[k], (const char*)d->challenges_mont + k * sizeof(Fr), sizeof(Fr));
     }
+    Staged in[3] = {staged(d->time_entries_mont, n * K * sizeof(Fr)), staged(d->addr_entries_mont, n * K * sizeof(Fr)),
+                    staged(d->consts_mont, d->n_consts * sizeof(Fr))};
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void *te, *ae, *cd;
     u32* off_d;
     Fr *prods, *tops, *evals, *leaves, *nodes, *sibs;
     HK_TRY(L->carve([&](Carve& c) {
-        te = c.take(n * K * sizeof(Fr));
-        ae = c.take(n * K * sizeof(Fr));
-        cd = c.take(d->n_consts * sizeof(Fr));
+        stage_carve(c, in, 3);
         off_d = c.n<u32>(n_sub + 1);
         prods = c.n<Fr>(2 * (size_t)n_chunks);
         tops = c.n<Fr>(2 * (size_t)n_tiles);
@@ -326,11 +315,9 @@ hk_status Ops<C>::exec_tree(hk_ctx* ctx, const hk_exec_tree_desc* d, const hk_ex
         sibs = c.n<Fr>(n_sub * depth);
     }));
     hipStream_t s = L->stream;
-    HK_TRY(to_device(L, d->time_entries_mont, n * K * sizeof(Fr), &te));
-    HK_TRY(to_device(L, d->addr_entries_mont, n * K * sizeof(Fr), &ae));
-    HK_TRY(to_device(L, d->consts_mont, d->n_consts * sizeof(Fr), &cd));
+    HK_TRY(stage_upload(L, in, 3));
     HK_HIP(hipMemcpyAsync(off_d, d->offsets, 4 * (n_sub + 1), hipMemcpyHostToDevice, s));
-    const Fr *tp = (const Fr*)te, *ap = (const Fr*)ae, *cp = (const Fr*)cd;
+    const Fr *tp = (const Fr*)in[0].p, *ap = (const Fr*)in[1].p, *cp = (const Fr*)in[2].p;
     const u32 ns = (u32)n_sub;
 
     // (a) running evaluations and leaves
@@ -348,8 +335,7 @@ hk_status Ops<C>::exec_tree(hk_ctx* ctx, const hk_exec_tree_desc* d, const hk_ex
                            n_tiles, ch, (const Fr*)prods, (const Fr*)tops, evals, leaves);
 
     // (b) the tree: nodes = leaf digests, then each level, root last
-    PoseidonDesc a{lh->t, lh->alpha, lh->full_rounds, lh->partial_rounds, lh->consts_offset};
-    PoseidonDesc b{nh->t, nh->alpha, nh->full_rounds, nh->partial_rounds, nh->consts_offset};
+    const PoseidonDesc a = poseidon_desc(d->leaf_hash), b = poseidon_desc(d->node_hash);
     const bool fused_leaves = ns <= ET_WG_STATES;
     if (!fused_leaves)
         hipLaunchKernelGGL((k_et_leaf_hash<Fr>), dim3((ns + ET_WG_STATES - 1) / ET_WG_STATES), dim3(256), 0, s, cp, a,

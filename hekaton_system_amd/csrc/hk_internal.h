@@ -359,4 +359,35 @@ static inline float ev_ms(hipEvent_t a, hipEvent_t b) {
 // *p: `bytes` of lane scratch carved for the input `src`.  A host `src` is copied there; a device `src` replaces *p.
 hk_status to_device(Lane* L, const void* src, size_t bytes, const void** p);
 
+// ---- a call's host-or-device buffers ----------------------------------------------------------
+// One record per input or output.  staged(): where the buffer lives is asked ONCE, before the carve - a device-resident or
+// absent (NULL) one takes no scratch.  stage_carve() inside the call's carve lambda: p = the buffer itself when it is
+// resident, else its slice of scratch.  Kernels read and write p; stage_upload() queues the host inputs' copies in front of
+// them, stage_download() the host outputs' copies behind them (before settle()).
+struct Staged {
+    const void* buf;              // the caller's pointer; NULL: absent
+    size_t bytes;
+    size_t scratch;               // bytes of lane scratch: `bytes` for a host buffer, 0 for a resident or absent one
+    void* p;                      // what the kernels get (after stage_carve)
+};
+static inline Staged staged(const void* buf, size_t bytes) {
+    return {buf, bytes, buf && !is_device_ptr(buf) ? bytes : 0, nullptr};
+}
+static inline void stage_carve(Carve& c, Staged* s, size_t n) {
+    for (size_t k = 0; k < n; k++) {
+        void* slice = c.take(s[k].scratch);
+        s[k].p = s[k].scratch ? slice : (void*)s[k].buf;
+    }
+}
+static inline hk_status stage_upload(Lane* L, const Staged* s, size_t n) {
+    for (size_t k = 0; k < n; k++)
+        if (s[k].scratch) HK_HIP(hipMemcpyAsync(s[k].p, s[k].buf, s[k].bytes, hipMemcpyHostToDevice, L->stream));
+    return HK_OK;
+}
+static inline hk_status stage_download(Lane* L, const Staged* s, size_t n) {
+    for (size_t k = 0; k < n; k++)
+        if (s[k].scratch) HK_HIP(hipMemcpyAsync((void*)s[k].buf, s[k].p, s[k].bytes, hipMemcpyDeviceToHost, L->stream));
+    return HK_OK;
+}
+
 }  // namespace hk

@@ -188,16 +188,15 @@ hk_status Ops<C>::r1cs_check(hk_ctx* ctx, const hk_csr* A, const hk_csr* B, cons
     if (done) return HK_OK;
     R1csRun<C> run(A->n_rows, n_v, batch, bad_rows, bad_vals, cap);
     R1csStage stage(A, B, Cm, n_v, sizeof(Fr));
-    const size_t z_bytes = batch * n_v * sizeof(Fr), z_staged = is_device_ptr(z) ? 0 : z_bytes;
+    Staged zin = staged(z, batch * n_v * sizeof(Fr));
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void* zd;
-    HK_TRY(L->carve([&](Carve& c) { stage.carve(c); zd = c.take(z_staged); run.carve(c); }));
+    HK_TRY(L->carve([&](Carve& c) { stage.carve(c); stage_carve(c, &zin, 1); run.carve(c); }));
     CsrDev D[3];
     HK_TRY(stage.upload(L, D));
-    HK_TRY(to_device(L, z, z_bytes, &zd));
-    HK_TRY(run.run(L->stream, D, (const Fr*)zd, verdicts, bad_rows, bad_vals));
+    HK_TRY(stage_upload(L, &zin, 1));
+    HK_TRY(run.run(L->stream, D, (const Fr*)zin.p, verdicts, bad_rows, bad_vals));
     return L->settle();
 }
 
@@ -211,14 +210,13 @@ hk_status Ops<C>::pk_r1cs_check(hk_ctx* ctx, const hk_pk* h, const void* z, size
     HK_TRY(r1cs_check_args(pk->csr[0].n_rows, n_v, batch, z, verdicts, bad_rows, bad_vals, cap, &done));
     if (done) return HK_OK;
     R1csRun<C> run(pk->csr[0].n_rows, n_v, batch, bad_rows, bad_vals, cap);
-    const size_t z_bytes = batch * n_v * sizeof(Fr), z_staged = is_device_ptr(z) ? 0 : z_bytes;
+    Staged zin = staged(z, batch * n_v * sizeof(Fr));
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void* zd;
-    HK_TRY(L->carve([&](Carve& c) { zd = c.take(z_staged); run.carve(c); }));
-    HK_TRY(to_device(L, z, z_bytes, &zd));
-    HK_TRY(run.run(L->stream, pk->csr, (const Fr*)zd, verdicts, bad_rows, bad_vals));
+    HK_TRY(L->carve([&](Carve& c) { stage_carve(c, &zin, 1); run.carve(c); }));
+    HK_TRY(stage_upload(L, &zin, 1));
+    HK_TRY(run.run(L->stream, pk->csr, (const Fr*)zin.p, verdicts, bad_rows, bad_vals));
     return L->settle();
 }
 

@@ -15,7 +15,6 @@
 //                Fr of one witness and stores 64 consecutive Fr of one row (the first lane of a row stores the constant 1).
 #pragma once
 #include "stage1.cuh"
-#include "sha_tree.cuh"      // st_overlap
 
 namespace hk {
 
@@ -62,9 +61,7 @@ static inline hk_status rj_check(const hk_r1cs_job_desc* d, size_t* n_wit) {
     const size_t P = d->n_parts, T = d->n_txs;
     if (P == 0 || T == 0 || P * T > ((size_t)1 << 24)) return HK_ERR_ARG;                      // as hk_exec_tree's n_sub
     if (d->tx_len == 0) return HK_ERR_ARG;                                                     // a block holds wire 0 at least
-    if (d->slot_offsets[0] != 0) return HK_ERR_ARG;
-    for (size_t p = 0; p < P; p++)
-        if (d->slot_offsets[p + 1] < d->slot_offsets[p]) return HK_ERR_ARG;
+    HK_TRY(offsets_check(d->slot_offsets, P));
     const size_t S = d->slot_offsets[P];
     for (size_t s = 0; s < S; s++) {
         if (d->slot_rank[s] >= d->sets_per_tx) return HK_ERR_ARG;
@@ -83,30 +80,28 @@ hk_status Ops<C>::r1cs_job_trace(hk_ctx* ctx, const hk_r1cs_job_desc* d, void* t
     HK_TRY(rj_check(d, &n_wit));
     const size_t S = d->slot_offsets[d->n_parts], n_fr = 2 * S * d->n_txs, fr = sizeof(Fr);
     if (n_fr == 0) return HK_OK;
-    if (!time_entries_out || st_overlap(time_entries_out, n_fr * fr, d->witness_mont, n_wit * fr)) return HK_ERR_ARG;
-    const bool out_dev = is_device_ptr(time_entries_out);
-    const size_t staged = is_device_ptr(d->witness_mont) ? 0 : n_wit * fr;
+    if (!time_entries_out || bufs_overlap(time_entries_out, n_fr * fr, d->witness_mont, n_wit * fr)) return HK_ERR_ARG;
+    Staged in = staged(d->witness_mont, n_wit * fr), out = staged(time_entries_out, n_fr * fr);
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void* wit;
     u32 *rank_d, *src_d;
-    Fr* out_d;
     HK_TRY(L->carve([&](Carve& c) {
-        wit = c.take(staged);
+        stage_carve(c, &in, 1);
         rank_d = c.n<u32>(S);
         src_d = c.n<u32>(S);
-        out_d = c.n<Fr>(out_dev ? 0 : n_fr);
+        stage_carve(c, &out, 1);
     }));
     hipStream_t s = L->stream;
-    HK_TRY(to_device(L, d->witness_mont, n_wit * fr, &wit));
+    const void* wit = in.p;
+    Fr* out_d = (Fr*)out.p;
+    HK_TRY(stage_upload(L, &in, 1));
     HK_HIP(hipMemcpyAsync(rank_d, d->slot_rank, 4 * S, hipMemcpyHostToDevice, s));
     HK_HIP(hipMemcpyAsync(src_d, d->slot_src, 4 * S, hipMemcpyHostToDevice, s));
-    if (out_dev) out_d = (Fr*)time_entries_out;
     hipLaunchKernelGGL((k_rj_trace<Fr>), dim3((u32)((n_fr + 255) / 256)), dim3(256), 0, s, (const Fr*)wit, (const u32*)rank_d,
                        (const u32*)src_d, (u32)S, d->sets_per_tx, d->tx_stride, (u32)n_fr, out_d);
     HK_HIP(hipGetLastError());
-    if (!out_dev) HK_HIP(hipMemcpyAsync(time_entries_out, out_d, n_fr * fr, hipMemcpyDeviceToHost, s));
+    HK_TRY(stage_download(L, &out, 1));
     return L->settle();
 }
 
@@ -132,19 +127,19 @@ hk_status Ops<C>::r1cs_job_witness(hk_ctx* ctx, const hk_r1cs_job_desc* d, const
     if (batch == 0) return HK_OK;
     const size_t len = d->body_len[sub_index[0] % P];
     if (body_col0 < 1 || body_col0 > n_v || len > n_v - body_col0) return HK_ERR_ARG;
-    if (!is_device_ptr(z_out) || st_overlap(z_out, batch * n_v * fr, d->witness_mont, n_wit * fr)) return HK_ERR_ARG;
-    const size_t staged = is_device_ptr(d->witness_mont) ? 0 : n_wit * fr;
+    if (!is_device_ptr(z_out) || bufs_overlap(z_out, batch * n_v * fr, d->witness_mont, n_wit * fr)) return HK_ERR_ARG;
+    Staged in = staged(d->witness_mont, n_wit * fr);
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void* wit;
     u64* base_d;
     HK_TRY(L->carve([&](Carve& c) {
-        wit = c.take(staged);
+        stage_carve(c, &in, 1);
         base_d = c.n<u64>(batch);
     }));
     hipStream_t s = L->stream;
-    HK_TRY(to_device(L, d->witness_mont, n_wit * fr, &wit));
+    const void* wit = in.p;
+    HK_TRY(stage_upload(L, &in, 1));
     HK_HIP(hipMemcpyAsync(base_d, base.data(), 8 * batch, hipMemcpyHostToDevice, s));
     const u32 per = (u32)(1 + len);                                // <= n_v < 2^31
     for (size_t b0 = 0; b0 < batch; b0 += RJ_GRID_ROWS) {           // a grid's y holds at most 65 535 rows

@@ -239,22 +239,6 @@ __global__ void __launch_bounds__(256) k_rw_chain_walk(RwArgs<Fr> a, EtChal<Fr> 
 
 #endif  // __HIPCC__
 
-// what both calls check of (offsets, sub_index) and what they hand the kernels: (subcircuit, its first entry) per row
-static inline hk_status rw_rows(const uint32_t* offsets, size_t n_sub, size_t K, const uint32_t* sub_index, size_t batch,
-                                std::vector<u32>& rows) {
-    if (offsets[0] != 0) return HK_ERR_ARG;
-    for (size_t i = 0; i < n_sub; i++)
-        if (offsets[i + 1] < offsets[i]) return HK_ERR_ARG;
-    rows.resize(2 * batch);
-    for (size_t b = 0; b < batch; b++) {
-        const u32 i = sub_index[b];
-        if (i >= n_sub || offsets[i + 1] - offsets[i] != K) return HK_ERR_ARG;
-        rows[2 * b] = i;
-        rows[2 * b + 1] = offsets[i];
-    }
-    return HK_OK;
-}
-
 // the lane counts of both calls: every grid is ceil(lanes / 256) blocks, lanes a u64 below 2^38
 static inline bool rw_lanes_ok(size_t K, size_t batch, size_t n_v) {
     return K != 0 && K <= (1u << 16) && batch < (1u << 20) && batch * (40 + 105 * K) < ((size_t)1 << 38) &&
@@ -269,31 +253,28 @@ hk_status Ops<C>::ram_stage0_witness(hk_ctx* ctx, const uint32_t* offsets, uint3
     const size_t K = n_portals;
     if (n_sub == 0 || !rw_lanes_ok(K, batch, 70 * K)) return HK_ERR_ARG;
     std::vector<u32> rows;                                 // outlives the lane's copy
-    HK_TRY(rw_rows(offsets, n_sub, K, sub_index, batch, rows));
+    HK_TRY(portal_rows(offsets, n_sub, K, sub_index, batch, rows));
     if (batch == 0) return HK_OK;
     if (!is_device_ptr(w_out)) return HK_ERR_ARG;
     const size_t bytes = (size_t)offsets[n_sub] * 4 * sizeof(Fr);
-    const size_t staged[2] = {is_device_ptr(time_entries) ? 0 : bytes, is_device_ptr(addr_entries) ? 0 : bytes};
+    Staged in[2] = {staged(time_entries, bytes), staged(addr_entries, bytes)};
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void *te, *ae;
     u32 *rows_d, *ts32, *same, *flag;
     HK_TRY(L->carve([&](Carve& c) {
-        te = c.take(staged[0]);
-        ae = c.take(staged[1]);
+        stage_carve(c, in, 2);
         rows_d = c.n<u32>(2 * batch);
         ts32 = c.n<u32>(batch * (2 * K + 1));
         same = c.n<u32>(batch * K);
         flag = c.n<u32>(1);
     }));
     hipStream_t s = L->stream;
-    HK_TRY(to_device(L, time_entries, bytes, &te));
-    HK_TRY(to_device(L, addr_entries, bytes, &ae));
+    HK_TRY(stage_upload(L, in, 2));
     HK_HIP(hipMemcpyAsync(rows_d, rows.data(), 4 * rows.size(), hipMemcpyHostToDevice, s));
     HK_HIP(hipMemsetAsync(flag, 0, 4, s));
     // a row of w_out is the 70 K stage-0 columns alone: stage0_col0 = 0, n_v = 70 K; the other ranges are never written
-    RwArgs<Fr> a{(const Fr*)te, (const Fr*)ae, rows_d, ts32, same, (u32)batch, (u32)K, 70 * K, 0, 0, 0, (Fr*)w_out};
+    RwArgs<Fr> a{(const Fr*)in[0].p, (const Fr*)in[1].p, rows_d, ts32, same, (u32)batch, (u32)K, 70 * K, 0, 0, 0, (Fr*)w_out};
     const u64 n_canon = (u64)batch * (2 * K + 1), n_fill = (u64)batch * 70 * K;
     // the timestamps and the error word first: nothing touches w_out before the host has read it (as hk_ram_stage1_witness)
     hipLaunchKernelGGL((k_rw_canon<Fr>), dim3((u32)((n_canon + 255) / 256)), dim3(256), 0, s, a, flag);
@@ -310,45 +291,24 @@ hk_status Ops<C>::ram_stage0_witness(hk_ctx* ctx, const uint32_t* offsets, uint3
 template <class C>
 hk_status Ops<C>::ram_stage1_witness(hk_ctx* ctx, const hk_ram_stage1_desc* d, const uint32_t* sub_index, size_t batch, size_t n_v,
                                      void* z_out) {
-    if (!d->offsets || !d->time_entries_mont || !d->addr_entries_mont || !d->challenges_mont || !d->evals_mont ||
-        !d->leaves_mont || !d->siblings_mont || !d->root_mont || !d->consts_mont || !d->leaf_hash || !d->node_hash ||
-        (batch && (!sub_index || !z_out)))
-        return HK_ERR_ARG;
     const size_t n_sub = d->n_sub, K = d->n_portals, depth = d->depth;
-    if (n_sub < 2 || (n_sub & (n_sub - 1)) || n_sub > ((size_t)1 << 24) || depth > 24 || ((size_t)1 << depth) != n_sub)
-        return HK_ERR_ARG;
     if (!rw_lanes_ok(K, batch, n_v)) return HK_ERR_ARG;
     std::vector<u32> rows;                                 // outlives the lane's copies
-    HK_TRY(rw_rows(d->offsets, n_sub, K, sub_index, batch, rows));
-    const hk_poseidon_desc *lh = d->leaf_hash, *nh = d->node_hash;
-    for (const hk_poseidon_desc* p : {lh, nh}) {
-        if ((p->full_rounds & 1) || p->full_rounds + p->partial_rounds == 0 ||
-            (size_t)p->consts_offset + (size_t)(p->full_rounds + p->partial_rounds) * p->t + (size_t)p->t * p->t > d->n_consts)
-            return HK_ERR_ARG;
-    }
-    if (lh->t != 4 || nh->t != 3 || lh->alpha != 5 || nh->alpha != 17) return HK_ERR_ARG;      // as hk_stage1_witness
+    EtChal<Fr> ch;
+    HK_TRY(s1_prologue(d, sub_index, batch, z_out, 4, rows, ch));
     // the four column ranges: inside [1, n_v), no two overlapping.  Six leaf fields take two permutations, as four do.
     const size_t lo[4] = {d->inst_col0, d->stage0_col0, d->col0, d->pos_col0};
-    const size_t len[4] = {5, 70 * K, 43 * K + 37, 2 * poseidon_trace_len(lh) + depth * (3 + poseidon_trace_len(nh))};
-    for (int a = 0; a < 4; a++) {
-        if (lo[a] < 1 || lo[a] > n_v || len[a] > n_v - lo[a]) return HK_ERR_ARG;
-        for (int b = 0; b < a; b++)
-            if (lo[a] < lo[b] + len[b] && lo[b] < lo[a] + len[a]) return HK_ERR_ARG;
-    }
+    const size_t len[4] = {5, 70 * K, 43 * K + 37, poseidon_path_len(d->leaf_hash, d->node_hash, depth)};
+    HK_TRY(col_ranges_check(lo, len, 4, n_v));
     if (batch == 0) return HK_OK;
     if (!is_device_ptr(z_out)) return HK_ERR_ARG;
 
     const size_t n = d->offsets[n_sub], fr = sizeof(Fr);
-    struct In { const void* src; size_t bytes; const void* p; };
-    In in[] = {{d->time_entries_mont, n * 4 * fr, nullptr}, {d->addr_entries_mont, n * 4 * fr, nullptr},
-               {d->consts_mont, d->n_consts * fr, nullptr}, {d->evals_mont, n_sub * 2 * fr, nullptr},
-               {d->leaves_mont, n_sub * 6 * fr, nullptr},   {d->siblings_mont, n_sub * depth * fr, nullptr},
-               {d->root_mont, fr, nullptr},                 {d->template_mont, d->template_mont ? n_v * fr : 0, nullptr}};
-    constexpr int N_IN = 8;
-    size_t staged[N_IN];                                   // bytes of lane scratch per input: none for a device-resident one
-    for (int k = 0; k < N_IN; k++) staged[k] = !in[k].src || is_device_ptr(in[k].src) ? 0 : in[k].bytes;
-    EtChal<Fr> ch;
-    for (size_t k = 0; k < 4; k++) memcpy(&ch.c[k], (const char*)d->challenges_mont + k * fr, fr);
+    constexpr int N_IN = 8;                                // the last one, the template, may be absent
+    Staged in[N_IN] = {staged(d->time_entries_mont, n * 4 * fr), staged(d->addr_entries_mont, n * 4 * fr),
+                       staged(d->consts_mont, d->n_consts * fr), staged(d->evals_mont, n_sub * 2 * fr),
+                       staged(d->leaves_mont, n_sub * 6 * fr),   staged(d->siblings_mont, n_sub * depth * fr),
+                       staged(d->root_mont, fr),                 staged(d->template_mont, n_v * fr)};
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
@@ -356,7 +316,7 @@ hk_status Ops<C>::ram_stage1_witness(hk_ctx* ctx, const hk_ram_stage1_desc* d, c
     Fr* prods;
     const u32 n_chunks = (u32)((K + RW_CHUNK - 1) / RW_CHUNK);
     HK_TRY(L->carve([&](Carve& c) {
-        for (int k = 0; k < N_IN; k++) in[k].p = c.take(staged[k]);
+        stage_carve(c, in, N_IN);
         rows_d = c.n<u32>(2 * batch);
         ts32 = c.n<u32>(batch * (2 * K + 1));
         same = c.n<u32>(batch * K);
@@ -364,8 +324,7 @@ hk_status Ops<C>::ram_stage1_witness(hk_ctx* ctx, const hk_ram_stage1_desc* d, c
         prods = c.n<Fr>(2 * batch * n_chunks);
     }));
     hipStream_t s = L->stream;
-    for (int k = 0; k < N_IN; k++)
-        if (in[k].src) HK_TRY(to_device(L, in[k].src, in[k].bytes, &in[k].p));
+    HK_TRY(stage_upload(L, in, N_IN));
     HK_HIP(hipMemcpyAsync(rows_d, rows.data(), 4 * rows.size(), hipMemcpyHostToDevice, s));
     HK_HIP(hipMemsetAsync(flag, 0, 4, s));
     RwArgs<Fr> a{(const Fr*)in[0].p, (const Fr*)in[1].p, rows_d, ts32, same, (u32)batch, (u32)K, n_v,
@@ -387,11 +346,7 @@ hk_status Ops<C>::ram_stage1_witness(hk_ctx* ctx, const hk_ram_stage1_desc* d, c
     hipLaunchKernelGGL((k_rw_chunk_prod<Fr>), blocks((u64)2 * batch * n_chunks), dim3(256), 0, s, a, ch, n_chunks, prods);
     hipLaunchKernelGGL((k_rw_chunk_scan<Fr>), dim3((2 * nb + 63) / 64), dim3(64), 0, s, a, (const Fr*)in[3].p, n_chunks, prods);
     hipLaunchKernelGGL((k_rw_chain_walk<Fr>), blocks((u64)2 * batch * n_chunks), dim3(256), 0, s, a, ch, n_chunks, (const Fr*)prods);
-    PoseidonDesc pa{lh->t, lh->alpha, lh->full_rounds, lh->partial_rounds, lh->consts_offset};
-    PoseidonDesc pb{nh->t, nh->alpha, nh->full_rounds, nh->partial_rounds, nh->consts_offset};
-    hipLaunchKernelGGL((k_s1_membership<Fr, 6>), dim3((nb + S1_WG_ROWS - 1) / S1_WG_ROWS), dim3(256), 0, s, (const Fr*)in[2].p, pa, pb,
-                       (const Fr*)in[4].p, (const Fr*)in[5].p, (const u32*)rows_d, (u32)depth, nb, n_v, (size_t)d->pos_col0,
-                       (Fr*)z_out);
+    s1_membership<Fr, 6>(s, d, in[2].p, in[4].p, in[5].p, rows_d, batch, n_v, z_out);
     HK_HIP(hipGetLastError());
     return L->settle();
 }

@@ -16,6 +16,7 @@
 #include "curve_ops_impl.cuh"
 #include "ntt.cuh"           // fr_store
 #include "sha256.cuh"
+#include "job_args.h"
 
 namespace hk {
 
@@ -157,9 +158,6 @@ k_sha_tree_inputs(const unsigned char* __restrict__ leaves, const unsigned char*
 
 // n_sub a power of two in [4, 2^20]
 static inline bool st_n_sub_ok(uint32_t n) { return n >= 4 && n <= (1u << 20) && (n & (n - 1)) == 0; }
-static inline bool st_overlap(const void* a, size_t a_len, const void* b, size_t b_len) {
-    return a && b && (const char*)a < (const char*)b + b_len && (const char*)b < (const char*)a + a_len;
-}
 
 template <class C>
 hk_status Ops<C>::sha_tree(hk_ctx* ctx, const void* leaves, uint32_t n_sub, uint32_t ns, uint32_t n_portals,
@@ -169,8 +167,9 @@ hk_status Ops<C>::sha_tree(hk_ctx* ctx, const void* leaves, uint32_t n_sub, uint
     if ((u64)n_sub * n_portals >= ((u64)1 << 28)) return HK_ERR_ARG;                 // lanes of k_sha_tree_trace
     const size_t n = n_sub, nl = n / 2, np = n_portals;
     const size_t leaf_bytes = nl * 64, dig_bytes = n * 32, time_bytes = n * np * 2 * sizeof(Fr);
-    if (st_overlap(o->digests_out, dig_bytes, leaves, leaf_bytes) || st_overlap(o->time_entries_mont_out, time_bytes, leaves, leaf_bytes) ||
-        st_overlap(o->sha_root_mont_out, sizeof(Fr), leaves, leaf_bytes))
+    if (bufs_overlap(o->digests_out, dig_bytes, leaves, leaf_bytes) ||
+        bufs_overlap(o->time_entries_mont_out, time_bytes, leaves, leaf_bytes) ||
+        bufs_overlap(o->sha_root_mont_out, sizeof(Fr), leaves, leaf_bytes))
         return HK_ERR_ARG;
     // the level lanes read a leaf as four 16-B words: device-resident leaves are read in place when they are aligned so
     const bool in_place = is_device_ptr(leaves) && ((uintptr_t)leaves & 15) == 0;
@@ -226,23 +225,22 @@ hk_status Ops<C>::sha_tree_inputs(hk_ctx* ctx, const void* leaves, const void* d
     }
     const void* src = of_leaves ? leaves : digests;                // the one input this kind reads
     const size_t src_bytes = of_leaves ? nl * 64 : n * 32, out_bytes = batch * n_inputs * 4;
-    if (st_overlap(inputs_out, out_bytes, leaves, nl * 64) || st_overlap(inputs_out, out_bytes, digests, n * 32)) return HK_ERR_ARG;
-    const size_t staged = is_device_ptr(src) ? 0 : src_bytes;
+    if (bufs_overlap(inputs_out, out_bytes, leaves, nl * 64) || bufs_overlap(inputs_out, out_bytes, digests, n * 32)) return HK_ERR_ARG;
+    Staged in = staged(src, src_bytes);
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void* sd;
     u32 *sub_d, *out_d;
     HK_TRY(L->carve([&](Carve& c) {
-        sd = c.take(staged);
+        stage_carve(c, &in, 1);
         sub_d = c.n<u32>(batch);
         out_d = c.n<u32>(batch * n_inputs);
     }));
     hipStream_t s = L->stream;
-    HK_TRY(to_device(L, src, src_bytes, &sd));
+    HK_TRY(stage_upload(L, &in, 1));
     HK_HIP(hipMemcpyAsync(sub_d, sub_index, 4 * batch, hipMemcpyHostToDevice, s));
     const u32 total = (u32)(batch * n_inputs);
-    const unsigned char* p = (const unsigned char*)sd;
+    const unsigned char* p = (const unsigned char*)in.p;
     hipLaunchKernelGGL((k_sha_tree_inputs<0>), dim3((total + 255) / 256), dim3(256), 0, s, of_leaves ? p : nullptr, of_leaves ? nullptr : p,
                        (u32)n, n_inputs, (const u32*)sub_d, total, out_d);
     HK_HIP(hipGetLastError());

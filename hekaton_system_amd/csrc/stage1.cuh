@@ -160,78 +160,72 @@ k_s1_membership(const Fr* __restrict__ consts, PoseidonDesc leaf_d, PoseidonDesc
 
 #endif  // __HIPCC__
 
-template <class C>
-hk_status Ops<C>::stage1_witness(hk_ctx* ctx, const hk_stage1_desc* d, const uint32_t* sub_index, size_t batch, size_t n_v,
-                                 void* z_out) {
+// What hk_stage1_witness and hk_ram_stage1_witness check alike of a descriptor D (hk_stage1_desc / hk_ram_stage1_desc: the same
+// leading fields) and hand their kernels: the NULL pointers, the tree's shape, the rows (job_args.h portal_rows), the Poseidon
+// pair, and the n_chal challenges (the rest zero).  Reads sub_index[0 .. batch): the caller bounds its lane counts before.
+template <class Fr, class D>
+hk_status s1_prologue(const D* d, const uint32_t* sub_index, size_t batch, const void* z_out, size_t n_chal, std::vector<u32>& rows,
+                      EtChal<Fr>& ch) {
     if (!d->offsets || !d->time_entries_mont || !d->addr_entries_mont || !d->challenges_mont || !d->evals_mont ||
         !d->leaves_mont || !d->siblings_mont || !d->root_mont || !d->consts_mont || !d->leaf_hash || !d->node_hash ||
         (batch && (!sub_index || !z_out)))
         return HK_ERR_ARG;
+    HK_TRY(tree_shape_check(d->n_sub, d->depth));
+    HK_TRY(portal_rows(d->offsets, d->n_sub, d->n_portals, sub_index, batch, rows));
+    HK_TRY(poseidon_pair_check(d->leaf_hash, d->node_hash, d->n_consts));
+    for (size_t k = 0; k < 4; k++) {
+        ch.c[k] = Fr::zero();
+        if (k < n_chal) memcpy(&ch.c[k], (const char*)d->challenges_mont + k * sizeof(Fr), sizeof(Fr));
+    }
+    return HK_OK;
+}
+
+// the membership block of every row, behind the kernels that fill the row's other columns (same stream)
+template <class Fr, int NF, class D>
+void s1_membership(hipStream_t s, const D* d, const void* consts, const void* leaves, const void* siblings, const u32* rows_d,
+                   size_t batch, size_t n_v, void* z_out) {
+    const u32 nb = (u32)batch;
+    hipLaunchKernelGGL((k_s1_membership<Fr, NF>), dim3((nb + S1_WG_ROWS - 1) / S1_WG_ROWS), dim3(256), 0, s, (const Fr*)consts,
+                       poseidon_desc(d->leaf_hash), poseidon_desc(d->node_hash), (const Fr*)leaves, (const Fr*)siblings, rows_d,
+                       (u32)d->depth, nb, n_v, (size_t)d->pos_col0, (Fr*)z_out);
+}
+
+template <class C>
+hk_status Ops<C>::stage1_witness(hk_ctx* ctx, const hk_stage1_desc* d, const uint32_t* sub_index, size_t batch, size_t n_v,
+                                 void* z_out) {
     const size_t n_sub = d->n_sub, K = d->n_portals, depth = d->depth;
-    if (n_sub < 2 || (n_sub & (n_sub - 1)) || n_sub > ((size_t)1 << 24) || depth > 24 || ((size_t)1 << depth) != n_sub)
-        return HK_ERR_ARG;
     if (K == 0 || K > (1u << 16) || batch >= (1u << 20) || (7 + 5 * K) * batch >= ((size_t)1 << 31)) return HK_ERR_ARG;   // lanes of k_s1_values
-    if (d->offsets[0] != 0) return HK_ERR_ARG;
-    for (size_t i = 0; i < n_sub; i++)
-        if (d->offsets[i + 1] < d->offsets[i]) return HK_ERR_ARG;
-    std::vector<u32> rows(2 * batch);                      // (subcircuit, its first entry) per row; outlives the lane's copies
-    for (size_t b = 0; b < batch; b++) {
-        const u32 i = sub_index[b];
-        if (i >= n_sub || d->offsets[i + 1] - d->offsets[i] != K) return HK_ERR_ARG;
-        rows[2 * b] = i;
-        rows[2 * b + 1] = d->offsets[i];
-    }
-    const hk_poseidon_desc *lh = d->leaf_hash, *nh = d->node_hash;
-    for (const hk_poseidon_desc* p : {lh, nh}) {
-        if ((p->full_rounds & 1) || p->full_rounds + p->partial_rounds == 0 ||
-            (size_t)p->consts_offset + (size_t)(p->full_rounds + p->partial_rounds) * p->t + (size_t)p->t * p->t > d->n_consts)
-            return HK_ERR_ARG;
-    }
-    // compiled for the reference's two instances (poseidon_util.rs:53-62), as hk_poseidon_path and hk_exec_tree are
-    if (lh->t != 4 || nh->t != 3 || lh->alpha != 5 || nh->alpha != 17) return HK_ERR_ARG;
+    std::vector<u32> rows;                                 // (subcircuit, its first entry) per row; outlives the lane's copies
+    EtChal<Fr> ch;
+    HK_TRY(s1_prologue(d, sub_index, batch, z_out, 2, rows, ch));
     // the three column ranges: inside [1, n_v), no two overlapping
     const size_t lo[3] = {d->inst_col0, d->col0, d->pos_col0};
-    const size_t len[3] = {3, 10 * K + 4, 2 * poseidon_trace_len(lh) + depth * (3 + poseidon_trace_len(nh))};   // as hk_poseidon_path
-    for (int a = 0; a < 3; a++) {
-        if (lo[a] < 1 || lo[a] > n_v || len[a] > n_v - lo[a]) return HK_ERR_ARG;
-        for (int b = 0; b < a; b++)
-            if (lo[a] < lo[b] + len[b] && lo[b] < lo[a] + len[a]) return HK_ERR_ARG;
-    }
+    const size_t len[3] = {3, 10 * K + 4, poseidon_path_len(d->leaf_hash, d->node_hash, depth)};      // as hk_poseidon_path
+    HK_TRY(col_ranges_check(lo, len, 3, n_v));
     if (batch == 0) return HK_OK;
     if (!is_device_ptr(z_out)) return HK_ERR_ARG;
 
     const size_t n = d->offsets[n_sub], fr = sizeof(Fr);
-    struct In { const void* src; size_t bytes; const void* p; };
-    In in[] = {{d->time_entries_mont, n * 2 * fr, nullptr}, {d->addr_entries_mont, n * 2 * fr, nullptr},
-               {d->consts_mont, d->n_consts * fr, nullptr}, {d->evals_mont, n_sub * 2 * fr, nullptr},
-               {d->leaves_mont, n_sub * 4 * fr, nullptr},   {d->siblings_mont, n_sub * depth * fr, nullptr},
-               {d->root_mont, fr, nullptr}};
-    size_t staged[7];                                      // bytes of lane scratch per input: none for a device-resident one
-    for (int k = 0; k < 7; k++) staged[k] = is_device_ptr(in[k].src) ? 0 : in[k].bytes;
-    EtChal<Fr> ch;
-    for (size_t k = 0; k < 4; k++) {
-        ch.c[k] = Fr::zero();
-        if (k < 2) memcpy(&ch.c[k], (const char*)d->challenges_mont + k * fr, fr);
-    }
+    Staged in[] = {staged(d->time_entries_mont, n * 2 * fr), staged(d->addr_entries_mont, n * 2 * fr),
+                   staged(d->consts_mont, d->n_consts * fr), staged(d->evals_mont, n_sub * 2 * fr),
+                   staged(d->leaves_mont, n_sub * 4 * fr),   staged(d->siblings_mont, n_sub * depth * fr),
+                   staged(d->root_mont, fr)};
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
     u32* rows_d;
     HK_TRY(L->carve([&](Carve& c) {
-        for (int k = 0; k < 7; k++) in[k].p = c.take(staged[k]);
+        stage_carve(c, in, 7);
         rows_d = c.n<u32>(2 * batch);
     }));
     hipStream_t s = L->stream;
-    for (int k = 0; k < 7; k++) HK_TRY(to_device(L, in[k].src, in[k].bytes, &in[k].p));
+    HK_TRY(stage_upload(L, in, 7));
     HK_HIP(hipMemcpyAsync(rows_d, rows.data(), 4 * rows.size(), hipMemcpyHostToDevice, s));
-    const Fr *tp = (const Fr*)in[0].p, *ap = (const Fr*)in[1].p, *cp = (const Fr*)in[2].p;
+    const Fr *tp = (const Fr*)in[0].p, *ap = (const Fr*)in[1].p;
     const u32 nb = (u32)batch, lanes = (u32)((7 + 5 * K) * batch);
     hipLaunchKernelGGL((k_s1_values<Fr>), dim3((lanes + 255) / 256), dim3(256), 0, s, tp, ap, (const u32*)rows_d, nb, (u32)K, ch,
                        (const Fr*)in[3].p, (const Fr*)in[6].p, n_v, (size_t)d->inst_col0, (size_t)d->col0, (Fr*)z_out);
-    PoseidonDesc a{lh->t, lh->alpha, lh->full_rounds, lh->partial_rounds, lh->consts_offset};
-    PoseidonDesc b{nh->t, nh->alpha, nh->full_rounds, nh->partial_rounds, nh->consts_offset};
-    hipLaunchKernelGGL((k_s1_membership<Fr, 4>), dim3((nb + S1_WG_ROWS - 1) / S1_WG_ROWS), dim3(256), 0, s, cp, a, b,
-                       (const Fr*)in[4].p, (const Fr*)in[5].p, (const u32*)rows_d, (u32)depth, nb, n_v, (size_t)d->pos_col0, (Fr*)z_out);
+    s1_membership<Fr, 4>(s, d, in[2].p, in[4].p, in[5].p, rows_d, batch, n_v, z_out);
     HK_HIP(hipGetLastError());
     return L->settle();
 }

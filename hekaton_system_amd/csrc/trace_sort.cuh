@@ -17,6 +17,7 @@
 #include "curve_ops_impl.cuh"
 #include "ntt.cuh"           // fr_load
 #include "scan.cuh"
+#include "job_args.h"
 
 namespace hk {
 
@@ -236,21 +237,18 @@ hk_status Ops<C>::trace_sort(hk_ctx* ctx, uint32_t entry_fields, const void* tim
     if (n == 0) return HK_OK;
     if (!time_entries || !addr_out) return HK_ERR_ARG;
     const size_t bytes = n * K * sizeof(Fr);
-    const char *in_lo = (const char*)time_entries, *in_hi = in_lo + bytes;
-    auto overlaps = [&](const void* p, size_t len) { return p && (const char*)p < in_hi && in_lo < (const char*)p + len; };
-    if (overlaps(addr_out, bytes) || overlaps(perm_out, 4 * n)) return HK_ERR_ARG;
+    if (bufs_overlap(addr_out, bytes, time_entries, bytes) || bufs_overlap(perm_out, 4 * n, time_entries, bytes)) return HK_ERR_ARG;
 
     const u32 W = K == 2 ? 2 : 3, nn = (u32)n;
     const u32 n_tiles = (nn + TS_TILE - 1) / TS_TILE, n_hist = 256 * n_tiles;
-    const size_t staged_in = is_device_ptr(time_entries) ? 0 : bytes;
+    Staged in = staged(time_entries, bytes);
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void* te;
     u32 *keys[2], *idx[2], *hist, *gbase, *tops, *flags;
     Fr* sorted;
     HK_TRY(L->carve([&](Carve& c) {
-        te = c.take(staged_in);
+        stage_carve(c, &in, 1);
         for (int k = 0; k < 2; k++) keys[k] = c.n<u32>((size_t)W * n);
         for (int k = 0; k < 2; k++) idx[k] = c.n<u32>(n + (k ? n : 0));     // the second one: + the small form's perm
         hist = c.n<u32>(n_hist);
@@ -260,8 +258,8 @@ hk_status Ops<C>::trace_sort(hk_ctx* ctx, uint32_t entry_fields, const void* tim
         sorted = c.n<Fr>(n * K);
     }));
     hipStream_t s = L->stream;
-    HK_TRY(to_device(L, time_entries, bytes, &te));
-    const Fr* tp = (const Fr*)te;
+    HK_TRY(stage_upload(L, &in, 1));
+    const Fr* tp = (const Fr*)in.p;
     u32 fl[TS_FLAG_WORDS] = {0, 0, 0, 0, ~0u, ~0u, ~0u, 0};
     const u32* perm = nullptr;
     if (n_tiles == 1) {
@@ -320,32 +318,24 @@ hk_status Ops<C>::stage0_witness(hk_ctx* ctx, const uint32_t* offsets, uint32_t 
     if (!offsets || !time_entries || !addr_entries || (batch && (!sub_index || !w_out))) return HK_ERR_ARG;
     const size_t K = n_portals;
     if (K == 0 || K > (1u << 16) || batch >= (1u << 20) || batch * K >= ((size_t)1 << 28)) return HK_ERR_ARG;   // lanes of k_s0_rows
-    if (offsets[0] != 0) return HK_ERR_ARG;
-    for (size_t i = 0; i < n_sub; i++)
-        if (offsets[i + 1] < offsets[i]) return HK_ERR_ARG;
-    std::vector<u32> offs(batch);                          // each row's first entry; outlives the lane's copy
-    for (size_t b = 0; b < batch; b++) {
-        const u32 i = sub_index[b];
-        if (i >= n_sub || offsets[i + 1] - offsets[i] != K) return HK_ERR_ARG;
-        offs[b] = offsets[i];
-    }
+    std::vector<u32> rows, offs(batch);                    // each row's first entry; outlives the lane's copy
+    HK_TRY(portal_rows(offsets, n_sub, K, sub_index, batch, rows));
+    for (size_t b = 0; b < batch; b++) offs[b] = rows[2 * b + 1];
     if (batch == 0) return HK_OK;
     if (!is_device_ptr(w_out)) return HK_ERR_ARG;
     const size_t bytes = (size_t)offsets[n_sub] * 2 * sizeof(Fr);
-    const size_t staged[2] = {is_device_ptr(time_entries) ? 0 : bytes, is_device_ptr(addr_entries) ? 0 : bytes};
+    Staged in[2] = {staged(time_entries, bytes), staged(addr_entries, bytes)};
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void *te, *ae;
     u32* offs_d;
     HK_TRY(L->carve([&](Carve& c) {
-        te = c.take(staged[0]);
-        ae = c.take(staged[1]);
+        stage_carve(c, in, 2);
         offs_d = c.n<u32>(batch);
     }));
     hipStream_t s = L->stream;
-    HK_TRY(to_device(L, time_entries, bytes, &te));
-    HK_TRY(to_device(L, addr_entries, bytes, &ae));
+    HK_TRY(stage_upload(L, in, 2));
+    const void *te = in[0].p, *ae = in[1].p;
     HK_HIP(hipMemcpyAsync(offs_d, offs.data(), 4 * batch, hipMemcpyHostToDevice, s));
     const u64 total = (u64)batch * 8 * K;                  // < 2^31
     hipLaunchKernelGGL((k_s0_rows<0>), dim3((u32)((total + 255) / 256)), dim3(256), 0, s, (const uint4*)te, (const uint4*)ae,

@@ -24,7 +24,6 @@
 // are guarded.  No limb array is indexed by a run-time value: no private memory.
 #pragma once
 #include "stage1.cuh"
-#include "sha_tree.cuh"      // st_overlap
 
 namespace hk {
 
@@ -322,15 +321,7 @@ static inline hk_status vkd_check(const hk_vkd_desc* d, size_t* n_sub, size_t* n
     if (d->n_slots == 0 || (u64)d->n_slots >= ((u64)1 << 30)) return HK_ERR_LEN;               // 2 n_slots lanes, below 2^31
     for (size_t s = 0; s < d->n_slots; s++)
         if (d->slot_src[s] != HK_VKD_SRC_ZERO && d->slot_src[s] >= *n_vals) return HK_ERR_ARG;
-    const hk_poseidon_desc *lh = d->leaf_hash, *nh = d->node_hash;
-    for (const hk_poseidon_desc* p : {lh, nh}) {
-        if ((p->full_rounds & 1) || p->full_rounds + p->partial_rounds == 0 ||
-            (size_t)p->consts_offset + (size_t)(p->full_rounds + p->partial_rounds) * p->t + (size_t)p->t * p->t > d->n_consts)
-            return HK_ERR_ARG;
-    }
-    // compiled for the reference's two instances (poseidon_util.rs:53-62), as hk_poseidon_path and hk_exec_tree are
-    if (lh->t != 4 || nh->t != 3 || lh->alpha != 5 || nh->alpha != 17) return HK_ERR_ARG;
-    return HK_OK;
+    return poseidon_pair_check(d->leaf_hash, d->node_hash, d->n_consts);
 }
 
 template <class C>
@@ -339,47 +330,37 @@ hk_status Ops<C>::vkd_trace(hk_ctx* ctx, const hk_vkd_desc* d, void* values_out,
     HK_TRY(vkd_check(d, &n_sub, &V));
     if (!values_out || !time_entries_out) return HK_ERR_ARG;
     const size_t U = d->n_updates, S = d->split, depth = d->depth, fr = sizeof(Fr), n_fr = 2 * (size_t)d->n_slots;
-    const size_t leaf_bytes = U * 2 * VKD_LEAF_BYTES, sib_bytes = U * depth * fr;
-    const void* ins[] = {d->leaves, d->siblings_mont, d->consts_mont};
-    const size_t in_bytes[] = {leaf_bytes, sib_bytes, d->n_consts * fr};
-    for (int k = 0; k < 3; k++)
-        if (st_overlap(values_out, V * fr, ins[k], in_bytes[k]) || st_overlap(time_entries_out, n_fr * fr, ins[k], in_bytes[k]))
+    Staged in[3] = {staged(d->leaves, U * 2 * VKD_LEAF_BYTES), staged(d->siblings_mont, U * depth * fr),
+                    staged(d->consts_mont, d->n_consts * fr)};
+    Staged out[2] = {staged(values_out, V * fr), staged(time_entries_out, n_fr * fr)};
+    for (const Staged& x : in)
+        if (bufs_overlap(values_out, V * fr, x.buf, x.bytes) || bufs_overlap(time_entries_out, n_fr * fr, x.buf, x.bytes))
             return HK_ERR_ARG;
-    if (st_overlap(values_out, V * fr, time_entries_out, n_fr * fr)) return HK_ERR_ARG;
-    const bool val_dev = is_device_ptr(values_out), out_dev = is_device_ptr(time_entries_out);
+    if (bufs_overlap(values_out, V * fr, time_entries_out, n_fr * fr)) return HK_ERR_ARG;
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void *leaves, *sibs, *consts;
     u32 *kinds_d, *addr_d, *src_d, *raw_d;
     unsigned char* zeros_d;
-    Fr *vals_d, *out_d;
     HK_TRY(L->carve([&](Carve& c) {
-        leaves = c.take(is_device_ptr(d->leaves) ? 0 : leaf_bytes);
-        sibs = c.take(is_device_ptr(d->siblings_mont) ? 0 : sib_bytes);
-        consts = c.take(is_device_ptr(d->consts_mont) ? 0 : d->n_consts * fr);
+        stage_carve(c, in, 3);
         kinds_d = c.n<u32>(U);
         addr_d = c.n<u32>(d->n_slots);
         src_d = c.n<u32>(d->n_slots);
         raw_d = c.n<u32>(8 * U);
         zeros_d = (unsigned char*)c.n<u32>(VKD_NAME_BYTES / 4);
-        vals_d = c.n<Fr>(val_dev ? 0 : V);
-        out_d = c.n<Fr>(out_dev ? 0 : n_fr);
+        stage_carve(c, out, 2);
     }));
     hipStream_t s = L->stream;
-    HK_TRY(to_device(L, d->leaves, leaf_bytes, &leaves));
-    HK_TRY(to_device(L, d->siblings_mont, sib_bytes, &sibs));
-    HK_TRY(to_device(L, d->consts_mont, d->n_consts * fr, &consts));
+    const void *leaves = in[0].p, *sibs = in[1].p, *consts = in[2].p;
+    Fr *vals_d = (Fr*)out[0].p, *out_d = (Fr*)out[1].p;
+    HK_TRY(stage_upload(L, in, 3));
     HK_HIP(hipMemcpyAsync(kinds_d, d->kinds, 4 * U, hipMemcpyHostToDevice, s));
     HK_HIP(hipMemcpyAsync(addr_d, d->slot_addr, 4 * (size_t)d->n_slots, hipMemcpyHostToDevice, s));
     HK_HIP(hipMemcpyAsync(src_d, d->slot_src, 4 * (size_t)d->n_slots, hipMemcpyHostToDevice, s));
     HK_HIP(hipMemsetAsync(zeros_d, 0, VKD_NAME_BYTES, s));
-    if (val_dev) vals_d = (Fr*)values_out;
-    if (out_dev) out_d = (Fr*)time_entries_out;
     HK_HIP(hipMemcpyAsync(vals_d, d->roots_mont, 2 * fr, hipMemcpyHostToDevice, s));
-    const hk_poseidon_desc *lh = d->leaf_hash, *nh = d->node_hash;
-    PoseidonDesc a{lh->t, lh->alpha, lh->full_rounds, lh->partial_rounds, lh->consts_offset};
-    PoseidonDesc b{nh->t, nh->alpha, nh->full_rounds, nh->partial_rounds, nh->consts_offset};
+    const PoseidonDesc a = poseidon_desc(d->leaf_hash), b = poseidon_desc(d->node_hash);
     const u32 nu = (u32)U, seg = (u32)(depth / S);
     hipLaunchKernelGGL((k_vkd_hash<Fr>), dim3((1 + 3 * nu + 63) / 64), dim3(256), 0, s, (const Fr*)consts, a,
                        (const unsigned char*)leaves, (const unsigned char*)zeros_d, (const u32*)kinds_d, nu, (u32)S, seg, vals_d, raw_d);
@@ -388,8 +369,7 @@ hk_status Ops<C>::vkd_trace(hk_ctx* ctx, const hk_vkd_desc* d, void* values_out,
     hipLaunchKernelGGL((k_vkd_trace<Fr>), dim3((u32)((n_fr + 255) / 256)), dim3(256), 0, s, (const Fr*)vals_d, (const u32*)addr_d,
                        (const u32*)src_d, (u32)n_fr, out_d);
     HK_HIP(hipGetLastError());
-    if (!val_dev) HK_HIP(hipMemcpyAsync(values_out, vals_d, V * fr, hipMemcpyDeviceToHost, s));
-    if (!out_dev) HK_HIP(hipMemcpyAsync(time_entries_out, out_d, n_fr * fr, hipMemcpyDeviceToHost, s));
+    HK_TRY(stage_download(L, out, 2));
     return L->settle();
 }
 
@@ -443,26 +423,23 @@ hk_status Ops<C>::vkd_witness(hk_ctx* ctx, const hk_vkd_desc* d, const uint32_t*
     }
     if (batch == 0) return HK_OK;
     if (!is_device_ptr(z_out)) return HK_ERR_ARG;
-    const size_t leaf_bytes = U * 2 * VKD_LEAF_BYTES, sib_bytes = U * depth * fr;
-    const void* ins[] = {d->leaves, d->siblings_mont, d->consts_mont, d->values_mont};
-    const size_t in_bytes[] = {leaf_bytes, sib_bytes, d->n_consts * fr, V * fr};
-    for (int k = 0; k < 4; k++)
-        if (st_overlap(z_out, batch * n_v * fr, ins[k], in_bytes[k])) return HK_ERR_ARG;
+    Staged in[4] = {staged(d->leaves, U * 2 * VKD_LEAF_BYTES), staged(d->siblings_mont, U * depth * fr),
+                    staged(d->consts_mont, d->n_consts * fr), staged(d->values_mont, V * fr)};
+    for (const Staged& x : in)
+        if (bufs_overlap(z_out, batch * n_v * fr, x.buf, x.bytes)) return HK_ERR_ARG;
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void* p[4];
     VkdRow* rows_d;
     HK_TRY(L->carve([&](Carve& c) {
-        for (int k = 0; k < 4; k++) p[k] = c.take(is_device_ptr(ins[k]) ? 0 : in_bytes[k]);
+        stage_carve(c, in, 4);
         rows_d = (VkdRow*)c.n<u32>(4 * batch);
     }));
     hipStream_t s = L->stream;
-    for (int k = 0; k < 4; k++) HK_TRY(to_device(L, ins[k], in_bytes[k], &p[k]));
+    const void* const p[4] = {in[0].p, in[1].p, in[2].p, in[3].p};
+    HK_TRY(stage_upload(L, in, 4));
     HK_HIP(hipMemcpyAsync(rows_d, rows.data(), sizeof(VkdRow) * batch, hipMemcpyHostToDevice, s));
-    const hk_poseidon_desc *lh = d->leaf_hash, *nh = d->node_hash;
-    PoseidonDesc a{lh->t, lh->alpha, lh->full_rounds, lh->partial_rounds, lh->consts_offset};
-    PoseidonDesc bd{nh->t, nh->alpha, nh->full_rounds, nh->partial_rounds, nh->consts_offset};
+    const PoseidonDesc a = poseidon_desc(d->leaf_hash), bd = poseidon_desc(d->node_hash);
     const u32 nb = (u32)batch;
     hipLaunchKernelGGL((k_vkd_one<Fr>), dim3((nb + 255) / 256), dim3(256), 0, s, nb, n_v, (Fr*)z_out);
     if (has_hash)

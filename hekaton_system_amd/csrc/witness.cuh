@@ -13,6 +13,7 @@
 // A subcircuit's assignment never exists on the host and crosses PCIe as its inputs (64 .. 216 B) + ~1.3 KB.
 #pragma once
 #include "hk_internal.h"
+#include "job_args.h"
 
 namespace hk {
 
@@ -152,15 +153,7 @@ __global__ void k_scatter_full_batch(const u32* __restrict__ cols, const Fr* __r
 }
 
 // ---- Poseidon membership block (execution tree, subcircuit_circuit.rs:233-252) --------------------------------------
-// The host-side description of one Poseidon instance of the tree (poseidon_util.rs:53-62): width t = rate + 1 (3 or 4),
-// S-box exponent 5 or 17, rf full and rp partial rounds; consts = ark[(rf + rp)][t] then mds[t][t], Montgomery.
-struct PoseidonDesc { u32 t, alpha, rf, rp, off; };
-// witnesses of one traced permutation: per S-box 3 chain values at alpha 5 and 5 at 17, t of them in a full round and one in
-// a partial round, and the t state elements after every round
-inline size_t poseidon_trace_len(const hk_poseidon_desc* d) {
-    size_t chain = d->alpha == 5 ? 3 : 5;
-    return (size_t)d->full_rounds * (d->t * chain + d->t) + (size_t)d->partial_rounds * (chain + d->t);
-}
+// PoseidonDesc, the host-side description of one Poseidon instance of the tree, and poseidon_trace_len: job_args.h.
 
 // Width and S-box exponent are template parameters: the state, the round's S-box outputs and the MDS row sums stay in
 // registers (with runtime widths they were runtime-indexed arrays in private memory and the block took 20 ms per step).

@@ -116,23 +116,21 @@ hk_status Ops<C>::wprog_run(hk_ctx* ctx, const hk_wprog* h, const uint32_t* inpu
     const WprogImpl* w = h->impl;
     if (batch == 0) return HK_OK;
     if (batch >= (1u << 16) || !is_device_ptr(z_out)) return HK_ERR_ARG;
-    if (!is_device_ptr(full_cols))
+    Staged in[3] = {staged(inputs, 4 * batch * w->n_inputs), staged(full_cols, 4 * n_full),
+                    staged(full_vals, sizeof(Fr) * n_full * batch)};
+    if (in[1].scratch)                                      // host columns are checked here; resident ones by the kernel
         for (size_t k = 0; k < n_full; k++) if (full_cols[k] >= w->n_v) return HK_ERR_ARG;
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void *in_d, *cd, *vd;
     u32* values;
     HK_TRY(L->carve([&](Carve& c) {
-        in_d = c.take(4 * batch * w->n_inputs);
-        cd = c.take(4 * n_full);
-        vd = c.take(sizeof(Fr) * n_full * batch);
+        stage_carve(c, in, 3);
         values = c.n<u32>((size_t)w->n_values * batch);
     }));
     hipStream_t s = L->stream;
-    HK_TRY(to_device(L, inputs, 4 * batch * w->n_inputs, &in_d));
-    HK_TRY(to_device(L, full_cols, 4 * n_full, &cd));
-    HK_TRY(to_device(L, full_vals, sizeof(Fr) * n_full * batch, &vd));
+    const void *in_d = in[0].p, *cd = in[1].p, *vd = in[2].p;
+    HK_TRY(stage_upload(L, in, 3));
     hipLaunchKernelGGL((k_word_program<0>), dim3((u32)((batch + 63) / 64)), dim3(64), 0, s, w->ops, w->n_ops, w->refs,
                        (const u32*)in_d, w->n_inputs, (u32)batch, values);
     hipLaunchKernelGGL((k_witness_expand<Fr>), dim3((u32)((w->n_v + 255) / 256), (u32)batch), dim3(256), 0, s, w->map, w->n_v,
@@ -151,15 +149,15 @@ hk_status Ops<C>::assignment_scatter(hk_ctx* ctx, const uint32_t* full_cols, con
                                      size_t n_v, void* z_out) {
     if (batch == 0 || n_full == 0) return HK_OK;
     if (batch >= (1u << 16) || !is_device_ptr(z_out)) return HK_ERR_ARG;
-    if (!is_device_ptr(full_cols))
+    Staged in[2] = {staged(full_cols, 4 * n_full), staged(full_vals, sizeof(Fr) * n_full * batch)};
+    if (in[0].scratch)                                      // as hk_wprog_run
         for (size_t k = 0; k < n_full; k++) if (full_cols[k] >= n_v) return HK_ERR_ARG;
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void *cd, *vd;
-    HK_TRY(L->carve([&](Carve& c) { cd = c.take(4 * n_full); vd = c.take(sizeof(Fr) * n_full * batch); }));
-    HK_TRY(to_device(L, full_cols, 4 * n_full, &cd));
-    HK_TRY(to_device(L, full_vals, sizeof(Fr) * n_full * batch, &vd));
+    HK_TRY(L->carve([&](Carve& c) { stage_carve(c, in, 2); }));
+    const void *cd = in[0].p, *vd = in[1].p;
+    HK_TRY(stage_upload(L, in, 2));
     hipLaunchKernelGGL((k_scatter_full_batch<Fr>), dim3((u32)((n_full + 63) / 64), (u32)batch), dim3(64), 0, L->stream,
                        (const u32*)cd, (const Fr*)vd, (u32)n_full, n_v, (Fr*)z_out);
     HK_HIP(hipGetLastError());
@@ -181,24 +179,17 @@ hk_status Ops<C>::poseidon_path(hk_ctx* ctx, const void* consts, size_t n_consts
     // the kernel is compiled for the reference's two instances (poseidon_util.rs:53-62): rate 3 / x^5 over the 4 leaf
     // fields, rate 2 / x^17 for two-to-one; round counts and constants stay run-time data
     if (lh->t != 4 || nh->t != 3 || lh->alpha != 5 || nh->alpha != 17) return HK_ERR_ARG;
-    size_t block = 2 * poseidon_trace_len(lh) + depth * (3 + poseidon_trace_len(nh));
+    size_t block = poseidon_path_len(lh, nh, depth);
     if (col0 > n_v || block > n_v - col0) return HK_ERR_ARG;
+    Staged in[4] = {staged(consts, n_consts * sizeof(Fr)), staged(leaf, batch * 4 * sizeof(Fr)),
+                    staged(siblings, batch * depth * sizeof(Fr)), staged(index, 4 * batch)};
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void *cd, *ld, *sd, *id;
-    HK_TRY(L->carve([&](Carve& c) {
-        cd = c.take(n_consts * sizeof(Fr));
-        ld = c.take(batch * 4 * sizeof(Fr));
-        sd = c.take(batch * depth * sizeof(Fr));
-        id = c.take(4 * batch);
-    }));
-    HK_TRY(to_device(L, consts, n_consts * sizeof(Fr), &cd));
-    HK_TRY(to_device(L, leaf, batch * 4 * sizeof(Fr), &ld));
-    HK_TRY(to_device(L, siblings, batch * depth * sizeof(Fr), &sd));
-    HK_TRY(to_device(L, index, 4 * batch, &id));
-    PoseidonDesc a{lh->t, lh->alpha, lh->full_rounds, lh->partial_rounds, lh->consts_offset};
-    PoseidonDesc b{nh->t, nh->alpha, nh->full_rounds, nh->partial_rounds, nh->consts_offset};
+    HK_TRY(L->carve([&](Carve& c) { stage_carve(c, in, 4); }));
+    const void *cd = in[0].p, *ld = in[1].p, *sd = in[2].p, *id = in[3].p;
+    HK_TRY(stage_upload(L, in, 4));
+    const PoseidonDesc a = poseidon_desc(lh), b = poseidon_desc(nh);
     hipLaunchKernelGGL((k_poseidon_path<Fr>), dim3((u32)((batch + 63) / 64)), dim3(64), 0, L->stream, (const Fr*)cd, a, b,
                        (const Fr*)ld, (const Fr*)sd, (const u32*)id, (u32)depth, (u32)batch, n_v, col0, (Fr*)z_out);
     HK_HIP(hipGetLastError());
