@@ -4,6 +4,7 @@
 #pragma once
 #include "curve_ops_impl.cuh"
 #include "ntt.cuh"
+#include "ntt_plan.h"
 #include "csr.cuh"
 
 namespace hk {
@@ -137,34 +138,21 @@ struct NttHost {
                             const Post& ep = Post()) {
         if (logn == 0) return HK_OK;
         // bottom pass: the low min(logn, 11) stages on contiguous tiles; the rest in passes of at most
-        // `upper_max` stages whose tiles are 2^nst rows of 2^(11 - nst) contiguous elements
-        static const u32 upper_max = [] {
-            const char* e = getenv("HK_NTT_UPPER_MAX");
-            u32 v = e ? (u32)atoi(e) : 6u;      // 2^21: 11+5+5, 2^22: 11+6+5 (a single 10-stage upper pass with
-                                                // 64-B rows measured the same alone and less steady under load)
-            return v < 1 ? 1u : (v > 10 ? 10u : v);
-        }();
+        // `upper_max` stages whose tiles are 2^nst rows of 2^(11 - nst) contiguous elements (ntt_plan.h)
         static const u32 tile_log = [] {
             const char* e = getenv("HK_NTT_TILE_LOG");
-            u32 v = e ? (u32)atoi(e) : (u32)NTT_TILE_LOG;
-            return v < 8 ? 8u : (v > (u32)NTT_TILE_LOG ? (u32)NTT_TILE_LOG : v);
+            return ntt_plan_tile_log(e ? (u32)atoi(e) : NTT_PLAN_TILE_LOG);
+        }();
+        static const u32 upper_max = [] {
+            const char* e = getenv("HK_NTT_UPPER_MAX");
+            return ntt_plan_upper_max(e ? (u32)atoi(e) : NTT_PLAN_UPPER_MAX, tile_log);
         }();
         const u32 threads = 1u << (tile_log - 2);                    // one radix-4 quad per thread
-        u32 bottom = logn < tile_log ? logn : tile_log;
-        u32 rest = logn - bottom;
-        u32 npass = (rest + upper_max - 1) / upper_max;
-        struct P { u32 lo, nst, cols_bits; } ps[34];
-        int np = 0;
-        ps[np++] = {0, bottom, 0};
-        u32 lo = bottom;
-        for (u32 i = 0; i < npass; i++) {
-            u32 nst = (rest - (lo - bottom) + (npass - i) - 1) / (npass - i);
-            ps[np++] = {lo, nst, tile_log - nst};
-            lo += nst;
-        }
+        NttPass ps[NTT_PLAN_MAX_PASSES];
+        int np = ntt_pass_plan(logn, tile_log, upper_max, ps);
         Fr one = Fr::one();
         for (int k = 0; k < np; k++) {
-            const P& p = dit ? ps[k] : ps[np - 1 - k];
+            const NttPass& p = dit ? ps[k] : ps[np - 1 - k];
             u32 tile_log = p.nst + p.cols_bits;
             dim3 grid(1u << (logn - tile_log), batch);
             size_t lds = sizeof(Fr) << tile_log;

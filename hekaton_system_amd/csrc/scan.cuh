@@ -67,8 +67,10 @@ __global__ void __launch_bounds__(256) k_scan_u32_add(u32* __restrict__ out, con
     if (k < n) out[k] += tops[k / SCAN_U32_TILE];
 }
 
-// out[i] = in[0] + ... + in[i - 1], i < n, on stream s.  tops: scan_u32_tops_len(n) u32 of scratch.
+// out[i] = in[0] + ... + in[i - 1], i < n, on stream s.  tops: scan_u32_tops_len(n) u32 of scratch.  n == 0: nothing to
+// write and nothing launched (a grid of zero blocks is a launch error).
 static hk_status scan_u32(hipStream_t s, const u32* in, u32* out, u32* tops, u32 n) {
+    if (n == 0) return HK_OK;
     u32 nt = (n + SCAN_U32_TILE - 1) / SCAN_U32_TILE;
     hipLaunchKernelGGL((k_scan_u32_tile<0>), dim3(nt), dim3(256), 0, s, in, out, tops, n);
     hipLaunchKernelGGL((k_scan_u32_tops<0>), dim3(1), dim3(256), 0, s, tops, nt);

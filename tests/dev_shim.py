@@ -1,7 +1,8 @@
 """Loaders and integer packing for the test-only device shims: tests/device_shim/field_dev_shim.hip (plain helper of
 tests/test_field_device_gpu.py and tests/test_wave_f12_gpu.py), tests/device_shim/ec_dev_shim.hip (of
-tests/test_ec_device_gpu.py and tests/test_msm_plan_device_gpu.py) and tests/device_shim/pair_dev_shim.hip (of
-tests/test_pair_device_gpu.py).  The shims run in the calling process."""
+tests/test_ec_device_gpu.py and tests/test_msm_plan_device_gpu.py), tests/device_shim/pair_dev_shim.hip (of
+tests/test_pair_device_gpu.py) and tests/device_shim/ntt_dev_shim.hip (of tests/test_ntt_device_gpu.py and
+tests/test_scan_gpu.py).  The shims run in the calling process."""
 import ctypes
 import os
 
@@ -32,9 +33,15 @@ PAIR_VARIANTS = {"asm": "libpair_dev_shim.so"}
 Q_MUL, Q_SQR, Q_MUL_BY_CHAR, Q_PSI = range(4)
 FORM_LANE, FORM_QUAD = 0, 1
 
+# ntt_dev_shim.hip
+NTT_VARIANTS = {"asm": "libntt_dev_shim.so", "noasm": "libntt_dev_shim_noasm.so"}
+NTT_REFUSED = 1000           # DSHIM_NTT_REFUSED: arguments outside a kernel's contract, nothing launched
+FR_BYTES = 32
+
 _loaded = {}
 _loaded_ec = {}
 _loaded_pair = {}
+_loaded_ntt = {}
 
 
 def pack(elems, nbytes):
@@ -241,3 +248,112 @@ def load_pair(variant):
     if variant not in _loaded_pair:
         _loaded_pair[variant] = PairShim(variant)
     return _loaded_pair[variant]
+
+
+class NttShim:
+    """One launch per call of the Fr transform layer.  Fr vectors travel as bytes: canonical Montgomery values, 32 bytes
+    each, little-endian - what the kernels read and write.  `curve` is 0 (BN254 Fr) or 1 (BLS12-381 Fr).  The *_status forms
+    give (status, bytes or None): 0, NTT_REFUSED, or minus a hipError_t."""
+
+    def __init__(self, variant):
+        path = os.path.join(ROOT, "hekaton_system_amd", "lib", NTT_VARIANTS[variant])
+        assert os.path.exists(path), "build the device shim first (python __graft_entry__.py)"
+        self.variant = variant
+        self.lib = ctypes.CDLL(path)
+        vp, ui, sz, ci = ctypes.c_char_p, ctypes.c_uint, ctypes.c_size_t, ctypes.c_int
+        self.lib.dshim_ntt_tables.argtypes = [ci, ui, vp, vp]
+        self.lib.dshim_pow_table.argtypes = [ci, vp, ui, ui, vp]
+        self.lib.dshim_pow_from_tables.argtypes = [ci, vp, ctypes.POINTER(ui), ui, ui, vp]
+        self.lib.dshim_ntt_pass.argtypes = [ci, ci, vp, sz, ui, vp, ui, ui, ui, ui, ui, ci, ui, vp, vp, vp, vp]
+        self.lib.dshim_scale_pow.argtypes = [ci, vp, sz, ui, vp, vp, ui, ci, ci]
+        self.lib.dshim_bitrev.argtypes = [ci, vp, ui]
+        self.lib.dshim_mul_pointwise.argtypes = [ci, vp, vp, sz]
+        self.lib.dshim_spmv.argtypes = [ci, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ui), vp, sz, vp, sz, vp, ui, ui, ui]
+        self.lib.dshim_scan_u32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ui]
+        self.lib.dshim_ntt_scan_pad.restype = ui
+        self.scan_pad = self.lib.dshim_ntt_scan_pad()
+        assert self.lib.dshim_ntt_uses_asm() == (1 if variant == "asm" else 0)
+
+    def ntt_tables(self, curve, log_table, sq):
+        """sq: bytes of log_table entries w^(2^k) -> bytes of the 2^log_table - 1 stage-table entries"""
+        assert len(sq) == log_table * FR_BYTES
+        out = ctypes.create_string_buffer(((1 << log_table) - 1) * FR_BYTES)
+        st = self.lib.dshim_ntt_tables(curve, log_table, bytes(sq), out)
+        assert st == 0, "dshim_ntt_tables(curve %d, log_table %d): status %d" % (curve, log_table, st)
+        return out.raw
+
+    def pow_table(self, curve, sq, count, nbits):
+        assert len(sq) == nbits * FR_BYTES
+        out = ctypes.create_string_buffer(count * FR_BYTES)
+        st = self.lib.dshim_pow_table(curve, bytes(sq), count, nbits, out)
+        assert st == 0, "dshim_pow_table(curve %d, count %d, nbits %d): status %d" % (curve, count, nbits, st)
+        return out.raw
+
+    def pow_from_tables(self, curve, pw, js, logn):
+        assert len(pw) == 3 * 2048 * FR_BYTES
+        out = ctypes.create_string_buffer(len(js) * FR_BYTES)
+        st = self.lib.dshim_pow_from_tables(curve, bytes(pw), (ctypes.c_uint * len(js))(*js), len(js), logn, out)
+        assert st == 0, "dshim_pow_from_tables(curve %d, logn %d): status %d" % (curve, logn, st)
+        return out.raw
+
+    def ntt_pass_status(self, curve, dit, data, stride, batch, tws, logn, lo, nst, cols_bits, threads, post=0, npost=0xffffffff,
+                        scale=None, pw=None, sub=None, kc=None):
+        """data: bytes of batch x stride elements (vector v at v * stride) -> the same after one k_ntt_pass4 launch.
+        tws: the 2^logn - 1 stage-table entries; scale, kc: one element; pw: 3 x 2048; sub: 2^logn"""
+        assert len(data) == batch * stride * FR_BYTES and len(tws) == ((1 << logn) - 1) * FR_BYTES
+        assert sub is None or len(sub) == FR_BYTES << logn
+        buf = ctypes.create_string_buffer(bytes(data), len(data))
+        st = self.lib.dshim_ntt_pass(curve, dit, buf, stride, batch, bytes(tws), logn, lo, nst, cols_bits, threads, post, npost,
+                                     scale, pw, sub, kc)
+        return st, (buf.raw if st == 0 else None)
+
+    def ntt_pass(self, curve, dit, data, stride, batch, tws, logn, lo, nst, cols_bits, threads, **ep):
+        st, out = self.ntt_pass_status(curve, dit, data, stride, batch, tws, logn, lo, nst, cols_bits, threads, **ep)
+        assert st == 0, "dshim_ntt_pass(curve %d, dit %d, logn %d, lo %d, nst %d, cols_bits %d, threads %d): status %d" % (
+            curve, dit, logn, lo, nst, cols_bits, threads, st)
+        return out
+
+    def scale_pow(self, curve, data, stride, batch, pw, scale, logn, bitrev_index, use_pow):
+        assert len(data) == batch * stride * FR_BYTES
+        buf = ctypes.create_string_buffer(bytes(data), len(data))
+        st = self.lib.dshim_scale_pow(curve, buf, stride, batch, pw, scale, logn, bitrev_index, use_pow)
+        assert st == 0, "dshim_scale_pow(curve %d, logn %d): status %d" % (curve, logn, st)
+        return buf.raw
+
+    def bitrev(self, curve, data, logn):
+        assert len(data) == FR_BYTES << logn
+        buf = ctypes.create_string_buffer(bytes(data), len(data))
+        st = self.lib.dshim_bitrev(curve, buf, logn)
+        assert st == 0, "dshim_bitrev(curve %d, logn %d): status %d" % (curve, logn, st)
+        return buf.raw
+
+    def mul_pointwise(self, curve, a, b):
+        assert len(a) == len(b)
+        buf = ctypes.create_string_buffer(bytes(a), len(a))
+        st = self.lib.dshim_mul_pointwise(curve, buf, bytes(b), len(a) // FR_BYTES)
+        assert st == 0, "dshim_mul_pointwise(curve %d, m %d): status %d" % (curve, len(a) // FR_BYTES, st)
+        return buf.raw
+
+    def spmv(self, curve, row_ptr, col, val, z, out, n_copy):
+        """row_ptr, col: lists; val, z: bytes; out: bytes of the m elements as they lie before the launch -> after it"""
+        n_rows, nnz, m = len(row_ptr) - 1, len(col), len(out) // FR_BYTES
+        assert len(val) == nnz * FR_BYTES
+        buf = ctypes.create_string_buffer(bytes(out), len(out))
+        st = self.lib.dshim_spmv(curve, (ctypes.c_ulonglong * (n_rows + 1))(*row_ptr), (ctypes.c_uint * max(nnz, 1))(*col),
+                                 bytes(val), nnz, bytes(z), len(z) // FR_BYTES, buf, n_rows, n_copy, m)
+        assert st == 0, "dshim_spmv(curve %d, n_rows %d, n_copy %d, m %d): status %d" % (curve, n_rows, n_copy, m, st)
+        return buf.raw
+
+    def scan_u32(self, counts, out):
+        """counts: numpy uint32 of n; out: numpy uint32 of n + scan_pad, as it lies before the call (changed in place)"""
+        n = len(counts)
+        assert counts.dtype.name == "uint32" and out.dtype.name == "uint32" and len(out) == n + self.scan_pad
+        assert counts.flags["C_CONTIGUOUS"] and out.flags["C_CONTIGUOUS"]
+        st = self.lib.dshim_scan_u32(counts.ctypes.data if n else None, out.ctypes.data, n)
+        assert st == 0, "dshim_scan_u32(n %d): status %d" % (n, st)
+
+
+def load_ntt(variant):
+    if variant not in _loaded_ntt:
+        _loaded_ntt[variant] = NttShim(variant)
+    return _loaded_ntt[variant]

@@ -42,21 +42,46 @@ def test_ntt_domain_too_large(ctx_bn254):
     assert e.value.status == capi.HK_ERR_DOMAIN_TOO_LARGE
 
 
-@pytest.mark.parametrize("n_c,n_inst", [(3, 2), (24, 3), (200, 4), (1021, 4)])
-def test_witness_map_vs_oracle(n_c, n_inst, ctx_bn254):
-    cp = BN254
+# (1020, 4): n_c + n_inst = 2^10 exactly; (1024, 2): n_c a power of two, the domain doubles for the instance rows alone;
+# (4093, 3): log_m = 12, the first two-pass DIT (nst = 1); (8000, 4): log_m = 13 (nst = 2).  The big-int oracle takes about a
+# second at 2^13, so it stays the reference for every case.
+WITNESS_MAP_CASES = [(3, 2), (24, 3), (200, 4), (1021, 4), (1020, 4), (1024, 2), (4093, 3), (8000, 4)]
+CTX_FIXTURE = {"bn254": "ctx_bn254", "bls12_381": "ctx_bls"}
+
+
+def _witness_map_case(request, cname, n_c, n_inst, spoil):
+    cp = CURVES[cname]
+    ctx = request.getfixturevalue(CTX_FIXTURE[cname])
     cd = Codec(cp)
     rnd = random.Random(n_c)
     cs = synthetic_r1cs(cp, rnd, n_inst, 10, n_c)
     assert cs.is_satisfied()
     A, B, C = cs.matrices()
     z = cs.full_assignment()
+    if spoil:
+        z[len(z) // 2] = (z[len(z) // 2] + 1) % cp.r
     want = groth16.witness_map_from_matrices(cp, A, B, C, cs.num_instance, n_c, z)
-    assert want[-1] == 0
-    got, m = ctx_bn254.witness_map(csr_from_rows(cd, A), csr_from_rows(cd, B), csr_from_rows(cd, C),
-                                   cs.num_instance, n_c, cd.fr_vec_mont(z))
+    assert (want[-1] != 0) == spoil
+    got, m = ctx.witness_map(csr_from_rows(cd, A), csr_from_rows(cd, B), csr_from_rows(cd, C),
+                             cs.num_instance, n_c, cd.fr_vec_mont(z))
     assert m == len(want)
     assert cd.fr_vec_from_mont(got) == want
+
+
+# the BN254 cases keep the ids they had before the test took a curve
+@pytest.mark.parametrize("cname,n_c,n_inst",
+                         [pytest.param("bn254", n_c, n_inst, id="%d-%d" % (n_c, n_inst)) for n_c, n_inst in WITNESS_MAP_CASES] +
+                         [pytest.param("bls12_381", n_c, n_inst, id="bls12_381-%d-%d" % (n_c, n_inst))
+                          for n_c, n_inst in WITNESS_MAP_CASES])
+def test_witness_map_vs_oracle(cname, n_c, n_inst, request):
+    _witness_map_case(request, cname, n_c, n_inst, False)
+
+
+@pytest.mark.parametrize("cname", ["bn254", "bls12_381"])
+def test_witness_map_of_an_unsatisfying_assignment(cname, request):
+    """One entry of z changed: a o b - c no longer vanishes on the domain, the top coefficient of h is non-zero, and h is still
+    what the reference computes - the witness map is a map, not a check."""
+    _witness_map_case(request, cname, 200, 4, True)
 
 
 def _setup(cp, cs, rnd):
