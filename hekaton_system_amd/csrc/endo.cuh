@@ -303,6 +303,17 @@ HK_HD void split_bias(u32 (&m)[6]) {
 }
 HK_HD int split_digit(const u32 (&m)[6], int d) { return (int)((m[d >> 3] >> (4 * (d & 7))) & 15u) - 8; }
 template <class F> struct SplitDigits { static constexpr int ND = (EndoOf<F>::STEPS + 3) / 4 + 1; };
+// whether the K-lane form reads the canonical magnitude m (8 limbs) whole: m + 0x88..8 must stay inside ND nibbles, i.e.
+// m <= 0x77..7 (ND nibbles: 135 bits in G1, 71 in G2).  A longer magnitude needs the one-lane kernel, which scans all 256 bits.
+template <int ND>
+HK_HD bool split_mag_fits(const u32* m) {
+    for (int l = 7; l >= 0; l--) {
+        int nib = ND - 8 * l;
+        u32 lim = nib >= 8 ? 0x77777777u : nib <= 0 ? 0u : (0x77777777u & ((1u << (4 * nib)) - 1u));
+        if (m[l] != lim) return m[l] < lim;
+    }
+    return true;
+}
 
 #if defined(__HIPCC__)
 // ---- Fq2 on FOUR lanes -------------------------------------------------------------------------------------------------

@@ -314,11 +314,23 @@ hk_status Ops<C>::points_fold(hk_ctx* ctx, size_t k, const void* const* lo, cons
     }
     HK_HIP(hipMemcpyAsync(cd, coeffs, K * sizeof(Fr), is_device_ptr(coeffs) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                           L->stream));
-    if (!is_device_ptr(coeffs)) HK_HIP(hipStreamSynchronize(L->stream));      // a pageable caller buffer: done with it now
+    // the K-lane form of short vectors reads a magnitude up to 0x77..7 over ND nibbles (endo.cuh); a host caller's longer
+    // one goes to the one-lane kernel, which is right for any magnitude.  Device-resident magnitudes are not inspected: the
+    // bound is the caller's (include/hekaton.h)
+    bool long_mags = false;
+    if (!is_device_ptr(coeffs)) {
+        HK_HIP(hipStreamSynchronize(L->stream));                              // a pageable caller buffer: done with it now
+        for (int j = 0; j < K; j++) {
+            Fr m;
+            memcpy(&m, (const char*)coeffs + j * sizeof(Fr), sizeof(Fr));
+            m = Fr::from_mont(m);
+            if (!split_mag_fits<SplitDigits<F>::ND>(m.v)) long_mags = true;
+        }
+    }
     // one vector into a device buffer is normalised in place; otherwise into one array that is then handed out
     bool direct = k == 1 && is_device_ptr(out[0]);
     Affine<F>* od = direct ? (Affine<F>*)out[0] : out_s;
-    HK_TRY(MsmRun<F>::fold_endo(L->stream, (u32)k, lod, hid, cd, neg_mask, (u32)n, tab, xy, pref, od));
+    HK_TRY(MsmRun<F>::fold_endo(L->stream, (u32)k, lod, hid, cd, neg_mask, (u32)n, tab, xy, pref, od, long_mags));
     if (!direct) {
         GatherRows gr;
         bool ok = n * sizeof(Affine<F>) < ((size_t)1 << 32);

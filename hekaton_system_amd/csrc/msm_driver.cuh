@@ -67,9 +67,11 @@ struct MsmRun {
     static hk_status lincomb(hipStream_t s, const Affine<F>* const* vecs, const void* coeffs_mont, u32 k, u32 n,
                              XYZZ<F>* xy, F* pref, Affine<F>* out);
     // out[i] = lo[i] + c * hi[i], c given as EndoOf<F>::K magnitudes (Montgomery Fr) and a sign mask (endo.cuh
-    // k_points_fold_endo / k_points_mul_split); tab: endo_tab_bytes(n) of scratch
+    // k_points_fold_endo / k_points_mul_split); tab: endo_tab_bytes(n) of scratch.  The K-lane form of short vectors reads a
+    // magnitude up to 0x77..7 over SplitDigits<F>::ND nibbles only (split_mag_fits): long_mags sends the call to the
+    // one-lane kernel whatever n
     static hk_status fold_endo(hipStream_t s, u32 k, const Affine<F>* const* lo, const Affine<F>* const* hi, const void* coeffs_mont,
-                               u32 neg_mask, u32 n, XYZZ<F>* tab, XYZZ<F>* xy, F* pref, Affine<F>* out);
+                               u32 neg_mask, u32 n, XYZZ<F>* tab, XYZZ<F>* xy, F* pref, Affine<F>* out, bool long_mags = false);
     // a short one-off MSM without tables (n K <= SPLIT_MAX_LANES): element-wise products + one workgroup's sum; result: 1 XYZZ
     static hk_status small_msm(hipStream_t s, const Affine<F>* bases, const void* scalars, int mont, u32 n, XYZZ<F>* tab,
                                XYZZ<F>* xy, XYZZ<F>* result);

@@ -260,11 +260,11 @@ hk_status MsmRun<F>::small_msm_rows(hipStream_t s, const Affine<F>* bases, const
 
 template <class F>
 hk_status MsmRun<F>::fold_endo(hipStream_t s, u32 k, const Affine<F>* const* lo, const Affine<F>* const* hi, const void* coeffs_mont,
-                               u32 neg_mask, u32 n, XYZZ<F>* tab, XYZZ<F>* xy, F* pref, Affine<F>* out) {
+                               u32 neg_mask, u32 n, XYZZ<F>* tab, XYZZ<F>* xy, F* pref, Affine<F>* out, bool long_mags) {
     typedef typename ScalarOf<F>::type Fr;
     if (n == 0 || k == 0) return HK_OK;
     if (k > (u32)FOLD_MAX) return HK_ERR_ARG;
-    const bool one_lane = getenv("HK_ENDO_ONE_LANE") != nullptr;
+    const bool one_lane = long_mags || getenv("HK_ENDO_ONE_LANE") != nullptr;
     if (!one_lane && (size_t)n * EndoOf<F>::K <= SPLIT_MAX_LANES) {
         static const auto E = EndoOf<F>::split();                                // unused by the uniform form
         SplitVecs<F> v = {};

@@ -225,7 +225,11 @@ hk_status hk_points_lincomb_g2(hk_ctx* ctx, const void* const* vecs, const void*
  * `lo + c * hi` of a TIPA / GIPA round (ark-ip-proofs `gipa`, called from distributed-prover/src/aggregation.rs:340) with the
  * challenge split by the caller into four ~64-bit parts along psi, the untwist-Frobenius-twist endomorphism of G2
  * (psi(Q) = [q mod r] Q: c = sum s_j coeffs4[j] lambda^j mod r with lambda = 6 x^2 on BN254, x on BLS12-381) - the shared
- * doubling chain is ~66 steps instead of 254.  lo, hi [h|d]: n G2 points; coeffs4_mont [h|d]: 4 Fr; out [h|d]: n G2. */
+ * doubling chain is ~66 steps instead of 254.  lo, hi [h|d]: n G2 points; coeffs4_mont [h|d]: 4 Fr; out [h|d]: n G2.
+ * Magnitudes: host-resident coeffs may be any values below r - parts longer than the short-vector kernel reads (above
+ * 0x77..7 over 18 hex digits, 71 bits; G1: over 34 hex digits, 135 bits) take a slower kernel that is right for every
+ * magnitude.  Device-resident coeffs are not inspected and MUST stay within that bound (a nearest-plane split does: its
+ * parts are below 2^66 in G2 and 2^130 in G1); beyond it the result of a call with 4 n <= 65536 (G1: 2 n) is undefined. */
 hk_status hk_points_fold_g2(hk_ctx* ctx, const void* lo, const void* hi, const void* coeffs4_mont, unsigned neg_mask, size_t n,
                             void* out);
 /* Host utility (no device work): Keccak-f[1600] on 25 little-endian 64-bit lanes - the permutation under the merlin
@@ -234,13 +238,15 @@ void hk_keccak_f1600(uint64_t* state25);
 
 /* The same for G1 along the GLV endomorphism phi(x, y) = (beta x, y) (phi(P) = [lambda] P, lambda^2 + lambda + 1 = 0 mod r):
  * out[i] = lo[i] + s_0 coeffs2[0] hi[i] + s_1 coeffs2[1] phi(hi[i]), c = s_0 coeffs2[0] + s_1 coeffs2[1] lambda mod r with two
- * ~128-bit parts - the folds `A' = A_L + c A_R`, `w' = w_L + c w_R` of a round.  128 doubling steps instead of 254. */
+ * ~128-bit parts - the folds `A' = A_L + c A_R`, `w' = w_L + c w_R` of a round.  128 doubling steps instead of 254.
+ * The magnitude rule of hk_points_fold_g2 applies (here: 0x77..7 over 34 hex digits). */
 hk_status hk_points_fold_g1(hk_ctx* ctx, const void* lo, const void* hi, const void* coeffs2_mont, unsigned neg_mask, size_t n,
                             void* out);
 /* k <= 4 folds that share ONE scalar, as the folds of one GIPA round do (`A' = A_L + c A_R`, `w1' = ..`, `w2' = ..` with c;
  * `B'`, `v1'`, `v2'` with c^-1: ark-ip-proofs `gipa`, reached from distributed-prover/src/aggregation.rs:340 - there one rayon
  * sweep per vector): out[y][i] = lo[y][i] + c * hi[y][i], one launch and one normalisation for all k vectors.
- * lo, hi, out [h]: k pointers, each [h|d] to n packed affine points; coeffs / neg_mask as in hk_points_fold_g1 / _g2. */
+ * lo, hi, out [h]: k pointers, each [h|d] to n packed affine points; coeffs / neg_mask (and the magnitude rule) as in
+ * hk_points_fold_g1 / _g2. */
 hk_status hk_points_fold_many_g1(hk_ctx* ctx, size_t k, const void* const* lo, const void* const* hi, const void* coeffs2_mont,
                                  unsigned neg_mask, size_t n, void* const* out);
 hk_status hk_points_fold_many_g2(hk_ctx* ctx, size_t k, const void* const* lo, const void* const* hi, const void* coeffs4_mont,

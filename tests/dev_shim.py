@@ -1,8 +1,9 @@
 """Loaders and integer packing for the test-only device shims: tests/device_shim/field_dev_shim.hip (plain helper of
 tests/test_field_device_gpu.py and tests/test_wave_f12_gpu.py), tests/device_shim/ec_dev_shim.hip (of
 tests/test_ec_device_gpu.py and tests/test_msm_plan_device_gpu.py), tests/device_shim/pair_dev_shim.hip (of
-tests/test_pair_device_gpu.py) and tests/device_shim/ntt_dev_shim.hip (of tests/test_ntt_device_gpu.py and
-tests/test_scan_gpu.py).  The shims run in the calling process."""
+tests/test_pair_device_gpu.py), tests/device_shim/ntt_dev_shim.hip (of tests/test_ntt_device_gpu.py and
+tests/test_scan_gpu.py) and tests/device_shim/sweep_dev_shim.hip (of tests/test_sweep_device_gpu.py).  The shims run in the
+calling process."""
 import ctypes
 import os
 
@@ -38,7 +39,13 @@ NTT_VARIANTS = {"asm": "libntt_dev_shim.so", "noasm": "libntt_dev_shim_noasm.so"
 NTT_REFUSED = 1000           # DSHIM_NTT_REFUSED: arguments outside a kernel's contract, nothing launched
 FR_BYTES = 32
 
+# sweep_dev_shim.hip: built as shipped only (see the header of tests/device_shim/Makefile)
+SWEEP_LIB = "libsweep_dev_shim.so"
+SPLIT_K_LANE, SPLIT_QUAD = 0, 1
+MUL_PLAIN, MUL_ENDO = 0, 1
+
 _loaded = {}
+_loaded_sweep = []
 _loaded_ec = {}
 _loaded_pair = {}
 _loaded_ntt = {}
@@ -357,3 +364,106 @@ def load_ntt(variant):
     if variant not in _loaded_ntt:
         _loaded_ntt[variant] = NttShim(variant)
     return _loaded_ntt[variant]
+
+
+class SweepShim:
+    """One launch per call of the group sweeps (fixed_base.cuh, endo.cuh).  Everything travels as the bytes the kernels read
+    and write: affine points and Fr scalars in memory form (pb bytes per affine point, 32 per scalar), XYZZ results as stored
+    (2 pb bytes: x, y, zz, zzz).  `gid`: 0 bn254 G1, 1 bn254 G2, 2 bls G1, 3 bls G2.  The *_status forms give (status, bytes
+    or None): 0 or minus a hipError_t."""
+
+    def __init__(self):
+        path = os.path.join(ROOT, "hekaton_system_amd", "lib", SWEEP_LIB)
+        assert os.path.exists(path), "build the device shim first (python __graft_entry__.py)"
+        self.lib = ctypes.CDLL(path)
+        vp, ui, ci = ctypes.c_char_p, ctypes.c_uint, ctypes.c_int
+        self.lib.dshim_fb_table.argtypes = [ci, vp, vp]
+        self.lib.dshim_fb_mul.argtypes = [ci, vp, vp, ci, ui, vp]
+        self.lib.dshim_points_lincomb.argtypes = [ci, vp, vp, ui, ui, vp]
+        self.lib.dshim_scalar_mul.argtypes = [ci, ci, vp, vp, ui, vp]
+        self.lib.dshim_points_fold_endo.argtypes = [ci, vp, vp, vp, ui, ui, vp]
+        self.lib.dshim_points_mul_split.argtypes = [ci, ci, ci, vp, vp, vp, ui, ui, ui, ui, ci, vp]
+        self.lib.dshim_points_sum.argtypes = [ci, vp, ui, vp]
+        self.lib.dshim_points_sum_seg.argtypes = [ci, vp, ui, ui, vp]
+
+    def sum_threads(self, gid):
+        return self.lib.dshim_sweep_sum_threads(gid)
+
+    def split_elems(self, gid, form):
+        """elements per workgroup of k_points_mul_split in the K-lane (SPLIT_K_LANE) or quad (SPLIT_QUAD; 0 in G1) form"""
+        return self.lib.dshim_sweep_split_elems(gid, form)
+
+    def split_nd(self, gid):
+        return self.lib.dshim_sweep_split_nd(gid)
+
+    def split_steps(self, gid):
+        return self.lib.dshim_sweep_split_steps(gid)
+
+    @staticmethod
+    def _done(st, what, out):
+        assert st == 0, "%s: HIP error %d" % (what, -st)
+        return out.raw
+
+    def fb_table(self, gid, pb, base):
+        assert len(base) == pb
+        out = ctypes.create_string_buffer(32 * 256 * pb)
+        return self._done(self.lib.dshim_fb_table(gid, bytes(base), out), "dshim_fb_table(g%d)" % gid, out)
+
+    def fb_mul(self, gid, pb, table, scalars, mont):
+        n = len(scalars) // FR_BYTES
+        assert len(table) == 32 * 256 * pb and len(scalars) == n * FR_BYTES
+        out = ctypes.create_string_buffer(n * 2 * pb)
+        return self._done(self.lib.dshim_fb_mul(gid, bytes(table), bytes(scalars), 1 if mont else 0, n, out),
+                          "dshim_fb_mul(g%d, n %d)" % (gid, n), out)
+
+    def lincomb(self, gid, pb, vecs, coeffs, k, n):
+        assert len(vecs) == k * n * pb and len(coeffs) == k * FR_BYTES
+        out = ctypes.create_string_buffer(n * 2 * pb)
+        return self._done(self.lib.dshim_points_lincomb(gid, bytes(vecs), bytes(coeffs), k, n, out),
+                          "dshim_points_lincomb(g%d, k %d, n %d)" % (gid, k, n), out)
+
+    def scalar_mul(self, gid, pb, kind, pts, scalars):
+        n = len(scalars) // FR_BYTES
+        assert len(pts) == n * pb
+        out = ctypes.create_string_buffer(n * 2 * pb)
+        return self._done(self.lib.dshim_scalar_mul(gid, kind, bytes(pts), bytes(scalars), n, out),
+                          "dshim_scalar_mul(g%d, kind %d, n %d)" % (gid, kind, n), out)
+
+    def fold_endo(self, gid, pb, lo, hi, coeffs, neg):
+        n = len(hi) // pb
+        assert len(lo) == n * pb
+        out = ctypes.create_string_buffer(n * 2 * pb)
+        return self._done(self.lib.dshim_points_fold_endo(gid, bytes(lo), bytes(hi), bytes(coeffs), neg, n, out),
+                          "dshim_points_fold_endo(g%d, n %d)" % (gid, n), out)
+
+    def mul_split_status(self, gid, pb, form, uniform, pts, scalars, n, lo=None, neg=0, pts_mod=0, vectors=1, mont=1):
+        """pts: vectors x (pts_mod or n) points; lo: vectors x n points or None; scalars: the K magnitudes (uniform) or n Fr
+        -> vectors x n XYZZ"""
+        assert len(pts) == vectors * (pts_mod or n) * pb and (lo is None or len(lo) == vectors * n * pb)
+        out = ctypes.create_string_buffer(vectors * n * 2 * pb)
+        st = self.lib.dshim_points_mul_split(gid, form, 1 if uniform else 0, None if lo is None else bytes(lo), bytes(pts),
+                                             bytes(scalars), neg, n, pts_mod, vectors, mont, out)
+        return st, (out.raw if st == 0 else None)
+
+    def mul_split(self, gid, pb, form, uniform, pts, scalars, n, **kw):
+        st, out = self.mul_split_status(gid, pb, form, uniform, pts, scalars, n, **kw)
+        assert st == 0, "dshim_points_mul_split(g%d, form %d, uniform %d, n %d, %r): HIP error %d" % (gid, form, uniform, n,
+                                                                                                     sorted(kw), -st)
+        return out
+
+    def points_sum(self, gid, pb, pts):
+        n = len(pts) // (2 * pb)
+        out = ctypes.create_string_buffer(2 * pb)
+        return self._done(self.lib.dshim_points_sum(gid, bytes(pts), n, out), "dshim_points_sum(g%d, n %d)" % (gid, n), out)
+
+    def points_sum_seg(self, gid, pb, pts, seg, batch):
+        assert len(pts) == seg * batch * 2 * pb
+        out = ctypes.create_string_buffer(batch * 2 * pb)
+        return self._done(self.lib.dshim_points_sum_seg(gid, bytes(pts), seg, batch, out),
+                          "dshim_points_sum_seg(g%d, seg %d, batch %d)" % (gid, seg, batch), out)
+
+
+def load_sweep():
+    if not _loaded_sweep:
+        _loaded_sweep.append(SweepShim())
+    return _loaded_sweep[0]

@@ -117,6 +117,19 @@ void shim_split_mul(int group, const void* pt, const unsigned* mag, void* out) {
         case 3: split_mul<Fp2<Bls381FqP>>(pt, mag, out); break;
     }
 }
+// whether one lane of k_points_mul_split reads the magnitude m (8 limbs) whole: split_mag_fits of csrc/endo.cuh, by which
+// hk_points_fold_* picks the kernel.  group as above
+int shim_split_mag_fits(int group, const unsigned* m) {
+    u32 mm[8];
+    for (int i = 0; i < 8; i++) mm[i] = m[i];
+    switch (group) {
+        case 0: return split_mag_fits<SplitDigits<Fp<Bn254FqP>>::ND>(mm);
+        case 1: return split_mag_fits<SplitDigits<Fp2<Bn254FqP>>::ND>(mm);
+        case 2: return split_mag_fits<SplitDigits<Fp<Bls381FqP>>::ND>(mm);
+        case 3: return split_mag_fits<SplitDigits<Fp2<Bls381FqP>>::ND>(mm);
+    }
+    return -1;
+}
 // curve: 0 bn254, 1 bls12-381
 void shim_f12_op(int curve, int op, const void* a, const void* b, void* out) {
     if (curve == 0) f12_op<Bn254FqP>(op, a, b, out); else f12_op<Bls381FqP>(op, a, b, out);
