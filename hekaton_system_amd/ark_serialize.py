@@ -24,8 +24,9 @@ PARITY UNPINNED by reference bytes: the reference holds no serialised fixture. W
 published generator encodings (tests/test_ark_serialize.py), the record sizes SURVEY.md §8(a10) derives from the
 reference's types, RFC 7539 / eSTREAM ChaCha keystream vectors, and round trips.
 
-Bulk Montgomery <-> canonical conversion runs on the device (`hk_field_convert`) when a `capi.Context` is given;
-without one the (slow) Python big-int path is used — fine for responses and proofs, not for key files.
+Bulk Montgomery <-> canonical conversion runs on the device (`hk_field_convert`) when a `capi.Context` is given, and so
+do the square roots and sign flags of compressed points (`hk_points_decompress_*` / `hk_points_compress_*`); without one
+the (slow) Python big-int path is used — fine for responses and proofs, not for key files.
 """
 import struct
 
@@ -193,16 +194,21 @@ class ArkCodec:
         if n == 0:
             return b""
         inf = ~abi.any(axis=1)                          # Montgomery zero == canonical zero == the ABI's infinity
-        canon = self._convert(1, abi, False).reshape(n, coords, fqb)
-        neg = self._y_negative(canon, group) & ~inf
         half = coords // 2
+        if compress and self.ctx is not None:           # x and the sign flag from the device; no y leaves it
+            xc, fl = self.ctx.points_compress(group, abi.reshape(-1))
+            canon = np.asarray(xc, dtype=np.uint8).reshape(n, half, fqb)
+            neg = (np.asarray(fl, dtype=np.uint8) & 2 != 0) & ~inf
+        else:
+            canon = self._convert(1, abi, False).reshape(n, coords, fqb)
+            neg = self._y_negative(canon, group) & ~inf
         if not self.zcash:
             out = canon[:, :half].reshape(n, -1).copy() if compress else canon.reshape(n, -1).copy()
             out[:, -1] |= np.where(inf, 0x40, np.where(neg, 0x80, 0)).astype(np.uint8)
             return out.tobytes()
         be = canon[:, :, ::-1]                          # big-endian coordinates
         if group == 2:
-            be = be[:, [1, 0, 3, 2]]                    # c1 || c0
+            be = be[:, [1, 0, 3, 2][:be.shape[1]]]      # c1 || c0 (x alone when the device compressed)
         out = (be[:, :half] if compress else be).reshape(n, -1).copy()
         flags = np.where(inf, 0x40, 0).astype(np.uint8)
         if compress:
@@ -215,9 +221,14 @@ class ArkCodec:
         full = self.g1b if group == 1 else self.g2b
         return full // 2 if compress else full
 
-    def points_from_wire(self, group, buf, n, compress=False):
+    def points_from_wire(self, group, buf, n, compress=False, validate=False, out=None):
         """n encoded points -> ABI array.  Unchecked like the reference's `deserialize_*_unchecked` (no curve or
-        subgroup check); flags and canonical-range are validated as ark-serialize always does."""
+        subgroup check); flags and canonical-range are validated as ark-serialize always does.
+        With a context, compressed points are decompressed on the device (`hk_points_decompress_*`): validate=True then
+        also runs ark's checked `deserialize_compressed` (InvalidData for a point outside the prime-order subgroup), and
+        `out` - a DeviceBuffer / DeviceView of n points - receives the array in HBM and is returned in its place."""
+        if (validate or out is not None) and not (compress and self.ctx is not None):
+            raise ValueError("validate / out belong to the device's decompression: compress=True and a context")
         coords = 2 if group == 1 else 4
         fqb = self.fqb
         half = coords // 2
@@ -226,7 +237,7 @@ class ArkCodec:
         if a.size != n * size:
             raise SerializationError("IoError: wrong length")
         if n == 0:
-            return np.zeros(0, dtype=np.uint8)
+            return np.zeros(0, dtype=np.uint8) if out is None else out
         a = a.reshape(n, size).copy()
         if not self.zcash:
             fl = a[:, -1] & 0xC0
@@ -253,13 +264,21 @@ class ArkCodec:
         self._check_reduced(canon.reshape(-1), fqb, self.q)
         if inf.any() and canon[inf].any():
             raise SerializationError("InvalidData: infinity with non-zero coordinates")
+        if compress and self.ctx is not None:
+            flags = inf.astype(np.uint8) | (neg.astype(np.uint8) << 1)
+            pts, status = self.ctx.points_decompress(group, canon.reshape(-1), flags, check=validate, out=out)
+            if (status == 0).any():
+                raise SerializationError("InvalidData: x is not on the curve")
+            if (status == 2).any():
+                raise SerializationError("InvalidData: point is not in the prime-order subgroup")
+            return pts
         if compress:
             canon = self._decompress(group, canon, inf, neg)
         mont = self._convert(1, canon, True).reshape(n, coords * fqb)
         mont[inf] = 0
         return mont.reshape(-1)
 
-    # ---- decompression (host big-int; the reference only ever *writes* compressed points, node.rs:611) ----
+    # ---- decompression without a context (host big-int, one point at a time: the mirror the device path is tested against) ----
     def _fq_sqrt(self, a):
         q = self.q                                       # q = 3 mod 4 on both curves
         s = pow(a, (q + 1) // 4, q)
@@ -333,15 +352,26 @@ class ArkCodec:
         w.u64(abi.size // pb)
         w.put(self.points_to_wire(group, abi, compress))
 
-    def read_points_vec(self, r, group, compress=False):
+    def read_points_vec(self, r, group, compress=False, validate=False, device=False):
+        """device=True (compressed, with a context): the array is decompressed into a DeviceBuffer of its own and stays in
+        HBM - hk_pk_upload takes it from there."""
         n = r.u64()
-        return self.points_from_wire(group, r.take(n * self.point_size(group, compress)), n, compress)
+        out = None
+        if device and n:
+            from .capi import DeviceBuffer
+            out = DeviceBuffer(self.ctx, n * (self.g1b if group == 1 else self.g2b))
+        try:
+            return self.points_from_wire(group, r.take(n * self.point_size(group, compress)), n, compress, validate, out)
+        except Exception:
+            if out is not None:
+                out.free()
+            raise
 
     def write_point(self, w, group, abi, compress=False):
         w.put(self.points_to_wire(group, _host(abi, self.ctx), compress))
 
-    def read_point(self, r, group, compress=False):
-        return self.points_from_wire(group, r.take(self.point_size(group, compress)), 1, compress)
+    def read_point(self, r, group, compress=False, validate=False):
+        return self.points_from_wire(group, r.take(self.point_size(group, compress)), 1, compress, validate)
 
     # ---- cp-groth16 records (field order = derive order, data_structures.rs) ----
     def write_proof(self, w, proof, compress=False):                       # :6-16
@@ -358,47 +388,51 @@ class ArkCodec:
         ds = self.read_points_vec(r, 1, compress)
         return Proof(a, b, c, [ds[i:i + self.g1b].copy() for i in range(0, ds.size, self.g1b)])
 
-    def write_vk(self, w, vk):                                              # :32-46
-        self.write_point(w, 1, vk.alpha_g)
-        self.write_point(w, 2, vk.beta_h)
-        self.write_point(w, 2, vk.gamma_h)
-        self.write_point(w, 2, vk.last_delta_h)
-        self.write_points_vec(w, 1, vk.gamma_abc_g)
-        self.write_points_vec(w, 2, vk.deltas_h)
+    def write_vk(self, w, vk, compress=False):                              # :32-46
+        self.write_point(w, 1, vk.alpha_g, compress)
+        self.write_point(w, 2, vk.beta_h, compress)
+        self.write_point(w, 2, vk.gamma_h, compress)
+        self.write_point(w, 2, vk.last_delta_h, compress)
+        self.write_points_vec(w, 1, vk.gamma_abc_g, compress)
+        self.write_points_vec(w, 2, vk.deltas_h, compress)
 
-    def read_vk(self, r):
-        return VerifyingKey(self.read_point(r, 1), self.read_point(r, 2), self.read_point(r, 2),
-                            self.read_point(r, 2), self.read_points_vec(r, 1), self.read_points_vec(r, 2))
+    def read_vk(self, r, compress=False, validate=False):
+        c, v = compress, validate
+        return VerifyingKey(self.read_point(r, 1, c, v), self.read_point(r, 2, c, v), self.read_point(r, 2, c, v),
+                            self.read_point(r, 2, c, v), self.read_points_vec(r, 1, c, v), self.read_points_vec(r, 2, c, v))
 
-    def write_ck(self, w, ck):                                              # :107-114
-        self.write_point(w, 1, ck.last_delta_g)
+    def write_ck(self, w, ck, compress=False):                              # :107-114
+        self.write_point(w, 1, ck.last_delta_g, compress)
         w.u64(len(ck.deltas_abc_g))
         for v in ck.deltas_abc_g:
-            self.write_points_vec(w, 1, v)
+            self.write_points_vec(w, 1, v, compress)
 
-    def read_ck(self, r):
-        last = self.read_point(r, 1)
-        return CommitterKey(last, [self.read_points_vec(r, 1) for _ in range(r.u64())])
+    def read_ck(self, r, compress=False, validate=False, device=False):
+        last = self.read_point(r, 1, compress, validate)
+        return CommitterKey(last, [self.read_points_vec(r, 1, compress, validate, device) for _ in range(r.u64())])
 
-    def write_pk(self, w, pk):                                              # :65-83
-        self.write_vk(w, pk.vk)
-        self.write_point(w, 1, pk.beta_g)
-        self.write_points_vec(w, 1, pk.a_g)
-        self.write_points_vec(w, 1, pk.b_g)
-        self.write_points_vec(w, 2, pk.b_h)
-        self.write_points_vec(w, 1, pk.h_g)
-        self.write_ck(w, pk.ck)
-        self.write_points_vec(w, 1, pk.deltas_g)
+    def write_pk(self, w, pk, compress=False):                              # :65-83
+        self.write_vk(w, pk.vk, compress)
+        self.write_point(w, 1, pk.beta_g, compress)
+        self.write_points_vec(w, 1, pk.a_g, compress)
+        self.write_points_vec(w, 1, pk.b_g, compress)
+        self.write_points_vec(w, 2, pk.b_h, compress)
+        self.write_points_vec(w, 1, pk.h_g, compress)
+        self.write_ck(w, pk.ck, compress)
+        self.write_points_vec(w, 1, pk.deltas_g, compress)
 
-    def read_pk(self, r):
-        vk = self.read_vk(r)
-        beta_g = self.read_point(r, 1)
-        a_g = self.read_points_vec(r, 1)
-        b_g = self.read_points_vec(r, 1)
-        b_h = self.read_points_vec(r, 2)
-        h_g = self.read_points_vec(r, 1)
-        ck = self.read_ck(r)
-        deltas_g = self.read_points_vec(r, 1)
+    def read_pk(self, r, compress=False, validate=False, device=False):
+        """device=True: the key's queries (a_g, b_g, b_h, h_g, the committer key's stages, deltas_g) stay in HBM as
+        DeviceBuffers, as `capi.Context.pk_upload` takes them; the verifying key and the single points come to the host."""
+        c, v, d = compress, validate, device
+        vk = self.read_vk(r, c, v)
+        beta_g = self.read_point(r, 1, c, v)
+        a_g = self.read_points_vec(r, 1, c, v, d)
+        b_g = self.read_points_vec(r, 1, c, v, d)
+        b_h = self.read_points_vec(r, 2, c, v, d)
+        h_g = self.read_points_vec(r, 1, c, v, d)
+        ck = self.read_ck(r, c, v, d)
+        deltas_g = self.read_points_vec(r, 1, c, v, d)
         return ProvingKey(vk, beta_g, a_g, b_g, b_h, h_g, ck, deltas_g)
 
     # ---- worker responses (distributed-prover/src/worker.rs:20-52) ----
@@ -586,9 +620,10 @@ class ProvingKeys:
     def num_subcircuits(self):
         return len(self.subcircuit_representative_map)
 
-    def serialize(self, codec, with_id=True):
+    def serialize(self, codec, with_id=True, compress=False):
         """with_id=True: the derived impl on `ProvingKeys` (what `pks.serialize_uncompressed` writes to disk);
-        with_id=False: the hand-written impl on `&ProvingKeys` (:112-135), which omits `circuit_id`."""
+        with_id=False: the hand-written impl on `&ProvingKeys` (:112-135), which omits `circuit_id`.
+        compress=True: `serialize_compressed` - every point as x and a sign flag."""
         w = Writer()
         if with_id:
             write_bytes_vec(w, self.circuit_id.encode("utf-8"))
@@ -596,19 +631,21 @@ class ProvingKeys:
         w.u64(len(self.minimal_proving_keys))
         for k in sorted(self.minimal_proving_keys):
             w.u64(k)
-            codec.write_pk(w, self.minimal_proving_keys[k])
+            codec.write_pk(w, self.minimal_proving_keys[k], compress)
         write_usize_map(w, self.subcircuit_representative_map)
         return w.getvalue()
 
     @classmethod
-    def deserialize(cls, codec, buf, with_id=True):
+    def deserialize(cls, codec, buf, with_id=True, compress=False, validate=False, device=False):
+        """compress / validate / device: as `ArkCodec.read_pk` - `deserialize_compressed` (validate: checked), with the
+        keys' queries left in HBM when `device`."""
         r = Reader(buf)
         cid = read_bytes_vec(r).decode("utf-8") if with_id else ""
         params = read_bytes_vec(r)
         pks = {}
         for _ in range(r.u64()):
             k = r.u64()
-            pks[k] = codec.read_pk(r)
+            pks[k] = codec.read_pk(r, compress, validate, device)
         rep = read_usize_map(r)
         return cls(cid, params, pks, rep)
 

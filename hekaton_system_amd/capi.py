@@ -152,7 +152,8 @@ EXPORTS = ["hk_status_str", "hk_version", "hk_ctx_create", "hk_ctx_destroy", "hk
            "hk_trace_sort", "hk_stage0_witness", "hk_r1cs_check", "hk_pk_r1cs_check",
            "hk_sha_tree", "hk_sha_tree_inputs", "hk_ram_stage0_witness", "hk_ram_stage1_witness",
            "hk_r1cs_job_trace", "hk_r1cs_job_witness", "hk_vkd_trace", "hk_vkd_witness",
-           "hk_scalar_powers", "hk_ipa_quotient"]
+           "hk_scalar_powers", "hk_ipa_quotient", "hk_field_sqrt", "hk_points_decompress_g1", "hk_points_decompress_g2",
+           "hk_points_compress_g1", "hk_points_compress_g2"]
 
 HK_VERIFY_CHECK_POINTS = 1
 VERDICT_REJECT, VERDICT_ACCEPT, VERDICT_BAD_POINT = 0, 1, 2
@@ -257,6 +258,12 @@ def load():
     lib.hk_vkd_witness.argtypes = [vp, C.POINTER(hk_vkd_desc), vp, sz, sz, C.POINTER(hk_vkd_cols), vp]
     lib.hk_scalar_powers.argtypes = [vp, vp, sz, sz, vp]
     lib.hk_ipa_quotient.argtypes = [vp, vp, sz, vp, vp, sz, vp]
+    if hasattr(lib, "hk_field_sqrt"):             # absent only from older experiment builds loaded through HK_LIB
+        lib.hk_field_sqrt.argtypes = [vp, i, vp, sz, vp, vp]
+        for f in (lib.hk_points_decompress_g1, lib.hk_points_decompress_g2):
+            f.argtypes = [vp, vp, vp, sz, i, vp, vp]
+        for f in (lib.hk_points_compress_g1, lib.hk_points_compress_g2):
+            f.argtypes = [vp, vp, sz, vp, vp]
     _lib = lib
     return lib
 
@@ -1024,6 +1031,47 @@ class Context:
         check(fn(self.handle, ptr(pts) if n else None, n, ok.ctypes.data), fn.__name__)
         return ok
 
+    def field_sqrt(self, which, data):
+        """hk_field_sqrt: square roots of packed Montgomery Fq (`which` = 1) or Fq2 (2) elements.  Returns (roots, ok):
+        the root that is not larger than its negative (ark's order), zeros where there is none; ok np.uint8[n] of 1 / 0."""
+        eb = self.fq_bytes * int(which)
+        data = _hd(data)
+        n = (data.nbytes if isinstance(data, DeviceBuffer) else data.size) // eb
+        out, ok = np.zeros(n * eb, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        check(self.lib.hk_field_sqrt(self.handle, int(which), ptr(data) if n else None, n, out.ctypes.data, ok.ctypes.data),
+              "hk_field_sqrt")
+        return out, ok
+
+    def points_decompress(self, group, x_canon, flags, check=False, out=None):
+        """hk_points_decompress_g1 / _g2: ark-ec's `get_point_from_x_unchecked` under `deserialize_compressed`.  x_canon:
+        n canonical little-endian x (G2: c0 || c1); flags: n bytes, bit 0 infinity, bit 1 "y is the larger root".  Returns
+        (points, status): packed affine Montgomery points and np.uint8[n] of 1 ok | 0 no such point (zeros) | 2 - with
+        `check` - outside the prime-order subgroup.  `out` may be a DeviceBuffer / DeviceView of n points: they stay in
+        HBM (ready for hk_pk_upload) and `out` is returned as `points`."""
+        xb = self.fq_bytes * (1 if group == 1 else 2)
+        x_canon, flags = _hd(x_canon), _hd(flags)
+        n = flags.nbytes if isinstance(flags, DeviceBuffer) else flags.size
+        pts = out if out is not None else np.zeros(2 * n * xb, dtype=np.uint8)
+        status = np.zeros(n, dtype=np.uint8)
+        fn = self.lib.hk_points_decompress_g1 if group == 1 else self.lib.hk_points_decompress_g2
+        st = fn(self.handle, ptr(x_canon) if n else None, ptr(flags) if n else None, n, int(bool(check)),
+                ptr(pts) if n else None, status.ctypes.data)
+        if st != HK_OK:                                    # the module's check() is shadowed by the keyword
+            raise HekatonError(st, fn.__name__)
+        return pts, status
+
+    def points_compress(self, group, pts):
+        """hk_points_compress_g1 / _g2: the x coordinate and `SWFlags::from_y_coordinate` of `serialize_compressed`.  pts:
+        packed affine Montgomery points (uint8 array or DeviceBuffer).  Returns (x_canon, flags) as points_decompress takes
+        them."""
+        xb = self.fq_bytes * (1 if group == 1 else 2)
+        pts = _hd(pts)
+        n = (pts.nbytes if isinstance(pts, DeviceBuffer) else pts.size) // (2 * xb)
+        x, flags = np.zeros(n * xb, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        fn = self.lib.hk_points_compress_g1 if group == 1 else self.lib.hk_points_compress_g2
+        check(fn(self.handle, ptr(pts) if n else None, n, x.ctypes.data, flags.ctypes.data), fn.__name__)
+        return x, flags
+
     def vk_prepare(self, *, alpha_g, beta_h, gamma_h, deltas_h, gamma_abc_g):
         """hk_vk_prepare (prepare_verifying_key, verifier.rs:7-18).  deltas_h: the stage deltas then delta_last, packed G2
         bytes; gamma_abc_g: packed G1 bytes.  Returns a DeviceVk."""
@@ -1065,7 +1113,7 @@ class Context:
         d.ck_stage, d.ck_len, d.n_stages = ck_ptrs, ck_lens, len(cks)
         small = [arr(x) for x in (deltas_g, last_delta_h, alpha_g, beta_g, beta_h)]
         keep += small
-        d.deltas_g, d.last_delta_h, d.alpha_g, d.beta_g, d.beta_h = [s.ctypes.data for s in small]
+        d.deltas_g, d.last_delta_h, d.alpha_g, d.beta_g, d.beta_h = [addr(s) for s in small]
         csrs = []
         if matrices is not None:
             for (rp, col, val) in matrices:

@@ -39,6 +39,7 @@ struct Ops final : CurveOps {
     typedef typename C::Fq Fq;
     typedef typename C::Fq2 Fq2;
     typedef VerifyRun<typename Fq::Params> Verify;
+    typedef CodecRun<typename Fq::Params> Codec;
 
     Ops() : CurveOps(sizeof(Fr), sizeof(Fq), sizeof(Affine<Fq>), sizeof(Affine<Fq2>), sizeof(Fp12<typename Fq::Params>)) {}
 
@@ -120,6 +121,8 @@ struct Ops final : CurveOps {
         b = PairRun<typename Fq::Params>::max_private_bytes();
         if (b > m) m = b;
         b = Verify::max_private_bytes();
+        if (b > m) m = b;
+        b = Codec::max_private_bytes();
         if (b > m) m = b;
         b = finish_private_bytes();
         return b > m ? b : m;
@@ -208,6 +211,18 @@ struct Ops final : CurveOps {
     // agg_scalars.cuh
     hk_status scalar_powers(hk_ctx*, const void*, size_t, size_t, void*) override;
     hk_status ipa_quotient(hk_ctx*, const void*, size_t, const void*, const void*, size_t, void*) override;
+    // point_codec.cuh
+    hk_status field_sqrt(hk_ctx* ctx, int which, const void* in, size_t n, void* out, unsigned char* ok) override {
+        return Codec::field_sqrt(ctx, which, in, n, out, ok);
+    }
+    hk_status points_decompress(hk_ctx* ctx, int group, const void* x_canon, const unsigned char* flags, size_t n, int check,
+                                void* points_out, unsigned char* status) override {
+        return Codec::points_decompress(ctx, group, x_canon, flags, n, check, points_out, status);
+    }
+    hk_status points_compress(hk_ctx* ctx, int group, const void* points, size_t n, void* x_canon_out,
+                              unsigned char* flags_out) override {
+        return Codec::points_compress(ctx, group, points, n, x_canon_out, flags_out);
+    }
 };
 
 }  // namespace hk

@@ -22,6 +22,7 @@ extern template struct MsmRun<CurveBls381::Fq2>;
 extern template struct MsmSort<CurveBls381::Fr>;
 extern template struct PairRun<CurveBls381::Fq::Params>;
 extern template struct VerifyRun<CurveBls381::Fq::Params>;
+extern template struct CodecRun<CurveBls381::Fq::Params>;
 CurveOps* curve_ops_bls381() {
     static Ops<CurveBls381> ops;
     return &ops;

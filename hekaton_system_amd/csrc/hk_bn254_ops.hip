@@ -22,6 +22,7 @@ extern template struct MsmRun<CurveBn254::Fq2>;
 extern template struct MsmSort<CurveBn254::Fr>;
 extern template struct PairRun<CurveBn254::Fq::Params>;
 extern template struct VerifyRun<CurveBn254::Fq::Params>;
+extern template struct CodecRun<CurveBn254::Fq::Params>;
 CurveOps* curve_ops_bn254() {
     static Ops<CurveBn254> ops;
     return &ops;

@@ -1,6 +1,7 @@
 #include <utility>
 // hk_core.hip — context / lane management and the C ABI entry points (dispatch to per-curve code).
 #include "hk_internal.h"
+#include "job_args.h"
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
 #include <atomic>
@@ -740,6 +741,67 @@ hk_status hk_ipa_quotient(hk_ctx* ctx, const void* challenges_mont, size_t l, co
                           size_t shift, void* q_out) {
     if (!ctx) return HK_ERR_ARG;
     return ctx->ops->ipa_quotient(ctx, challenges_mont, l, rho_mont, z_mont, shift, q_out);
+}
+
+// ---- compressed points (point_codec.cuh).  A rule refuses with HK_ERR_ARG before anything is written: a missing buffer, an
+// input that shares a byte with an output, two outputs that share one, n >= 2^31.
+static bool codec_bufs_bad(const void* const* in, const size_t* in_len, int n_in, const void* const* out, const size_t* out_len,
+                           int n_out) {
+    for (int a = 0; a < n_in; a++)
+        if (!in[a]) return true;
+    for (int b = 0; b < n_out; b++) {
+        if (!out[b]) return true;
+        for (int a = 0; a < n_in; a++)
+            if (hk::bufs_overlap(in[a], in_len[a], out[b], out_len[b])) return true;
+        for (int c = 0; c < b; c++)
+            if (hk::bufs_overlap(out[c], out_len[c], out[b], out_len[b])) return true;
+    }
+    return false;
+}
+hk_status hk_field_sqrt(hk_ctx* ctx, int which, const void* in_mont, size_t n, void* out_mont, uint8_t* ok) {
+    if (!ctx || (which != 1 && which != 2) || n >= ((size_t)1 << 31)) return HK_ERR_ARG;
+    if (n == 0) return HK_OK;
+    const size_t eb = ctx->ops->fq_bytes * (size_t)which;
+    const void* in[1] = {in_mont};
+    const void* out[2] = {out_mont, ok};
+    const size_t il[1] = {n * eb}, ol[2] = {n * eb, n};
+    if (codec_bufs_bad(in, il, 1, out, ol, 2)) return HK_ERR_ARG;
+    return ctx->ops->field_sqrt(ctx, which, in_mont, n, out_mont, ok);
+}
+static hk_status points_decompress(hk_ctx* ctx, int group, const void* x_canon, const uint8_t* flags, size_t n, int check,
+                                   void* points_out, uint8_t* status) {
+    if (!ctx || n >= ((size_t)1 << 31)) return HK_ERR_ARG;
+    if (n == 0) return HK_OK;
+    const size_t xb = ctx->ops->fq_bytes * (size_t)group;
+    const void* in[2] = {x_canon, flags};
+    const void* out[2] = {points_out, status};
+    const size_t il[2] = {n * xb, n}, ol[2] = {2 * n * xb, n};
+    if (codec_bufs_bad(in, il, 2, out, ol, 2)) return HK_ERR_ARG;
+    return ctx->ops->points_decompress(ctx, group, x_canon, flags, n, check, points_out, status);
+}
+static hk_status points_compress(hk_ctx* ctx, int group, const void* points, size_t n, void* x_canon_out, uint8_t* flags_out) {
+    if (!ctx || n >= ((size_t)1 << 31)) return HK_ERR_ARG;
+    if (n == 0) return HK_OK;
+    const size_t xb = ctx->ops->fq_bytes * (size_t)group;
+    const void* in[1] = {points};
+    const void* out[2] = {x_canon_out, flags_out};
+    const size_t il[1] = {2 * n * xb}, ol[2] = {n * xb, n};
+    if (codec_bufs_bad(in, il, 1, out, ol, 2)) return HK_ERR_ARG;
+    return ctx->ops->points_compress(ctx, group, points, n, x_canon_out, flags_out);
+}
+hk_status hk_points_decompress_g1(hk_ctx* ctx, const void* x_canon, const uint8_t* flags, size_t n, int check, void* points_out,
+                                  uint8_t* status) {
+    return points_decompress(ctx, 1, x_canon, flags, n, check, points_out, status);
+}
+hk_status hk_points_decompress_g2(hk_ctx* ctx, const void* x_canon, const uint8_t* flags, size_t n, int check, void* points_out,
+                                  uint8_t* status) {
+    return points_decompress(ctx, 2, x_canon, flags, n, check, points_out, status);
+}
+hk_status hk_points_compress_g1(hk_ctx* ctx, const void* points, size_t n, void* x_canon_out, uint8_t* flags_out) {
+    return points_compress(ctx, 1, points, n, x_canon_out, flags_out);
+}
+hk_status hk_points_compress_g2(hk_ctx* ctx, const void* points, size_t n, void* x_canon_out, uint8_t* flags_out) {
+    return points_compress(ctx, 2, points, n, x_canon_out, flags_out);
 }
 
 }  // extern "C"

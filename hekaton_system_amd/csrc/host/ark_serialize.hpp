@@ -9,7 +9,8 @@
 // the published ChaCha keystream and generator encodings).  Points cross as the ABI's packed-affine Montgomery bytes;
 // the Montgomery <-> canonical conversion is hk_field_convert (device).  ArkCodecBn254 is ark's default short-Weierstrass
 // encoding; ArkCodecBls381 the zcash format ark-bls12-381 overrides it with (big-endian, Fp2 = c1 || c0, flags in the
-// three top bits of the FIRST byte; uncompressed records only - what the worker protocol carries).
+// three top bits of the FIRST byte).  Compressed points (x and a sign flag; serialize_compressed / deserialize_compressed)
+// go over hk_points_compress_* / hk_points_decompress_*: the square root and the sign rule run on the device.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -43,9 +44,16 @@ public:
     // group: 1 = G1 (x, y), 2 = G2 (x.c0, x.c1, y.c0, y.c1); abi = n packed Montgomery points
     Bytes points_to_wire(int group, const Bytes& abi, bool compress = false) const {
         const size_t coords = group == 1 ? 2 : 4, pb = coords * 32, n = abi.size() / pb;
+        if (compress) {                                       // x and the flag from the device (hk_points_compress_*)
+            Bytes out(n * pb / 2), fl(n);
+            if (n) check((group == 1 ? hk_points_compress_g1 : hk_points_compress_g2)(ctx_.raw(), abi.data(), n, out.data(), fl.data()),
+                         "hk_points_compress");
+            for (size_t i = 0; i < n; i++) out[(i + 1) * (pb / 2) - 1] |= (fl[i] & 1) ? 0x40 : ((fl[i] & 2) ? 0x80 : 0);
+            return out;
+        }
         Bytes canon(abi.size());
         if (n) check(hk_field_convert(ctx_.raw(), 1, abi.data(), canon.data(), n * coords, 0), "hk_field_convert");
-        const size_t out_sz = compress ? pb / 2 : pb;
+        const size_t out_sz = pb;
         Bytes out(n * out_sz);
         for (size_t i = 0; i < n; i++) {
             const uint8_t* src = &abi[i * pb];
@@ -71,7 +79,29 @@ public:
         return out;
     }
 
-    // uncompressed only (what the reference reads: deserialize_uncompressed_unchecked) -> ABI bytes
+    // compressed (deserialize_compressed; validate: its checked form, ark's AffineRepr::check) -> ABI bytes
+    Bytes points_from_wire(int group, const uint8_t* buf, size_t n, bool compress, bool validate = false) const {
+        if (!compress) return points_from_wire(group, buf, n);
+        const size_t xb = group == 1 ? 32 : 64;
+        Bytes x(buf, buf + n * xb), fl(n), abi(2 * n * xb), status(n);
+        for (size_t i = 0; i < n; i++) {
+            uint8_t& last = x[(i + 1) * xb - 1];
+            uint8_t f = last & 0xC0;
+            if (f == 0xC0) throw SerializationError("UnexpectedFlags");
+            last &= 0x3F;
+            fl[i] = f == 0x40 ? 1 : (f == 0x80 ? 2 : 0);
+            if (fl[i] == 1 && !std::all_of(&x[i * xb], &x[i * xb] + xb, [](uint8_t b) { return b == 0; }))
+                throw SerializationError("InvalidData: infinity with non-zero coordinates");
+        }
+        if (n) check((group == 1 ? hk_points_decompress_g1 : hk_points_decompress_g2)(ctx_.raw(), x.data(), fl.data(), n, validate,
+                                                                                   abi.data(), status.data()), "hk_points_decompress");
+        for (size_t i = 0; i < n; i++) {
+            if (status[i] == 0) throw SerializationError("InvalidData: x is not on the curve");
+            if (status[i] == 2) throw SerializationError("InvalidData: point is not in the prime-order subgroup");
+        }
+        return abi;
+    }
+    // uncompressed (what the reference reads: deserialize_uncompressed_unchecked) -> ABI bytes
     Bytes points_from_wire(int group, const uint8_t* buf, size_t n) const {
         const size_t coords = group == 1 ? 2 : 4, pb = coords * 32;
         Bytes canon(buf, buf + n * pb);
@@ -96,12 +126,25 @@ public:
     static uint64_t get_u64(const uint8_t* p) { uint64_t v = 0; for (int i = 7; i >= 0; i--) v = (v << 8) | p[i]; return v; }
     void put(Bytes& w, const Bytes& b) const { w.insert(w.end(), b.begin(), b.end()); }
 
-    Bytes proof_to_wire(const Proof& p) const {                                 // data_structures.rs:6-16
+    Bytes proof_to_wire(const Proof& p, bool compress = false) const {          // data_structures.rs:6-16
         Bytes w;
-        put(w, points_to_wire(1, p.a)); put(w, points_to_wire(2, p.b)); put(w, points_to_wire(1, p.c));
+        put(w, points_to_wire(1, p.a, compress)); put(w, points_to_wire(2, p.b, compress)); put(w, points_to_wire(1, p.c, compress));
         put_u64(w, p.ds.size());                                                // Vec<G1Affine>: u64 length prefix
-        for (auto& d : p.ds) put(w, points_to_wire(1, d));
+        for (auto& d : p.ds) put(w, points_to_wire(1, d, compress));
         return w;
+    }
+    Proof proof_from_wire(const Bytes& b, bool compress = false, bool validate = false) const {
+        const size_t g1 = compress ? 32 : 64, g2 = 2 * g1;
+        if (b.size() < 2 * g1 + g2 + 8) throw SerializationError("IoError: unexpected end of input");
+        Proof r;
+        const uint8_t* p = b.data();
+        r.a = points_from_wire(1, p, 1, compress, validate); p += g1;
+        r.b = points_from_wire(2, p, 1, compress, validate); p += g2;
+        r.c = points_from_wire(1, p, 1, compress, validate); p += g1;
+        uint64_t nd = get_u64(p); p += 8;
+        if (b.size() != 2 * g1 + g2 + 8 + nd * g1) throw SerializationError("IoError: wrong length");
+        for (uint64_t i = 0; i < nd; i++, p += g1) r.ds.push_back(points_from_wire(1, p, 1, compress, validate));
+        return r;
     }
     Bytes stage0_response_to_wire(const Stage0Response& r) const {              // worker.rs:20-25, 104 bytes
         Bytes w;
@@ -217,9 +260,23 @@ public:
     explicit ArkCodecBls381(const Context& ctx) : ctx_(ctx) {
         if (ctx.sizes().fq != FQ) throw SerializationError("ArkCodecBls381 needs a BLS12-381 context");
     }
-    // group: 1 = G1 (x, y), 2 = G2 (x.c0, x.c1, y.c0, y.c1 in the ABI; c1 || c0 on the wire); uncompressed
-    Bytes points_to_wire(int group, const Bytes& abi) const {
+    // group: 1 = G1 (x, y), 2 = G2 (x.c0, x.c1, y.c0, y.c1 in the ABI; c1 || c0 on the wire)
+    Bytes points_to_wire(int group, const Bytes& abi, bool compress = false) const {
         const size_t coords = group == 1 ? 2 : 4, pb = coords * FQ, n = abi.size() / pb;
+        if (compress) {                                       // x and the flag from the device (hk_points_compress_*)
+            const size_t xc = coords / 2, xb = xc * FQ;
+            Bytes x(n * xb), fl(n), out(n * xb);
+            if (n) check((group == 1 ? hk_points_compress_g1 : hk_points_compress_g2)(ctx_.raw(), abi.data(), n, x.data(), fl.data()),
+                         "hk_points_compress");
+            for (size_t i = 0; i < n; i++) {
+                for (size_t c = 0; c < xc; c++) {
+                    const uint8_t* le = &x[i * xb + (xc - 1 - c) * FQ];         // Fp2: c1 first
+                    for (size_t b = 0; b < FQ; b++) out[i * xb + c * FQ + b] = le[FQ - 1 - b];
+                }
+                out[i * xb] |= 0x80 | ((fl[i] & 1) ? 0x40 : ((fl[i] & 2) ? 0x20 : 0));
+            }
+            return out;
+        }
         Bytes canon(abi.size());
         if (n) check(hk_field_convert(ctx_.raw(), 1, abi.data(), canon.data(), n * coords, 0), "hk_field_convert");
         Bytes out(n * pb);
@@ -235,6 +292,31 @@ public:
             if (inf) o[0] |= 0x40;
         }
         return out;
+    }
+    // compressed (deserialize_compressed; validate: its checked form) -> ABI bytes
+    Bytes points_from_wire(int group, const uint8_t* buf, size_t n, bool compress, bool validate = false) const {
+        if (!compress) return points_from_wire(group, buf, n);
+        const size_t xc = group == 1 ? 1 : 2, xb = xc * FQ;
+        Bytes x(n * xb), fl(n), abi(2 * n * xb), status(n);
+        for (size_t i = 0; i < n; i++) {
+            Bytes be(buf + i * xb, buf + (i + 1) * xb);
+            uint8_t f = be[0] & 0xE0;
+            if (!(f & 0x80)) throw SerializationError("UnexpectedFlags: compression bit");
+            if ((f & 0x40) && (f & 0x20)) throw SerializationError("UnexpectedFlags");
+            be[0] &= 0x1F;
+            fl[i] = (f & 0x40) ? 1 : ((f & 0x20) ? 2 : 0);
+            if (fl[i] == 1 && !std::all_of(be.begin(), be.end(), [](uint8_t b) { return b == 0; }))
+                throw SerializationError("InvalidData: infinity with non-zero coordinates");
+            for (size_t c = 0; c < xc; c++)
+                for (size_t b = 0; b < FQ; b++) x[i * xb + (xc - 1 - c) * FQ + b] = be[c * FQ + FQ - 1 - b];
+        }
+        if (n) check((group == 1 ? hk_points_decompress_g1 : hk_points_decompress_g2)(ctx_.raw(), x.data(), fl.data(), n, validate,
+                                                                                   abi.data(), status.data()), "hk_points_decompress");
+        for (size_t i = 0; i < n; i++) {
+            if (status[i] == 0) throw SerializationError("InvalidData: x is not on the curve");
+            if (status[i] == 2) throw SerializationError("InvalidData: point is not in the prime-order subgroup");
+        }
+        return abi;
     }
     Bytes points_from_wire(int group, const uint8_t* buf, size_t n) const {
         const size_t coords = group == 1 ? 2 : 4, pb = coords * FQ;
@@ -262,12 +344,25 @@ public:
     static void put_u64(Bytes& w, uint64_t v) { for (int i = 0; i < 8; i++) w.push_back((uint8_t)(v >> (8 * i))); }
     static uint64_t get_u64(const uint8_t* p) { uint64_t v = 0; for (int i = 7; i >= 0; i--) v = (v << 8) | p[i]; return v; }
     void put(Bytes& w, const Bytes& b) const { w.insert(w.end(), b.begin(), b.end()); }
-    Bytes proof_to_wire(const Proof& p) const {
+    Bytes proof_to_wire(const Proof& p, bool compress = false) const {
         Bytes w;
-        put(w, points_to_wire(1, p.a)); put(w, points_to_wire(2, p.b)); put(w, points_to_wire(1, p.c));
+        put(w, points_to_wire(1, p.a, compress)); put(w, points_to_wire(2, p.b, compress)); put(w, points_to_wire(1, p.c, compress));
         put_u64(w, p.ds.size());
-        for (auto& d : p.ds) put(w, points_to_wire(1, d));
+        for (auto& d : p.ds) put(w, points_to_wire(1, d, compress));
         return w;
+    }
+    Proof proof_from_wire(const Bytes& b, bool compress = false, bool validate = false) const {
+        const size_t g1 = compress ? FQ : 2 * FQ, g2 = 2 * g1;
+        if (b.size() < 2 * g1 + g2 + 8) throw SerializationError("IoError: unexpected end of input");
+        Proof r;
+        const uint8_t* p = b.data();
+        r.a = points_from_wire(1, p, 1, compress, validate); p += g1;
+        r.b = points_from_wire(2, p, 1, compress, validate); p += g2;
+        r.c = points_from_wire(1, p, 1, compress, validate); p += g1;
+        uint64_t nd = get_u64(p); p += 8;
+        if (b.size() != 2 * g1 + g2 + 8 + nd * g1) throw SerializationError("IoError: wrong length");
+        for (uint64_t i = 0; i < nd; i++, p += g1) r.ds.push_back(points_from_wire(1, p, 1, compress, validate));
+        return r;
     }
     Bytes stage0_response_to_wire(const Stage0Response& r) const {              // 8 + 96 + 32 = 136 bytes
         Bytes w;

@@ -120,4 +120,15 @@ struct VerifyRun {
     static size_t max_private_bytes();
 };
 
+// compressed points (point_codec.cuh): the hk_field_sqrt / hk_points_decompress_* / hk_points_compress_* entry points of a
+// curve; explicit instantiation in hk_<curve>_codec.hip
+template <class P>
+struct CodecRun {
+    static hk_status field_sqrt(hk_ctx*, int which, const void* in, size_t n, void* out, unsigned char* ok);
+    static hk_status points_decompress(hk_ctx*, int group, const void* x_canon, const unsigned char* flags, size_t n, int check,
+                                       void* points_out, unsigned char* status);
+    static hk_status points_compress(hk_ctx*, int group, const void* points, size_t n, void* x_canon_out, unsigned char* flags_out);
+    static size_t max_private_bytes();
+};
+
 }  // namespace hk

@@ -440,6 +440,32 @@ hk_status hk_verify_batch(hk_ctx* ctx, const hk_vk* vk, const void* a_g1, const 
 hk_status hk_points_check_g1(hk_ctx* ctx, const void* points, size_t n, uint8_t* ok);
 hk_status hk_points_check_g2(hk_ctx* ctx, const void* points, size_t n, uint8_t* ok);
 
+/* ---- compressed points (ark-serialize's second wire form: x and a sign flag, half the bytes) ---------------------------
+ * Every array is [h|d]; calls are thread-safe on a shared context.  HK_ERR_ARG, with nothing written, for: a NULL pointer
+ * with n > 0, `which` outside {1, 2}, n >= 2^31, an input range that shares a byte with an output range (or two outputs that
+ * do).  n == 0 is HK_OK and writes nothing.
+ *
+ * hk_field_sqrt: square roots in the coordinate fields (which: 1 = Fq, 2 = Fq2; both curves have q = 3 mod 4).  in_mont n
+ * elements (Montgomery); out_mont[i] = the root r of in[i] that is not larger than -r, or zero where in[i] is no square;
+ * ok[i] = 1 / 0.  "Larger" is ark's order, on canonical values: r > (q - 1) / 2 in Fq; in Fq2 decided on c1 unless c1 == 0,
+ * then on c0.  Fr is out of scope: its two-adicity is 28, so its roots need Tonelli-Shanks, and nothing on the wire needs them.
+ *
+ * hk_points_decompress_g1 / _g2 replace ark-ec's `get_point_from_x_unchecked` + `SWFlags` under `deserialize_compressed`
+ * (and, with check != 0, the `check()` of its Validate::Yes form):
+ *   x_canon n coordinates, canonical little-endian (G2: c0 || c1); flags n bytes, bit 0 = infinity, bit 1 = y is the larger of
+ *   (y, -y); points_out n packed affine Montgomery points - y the root of x^3 + b the flag names, infinity all zeros;
+ *   status n bytes: 1 ok | 0 x is not below q or x^3 + b is no square (the point is zeros) | 2 - only when check != 0 - on the
+ *   curve but outside the prime-order subgroup (the point is still written).
+ * hk_points_compress_g1 / _g2 are the inverse and replace `SWFlags::from_y_coordinate` + the x of `serialize_compressed`:
+ *   points n packed affine -> x_canon_out, flags_out as above.  No curve check: y only decides the flag. */
+hk_status hk_field_sqrt(hk_ctx* ctx, int which, const void* in_mont, size_t n, void* out_mont, uint8_t* ok);
+hk_status hk_points_decompress_g1(hk_ctx* ctx, const void* x_canon, const uint8_t* flags, size_t n, int check,
+                                  void* points_out, uint8_t* status);
+hk_status hk_points_decompress_g2(hk_ctx* ctx, const void* x_canon, const uint8_t* flags, size_t n, int check,
+                                  void* points_out, uint8_t* status);
+hk_status hk_points_compress_g1(hk_ctx* ctx, const void* points, size_t n, void* x_canon_out, uint8_t* flags_out);
+hk_status hk_points_compress_g2(hk_ctx* ctx, const void* points, size_t n, void* x_canon_out, uint8_t* flags_out);
+
 /* ---- trusted setup past synthesis (cp-groth16/src/generator.rs:66-224) ---------------------------------------------
  * Both entries take the class's matrices in the hk_csr form of hk_witness_map / hk_pk_upload ([h|d]).  Errors, checked in
  * this order: HK_ERR_DOMAIN_TOO_LARGE when log2(m) exceeds the curve's two-adicity (from the sizes alone, before any array
