@@ -333,11 +333,11 @@ class DeviceView(DeviceBuffer):
         pass
 
 
-# ---- what the job entries' wrappers share -------------------------------------------------------------------------------
-def _hd(x):
+# ---- what the wrappers share -------------------------------------------------------------------------------------------
+def _hd(x, dtype=np.uint8):
     """A host-or-device operand as the library reads it: a DeviceBuffer (or None, an absent one) as it is, anything else as
-    contiguous bytes.  The caller keeps the result alive over the call."""
-    return x if x is None or isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8)
+    a contiguous array of `dtype` (bytes, unless the entry reads words).  The caller keeps the result alive over the call."""
+    return x if x is None or isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=dtype)
 
 
 def _nullable(x):
@@ -348,6 +348,11 @@ def _nullable(x):
     if isinstance(x, DeviceBuffer):
         return x.ptr if x.nbytes else None
     return x.ctypes.data if x.size else None
+
+
+def _ptr_array(xs):
+    """The addresses of numpy arrays and DeviceBuffers as a c_void_p array, each as _nullable gives it; never of length 0."""
+    return (C.c_void_p * max(len(xs), 1))(*[_nullable(x) for x in xs])
 
 
 def _device_addr(z):
@@ -439,9 +444,9 @@ class Context:
         pb = self.g1_bytes if group == 1 else self.g2_bytes
         n = n if n is not None else len(scalars) // self.fr_bytes
         fn = self.lib.hk_fixed_base_g1 if group == 1 else self.lib.hk_fixed_base_g2
-        base = np.ascontiguousarray(base, dtype=np.uint8)
+        base = _hd(base)
         res = out if out is not None else np.zeros(n * pb, dtype=np.uint8)
-        check(fn(self.handle, base.ctypes.data, ptr(scalars), n, int(montgomery), ptr(res)), fn.__name__)
+        check(fn(self.handle, ptr(base), ptr(scalars), n, int(montgomery), ptr(res)), fn.__name__)
         return res
 
     def scalar_pairing(self, group, points, scalars, n=None, out=None):
@@ -482,22 +487,20 @@ class Context:
         """hk_gt_pow: element-wise powers in GT (the exponent split along the Frobenius - the bases must have order r);
         in_gt=False: hk_fq12_pow, the plain chain for values of unknown provenance (a verifier's inputs).
         gts: (n, gt_bytes) uint8; scalars: n Fr Montgomery bytes."""
-        gts = np.ascontiguousarray(gts, dtype=np.uint8).reshape(-1, self.gt_bytes)
-        scalars = np.ascontiguousarray(scalars, dtype=np.uint8)
-        out = np.zeros_like(gts)
+        gts, scalars = _hd(gts), _hd(scalars)
+        out = np.zeros((gts.nbytes // self.gt_bytes, self.gt_bytes), dtype=np.uint8)
         fn = self.lib.hk_gt_pow if in_gt else self.lib.hk_fq12_pow
-        check(fn(self.handle, gts.ctypes.data, scalars.ctypes.data, gts.shape[0], out.ctypes.data), fn.__name__)
+        check(fn(self.handle, ptr(gts), ptr(scalars), out.shape[0], out.ctypes.data), fn.__name__)
         return out
 
     def gt_pow_prod(self, gts, scalars, group_len, in_gt=True):
         """hk_gt_pow_prod: out[g] = prod_j gts[g * group_len + j]^scalars[g * group_len + j] (a verifier's
         multi-exponentiations).  Returns (n / group_len, gt_bytes) uint8."""
-        gts = np.ascontiguousarray(gts, dtype=np.uint8).reshape(-1, self.gt_bytes)
-        scalars = np.ascontiguousarray(scalars, dtype=np.uint8)
-        n = gts.shape[0]
+        gts, scalars = _hd(gts), _hd(scalars)
+        n = gts.nbytes // self.gt_bytes
         out = np.zeros((n // max(1, group_len), self.gt_bytes), dtype=np.uint8)
-        check(self.lib.hk_gt_pow_prod(self.handle, gts.ctypes.data, scalars.ctypes.data, n, group_len, 1 if in_gt else 0,
-                                      out.ctypes.data), "hk_gt_pow_prod")
+        check(self.lib.hk_gt_pow_prod(self.handle, ptr(gts), ptr(scalars), n, group_len, 1 if in_gt else 0, out.ctypes.data),
+              "hk_gt_pow_prod")
         return out
 
     def multi_pairing(self, g1, g2, n=None):
@@ -513,10 +516,8 @@ class Context:
         """Every G1 vector of `lhs` against every G2 vector of `rhs` in one batched launch (the `cross_terms` of
         aggregation.rs:255-263): returns a (len(lhs), len(rhs), gt_bytes) uint8 array."""
         n = n if n is not None else len(lhs[0]) // self.g1_bytes
-        keep = [x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8) for x in list(lhs) + list(rhs)]
-        addr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x.ctypes.data
-        lp = (C.c_void_p * len(lhs))(*[addr(x) for x in keep[:len(lhs)]])
-        rp = (C.c_void_p * len(rhs))(*[addr(x) for x in keep[len(lhs):]])
+        lhs, rhs = [_hd(x) for x in lhs], [_hd(x) for x in rhs]
+        lp, rp = _ptr_array(lhs), _ptr_array(rhs)
         out = np.zeros((len(lhs), len(rhs), self.gt_bytes), dtype=np.uint8)
         check(self.lib.hk_pairing_products(self.handle, lp, len(lhs), rp, len(rhs), n, out.ctypes.data),
               "hk_pairing_products")
@@ -526,10 +527,8 @@ class Context:
         """pairing(lhs[a], rhs[b]) for each (a, b) of `pairs` in one batched launch (hk_pairing_pairs: the cross terms of a
         GIPA round): returns a (len(pairs), gt_bytes) uint8 array."""
         n = n if n is not None else len(lhs[0]) // self.g1_bytes
-        keep = [x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8) for x in list(lhs) + list(rhs)]
-        addr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x.ctypes.data
-        lp = (C.c_void_p * len(lhs))(*[addr(x) for x in keep[:len(lhs)]])
-        rp = (C.c_void_p * len(rhs))(*[addr(x) for x in keep[len(lhs):]])
+        lhs, rhs = [_hd(x) for x in lhs], [_hd(x) for x in rhs]
+        lp, rp = _ptr_array(lhs), _ptr_array(rhs)
         pa = (C.c_uint32 * len(pairs))(*[a for a, _ in pairs])
         pb = (C.c_uint32 * len(pairs))(*[b for _, b in pairs])
         out = np.zeros((len(pairs), self.gt_bytes), dtype=np.uint8)
@@ -541,61 +540,51 @@ class Context:
         """out[i] = sum_j coeffs[j] * vecs[j][i] (aggregation.rs:192-203,293-326); coeffs: k Fr Montgomery bytes."""
         pb = self.g1_bytes if group == 1 else self.g2_bytes
         n = n if n is not None else len(vecs[0]) // pb
-        keep = [x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8) for x in vecs]
-        vp_ = (C.c_void_p * len(keep))(*[x.ptr if isinstance(x, DeviceBuffer) else x.ctypes.data for x in keep])
-        coeffs = np.ascontiguousarray(coeffs, dtype=np.uint8)
+        vecs, coeffs = [_hd(x) for x in vecs], _hd(coeffs)
         out = np.zeros(n * pb, dtype=np.uint8)
         fn = self.lib.hk_points_lincomb_g1 if group == 1 else self.lib.hk_points_lincomb_g2
-        check(fn(self.handle, vp_, coeffs.ctypes.data, len(keep), n, out.ctypes.data), fn.__name__)
+        check(fn(self.handle, _ptr_array(vecs), ptr(coeffs), len(vecs), n, out.ctypes.data), fn.__name__)
         return out
+
+    def _fold_coeffs(self, group, c):
+        """The scalar c (an int mod r) split along the group's endomorphism (endo.Phi2 in G1, endo.Psi4 in G2): the parts'
+        magnitudes as Montgomery bytes and the mask of the negative ones."""
+        from .cp_groth16 import FrCodec
+        from .endo import phi2, psi4
+        k = (phi2 if group == 1 else psi4)(self.curve).decompose(c)
+        neg = sum(1 << j for j, v in enumerate(k) if v < 0)
+        return np.ascontiguousarray(FrCodec(self.curve).enc([abs(v) for v in k]), dtype=np.uint8), neg
+
+    def _points_fold(self, group, lo, hi, c, n, out):
+        pb = self.g1_bytes if group == 1 else self.g2_bytes
+        n = n if n is not None else len(hi) // pb
+        coeffs, neg = self._fold_coeffs(group, c)
+        lo, hi = _hd(lo), _hd(hi)
+        res = out if out is not None else np.zeros(n * pb, dtype=np.uint8)                      # a DeviceBuffer stays in HBM
+        fn = self.lib.hk_points_fold_g1 if group == 1 else self.lib.hk_points_fold_g2
+        check(fn(self.handle, ptr(lo), ptr(hi), coeffs.ctypes.data, neg, n, ptr(res)), fn.__name__)
+        return res
 
     def points_fold_g2(self, lo, hi, c, n=None, out=None):
         """out[i] = lo[i] + c * hi[i] in G2 (the fold of a TIPA round) through hk_points_fold_g2: the scalar c (an int mod r)
         is split along the endomorphism psi into four ~64-bit parts (endo.Psi4), so the element-wise double-and-add chain is
         ~66 steps instead of 254."""
-        from .cp_groth16 import FrCodec
-        from .endo import psi4
-        n = n if n is not None else len(hi) // self.g2_bytes
-        k = psi4(self.curve).decompose(c)
-        neg = sum(1 << j for j, v in enumerate(k) if v < 0)
-        coeffs = np.ascontiguousarray(FrCodec(self.curve).enc([abs(v) for v in k]), dtype=np.uint8)
-        lo_, hi_ = (x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8) for x in (lo, hi))
-        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x.ctypes.data
-        res = out if out is not None else np.zeros(n * self.g2_bytes, dtype=np.uint8)          # a DeviceBuffer stays in HBM
-        check(self.lib.hk_points_fold_g2(self.handle, ptr(lo_), ptr(hi_), coeffs.ctypes.data, neg, n,
-                                         res.ptr if isinstance(res, DeviceBuffer) else res.ctypes.data), "hk_points_fold_g2")
-        return res
+        return self._points_fold(2, lo, hi, c, n, out)
 
     def points_fold_g1(self, lo, hi, c, n=None, out=None):
         """out[i] = lo[i] + c * hi[i] in G1 through hk_points_fold_g1: c split along the GLV endomorphism into two ~128-bit
         parts (endo.Phi2)."""
-        from .cp_groth16 import FrCodec
-        from .endo import phi2
-        n = n if n is not None else len(hi) // self.g1_bytes
-        k = phi2(self.curve).decompose(c)
-        neg = sum(1 << j for j, v in enumerate(k) if v < 0)
-        coeffs = np.ascontiguousarray(FrCodec(self.curve).enc([abs(v) for v in k]), dtype=np.uint8)
-        lo_, hi_ = (x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8) for x in (lo, hi))
-        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x.ctypes.data
-        res = out if out is not None else np.zeros(n * self.g1_bytes, dtype=np.uint8)          # a DeviceBuffer stays in HBM
-        check(self.lib.hk_points_fold_g1(self.handle, ptr(lo_), ptr(hi_), coeffs.ctypes.data, neg, n,
-                                         res.ptr if isinstance(res, DeviceBuffer) else res.ctypes.data), "hk_points_fold_g1")
-        return res
+        return self._points_fold(1, lo, hi, c, n, out)
 
     def points_fold_many(self, group, los, his, c, n, outs):
         """outs[y][i] = los[y][i] + c * his[y][i] for up to 4 vector pairs and one scalar c (hk_points_fold_many_g1 / _g2):
         the folds of one TIPA round that share a challenge.  los / his: DeviceBuffer / DeviceView or uint8 arrays; outs:
         DeviceBuffer / DeviceView (stay in HBM) or uint8 arrays of n points each."""
-        from .cp_groth16 import FrCodec
-        from .endo import phi2, psi4
-        k = (phi2 if group == 1 else psi4)(self.curve).decompose(c)
-        neg = sum(1 << j for j, v in enumerate(k) if v < 0)
-        coeffs = np.ascontiguousarray(FrCodec(self.curve).enc([abs(v) for v in k]), dtype=np.uint8)
-        keep = [[x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8) for x in xs] for xs in (los, his)]
-        ptr = lambda x: x.ptr if isinstance(x, DeviceBuffer) else x.ctypes.data
-        arr = lambda xs: (C.c_void_p * len(xs))(*[ptr(x) for x in xs])
+        coeffs, neg = self._fold_coeffs(group, c)
+        los, his = [_hd(x) for x in los], [_hd(x) for x in his]
         fn = self.lib.hk_points_fold_many_g1 if group == 1 else self.lib.hk_points_fold_many_g2
-        check(fn(self.handle, len(outs), arr(keep[0]), arr(keep[1]), coeffs.ctypes.data, neg, n, arr(outs)), fn.__name__)
+        check(fn(self.handle, len(outs), _ptr_array(los), _ptr_array(his), coeffs.ctypes.data, neg, n, _ptr_array(outs)),
+              fn.__name__)
         return outs
 
     def assignment_from_bits(self, bits, full_cols, full_vals, out=None):
@@ -629,10 +618,9 @@ class Context:
             siblings = np.ascontiguousarray(siblings, dtype=np.uint8).reshape(batch, -1)
             depth = siblings.shape[1] // self.fr_bytes
         a, b = hk_poseidon_desc(*ld), hk_poseidon_desc(*nd)
-        zp = z_out.ptr if isinstance(z_out, DeviceBuffer) else int(z_out)
         check(self.lib.hk_poseidon_path(self.handle, ptr(consts), int(n_consts), C.byref(a), C.byref(b), ptr(leaf),
                                         ptr(siblings) if depth else None, index.ctypes.data, depth, batch, int(n_v),
-                                        int(col0), zp), "hk_poseidon_path")
+                                        int(col0), _device_addr(z_out)), "hk_poseidon_path")
 
     def wprog_upload(self, ops, refs, vmap, n_values, n_inputs):
         """hk_wprog_upload: a class's word program (sha_circuit.Tape.word_program) resident on the device."""
@@ -696,13 +684,11 @@ class Context:
         """hk_csr structs over (row_ptr, col, val) triples; each member a numpy array (host) or a DeviceBuffer (device)."""
         out = []
         for (rp, col, val) in matrices:
-            arrs = [x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=dt)
-                    for x, dt in ((rp, np.uint64), (col, np.uint32), (val, np.uint8))]
+            arrs = [_hd(rp, np.uint64), _hd(col, np.uint32), _hd(val)]
             keep += arrs
             n_rows = arrs[0].nbytes // 8 - 1
             nnz = arrs[1].nbytes // 4
-            out.append(hk_csr(*[ptr(x).value if (x.nbytes if isinstance(x, DeviceBuffer) else x.size) else None
-                                for x in arrs], n_rows, nnz))
+            out.append(hk_csr(*[_nullable(x) for x in arrs], n_rows, nnz))
         return out
 
     def qap_eval(self, A, B, Cm, n_inst, n_constraints, n_v, t, out=None):
@@ -753,11 +739,10 @@ class Context:
         keep += [sr, dl] + sc
         d = hk_keygen_desc(C.pointer(csrs[0]), C.pointer(csrs[1]), C.pointer(csrs[2]), n_inst, n_constraints, n_v,
                            sr.ctypes.data if ns else None, ns, *[x.ctypes.data for x in sc], dl.ctypes.data if ns else None)
-        ckp = (C.c_void_p * max(ns, 1))(*[ptr(x).value if x.size else None for x in res["ck"]])
-        pp = lambda x: ptr(x).value if (x.nbytes if isinstance(x, DeviceBuffer) else x.size) else None
-        o = hk_keygen_out(pp(res["a_g"]), pp(res["b_g"]), pp(res["b_h"]), pp(res["h_g"]), ckp,
-                          *[pp(res[k]) for k in ("deltas_g", "alpha_g", "beta_g", "gamma_abc_g", "beta_h", "gamma_h",
-                                                 "deltas_h")], pp(res["qap_abc"]) if with_qap else None)
+        ckp = _ptr_array(res["ck"])
+        o = hk_keygen_out(*[_nullable(res[k]) for k in ("a_g", "b_g", "b_h", "h_g")], ckp,
+                          *[_nullable(res[k]) for k in ("deltas_g", "alpha_g", "beta_g", "gamma_abc_g", "beta_h", "gamma_h",
+                                                        "deltas_h")], _nullable(res.get("qap_abc")))
         m_out = C.c_size_t()
         try:
             check(self.lib.hk_keygen(self.handle, C.byref(d), C.byref(o), C.byref(m_out)), "hk_keygen")

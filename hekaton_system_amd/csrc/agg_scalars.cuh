@@ -318,22 +318,21 @@ hk_status Ops<C>::scalar_powers(hk_ctx* ctx, const void* x_mont, size_t n, size_
     const u32 n_chunks = (u32)((n + AQ_CHUNK - 1) / AQ_CHUNK);
     u32 nbits = 0;
     while (((u64)1 << nbits) < n_chunks) nbits++;
-    const bool dev = is_device_ptr(out);
+    Staged to = staged(out, reps * n * sizeof(Fr));
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    Fr *tab_d, *stage = nullptr;
+    Fr* tab_d;
     HK_TRY(L->carve([&](Carve& c) {
         tab_d = c.n<Fr>(AQ_PW_LEN);
-        if (!dev) stage = c.n<Fr>(reps * n);
+        stage_carve(c, &to, 1);
     }));
     hipStream_t s = L->stream;
     HK_HIP(hipMemcpyAsync(tab_d, tab, sizeof(tab), hipMemcpyHostToDevice, s));
-    Fr* dst = dev ? (Fr*)out : stage;
     hipLaunchKernelGGL((k_powers<Fr>), dim3((n_chunks + 255) / 256, (u32)reps), dim3(256), 0, s, (const Fr*)tab_d, n_chunks, nbits,
-                       (u64)n, dst);
+                       (u64)n, (Fr*)to.p);
     HK_HIP(hipGetLastError());
-    if (!dev) HK_HIP(hipMemcpyAsync(out, stage, reps * n * sizeof(Fr), hipMemcpyDeviceToHost, s));
+    HK_TRY(stage_download(L, &to, 1));
     return L->settle();                                                     // `tab` is read until here
 }
 
@@ -357,22 +356,22 @@ hk_status Ops<C>::ipa_quotient(hk_ctx* ctx, const void* challenges_mont, size_t 
     std::vector<Fr> tab(AQ_LEN);
     aq_quotient_table<Fr>(ch, sh.l, rho, z, fused ? 0 : per, tab.data());
     const size_t n_tab = fused ? AQ_QP : AQ_LEN;
-    const bool dev = is_device_ptr(q_out);
+    Staged to = staged(q_out, sh.len * sizeof(Fr));
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    Fr *tab_d, *part = nullptr, *tops = nullptr, *stage = nullptr;
+    Fr *tab_d, *part = nullptr, *tops = nullptr;
     HK_TRY(L->carve([&](Carve& c) {
         tab_d = c.n<Fr>(n_tab);
         if (!fused) {
             part = c.n<Fr>(sh.n_chunks);
             tops = c.n<Fr>(n_tiles);
         }
-        if (!dev) stage = c.n<Fr>(sh.len);
+        stage_carve(c, &to, 1);
     }));
     hipStream_t s = L->stream;
     HK_HIP(hipMemcpyAsync(tab_d, tab.data(), n_tab * sizeof(Fr), hipMemcpyHostToDevice, s));
-    Fr* q = dev ? (Fr*)q_out : stage;
+    Fr* q = (Fr*)to.p;
     const Fr* tp = tab_d;
     if (fused) {
         hipLaunchKernelGGL((k_ipaq_tail<Fr>), dim3(1), dim3(AQ_TILE), 0, s, tp, sh, q);
@@ -383,7 +382,7 @@ hk_status Ops<C>::ipa_quotient(hk_ctx* ctx, const void* challenges_mont, size_t 
         hipLaunchKernelGGL((k_ipaq_walk<Fr>), dim3(n_tiles), dim3(AQ_TILE), 0, s, tp, sh, (const Fr*)part, (const Fr*)tops, q);
     }
     HK_HIP(hipGetLastError());
-    if (!dev) HK_HIP(hipMemcpyAsync(q_out, stage, sh.len * sizeof(Fr), hipMemcpyDeviceToHost, s));
+    HK_TRY(stage_download(L, &to, 1));
     return L->settle();                                                     // `tab` is read until here
 }
 

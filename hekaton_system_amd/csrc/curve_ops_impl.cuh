@@ -90,6 +90,7 @@ struct Ops final : CurveOps {
         if (n == 0) { memset(out, 0, sizeof(Affine<F>)); return HK_OK; }
         if (!bases || !scalars) return HK_ERR_ARG;
         if (n >= (1u << 26)) return HK_ERR_ARG;
+        Staged in[2] = {staged(scalars, n * sizeof(Fr)), staged(bases, n * sizeof(Affine<F>))};
         LaneGuard g(ctx);
         Lane* L = g.lane;
         if (!L) return HK_ERR_DEVICE;
@@ -100,11 +101,9 @@ struct Ops final : CurveOps {
             p = msm_make_plan((u32)n, C::FR_BITS, msm_pick_c_plain(n, C::FR_BITS), 0xffffffffu, ctx->max_lanes0, C::Fr::Params::MOD,
                               C::Fr::Params::N);
         OneMsm<F> msm{small, &p, (u32)n};
-        const void *sc_d, *b_d;
-        HK_TRY(L->carve([&](Carve& c) { sc_d = c.take(n * sizeof(Fr)); b_d = c.take(n * sizeof(Affine<F>)); msm.carve(c); }));
-        HK_TRY(to_device(L, scalars, n * sizeof(Fr), &sc_d));
-        HK_TRY(to_device(L, bases, n * sizeof(Affine<F>), &b_d));
-        HK_TRY(msm.run(L->stream, (const Affine<F>*)b_d, sc_d, mont, out, hipMemcpyDeviceToHost));
+        HK_TRY(L->carve([&](Carve& c) { stage_carve(c, in, 2); msm.carve(c); }));
+        HK_TRY(stage_upload(L, in, 2));
+        HK_TRY(msm.run(L->stream, (const Affine<F>*)in[1].p, in[0].p, mont, out, hipMemcpyDeviceToHost));
         return L->settle();
     }
 

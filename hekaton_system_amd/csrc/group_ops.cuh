@@ -76,24 +76,23 @@ hk_status Ops<C>::msm_bases(hk_ctx* ctx, const hk_bases* h, const void* scalars,
         typedef decltype(ftag) F;
         if (n == 0) { memset(out, 0, sizeof(Affine<F>)); return HK_OK; }
         if (!scalars) return HK_ERR_ARG;
-        LaneGuard g(ctx);
-        Lane* L = g.lane;
-        if (!L) return HK_ERR_DEVICE;
         // a short G2 MSM: even with the tables' bucket pass free of a Horner tail, n element-wise products over psi + one sum
         // are quicker (1.9 - 2.4 ms against 2.3 - 3.0; G1 stays with the tables: 1.0 - 1.2 ms against 1.4 - 1.5)
         const bool small = !b->has_tables || (sizeof(F) > sizeof(Fq) && n <= 2048 && !getenv("HK_MSM_NO_SMALL"));
+        Staged in = staged(small ? scalars : nullptr, n * sizeof(Fr));   // the bucket pass copies into a buffer of its own
+        LaneGuard g(ctx);
+        Lane* L = g.lane;
+        if (!L) return HK_ERR_DEVICE;
         OneMsm<F> msm{small, &b->plan, small ? (u32)n : b->n};     // the bucket pass is planned for b->n scalars
         Fr* sc;
-        HK_TRY(L->carve([&](Carve& c) { sc = c.n<Fr>(msm.n); msm.carve(c); }));
+        HK_TRY(L->carve([&](Carve& c) { stage_carve(c, &in, 1); sc = c.n<Fr>(small ? 0 : msm.n); msm.carve(c); }));
         hipStream_t s = L->stream;
-        const void* sc_d = sc;
-        if (small)
-            HK_TRY(to_device(L, scalars, n * sizeof(Fr), &sc_d));
-        else {                                                       // the tail reads zeros
+        HK_TRY(stage_upload(L, &in, 1));
+        if (!small) {                                                // the tail reads zeros
             HK_HIP(hipMemcpyAsync(sc, scalars, n * sizeof(Fr), h2d_kind(scalars), s));
             if (n < b->n) HK_HIP(hipMemsetAsync(sc + n, 0, (b->n - n) * sizeof(Fr), s));
         }
-        HK_TRY(msm.run(s, (const Affine<F>*)b->tab, sc_d, mont, out,                  // group 0 of the table = the bases
+        HK_TRY(msm.run(s, (const Affine<F>*)b->tab, small ? in.p : sc, mont, out,    // group 0 of the table = the bases
                        is_device_ptr(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
         return L->settle();
     };
@@ -151,36 +150,34 @@ hk_status Ops<C>::fixed_base(hk_ctx* ctx, int group, const void* base, const voi
                              void* out) {
     if (n == 0) return HK_OK;
     if (n >= (1u << 30)) return HK_ERR_ARG;
+    const size_t pt = group == 1 ? g1_bytes : g2_bytes;
+    Staged in[2] = {staged(base, pt), staged(scalars, n * sizeof(Fr))}, to = staged(out, n * pt);
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
     auto run = [&](auto ftag) -> hk_status {
         typedef decltype(ftag) F;
-        const void *bd, *sd;
-        Affine<F>*tab_s, *out_s;
+        Affine<F>* tab_s;
         XYZZ<F>* xy;
         F* pref;
         HK_TRY(L->carve([&](Carve& c) {
-            bd = c.take(sizeof(Affine<F>));
-            sd = c.take(n * sizeof(Fr));
+            stage_carve(c, in, 2);
             tab_s = c.n<Affine<F>>(FB_WINDOWS * 256);
             xy = c.n<XYZZ<F>>(n);
             pref = c.n<F>(n);
-            out_s = c.n<Affine<F>>(n);
+            stage_carve(c, &to, 1);
         }));
         // the base's window table: from the context's cache when this base has been multiplied before (host bases only: the
         // key is the base's bytes), else built now - into a cache slot when one is free, into the lane's scratch otherwise
         const size_t tbytes = sizeof(Affine<F>) * FB_WINDOWS * 256;
-        FbCacheUse claimed(ctx, group, is_device_ptr(base) ? nullptr : base, sizeof(Affine<F>), tbytes);
+        FbCacheUse claimed(ctx, group, in[0].scratch ? base : nullptr, sizeof(Affine<F>), tbytes);
         Affine<F>* table = (Affine<F>*)claimed.table;
         bool build = claimed.build;
-        HK_TRY(to_device(L, base, sizeof(Affine<F>), &bd));
-        HK_TRY(to_device(L, scalars, n * sizeof(Fr), &sd));
+        HK_TRY(stage_upload(L, in, 2));
         if (!table) table = tab_s;
-        bool out_dev = is_device_ptr(out);
-        Affine<F>* od = out_dev ? (Affine<F>*)out : out_s;
-        HK_TRY(MsmRun<F>::fixed_base(L->stream, (const Affine<F>*)bd, sd, mont, (u32)n, table, xy, pref, od, build));
-        if (!out_dev) HK_HIP(hipMemcpyAsync(out, od, n * sizeof(Affine<F>), hipMemcpyDeviceToHost, L->stream));
+        HK_TRY(MsmRun<F>::fixed_base(L->stream, (const Affine<F>*)in[0].p, in[1].p, mont, (u32)n, table, xy, pref,
+                                     (Affine<F>*)to.p, build));
+        HK_TRY(stage_download(L, &to, 1));
         HK_TRY(L->settle());
         claimed.publish();                                       // the table is complete: later calls may read it
         return HK_OK;
@@ -193,29 +190,25 @@ hk_status Ops<C>::scalar_pairing(hk_ctx* ctx, int group, const void* points, con
                                  void* out) {
     if (n == 0) return HK_OK;
     if (n >= (1u << 28)) return HK_ERR_ARG;
+    const size_t pt = group == 1 ? g1_bytes : g2_bytes;
+    Staged in[2] = {staged(points, n * pt), staged(scalars, n * sizeof(Fr))}, to = staged(out, n * pt);
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
     auto run = [&](auto ftag) -> hk_status {
         typedef decltype(ftag) F;
-        const void *pd, *sd;
         XYZZ<F>*xy, *tab;
         F* pref;
-        Affine<F>* out_s;
         HK_TRY(L->carve([&](Carve& c) {
-            pd = c.take(n * sizeof(Affine<F>));
-            sd = c.take(n * sizeof(Fr));
+            stage_carve(c, in, 2);
             xy = c.n<XYZZ<F>>(n);
             pref = c.n<F>(n);
             tab = (XYZZ<F>*)c.take(endo_tab_bytes<F>(n));            // the chains' tables (endo.cuh)
-            out_s = c.n<Affine<F>>(n);
+            stage_carve(c, &to, 1);
         }));
-        HK_TRY(to_device(L, points, n * sizeof(Affine<F>), &pd));
-        HK_TRY(to_device(L, scalars, n * sizeof(Fr), &sd));
-        bool out_dev = is_device_ptr(out);
-        Affine<F>* od = out_dev ? (Affine<F>*)out : out_s;
-        HK_TRY(MsmRun<F>::scalar_mul_each(L->stream, (const Affine<F>*)pd, sd, (u32)n, xy, pref, od, tab));
-        if (!out_dev) HK_HIP(hipMemcpyAsync(out, od, n * sizeof(Affine<F>), hipMemcpyDeviceToHost, L->stream));
+        HK_TRY(stage_upload(L, in, 2));
+        HK_TRY(MsmRun<F>::scalar_mul_each(L->stream, (const Affine<F>*)in[0].p, in[1].p, (u32)n, xy, pref, (Affine<F>*)to.p, tab));
+        HK_TRY(stage_download(L, &to, 1));
         return L->settle();
     };
     return group == 1 ? run(Fq()) : run(Fq2());
@@ -227,33 +220,28 @@ hk_status Ops<C>::points_lincomb(hk_ctx* ctx, int group, const void* const* vecs
     if (n == 0) return HK_OK;
     if (k == 0 || k > (size_t)LINCOMB_MAX || n >= (1u << 28)) return HK_ERR_ARG;
     for (size_t j = 0; j < k; j++) if (!vecs[j]) return HK_ERR_ARG;
+    const size_t pt = group == 1 ? g1_bytes : g2_bytes;
+    Staged in[LINCOMB_MAX + 1], to = staged(out, n * pt);         // the k vectors, then the coefficients
+    for (size_t j = 0; j < k; j++) in[j] = staged(vecs[j], n * pt);
+    in[k] = staged(coeffs, k * sizeof(Fr));
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
     auto run = [&](auto ftag) -> hk_status {
         typedef decltype(ftag) F;
         const Affine<F>* dv[LINCOMB_MAX];
-        const void* cd;
         XYZZ<F>* xy;
         F* pref;
-        Affine<F>* out_s;
         HK_TRY(L->carve([&](Carve& c) {
-            for (size_t j = 0; j < k; j++) dv[j] = c.n<Affine<F>>(n);
-            cd = c.take(k * sizeof(Fr));
+            stage_carve(c, in, k + 1);
             xy = c.n<XYZZ<F>>(n);
             pref = c.n<F>(n);
-            out_s = c.n<Affine<F>>(n);
+            stage_carve(c, &to, 1);
         }));
-        for (size_t j = 0; j < k; j++) {
-            const void* d = dv[j];
-            HK_TRY(to_device(L, vecs[j], n * sizeof(Affine<F>), &d));
-            dv[j] = (const Affine<F>*)d;
-        }
-        HK_TRY(to_device(L, coeffs, k * sizeof(Fr), &cd));
-        bool out_dev = is_device_ptr(out);
-        Affine<F>* od = out_dev ? (Affine<F>*)out : out_s;
-        HK_TRY(MsmRun<F>::lincomb(L->stream, dv, cd, (u32)k, (u32)n, xy, pref, od));
-        if (!out_dev) HK_HIP(hipMemcpyAsync(out, od, n * sizeof(Affine<F>), hipMemcpyDeviceToHost, L->stream));
+        for (size_t j = 0; j < k; j++) dv[j] = (const Affine<F>*)in[j].p;
+        HK_TRY(stage_upload(L, in, k + 1));
+        HK_TRY(MsmRun<F>::lincomb(L->stream, dv, in[k].p, (u32)k, (u32)n, xy, pref, (Affine<F>*)to.p));
+        HK_TRY(stage_download(L, &to, 1));
         return L->settle();
     };
     return group == 1 ? run(Fq()) : run(Fq2());
@@ -286,6 +274,14 @@ hk_status Ops<C>::points_fold(hk_ctx* ctx, size_t k, const void* const* lo, cons
     if (n == 0 || k == 0) return HK_OK;
     if (!lo || !hi || !coeffs || !out || k > (size_t)FOLD_MAX || n >= (1u << 28) / FOLD_MAX || neg_mask >= (1u << K)) return HK_ERR_ARG;
     for (size_t y = 0; y < k; y++) if (!lo[y] || !hi[y] || !out[y]) return HK_ERR_ARG;
+    Staged in[2 * FOLD_MAX];                                        // lo_0, hi_0, lo_1, hi_1, ...
+    for (size_t y = 0; y < k; y++) {
+        in[2 * y] = staged(lo[y], n * sizeof(Affine<F>));
+        in[2 * y + 1] = staged(hi[y], n * sizeof(Affine<F>));
+    }
+    const bool coeffs_dev = is_device_ptr(coeffs);
+    // one vector into a device buffer is normalised in place; otherwise into one array that is then handed out
+    const bool direct = k == 1 && is_device_ptr(out[0]);
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
@@ -295,30 +291,24 @@ hk_status Ops<C>::points_fold(hk_ctx* ctx, size_t k, const void* const* lo, cons
     F* pref;
     Affine<F>* out_s;
     HK_TRY(L->carve([&](Carve& c) {
-        for (size_t y = 0; y < k; y++) {
-            lod[y] = c.n<Affine<F>>(n);
-            hid[y] = c.n<Affine<F>>(n);
-        }
+        stage_carve(c, in, 2 * k);
         cd = c.n<Fr>(K);
         tab = (XYZZ<F>*)c.take(endo_tab_bytes<F>(n, k));
         xy = c.n<XYZZ<F>>(k * n);
         pref = c.n<F>(k * n);
-        out_s = c.n<Affine<F>>(k * n);
+        out_s = c.n<Affine<F>>(direct ? 0 : k * n);
     }));
     for (size_t y = 0; y < k; y++) {
-        const void *l = lod[y], *h = hid[y];
-        HK_TRY(to_device(L, lo[y], n * sizeof(Affine<F>), &l));
-        HK_TRY(to_device(L, hi[y], n * sizeof(Affine<F>), &h));
-        lod[y] = (const Affine<F>*)l;
-        hid[y] = (const Affine<F>*)h;
+        lod[y] = (const Affine<F>*)in[2 * y].p;
+        hid[y] = (const Affine<F>*)in[2 * y + 1].p;
     }
-    HK_HIP(hipMemcpyAsync(cd, coeffs, K * sizeof(Fr), is_device_ptr(coeffs) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                          L->stream));
+    HK_TRY(stage_upload(L, in, 2 * k));
+    HK_HIP(hipMemcpyAsync(cd, coeffs, K * sizeof(Fr), coeffs_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, L->stream));
     // the K-lane form of short vectors reads a magnitude up to 0x77..7 over ND nibbles (endo.cuh); a host caller's longer
     // one goes to the one-lane kernel, which is right for any magnitude.  Device-resident magnitudes are not inspected: the
     // bound is the caller's (include/hekaton.h)
     bool long_mags = false;
-    if (!is_device_ptr(coeffs)) {
+    if (!coeffs_dev) {
         HK_HIP(hipStreamSynchronize(L->stream));                              // a pageable caller buffer: done with it now
         for (int j = 0; j < K; j++) {
             Fr m;
@@ -327,8 +317,6 @@ hk_status Ops<C>::points_fold(hk_ctx* ctx, size_t k, const void* const* lo, cons
             if (!split_mag_fits<SplitDigits<F>::ND>(m.v)) long_mags = true;
         }
     }
-    // one vector into a device buffer is normalised in place; otherwise into one array that is then handed out
-    bool direct = k == 1 && is_device_ptr(out[0]);
     Affine<F>* od = direct ? (Affine<F>*)out[0] : out_s;
     HK_TRY(MsmRun<F>::fold_endo(L->stream, (u32)k, lod, hid, cd, neg_mask, (u32)n, tab, xy, pref, od, long_mags));
     if (!direct) {

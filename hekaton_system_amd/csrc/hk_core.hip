@@ -267,12 +267,6 @@ bool is_device_ptr(const void* p) {
     return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
 }
 
-hk_status to_device(Lane* L, const void* src, size_t bytes, const void** p) {
-    if (bytes == 0 || is_device_ptr(src)) { *p = src; return HK_OK; }
-    HK_HIP(hipMemcpyAsync((void*)*p, src, bytes, hipMemcpyHostToDevice, L->stream));
-    return HK_OK;
-}
-
 }  // namespace hk
 
 using namespace hk;

@@ -362,8 +362,6 @@ static inline float ev_ms(hipEvent_t a, hipEvent_t b) {
     if (hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void)hipGetLastError(); return 0.f; }
     return ms;
 }
-// *p: `bytes` of lane scratch carved for the input `src`.  A host `src` is copied there; a device `src` replaces *p.
-hk_status to_device(Lane* L, const void* src, size_t bytes, const void** p);
 
 // ---- a call's host-or-device buffers ----------------------------------------------------------
 // One record per input or output.  staged(): where the buffer lives is asked ONCE, before the carve - a device-resident or

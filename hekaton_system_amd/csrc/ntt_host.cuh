@@ -291,20 +291,20 @@ hk_status Ops<C>::witness_map(hk_ctx* ctx, const hk_csr* A, const hk_csr* B, con
     NttTables* T;
     HK_TRY(NttHost<C>::ensure(ctx, log_m, &T));
     R1csStage stage(A, B, Cm, n_v, sizeof(Fr));
+    Staged zin = staged(z, n_v * sizeof(Fr));
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void* zd;
     Fr* abc;
     HK_TRY(L->carve([&](Carve& c) {
         stage.carve(c);
-        zd = c.take(n_v * sizeof(Fr));
+        stage_carve(c, &zin, 1);
         abc = c.n<Fr>(3 * m);
     }));
     CsrDev D[3];
     HK_TRY(stage.upload(L, D));
-    HK_TRY(to_device(L, z, n_v * sizeof(Fr), &zd));
-    HK_TRY(Q::run(L->stream, T, D[0], D[1], D[2], n_inst, n_c, (const Fr*)zd, abc, log_m));
+    HK_TRY(stage_upload(L, &zin, 1));
+    HK_TRY(Q::run(L->stream, T, D[0], D[1], D[2], n_inst, n_c, (const Fr*)zin.p, abc, log_m));
     HK_TRY(NttHost<C>::bitrev(L->stream, abc, log_m));         // API returns natural order
     HK_HIP(hipMemcpyAsync(h_out, abc, m * sizeof(Fr),
                           is_device_ptr(h_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, L->stream));

@@ -100,28 +100,21 @@ hk_status Ops<C>::gt_pow(hk_ctx* ctx, const void* gt_in, const void* scalars, si
     // group_len > 1: out[g] = prod_{j < group_len} in[g * group_len + j]^scalars[...] (a verifier's multi-exponentiations)
     if (group_len == 0 || n % group_len != 0 || n / group_len > 65535) return HK_ERR_ARG;
     size_t n_out = n / group_len;
+    Staged in[2] = {staged(gt_in, n * sizeof(GT)), staged(scalars, n * sizeof(Fr))}, to = staged(gt_out, n_out * sizeof(GT));
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void *ind, *sd;
-    GT *pw_s, *od_s;
+    GT* pw;                                                        // the n powers: the output itself when group_len == 1
     HK_TRY(L->carve([&](Carve& c) {
-        ind = c.take(n * sizeof(GT));
-        sd = c.take(n * sizeof(Fr));
-        pw_s = c.n<GT>(n);
-        od_s = c.n<GT>(n_out);
+        stage_carve(c, in, 2);
+        pw = c.n<GT>(group_len > 1 ? n : 0);
+        stage_carve(c, &to, 1);
     }));
-    HK_TRY(to_device(L, gt_in, n * sizeof(GT), &ind));
-    HK_TRY(to_device(L, scalars, n * sizeof(Fr), &sd));
-    bool out_dev = is_device_ptr(gt_out);
-    GT* pw = (out_dev && group_len == 1) ? (GT*)gt_out : pw_s;
-    HK_TRY(PairRun<P>::gt_pow(L->stream, (const GT*)ind, sd, (u32)n, pw, in_gt != 0));
-    GT* od = pw;
-    if (group_len > 1) {
-        od = out_dev ? (GT*)gt_out : od_s;
-        HK_TRY(PairRun<P>::gt_prod(L->stream, pw, (u32)group_len, (u32)n_out, od));
-    }
-    if (!out_dev) HK_HIP(hipMemcpyAsync(gt_out, od, n_out * sizeof(GT), hipMemcpyDeviceToHost, L->stream));
+    if (group_len == 1) pw = (GT*)to.p;
+    HK_TRY(stage_upload(L, in, 2));
+    HK_TRY(PairRun<P>::gt_pow(L->stream, (const GT*)in[0].p, in[1].p, (u32)n, pw, in_gt != 0));
+    if (group_len > 1) HK_TRY(PairRun<P>::gt_prod(L->stream, pw, (u32)group_len, (u32)n_out, (GT*)to.p));
+    HK_TRY(stage_download(L, &to, 1));
     return L->settle();
 }
 

@@ -297,23 +297,21 @@ hk_status VerifyRun<P>::vk_prepare(hk_ctx* ctx, const hk_vk_desc* d, hk_vk** out
     HK_HIP(hipMemcpy(&neg[0], d->gamma_h, sizeof(Affine<Fq2>), hipMemcpyDefault));
     HK_HIP(hipMemcpy(&neg[1], d->deltas_h, d->n_deltas * sizeof(Affine<Fq2>), hipMemcpyDefault));
     for (auto& q : neg) q.y = Fq2::neg(q.y);
+    Staged in[2] = {staged(d->alpha_g, sizeof(Affine<Fq>)), staged(d->beta_h, sizeof(Affine<Fq2>))};
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
     size_t mbytes = PairRun<P>::scratch_bytes(1, 1, 1);
     Affine<Fq2>* g2;
-    const void *al, *be;
     GT *miller, *prod;
     HK_TRY(L->carve([&](Carve& c) {
         g2 = c.n<Affine<Fq2>>(nst);
-        al = c.take(sizeof(Affine<Fq>));
-        be = c.take(sizeof(Affine<Fq2>));
+        stage_carve(c, in, 2);
         miller = (GT*)c.take(mbytes);
         prod = c.n<GT>(1);
     }));
     hipStream_t s = L->stream;
-    HK_TRY(to_device(L, d->alpha_g, sizeof(Affine<Fq>), &al));
-    HK_TRY(to_device(L, d->beta_h, sizeof(Affine<Fq2>), &be));
+    HK_TRY(stage_upload(L, in, 2));
     VkImpl<P>* v = new VkImpl<P>();
     v->n_deltas = (u32)d->n_deltas;
     v->n_abc = (u32)d->n_abc;
@@ -328,7 +326,7 @@ hk_status VerifyRun<P>::vk_prepare(hk_ctx* ctx, const hk_vk_desc* d, hk_vk** out
         return fail(HK_ERR_DEVICE);
     hk_status st = verify_lines<P>(s, g2, nst, v->lines);
     if (st == HK_OK)
-        st = PairRun<P>::run(s, (const Affine<Fq>*)al, (const Affine<Fq2>*)be, 1, 1, 1, miller, prod, v->alpha_beta);
+        st = PairRun<P>::run(s, (const Affine<Fq>*)in[0].p, (const Affine<Fq2>*)in[1].p, 1, 1, 1, miller, prod, v->alpha_beta);
     if (st == HK_OK) st = L->settle();
     if (st != HK_OK) return fail(st);
     hk_vk* h = new hk_vk();
@@ -363,20 +361,18 @@ template <class P>
 hk_status VerifyRun<P>::points_check(hk_ctx* ctx, int group, const void* pts, size_t n, unsigned char* ok) {
     if (n == 0) return HK_OK;
     if (n >= ((size_t)1 << 31)) return HK_ERR_ARG;
+    Staged io[2] = {staged(pts, n * (group == 1 ? sizeof(Affine<Fp<P>>) : sizeof(Affine<Fp2<P>>))), staged(ok, n)};
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
     auto run = [&](auto ftag) -> hk_status {
         typedef decltype(ftag) F;
-        const void* pd;
-        unsigned char* out_s;
-        HK_TRY(L->carve([&](Carve& c) { pd = c.take(n * sizeof(Affine<F>)); out_s = c.n<unsigned char>(n); }));
-        HK_TRY(to_device(L, pts, n * sizeof(Affine<F>), &pd));
-        bool dev = is_device_ptr(ok);
-        unsigned char* od = dev ? ok : out_s;
-        hipLaunchKernelGGL((k_points_check<F>), dim3((u32)((n + 63) / 64)), dim3(64), 0, L->stream, (const Affine<F>*)pd, (u32)n, 0u, od);
+        HK_TRY(L->carve([&](Carve& c) { stage_carve(c, io, 2); }));
+        HK_TRY(stage_upload(L, io, 1));
+        hipLaunchKernelGGL((k_points_check<F>), dim3((u32)((n + 63) / 64)), dim3(64), 0, L->stream, (const Affine<F>*)io[0].p, (u32)n,
+                           0u, (unsigned char*)io[1].p);
         HK_HIP(hipGetLastError());
-        if (!dev) HK_HIP(hipMemcpyAsync(ok, od, n, hipMemcpyDeviceToHost, L->stream));
+        HK_TRY(stage_download(L, io + 1, 1));
         return L->settle();
     };
     return group == 1 ? run(Fp<P>()) : run(Fp2<P>());
@@ -401,13 +397,19 @@ hk_status VerifyRun<P>::verify_batch(hk_ctx* ctx, const hk_vk* h, const void* a,
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
     hipStream_t s = L->stream;
-    const bool out_dev = is_device_ptr(verdicts);
     const u32 gpp = (1 + nst + 15) / 16;                   // first-level groups of a per-proof product
     for (size_t o = 0; o < n; o += VERIFY_CHUNK) {
         const u32 m = (u32)(n - o < VERIFY_CHUNK ? n - o : VERIFY_CHUNK);
         const u32 gb = (m + nst + 15) / 16;                // ... of the batch product
-        const void *ad, *bd, *cd, *dd, *xd, *rd;
-        unsigned char *flag, *vd_s;
+        // this chunk of a, b, c, ds, inputs and rand, then of the verdicts
+        Staged io[7] = {staged((const char*)a + o * g1b, m * g1b),
+                        staged((const char*)b + o * g2b, m * g2b),
+                        staged((const char*)c + o * g1b, m * g1b),
+                        staged(nd > 1 ? (const char*)ds + o * (nd - 1) * g1b : nullptr, (size_t)m * (nd - 1) * g1b),
+                        staged(nk ? (const char*)inputs + o * nk * frb : nullptr, (size_t)m * nk * frb),
+                        staged(rand ? (const char*)rand + o * frb : nullptr, m * frb),
+                        staged(verdicts + o, m)};
+        unsigned char* flag;
         Affine<Fq>* gst;
         Line6<P>* lines;
         GT *pp0, *pp1, *res;
@@ -419,14 +421,8 @@ hk_status VerifyRun<P>::verify_batch(hk_ctx* ctx, const hk_vk* h, const void* a,
         GT *qa = nullptr, *qb = nullptr, *one = nullptr, *want = nullptr;
         unsigned char* eq = nullptr;
         HK_TRY(L->carve([&](Carve& k) {
-            ad = k.take(m * g1b);
-            bd = k.take(m * g2b);
-            cd = k.take(m * g1b);
-            dd = k.take((size_t)m * (nd - 1) * g1b);
-            xd = k.take((size_t)m * nk * frb);
-            rd = k.take(rand ? m * frb : 0);
+            stage_carve(k, io, 7);
             flag = k.n<unsigned char>(m);
-            vd_s = k.n<unsigned char>(m);
             gst = k.n<Affine<Fq>>((size_t)m * nst);
             lines = k.n<Line6<P>>((size_t)m * S);
             pp0 = k.n<GT>((size_t)m * S * gpp);
@@ -447,13 +443,9 @@ hk_status VerifyRun<P>::verify_batch(hk_ctx* ctx, const hk_vk* h, const void* a,
             want = k.n<GT>(1);
             eq = k.n<unsigned char>(1);
         }));
-        HK_TRY(to_device(L, (const char*)a + o * g1b, m * g1b, &ad));
-        HK_TRY(to_device(L, (const char*)b + o * g2b, m * g2b, &bd));
-        HK_TRY(to_device(L, (const char*)c + o * g1b, m * g1b, &cd));
-        if (nd > 1) HK_TRY(to_device(L, (const char*)ds + o * (nd - 1) * g1b, (size_t)m * (nd - 1) * g1b, &dd));
-        if (nk) HK_TRY(to_device(L, (const char*)inputs + o * nk * frb, (size_t)m * nk * frb, &xd));
-        if (rand) HK_TRY(to_device(L, (const char*)rand + o * frb, m * frb, &rd));
-        unsigned char* vd = out_dev ? verdicts + o : vd_s;
+        const void *ad = io[0].p, *bd = io[1].p, *cd = io[2].p, *dd = io[3].p, *xd = io[4].p, *rd = io[5].p;
+        unsigned char* vd = (unsigned char*)io[6].p;
+        HK_TRY(stage_upload(L, io, 6));
         HK_HIP(hipMemsetAsync(flag, 0, m, s));
         bool any_bad = false;
         if (check) {
@@ -516,7 +508,7 @@ hk_status VerifyRun<P>::verify_batch(hk_ctx* ctx, const hk_vk* h, const void* a,
                                check ? (const unsigned char*)flag : nullptr, vd);
             HK_HIP(hipGetLastError());
         }
-        if (!out_dev) HK_HIP(hipMemcpyAsync(verdicts + o, vd, m, hipMemcpyDeviceToHost, s));
+        HK_TRY(stage_download(L, io + 6, 1));
         HK_TRY(L->settle());
     }
     return HK_OK;

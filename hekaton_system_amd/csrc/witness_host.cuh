@@ -27,20 +27,19 @@ hk_status Ops<C>::assignment_from_bits(hk_ctx* ctx, const void* bits, size_t n_v
                                        const void* full_vals, size_t n_full, void* z_out) {
     if (n_v == 0) return HK_OK;
     if (!is_device_ptr(z_out)) return HK_ERR_ARG;
-    for (size_t k = 0; k < n_full; k++) if (!is_device_ptr(full_cols) && full_cols[k] >= n_v) return HK_ERR_ARG;
+    Staged in[3] = {staged(bits, n_v), staged(full_cols, 4 * n_full), staged(full_vals, sizeof(Fr) * n_full)};
+    if (in[1].scratch)                                      // host columns are checked here; resident ones by the kernel
+        for (size_t k = 0; k < n_full; k++) if (full_cols[k] >= n_v) return HK_ERR_ARG;
     LaneGuard g(ctx);
     Lane* L = g.lane;
     if (!L) return HK_ERR_DEVICE;
-    const void *bd, *cd, *vd;
-    HK_TRY(L->carve([&](Carve& c) { bd = c.take(n_v); cd = c.take(4 * n_full); vd = c.take(sizeof(Fr) * n_full); }));
-    HK_TRY(to_device(L, bits, n_v, &bd));
-    HK_TRY(to_device(L, full_cols, 4 * n_full, &cd));
-    HK_TRY(to_device(L, full_vals, sizeof(Fr) * n_full, &vd));
-    hipLaunchKernelGGL((k_expand_bits<Fr>), dim3((u32)((n_v + 255) / 256)), dim3(256), 0, L->stream, (const unsigned char*)bd, n_v,
-                       (Fr*)z_out);
+    HK_TRY(L->carve([&](Carve& c) { stage_carve(c, in, 3); }));
+    HK_TRY(stage_upload(L, in, 3));
+    hipLaunchKernelGGL((k_expand_bits<Fr>), dim3((u32)((n_v + 255) / 256)), dim3(256), 0, L->stream, (const unsigned char*)in[0].p,
+                       n_v, (Fr*)z_out);
     if (n_full)
-        hipLaunchKernelGGL((k_scatter_full<Fr>), dim3((u32)((n_full + 63) / 64)), dim3(64), 0, L->stream, (const u32*)cd,
-                           (const Fr*)vd, (u32)n_full, n_v, (Fr*)z_out);
+        hipLaunchKernelGGL((k_scatter_full<Fr>), dim3((u32)((n_full + 63) / 64)), dim3(64), 0, L->stream, (const u32*)in[1].p,
+                           (const Fr*)in[2].p, (u32)n_full, n_v, (Fr*)z_out);
     HK_HIP(hipGetLastError());
     return L->settle();
 }

@@ -3,6 +3,7 @@ name for them (test_exec_tree_gpu, test_stage1_witness_gpu, test_ram_witness_gpu
 test_r1cs_job_gpu, test_sha_tree_gpu), each beside its nearest valid case.  tests/host_shim/job_args_driver.cpp runs the
 table as a stand-alone host program: once as built plainly, once under AddressSanitizer + UBSan in a process of its own."""
 import os
+import re
 import subprocess
 
 import pytest
@@ -90,3 +91,32 @@ def test_carve_lambdas_only_carve():
             seen += 1
             at = src.find("carve([&]", k)
     assert seen >= 20
+
+
+def test_one_staging_idiom():
+    """Every entry stages its host-or-device operands through Staged (hk_internal.h): the older helper is gone."""
+    assert [f for f, src in _sources().items() if "to_device(" in src] == []
+
+
+def test_witness_host_asks_residency_outside_loops():
+    """One hipPointerGetAttributes per operand, not one per element: no is_device_ptr( in a for / while header or body."""
+    src = _sources()["witness_host.cuh"]
+    loops = list(re.finditer(r"\b(for|while)\s*\(", src))
+    assert loops
+    for m in loops:
+        depth, k = 0, m.end() - 1
+        for k in range(k, len(src)):                      # the header's closing parenthesis
+            depth += {"(": 1, ")": -1}.get(src[k], 0)
+            if depth == 0:
+                break
+        end = k + 1
+        while src[end].isspace():
+            end += 1
+        if src[end] == "{":                                # a braced body, else one statement
+            for end in range(end, len(src)):
+                depth += {"{": 1, "}": -1}.get(src[end], 0)
+                if depth == 0:
+                    break
+        else:
+            end = src.index(";", end)
+        assert "is_device_ptr(" not in src[m.start():end + 1], src[m.start():end + 1]
