@@ -121,6 +121,12 @@ class hk_vkd_cols(C.Structure):               # include/hekaton.h
     _fields_ = [("kind", C.c_uint32), ("hash_col0", C.c_uint32), ("index_col0", C.c_uint32), ("path_col0", C.c_uint32)]
 
 
+class hk_vkd_tree_desc(C.Structure):          # include/hekaton.h
+    _fields_ = [("depth", C.c_uint32), ("n_leaves0", C.c_uint32), ("leaves0", C.c_void_p), ("n_updates", C.c_uint32),
+                ("kinds", C.c_void_p), ("leaves", C.c_void_p), ("consts_mont", C.c_void_p), ("n_consts", C.c_size_t),
+                ("leaf_hash", C.POINTER(hk_poseidon_desc)), ("node_hash", C.POINTER(hk_poseidon_desc))]
+
+
 class hk_sha_tree_out(C.Structure):           # include/hekaton.h
     _fields_ = [("digests_out", C.c_void_p), ("time_entries_mont_out", C.c_void_p), ("sha_root_mont_out", C.c_void_p)]
 
@@ -151,7 +157,7 @@ EXPORTS = ["hk_status_str", "hk_version", "hk_ctx_create", "hk_ctx_destroy", "hk
            "hk_points_check_g2", "hk_qap_eval", "hk_keygen", "hk_exec_tree", "hk_stage1_witness",
            "hk_trace_sort", "hk_stage0_witness", "hk_r1cs_check", "hk_pk_r1cs_check",
            "hk_sha_tree", "hk_sha_tree_inputs", "hk_ram_stage0_witness", "hk_ram_stage1_witness",
-           "hk_r1cs_job_trace", "hk_r1cs_job_witness", "hk_vkd_trace", "hk_vkd_witness",
+           "hk_r1cs_job_trace", "hk_r1cs_job_witness", "hk_vkd_trace", "hk_vkd_witness", "hk_vkd_tree",
            "hk_scalar_powers", "hk_ipa_quotient", "hk_field_sqrt", "hk_points_decompress_g1", "hk_points_decompress_g2",
            "hk_points_compress_g1", "hk_points_compress_g2"]
 
@@ -256,6 +262,7 @@ def load():
     lib.hk_r1cs_job_witness.argtypes = [vp, C.POINTER(hk_r1cs_job_desc), vp, sz, sz, sz, vp]
     lib.hk_vkd_trace.argtypes = [vp, C.POINTER(hk_vkd_desc), vp, vp]
     lib.hk_vkd_witness.argtypes = [vp, C.POINTER(hk_vkd_desc), vp, sz, sz, C.POINTER(hk_vkd_cols), vp]
+    lib.hk_vkd_tree.argtypes = [vp, C.POINTER(hk_vkd_tree_desc), vp, vp, vp]
     lib.hk_scalar_powers.argtypes = [vp, vp, sz, sz, vp]
     lib.hk_ipa_quotient.argtypes = [vp, vp, sz, vp, vp, sz, vp]
     if hasattr(lib, "hk_field_sqrt"):             # absent only from older experiment builds loaded through HK_LIB
@@ -978,6 +985,34 @@ class Context:
         check(self.lib.hk_vkd_witness(self.handle, C.byref(d), _nullable(sub_index), sub_index.size, int(n_v), C.byref(c),
                                       None if z_out is None else _device_addr(z_out)), "hk_vkd_witness")
         return z_out
+
+    def vkd_tree(self, depth, leaves0, kinds, leaves, params, device_out=False, out=None):
+        """hk_vkd_tree: a batch of updates applied to a directory - the sibling paths `VkdJob.tables()["siblings"]` holds and
+        the roots before and after the batch, every hash on the device (`vkd_circuit.directory_paths` is the host mirror).
+        leaves0: the directory's leaves, M x 66 bytes (bytes, an array, a DeviceBuffer, or None / empty for M = 0); kinds:
+        U words, 0 append / 1 update; leaves: U x 2 x 66 bytes as `tables()["leaves"]` (bytes, an array or a DeviceBuffer);
+        params: what vkd_trace takes.  Returns (siblings [U x depth Fr], roots [2 Fr], status [U bytes, HK_VKD_ST_*]) as uint8
+        arrays, or as DeviceBuffers when device_out is set; out: a triple of buffers of those sizes to fill instead, the third
+        one None for no status."""
+        consts, n_consts, ld, nd = params
+        kinds = np.ascontiguousarray(kinds, dtype=np.uint32).reshape(-1)
+        if isinstance(leaves0, (bytes, bytearray)):
+            leaves0 = np.frombuffer(bytes(leaves0), np.uint8)
+        if isinstance(leaves, (bytes, bytearray)):
+            leaves = np.frombuffer(bytes(leaves), np.uint8)
+        keep = [_hd(leaves0), _hd(leaves), _hd(consts)]
+        m = 0 if keep[0] is None else (keep[0].nbytes if isinstance(keep[0], DeviceBuffer) else keep[0].size) // 66
+        u, fr = kinds.size, self.fr_bytes
+        a, b = hk_poseidon_desc(*ld), hk_poseidon_desc(*nd)
+        d = hk_vkd_tree_desc(int(depth), m, _nullable(keep[0]) if m else None, u, _nullable(kinds), _nullable(keep[1]),
+                             _nullable(keep[2]), int(n_consts), C.pointer(a), C.pointer(b))
+        own = out is None
+        if own:
+            sizes = [u * int(depth) * fr, 2 * fr, u]
+            out = tuple(DeviceBuffer(self, max(n, 1)) if device_out else np.zeros(n, dtype=np.uint8) for n in sizes)
+        with _owned(out, own):
+            check(self.lib.hk_vkd_tree(self.handle, C.byref(d), ptr(out[0]), ptr(out[1]), ptr(out[2])), "hk_vkd_tree")
+        return tuple(out)
 
     def _r1cs_call(self, fn, head, z, n_v, batch, cap, want_vals):
         """The shared tail of Context.r1cs_check / DevicePk.r1cs_check: `fn(*head, z, n_v, batch, verdicts, rows, vals, cap)`."""

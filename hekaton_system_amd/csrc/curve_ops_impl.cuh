@@ -207,6 +207,8 @@ struct Ops final : CurveOps {
     // vkd.cuh
     hk_status vkd_trace(hk_ctx*, const hk_vkd_desc*, void*, void*) override;
     hk_status vkd_witness(hk_ctx*, const hk_vkd_desc*, const uint32_t*, size_t, size_t, const hk_vkd_cols*, void*) override;
+    // vkd_tree.cuh
+    hk_status vkd_tree(hk_ctx*, const hk_vkd_tree_desc*, void*, void*, uint8_t*) override;
     // agg_scalars.cuh
     hk_status scalar_powers(hk_ctx*, const void*, size_t, size_t, void*) override;
     hk_status ipa_quotient(hk_ctx*, const void*, size_t, const void*, const void*, size_t, void*) override;

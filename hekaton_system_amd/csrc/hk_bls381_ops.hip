@@ -15,6 +15,7 @@
 #include "ram_witness.cuh"
 #include "r1cs_job.cuh"
 #include "vkd.cuh"
+#include "vkd_tree.cuh"
 #include "agg_scalars.cuh"
 namespace hk {
 extern template struct MsmRun<CurveBls381::Fq>;

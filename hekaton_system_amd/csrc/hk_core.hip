@@ -727,6 +727,10 @@ hk_status hk_vkd_witness(hk_ctx* ctx, const hk_vkd_desc* desc, const uint32_t* s
     if (!ctx || !desc) return HK_ERR_ARG;
     return ctx->ops->vkd_witness(ctx, desc, sub_index, batch, n_v, cols, z_out);
 }
+hk_status hk_vkd_tree(hk_ctx* ctx, const hk_vkd_tree_desc* desc, void* siblings_mont_out, void* roots_mont_out, uint8_t* status_out) {
+    if (!ctx || !desc) return HK_ERR_ARG;
+    return ctx->ops->vkd_tree(ctx, desc, siblings_mont_out, roots_mont_out, status_out);
+}
 hk_status hk_scalar_powers(hk_ctx* ctx, const void* x_mont, size_t n, size_t reps, void* out) {
     if (!ctx) return HK_ERR_ARG;
     return ctx->ops->scalar_powers(ctx, x_mont, n, reps, out);

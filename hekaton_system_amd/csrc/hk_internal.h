@@ -260,6 +260,8 @@ struct CurveOps {
     virtual hk_status vkd_trace(hk_ctx*, const hk_vkd_desc*, void* values_out, void* time_entries_out) = 0;
     virtual hk_status vkd_witness(hk_ctx*, const hk_vkd_desc*, const uint32_t* sub_index, size_t batch, size_t n_v,
                                   const hk_vkd_cols* cols, void* z_out) = 0;
+    // vkd_tree.cuh
+    virtual hk_status vkd_tree(hk_ctx*, const hk_vkd_tree_desc*, void* siblings_out, void* roots_out, uint8_t* status_out) = 0;
     // agg_scalars.cuh
     virtual hk_status scalar_powers(hk_ctx*, const void* x, size_t n, size_t reps, void* out) = 0;
     virtual hk_status ipa_quotient(hk_ctx*, const void* challenges, size_t l, const void* rho, const void* z, size_t shift,

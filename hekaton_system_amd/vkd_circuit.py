@@ -127,23 +127,63 @@ class SparseTree:
         return path
 
 
+ST_OK, ST_OCCUPIED, ST_ABSENT, ST_STALE = 0, 1, 2, 3    # include/hekaton.h HK_VKD_ST_*
+
+
 class Append:
-    """`VkdAppend`: add (username, 0, key); path: the `depth` siblings of the user's (still empty) leaf."""
+    """`VkdAppend`: add (username, 0, key); path: the `depth` siblings of the user's (still empty) leaf, or None when the
+    job reads its siblings from the device (`VkdJob(siblings=...)`)."""
     kind = KIND_APPEND
 
-    def __init__(self, username, key, path):
-        self.username, self.key, self.path = bytes(username), bytes(key), [int(x) for x in path]
+    def __init__(self, username, key, path=None):
+        self.username, self.key = bytes(username), bytes(key)
+        self.path = None if path is None else [int(x) for x in path]
         self.leaf_old, self.leaf_new = None, concat(username, key, 0)
 
 
 class Update:
-    """`VkdUpdate`: (username, counter, key1) -> (username, counter + 1, key2); path: the siblings of the user's leaf."""
+    """`VkdUpdate`: (username, counter, key1) -> (username, counter + 1, key2); path: the siblings of the user's leaf, or
+    None as for `Append`."""
     kind = KIND_UPDATE
 
-    def __init__(self, username, counter, key1, key2, path):
+    def __init__(self, username, counter, key1, key2, path=None):
         self.username, self.counter, self.key1, self.key2 = bytes(username), int(counter), bytes(key1), bytes(key2)
-        self.path = [int(x) for x in path]
+        self.path = None if path is None else [int(x) for x in path]
         self.leaf_old, self.leaf_new = concat(username, key1, counter), concat(username, key2, counter + 1)
+
+
+def leaves_table(changes):
+    """U x 2 x 66 bytes: (leaf_old - zeros for an append -, leaf_new) of every change: hk_vkd_desc.leaves."""
+    leaves = np.zeros((len(changes), 2, LEAF_BYTES), np.uint8)
+    for i, u in enumerate(changes):
+        if u.kind == KIND_UPDATE:
+            leaves[i, 0] = np.frombuffer(u.leaf_old, np.uint8)
+        leaves[i, 1] = np.frombuffer(u.leaf_new, np.uint8)
+    return leaves
+
+
+def directory_paths(curve, depth, leaves0, changes):
+    """The host mirror of hk_vkd_tree: a `SparseTree` that takes the directory's leaves `leaves0`
+    (66 bytes each, a later one replacing an earlier one of the same index), then one change after the other.  Returns
+    (initial_root, final_root, paths, status): paths[u] the `depth` siblings of change u's leaf right before it is applied,
+    status[u] what the change met (ST_*): an append onto an occupied index, an update of an absent user or one whose leaf_old
+    is not what the index holds.  The tree inserts whatever the status is, as the reference's does."""
+    t = SparseTree(curve, depth)
+    for leaf in leaves0:
+        leaf = bytes(leaf)
+        assert len(leaf) == LEAF_BYTES
+        t.insert(get_index(curve, leaf[:NAME_BYTES], depth), leaf)
+    initial, paths, status = t.root, [], []
+    for u in changes:
+        idx = get_index(curve, u.username, depth)
+        held = t.leaves.get(idx)
+        if u.kind == KIND_APPEND:
+            status.append(ST_OK if held is None else ST_OCCUPIED)
+        else:
+            status.append(ST_ABSENT if held is None else ST_OK if held == u.leaf_old else ST_STALE)
+        paths.append(t.lookup_path(idx))
+        t.insert(idx, u.leaf_new)
+    return initial, t.root, paths, status
 
 
 # ---- one proving-key class ---------------------------------------------------------------------------------------------
@@ -306,7 +346,8 @@ class VkdJob(PortalJob):
     """A whole VKD job: N = 8 + 2 split U subcircuits over U updates (6 paddings, write-pp, 2 split per update, the final
     equality), the addresses `SetupRomPortalManager` hands out, the VALUE TABLE every traced value is read from, the
     time-ordered trace, its address order and - once the round's challenges are in - the running evaluations, the
-    execution tree and every subcircuit's inputs.  The job never builds the sparse tree: every update carries its siblings.
+    execution tree and every subcircuit's inputs.  The job never builds the sparse tree: every update carries its siblings,
+    or `from_directory` has hk_vkd_tree compute them from the directory's leaves on the device.
 
     The value table (what hk_vkd_trace writes as `values_out`), V = 3 + U (2 + 3 split) nodes / words:
         0 initial root   1 final root   2 null leaf
@@ -314,10 +355,15 @@ class VkdJob(PortalJob):
                                         + 2 + s index word s of the update's user
                                         + 2 + split + p split + s the node after segment s of path p
     ValueError: N no power of two >= 16; depth no multiple of 8 split or L < 8; a path of another length than depth; a name
-    set twice; a name read before it is set (where the reference panics)."""
+    set twice; a name read before it is set (where the reference panics).
 
-    def __init__(self, curve, initial_root, final_root, updates, depth=128, split=4, host_values=True):
+    siblings: a `DeviceBuffer` of U x depth Fr (hk_vkd_tree's siblings_mont_out) the job reads instead of the updates' own
+    paths, which may then be None; `tables()["siblings"]` is that buffer.  ValueError: given with host_values, or of another
+    size than U x depth Fr."""
+
+    def __init__(self, curve, initial_root, final_root, updates, depth=128, split=4, host_values=True, siblings=None):
         self.depth_tree, self.split, self.updates = int(depth), int(split), list(updates)
+        self.siblings = siblings
         S, U = self.split, len(self.updates)
         if S < 2 or depth % (8 * S) or depth // S < 8:
             raise ValueError("depth %d over %d segments: L must be a multiple of 8, at least 8, and split >= 2" % (depth, S))
@@ -325,7 +371,13 @@ class VkdJob(PortalJob):
         n = 8 + 2 * S * U
         if n < 16 or n & (n - 1):
             raise ValueError("8 + 2 x %d x %d updates = %d subcircuits: not a power of two >= 16" % (S, U, n))
-        if any(len(u.path) != depth for u in self.updates):
+        if siblings is not None:
+            if host_values:
+                raise ValueError("siblings on the device: the value table is the device's too (host_values=False)")
+            fr = CURVE_PARAMS[curve]["fr_bytes"]
+            if not isinstance(siblings, capi.DeviceBuffer) or siblings.nbytes != U * depth * fr:
+                raise ValueError("siblings: a DeviceBuffer of %d x %d Fr" % (U, depth))
+        elif any(u.path is None or len(u.path) != depth for u in self.updates):
             raise ValueError("every update carries its %d siblings" % depth)
         self._set_shape(curve, n)
         self.initial_root, self.final_root = int(initial_root) & NODE_MASK, int(final_root) & NODE_MASK
@@ -431,11 +483,43 @@ class VkdJob(PortalJob):
         job.dev0 = VkdStage0Device(job, ctx)
         return job
 
+    @classmethod
+    def from_directory(cls, ctx, curve, leaves0, changes, depth=128, split=4):
+        """An `on_device` job from the directory itself: hk_vkd_tree applies `changes` (`Append` / `Update`, no path needed)
+        to the directory of leaves `leaves0` on the device; only the two roots come back.  The siblings stay in HBM
+        (`job.siblings`, released by `free()`); `job.status` holds what each change met (ST_*)."""
+        changes = list(changes)
+        consts, n_consts, ld, nd = device_params(curve, FrCodec(curve))
+        consts_d = capi.DeviceBuffer.from_host(ctx, consts)
+        try:
+            leaves0 = np.frombuffer(b"".join(bytes(x) for x in leaves0), np.uint8)
+            sib, roots, status = ctx.vkd_tree(depth, leaves0, [u.kind for u in changes], leaves_table(changes),
+                                              (consts_d, n_consts, ld, nd), device_out=True)
+        finally:
+            consts_d.free()
+        try:
+            initial, final = FrCodec(curve).dec(roots.to_host())
+            st = status.to_host()[:len(changes)].copy()
+        finally:
+            roots.free()
+            status.free()
+        try:
+            job = cls(curve, initial, final, changes, depth=depth, split=split, host_values=False, siblings=sib)
+            job.dev0 = VkdStage0Device(job, ctx)
+        except Exception:
+            sib.free()
+            raise
+        job.status = st
+        return job
+
     def free(self):
         for name in ("dev1", "dev0"):
             if getattr(self, name, None) is not None:
                 getattr(self, name).free()
                 setattr(self, name, None)
+        if self.siblings is not None:
+            self.siblings.free()
+            self.siblings = None
 
     def verify(self):
         """`verify` (vkd.rs:216-275) with pp = the null leaf: every path leads from the old leaf (or the null leaf) to the
@@ -501,14 +585,10 @@ class VkdJob(PortalJob):
     def tables(self):
         """The job as hk_vkd_desc states it (`Context.vkd_trace` takes this dict)."""
         fc = FrCodec(self.curve)
-        leaves = np.zeros((len(self.updates), 2, LEAF_BYTES), np.uint8)
-        for i, u in enumerate(self.updates):
-            if u.kind == KIND_UPDATE:
-                leaves[i, 0] = np.frombuffer(u.leaf_old, np.uint8)
-            leaves[i, 1] = np.frombuffer(u.leaf_new, np.uint8)
+        siblings = self.siblings if self.siblings is not None else fc.enc([x for u in self.updates for x in u.path])
         return dict(depth=self.depth_tree, split=self.split, n_updates=len(self.updates),
-                    kinds=np.array([u.kind for u in self.updates], np.uint32), leaves=leaves,
-                    siblings=fc.enc([x for u in self.updates for x in u.path]),
+                    kinds=np.array([u.kind for u in self.updates], np.uint32), leaves=leaves_table(self.updates),
+                    siblings=siblings,
                     roots=fc.enc([self.initial_root, self.final_root]), slot_addr=self.slot_addr.copy(),
                     slot_src=self.slot_src.copy())
 

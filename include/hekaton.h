@@ -864,6 +864,42 @@ hk_status hk_vkd_trace(hk_ctx* ctx, const hk_vkd_desc* desc, void* values_mont_o
 hk_status hk_vkd_witness(hk_ctx* ctx, const hk_vkd_desc* desc, const uint32_t* sub_index /* [h] batch */, size_t batch,
                          size_t n_v, const hk_vkd_cols* cols, void* z_out /* [d] batch x n_v Fr */);
 
+/* ---- a VKD batch applied to the directory (vkd/sparse_tree.rs:70-177 `SparseMerkleTree`) ------------
+ * What hk_vkd_desc.siblings_mont and roots_mont want, from the leaves themselves: the directory holds leaves0 (one 66-byte
+ * leaf per user, at the index the low `depth` bits of its username's digest give), and update u of the batch inserts
+ * leaves[u][1] - its leaf_new - at its own index.  The outputs are byte for byte those of the host loop
+ *     t = SparseTree(depth); for each initial leaf: t.insert(index, leaf); roots[0] = t.root
+ *     for each update u: siblings[u] = t.lookup_path(index_u); t.insert(index_u, leaf_new_u)
+ *     roots[1] = t.root
+ * (hekaton_system_amd/vkd_circuit.py `directory_paths`).  An insert overwrites, as in the reference.  status_out only
+ * reports what the batch meets - the siblings are written whatever the status is: an append onto an index that holds a
+ * leaf, an update of an index that holds none, an update whose leaf_old differs from the 66 bytes its index holds.
+ * Every hash runs on the device, one quad of lanes per event (initial leaf or update) and level: `depth` dependent launches,
+ * each data-parallel over the M + U events; up to 64 events, one launch of one workgroup.  The call runs on the caller's
+ * lane; host-resident buffers are staged in lane scratch, device-resident ones read and written in place.
+ * HK_ERR_ARG / HK_ERR_LEN, before any device work and with the outputs untouched: a NULL pointer (leaves0 only when
+ * n_leaves0 > 0; status_out may be NULL); a depth that is no multiple of 8 in 16 .. 256; n_updates 0 or above 2^20;
+ * n_leaves0 + n_updates above 2^22 (LEN); a kind that is neither HK_VKD_APPEND nor HK_VKD_UPDATE; Poseidon descriptors other
+ * than the two instances hk_exec_tree takes; an output range that overlaps an input or another output. */
+#define HK_VKD_ST_OK       0u
+#define HK_VKD_ST_OCCUPIED 1u   /* an append whose index already holds a leaf */
+#define HK_VKD_ST_ABSENT   2u   /* an update whose index holds no leaf */
+#define HK_VKD_ST_STALE    3u   /* an update whose leaf_old is not the 66 bytes that index holds */
+typedef struct {
+    uint32_t depth;             /* a multiple of 8, 16 .. 256 */
+    uint32_t n_leaves0;         /* M: the directory before the batch; may be 0 */
+    const uint8_t* leaves0;     /* [h|d] M x 66 bytes, one leaf per user; a later one replaces an earlier one of the same index */
+    uint32_t n_updates;         /* U >= 1 */
+    const uint32_t* kinds;      /* [h] U: HK_VKD_APPEND / HK_VKD_UPDATE */
+    const uint8_t* leaves;      /* [h|d] U x 2 x 66: exactly hk_vkd_desc.leaves (leaf_old is not read for an append) */
+    const void* consts_mont; size_t n_consts;
+    const hk_poseidon_desc* leaf_hash; const hk_poseidon_desc* node_hash;   /* as hk_vkd_trace */
+} hk_vkd_tree_desc;
+hk_status hk_vkd_tree(hk_ctx* ctx, const hk_vkd_tree_desc* desc,
+                      void* siblings_mont_out /* [h|d] U x depth Fr, the leaf's sibling first: hk_vkd_desc.siblings_mont */,
+                      void* roots_mont_out    /* [h|d] 2 Fr: root before the batch, root after it */,
+                      uint8_t* status_out     /* [h|d] U bytes, HK_VKD_ST_*; may be NULL */);
+
 /* ---- the aggregator's scalar vectors ------------------------------------------------------------
  * What `TIPA::setup`, `agg_subcircuit_proofs` and `TIPA::prove` build one field product at a time on the host: the powers of
  * a trapdoor or of the twist, and the two KZG witness polynomials of the folded keys.  Both results may stay on the device,
