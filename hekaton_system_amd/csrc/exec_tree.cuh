@@ -13,8 +13,7 @@
 //   (c) paths         siblings[i][l] = level_l[(i >> l) ^ 1], one lane per (i, l).
 #pragma once
 #include "curve_ops_impl.cuh"
-#include "ntt.cuh"
-#include "witness.cuh"
+#include "poseidon.cuh"
 
 namespace hk {
 
@@ -43,12 +42,6 @@ template <class Fr, int K>
 __device__ __forceinline__ Fr et_factor(const Fr* __restrict__ e, const EtChal<Fr>& ch) {
     return Fr::sub(ch.c[K - 1], et_repr<Fr, K>(e, ch));
 }
-template <class Fr>
-__device__ __forceinline__ Fr et_select(bool take, const Fr& a, const Fr& b) {
-    Fr r;
-    HK_UNROLL for (int i = 0; i < Fr::N; i++) r.v[i] = take ? a.v[i] : b.v[i];
-    return r;
-}
 
 // (a1) prods[y][c] = product of the factors of entries [c ET_CHUNK, (c + 1) ET_CHUNK) of order y (0 time, 1 address); an
 // entry past n counts as 1.  n_chunks = n / ET_CHUNK + 1: every boundary b <= n has its chunk b / ET_CHUNK.
@@ -75,7 +68,7 @@ __device__ __forceinline__ Fr et_wg_scan(Fr* s, u32 tid, Fr v) {
     __syncthreads();
     HK_NOUNROLL for (u32 off = 1; off < W; off <<= 1) {
         Fr x = s[tid >= off ? tid - off : tid];
-        x = et_select(tid >= off, x, Fr::one());
+        x = fr_select(tid >= off, x, Fr::one());
         __syncthreads();
         v = Fr::mul(v, x);
         s[tid] = v;
@@ -95,7 +88,7 @@ k_et_scan_tile(Fr* __restrict__ prods, Fr* __restrict__ tops, u32 n_chunks, u32 
     Fr v = Fr::one();
     if (c < n_chunks) v = fr_load(&p[c]);
     Fr inc = et_wg_scan<Fr, ET_SCAN_TILE>(s, tid, v);
-    Fr exc = et_select(tid != 0, s[tid ? tid - 1 : 0], Fr::one());
+    Fr exc = fr_select(tid != 0, s[tid ? tid - 1 : 0], Fr::one());
     if (c < n_chunks) fr_store(&p[c], exc);
     if (tid == ET_SCAN_TILE - 1) fr_store(&tops[(size_t)blockIdx.y * n_tiles + blockIdx.x], inc);
 }
@@ -114,7 +107,7 @@ __global__ void __launch_bounds__(ET_TOPS_LANES) k_et_scan_tops(Fr* __restrict__
         if (i < n_tiles) acc = Fr::mul(acc, fr_load(&p[i]));
     }
     et_wg_scan<Fr, ET_TOPS_LANES>(s, tid, acc);
-    Fr run = et_select(tid != 0, s[tid ? tid - 1 : 0], Fr::one());
+    Fr run = fr_select(tid != 0, s[tid ? tid - 1 : 0], Fr::one());
     HK_NOUNROLL for (u32 j = 0; j < per; j++) {
         u32 i = tid * per + j;
         if (i < n_tiles) {
@@ -155,75 +148,23 @@ k_et_leaves(const Fr* __restrict__ time_e, const Fr* __restrict__ addr_e, const 
     }
 }
 
-// ---- Poseidon on a quad of lanes ---------------------------------------------------------------------------------------
-// State element i lives on lane i of a quad (lanes 4 t .. 4 t + 3); with T = 3 the fourth lane computes along on element 0's
-// constants and its value is never read.  A round per lane: add its own round constant, raise its own element to ALPHA
-// (in a partial round every lane still does, and lanes != 0 then keep their input: a select, no branch), read the T S-box
-// outputs of the quad over DPP quad_perm broadcasts and form its own MDS row - 3 + 4 dependent products at T = 4,
-// ALPHA = 5 and 5 + 3 at T = 3, ALPHA = 17, instead of 28 / 24 with one lane per state.  All four lanes of a quad must be
-// active at every call (DPP reads an inactive lane as 0): callers guard their stores, never the call.
-template <class Fr, int CTRL>
-__device__ __forceinline__ Fr et_quad_bcast(const Fr& v) {
-    Fr r;
-    HK_UNROLL for (int i = 0; i < Fr::N; i++) r.v[i] = (u32)__builtin_amdgcn_update_dpp(0, (int)v.v[i], CTRL, 0xf, 0xf, true);
-    return r;
-}
-template <class Fr, int T, int ALPHA>
-__device__ __forceinline__ Fr poseidon_permute_quad(const Fr* __restrict__ consts, const PoseidonDesc& d, Fr s) {
-    static_assert(T == 3 || T == 4, "one state element per lane of a quad");
-    const u32 q = threadIdx.x & 3u;
-    const u32 qc = q < (u32)T ? q : 0u;
-    const Fr* ark = consts + d.off;
-    const Fr* mds = ark + (size_t)(d.rf + d.rp) * T;
-    const u32 rounds = d.rf + d.rp, half = d.rf / 2;
-    Fr m[T];
-    HK_UNROLL for (int j = 0; j < T; j++) m[j] = fr_load(&mds[qc * T + j]);
-    Fr k = fr_load(&ark[qc]);
-    HK_NOUNROLL for (u32 r = 0; r < rounds; r++) {
-        const bool keep = r < half || r >= half + d.rp || q == 0;
-        Fr y = Fr::add(s, k);
-        k = fr_load(&ark[(r + 1 < rounds ? r + 1 : r) * T + qc]);       // the next round's constant, under this round's products
-        Fr x = Fr::mul(y, y);
-        HK_UNROLL for (int e = 0; e < (ALPHA == 5 ? 1 : 3); e++) x = Fr::mul(x, x);
-        x = Fr::mul(x, y);
-        x = et_select(keep, x, y);
-        s = Fr::mul(m[0], et_quad_bcast<Fr, 0x00>(x));
-        s = Fr::add(s, Fr::mul(m[1], et_quad_bcast<Fr, 0x55>(x)));
-        s = Fr::add(s, Fr::mul(m[2], et_quad_bcast<Fr, 0xAA>(x)));
-        if constexpr (T == 4) s = Fr::add(s, Fr::mul(m[3], et_quad_bcast<Fr, 0xFF>(x)));
-    }
-    return s;
-}
-
-// digest of leaf i on a quad, valid on lane 1: the rate-3 sponge over its nf = 4 or 6 fields (poseidon.PoseidonConfig.crh:
-// capacity element first, absorb three, permute, absorb the rest, permute, squeeze state[1])
-template <class Fr>
-__device__ __forceinline__ Fr et_leaf_digest(const Fr* __restrict__ consts, const PoseidonDesc& d, const Fr* __restrict__ leaf,
-                                             u32 nf) {
-    const u32 q = threadIdx.x & 3u;
-    // every lane loads (an index it may read) and selects: no branch inside the quad
-    Fr s = et_select(q != 0, fr_load(&leaf[q ? q - 1 : 0]), Fr::zero());
-    s = poseidon_permute_quad<Fr, 4, 5>(consts, d, s);
-    const bool more = q != 0 && 2 + q < nf;
-    s = Fr::add(s, et_select(more, fr_load(&leaf[more ? 2 + q : 0]), Fr::zero()));
-    return poseidon_permute_quad<Fr, 4, 5>(consts, d, s);
-}
-// two-to-one hash of in[0], in[1] on a quad, valid on lane 1
+// ---- the tree: Poseidon on a quad of lanes (poseidon.cuh) ------------------------------------------------------------------
+// two-to-one hash of in[0], in[1] on a quad, valid on lane 1: lane 2 loads the right input, every other lane the left one
 template <class Fr>
 __device__ __forceinline__ Fr et_node_digest(const Fr* __restrict__ consts, const PoseidonDesc& d, const Fr* __restrict__ in) {
-    const u32 q = threadIdx.x & 3u;
-    Fr s = et_select(q == 1 || q == 2, fr_load(&in[q == 2 ? 1 : 0]), Fr::zero());
-    return poseidon_permute_quad<Fr, 3, 17>(consts, d, s);
+    const Fr v = fr_load(&in[(threadIdx.x & 3u) == 2 ? 1 : 0]);
+    return poseidon_permute_quad<Fr, 3, 17>(consts, d, poseidon_pair_input(v, v));
 }
 
-// (b1) nodes[i] = digest of leaf i, one quad per leaf.  A quad past the end hashes the last leaf and stores nothing.
+// (b1) nodes[i] = digest of leaf i (lane 1 of its sponge), one quad per leaf.  A quad past the end hashes the last leaf and
+// stores nothing.
 template <class Fr>
 __global__ void __launch_bounds__(256)
 k_et_leaf_hash(const Fr* __restrict__ consts, PoseidonDesc leaf_d, const Fr* __restrict__ leaves, u32 nf, u32 n_sub,
                Fr* __restrict__ nodes) {
     const u32 t = (blockIdx.x * blockDim.x + threadIdx.x) >> 2;
     const u32 i = t < n_sub ? t : n_sub - 1;
-    Fr h = et_leaf_digest<Fr>(consts, leaf_d, leaves + (size_t)i * nf, nf);
+    Fr h = poseidon_leaf_sponge<Fr>(consts, leaf_d, leaves + (size_t)i * nf, nf);
     if (t < n_sub && (threadIdx.x & 3u) == 1) fr_store(&nodes[t], h);
 }
 
@@ -248,7 +189,7 @@ k_et_tree_tail(const Fr* __restrict__ consts, PoseidonDesc leaf_d, PoseidonDesc 
     const bool writer = (threadIdx.x & 3u) == 1;
     if (with_leaves) {
         const u32 i = t < w ? t : w - 1;
-        Fr h = et_leaf_digest<Fr>(consts, leaf_d, leaves + (size_t)i * nf, nf);
+        Fr h = poseidon_leaf_sponge<Fr>(consts, leaf_d, leaves + (size_t)i * nf, nf);
         if (t < w && writer) fr_store(&nodes[off + t], h);
         __syncthreads();
     }

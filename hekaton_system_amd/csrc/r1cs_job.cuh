@@ -14,7 +14,9 @@
 //   k_rj_body    one lane per (row, column) over column 0 and the body columns, a row per blockIdx.y: a wave reads 64 consecutive
 //                Fr of one witness and stores 64 consecutive Fr of one row (the first lane of a row stores the constant 1).
 #pragma once
-#include "stage1.cuh"
+#include "curve_ops_impl.cuh"
+#include "job_args.h"
+#include "poseidon.cuh"         // fr_select
 
 namespace hk {
 
@@ -38,7 +40,7 @@ k_rj_trace(const Fr* __restrict__ wit, const u32* __restrict__ rank, const u32* 
     Fr a = Fr::zero();
     a.v[0] = 1u + g * sets_per_tx + rank[s];                       // below 2^32: the call checked 1 + T O
     a = Fr::to_mont(a);
-    fr_store(&out[t], et_select(is_val, et_select(k != HK_R1CS_SRC_ZERO, v, Fr::zero()), a));
+    fr_store(&out[t], fr_select(is_val, fr_select(k != HK_R1CS_SRC_ZERO, v, Fr::zero()), a));
 }
 
 // row blockIdx.y starts at wire 0 of its subcircuit's witness, wit + base[row]; lane c of the row: c == 0 -> column 0 <- 1,
@@ -49,7 +51,7 @@ k_rj_body(const Fr* __restrict__ wit, const u64* __restrict__ base, u32 per, siz
     const u32 c = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
     if (c >= per) return;
     Fr* row = z + (size_t)b * n_v;
-    const Fr x = et_select(c != 0, fr_load(&wit[base[b] + c]), Fr::one());
+    const Fr x = fr_select(c != 0, fr_load(&wit[base[b] + c]), Fr::one());
     fr_store(c ? &row[body_col0 + c - 1] : &row[0], x);
 }
 

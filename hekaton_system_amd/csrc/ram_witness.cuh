@@ -24,9 +24,10 @@
 //   k_rw_chunk_prod / k_rw_chunk_scan / k_rw_chain_walk   the two chains of a row in chunks of RW_CHUNK entries: the product of
 //                  each chunk's factors tr_chal - e, one lane per chain over the chunk products, then every chunk walked from
 //                  the evaluation in front of it: RW_CHUNK + K / RW_CHUNK + RW_CHUNK products in sequence instead of K.
-//   k_s1_membership<Fr, 6>   stage1.cuh's quad kernel with a six-field leaf.
+//   k_poseidon_membership<Fr, 6>   poseidon.cuh's quad kernel with a six-field leaf.
 #pragma once
-#include "stage1.cuh"
+#include "poseidon.cuh"
+#include "stage1.cuh"        // s1_prologue, EtChal
 
 namespace hk {
 
@@ -346,7 +347,8 @@ hk_status Ops<C>::ram_stage1_witness(hk_ctx* ctx, const hk_ram_stage1_desc* d, c
     hipLaunchKernelGGL((k_rw_chunk_prod<Fr>), blocks((u64)2 * batch * n_chunks), dim3(256), 0, s, a, ch, n_chunks, prods);
     hipLaunchKernelGGL((k_rw_chunk_scan<Fr>), dim3((2 * nb + 63) / 64), dim3(64), 0, s, a, (const Fr*)in[3].p, n_chunks, prods);
     hipLaunchKernelGGL((k_rw_chain_walk<Fr>), blocks((u64)2 * batch * n_chunks), dim3(256), 0, s, a, ch, n_chunks, (const Fr*)prods);
-    s1_membership<Fr, 6>(s, d, in[2].p, in[4].p, in[5].p, rows_d, batch, n_v, z_out);
+    poseidon_membership<Fr, 6>(s, in[2].p, d->leaf_hash, d->node_hash, in[4].p, in[5].p, rows_d, rows_d, 2, depth, batch, n_v,
+                               (size_t)d->pos_col0, z_out);
     HK_HIP(hipGetLastError());
     return L->settle();
 }

@@ -5,14 +5,12 @@
 //   k_s1_values      the three instance values and the portal block (10 k + 4 columns for k entries per order): copies, the two
 //                    running-evaluation chains, the address-step (inv, same) pairs.  One lane per (role, row), role-major, so
 //                    the lanes of a wave share a role: 4 k + 5 copies, 2 chains of k products, k inversions.
-//   k_s1_membership  the Poseidon membership block on a quad of lanes per row: poseidon_permute_quad with every S-box chain and
-//                    round state stored where k_poseidon_path's one lane stores them.
+//   k_poseidon_membership<Fr, 4>   the Poseidon membership block on a quad of lanes per row (poseidon.cuh).
 #pragma once
-#include "exec_tree.cuh"
+#include "exec_tree.cuh"     // EtChal, et_repr
+#include "poseidon.cuh"
 
 namespace hk {
-
-constexpr u32 S1_WG_ROWS = 64;         // rows of one 256-lane workgroup of k_s1_membership (a quad each)
 
 #if defined(__HIPCC__)
 
@@ -72,92 +70,6 @@ k_s1_values(const Fr* __restrict__ time_e, const Fr* __restrict__ addr_e, const 
     }
 }
 
-// poseidon_permute_quad with the trace of poseidon_permute_trace: in a round that starts at w, lane i < T stores its S-box
-// chain (L = 3 values at ALPHA 5, 5 at 17) at w + i L + step when the round is full or i = 0, and its new state element at
-// w + (full ? T : 1) L + i; w advances by the same amount on every lane.  `store` is false on the lanes of a quad past the
-// batch and on the fourth lane at T = 3: they compute along (every lane of a quad is in every DPP exchange) and write nothing.
-template <class Fr, int T, int ALPHA>
-__device__ __forceinline__ Fr s1_permute_quad_trace(const Fr* __restrict__ consts, const PoseidonDesc& d, Fr s, bool store,
-                                                    Fr*& w) {
-    static_assert(T == 3 || T == 4, "one state element per lane of a quad");
-    constexpr u32 L = ALPHA == 5 ? 3 : 5;
-    const u32 q = threadIdx.x & 3u;
-    const u32 qc = q < (u32)T ? q : 0u;
-    const Fr* ark = consts + d.off;
-    const Fr* mds = ark + (size_t)(d.rf + d.rp) * T;
-    const u32 rounds = d.rf + d.rp, half = d.rf / 2;
-    const bool mine = store && q < (u32)T;
-    Fr m[T];
-    HK_UNROLL for (int j = 0; j < T; j++) m[j] = fr_load(&mds[qc * T + j]);
-    Fr k = fr_load(&ark[qc]);
-    HK_NOUNROLL for (u32 r = 0; r < rounds; r++) {
-        const bool full = r < half || r >= half + d.rp;
-        const bool keep = full || q == 0;
-        const bool trace = mine && keep;
-        Fr* c = w + qc * L;
-        Fr y = Fr::add(s, k);
-        k = fr_load(&ark[(r + 1 < rounds ? r + 1 : r) * T + qc]);       // the next round's constant, under this round's products
-        Fr x = Fr::mul(y, y);
-        if (trace) fr_store(c++, x);
-        HK_UNROLL for (int e = 0; e < (ALPHA == 5 ? 1 : 3); e++) {
-            x = Fr::mul(x, x);
-            if (trace) fr_store(c++, x);
-        }
-        x = Fr::mul(x, y);
-        if (trace) fr_store(c, x);
-        x = et_select(keep, x, y);
-        s = Fr::mul(m[0], et_quad_bcast<Fr, 0x00>(x));
-        s = Fr::add(s, Fr::mul(m[1], et_quad_bcast<Fr, 0x55>(x)));
-        s = Fr::add(s, Fr::mul(m[2], et_quad_bcast<Fr, 0xAA>(x)));
-        if constexpr (T == 4) s = Fr::add(s, Fr::mul(m[3], et_quad_bcast<Fr, 0xFF>(x)));
-        w += (full ? (u32)T : 1u) * L;
-        if (mine) fr_store(&w[qc], s);
-        w += T;
-    }
-    return s;
-}
-
-// One quad per row: the membership block of subcircuit i = rows[2 b] - leaf leaves[i], path siblings[i], index i - in the order
-// of k_poseidon_path / sha_circuit.poseidon_path_trace, at column pos_col0 of row b.  A quad past the batch recomputes the last
-// row and stores nothing: no lane leaves in front of a DPP read.
-// NF = 4 (a ROM leaf) or 6 (a RAM leaf: hk_ram_stage1_witness): the second absorption adds leaf[3 .. NF) to lanes 1 .. NF - 3.
-template <class Fr, int NF>
-__global__ void __launch_bounds__(256)
-k_s1_membership(const Fr* __restrict__ consts, PoseidonDesc leaf_d, PoseidonDesc node_d, const Fr* __restrict__ leaves,
-                const Fr* __restrict__ siblings, const u32* __restrict__ rows, u32 depth, u32 batch, size_t n_v, size_t pos_col0,
-                Fr* __restrict__ z_out) {
-    const u32 t = (blockIdx.x * blockDim.x + threadIdx.x) >> 2;
-    const u32 q = threadIdx.x & 3u;
-    const bool store = t < batch;
-    const u32 b = store ? t : batch - 1;
-    const u32 i = rows[2 * b];
-    static_assert(NF == 4 || NF == 6, "an execution leaf has 2 + entry_fields fields");
-    const Fr* leaf = leaves + (size_t)i * NF;
-    Fr* w = z_out + (size_t)b * n_v + pos_col0;
-    // the rate-3 sponge over the NF leaf fields (et_leaf_digest with the trace): every lane loads an index it may read
-    Fr s = et_select(q != 0, fr_load(&leaf[q ? q - 1 : 0]), Fr::zero());
-    s = s1_permute_quad_trace<Fr, 4, 5>(consts, leaf_d, s, store, w);
-    if constexpr (NF == 4)
-        s = Fr::add(s, et_select(q == 1, fr_load(&leaf[3]), Fr::zero()));
-    else
-        s = Fr::add(s, et_select(q != 0, fr_load(&leaf[q ? 2 + q : 3]), Fr::zero()));
-    s = s1_permute_quad_trace<Fr, 4, 5>(consts, leaf_d, s, store, w);
-    Fr cur = et_quad_bcast<Fr, 0x55>(s);
-    HK_NOUNROLL for (u32 l = 0; l < depth; l++) {
-        const Fr sib = fr_load(&siblings[(size_t)i * depth + l]);
-        const bool bit = (i >> l) & 1u;
-        const Fr left = et_select(bit, sib, cur), right = et_select(bit, cur, sib);
-        // bit / sibling / left: lane 0, 1, 2 one each
-        Fr v = et_select(q == 1, sib, left);
-        v = et_select(q == 0, bit ? Fr::one() : Fr::zero(), v);
-        if (store && q < 3) fr_store(&w[q], v);
-        w += 3;
-        s = et_select(q == 1, left, et_select(q == 2, right, Fr::zero()));
-        s = s1_permute_quad_trace<Fr, 3, 17>(consts, node_d, s, store, w);
-        cur = et_quad_bcast<Fr, 0x55>(s);
-    }
-}
-
 #endif  // __HIPCC__
 
 // What hk_stage1_witness and hk_ram_stage1_witness check alike of a descriptor D (hk_stage1_desc / hk_ram_stage1_desc: the same
@@ -178,16 +90,6 @@ hk_status s1_prologue(const D* d, const uint32_t* sub_index, size_t batch, const
         if (k < n_chal) memcpy(&ch.c[k], (const char*)d->challenges_mont + k * sizeof(Fr), sizeof(Fr));
     }
     return HK_OK;
-}
-
-// the membership block of every row, behind the kernels that fill the row's other columns (same stream)
-template <class Fr, int NF, class D>
-void s1_membership(hipStream_t s, const D* d, const void* consts, const void* leaves, const void* siblings, const u32* rows_d,
-                   size_t batch, size_t n_v, void* z_out) {
-    const u32 nb = (u32)batch;
-    hipLaunchKernelGGL((k_s1_membership<Fr, NF>), dim3((nb + S1_WG_ROWS - 1) / S1_WG_ROWS), dim3(256), 0, s, (const Fr*)consts,
-                       poseidon_desc(d->leaf_hash), poseidon_desc(d->node_hash), (const Fr*)leaves, (const Fr*)siblings, rows_d,
-                       (u32)d->depth, nb, n_v, (size_t)d->pos_col0, (Fr*)z_out);
 }
 
 template <class C>
@@ -225,7 +127,8 @@ hk_status Ops<C>::stage1_witness(hk_ctx* ctx, const hk_stage1_desc* d, const uin
     const u32 nb = (u32)batch, lanes = (u32)((7 + 5 * K) * batch);
     hipLaunchKernelGGL((k_s1_values<Fr>), dim3((lanes + 255) / 256), dim3(256), 0, s, tp, ap, (const u32*)rows_d, nb, (u32)K, ch,
                        (const Fr*)in[3].p, (const Fr*)in[6].p, n_v, (size_t)d->inst_col0, (size_t)d->col0, (Fr*)z_out);
-    s1_membership<Fr, 4>(s, d, in[2].p, in[4].p, in[5].p, rows_d, batch, n_v, z_out);
+    poseidon_membership<Fr, 4>(s, in[2].p, d->leaf_hash, d->node_hash, in[4].p, in[5].p, rows_d, rows_d, 2, depth, batch, n_v,
+                               (size_t)d->pos_col0, z_out);
     HK_HIP(hipGetLastError());
     return L->settle();
 }

@@ -19,11 +19,12 @@
 //   k_vkd_leaf_bits  one lane per (row, bit column of the leaf), column fastest.
 //   k_vkd_body     one quad per (row, primitive chain), the chain a grid row: a leaf hash, a username hash or the L hashes of
 //                  a segment, with every S-box chain value and round state stored in poseidon_path_trace order
-//                  (s1_permute_quad_trace) and the `bits` / `canon` columns from integer tests of the canonical limbs.
+//                  (poseidon_permute_quad with TRACE) and the `bits` / `canon` columns from integer tests of the canonical limbs.
 // A quad past the end recomputes the last one and stores nothing: every lane of a quad is in every DPP exchange, only stores
 // are guarded.  No limb array is indexed by a run-time value: no private memory.
 #pragma once
-#include "stage1.cuh"
+#include "curve_ops_impl.cuh"
+#include "poseidon.cuh"
 
 namespace hk {
 
@@ -104,8 +105,8 @@ __device__ __forceinline__ Fr vkd_hash_quad(const Fr* __restrict__ consts, const
                                             u32 n) {
     const u32 q = threadIdx.x & 3u;
     const Fr c = Fr::to_mont(vkd_chunk<Fr>(p, n, q ? q - 1 : 0u));
-    Fr s = poseidon_permute_quad<Fr, 4, 5>(consts, d, et_select(q != 0, c, Fr::zero()));
-    return et_quad_bcast<Fr, 0x55>(s);
+    Fr s = poseidon_permute_quad<Fr, 4, 5>(consts, d, fr_select(q != 0, c, Fr::zero()));
+    return quad_bcast<Fr, 0x55>(s);
 }
 
 // jobs of k_vkd_hash: 0 the null leaf (32 zero bytes: `zeros`); 1 + 3 u + j: j = 0 leaf_old, 1 leaf_new, 2 the username
@@ -126,7 +127,7 @@ k_vkd_hash(const Fr* __restrict__ consts, PoseidonDesc leaf_d, const unsigned ch
     if (job == 0 || j < 2) {
         // an append has no old leaf: its entry is 0
         const bool none = job && j == 0 && kinds[u] == HK_VKD_APPEND;
-        const Fr node = et_select(none, Fr::zero(), Fr::to_mont(vkd_mask_node(d)));
+        const Fr node = fr_select(none, Fr::zero(), Fr::to_mont(vkd_mask_node(d)));
         if (store && q == 0) fr_store(&values[job ? base + j : 2u], node);
     } else {
         HK_NOUNROLL for (u32 s0 = 0; s0 < split; s0 += 4) {
@@ -156,10 +157,9 @@ k_vkd_chain(const Fr* __restrict__ consts, PoseidonDesc node_d, const Fr* __rest
     HK_NOUNROLL for (u32 l = 0; l < depth; l++) {
         const Fr sib = fr_load(&siblings[(size_t)u * depth + l]);
         const bool bit = (index_raw[(size_t)u * 8 + (l >> 5)] >> (l & 31u)) & 1u;
-        const Fr left = et_select(bit, sib, cur), right = et_select(bit, cur, sib);
-        Fr s = et_select(q == 1, left, et_select(q == 2, right, Fr::zero()));
-        s = poseidon_permute_quad<Fr, 3, 17>(consts, node_d, s);
-        cur = Fr::to_mont(vkd_mask_node(Fr::from_mont(et_quad_bcast<Fr, 0x55>(s))));
+        const Fr left = fr_select(bit, sib, cur), right = fr_select(bit, cur, sib);
+        Fr s = poseidon_permute_quad<Fr, 3, 17>(consts, node_d, poseidon_pair_input(left, right));
+        cur = Fr::to_mont(vkd_mask_node(Fr::from_mont(quad_bcast<Fr, 0x55>(s))));
         if (++in_seg == L) {                                             // uniform over the grid
             if (store && q == 0) fr_store(out, cur);
             out++;
@@ -181,7 +181,7 @@ k_vkd_trace(const Fr* __restrict__ values, const u32* __restrict__ slot_addr, co
     Fr a = Fr::zero();
     a.v[0] = slot_addr[e];
     a = Fr::to_mont(a);
-    fr_store(&out[t], et_select(is_val, et_select(k != HK_VKD_SRC_ZERO, v, Fr::zero()), a));
+    fr_store(&out[t], fr_select(is_val, fr_select(k != HK_VKD_SRC_ZERO, v, Fr::zero()), a));
 }
 
 // ---- the body columns --------------------------------------------------------------------------------------------------
@@ -253,8 +253,8 @@ k_vkd_body(const Fr* __restrict__ consts, PoseidonDesc leaf_d, PoseidonDesc node
     if (which != VKD_CH_PATH) {
         const u32 n = which == VKD_CH_HASH ? VKD_LEAF_BYTES : VKD_NAME_BYTES;
         const Fr c = Fr::to_mont(vkd_chunk<Fr>(leaves + row.leaf_off, n, q ? q - 1 : 0u));
-        Fr s = s1_permute_quad_trace<Fr, 4, 5>(consts, leaf_d, et_select(q != 0, c, Fr::zero()), store, w);
-        vkd_digest_cols<Fr>(Fr::from_mont(et_quad_bcast<Fr, 0x55>(s)), w, store);
+        Fr s = poseidon_permute_quad<Fr, 4, 5, true>(consts, leaf_d, fr_select(q != 0, c, Fr::zero()), store, w);
+        vkd_digest_cols<Fr>(Fr::from_mont(quad_bcast<Fr, 0x55>(s)), w, store);
         return;
     }
     Fr cur = fr_load(&values[row.init_src]);
@@ -268,12 +268,11 @@ k_vkd_body(const Fr* __restrict__ consts, PoseidonDesc leaf_d, PoseidonDesc node
     HK_NOUNROLL for (u32 l = 0; l < L; l++) {
         const Fr sib = fr_load(&siblings[(size_t)row.sib_off + l]);
         const bool bit = (vkd_limb(word, l >> 5) >> (l & 31u)) & 1u;
-        const Fr left = et_select(bit, sib, cur), right = et_select(bit, cur, sib);
-        if (store && q < 2) fr_store(&w[q], et_select(q == 0, sib, left));
+        const Fr left = fr_select(bit, sib, cur), right = fr_select(bit, cur, sib);
+        if (store && q < 2) fr_store(&w[q], fr_select(q == 0, sib, left));
         w += 2;
-        Fr s = et_select(q == 1, left, et_select(q == 2, right, Fr::zero()));
-        s = s1_permute_quad_trace<Fr, 3, 17>(consts, node_d, s, store, w);
-        const Fr d = Fr::from_mont(et_quad_bcast<Fr, 0x55>(s));
+        Fr s = poseidon_permute_quad<Fr, 3, 17, true>(consts, node_d, poseidon_pair_input(left, right), store, w);
+        const Fr d = Fr::from_mont(quad_bcast<Fr, 0x55>(s));
         vkd_digest_cols<Fr>(d, w, store);
         w += NB + NC;
         cur = Fr::to_mont(vkd_mask_node(d));

@@ -136,10 +136,9 @@ __device__ __forceinline__ void vt_level(const Fr* consts, const PoseidonDesc& n
     const u32 pred = ord[c ? lo - 1 : t];
     const Fr sv = fr_load(c ? &nin[pred] : &empty[l]);
     const Fr cur = fr_load(&nin[e]);
-    const Fr left = et_select(bit, sv, cur), right = et_select(bit, cur, sv);
-    Fr st = et_select(q == 1, left, et_select(q == 2, right, Fr::zero()));
-    st = poseidon_permute_quad<Fr, 3, 17>(consts, node_d, st);
-    const Fr nxt = Fr::to_mont(vkd_mask_node(Fr::from_mont(et_quad_bcast<Fr, 0x55>(st))));
+    const Fr left = fr_select(bit, sv, cur), right = fr_select(bit, cur, sv);
+    const Fr st = poseidon_permute_quad<Fr, 3, 17>(consts, node_d, poseidon_pair_input(left, right));
+    const Fr nxt = Fr::to_mont(vkd_mask_node(Fr::from_mont(quad_bcast<Fr, 0x55>(st))));
     const u32 ps = sib && bit ? ss : s, pe = sib && !bit ? se : end;             // the merged run
     const u32 np = ps + (t - s) + c;
     if (store && q == 0 && np < E) {                                             // np < E: a permutation of the positions
@@ -157,14 +156,12 @@ template <class Fr>
 __global__ void __launch_bounds__(64)
 k_vt_empty(const Fr* __restrict__ consts, PoseidonDesc leaf_d, PoseidonDesc node_d, const unsigned char* __restrict__ zeros,
            u32 depth, Fr* __restrict__ empty) {
-    const u32 q = threadIdx.x & 3u;
     const bool writer = threadIdx.x == 0;
     Fr cur = Fr::to_mont(vkd_mask_node(Fr::from_mont(vkd_hash_quad<Fr>(consts, leaf_d, zeros, VKD_NAME_BYTES))));
     if (writer) fr_store(&empty[0], cur);
     HK_NOUNROLL for (u32 l = 0; l < depth; l++) {
-        Fr s = et_select(q == 1 || q == 2, cur, Fr::zero());
-        s = poseidon_permute_quad<Fr, 3, 17>(consts, node_d, s);
-        cur = Fr::to_mont(vkd_mask_node(Fr::from_mont(et_quad_bcast<Fr, 0x55>(s))));
+        const Fr s = poseidon_permute_quad<Fr, 3, 17>(consts, node_d, poseidon_pair_input(cur, cur));
+        cur = Fr::to_mont(vkd_mask_node(Fr::from_mont(quad_bcast<Fr, 0x55>(s))));
         if (writer) fr_store(&empty[l + 1], cur);
     }
 }

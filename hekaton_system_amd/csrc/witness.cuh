@@ -13,7 +13,7 @@
 // A subcircuit's assignment never exists on the host and crosses PCIe as its inputs (64 .. 216 B) + ~1.3 KB.
 #pragma once
 #include "hk_internal.h"
-#include "job_args.h"
+#include "ntt.cuh"           // fr_load, fr_store
 
 namespace hk {
 
@@ -150,84 +150,6 @@ __global__ void k_scatter_full_batch(const u32* __restrict__ cols, const Fr* __r
     if (j >= k) return;
     u32 c = cols[j];
     if (c < n_v) fr_store(&z_out[(size_t)b * n_v + c], fr_load(&vals[(size_t)b * k + j]));
-}
-
-// ---- Poseidon membership block (execution tree, subcircuit_circuit.rs:233-252) --------------------------------------
-// PoseidonDesc, the host-side description of one Poseidon instance of the tree, and poseidon_trace_len: job_args.h.
-
-// Width and S-box exponent are template parameters: the state, the round's S-box outputs and the MDS row sums stay in
-// registers (with runtime widths they were runtime-indexed arrays in private memory and the block took 20 ms per step).
-template <class Fr, int T, int ALPHA>
-__device__ __forceinline__ void poseidon_permute_trace(const Fr* __restrict__ consts, const PoseidonDesc& d, Fr (&s)[T],
-                                                       Fr*& w) {
-    const Fr* ark = consts + d.off;
-    const Fr* mds = ark + (size_t)(d.rf + d.rp) * T;
-    const u32 half = d.rf / 2;
-    Fr m[T * T];
-#pragma unroll
-    for (int i = 0; i < T * T; i++) m[i] = fr_load(&mds[i]);
-    HK_NOUNROLL for (u32 r = 0; r < d.rf + d.rp; r++) {
-        bool full = r < half || r >= half + d.rp;
-        Fr y[T];
-#pragma unroll
-        for (int i = 0; i < T; i++) y[i] = Fr::add(s[i], fr_load(&ark[r * T + i]));
-#pragma unroll
-        for (int i = 0; i < T; i++) {
-            if (i == 0 || full) {
-                Fr u = y[i];
-                Fr x = Fr::mul(u, u);                       // u^2
-                fr_store(w++, x);
-#pragma unroll
-                for (int k = 0; k < (ALPHA == 5 ? 1 : 3); k++) { x = Fr::mul(x, x); fr_store(w++, x); }   // u^4 (u^8 u^16)
-                x = Fr::mul(x, u);                          // u^5 / u^17
-                fr_store(w++, x);
-                y[i] = x;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < T; i++) {
-            Fr acc = Fr::mul(m[i * T], y[0]);
-#pragma unroll
-            for (int j = 1; j < T; j++) acc = Fr::add(acc, Fr::mul(m[i * T + j], y[j]));
-            s[i] = acc;
-        }
-#pragma unroll
-        for (int i = 0; i < T; i++) fr_store(w++, s[i]);
-    }
-}
-
-// One lane per subcircuit: the witnesses of its membership block, in the order sha_circuit.poseidon_path_trace lists
-// them - the leaf hash (sponge of rate 3 over the 4 leaf fields: two permutations), then per level the bit, the sibling,
-// the left input and the two-to-one hash - written straight into the assignment at column col0.
-// leaf: [batch][4], siblings: [batch][depth], index: [batch]; z: [batch][n_v].
-template <class Fr>
-__global__ void __launch_bounds__(64)
-k_poseidon_path(const Fr* __restrict__ consts, PoseidonDesc leaf_d, PoseidonDesc node_d, const Fr* __restrict__ leaf,
-                const Fr* __restrict__ siblings, const u32* __restrict__ index, u32 depth, u32 batch, size_t n_v,
-                size_t col0, Fr* __restrict__ z) {
-    u32 b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= batch) return;
-    Fr* w = z + (size_t)b * n_v + col0;
-    Fr s[4];
-    s[0] = Fr::zero();
-    for (u32 i = 0; i < 3; i++) s[1 + i] = fr_load(&leaf[(size_t)b * 4 + i]);
-    poseidon_permute_trace<Fr, 4, 5>(consts, leaf_d, s, w);
-    s[1] = Fr::add(s[1], fr_load(&leaf[(size_t)b * 4 + 3]));
-    poseidon_permute_trace<Fr, 4, 5>(consts, leaf_d, s, w);
-    Fr cur = s[1];
-    u32 idx = index[b];
-    HK_NOUNROLL for (u32 l = 0; l < depth; l++) {
-        Fr sib = fr_load(&siblings[(size_t)b * depth + l]);
-        bool bit = (idx >> l) & 1u;
-        Fr left = bit ? sib : cur, right = bit ? cur : sib;
-        fr_store(w++, bit ? Fr::one() : Fr::zero());
-        fr_store(w++, sib);
-        fr_store(w++, left);
-        Fr t3[3];
-        t3[0] = Fr::zero(); t3[1] = left; t3[2] = right;
-        poseidon_permute_trace<Fr, 3, 17>(consts, node_d, t3, w);
-        cur = t3[1];
-    }
 }
 
 #endif  // __HIPCC__

@@ -1,8 +1,10 @@
 // witness_host.cuh — assignments built on the device: bit expansion, word programs and Poseidon Merkle paths (kernels in
-// witness.cuh).  Defines Ops<C>::assignment_from_bits (hk_assignment_from_bits), wprog_upload / wprog_free / wprog_run
+// witness.cuh; the membership walk in poseidon.cuh).  Defines Ops<C>::assignment_from_bits (hk_assignment_from_bits), wprog_upload / wprog_free / wprog_run
 // (hk_wprog_*), assignment_scatter (hk_assignment_scatter), poseidon_path (hk_poseidon_path).
 #pragma once
 #include "curve_ops_impl.cuh"
+#include "job_args.h"
+#include "poseidon.cuh"
 #include "witness.cuh"
 
 namespace hk {
@@ -188,9 +190,8 @@ hk_status Ops<C>::poseidon_path(hk_ctx* ctx, const void* consts, size_t n_consts
     HK_TRY(L->carve([&](Carve& c) { stage_carve(c, in, 4); }));
     const void *cd = in[0].p, *ld = in[1].p, *sd = in[2].p, *id = in[3].p;
     HK_TRY(stage_upload(L, in, 4));
-    const PoseidonDesc a = poseidon_desc(lh), b = poseidon_desc(nh);
-    hipLaunchKernelGGL((k_poseidon_path<Fr>), dim3((u32)((batch + 63) / 64)), dim3(64), 0, L->stream, (const Fr*)cd, a, b,
-                       (const Fr*)ld, (const Fr*)sd, (const u32*)id, (u32)depth, (u32)batch, n_v, col0, (Fr*)z_out);
+    // row b is its own source: leaf b, path b, direction bits from index[b]
+    poseidon_membership<Fr, 4>(L->stream, cd, lh, nh, ld, sd, nullptr, (const u32*)id, 1, depth, batch, n_v, col0, z_out);
     HK_HIP(hipGetLastError());
     return L->settle();
 }

@@ -25,7 +25,7 @@ ONE = 0                       # column of the constant 1
 
 
 def poseidon_path_trace(leaf_cfg, node_cfg, leaf, siblings, index):
-    """Every witness of the membership block of one subcircuit, in allocation order (= what `k_poseidon_path` writes):
+    """Every witness of the membership block of one subcircuit, in allocation order (= what `k_poseidon_membership` writes):
     the leaf hash's permutation traces, then per level (bit, sibling, left, the two-to-one hash's trace).  The last
     value is the root the path leads to."""
     out = []

@@ -14,7 +14,7 @@ partial) instance - first round constants, first MDS entry and poseidon([1, 2]) 
 PARITY UNPINNED: the reference's own instances (alpha 17 at rate 2; 56 partial rounds at rate 3) have no published
 vectors, and the sponge's state layout (capacity element at index 0, output = state[1], one permutation per full block
 and one before the squeeze) is remembered from ark's source, not checked against it.  The circuit gadget
-(sha_circuit.py) and the GPU witness kernel (csrc/witness.cuh `k_poseidon_path`) are checked against THIS module bit for
+(sha_circuit.py) and the GPU witness kernel (csrc/poseidon.cuh `k_poseidon_membership`) are checked against THIS module bit for
 bit.
 """
 from functools import lru_cache

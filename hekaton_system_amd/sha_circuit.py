@@ -1040,7 +1040,7 @@ def full_values(circ, inputs):
         for k in range(1, len(chain)):
             d = (chain[k][0] - chain[k - 1][0]) % r
             vals += [pow(d, -1, r) if d else 0, 0 if d else 1]; c_local += [col, col + 1]; col += 2
-        assert col == circ.pos_col0                       # the membership block follows: k_poseidon_path fills it
+        assert col == circ.pos_col0                       # the membership block follows: k_poseidon_membership fills it
         if circ.kind == "root":
             vals.append(w["sha_root"]); c_local.append(circ.sha_root_col)
         rows.append(circ.fc.enc(vals))

@@ -263,7 +263,7 @@ def test_assignment_materialised_on_the_device_equals_the_host_bytes(ctx_bn254):
 
 @pytest.mark.parametrize("kind,macro", [("leaf", True), ("parent", True), ("parent", False)])
 def test_witness_generated_on_the_device_equals_the_host_trace(kind, macro, ctx_bn254, monkeypatch):
-    """hk_wprog_upload / hk_wprog_run + hk_poseidon_path (csrc/witness.cuh): the class's word program interpreted on the
+    """hk_wprog_upload / hk_wprog_run + hk_poseidon_path (csrc/witness.cuh, csrc/poseidon.cuh): the class's word program interpreted on the
     GPU from the subcircuits' inputs, and the Poseidon membership block computed on the GPU from the execution leaf and
     its path, give bit for bit the assignments the host trace emits (themselves checked against hashlib, poseidon.py and
     the R1CS on the CPU); then a proof from the device-generated assignment verifies."""

@@ -173,7 +173,7 @@ def test_word_program_reproduces_the_trace(kind):
     got = ((vals[vmap[mask] >> 5] >> (vmap[mask] & 31)[:, None]) & 1).T.astype(np.uint8)
     assert np.array_equal(got, bits_ref[:, mask])
     cols, fv = full_values(circ, ws)
-    # full-width columns = the host-computed values + the membership block (filled by k_poseidon_path on the device, by
+    # full-width columns = the host-computed values + the membership block (filled by k_poseidon_membership on the device, by
     # poseidon_path_trace here)
     block = list(range(circ.pos_col0, circ.pos_col0 + circ.pos_cols))
     assert sorted(cols.tolist() + block) == sorted([1, 2, 3] + list(full_ref.keys()))

@@ -250,7 +250,9 @@ def test_sha_merkle_job_stage1_device_fills_every_class(curve, ctx_bn254, ctx_bl
     for i in range(job.n):
         classes.setdefault(job.class_of(i), []).append(i)
     assert len(classes) == 5
-    params = device_params(curve, FrCodec(curve))
+    fc = FrCodec(curve)
+    params = device_params(curve, fc)
+    leaf_cfg, node_cfg = merkle_params(curve)
     for key, members in classes.items():
         circ = job.make_class(members[0])
         prefill = _pattern(len(members) * circ.n_v * 32, seed=len(members))
@@ -270,6 +272,11 @@ def test_sha_merkle_job_stage1_device_fills_every_class(curve, ctx_bn254, ctx_bl
         z_new.free()
         assert (got == want).all(), key
         assert not (got == prefill).all()
+        # both sides above run one membership kernel: the block itself against the host trace
+        rows = got.reshape(len(members), circ.n_v, ctx.fr_bytes)
+        for m, w in enumerate(ws):
+            trace = poseidon_path_trace(leaf_cfg, node_cfg, fc.dec(leaves[m]), [s % r for s in w["path"][0]], w["path"][1])
+            assert fc.dec(rows[m, circ.pos_col0:circ.pos_col0 + len(trace)].reshape(-1)) == trace, (key, members[m])
     dev.free()
 
 

@@ -5,9 +5,10 @@ Per curve and shape (n_sub subcircuits x k entries per order, every subcircuit s
 hk_stage1_witness call over hk_exec_tree's outputs and the two traces, all resident on the device (median of --reps runs
 after --warmup), and beside it the parent path on the same inputs in the same run - sha_circuit.full_values +
 poseidon_inputs on the host (run once), then hk_assignment_scatter + hk_poseidon_path with the host arrays they return
-(median of --reps).  hk_poseidon_path over the device-resident leaves and siblings is timed too: the one-lane membership
-kernel alone, to set against the quad form inside the new call.  The two assignments are compared byte for byte before a row
-is written.  One JSON line per row, appended to profiles/stage1_witness_bench.jsonl (--out).
+(median of --reps).  hk_poseidon_path over the device-resident leaves and siblings is timed too: the membership kernel
+alone (the same quad kernel the new call launches; rows before this one in the jsonl timed the retired one-lane kernel
+here), with the minimum and maximum over its repetitions as its spread.  The two assignments are compared byte for byte
+before a row is written.  One JSON line per row, appended to profiles/stage1_witness_bench.jsonl (--out).
 
     python tools/stage1_witness_bench.py [--curves bn254,bls12_381] [--shapes 64x4,1024x4]
 """
@@ -42,7 +43,7 @@ def _median_ms(ctx, fn, warmup, reps):
         fn()
         if i >= warmup:
             wall.append((time.perf_counter() - t0) * 1e3)
-    return round(statistics.median(wall), 3), round(min(wall), 3)
+    return round(statistics.median(wall), 3), round(min(wall), 3), round(max(wall), 3)
 
 
 def bench_shape(ctx, curve, n_sub, k, warmup, reps):
@@ -84,25 +85,26 @@ def bench_shape(ctx, curve, n_sub, k, warmup, reps):
     z_new = capi.DeviceBuffer.from_host(ctx, np.zeros(n_sub * n_v * ctx.fr_bytes, np.uint8))
     scatter = lambda: capi.check(ctx.lib.hk_assignment_scatter(ctx.handle, cols.ctypes.data, vals.ctypes.data, cols.size, n_sub,
                                                                n_v, z_ref.ptr), "hk_assignment_scatter")
-    scatter_ms, _ = _median_ms(ctx, scatter, warmup, reps)
-    path_ms, _ = _median_ms(ctx, lambda: ctx.poseidon_path(params_d, leaves, sibs, idx, n_v, pos_col0, z_ref), warmup, reps)
-    path_res_ms, _ = _median_ms(ctx, lambda: ctx.poseidon_path(params_d, outs[1], outs[3], idx, n_v, pos_col0, z_ref), warmup,
-                                reps)
+    scatter_ms, _, _ = _median_ms(ctx, scatter, warmup, reps)
+    path_ms, _, _ = _median_ms(ctx, lambda: ctx.poseidon_path(params_d, leaves, sibs, idx, n_v, pos_col0, z_ref), warmup, reps)
+    path_res = lambda: ctx.poseidon_path(params_d, outs[1], outs[3], idx, n_v, pos_col0, z_ref)
+    path_res_ms, path_res_min, path_res_max = _median_ms(ctx, path_res, warmup, reps)
     rows = np.arange(n_sub, dtype=np.uint32)
     new = lambda: ctx.stage1_witness(params_d, k, offsets, res[0], res[1], chal_b, outs, rows, n_v, (1, N_INST, pos_col0), z_new)
-    new_ms, new_min = _median_ms(ctx, new, warmup, reps)
+    new_ms, new_min, new_max = _median_ms(ctx, new, warmup, reps)
     want, got = z_ref.to_host().reshape(n_sub, n_v, 32), z_new.to_host().reshape(n_sub, n_v, 32)
     assert (got[:, 1:] == want[:, 1:]).all(), "hk_stage1_witness differs from the parent path"
     for x in res + list(outs) + [z_ref, z_new]:
         x.free()
     host_ms = (t2 - t0) * 1e3
     row = dict(curve=curve, n_sub=n_sub, n_portals=k, depth=depth, n_v=n_v, reps=reps, warmup=warmup,
-               stage1_witness_wall_ms=new_ms, stage1_witness_wall_ms_min=new_min,
+               stage1_witness_wall_ms=new_ms, stage1_witness_wall_ms_min=new_min, stage1_witness_wall_ms_max=new_max,
                host_full_values_ms=round((t1 - t0) * 1e3, 2), host_poseidon_inputs_ms=round((t2 - t1) * 1e3, 2),
                assignment_scatter_wall_ms=scatter_ms, poseidon_path_wall_ms=path_ms,
-               parent_path_ms=round(host_ms + scatter_ms + path_ms, 3), poseidon_path_resident_wall_ms=path_res_ms)
+               parent_path_ms=round(host_ms + scatter_ms + path_ms, 3), poseidon_path_resident_wall_ms=path_res_ms,
+               poseidon_path_resident_wall_ms_min=path_res_min, poseidon_path_resident_wall_ms_max=path_res_max)
     row["device_faster"] = row["stage1_witness_wall_ms"] < row["parent_path_ms"]
-    row["quad_call_faster_than_one_lane_membership"] = row["stage1_witness_wall_ms"] < row["poseidon_path_resident_wall_ms"]
+    row["call_faster_than_membership_alone"] = row["stage1_witness_wall_ms"] < row["poseidon_path_resident_wall_ms"]
     return row
 
 
@@ -112,6 +114,7 @@ def main():
     ap.add_argument("--shapes", default="64x4,1024x4")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--build", default=None, help="a name for the library under test, kept in every row (HK_LIB builds)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stage1_witness_bench.jsonl"))
     a = ap.parse_args()
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
@@ -120,6 +123,8 @@ def main():
             for s in a.shapes.split(","):
                 n_sub, k = (int(x) for x in s.split("x"))
                 row = bench_shape(ctx, curve, n_sub, k, a.warmup, a.reps)
+                if a.build:
+                    row["build"] = a.build
                 print(json.dumps(row), flush=True)
                 with open(a.out, "a") as f:
                     f.write(json.dumps(row) + "\n")
