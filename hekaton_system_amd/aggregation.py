@@ -102,9 +102,11 @@ class IppCom:
         return IppCom(self.F, res[0], res[1], res[2] if len(res) > 2 else None, self.ctx)
 
     @staticmethod
-    def lincomb(terms):
+    def lincomb(terms, in_gt=True):
         """sum_k com_k * scalar_k (additive notation) with every GT power of the sum in ONE hk_gt_pow call.
-        terms: [(IppCom, int scalar or None for 1)]."""
+        terms: [(IppCom, int scalar or None for 1)].  in_gt=False: the plain chain (hk_gt_pow_prod's in_gt = 0) for members
+        of unknown provenance - a verifier's inputs; the default splits the exponents along the Frobenius, which is a power
+        only for members of order r."""
         F = terms[0][0].F
         ctx = next((c.ctx for c, _ in terms if c.ctx is not None), None)
         has_ip = any(com.ip is not None for com, _ in terms)
@@ -119,7 +121,7 @@ class IppCom:
                     bases.append(parts[j] if parts[j] is not None else F.one)
                     exps.append(k if parts[j] is not None else 0)
             out = ctx.gt_pow_prod(np.frombuffer(b"".join(F.encode(x) for x in bases), np.uint8), FrCodec(ctx.curve).enc(exps),
-                                  len(terms))
+                                  len(terms), in_gt)
             res = [F.decode(out[j]) for j in range(len(out))]
         else:
             res = []
@@ -207,26 +209,27 @@ class AggProvingKey:
         self.com_h, self.com_delta0, self.com_delta1 = (IppCom(self.F, D(o[2 * k + 2 * c]), D(o[2 * k + 1 + 2 * c]), ctx=ctx)
                                                         for c in range(3))
 
-    def agg_subcircuit_proofs(self, pt, super_com, proofs, pub_inputs, srs, tipp=None, check=True):
+    def agg_subcircuit_proofs(self, pt, super_com, proofs, pub_inputs, srs, tipp=None, check=True, assert_products=True):
         """aggregation.rs:138-345 whole: the challenges come from the merlin transcript `pt` (merlin.Transcript) exactly
         where the reference draws them (:219-222, :276-278), then `TIPA::prove` and, as the reference does (:340), the
-        aggregator verifies its own proof.  Returns (tipp_proof, instance dict)."""
+        aggregator verifies its own proof.  assert_products: as in agg_front.  Returns (tipp_proof, instance dict)."""
         from . import tipa
         tipp = tipp or tipa.Tipp(self.ctx, self.curve)
-        inst = self.agg_front(super_com, proofs, pub_inputs, pt=pt)
+        inst = self.agg_front(super_com, proofs, pub_inputs, pt=pt, assert_products=assert_products)
         proof = tipp.prove(srs, inst["left"], inst["right"], inst["twist"], inst["commitment"], inst["output"])
         if check:
             vk = tipa.verifier_key(self.ctx, self.curve, srs)
             assert tipp.verify(vk, inst["commitment"], inst["output"], inst["twist"], proof), "TIPA proof rejected (aggregation.rs:340)"
         return proof, inst
 
-    def agg_front(self, super_com, proofs, pub_inputs, twist=None, s=None, t=None, pt=None):
+    def agg_front(self, super_com, proofs, pub_inputs, twist=None, s=None, t=None, pt=None, assert_products=True):
         """aggregation.rs:138-330 up to the `TIPA::prove` call.  proofs: [cp_groth16.Proof] with one stage-0
         commitment each; pub_inputs: one int per public input
         of the keys (3 for the ROM circuits, 5 for the RAM ones); the Fiat-Shamir challenges either as ints (twist, s, t) or drawn from the
         merlin transcript `pt` at the reference's points.  Returns a dict with the
         TIPA instance (`output` = z_lr, `commitment` = com_lr, `twist`), the witness (`left`, `right`) and the 4 x 4
-        `cross_terms`; raises AssertionError if the pairing-product equation of :265-269 fails."""
+        `cross_terms`; raises AssertionError if the pairing-product equation of :265-269 fails - unless assert_products is False:
+        then a bad subcircuit proof is aggregated all the same (for agg_verify.verify_aggregate to reject)."""
         ctx, F, ck, fc = self.ctx, self.F, self.ck, FrCodec(self.curve)
         r_mod = CURVE_PARAMS[self.curve]["r"]
         n = len(proofs)
@@ -267,7 +270,7 @@ class AggProvingKey:
         z = [[F.decode(cross[i, j]) for j in range(4)] for i in range(4)]
         z_alpha_beta = F.decode(f_ab_z.result())
         rhs = F.mul(F.mul(z_alpha_beta, z[1][1]), F.mul(z[2][2], z[3][3]))
-        assert z[0][0] == rhs, "pairing-product equation of the twisted proofs does not hold (aggregation.rs:265-269)"
+        assert not assert_products or z[0][0] == rhs, "pairing-product equation of the twisted proofs does not hold (aggregation.rs:265-269)"
         if pt is not None:                                                                          # :276-278
             # Vec<Vec<PairingOutput>>: u64 length prefixes, elements canonical
             ser = (4).to_bytes(8, "little") + b"".join((4).to_bytes(8, "little") + b"".join(F.serialize(e) for e in row) for row in z)

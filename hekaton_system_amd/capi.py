@@ -158,7 +158,7 @@ EXPORTS = ["hk_status_str", "hk_version", "hk_ctx_create", "hk_ctx_destroy", "hk
            "hk_trace_sort", "hk_stage0_witness", "hk_r1cs_check", "hk_pk_r1cs_check",
            "hk_sha_tree", "hk_sha_tree_inputs", "hk_ram_stage0_witness", "hk_ram_stage1_witness",
            "hk_r1cs_job_trace", "hk_r1cs_job_witness", "hk_vkd_trace", "hk_vkd_witness", "hk_vkd_tree",
-           "hk_scalar_powers", "hk_ipa_quotient", "hk_field_sqrt", "hk_points_decompress_g1", "hk_points_decompress_g2",
+           "hk_scalar_powers", "hk_ipa_quotient", "hk_class_power_sums", "hk_field_sqrt", "hk_points_decompress_g1", "hk_points_decompress_g2",
            "hk_points_compress_g1", "hk_points_compress_g2"]
 
 HK_VERIFY_CHECK_POINTS = 1
@@ -265,6 +265,7 @@ def load():
     lib.hk_vkd_tree.argtypes = [vp, C.POINTER(hk_vkd_tree_desc), vp, vp, vp]
     lib.hk_scalar_powers.argtypes = [vp, vp, sz, sz, vp]
     lib.hk_ipa_quotient.argtypes = [vp, vp, sz, vp, vp, sz, vp]
+    lib.hk_class_power_sums.argtypes = [vp, vp, vp, sz, sz, vp]
     if hasattr(lib, "hk_field_sqrt"):             # absent only from older experiment builds loaded through HK_LIB
         lib.hk_field_sqrt.argtypes = [vp, i, vp, sz, vp, vp]
         for f in (lib.hk_points_decompress_g1, lib.hk_points_decompress_g2):
@@ -488,6 +489,22 @@ class Context:
         res = out if out is not None else np.zeros((shift + (1 << l)) * self.fr_bytes, dtype=np.uint8)
         check(self.lib.hk_ipa_quotient(self.handle, ch.ctypes.data if l else None, l, rb.ctypes.data, zb.ctypes.data, int(shift),
                                        ptr(res)), "hk_ipa_quotient")
+        return res
+
+    def class_power_sums(self, x, class_of, n_classes, out=None):
+        """hk_class_power_sums: the Montgomery bytes of sums[c] = sum of x^i over the i with class_of[i] == c, c < n_classes
+        (x an int) - the exponents of an aggregate verifier's prod_c e(alpha_c, beta_c)^(sums[c]).  class_of: a uint32 array or
+        a DeviceBuffer of n uint32.  `out` may be a DeviceBuffer / DeviceView of n_classes Fr (the result stays in HBM);
+        otherwise a numpy array is returned.  A class id >= n_classes is refused (HK_ERR_ARG)."""
+        from .cp_groth16 import FrCodec
+        xb = FrCodec(self.curve).enc1(x)
+        class_of = _hd(class_of, np.uint32)
+        n = class_of.nbytes // 4
+        if n == 0 and not isinstance(class_of, DeviceBuffer):
+            class_of = np.zeros(1, np.uint32)                 # the entry wants a pointer even where it reads nothing
+        res = out if out is not None else np.zeros(int(n_classes) * self.fr_bytes, dtype=np.uint8)
+        check(self.lib.hk_class_power_sums(self.handle, xb.ctypes.data, ptr(class_of), n, int(n_classes), ptr(res)),
+              "hk_class_power_sums")
         return res
 
     def gt_pow(self, gts, scalars, in_gt=True):

@@ -212,6 +212,8 @@ struct Ops final : CurveOps {
     // agg_scalars.cuh
     hk_status scalar_powers(hk_ctx*, const void*, size_t, size_t, void*) override;
     hk_status ipa_quotient(hk_ctx*, const void*, size_t, const void*, const void*, size_t, void*) override;
+    // class_sums.cuh
+    hk_status class_power_sums(hk_ctx*, const void*, const uint32_t*, size_t, size_t, void*) override;
     // point_codec.cuh
     hk_status field_sqrt(hk_ctx* ctx, int which, const void* in, size_t n, void* out, unsigned char* ok) override {
         return Codec::field_sqrt(ctx, which, in, n, out, ok);

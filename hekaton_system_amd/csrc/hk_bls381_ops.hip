@@ -17,6 +17,7 @@
 #include "vkd.cuh"
 #include "vkd_tree.cuh"
 #include "agg_scalars.cuh"
+#include "class_sums.cuh"
 namespace hk {
 extern template struct MsmRun<CurveBls381::Fq>;
 extern template struct MsmRun<CurveBls381::Fq2>;

@@ -740,6 +740,11 @@ hk_status hk_ipa_quotient(hk_ctx* ctx, const void* challenges_mont, size_t l, co
     if (!ctx) return HK_ERR_ARG;
     return ctx->ops->ipa_quotient(ctx, challenges_mont, l, rho_mont, z_mont, shift, q_out);
 }
+hk_status hk_class_power_sums(hk_ctx* ctx, const void* x_mont, const uint32_t* class_of, size_t n, size_t n_classes,
+                              void* sums_out) {
+    if (!ctx) return HK_ERR_ARG;
+    return ctx->ops->class_power_sums(ctx, x_mont, class_of, n, n_classes, sums_out);
+}
 
 // ---- compressed points (point_codec.cuh).  A rule refuses with HK_ERR_ARG before anything is written: a missing buffer, an
 // input that shares a byte with an output, two outputs that share one, n >= 2^31.

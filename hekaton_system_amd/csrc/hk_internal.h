@@ -266,6 +266,9 @@ struct CurveOps {
     virtual hk_status scalar_powers(hk_ctx*, const void* x, size_t n, size_t reps, void* out) = 0;
     virtual hk_status ipa_quotient(hk_ctx*, const void* challenges, size_t l, const void* rho, const void* z, size_t shift,
                                    void* q_out) = 0;
+    // class_sums.cuh
+    virtual hk_status class_power_sums(hk_ctx*, const void* x, const uint32_t* class_of, size_t n, size_t n_classes,
+                                       void* sums_out) = 0;
     // point_codec.cuh
     virtual hk_status field_sqrt(hk_ctx*, int which, const void* in, size_t n, void* out, unsigned char* ok) = 0;
     virtual hk_status points_decompress(hk_ctx*, int group, const void* x_canon, const unsigned char* flags, size_t n, int check,

@@ -919,6 +919,16 @@ hk_status hk_scalar_powers(hk_ctx* ctx, const void* x_mont, size_t n, size_t rep
 hk_status hk_ipa_quotient(hk_ctx* ctx, const void* challenges_mont, size_t l, const void* rho_mont, const void* z_mont,
                           size_t shift, void* q_out);
 
+/* ---- the aggregate verifier's class sums ---------------------------------------------------------
+ * The keys of a job differ by class (aggregation.rs:76), so the verifier forms prod_i e(alpha_i, beta_i)^(x^i) as
+ * prod_c e(alpha_c, beta_c)^(sums[c]): its one computation that grows with the number of proofs.
+ *
+ * sums_out[c] = sum of x^i over the i < n with class_of[i] == c (Fr, Montgomery); a class without members gives 0.
+ * x_mont [h]: one Fr; class_of [h|d]: n uint32; sums_out [h|d]: n_classes Fr.  n == 0: n_classes zeros.
+ * HK_ERR_ARG, nothing written: a null pointer, n > 2^27, n_classes == 0 or > 1024, some class_of[i] >= n_classes. */
+hk_status hk_class_power_sums(hk_ctx* ctx, const void* x_mont, const uint32_t* class_of, size_t n, size_t n_classes,
+                              void* sums_out);
+
 #ifdef __cplusplus
 }
 #endif
