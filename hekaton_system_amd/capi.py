@@ -5,6 +5,7 @@ There is no CPU path: importing works anywhere (so host logic can be tested), bu
 """
 import contextlib
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -146,29 +147,115 @@ class hk_timings(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
-# every symbol include/hekaton.h declares (tests check the library exports all of them)
-EXPORTS = ["hk_status_str", "hk_version", "hk_ctx_create", "hk_ctx_destroy", "hk_ctx_sync",
-           "hk_ctx_set_profiling", "hk_ctx_last_timings", "hk_ctx_sizes", "hk_dev_alloc", "hk_dev_free",
-           "hk_dev_upload", "hk_dev_download", "hk_msm_g1", "hk_msm_g2", "hk_ntt", "hk_witness_map",
-           "hk_pk_upload", "hk_pk_free", "hk_commit", "hk_prove", "hk_fixed_base_g1", "hk_fixed_base_g2", "hk_scalar_pairing_g1", "hk_scalar_pairing_g2", "hk_field_convert", "hk_bases_upload", "hk_bases_free",
-           "hk_msm_bases", "hk_multi_pairing", "hk_pairing_products", "hk_ctx_gt_bytes",
-           "hk_points_lincomb_g1", "hk_points_lincomb_g2", "hk_points_fold_g2", "hk_points_fold_g1", "hk_points_fold_many_g1", "hk_points_fold_many_g2", "hk_pairing_pairs", "hk_keccak_f1600", "hk_assignment_from_bits", "hk_wprog_upload", "hk_wprog_free", "hk_wprog_run", "hk_gt_pow", "hk_fq12_pow", "hk_gt_pow_prod", "hk_poseidon_path", "hk_assignment_scatter", "hk_commit_batch",
-           "hk_prove_batch", "hk_vk_prepare", "hk_vk_free", "hk_vk_alpha_beta", "hk_verify_batch", "hk_points_check_g1",
-           "hk_points_check_g2", "hk_qap_eval", "hk_keygen", "hk_exec_tree", "hk_stage1_witness",
-           "hk_trace_sort", "hk_stage0_witness", "hk_r1cs_check", "hk_pk_r1cs_check",
-           "hk_sha_tree", "hk_sha_tree_inputs", "hk_ram_stage0_witness", "hk_ram_stage1_witness",
-           "hk_r1cs_job_trace", "hk_r1cs_job_witness", "hk_vkd_trace", "hk_vkd_witness", "hk_vkd_tree",
-           "hk_scalar_powers", "hk_ipa_quotient", "hk_class_power_sums", "hk_field_sqrt", "hk_points_decompress_g1", "hk_points_decompress_g2",
-           "hk_points_compress_g1", "hk_points_compress_g2"]
-
 HK_VERIFY_CHECK_POINTS = 1
 VERDICT_REJECT, VERDICT_ACCEPT, VERDICT_BAD_POINT = 0, 1, 2
+
+_vp, _sz, _i, _u, _u32, _P = C.c_void_p, C.c_size_t, C.c_int, C.c_uint, C.c_uint32, C.POINTER
+_csr3 = [_P(hk_csr)] * 3
+_MSM = [_vp, _vp, _sz, _vp, _sz, _i, _i, _vp]
+_FIXED_BASE = [_vp, _vp, _vp, _sz, _i, _vp]
+_SCALAR_PAIRING = [_vp, _vp, _vp, _sz, _vp]
+_LINCOMB = [_vp, _P(_vp), _vp, _sz, _sz, _vp]
+_FOLD = [_vp, _vp, _vp, _vp, _u, _sz, _vp]
+_FOLD_MANY = [_vp, _sz, _P(_vp), _P(_vp), _vp, _u, _sz, _P(_vp)]
+_POINTS_CHECK = [_vp, _vp, _sz, _vp]
+_DECOMPRESS = [_vp, _vp, _vp, _sz, _i, _vp, _vp]
+_COMPRESS = [_vp, _vp, _sz, _vp, _vp]
+_STAGE0 = [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _sz, _vp]
+
+# Every function include/hekaton.h declares, in its order: the argtypes, and the restype where it is not hk_status.  EXPORTS
+# and load() follow from this table; tests/test_capi_signatures_cpu.py holds it against the header.
+_SIGNATURES = {
+    "hk_status_str": ([_i], C.c_char_p),
+    "hk_version": ([], C.c_char_p),
+    "hk_ctx_create": [_i, _i, _P(_vp)],
+    "hk_ctx_destroy": ([_vp], None),
+    "hk_ctx_sync": [_vp],
+    "hk_ctx_set_profiling": [_vp, _i],
+    "hk_ctx_last_timings": [_vp, _P(hk_timings)],
+    "hk_ctx_sizes": [_vp] + [_P(_sz)] * 4,
+    "hk_dev_alloc": [_vp, _sz, _P(_vp)],
+    "hk_dev_free": [_vp, _vp],
+    "hk_dev_upload": [_vp, _vp, _vp, _sz],
+    "hk_dev_download": [_vp, _vp, _vp, _sz],
+    "hk_msm_g1": _MSM,
+    "hk_msm_g2": _MSM,
+    "hk_ntt": [_vp, _vp, _u, _i, _i],
+    "hk_witness_map": [_vp] + _csr3 + [_sz, _sz, _vp, _sz, _vp, _sz, _P(_sz)],
+    "hk_fixed_base_g1": _FIXED_BASE,
+    "hk_fixed_base_g2": _FIXED_BASE,
+    "hk_scalar_pairing_g1": _SCALAR_PAIRING,
+    "hk_scalar_pairing_g2": _SCALAR_PAIRING,
+    "hk_multi_pairing": [_vp, _vp, _vp, _sz, _vp],
+    "hk_pairing_products": [_vp, _P(_vp), _sz, _P(_vp), _sz, _sz, _vp],
+    "hk_pairing_pairs": [_vp, _P(_vp), _sz, _P(_vp), _sz, _P(_u32), _P(_u32), _sz, _sz, _vp],
+    "hk_ctx_gt_bytes": [_vp, _P(_sz)],
+    "hk_gt_pow": [_vp, _vp, _vp, _sz, _vp],
+    "hk_fq12_pow": [_vp, _vp, _vp, _sz, _vp],
+    "hk_gt_pow_prod": [_vp, _vp, _vp, _sz, _sz, _i, _vp],
+    "hk_points_lincomb_g1": _LINCOMB,
+    "hk_points_lincomb_g2": _LINCOMB,
+    "hk_points_fold_g2": _FOLD,
+    "hk_keccak_f1600": ([_vp], None),
+    "hk_points_fold_g1": _FOLD,
+    "hk_points_fold_many_g1": _FOLD_MANY,
+    "hk_points_fold_many_g2": _FOLD_MANY,
+    "hk_bases_upload": [_vp, _i, _vp, _sz, _P(_vp)],
+    "hk_bases_free": ([_vp], None),
+    "hk_msm_bases": [_vp, _vp, _vp, _sz, _i, _i, _vp],
+    "hk_field_convert": [_vp, _i, _vp, _vp, _sz, _i],
+    "hk_assignment_from_bits": [_vp, _vp, _sz, _vp, _vp, _sz, _vp],
+    "hk_wprog_upload": [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _sz, _sz, _P(_vp)],
+    "hk_wprog_free": ([_vp], None),
+    "hk_wprog_run": [_vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp],
+    "hk_assignment_scatter": [_vp, _vp, _vp, _sz, _sz, _sz, _vp],
+    "hk_poseidon_path": [_vp, _vp, _sz, _P(hk_poseidon_desc), _P(hk_poseidon_desc), _vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp],
+    "hk_pk_upload": [_vp, _P(hk_pk_desc), _P(_vp)],
+    "hk_pk_free": ([_vp], None),
+    "hk_commit": [_vp, _vp, _sz, _vp, _sz, _vp, _vp],
+    "hk_commit_batch": [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp],
+    "hk_prove": [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp],
+    "hk_prove_batch": [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp],
+    "hk_vk_prepare": [_vp, _P(hk_vk_desc), _P(_vp)],
+    "hk_vk_free": ([_vp], None),
+    "hk_vk_alpha_beta": [_vp, _vp],
+    "hk_verify_batch": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _u, _vp, _vp],
+    "hk_points_check_g1": _POINTS_CHECK,
+    "hk_points_check_g2": _POINTS_CHECK,
+    "hk_field_sqrt": [_vp, _i, _vp, _sz, _vp, _vp],
+    "hk_points_decompress_g1": _DECOMPRESS,
+    "hk_points_decompress_g2": _DECOMPRESS,
+    "hk_points_compress_g1": _COMPRESS,
+    "hk_points_compress_g2": _COMPRESS,
+    "hk_qap_eval": [_vp] + _csr3 + [_sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _P(_sz)],
+    "hk_keygen": [_vp, _P(hk_keygen_desc), _P(hk_keygen_out), _P(_sz)],
+    "hk_exec_tree": [_vp, _P(hk_exec_tree_desc), _P(hk_exec_tree_out)],
+    "hk_stage1_witness": [_vp, _P(hk_stage1_desc), _vp, _sz, _sz, _vp],
+    "hk_trace_sort": [_vp, _u32, _vp, _sz, _vp, _vp],
+    "hk_stage0_witness": _STAGE0,
+    "hk_r1cs_check": [_vp] + _csr3 + [_vp, _sz, _sz, _vp, _vp, _vp, _sz],
+    "hk_pk_r1cs_check": [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz],
+    "hk_sha_tree": [_vp, _vp, _u32, _u32, _u32, _P(hk_sha_tree_out)],
+    "hk_sha_tree_inputs": [_vp, _vp, _vp, _u32, _u32, _vp, _sz, _vp],
+    "hk_ram_stage0_witness": _STAGE0,
+    "hk_ram_stage1_witness": [_vp, _P(hk_ram_stage1_desc), _vp, _sz, _sz, _vp],
+    "hk_r1cs_job_trace": [_vp, _P(hk_r1cs_job_desc), _vp],
+    "hk_r1cs_job_witness": [_vp, _P(hk_r1cs_job_desc), _vp, _sz, _sz, _sz, _vp],
+    "hk_vkd_trace": [_vp, _P(hk_vkd_desc), _vp, _vp],
+    "hk_vkd_witness": [_vp, _P(hk_vkd_desc), _vp, _sz, _sz, _P(hk_vkd_cols), _vp],
+    "hk_vkd_tree": [_vp, _P(hk_vkd_tree_desc), _vp, _vp, _vp],
+    "hk_scalar_powers": [_vp, _vp, _sz, _sz, _vp],
+    "hk_ipa_quotient": [_vp, _vp, _sz, _vp, _vp, _sz, _vp],
+    "hk_class_power_sums": [_vp, _vp, _vp, _sz, _sz, _vp],
+}
+EXPORTS = list(_SIGNATURES)
 
 _lib = None
 
 
 def load():
-    """Loads libhekaton.so (built by __graft_entry__.build()); fails loudly when absent."""
+    """Loads libhekaton.so (built by __graft_entry__.build()) and gives every declared function its signature; fails loudly
+    when the library is absent, and by the symbol's name (ctypes' AttributeError) when it lacks one."""
     global _lib
     if _lib is not None:
         return _lib
@@ -176,102 +263,9 @@ def load():
         raise ImportError("libhekaton.so not built (%s): run `python -c 'import __graft_entry__ as g; "
                           "g.build()'` — there is no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
-    lib.hk_status_str.restype = C.c_char_p
-    lib.hk_status_str.argtypes = [i]
-    lib.hk_version.restype = C.c_char_p
-    lib.hk_ctx_create.argtypes = [i, i, C.POINTER(vp)]
-    lib.hk_ctx_destroy.argtypes = [vp]
-    lib.hk_ctx_destroy.restype = None
-    lib.hk_ctx_sync.argtypes = [vp]
-    lib.hk_ctx_set_profiling.argtypes = [vp, i]
-    lib.hk_ctx_last_timings.argtypes = [vp, C.POINTER(hk_timings)]
-    lib.hk_ctx_sizes.argtypes = [vp] + [C.POINTER(sz)] * 4
-    lib.hk_dev_alloc.argtypes = [vp, sz, C.POINTER(vp)]
-    lib.hk_dev_free.argtypes = [vp, vp]
-    lib.hk_dev_upload.argtypes = [vp, vp, vp, sz]
-    lib.hk_dev_download.argtypes = [vp, vp, vp, sz]
-    for f in (lib.hk_msm_g1, lib.hk_msm_g2):
-        f.argtypes = [vp, vp, sz, vp, sz, i, i, vp]
-    lib.hk_ntt.argtypes = [vp, vp, C.c_uint, i, i]
-    for f in (lib.hk_fixed_base_g1, lib.hk_fixed_base_g2):
-        f.argtypes = [vp, vp, vp, sz, i, vp]
-    for f in (lib.hk_scalar_pairing_g1, lib.hk_scalar_pairing_g2):
-        f.argtypes = [vp, vp, vp, sz, vp]
-    lib.hk_field_convert.argtypes = [vp, i, vp, vp, sz, i]
-    lib.hk_bases_upload.argtypes = [vp, i, vp, sz, C.POINTER(vp)]
-    lib.hk_bases_free.argtypes = [vp]
-    lib.hk_bases_free.restype = None
-    lib.hk_msm_bases.argtypes = [vp, vp, vp, sz, i, i, vp]
-    if hasattr(lib, "hk_multi_pairing"):          # absent only from older experiment builds loaded through HK_LIB
-        lib.hk_multi_pairing.argtypes = [vp, vp, vp, sz, vp]
-        lib.hk_pairing_products.argtypes = [vp, C.POINTER(vp), sz, C.POINTER(vp), sz, sz, vp]
-        lib.hk_pairing_pairs.argtypes = [vp, C.POINTER(vp), sz, C.POINTER(vp), sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), sz, sz, vp]
-        lib.hk_ctx_gt_bytes.argtypes = [vp, C.POINTER(sz)]
-        for f in (lib.hk_points_lincomb_g1, lib.hk_points_lincomb_g2):
-            f.argtypes = [vp, C.POINTER(vp), vp, sz, sz, vp]
-    if hasattr(lib, "hk_points_fold_g2"):
-        lib.hk_points_fold_g2.argtypes = [vp, vp, vp, vp, C.c_uint, sz, vp]
-    if hasattr(lib, "hk_points_fold_g1"):
-        lib.hk_points_fold_g1.argtypes = [vp, vp, vp, vp, C.c_uint, sz, vp]
-    for name in ("hk_points_fold_many_g1", "hk_points_fold_many_g2"):
-        getattr(lib, name).argtypes = [vp, sz, C.POINTER(vp), C.POINTER(vp), vp, C.c_uint, sz, C.POINTER(vp)]
-    if hasattr(lib, "hk_assignment_from_bits"):
-        lib.hk_assignment_from_bits.argtypes = [vp, vp, sz, vp, vp, sz, vp]
-        lib.hk_wprog_upload.argtypes = [vp, vp, sz, vp, sz, vp, sz, sz, sz, C.POINTER(vp)]
-        lib.hk_wprog_free.argtypes = [vp]
-        lib.hk_wprog_free.restype = None
-        lib.hk_wprog_run.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
-        lib.hk_assignment_scatter.argtypes = [vp, vp, vp, sz, sz, sz, vp]
-    if hasattr(lib, "hk_gt_pow"):
-        lib.hk_gt_pow.argtypes = [vp, vp, vp, sz, vp]
-        lib.hk_fq12_pow.argtypes = [vp, vp, vp, sz, vp]
-        lib.hk_gt_pow_prod.argtypes = [vp, vp, vp, sz, sz, C.c_int, vp]
-    lib.hk_poseidon_path.argtypes = [vp, vp, sz, C.POINTER(hk_poseidon_desc), C.POINTER(hk_poseidon_desc), vp, vp, vp, sz, sz,
-                                     sz, sz, vp]
-    lib.hk_witness_map.argtypes = [vp, C.POINTER(hk_csr), C.POINTER(hk_csr), C.POINTER(hk_csr), sz, sz,
-                                   vp, sz, vp, sz, C.POINTER(sz)]
-    lib.hk_pk_upload.argtypes = [vp, C.POINTER(hk_pk_desc), C.POINTER(vp)]
-    lib.hk_pk_free.argtypes = [vp]
-    lib.hk_pk_free.restype = None
-    lib.hk_commit.argtypes = [vp, vp, sz, vp, sz, vp, vp]
-    lib.hk_commit_batch.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp]
-    lib.hk_prove.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp]
-    lib.hk_prove_batch.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, sz, vp, vp, vp]
-    lib.hk_vk_prepare.argtypes = [vp, C.POINTER(hk_vk_desc), C.POINTER(vp)]
-    lib.hk_vk_free.argtypes = [vp]
-    lib.hk_vk_free.restype = None
-    lib.hk_vk_alpha_beta.argtypes = [vp, vp]
-    lib.hk_verify_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, C.c_uint, vp, vp]
-    lib.hk_points_check_g1.argtypes = [vp, vp, sz, vp]
-    lib.hk_points_check_g2.argtypes = [vp, vp, sz, vp]
-    lib.hk_qap_eval.argtypes = [vp, C.POINTER(hk_csr), C.POINTER(hk_csr), C.POINTER(hk_csr), sz, sz, sz, vp, vp, vp, vp, vp,
-                                C.POINTER(sz)]
-    lib.hk_keygen.argtypes = [vp, C.POINTER(hk_keygen_desc), C.POINTER(hk_keygen_out), C.POINTER(sz)]
-    lib.hk_exec_tree.argtypes = [vp, C.POINTER(hk_exec_tree_desc), C.POINTER(hk_exec_tree_out)]
-    lib.hk_stage1_witness.argtypes = [vp, C.POINTER(hk_stage1_desc), vp, sz, sz, vp]
-    lib.hk_trace_sort.argtypes = [vp, C.c_uint32, vp, sz, vp, vp]
-    lib.hk_stage0_witness.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, sz, vp]
-    lib.hk_r1cs_check.argtypes = [vp, C.POINTER(hk_csr), C.POINTER(hk_csr), C.POINTER(hk_csr), vp, sz, sz, vp, vp, vp, sz]
-    lib.hk_pk_r1cs_check.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, sz]
-    lib.hk_sha_tree.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(hk_sha_tree_out)]
-    lib.hk_sha_tree_inputs.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, sz, vp]
-    lib.hk_ram_stage0_witness.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, sz, vp]
-    lib.hk_ram_stage1_witness.argtypes = [vp, C.POINTER(hk_ram_stage1_desc), vp, sz, sz, vp]
-    lib.hk_r1cs_job_trace.argtypes = [vp, C.POINTER(hk_r1cs_job_desc), vp]
-    lib.hk_r1cs_job_witness.argtypes = [vp, C.POINTER(hk_r1cs_job_desc), vp, sz, sz, sz, vp]
-    lib.hk_vkd_trace.argtypes = [vp, C.POINTER(hk_vkd_desc), vp, vp]
-    lib.hk_vkd_witness.argtypes = [vp, C.POINTER(hk_vkd_desc), vp, sz, sz, C.POINTER(hk_vkd_cols), vp]
-    lib.hk_vkd_tree.argtypes = [vp, C.POINTER(hk_vkd_tree_desc), vp, vp, vp]
-    lib.hk_scalar_powers.argtypes = [vp, vp, sz, sz, vp]
-    lib.hk_ipa_quotient.argtypes = [vp, vp, sz, vp, vp, sz, vp]
-    lib.hk_class_power_sums.argtypes = [vp, vp, vp, sz, sz, vp]
-    if hasattr(lib, "hk_field_sqrt"):             # absent only from older experiment builds loaded through HK_LIB
-        lib.hk_field_sqrt.argtypes = [vp, i, vp, sz, vp, vp]
-        for f in (lib.hk_points_decompress_g1, lib.hk_points_decompress_g2):
-            f.argtypes = [vp, vp, vp, sz, i, vp, vp]
-        for f in (lib.hk_points_compress_g1, lib.hk_points_compress_g2):
-            f.argtypes = [vp, vp, sz, vp, vp]
+    for name, sig in _SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = sig if isinstance(sig, tuple) else (sig, _i)
     _lib = lib
     return lib
 
@@ -283,6 +277,9 @@ def status_str(s):
 def check(status, what):
     if status != HK_OK:
         raise HekatonError(status, what)
+
+
+_check = check          # for Context.points_decompress, whose keyword `check` shadows the function
 
 
 def ptr(x):
@@ -312,9 +309,14 @@ class DeviceBuffer:
     @classmethod
     def from_host(cls, ctx, arr):
         arr = np.ascontiguousarray(arr)
-        buf = cls(ctx, arr.nbytes)
-        check(load().hk_dev_upload(ctx.handle, buf.ptr, arr.ctypes.data, arr.nbytes), "hk_dev_upload")
-        return buf
+        return cls(ctx, arr.nbytes).upload(arr)
+
+    def upload(self, arr):
+        """The bytes of `arr` (made contiguous) to the start of this allocation; returns self."""
+        arr = np.ascontiguousarray(arr)
+        assert arr.nbytes <= self.nbytes
+        check(load().hk_dev_upload(self.ctx.handle, self.ptr, arr.ctypes.data, arr.nbytes), "hk_dev_upload")
+        return self
 
     def to_host(self):
         out = np.empty(self.nbytes, dtype=np.uint8)
@@ -342,6 +344,9 @@ class DeviceView(DeviceBuffer):
 
 
 # ---- what the wrappers share -------------------------------------------------------------------------------------------
+# Keeping operands alive: every array whose address goes into a call or into a descriptor is bound to a local of the wrapper
+# (a name, or a list or tuple a name holds) until the call returns.  A ctypes structure that holds c_void_p integers keeps
+# nothing alive, so a helper that builds one hands back what it points into and the wrapper binds that too (`d, keep = ...`).
 def _hd(x, dtype=np.uint8):
     """A host-or-device operand as the library reads it: a DeviceBuffer (or None, an absent one) as it is, anything else as
     a contiguous array of `dtype` (bytes, unless the entry reads words).  The caller keeps the result alive over the call."""
@@ -358,6 +363,13 @@ def _nullable(x):
     return x.ctypes.data if x.size else None
 
 
+def _size(x):
+    """The bytes of a host-or-device operand; 0 for an absent one."""
+    if x is None:
+        return 0
+    return x.nbytes if isinstance(x, DeviceBuffer) else np.asarray(x).nbytes
+
+
 def _ptr_array(xs):
     """The addresses of numpy arrays and DeviceBuffers as a c_void_p array, each as _nullable gives it; never of length 0."""
     return (C.c_void_p * max(len(xs), 1))(*[_nullable(x) for x in xs])
@@ -368,12 +380,11 @@ def _device_addr(z):
     return z.ptr if isinstance(z, DeviceBuffer) else int(z)
 
 
-def _challenge_bytes(curve, challenges):
+def _challenge_bytes(ctx, challenges):
     """Challenges given as ints or as their Montgomery bytes."""
     if isinstance(challenges, np.ndarray):
         return np.ascontiguousarray(challenges, dtype=np.uint8)
-    from .cp_groth16 import FrCodec
-    return FrCodec(curve).enc(list(challenges))
+    return ctx.fc.enc(list(challenges))
 
 
 @contextlib.contextmanager
@@ -400,10 +411,24 @@ class Context:
         fr, fq, g1, g2 = (C.c_size_t() for _ in range(4))
         check(self.lib.hk_ctx_sizes(h, C.byref(fr), C.byref(fq), C.byref(g1), C.byref(g2)), "hk_ctx_sizes")
         self.fr_bytes, self.fq_bytes, self.g1_bytes, self.g2_bytes = fr.value, fq.value, g1.value, g2.value
-        gt = C.c_size_t(12 * fq.value)
-        if hasattr(self.lib, "hk_ctx_gt_bytes"):
-            check(self.lib.hk_ctx_gt_bytes(h, C.byref(gt)), "hk_ctx_gt_bytes")
+        gt = C.c_size_t()
+        check(self.lib.hk_ctx_gt_bytes(h, C.byref(gt)), "hk_ctx_gt_bytes")
         self.gt_bytes = gt.value
+
+    @functools.cached_property
+    def fc(self):
+        """The curve's FrCodec, made on first use: cp_groth16 imports this module."""
+        from .cp_groth16 import FrCodec
+        return FrCodec(self.curve)
+
+    def _group(self, group, stem=None):
+        """(bytes of a packed affine point of G1 / G2, the library's `stem`_g1 / `stem`_g2 - None without a stem)."""
+        pb, suffix = (self.g1_bytes, "_g1") if group == 1 else (self.g2_bytes, "_g2")
+        return pb, stem and getattr(self.lib, stem + suffix)
+
+    def _outputs(self, sizes, device_out):
+        """One output per byte count of `sizes`: zeroed uint8 arrays, or - device_out - DeviceBuffers, never of 0 bytes."""
+        return [DeviceBuffer(self, max(b, 1)) if device_out else np.zeros(b, dtype=np.uint8) for b in sizes]
 
     def close(self):
         if self.handle:
@@ -428,30 +453,27 @@ class Context:
         return t.as_dict()
 
     # ---- primitives ---------------------------------------------------------------------------
-    def _msm(self, fn, nbytes, bases, n_bases, scalars, n_scalars, mont, checked):
-        out = np.zeros(nbytes, dtype=np.uint8)
-        check(fn(self.handle, ptr(bases), n_bases, ptr(scalars), n_scalars, int(mont), int(checked),
-                 out.ctypes.data), fn.__name__)
+    def _msm(self, group, bases, scalars, n_bases, n_scalars, mont, checked):
+        pb, fn = self._group(group, "hk_msm")
+        nb = n_bases if n_bases is not None else _size(bases) // pb
+        ns = n_scalars if n_scalars is not None else _size(scalars) // self.fr_bytes
+        out = np.zeros(pb, dtype=np.uint8)
+        check(fn(self.handle, ptr(bases), nb, ptr(scalars), ns, int(mont), int(checked), out.ctypes.data), fn.__name__)
         return out
 
     def msm_g1(self, bases, scalars, n_bases=None, n_scalars=None, montgomery=True, checked=True):
         """E::G1::msm / msm_bigint / msm_unchecked (prover.rs:88,97,117,129; committer.rs:89,113)."""
-        nb = n_bases if n_bases is not None else len(bases) // self.g1_bytes
-        ns = n_scalars if n_scalars is not None else len(scalars) // self.fr_bytes
-        return self._msm(self.lib.hk_msm_g1, self.g1_bytes, bases, nb, scalars, ns, montgomery, checked)
+        return self._msm(1, bases, scalars, n_bases, n_scalars, montgomery, checked)
 
     def msm_g2(self, bases, scalars, n_bases=None, n_scalars=None, montgomery=True, checked=True):
         """E::G2 MSM (prover.rs:107)."""
-        nb = n_bases if n_bases is not None else len(bases) // self.g2_bytes
-        ns = n_scalars if n_scalars is not None else len(scalars) // self.fr_bytes
-        return self._msm(self.lib.hk_msm_g2, self.g2_bytes, bases, nb, scalars, ns, montgomery, checked)
+        return self._msm(2, bases, scalars, n_bases, n_scalars, montgomery, checked)
 
     def fixed_base(self, group, base, scalars, n=None, montgomery=True, out=None):
         """FixedBase::msm + normalize_batch (generator.rs:134-224): out[i] = scalars[i] * base.
         `out` may be a DeviceBuffer (stays in HBM); otherwise a numpy array is returned."""
-        pb = self.g1_bytes if group == 1 else self.g2_bytes
-        n = n if n is not None else len(scalars) // self.fr_bytes
-        fn = self.lib.hk_fixed_base_g1 if group == 1 else self.lib.hk_fixed_base_g2
+        pb, fn = self._group(group, "hk_fixed_base")
+        n = n if n is not None else _size(scalars) // self.fr_bytes
         base = _hd(base)
         res = out if out is not None else np.zeros(n * pb, dtype=np.uint8)
         check(fn(self.handle, ptr(base), ptr(scalars), n, int(montgomery), ptr(res)), fn.__name__)
@@ -460,9 +482,8 @@ class Context:
     def scalar_pairing(self, group, points, scalars, n=None, out=None):
         """`scalar_pairing` (distributed-prover/src/pairing_ops.rs:32-39): out[i] = scalars[i] * points[i].  `out` may be a
         DeviceBuffer (the result stays in HBM)."""
-        pb = self.g1_bytes if group == 1 else self.g2_bytes
-        n = n if n is not None else len(scalars) // self.fr_bytes
-        fn = self.lib.hk_scalar_pairing_g1 if group == 1 else self.lib.hk_scalar_pairing_g2
+        pb, fn = self._group(group, "hk_scalar_pairing")
+        n = n if n is not None else _size(scalars) // self.fr_bytes
         res = out if out is not None else np.zeros(n * pb, dtype=np.uint8)
         check(fn(self.handle, ptr(points), ptr(scalars), n, ptr(res)), fn.__name__)
         return res
@@ -471,8 +492,7 @@ class Context:
         """hk_scalar_powers: `structured_scalar_power` (distributed-prover/src/pairing_ops.rs:42-48) - the Montgomery bytes of
         x^0 .. x^(n - 1) (x an int), `reps` times back to back.  `out` may be a DeviceBuffer / DeviceView of reps * n Fr (the
         result stays in HBM); otherwise a numpy array is returned."""
-        from .cp_groth16 import FrCodec
-        xb = FrCodec(self.curve).enc1(x)
+        xb = self.fc.enc1(x)
         res = out if out is not None else np.zeros(reps * n * self.fr_bytes, dtype=np.uint8)
         check(self.lib.hk_scalar_powers(self.handle, xb.ctypes.data, int(n), int(reps), ptr(res)), "hk_scalar_powers")
         return res
@@ -481,11 +501,9 @@ class Context:
         """hk_ipa_quotient: the Montgomery bytes of the quotient of X^shift prod_k (1 + challenges[k] (rho X)^(2^k)) by
         (X - z), one zero appended: shift + 2^len(challenges) Fr (kzg.rs:122-141).  challenges, rho, z: ints.  `out` may be
         a DeviceBuffer / DeviceView of that size (the result stays in HBM); otherwise a numpy array is returned."""
-        from .cp_groth16 import FrCodec
-        fc = FrCodec(self.curve)
         challenges = list(challenges)
         l = len(challenges)
-        ch, rb, zb = fc.enc(challenges), fc.enc1(rho), fc.enc1(z)
+        ch, rb, zb = self.fc.enc(challenges), self.fc.enc1(rho), self.fc.enc1(z)
         res = out if out is not None else np.zeros((shift + (1 << l)) * self.fr_bytes, dtype=np.uint8)
         check(self.lib.hk_ipa_quotient(self.handle, ch.ctypes.data if l else None, l, rb.ctypes.data, zb.ctypes.data, int(shift),
                                        ptr(res)), "hk_ipa_quotient")
@@ -496,11 +514,10 @@ class Context:
         (x an int) - the exponents of an aggregate verifier's prod_c e(alpha_c, beta_c)^(sums[c]).  class_of: a uint32 array or
         a DeviceBuffer of n uint32.  `out` may be a DeviceBuffer / DeviceView of n_classes Fr (the result stays in HBM);
         otherwise a numpy array is returned.  A class id >= n_classes is refused (HK_ERR_ARG)."""
-        from .cp_groth16 import FrCodec
-        xb = FrCodec(self.curve).enc1(x)
+        xb = self.fc.enc1(x)
         class_of = _hd(class_of, np.uint32)
-        n = class_of.nbytes // 4
-        if n == 0 and not isinstance(class_of, DeviceBuffer):
+        n = _size(class_of) // 4
+        if n == 0 and isinstance(class_of, np.ndarray):
             class_of = np.zeros(1, np.uint32)                 # the entry wants a pointer even where it reads nothing
         res = out if out is not None else np.zeros(int(n_classes) * self.fr_bytes, dtype=np.uint8)
         check(self.lib.hk_class_power_sums(self.handle, xb.ctypes.data, ptr(class_of), n, int(n_classes), ptr(res)),
@@ -512,7 +529,7 @@ class Context:
         in_gt=False: hk_fq12_pow, the plain chain for values of unknown provenance (a verifier's inputs).
         gts: (n, gt_bytes) uint8; scalars: n Fr Montgomery bytes."""
         gts, scalars = _hd(gts), _hd(scalars)
-        out = np.zeros((gts.nbytes // self.gt_bytes, self.gt_bytes), dtype=np.uint8)
+        out = np.zeros((_size(gts) // self.gt_bytes, self.gt_bytes), dtype=np.uint8)
         fn = self.lib.hk_gt_pow if in_gt else self.lib.hk_fq12_pow
         check(fn(self.handle, ptr(gts), ptr(scalars), out.shape[0], out.ctypes.data), fn.__name__)
         return out
@@ -521,7 +538,7 @@ class Context:
         """hk_gt_pow_prod: out[g] = prod_j gts[g * group_len + j]^scalars[g * group_len + j] (a verifier's
         multi-exponentiations).  Returns (n / group_len, gt_bytes) uint8."""
         gts, scalars = _hd(gts), _hd(scalars)
-        n = gts.nbytes // self.gt_bytes
+        n = _size(gts) // self.gt_bytes
         out = np.zeros((n // max(1, group_len), self.gt_bytes), dtype=np.uint8)
         check(self.lib.hk_gt_pow_prod(self.handle, ptr(gts), ptr(scalars), n, group_len, 1 if in_gt else 0, out.ctypes.data),
               "hk_gt_pow_prod")
@@ -530,7 +547,7 @@ class Context:
     def multi_pairing(self, g1, g2, n=None):
         """`pairing(left, right)` (distributed-prover/src/pairing_ops.rs:25-29): prod_i e(g1[i], g2[i]) as ark's Fp12
         bytes (12 Fq, Montgomery)."""
-        n = n if n is not None else len(g1) // self.g1_bytes
+        n = n if n is not None else _size(g1) // self.g1_bytes
         out = np.zeros(self.gt_bytes, dtype=np.uint8)
         check(self.lib.hk_multi_pairing(self.handle, ptr(g1) if n else None, ptr(g2) if n else None, n, out.ctypes.data),
               "hk_multi_pairing")
@@ -539,8 +556,8 @@ class Context:
     def pairing_products(self, lhs, rhs, n=None):
         """Every G1 vector of `lhs` against every G2 vector of `rhs` in one batched launch (the `cross_terms` of
         aggregation.rs:255-263): returns a (len(lhs), len(rhs), gt_bytes) uint8 array."""
-        n = n if n is not None else len(lhs[0]) // self.g1_bytes
         lhs, rhs = [_hd(x) for x in lhs], [_hd(x) for x in rhs]
+        n = n if n is not None else _size(lhs[0]) // self.g1_bytes
         lp, rp = _ptr_array(lhs), _ptr_array(rhs)
         out = np.zeros((len(lhs), len(rhs), self.gt_bytes), dtype=np.uint8)
         check(self.lib.hk_pairing_products(self.handle, lp, len(lhs), rp, len(rhs), n, out.ctypes.data),
@@ -550,8 +567,8 @@ class Context:
     def pairing_pairs(self, lhs, rhs, pairs, n=None):
         """pairing(lhs[a], rhs[b]) for each (a, b) of `pairs` in one batched launch (hk_pairing_pairs: the cross terms of a
         GIPA round): returns a (len(pairs), gt_bytes) uint8 array."""
-        n = n if n is not None else len(lhs[0]) // self.g1_bytes
         lhs, rhs = [_hd(x) for x in lhs], [_hd(x) for x in rhs]
+        n = n if n is not None else _size(lhs[0]) // self.g1_bytes
         lp, rp = _ptr_array(lhs), _ptr_array(rhs)
         pa = (C.c_uint32 * len(pairs))(*[a for a, _ in pairs])
         pb = (C.c_uint32 * len(pairs))(*[b for _, b in pairs])
@@ -562,30 +579,27 @@ class Context:
 
     def points_lincomb(self, group, vecs, coeffs, n=None):
         """out[i] = sum_j coeffs[j] * vecs[j][i] (aggregation.rs:192-203,293-326); coeffs: k Fr Montgomery bytes."""
-        pb = self.g1_bytes if group == 1 else self.g2_bytes
-        n = n if n is not None else len(vecs[0]) // pb
+        pb, fn = self._group(group, "hk_points_lincomb")
         vecs, coeffs = [_hd(x) for x in vecs], _hd(coeffs)
+        n = n if n is not None else _size(vecs[0]) // pb
         out = np.zeros(n * pb, dtype=np.uint8)
-        fn = self.lib.hk_points_lincomb_g1 if group == 1 else self.lib.hk_points_lincomb_g2
         check(fn(self.handle, _ptr_array(vecs), ptr(coeffs), len(vecs), n, out.ctypes.data), fn.__name__)
         return out
 
     def _fold_coeffs(self, group, c):
         """The scalar c (an int mod r) split along the group's endomorphism (endo.Phi2 in G1, endo.Psi4 in G2): the parts'
         magnitudes as Montgomery bytes and the mask of the negative ones."""
-        from .cp_groth16 import FrCodec
         from .endo import phi2, psi4
-        k = (phi2 if group == 1 else psi4)(self.curve).decompose(c)
+        k = {1: phi2, 2: psi4}[group](self.curve).decompose(c)
         neg = sum(1 << j for j, v in enumerate(k) if v < 0)
-        return np.ascontiguousarray(FrCodec(self.curve).enc([abs(v) for v in k]), dtype=np.uint8), neg
+        return self.fc.enc([abs(v) for v in k]), neg
 
     def _points_fold(self, group, lo, hi, c, n, out):
-        pb = self.g1_bytes if group == 1 else self.g2_bytes
-        n = n if n is not None else len(hi) // pb
+        pb, fn = self._group(group, "hk_points_fold")
         coeffs, neg = self._fold_coeffs(group, c)
         lo, hi = _hd(lo), _hd(hi)
+        n = n if n is not None else _size(hi) // pb
         res = out if out is not None else np.zeros(n * pb, dtype=np.uint8)                      # a DeviceBuffer stays in HBM
-        fn = self.lib.hk_points_fold_g1 if group == 1 else self.lib.hk_points_fold_g2
         check(fn(self.handle, ptr(lo), ptr(hi), coeffs.ctypes.data, neg, n, ptr(res)), fn.__name__)
         return res
 
@@ -606,7 +620,7 @@ class Context:
         DeviceBuffer / DeviceView (stay in HBM) or uint8 arrays of n points each."""
         coeffs, neg = self._fold_coeffs(group, c)
         los, his = [_hd(x) for x in los], [_hd(x) for x in his]
-        fn = self.lib.hk_points_fold_many_g1 if group == 1 else self.lib.hk_points_fold_many_g2
+        fn = self._group(group, "hk_points_fold_many")[1]
         check(fn(self.handle, len(outs), _ptr_array(los), _ptr_array(his), coeffs.ctypes.data, neg, n, _ptr_array(outs)),
               fn.__name__)
         return outs
@@ -615,14 +629,11 @@ class Context:
         """hk_assignment_from_bits: the Montgomery assignment of a bit-valued witness, materialised in HBM.  bits: uint8
         array (one per variable); full_cols: column indices of the full-width values; full_vals: their Montgomery bytes.
         Returns a DeviceBuffer of n_v Fr (or fills `out`)."""
-        bits = np.ascontiguousarray(bits, dtype=np.uint8)
-        cols = np.ascontiguousarray(full_cols, dtype=np.uint32)
-        vals = np.ascontiguousarray(full_vals, dtype=np.uint8)
-        n_v = bits.size
+        bits, cols, vals = _hd(bits), _hd(full_cols, np.uint32), _hd(full_vals)
+        n_v, n_full = _size(bits), _size(cols) // 4
         buf = out if out is not None else DeviceBuffer(self, n_v * self.fr_bytes)
-        check(self.lib.hk_assignment_from_bits(self.handle, bits.ctypes.data, n_v, cols.ctypes.data if cols.size else None,
-                                               vals.ctypes.data if cols.size else None, cols.size, buf.ptr),
-              "hk_assignment_from_bits")
+        check(self.lib.hk_assignment_from_bits(self.handle, ptr(bits), n_v, ptr(cols) if n_full else None,
+                                               ptr(vals) if n_full else None, n_full, buf.ptr), "hk_assignment_from_bits")
         return buf
 
     def poseidon_path(self, params, leaf, siblings, index, n_v, col0, z_out):
@@ -633,14 +644,9 @@ class Context:
         DeviceBuffers hk_exec_tree left on the device (both then; batch = len(index))."""
         consts, n_consts, ld, nd = params
         index = np.ascontiguousarray(index, dtype=np.uint32)
-        if isinstance(leaf, DeviceBuffer):
-            batch = index.size
-            depth = siblings.nbytes // (batch * self.fr_bytes)
-        else:
-            leaf = np.ascontiguousarray(leaf, dtype=np.uint8)
-            batch = leaf.shape[0]
-            siblings = np.ascontiguousarray(siblings, dtype=np.uint8).reshape(batch, -1)
-            depth = siblings.shape[1] // self.fr_bytes
+        leaf, siblings = _hd(leaf), _hd(siblings)
+        batch = index.size
+        depth = _size(siblings) // (batch * self.fr_bytes)
         a, b = hk_poseidon_desc(*ld), hk_poseidon_desc(*nd)
         check(self.lib.hk_poseidon_path(self.handle, ptr(consts), int(n_consts), C.byref(a), C.byref(b), ptr(leaf),
                                         ptr(siblings) if depth else None, index.ctypes.data, depth, batch, int(n_v),
@@ -648,19 +654,16 @@ class Context:
 
     def wprog_upload(self, ops, refs, vmap, n_values, n_inputs):
         """hk_wprog_upload: a class's word program (sha_circuit.Tape.word_program) resident on the device."""
-        ops = np.ascontiguousarray(ops, dtype=np.uint32)
-        refs = np.ascontiguousarray(refs, dtype=np.uint32)
-        vmap = np.ascontiguousarray(vmap, dtype=np.uint32)
+        ops, refs, vmap = _hd(ops, np.uint32), _hd(refs, np.uint32), _hd(vmap, np.uint32)
+        n_v = _size(vmap) // 4
         h = C.c_void_p()
-        check(self.lib.hk_wprog_upload(self.handle, ops.ctypes.data, ops.shape[0], refs.ctypes.data if refs.size else None,
-                                       refs.size, vmap.ctypes.data, vmap.size, int(n_values), int(n_inputs), C.byref(h)),
-              "hk_wprog_upload")
-        return WordProgram(self, h, vmap.size, int(n_inputs))
+        check(self.lib.hk_wprog_upload(self.handle, ptr(ops), _size(ops) // 32, _nullable(refs), _size(refs) // 4, ptr(vmap), n_v,
+                                       int(n_values), int(n_inputs), C.byref(h)), "hk_wprog_upload")
+        return WordProgram(self, h, n_v, int(n_inputs))
 
     def bases_upload(self, group, bases, n=None):
         """Makes a static base set resident with its shift tables (hk_bases_upload); returns a ResidentBases."""
-        pb = self.g1_bytes if group == 1 else self.g2_bytes
-        n = n if n is not None else len(bases) // pb
+        n = n if n is not None else _size(bases) // self._group(group)[0]
         h = C.c_void_p()
         check(self.lib.hk_bases_upload(self.handle, int(group), ptr(bases), n, C.byref(h)), "hk_bases_upload")
         return ResidentBases(self, h, group, n)
@@ -669,10 +672,10 @@ class Context:
         """Montgomery <-> canonical for a packed array of Fr (`which` = 0) or Fq (1) elements: what ark-ff
         `from_bigint` / `into_bigint` do under ark-serialize.  Returns a new numpy uint8 array."""
         eb = self.fr_bytes if which == 0 else self.fq_bytes
-        data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
-        n = data.size // eb
+        data = _hd(data)
+        n = _size(data) // eb
         out = np.empty(n * eb, dtype=np.uint8)
-        check(self.lib.hk_field_convert(self.handle, int(which), data.ctypes.data, out.ctypes.data, n, int(to_mont)),
+        check(self.lib.hk_field_convert(self.handle, int(which), ptr(data), out.ctypes.data, n, int(to_mont)),
               "hk_field_convert")
         return out
 
@@ -685,14 +688,8 @@ class Context:
         """R1CSToQAP::witness_map (prover.rs:123).  A/B/Cm: (row_ptr u64, col u32, val bytes) triples.
         Returns (h bytes [m Fr, natural order], m)."""
         keep = []
-        csrs = []
-        for (rp, col, val) in (A, B, Cm):
-            rp = np.ascontiguousarray(rp, dtype=np.uint64)
-            col = np.ascontiguousarray(col, dtype=np.uint32)
-            val = np.ascontiguousarray(val, dtype=np.uint8)
-            keep += [rp, col, val]
-            csrs.append(hk_csr(rp.ctypes.data, col.ctypes.data, val.ctypes.data, len(rp) - 1, len(col)))
-        nv = n_v if n_v is not None else len(z) // self.fr_bytes
+        csrs = self._csrs((A, B, Cm), keep)
+        nv = n_v if n_v is not None else _size(z) // self.fr_bytes
         m = 1
         while m < n_constraints + n_inst:
             m *= 2
@@ -710,19 +707,16 @@ class Context:
         for (rp, col, val) in matrices:
             arrs = [_hd(rp, np.uint64), _hd(col, np.uint32), _hd(val)]
             keep += arrs
-            n_rows = arrs[0].nbytes // 8 - 1
-            nnz = arrs[1].nbytes // 4
-            out.append(hk_csr(*[_nullable(x) for x in arrs], n_rows, nnz))
+            out.append(hk_csr(*[_nullable(x) for x in arrs], _size(arrs[0]) // 8 - 1, _size(arrs[1]) // 4))
         return out
 
     def qap_eval(self, A, B, Cm, n_inst, n_constraints, n_v, t, out=None):
         """hk_qap_eval (instance_map_with_evaluation, generator.rs:75-76) at t (int, or Montgomery bytes).  A/B/Cm: CSR
         triples as in witness_map (members may be DeviceBuffers).  out: optional (a, b, c) DeviceBuffers of n_v Fr each.
         Returns (a, b, c, zt, m): a/b/c Montgomery bytes (numpy, or the given DeviceBuffers), zt Montgomery bytes."""
-        from .cp_groth16 import FrCodec
         keep = []
         csrs = self._csrs((A, B, Cm), keep)
-        t = FrCodec(self.curve).enc1(t) if isinstance(t, int) else np.ascontiguousarray(t, dtype=np.uint8)
+        t = self.fc.enc1(t) if isinstance(t, int) else np.ascontiguousarray(t, dtype=np.uint8)
         outs = out if out is not None else [np.zeros(n_v * self.fr_bytes, dtype=np.uint8) for _ in range(3)]
         zt = np.zeros(self.fr_bytes, dtype=np.uint8)
         m = C.c_size_t()
@@ -738,9 +732,7 @@ class Context:
         on_device: a_g, b_g, b_h, h_g come back as DeviceBuffers (the rest on the host).  Returns a dict of packed-affine
         arrays: a_g, b_g, b_h, h_g, ck (list per stage), deltas_g, alpha_g, beta_g, gamma_abc_g, beta_h, gamma_h, deltas_h,
         and m; with with_qap also qap_abc (3 n_v Fr, Montgomery bytes, a | b | c)."""
-        from .cp_groth16 import FrCodec
-        fc = FrCodec(self.curve)
-        enc = lambda x: fc.enc1(x) if isinstance(x, int) else np.ascontiguousarray(x, dtype=np.uint8)
+        enc = lambda x: self.fc.enc1(x) if isinstance(x, int) else np.ascontiguousarray(x, dtype=np.uint8)
         keep = []
         csrs = self._csrs(matrices, keep)
         ns = len(stage_ranges)
@@ -760,7 +752,6 @@ class Context:
         sr = np.array([v for be in stage_ranges for v in be], dtype=np.uint64)
         sc = [enc(x) for x in (alpha, beta, gamma, t, g1_scalar, g2_scalar)]
         dl = np.concatenate([enc(x) for x in deltas]) if ns else np.zeros(0, np.uint8)
-        keep += [sr, dl] + sc
         d = hk_keygen_desc(C.pointer(csrs[0]), C.pointer(csrs[1]), C.pointer(csrs[2]), n_inst, n_constraints, n_v,
                            sr.ctypes.data if ns else None, ns, *[x.ctypes.data for x in sc], dl.ctypes.data if ns else None)
         ckp = _ptr_array(res["ck"])
@@ -768,13 +759,8 @@ class Context:
                           *[_nullable(res[k]) for k in ("deltas_g", "alpha_g", "beta_g", "gamma_abc_g", "beta_h", "gamma_h",
                                                         "deltas_h")], _nullable(res.get("qap_abc")))
         m_out = C.c_size_t()
-        try:
+        with _owned(res.values()):
             check(self.lib.hk_keygen(self.handle, C.byref(d), C.byref(o), C.byref(m_out)), "hk_keygen")
-        except HekatonError:
-            for k in ("a_g", "b_g", "b_h", "h_g"):
-                if isinstance(res[k], DeviceBuffer):
-                    res[k].free()
-            raise
         res["m"] = m_out.value
         return res
 
@@ -791,7 +777,7 @@ class Context:
         offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
         n_sub = offsets.size - 1
         keep = [_hd(time_entries), _hd(addr_entries)]
-        ch = _challenge_bytes(self.curve, challenges)
+        ch = _challenge_bytes(self, challenges)
         depth = max(n_sub, 1).bit_length() - 1
         fr = self.fr_bytes
         sizes = [2 * n_sub, (2 + entry_fields) * n_sub, 2 * n_sub - 1, n_sub * depth, 1]
@@ -799,7 +785,7 @@ class Context:
             outs = list(out)
             assert [x.nbytes >= k * fr for x, k in zip(outs, sizes)] == [True] * 5
         else:
-            outs = [DeviceBuffer(self, max(k, 1) * fr) if device_out else np.zeros(max(k, 0) * fr, dtype=np.uint8) for k in sizes]
+            outs = self._outputs([max(k, 0) * fr for k in sizes], device_out)
         a, b = hk_poseidon_desc(*ld), hk_poseidon_desc(*nd)
         d = hk_exec_tree_desc(n_sub, int(entry_fields), offsets.ctypes.data, _nullable(keep[0]), _nullable(keep[1]),
                               ch.ctypes.data, ptr(consts), int(n_consts), C.pointer(a), C.pointer(b))
@@ -830,7 +816,7 @@ class Context:
         sub_index = np.ascontiguousarray(sub_index, dtype=np.uint32)
         evals, leaves, _nodes, siblings, root = exec_outs
         keep = [_hd(x) for x in (time_entries, addr_entries, evals, leaves, siblings, root) + tuple(extra)]
-        ch = _challenge_bytes(self.curve, challenges)
+        ch = _challenge_bytes(self, challenges)
         a, b = hk_poseidon_desc(*ld), hk_poseidon_desc(*nd)
         d = desc(n_sub, int(n_portals), max(n_sub, 1).bit_length() - 1, offsets.ctypes.data, _nullable(keep[0]),
                  _nullable(keep[1]), ch.ctypes.data, *[_nullable(x) for x in keep[2:6]], ptr(consts), int(n_consts),
@@ -847,15 +833,9 @@ class Context:
         perm): sorted entry j = time entry perm[j], uint32 (a numpy array, or a DeviceBuffer when device_out is set)."""
         k, fr = int(entry_fields), self.fr_bytes
         src = _hd(time_entries)
-        if n_entries is None:
-            n_entries = (src.nbytes if isinstance(src, DeviceBuffer) else src.size) // (max(k, 1) * fr)
-        n = int(n_entries)
-        if device_out:
-            out = DeviceBuffer(self, max(n * k * fr, 1))
-            perm = DeviceBuffer(self, max(4 * n, 1)) if want_perm else None
-        else:
-            out = np.zeros(n * k * fr, dtype=np.uint8)
-            perm = np.zeros(n, dtype=np.uint32) if want_perm else None
+        n = int(n_entries) if n_entries is not None else _size(src) // (max(k, 1) * fr)
+        out, *perm = self._outputs([n * k * fr] + [4 * n] * bool(want_perm), device_out)
+        perm = None if not want_perm else perm[0] if device_out else perm[0].view(np.uint32)
         with _owned((out, perm)):
             check(self.lib.hk_trace_sort(self.handle, k, ptr(src) if n else None, n, ptr(out) if n else None,
                                          ptr(perm) if n else None), "hk_trace_sort")
@@ -886,8 +866,7 @@ class Context:
         if isinstance(leaves, (list, tuple)):
             leaves = np.frombuffer(b"".join(leaves), np.uint8)
         src = _hd(leaves)
-        sizes = [32 * n, 2 * n * k * fr, fr]
-        outs = [DeviceBuffer(self, max(b, 1)) if device_out else np.zeros(b, dtype=np.uint8) for b in sizes]
+        outs = self._outputs([32 * n, 2 * n * k * fr, fr], device_out)
         o = hk_sha_tree_out(*[ptr(x) for x in outs])
         with _owned(outs):
             check(self.lib.hk_sha_tree(self.handle, ptr(src), n, int(ns), k, C.byref(o)), "hk_sha_tree")
@@ -901,7 +880,9 @@ class Context:
         keep = [_hd(leaves), _hd(digests)]
         sub_index = np.ascontiguousarray(sub_index, dtype=np.uint32)
         batch, k = sub_index.size, int(n_inputs)
-        out = DeviceBuffer(self, max(4 * batch * k, 1)) if device_out else np.zeros((batch, k), dtype=np.uint32)
+        out, = self._outputs([4 * batch * k], device_out)
+        if not device_out:
+            out = out.view(np.uint32).reshape(batch, k)
         with _owned((out,)):
             check(self.lib.hk_sha_tree_inputs(self.handle, ptr(keep[0]), ptr(keep[1]), int(n_sub), k, _nullable(sub_index), batch,
                                               ptr(out)), "hk_sha_tree_inputs")
@@ -945,7 +926,7 @@ class Context:
         n = int(tables["n_txs"]) * int(np.asarray(tables["slot_offsets"])[-1]) * 2 * self.fr_bytes
         own = out is None
         if own:
-            out = DeviceBuffer(self, max(n, 1)) if device_out else np.zeros(n, dtype=np.uint8)
+            out, = self._outputs([n], device_out)
         with _owned((out,), own):
             check(self.lib.hk_r1cs_job_trace(self.handle, C.byref(d), ptr(out)), "hk_r1cs_job_trace")
         return out
@@ -985,7 +966,7 @@ class Context:
         sizes = [(3 + int(tables["n_updates"]) * (2 + 3 * int(tables["split"]))) * fr, 2 * int(d.n_slots) * fr]
         own = out is None
         if own:
-            out = tuple(DeviceBuffer(self, max(b, 1)) if device_out else np.zeros(b, dtype=np.uint8) for b in sizes)
+            out = tuple(self._outputs(sizes, device_out))
         with _owned(out, own):
             check(self.lib.hk_vkd_trace(self.handle, C.byref(d), ptr(out[0]), ptr(out[1])), "hk_vkd_trace")
         return out
@@ -1018,15 +999,14 @@ class Context:
         if isinstance(leaves, (bytes, bytearray)):
             leaves = np.frombuffer(bytes(leaves), np.uint8)
         keep = [_hd(leaves0), _hd(leaves), _hd(consts)]
-        m = 0 if keep[0] is None else (keep[0].nbytes if isinstance(keep[0], DeviceBuffer) else keep[0].size) // 66
+        m = _size(keep[0]) // 66
         u, fr = kinds.size, self.fr_bytes
         a, b = hk_poseidon_desc(*ld), hk_poseidon_desc(*nd)
         d = hk_vkd_tree_desc(int(depth), m, _nullable(keep[0]) if m else None, u, _nullable(kinds), _nullable(keep[1]),
                              _nullable(keep[2]), int(n_consts), C.pointer(a), C.pointer(b))
         own = out is None
         if own:
-            sizes = [u * int(depth) * fr, 2 * fr, u]
-            out = tuple(DeviceBuffer(self, max(n, 1)) if device_out else np.zeros(n, dtype=np.uint8) for n in sizes)
+            out = self._outputs([u * int(depth) * fr, 2 * fr, u], device_out)
         with _owned(out, own):
             check(self.lib.hk_vkd_tree(self.handle, C.byref(d), ptr(out[0]), ptr(out[1]), ptr(out[2])), "hk_vkd_tree")
         return tuple(out)
@@ -1034,9 +1014,9 @@ class Context:
     def _r1cs_call(self, fn, head, z, n_v, batch, cap, want_vals):
         """The shared tail of Context.r1cs_check / DevicePk.r1cs_check: `fn(*head, z, n_v, batch, verdicts, rows, vals, cap)`."""
         fr, batch, cap = self.fr_bytes, int(batch), int(cap)
-        zz = z if isinstance(z, DeviceBuffer) else np.ascontiguousarray(z, dtype=np.uint8).reshape(-1)
+        zz = _hd(z)
         if n_v is None:
-            n_v = (zz.nbytes if isinstance(zz, DeviceBuffer) else zz.size) // (fr * max(batch, 1))
+            n_v = _size(zz) // (fr * max(batch, 1))
         verdicts = np.zeros((batch, 2), dtype=np.uint32)               # hk_r1cs_verdict: n_bad, first_bad
         rows = np.zeros((batch, cap), dtype=np.uint32) if cap else None
         vals = np.zeros((batch, cap, 3 * fr), dtype=np.uint8) if cap and want_vals else None
@@ -1061,10 +1041,9 @@ class Context:
     def points_check(self, group, pts, n=None):
         """hk_points_check_g1 / _g2: ark's AffineRepr::check of each point (on its curve, in the prime-order subgroup;
         infinity passes).  pts: packed affine bytes (uint8 array or DeviceBuffer).  Returns np.uint8[n] of 0 / 1."""
-        pb = self.g1_bytes if group == 1 else self.g2_bytes
-        n = n if n is not None else len(pts) // pb
+        pb, fn = self._group(group, "hk_points_check")
+        n = n if n is not None else _size(pts) // pb
         ok = np.zeros(n, dtype=np.uint8)
-        fn = self.lib.hk_points_check_g1 if group == 1 else self.lib.hk_points_check_g2
         check(fn(self.handle, ptr(pts) if n else None, n, ok.ctypes.data), fn.__name__)
         return ok
 
@@ -1073,7 +1052,7 @@ class Context:
         the root that is not larger than its negative (ark's order), zeros where there is none; ok np.uint8[n] of 1 / 0."""
         eb = self.fq_bytes * int(which)
         data = _hd(data)
-        n = (data.nbytes if isinstance(data, DeviceBuffer) else data.size) // eb
+        n = _size(data) // eb
         out, ok = np.zeros(n * eb, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
         check(self.lib.hk_field_sqrt(self.handle, int(which), ptr(data) if n else None, n, out.ctypes.data, ok.ctypes.data),
               "hk_field_sqrt")
@@ -1085,40 +1064,35 @@ class Context:
         (points, status): packed affine Montgomery points and np.uint8[n] of 1 ok | 0 no such point (zeros) | 2 - with
         `check` - outside the prime-order subgroup.  `out` may be a DeviceBuffer / DeviceView of n points: they stay in
         HBM (ready for hk_pk_upload) and `out` is returned as `points`."""
-        xb = self.fq_bytes * (1 if group == 1 else 2)
+        pb, fn = self._group(group, "hk_points_decompress")
         x_canon, flags = _hd(x_canon), _hd(flags)
-        n = flags.nbytes if isinstance(flags, DeviceBuffer) else flags.size
-        pts = out if out is not None else np.zeros(2 * n * xb, dtype=np.uint8)
+        n = _size(flags)
+        pts = out if out is not None else np.zeros(n * pb, dtype=np.uint8)
         status = np.zeros(n, dtype=np.uint8)
-        fn = self.lib.hk_points_decompress_g1 if group == 1 else self.lib.hk_points_decompress_g2
-        st = fn(self.handle, ptr(x_canon) if n else None, ptr(flags) if n else None, n, int(bool(check)),
-                ptr(pts) if n else None, status.ctypes.data)
-        if st != HK_OK:                                    # the module's check() is shadowed by the keyword
-            raise HekatonError(st, fn.__name__)
+        _check(fn(self.handle, ptr(x_canon) if n else None, ptr(flags) if n else None, n, int(bool(check)),
+                  ptr(pts) if n else None, status.ctypes.data), fn.__name__)
         return pts, status
 
     def points_compress(self, group, pts):
         """hk_points_compress_g1 / _g2: the x coordinate and `SWFlags::from_y_coordinate` of `serialize_compressed`.  pts:
         packed affine Montgomery points (uint8 array or DeviceBuffer).  Returns (x_canon, flags) as points_decompress takes
         them."""
-        xb = self.fq_bytes * (1 if group == 1 else 2)
+        pb, fn = self._group(group, "hk_points_compress")
         pts = _hd(pts)
-        n = (pts.nbytes if isinstance(pts, DeviceBuffer) else pts.size) // (2 * xb)
-        x, flags = np.zeros(n * xb, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
-        fn = self.lib.hk_points_compress_g1 if group == 1 else self.lib.hk_points_compress_g2
+        n = _size(pts) // pb
+        x, flags = np.zeros(n * pb // 2, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
         check(fn(self.handle, ptr(pts) if n else None, n, x.ctypes.data, flags.ctypes.data), fn.__name__)
         return x, flags
 
     def vk_prepare(self, *, alpha_g, beta_h, gamma_h, deltas_h, gamma_abc_g):
         """hk_vk_prepare (prepare_verifying_key, verifier.rs:7-18).  deltas_h: the stage deltas then delta_last, packed G2
         bytes; gamma_abc_g: packed G1 bytes.  Returns a DeviceVk."""
-        arrs = [np.ascontiguousarray(x, dtype=np.uint8).reshape(-1) for x in (alpha_g, beta_h, gamma_h, deltas_h, gamma_abc_g)]
-        if len(arrs[0]) != self.g1_bytes or len(arrs[1]) != self.g2_bytes or len(arrs[2]) != self.g2_bytes:
+        arrs = [_hd(x) for x in (alpha_g, beta_h, gamma_h, deltas_h, gamma_abc_g)]
+        size = [_size(x) for x in arrs]
+        if size[:3] != [self.g1_bytes, self.g2_bytes, self.g2_bytes] or size[3] % self.g2_bytes or size[4] % self.g1_bytes:
             raise HekatonError(HK_ERR_LEN, "hk_vk_prepare")
-        if len(arrs[3]) % self.g2_bytes or len(arrs[4]) % self.g1_bytes:
-            raise HekatonError(HK_ERR_LEN, "hk_vk_prepare")
-        d = hk_vk_desc(arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[2].ctypes.data, arrs[3].ctypes.data,
-                       len(arrs[3]) // self.g2_bytes, arrs[4].ctypes.data, len(arrs[4]) // self.g1_bytes)
+        d = hk_vk_desc(ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), ptr(arrs[3]), size[3] // self.g2_bytes, ptr(arrs[4]),
+                       size[4] // self.g1_bytes)
         h = C.c_void_p()
         check(self.lib.hk_vk_prepare(self.handle, C.byref(d), C.byref(h)), "hk_vk_prepare")
         return DeviceVk(self, h, d.n_deltas, d.n_abc)
@@ -1127,40 +1101,17 @@ class Context:
                   matrices=None, n_inst=0, n_constraints=0):
         """hk_pk_upload: all arguments packed-affine numpy uint8 arrays (or DeviceBuffers with explicit
         lengths via (buf, n) tuples).  matrices = (A, B, C) CSR triples as in witness_map."""
-        def arr(x):
-            return x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8)
-
-        def addr(x):
-            return x.ptr if isinstance(x, DeviceBuffer) else x.ctypes.data
-
-        def nbytes(x):
-            return x.nbytes
+        g1, g2 = self.g1_bytes, self.g2_bytes
+        big = [_hd(x) for x in (a_g, b_g, b_h, h_g)]
+        cks = [_hd(c) for c in ck_stages]
+        small = [_hd(x) for x in (deltas_g, last_delta_h, alpha_g, beta_g, beta_h)]
+        ck_ptrs = (C.c_void_p * len(cks))(*[ptr(c) for c in cks])          # an empty stage by its address, as the rest here
+        ck_lens = (C.c_size_t * len(cks))(*[_size(c) // g1 for c in cks])
         keep = []
-        d = hk_pk_desc()
-        a_g, b_g, b_h, h_g = arr(a_g), arr(b_g), arr(b_h), arr(h_g)
-        keep += [a_g, b_g, b_h, h_g]
-        d.a_g, d.a_len = addr(a_g), nbytes(a_g) // self.g1_bytes
-        d.b_g, d.b_g_len = addr(b_g), nbytes(b_g) // self.g1_bytes
-        d.b_h, d.b_h_len = addr(b_h), nbytes(b_h) // self.g2_bytes
-        d.h_g, d.h_len = addr(h_g), nbytes(h_g) // self.g1_bytes
-        cks = [arr(c) for c in ck_stages]
-        keep += cks
-        ck_ptrs = (C.c_void_p * len(cks))(*[addr(c) for c in cks])
-        ck_lens = (C.c_size_t * len(cks))(*[nbytes(c) // self.g1_bytes for c in cks])
-        d.ck_stage, d.ck_len, d.n_stages = ck_ptrs, ck_lens, len(cks)
-        small = [arr(x) for x in (deltas_g, last_delta_h, alpha_g, beta_g, beta_h)]
-        keep += small
-        d.deltas_g, d.last_delta_h, d.alpha_g, d.beta_g, d.beta_h = [addr(s) for s in small]
-        csrs = []
-        if matrices is not None:
-            for (rp, col, val) in matrices:
-                rp = np.ascontiguousarray(rp, dtype=np.uint64)
-                col = np.ascontiguousarray(col, dtype=np.uint32)
-                val = arr(val)
-                keep += [rp, col, val]
-                csrs.append(hk_csr(rp.ctypes.data, col.ctypes.data, val.ctypes.data, len(rp) - 1, len(col)))
-            d.A, d.B, d.C = C.pointer(csrs[0]), C.pointer(csrs[1]), C.pointer(csrs[2])
-        d.n_inst, d.n_constraints = n_inst, n_constraints
+        csrs = self._csrs(matrices, keep) if matrices is not None else [None] * 3
+        d = hk_pk_desc(ptr(big[0]), _size(big[0]) // g1, ptr(big[1]), _size(big[1]) // g1, ptr(big[2]), _size(big[2]) // g2,
+                       ptr(big[3]), _size(big[3]) // g1, ck_ptrs, ck_lens, len(cks), *[ptr(x) for x in small],
+                       *[m and C.pointer(m) for m in csrs], n_inst, n_constraints)
         h = C.c_void_p()
         check(self.lib.hk_pk_upload(self.handle, C.byref(d), C.byref(h)), "hk_pk_upload")
         return DevicePk(self, h)
@@ -1175,27 +1126,26 @@ class WordProgram:
     def run(self, inputs, full_cols, full_vals, out=None, batch=None):
         """inputs: uint32 (batch, n_inputs), or a DeviceBuffer of it with an explicit batch=; full_cols: uint32 (k);
         full_vals: Montgomery bytes (batch, k * fr_bytes).  Returns a DeviceBuffer holding batch x n_v Fr (or fills `out`)."""
-        if isinstance(inputs, DeviceBuffer):
+        if isinstance(inputs, DeviceBuffer):                   # a buffer does not say how many rows of it are meant
             assert batch is not None and inputs.nbytes >= 4 * int(batch) * self.n_inputs, "a DeviceBuffer of inputs needs batch="
-            batch, in_ptr = int(batch), inputs.ptr
+            batch = int(batch)
         else:
-            inputs = np.ascontiguousarray(inputs, dtype=np.uint32)
-            batch, in_ptr = inputs.shape[0], inputs.ctypes.data
-        cols = np.ascontiguousarray(full_cols, dtype=np.uint32)
-        vals = np.ascontiguousarray(full_vals, dtype=np.uint8)
+            inputs = _hd(inputs, np.uint32)
+            batch = inputs.shape[0]
+        cols, vals = _hd(full_cols, np.uint32), _hd(full_vals)
+        n_full = _size(cols) // 4
         buf = out if out is not None else DeviceBuffer(self.ctx, batch * self.n_v * self.ctx.fr_bytes)
-        check(self.ctx.lib.hk_wprog_run(self.ctx.handle, self.handle, in_ptr, batch,
-                                        cols.ctypes.data if cols.size else None, vals.ctypes.data if cols.size else None,
-                                        cols.size, buf.ptr), "hk_wprog_run")
+        check(self.ctx.lib.hk_wprog_run(self.ctx.handle, self.handle, ptr(inputs), batch, ptr(cols) if n_full else None,
+                                        ptr(vals) if n_full else None, n_full, buf.ptr), "hk_wprog_run")
         return buf
 
     def scatter(self, full_cols, full_vals, out):
         """The full-width values alone (hk_assignment_scatter), into assignments `run(inputs, [], [], out=...)` produced."""
-        cols = np.ascontiguousarray(full_cols, dtype=np.uint32)
-        vals = np.ascontiguousarray(full_vals, dtype=np.uint8)
-        batch = vals.size // max(1, cols.size * self.ctx.fr_bytes)
-        check(self.ctx.lib.hk_assignment_scatter(self.ctx.handle, cols.ctypes.data, vals.ctypes.data, cols.size, batch, self.n_v,
-                                                 out.ptr), "hk_assignment_scatter")
+        cols, vals = _hd(full_cols, np.uint32), _hd(full_vals)
+        n_full = _size(cols) // 4
+        batch = _size(vals) // max(1, n_full * self.ctx.fr_bytes)
+        check(self.ctx.lib.hk_assignment_scatter(self.ctx.handle, ptr(cols), ptr(vals), n_full, batch, self.n_v, out.ptr),
+              "hk_assignment_scatter")
         return out
 
     def free(self):
@@ -1212,8 +1162,8 @@ class ResidentBases:
 
     def msm(self, scalars, n_scalars=None, montgomery=True, checked=True):
         """`G::Group::msm(&srs_powers, &coeffs)` (distributed-prover/src/kzg.rs:151-152) over the resident bases."""
-        ns = n_scalars if n_scalars is not None else len(scalars) // self.ctx.fr_bytes
-        out = np.zeros(self.ctx.g1_bytes if self.group == 1 else self.ctx.g2_bytes, dtype=np.uint8)
+        ns = n_scalars if n_scalars is not None else _size(scalars) // self.ctx.fr_bytes
+        out = np.zeros(self.ctx._group(self.group)[0], dtype=np.uint8)
         check(self.ctx.lib.hk_msm_bases(self.ctx.handle, self.handle, ptr(scalars), ns, int(montgomery), int(checked),
                                         out.ctypes.data), "hk_msm_bases")
         return out
@@ -1250,8 +1200,7 @@ class DeviceVk:
         nd, nk = self.n_deltas - 1, self.n_abc - 1
         for arr, per in ((a, ctx.g1_bytes), (b, ctx.g2_bytes), (c, ctx.g1_bytes), (ds, nd * ctx.g1_bytes),
                          (inputs, nk * ctx.fr_bytes)):
-            size = arr.nbytes if isinstance(arr, DeviceBuffer) else (0 if arr is None else np.asarray(arr).nbytes)
-            if size != n * per:
+            if _size(arr) != n * per:
                 raise HekatonError(HK_ERR_LEN, "hk_verify_batch")
         if rand is not None:
             rr = np.ascontiguousarray(rand, dtype=np.uint8).reshape(-1)
@@ -1267,18 +1216,16 @@ class DeviceVk:
         verdicts: optional DeviceBuffer of n bytes to write to instead of a new host array."""
         ctx = self.ctx
         if n is None:
-            n = (a.nbytes if isinstance(a, DeviceBuffer) else np.asarray(a).nbytes) // ctx.g1_bytes
+            n = _size(a) // ctx.g1_bytes
         ds = ds if ds is not None else np.zeros(0, dtype=np.uint8)
         inputs = inputs if inputs is not None else np.zeros(0, dtype=np.uint8)
         self.check_args(n, a, b, c, ds, inputs, rand)
-        keep = [x if isinstance(x, DeviceBuffer) else np.ascontiguousarray(x, dtype=np.uint8) for x in (a, b, c, ds, inputs)]
-        rr = None if rand is None else np.ascontiguousarray(rand, dtype=np.uint8).reshape(-1)
+        ops = [_hd(x) for x in (a, b, c, ds, inputs)]
+        rr = _hd(rand)
         out = verdicts if verdicts is not None else np.zeros(n, dtype=np.uint8)
         flags = HK_VERIFY_CHECK_POINTS if check_points else 0
-        nz = lambda x: ptr(x) if n and (x.nbytes if isinstance(x, DeviceBuffer) else x.size) else None
-        check(ctx.lib.hk_verify_batch(ctx.handle, self.handle, nz(keep[0]), nz(keep[1]), nz(keep[2]), nz(keep[3]),
-                                      nz(keep[4]), n, flags, None if rr is None else rr.ctypes.data, ptr(out)),
-              "hk_verify_batch")
+        check(ctx.lib.hk_verify_batch(ctx.handle, self.handle, *[_nullable(x) if n else None for x in ops], n, flags, ptr(rr),
+                                      ptr(out)), "hk_verify_batch")
         return out
 
 
@@ -1302,11 +1249,11 @@ class DevicePk:
     def commit(self, stage, w_stage, kappa, n=None):
         """committer.rs:87-91 — msm(ck[stage], w) + kappa * last_delta_g; returns packed G1 bytes."""
         ctx = self.ctx
-        n = n if n is not None else len(w_stage) // ctx.fr_bytes
-        kappa = np.ascontiguousarray(kappa, dtype=np.uint8)
+        n = n if n is not None else _size(w_stage) // ctx.fr_bytes
+        kappa = _hd(kappa)
         out = np.zeros(ctx.g1_bytes, dtype=np.uint8)
-        check(ctx.lib.hk_commit(ctx.handle, self.handle, stage, ptr(w_stage) if n else None, n,
-                                kappa.ctypes.data, out.ctypes.data), "hk_commit")
+        check(ctx.lib.hk_commit(ctx.handle, self.handle, stage, ptr(w_stage) if n else None, n, ptr(kappa), out.ctypes.data),
+              "hk_commit")
         return out
 
     def commit_batch(self, stage, w_rows, kappas, n, batch):
@@ -1314,26 +1261,23 @@ class DevicePk:
         stage witnesses row after row (batch x n Fr Montgomery; uint8 array or DeviceBuffer); kappas: batch Fr Montgomery
         (uint8 array).  Returns (batch, g1_bytes) uint8."""
         ctx = self.ctx
-        kap = np.ascontiguousarray(kappas, dtype=np.uint8)
+        kap = _hd(kappas)
         out = np.zeros((batch, ctx.g1_bytes), dtype=np.uint8)
-        check(ctx.lib.hk_commit_batch(ctx.handle, self.handle, stage, ptr(w_rows) if n else None, n, kap.ctypes.data, batch,
+        check(ctx.lib.hk_commit_batch(ctx.handle, self.handle, stage, ptr(w_rows) if n else None, n, ptr(kap), batch,
                                       out.ctypes.data), "hk_commit_batch")
         return out
 
     def prove(self, z, r, s, kappas, n_v=None):
         """prover.rs:78-155 + committer.rs:112-114; returns (a, b, c) packed affine bytes."""
         ctx = self.ctx
-        n_v = n_v if n_v is not None else len(z) // ctx.fr_bytes
-        r = np.ascontiguousarray(r, dtype=np.uint8)
-        s = np.ascontiguousarray(s, dtype=np.uint8)
-        kap = np.ascontiguousarray(kappas, dtype=np.uint8)
-        nk = len(kap) // ctx.fr_bytes
+        n_v = n_v if n_v is not None else _size(z) // ctx.fr_bytes
+        r, s, kap = _hd(r), _hd(s), _hd(kappas)
+        nk = _size(kap) // ctx.fr_bytes
         a = np.zeros(ctx.g1_bytes, dtype=np.uint8)
         b = np.zeros(ctx.g2_bytes, dtype=np.uint8)
         c = np.zeros(ctx.g1_bytes, dtype=np.uint8)
-        check(ctx.lib.hk_prove(ctx.handle, self.handle, ptr(z), n_v, r.ctypes.data, s.ctypes.data,
-                               kap.ctypes.data if nk else None, nk, a.ctypes.data, b.ctypes.data,
-                               c.ctypes.data), "hk_prove")
+        check(ctx.lib.hk_prove(ctx.handle, self.handle, ptr(z), n_v, ptr(r), ptr(s), ptr(kap) if nk else None, nk,
+                               a.ctypes.data, b.ctypes.data, c.ctypes.data), "hk_prove")
         return a, b, c
 
     def prove_batch(self, z_rows, rs, ss, kappas, n_v, batch):
@@ -1342,14 +1286,11 @@ class DevicePk:
         (uint8 arrays, Montgomery).  Returns (a, b, c) as (batch, g1 | g2 | g1 bytes) uint8 arrays; row b equals
         prove() on row b."""
         ctx = self.ctx
-        r = np.ascontiguousarray(rs, dtype=np.uint8).reshape(-1)
-        s = np.ascontiguousarray(ss, dtype=np.uint8).reshape(-1)
-        kap = np.ascontiguousarray(kappas, dtype=np.uint8).reshape(-1)
-        nk = len(kap) // (ctx.fr_bytes * batch) if batch else 0
+        r, s, kap = _hd(rs), _hd(ss), _hd(kappas)
+        nk = _size(kap) // (ctx.fr_bytes * batch) if batch else 0
         a = np.zeros((batch, ctx.g1_bytes), dtype=np.uint8)
         b = np.zeros((batch, ctx.g2_bytes), dtype=np.uint8)
         c = np.zeros((batch, ctx.g1_bytes), dtype=np.uint8)
-        check(ctx.lib.hk_prove_batch(ctx.handle, self.handle, ptr(z_rows), n_v, r.ctypes.data, s.ctypes.data,
-                                     kap.ctypes.data if nk else None, nk, batch, a.ctypes.data, b.ctypes.data,
-                                     c.ctypes.data), "hk_prove_batch")
+        check(ctx.lib.hk_prove_batch(ctx.handle, self.handle, ptr(z_rows), n_v, ptr(r), ptr(s), ptr(kap) if nk else None, nk,
+                                     batch, a.ctypes.data, b.ctypes.data, c.ctypes.data), "hk_prove_batch")
         return a, b, c

@@ -45,10 +45,7 @@ def _native():
         try:
             import ctypes
             from . import capi
-            fn = capi.load().hk_keccak_f1600
-            fn.argtypes = [ctypes.c_void_p]
-            fn.restype = None
-            _NATIVE = (fn, ctypes)
+            _NATIVE = (capi.load().hk_keccak_f1600, ctypes)
         except Exception:       # noqa: BLE001  (library not built: the Python permutation is the same function)
             _NATIVE = False
     return _NATIVE

@@ -329,7 +329,7 @@ class Tipp:
         ctx, fc, F, r = self.ctx, self.fc, self.F, self.r
         n = srs.n
         g1b, g2b, frb = ctx.g1_bytes, ctx.g2_bytes, ctx.fr_bytes
-        from .capi import DeviceBuffer, check, load
+        from .capi import DeviceBuffer
         t_start = time.perf_counter()
         r_inv = pow(twist, -1, r)
         host = host_scalars()
@@ -358,8 +358,7 @@ class Tipp:
                      go(ctx.scalar_pairing, 1, srs.ck.w1, twib, n, win(4, 0, n)),
                      go(ctx.scalar_pairing, 1, srs.ck.w2, twib, n, win(5, 0, n))]
             for k, src in ((0, np.asarray(A)), (2, srs.ck.v1), (3, srs.ck.v2)):
-                src = np.ascontiguousarray(src, dtype=np.uint8)
-                check(load().hk_dev_upload(ctx.handle, win(k, 0, n).ptr, src.ctypes.data, src.nbytes), "hk_dev_upload")
+                win(k, 0, n).upload(np.ascontiguousarray(src, dtype=np.uint8))
             for f in first:
                 f.result()
             tr = Transcript(r)
