@@ -10,6 +10,9 @@
 //      counting-sorted by bucket with a 128 KiB LDS histogram per workgroup (LDS atomics absorb the
 //      heavy-hitter buckets that SHA-style 0/1 witnesses create) and one global atomic per
 //      (workgroup, non-empty bucket).
+//   1b. k_msm_sub_mark / k_msm_sub_emit / k_msm_sub_starts — a query over a fixed subset of the scalars (the non-infinity
+//      bases of a proving key's A or B query) takes its entry list from the sorted list of the whole vector by stream
+//      compaction instead of sorting its digits again.
 //   2. k_msm_accum0 — the sorted entry list is cut into EQUAL slices, one per lane, regardless of
 //      bucket boundaries (perfect load balance, 64-wide waves never idle on a short bucket); each lane
 //      runs mixed XYZZ adds in registers, writes buckets it fully owns, and emits at most two boundary
@@ -44,6 +47,7 @@ constexpr int MSM_SORT_THREADS = HK_MSM_SORT_THREADS;   // build-time knob (DESI
 // and 64 groups (c = 4) only occur for n < 2^10
 constexpr int MSM_ENTRY_GROUP_SHIFT = 26;
 constexpr int MSM_LDS_COUNTERS = 32768; // 128 KiB of LDS per sort workgroup
+constexpr u32 MSM_RANK_NONE = 0xffffffffu;   // rank table of a sub-list: this scalar index is not in the subset
 
 struct MsmPlan {
     u32 n;            // scalars / entries per group
@@ -115,12 +119,34 @@ __device__ __forceinline__ void msm_load_scalar(const u32* scalars, size_t i, in
     sp[Fr::N + 1] = 0;
 }
 
-__device__ __forceinline__ int msm_digit(const u32 (&sp)[10], u32 w, u32 c) {
-    u32 o = c * w;
-    u32 limb = o >> 5, sh = o & 31;
-    u64 two = ((u64)sp[limb + 1] << 32) | sp[limb];
-    u32 e = (u32)(two >> sh) & ((1u << c) - 1u);
-    return (int)e - (int)(1u << (c - 1));
+// digit w of a window size known at compile time: the limbs it reads are constants once the loop over w is unrolled, so
+// the window array stays in registers (a run-time limb index puts it in private memory: 48 B per lane of k_msm_hist)
+template <u32 C>
+__device__ __forceinline__ int msm_digit_at(const u32 (&sp)[10], u32 w) {
+    const u32 o = C * w;
+    const u32 limb = o >> 5, sh = o & 31;
+    u32 e = sp[limb] >> sh;
+    if (sh + C > 32) e |= sp[limb + 1] << (32 - sh);
+    return (int)(e & ((1u << C) - 1u)) - (int)(1u << (C - 1));
+}
+
+// one scalar's digits: stored window-major and counted in the workgroup's LDS histogram h
+template <class Fr, u32 C>
+__device__ __forceinline__ void msm_hist_scalar(const u32 (&sp)[10], size_t i, const MsmPlan& p, short* __restrict__ digits,
+                                                u32* h) {
+    constexpr u32 WMAX = (Fr::N * 32 + 2 + C - 1) / C;         // no plan of this field has more windows
+#pragma unroll
+    for (u32 w = 0; w < WMAX; w++) {
+        if (w >= p.W) break;
+        int d = msm_digit_at<C>(sp, w);
+        // the signed digits are computed ONCE per scalar (Montgomery reduction + split) and kept, window-major,
+        // for the two passes of k_msm_scatter: 2 bytes per digit, coalesced across the lanes of a wave
+        digits[(size_t)w * p.n + i] = (short)d;
+        if (d != 0) {
+            u32 mag = d < 0 ? (u32)(-d) : (u32)d;
+            atomicAdd(&h[(p.WP == 1 ? 0u : w % p.WP) * p.B + mag - 1], 1u);
+        }
+    }
 }
 
 // ---- counting sort, pass 1: histogram ------------------------------------------------------------
@@ -142,15 +168,11 @@ k_msm_hist(const u32* __restrict__ scalars_all, size_t scalar_stride_words, int 
         if (i >= p.n) break;
         u32 sp[10];
         msm_load_scalar<Fr>(scalars, i, is_mont, p, sp);
-        for (u32 w = 0; w < p.W; w++) {
-            int d = msm_digit(sp, w, p.c);
-            // the signed digits are computed ONCE per scalar (Montgomery reduction + split) and kept, window-major,
-            // for the two passes of k_msm_scatter: 2 bytes per digit, coalesced across the lanes of a wave
-            digits[(size_t)w * p.n + i] = (short)d;
-            if (d != 0) {
-                u32 mag = d < 0 ? (u32)(-d) : (u32)d;
-                atomicAdd(&h[(w % p.WP) * p.B + mag - 1], 1u);
-            }
+        switch (p.c) {                                     // every window size a plan may carry (MsmSort::run: 3 .. 16)
+#define HK_HIST_C(C) case C: msm_hist_scalar<Fr, C>(sp, i, p, digits, h); break;
+            HK_HIST_C(3) HK_HIST_C(4) HK_HIST_C(5) HK_HIST_C(6) HK_HIST_C(7) HK_HIST_C(8) HK_HIST_C(9) HK_HIST_C(10)
+            HK_HIST_C(11) HK_HIST_C(12) HK_HIST_C(13) HK_HIST_C(14) HK_HIST_C(15) HK_HIST_C(16)
+#undef HK_HIST_C
         }
     }
     __syncthreads();
@@ -232,6 +254,92 @@ k_msm_scatter(const short* __restrict__ digits_all, MsmPlan p, u32* __restrict__
             }
         }
     }
+}
+
+// ---- sub-list of a sorted entry list ---------------------------------------------------------------------
+// The entries of a proof's sorted list whose scalar index i belongs to a fixed subset (rank[i] != MSM_RANK_NONE),
+// renumbered to the subset's compact table (index rank[i], group field at the sub-list plan's gshift), in the same
+// order: a stable stream compaction, so bucket order and the order inside a bucket are the source's and no digit is
+// computed or counted again.  Source and sub-list plans share c, W, WP, B and NB (msm_sub_plan).  The list is cut into
+// tiles of MSM_SUB_TILE entries, one wave per tile: k_msm_sub_mark writes the keep bits (one ballot word per 64 entries)
+// and the kept count of every tile, scan_u32 (scan.cuh) turns the counts of all proofs into offsets, k_msm_sub_emit
+// writes every kept entry at its tile's offset plus the kept entries below it, and k_msm_sub_starts maps the bucket
+// boundaries.  msm_sub_tiles tiles per proof: position n W itself (start[NB] of a list without a zero digit) has one.
+// No atomics, no LDS, no private memory.  Proof blockIdx.y.
+constexpr u32 MSM_SUB_TILE = 1024;
+constexpr u32 MSM_SUB_WORDS = MSM_SUB_TILE / 64;          // ballot words per tile
+constexpr int MSM_SUB_THREADS = 256;                      // 4 waves, one tile each
+HK_HD u32 msm_sub_tiles(const MsmPlan& src) { return (u32)(((u64)src.n * src.W) / MSM_SUB_TILE) + 1u; }
+
+template <int UNUSED>
+__global__ void __launch_bounds__(MSM_SUB_THREADS)
+k_msm_sub_mark(const u32* __restrict__ sorted_all, const u32* __restrict__ start_all, MsmPlan ps,
+               const u32* __restrict__ rank, u64* __restrict__ mask_all, u32* __restrict__ tcount_all) {
+    const size_t pr = blockIdx.y;
+    const u32 tiles = msm_sub_tiles(ps);
+    const u32 tile = blockIdx.x * (MSM_SUB_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (tile >= tiles) return;
+    const u32* __restrict__ sorted = sorted_all + pr * msm_sorted_stride(ps);
+    const u32 E = start_all[pr * (ps.NB + 1) + ps.NB];
+    u64* __restrict__ mask = mask_all + (pr * tiles + tile) * MSM_SUB_WORDS;
+    const u32 imask = (1u << ps.gshift) - 1u;
+    u32 kept = 0;
+#pragma unroll 4
+    for (u32 k = 0; k < MSM_SUB_WORDS; k++) {
+        const u32 pos = tile * MSM_SUB_TILE + k * 64 + lane;
+        bool keep = false;
+        if (pos < E) keep = rank[sorted[pos] & imask] != MSM_RANK_NONE;
+        const u64 word = __ballot(keep);
+        if (lane == 0) mask[k] = word;
+        kept += (u32)__popcll(word);
+    }
+    if (lane == 0) tcount_all[pr * tiles + tile] = kept;
+}
+
+// toff_all: the exclusive scan of tcount_all over every proof's tiles; a proof's own offsets count from its first tile's
+template <int UNUSED>
+__global__ void __launch_bounds__(MSM_SUB_THREADS)
+k_msm_sub_emit(const u32* __restrict__ sorted_all, MsmPlan ps, const u32* __restrict__ rank,
+               const u64* __restrict__ mask_all, const u32* __restrict__ toff_all, MsmPlan pd, u32* __restrict__ out_all) {
+    const size_t pr = blockIdx.y;
+    const u32 tiles = msm_sub_tiles(ps);
+    const u32 tile = blockIdx.x * (MSM_SUB_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (tile >= tiles) return;
+    const u32* __restrict__ sorted = sorted_all + pr * msm_sorted_stride(ps);
+    u32* __restrict__ out = out_all + pr * msm_sorted_stride(pd);
+    const u64* __restrict__ mask = mask_all + (pr * tiles + tile) * MSM_SUB_WORDS;
+    const u32 imask = (1u << ps.gshift) - 1u;
+    const u64 below = ((u64)1 << lane) - 1u;
+    u32 run = toff_all[pr * tiles + tile] - toff_all[pr * tiles];
+#pragma unroll 4
+    for (u32 k = 0; k < MSM_SUB_WORDS; k++) {
+        const u64 word = mask[k];
+        if ((word >> lane) & 1u) {
+            const u32 e = sorted[tile * MSM_SUB_TILE + k * 64 + lane];
+            const u32 g = (e & 0x7fffffffu) >> ps.gshift;
+            out[run + (u32)__popcll(word & below)] = (e & 0x80000000u) | (g << pd.gshift) | rank[e & imask];
+        }
+        run += (u32)__popcll(word);
+    }
+}
+
+// start_dst[b] = kept entries below position start_src[b], b = 0 .. NB: a bucket that loses every entry gets
+// start_dst[b] == start_dst[b + 1], which the bucket kernels treat as empty
+template <int UNUSED>
+__global__ void __launch_bounds__(256)
+k_msm_sub_starts(const u32* __restrict__ start_src_all, MsmPlan ps, const u64* __restrict__ mask_all,
+                 const u32* __restrict__ toff_all, u32* __restrict__ start_dst_all) {
+    const size_t pr = blockIdx.y;
+    const u32 b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b > ps.NB) return;
+    const u32 tiles = msm_sub_tiles(ps);
+    const u32 pos = start_src_all[pr * (ps.NB + 1) + b];
+    const u32 tile = pos / MSM_SUB_TILE, in = pos % MSM_SUB_TILE;
+    const u64* __restrict__ mask = mask_all + (pr * tiles + tile) * MSM_SUB_WORDS;
+    u32 v = toff_all[pr * tiles + tile] - toff_all[pr * tiles];
+    for (u32 k = 0; k < in / 64; k++) v += (u32)__popcll(mask[k]);
+    if (in % 64) v += (u32)__popcll(mask[in / 64] & (((u64)1 << (in % 64)) - 1u));
+    start_dst_all[pr * (ps.NB + 1) + b] = v;
 }
 
 // ---- point I/O -----------------------------------------------------------------------------------------
@@ -731,6 +839,29 @@ inline MsmPlan msm_make_plan(u32 n, u32 fr_bits, u32 c, u32 WP, u32 max_lanes0, 
         p.kconst[bit >> 5] |= 1u << (bit & 31);
     }
     return p;
+}
+
+// ---- sub-lists: the plan rule of a compacted query (pk.cuh) ---------------------------------------------
+// The plan of a sub-list over `n` of the source plan's scalars.  It reuses the source's digits, so c - and with it W, WP, F, B,
+// NB, K and kconst - are the source's, whatever window a vector of n scalars would pick for itself; n, gshift, the sort
+// chunk and the lane counts are its own.
+inline MsmPlan msm_sub_plan(const MsmPlan& src, u32 n, u32 max_lanes0) {
+    MsmPlan p = src;
+    p.n = n;
+    p.gshift = 1;
+    while (((u64)1 << p.gshift) < n) p.gshift++;
+    p.chunk = (n + 511) / 512 < 1024 ? 1024 : (n + 511) / 512;
+    msm_set_lanes(p, max_lanes0);
+    return p;
+}
+
+// a query runs over its non-infinity bases only when it is long enough and sparse enough (thr: kept fraction below which)
+inline bool msm_compact_rule(size_t nq, size_t kept, double thr) { return nq >= 4096 && (double)kept < thr * (double)nq; }
+
+// rank[i] = position of i in idx (distinct indices below n_rank), MSM_RANK_NONE for every other i: the inverse of idx
+inline void msm_rank_table(const u32* idx, size_t n_idx, u32* rank, size_t n_rank) {
+    for (size_t i = 0; i < n_rank; i++) rank[i] = MSM_RANK_NONE;
+    for (size_t k = 0; k < n_idx; k++) rank[idx[k]] = (u32)k;
 }
 
 }  // namespace hk

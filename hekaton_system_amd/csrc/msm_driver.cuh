@@ -22,11 +22,23 @@ struct SortBufs {        // device buffers produced by the counting sort
     u32* cursor;         // [NB]
     u32* sorted;         // [n * W]    entry ids grouped by bucket
     short* digits;       // [W][n]     signed window digits, written once by k_msm_hist
+    // a sub-list (MsmSort::sublist) has start and sorted only, and instead of count, cursor and digits the scratch of its
+    // derivation, per tile of the SOURCE list (msm_sub_tiles of them per proof):
+    u64* mask = nullptr;           // [tiles][MSM_SUB_WORDS]  keep bits
+    u32* tcount = nullptr;         // [tiles]    kept entries per tile
+    u32* toff = nullptr;           // [tiles]    their exclusive scan over all proofs
+    u32* tops = nullptr;           // scan_u32's scratch
 };
 
 template <class Fr>
 struct MsmSort {
     static void alloc(Carve& c, const MsmPlan& p, SortBufs* out, u32 batch = 1);
+    // a sub-list of plan p (msm_sub_plan) derived from a list sorted under plan src
+    static void alloc_sub(Carve& c, const MsmPlan& src, const MsmPlan& p, SortBufs* out, u32 batch = 1);
+    // sb_dst = the entries of sb_src whose scalar index i has rank[i] != MSM_RANK_NONE (rank: src.n u32 on the device),
+    // renumbered to rank[i] under plan dst, in the same order; on stream s, behind the sort that fills sb_src
+    static hk_status sublist(hipStream_t s, const MsmPlan& src, const SortBufs& sb_src, const MsmPlan& dst, const u32* rank,
+                             const SortBufs& sb_dst, u32 batch = 1);
     // scalars_d: n field elements on the device (canonical, or Montgomery when is_mont); proof b's start scalar_stride
     // elements after proof b - 1's.
     // count_is_zero: the caller cleared sb.count in a kernel of its own that precedes this call in stream order

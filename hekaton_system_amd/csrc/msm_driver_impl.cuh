@@ -4,6 +4,7 @@
 #include "msm_driver.cuh"
 #include "fixed_base.cuh"
 #include "endo.cuh"
+#include "scan.cuh"
 
 namespace hk {
 
@@ -28,9 +29,46 @@ void MsmSort<Fr>::alloc(Carve& c, const MsmPlan& p, SortBufs* out, u32 batch) {
 }
 
 template <class Fr>
+void MsmSort<Fr>::alloc_sub(Carve& c, const MsmPlan& src, const MsmPlan& p, SortBufs* out, u32 batch) {
+    const size_t tiles = (size_t)msm_sub_tiles(src) * batch;
+    out->count = nullptr;
+    out->cursor = nullptr;
+    out->digits = nullptr;
+    out->start = c.n<u32>((size_t)(p.NB + 1) * batch);
+    out->sorted = c.n<u32>(msm_sorted_stride(p) * batch);
+    out->mask = c.n<u64>(tiles * MSM_SUB_WORDS);
+    out->tcount = c.n<u32>(tiles);
+    out->toff = c.n<u32>(tiles);
+    out->tops = c.n<u32>(scan_u32_tops_len(tiles));
+}
+
+template <class Fr>
+hk_status MsmSort<Fr>::sublist(hipStream_t s, const MsmPlan& src, const SortBufs& sb_src, const MsmPlan& dst, const u32* rank,
+                               const SortBufs& sb_dst, u32 batch) {
+    if (batch == 0 || batch > 65535u) return HK_ERR_ARG;
+    // the sub-list reuses the source's digits: same windows, same buckets; and it is no longer than the source
+    if (dst.c != src.c || dst.W != src.W || dst.WP != src.WP || dst.NB != src.NB || dst.n > src.n) return HK_ERR_ARG;
+    const u32 tiles = msm_sub_tiles(src);
+    if ((u64)tiles * batch > 0xffffffffull) return HK_ERR_ARG;
+    const dim3 gt((tiles + MSM_SUB_THREADS / 64 - 1) / (MSM_SUB_THREADS / 64), batch);
+    hipLaunchKernelGGL((k_msm_sub_mark<0>), gt, dim3(MSM_SUB_THREADS), 0, s, (const u32*)sb_src.sorted,
+                       (const u32*)sb_src.start, src, rank, sb_dst.mask, sb_dst.tcount);
+    HK_DBG(s, "k_msm_sub_mark");
+    HK_TRY(scan_u32(s, sb_dst.tcount, sb_dst.toff, sb_dst.tops, tiles * batch));
+    hipLaunchKernelGGL((k_msm_sub_emit<0>), gt, dim3(MSM_SUB_THREADS), 0, s, (const u32*)sb_src.sorted, src, rank,
+                       (const u64*)sb_dst.mask, (const u32*)sb_dst.toff, dst, sb_dst.sorted);
+    HK_DBG(s, "k_msm_sub_emit");
+    hipLaunchKernelGGL((k_msm_sub_starts<0>), dim3((src.NB + 1 + 255) / 256, batch), dim3(256), 0, s,
+                       (const u32*)sb_src.start, src, (const u64*)sb_dst.mask, (const u32*)sb_dst.toff, sb_dst.start);
+    HK_DBG(s, "k_msm_sub_starts");
+    HK_HIP(hipGetLastError());
+    return HK_OK;
+}
+
+template <class Fr>
 hk_status MsmSort<Fr>::run(hipStream_t s, const MsmPlan& p, const u32* scalars_d, int is_mont,
                            const SortBufs& sb, bool count_is_zero, u32 batch, size_t scalar_stride) {
-    if (p.NB > (u32)MSM_LDS_COUNTERS || p.c > 16) return HK_ERR_ARG;       // digits are stored as int16
+    if (p.NB > (u32)MSM_LDS_COUNTERS || p.c < 3 || p.c > 16) return HK_ERR_ARG;       // digits are stored as int16
     if (batch == 0 || batch > 65535u) return HK_ERR_ARG;
     if (!count_is_zero) HK_HIP(hipMemsetAsync(sb.count, 0, sizeof(u32) * p.NB * batch, s));
     u32 blocks = (p.n + p.chunk - 1) / p.chunk;

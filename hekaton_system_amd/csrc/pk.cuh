@@ -1,4 +1,4 @@
-// pk.cuh — the device-resident proving key: its tables (shift tables of every query, the compacted B queries, the
+// pk.cuh — the device-resident proving key: its tables (shift tables of every query, the compacted A and B queries, the
 // bit-reversed h query, the matrices) and the one-time work that builds them.  Defines Ops<C>::pk_upload (hk_pk_upload) and
 // Ops<C>::pk_free (hk_pk_free).
 #pragma once
@@ -14,18 +14,20 @@ struct PkImpl {
     typedef typename C::Fq Fq;
     typedef typename C::Fq2 Fq2;
     u32 n_v = 0, n_inst = 0, n_c = 0, n_stages = 0, n_ext = 0, n_extra = 0;
-    MsmPlan plan_z;                        // shared by the A / B1 / B2 / L queries (same scalar vector)
+    MsmPlan plan_z;                        // the one digit sort of the assignment: A / B1 / B2 / L read its list
     Affine<Fq>* a_tab = nullptr;           // [F][n_ext]   a_g[1..] | delta_g | inf ...
     Affine<Fq>* b1_tab = nullptr;          // [F][n_ext]   b_g[1..] | inf | delta_g | inf ...
     Affine<Fq2>* b2_tab = nullptr;         // [F][n_ext]   b_h[1..] | inf | delta_h | inf ...
-    // B-query density (bellman's DensityTracker idea): b_g[i] and b_h[i] are infinity for every variable that
-    // never occurs in B.  When enough of them are, B1 and B2 run over the compacted list b_idx (ext indices of
-    // the non-infinity bases, then every ext slot) with their own digit sort; b1_tab / b2_tab then hold
-    // [F][b_n] entries and plan_b replaces plan_z for them.
-    bool b_compact = false;
-    u32 b_n = 0;
-    u32* b_idx = nullptr;
-    MsmPlan plan_b;
+    // Query density (bellman's DensityTracker idea): a_g[i] is infinity for every variable that never occurs in A, b_g[i]
+    // and b_h[i] for every one that never occurs in B.  When enough of a query's bases are (msm_compact_rule), it runs over
+    // a compacted index list (ext indices of the non-infinity bases, then every ext slot): its tables then hold
+    // [F][a_n] / [F][b_n] entries, plan_a / plan_b (msm_sub_plan of plan_z: same windows, same buckets) replaces plan_z
+    // for it, and its entry list is the sub-list of z's sorted list that a_rank / b_rank - the inverse of the index list
+    // over the n_ext scalars - selects (MsmSort::sublist).  A query that does not meet the rule reads z's list as it is.
+    bool a_compact = false, b_compact = false;
+    u32 a_n = 0, b_n = 0;
+    u32 *a_rank = nullptr, *b_rank = nullptr;
+    MsmPlan plan_a, plan_b;
     Affine<Fq>* l_tab = nullptr;           // [F][l_n]     ck_last | inf | inf | -delta_g | -delta_i ...
     u32 l_n = 0, l_off = 0;
     bool has_qap = false;
@@ -141,68 +143,87 @@ hk_status Ops<C>::pk_upload(hk_ctx* ctx, const hk_pk_desc* d, hk_pk** out) {
     const char* deltas = (const char*)d->deltas_g;
     const char* delta_last_g = deltas + g1 * k;
     u32 shift = pz.c * pz.WP;
-    if ((st = pk_alloc_table(pk->owned, pk->bytes, pz.F, pk->n_ext, &pk->a_tab)) != HK_OK) return fail(st);
-    PK_HIP(hipMemset(pk->a_tab, 0, g1 * pk->n_ext));
-    if (nq) PK_HIP(hipMemcpy(pk->a_tab, a_g + g1, g1 * nq, h2d_kind(a_g)));
-    PK_HIP(hipMemcpy(pk->a_tab + nq + 0, delta_last_g, g1, h2d_kind(deltas)));          // r * delta_g
-    PK_TRY(MsmRun<Fq>::build_tables(s0, pk->a_tab, pk->n_ext, pz.F, shift));
     {
-        // B-query: full-size staging copies on the device, then either used as the tables' first group
-        // or compacted to the non-infinity bases
-        Affine<Fq>* sb1 = nullptr; Affine<Fq2>* sb2 = nullptr; u32* flags = nullptr;
+        // A and B queries: full-size staging copies on the device, then either used as the tables' first group or
+        // compacted to the non-infinity bases
+        Affine<Fq>*sa = nullptr, *sb1 = nullptr; Affine<Fq2>* sb2 = nullptr; u32* flags = nullptr;
         std::vector<void*> tmp;
         auto cleanup = [&]() { for (void* q : tmp) (void)hipFree(q); tmp.clear(); };
         auto tfail = [&](hk_status e) { cleanup(); return fail(e); };
         auto talloc = [&](void** q, size_t b) { if (hipMalloc(q, b ? b : 16) != hipSuccess) { (void)hipGetLastError(); return false; } tmp.push_back(*q); return true; };
-        if (!talloc((void**)&sb1, g1 * (nq + 1)) || !talloc((void**)&sb2, g2 * (nq + 1)) || !talloc((void**)&flags, 4 * (nq + 1)))
+        if (!talloc((void**)&sa, g1 * (nq + 1)) || !talloc((void**)&sb1, g1 * (nq + 1)) || !talloc((void**)&sb2, g2 * (nq + 1)) ||
+            !talloc((void**)&flags, 4 * (nq + 1)))
             return tfail(HK_ERR_NOMEM);
-        std::vector<u32> idx;
         if (nq) {
+            if (hipMemcpy(sa, a_g + g1, g1 * nq, h2d_kind(a_g)) != hipSuccess) return tfail(HK_ERR_DEVICE);
             if (hipMemcpy(sb1, b_g + g1, g1 * nq, h2d_kind(b_g)) != hipSuccess) return tfail(HK_ERR_DEVICE);
             if (hipMemcpy(sb2, b_h + g2, g2 * nq, h2d_kind(b_h)) != hipSuccess) return tfail(HK_ERR_DEVICE);
-            hipLaunchKernelGGL((k_mark_noninf<Fq>), dim3((u32)((nq + 255) / 256)), dim3(256), 0, s0, sb1, flags, (u32)nq);
-            std::vector<u32> hf(nq);
-            if (hipMemcpy(hf.data(), flags, 4 * nq, hipMemcpyDeviceToHost) != hipSuccess) return tfail(HK_ERR_DEVICE);
-            for (size_t i = 0; i < nq; i++) if (hf[i]) idx.push_back((u32)i);
         }
         static const char* dens_env = getenv("HK_B_COMPACT_BELOW");     // density threshold in percent; 0 disables
         double thr = dens_env ? atof(dens_env) / 100.0 : 0.75;
-        pk->b_compact = nq >= 4096 && (double)idx.size() < thr * (double)nq;
-        if (pk->b_compact) {
+        // one query's selection from its staged G1 bases: compact or not, its length and plan, the index list (device,
+        // transient: the table gathers read it) and the rank table (device, kept with the key)
+        auto select = [&](const Affine<Fq>* staged, bool* compact, u32* n_out, MsmPlan* plan, u32** idx_d, u32** rank_d) -> hk_status {
+            std::vector<u32> idx;
+            if (nq) {
+                hipLaunchKernelGGL((k_mark_noninf<Fq>), dim3((u32)((nq + 255) / 256)), dim3(256), 0, s0, staged, flags, (u32)nq);
+                std::vector<u32> hf(nq);
+                if (hipMemcpy(hf.data(), flags, 4 * nq, hipMemcpyDeviceToHost) != hipSuccess) return HK_ERR_DEVICE;
+                for (size_t i = 0; i < nq; i++) if (hf[i]) idx.push_back((u32)i);
+            }
+            *compact = msm_compact_rule(nq, idx.size(), thr);
+            *idx_d = *rank_d = nullptr;
+            if (!*compact) {
+                *n_out = pk->n_ext;
+                *plan = pz;
+                return HK_OK;
+            }
             for (u32 e = 0; e < pk->n_extra; e++) idx.push_back((u32)nq + e);
-            pk->b_n = (u32)idx.size();
-            pk->plan_b = make_plan(pk->b_n);
-            void* di = nullptr;
-            if (hipMalloc(&di, 4 * (size_t)pk->b_n) != hipSuccess) { (void)hipGetLastError(); return tfail(HK_ERR_NOMEM); }
-            pk->owned.push_back(di);
-            pk->b_idx = (u32*)di;
-            pk->bytes += 4 * (size_t)pk->b_n;
-            if (hipMemcpy(di, idx.data(), 4 * (size_t)pk->b_n, hipMemcpyHostToDevice) != hipSuccess) return tfail(HK_ERR_DEVICE);
-        } else {
-            pk->b_n = pk->n_ext;
-            pk->plan_b = pz;
-        }
-        const MsmPlan& pb = pk->plan_b;
-        if ((st = pk_alloc_table(pk->owned, pk->bytes, pb.F, pk->b_n, &pk->b1_tab)) != HK_OK) return tfail(st);
-        if ((st = pk_alloc_table(pk->owned, pk->bytes, pb.F, pk->b_n, &pk->b2_tab)) != HK_OK) return tfail(st);
-        if (hipMemset(pk->b1_tab, 0, g1 * pk->b_n) != hipSuccess || hipMemset(pk->b2_tab, 0, g2 * pk->b_n) != hipSuccess)
+            *n_out = (u32)idx.size();
+            *plan = msm_sub_plan(pz, *n_out, ctx->max_lanes0);
+            std::vector<u32> rank(pk->n_ext);
+            msm_rank_table(idx.data(), idx.size(), rank.data(), rank.size());
+            if (!talloc((void**)idx_d, 4 * idx.size())) return HK_ERR_NOMEM;
+            void* dr = nullptr;
+            if (hipMalloc(&dr, 4 * rank.size()) != hipSuccess) { (void)hipGetLastError(); return HK_ERR_NOMEM; }
+            pk->owned.push_back(dr);
+            pk->bytes += 4 * rank.size();
+            *rank_d = (u32*)dr;
+            if (hipMemcpy(*idx_d, idx.data(), 4 * idx.size(), hipMemcpyHostToDevice) != hipSuccess) return HK_ERR_DEVICE;
+            if (hipMemcpy(dr, rank.data(), 4 * rank.size(), hipMemcpyHostToDevice) != hipSuccess) return HK_ERR_DEVICE;
+            return HK_OK;
+        };
+        u32 *a_idx = nullptr, *b_idx = nullptr;
+        if ((st = select(sa, &pk->a_compact, &pk->a_n, &pk->plan_a, &a_idx, &pk->a_rank)) != HK_OK) return tfail(st);
+        if ((st = select(sb1, &pk->b_compact, &pk->b_n, &pk->plan_b, &b_idx, &pk->b_rank)) != HK_OK) return tfail(st);
+        if ((st = pk_alloc_table(pk->owned, pk->bytes, pz.F, pk->a_n, &pk->a_tab)) != HK_OK) return tfail(st);
+        if ((st = pk_alloc_table(pk->owned, pk->bytes, pz.F, pk->b_n, &pk->b1_tab)) != HK_OK) return tfail(st);
+        if ((st = pk_alloc_table(pk->owned, pk->bytes, pz.F, pk->b_n, &pk->b2_tab)) != HK_OK) return tfail(st);
+        if (hipMemset(pk->a_tab, 0, g1 * pk->a_n) != hipSuccess || hipMemset(pk->b1_tab, 0, g1 * pk->b_n) != hipSuccess ||
+            hipMemset(pk->b2_tab, 0, g2 * pk->b_n) != hipSuccess)
             return tfail(HK_ERR_DEVICE);
+        if (pk->a_compact) {
+            hipLaunchKernelGGL((k_gather<Affine<Fq>>), dim3((pk->a_n + 255) / 256), dim3(256), 0, s0, pk->a_tab, (const Affine<Fq>*)sa, (const u32*)a_idx, pk->a_n, (u32)nq);
+        } else if (nq) {
+            if (hipMemcpy(pk->a_tab, sa, g1 * nq, hipMemcpyDeviceToDevice) != hipSuccess) return tfail(HK_ERR_DEVICE);
+        }
         if (pk->b_compact) {
             u32 blocks = (pk->b_n + 255) / 256;
-            hipLaunchKernelGGL((k_gather<Affine<Fq>>), dim3(blocks), dim3(256), 0, s0, pk->b1_tab, (const Affine<Fq>*)sb1, pk->b_idx, pk->b_n, (u32)nq);
-            hipLaunchKernelGGL((k_gather<Affine<Fq2>>), dim3(blocks), dim3(256), 0, s0, pk->b2_tab, (const Affine<Fq2>*)sb2, pk->b_idx, pk->b_n, (u32)nq);
+            hipLaunchKernelGGL((k_gather<Affine<Fq>>), dim3(blocks), dim3(256), 0, s0, pk->b1_tab, (const Affine<Fq>*)sb1, (const u32*)b_idx, pk->b_n, (u32)nq);
+            hipLaunchKernelGGL((k_gather<Affine<Fq2>>), dim3(blocks), dim3(256), 0, s0, pk->b2_tab, (const Affine<Fq2>*)sb2, (const u32*)b_idx, pk->b_n, (u32)nq);
         } else if (nq) {
             if (hipMemcpy(pk->b1_tab, sb1, g1 * nq, hipMemcpyDeviceToDevice) != hipSuccess) return tfail(HK_ERR_DEVICE);
             if (hipMemcpy(pk->b2_tab, sb2, g2 * nq, hipMemcpyDeviceToDevice) != hipSuccess) return tfail(HK_ERR_DEVICE);
         }
-        u32 s_slot = pk->b_n - pk->n_extra + 1;                                              // ext slot of s
+        u32 r_slot = pk->a_n - pk->n_extra + 0, s_slot = pk->b_n - pk->n_extra + 1;              // ext slots of r (in A), s (in B)
+        if (hipMemcpy(pk->a_tab + r_slot, delta_last_g, g1, h2d_kind(deltas)) != hipSuccess) return tfail(HK_ERR_DEVICE);      // r * delta_g
         if (hipMemcpy(pk->b1_tab + s_slot, delta_last_g, g1, h2d_kind(deltas)) != hipSuccess) return tfail(HK_ERR_DEVICE);     // s * delta_g
         if (hipMemcpy(pk->b2_tab + s_slot, d->last_delta_h, g2, h2d_kind(d->last_delta_h)) != hipSuccess) return tfail(HK_ERR_DEVICE);   // s * delta_h
         if (hipDeviceSynchronize() != hipSuccess) return tfail(HK_ERR_DEVICE);
         cleanup();
-        u32 shift_b = pb.c * pb.WP;
-        PK_TRY(MsmRun<Fq>::build_tables(s0, pk->b1_tab, pk->b_n, pb.F, shift_b));
-        PK_TRY(MsmRun<Fq2>::build_tables(s0, pk->b2_tab, pk->b_n, pb.F, shift_b));
+        PK_TRY(MsmRun<Fq>::build_tables(s0, pk->a_tab, pk->a_n, pz.F, shift));
+        PK_TRY(MsmRun<Fq>::build_tables(s0, pk->b1_tab, pk->b_n, pz.F, shift));
+        PK_TRY(MsmRun<Fq2>::build_tables(s0, pk->b2_tab, pk->b_n, pz.F, shift));
     }
     // --- L table: last-stage committer key, then the negated deltas that fold -rs*delta and -kappa_i*delta_i
     size_t n1 = d->ck_len[k];

@@ -19,17 +19,15 @@ namespace hk {
 // ---- small device helpers for the fused calls -------------------------------------------------------------
 // ext[0] = r, ext[1] = s, ext[2] = r*s, ext[3+i] = kappa_i   (all Montgomery), for each of `batch` proofs: row b of ext
 // starts ext_stride elements after row b - 1, row b of rs_kappas (r, s, kappas) rs_stride after.
-// Also clears the bucket counters of the proofs' digit sorts (up to three arrays of `nb` u32 each, every proof's counters;
-// every workgroup takes a share): they are accumulated with atomics by k_msm_hist, and this kernel precedes every sort of
-// the proofs in stream order (the side streams wait for the event recorded behind it) - three memset launches less.
+// Also clears the bucket counters of the proofs' two digit sorts, z's and h's (arrays of `nb` u32 each, every proof's
+// counters; every workgroup takes a share): they are accumulated with atomics by k_msm_hist, and this kernel precedes both
+// sorts in stream order (the H stream waits for the event recorded behind it) - two memset launches less.
 template <class Fr>
 __global__ void k_prep_ext(Fr* __restrict__ ext, u32 ext_stride, const Fr* __restrict__ rs_kappas, u32 rs_stride,
-                           u32 n_kappas, u32 batch, u32* __restrict__ c0, u32* __restrict__ c1, u32* __restrict__ c2,
-                           u32 nb0, u32 nb1, u32 nb2) {
+                           u32 n_kappas, u32 batch, u32* __restrict__ c0, u32* __restrict__ c1, u32 nb0, u32 nb1) {
     u32 gt = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
     for (u32 i = gt; i < nb0; i += stride) c0[i] = 0;
     for (u32 i = gt; i < nb1; i += stride) c1[i] = 0;
-    for (u32 i = gt; i < nb2; i += stride) c2[i] = 0;
     if (gt >= batch) return;
     Fr* e = ext + (size_t)gt * ext_stride;
     const Fr* rk = rs_kappas + (size_t)gt * rs_stride;
@@ -262,7 +260,7 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
     if (!L) return HK_ERR_DEVICE;
     NttTables* T;
     HK_TRY(NttHost<C>::ensure(ctx, pk->log_m, &T));
-    const MsmPlan &pz = pk->plan_z, &ph = pk->plan_h, &pb = pk->plan_b;
+    const MsmPlan &pz = pk->plan_z, &ph = pk->plan_h, &pa = pk->plan_a, &pb = pk->plan_b;
     const size_t m = (size_t)1 << pk->log_m, fr = sizeof(Fr), rs_stride = 2 + n_kappas;
     std::vector<char> z_dev(batch);
     bool any_host = false;
@@ -272,8 +270,8 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
     }
     // the scratch of one chunk of `nb` proofs: every per-proof buffer times nb, the bucket pipelines sized by the lane plan
     // of the chunk (the chip's lanes split across it, so the boundary partials do not grow with nb)
-    Fr *zext, *small, *zt, *zb, *abc;
-    SortBufs sb, sbh, sbb;
+    Fr *zext, *small, *zt, *abc;
+    SortBufs sb, sbh, sba, sbb;                                               // z, h; the sub-lists of z for A and for B
     typename MsmRun<Fq>::Bufs rbA, rbB1, rbL, rbh;
     typename MsmRun<Fq2>::Bufs rb2;
     XYZZ<Fq>* res1;
@@ -287,13 +285,9 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
         zt = any_host ? c.n<Fr>(n_v * nb) : nullptr;                          // host rows of z, copied in (slot = row)
         MsmSort<Fr>::alloc(c, pz, &sb, nb);
         MsmSort<Fr>::alloc(c, ph, &sbh, nb);
-        sbb.count = nullptr;
-        zb = nullptr;
-        if (pk->b_compact) {
-            MsmSort<Fr>::alloc(c, pb, &sbb, nb);
-            zb = c.n<Fr>((size_t)pk->b_n * nb);
-        }
-        MsmRun<Fq>::alloc(c, pz, &rbA, nb);
+        if (pk->a_compact) MsmSort<Fr>::alloc_sub(c, pz, pa, &sba, nb);
+        if (pk->b_compact) MsmSort<Fr>::alloc_sub(c, pz, pb, &sbb, nb);
+        MsmRun<Fq>::alloc(c, pa, &rbA, nb);
         MsmRun<Fq>::alloc(c, pb, &rbB1, nb);
         MsmRun<Fq>::alloc(c, pz, &rbL, nb);
         MsmRun<Fq>::alloc(c, ph, &rbh, nb);
@@ -360,10 +354,10 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
                 HK_HIP(hipMemcpyAsync(zext + (size_t)j * pk->n_ext, zd[j] + 1, (n_v - 1) * fr, hipMemcpyDeviceToDevice, s));
         }
         HK_HIP(hipMemcpyAsync(small, rsk.data() + b0 * rs_stride * fr, nb * rs_stride * fr, hipMemcpyHostToDevice, s));
-        // --- one digit sort per proof shared by the four assignment-indexed queries
+        // --- one digit sort per proof for the four assignment-indexed queries: L reads its list as it is, A and B too, or -
+        // when they run over their non-infinity bases only - the sub-list of it that their rank table selects
         hipLaunchKernelGGL((k_prep_ext<Fr>), dim3(64), dim3(256), 0, s, zext + (n_v - 1), pk->n_ext, (const Fr*)small,
-                           (u32)rs_stride, (u32)n_kappas, nb, sb.count, sbh.count, sbb.count, pz.NB * nb, ph.NB * nb,
-                           pk->b_compact ? pb.NB * nb : 0u);
+                           (u32)rs_stride, (u32)n_kappas, nb, sb.count, sbh.count, pz.NB * nb, ph.NB * nb);
         // Fork: the five queries are independent once their scalars exist.  Streams let the latency-bound tails
         // (segmented levels, bucket reduction) of one query hide under the throughput-bound accumulation of another;
         // every launch covers the whole chunk.
@@ -393,18 +387,15 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
         HK_HIP(hipEventRecord(ev_sorted, s));
         if (prof) HK_HIP(hipEventRecord(ev[1], s));                            // digits done
         HK_TRY(wait(sL, ev_sorted, s));
-        const SortBufs* sbB = &sb;
+        const SortBufs *sbA = &sb, *sbB = &sb;
+        HK_TRY(wait(sB1, ev_sorted, s));
         if (pk->b_compact) {
-            // B1 / B2 over the non-infinity bases only: gather their scalars, sort those digits on B1's stream
-            HK_TRY(wait(sB1, ev_z, s));
-            hipLaunchKernelGGL((k_gather<Fr>), dim3((pk->b_n + 255) / 256, nb), dim3(256), 0, sB1, zb, (const Fr*)zext,
-                               (const u32*)pk->b_idx, pk->b_n, pk->n_ext);
-            HK_TRY(MsmSort<Fr>::run(sB1, pb, (const u32*)zb, 1, sbb, true, nb, pk->b_n));
+            // B1 / B2 over the non-infinity bases only: their entries of z's list, derived on B1's stream
+            HK_TRY(MsmSort<Fr>::sublist(sB1, pz, sb, pb, pk->b_rank, sbb, nb));
             HK_HIP(hipEventRecord(ev[28], sB1));
             HK_TRY(wait(sB2, ev[28], sB1));
             sbB = &sbb;
         } else {
-            HK_TRY(wait(sB1, ev_sorted, s));
             HK_TRY(wait(sB2, ev_sorted, s));
         }
         HK_TRY(MsmRun<Fq2>::run(sB2, pb, pk->b2_tab, pk->b_n, 0, *sbB, rb2, res2, nullptr, nullptr, nb, 1));
@@ -415,7 +406,12 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
         HK_TRY(MsmRun<Fq>::run(sL, pz, pk->l_tab, pk->l_n, pk->l_off, sb, rbL, res1 + 2, prof ? ev[24] : nullptr,
                                prof ? ev[25] : nullptr, nb, 4));
         HK_HIP(hipEventRecord(ev[18], sL));                                    // L done
-        HK_TRY(MsmRun<Fq>::run(s, pz, pk->a_tab, pk->n_ext, 0, sb, rbA, res1 + 0, prof ? ev[26] : nullptr,
+        if (pk->a_compact) {
+            // A likewise, on main: a base at infinity no longer takes a lane of the wave through the mixed add
+            HK_TRY(MsmSort<Fr>::sublist(s, pz, sb, pa, pk->a_rank, sba, nb));
+            sbA = &sba;
+        }
+        HK_TRY(MsmRun<Fq>::run(s, pa, pk->a_tab, pk->a_n, 0, *sbA, rbA, res1 + 0, prof ? ev[26] : nullptr,
                                prof ? ev[27] : nullptr, nb, 4));
         if (prof) HK_HIP(hipEventRecord(ev[2], s));                            // A done
         // Join the queries: A, B, and C without MH need nothing of H, so they no longer wait for it
@@ -448,10 +444,9 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
             // copies, from the moment H and k_finish_ab are both done.
             acc.digits_ms += ev_ms(ev_start, ev[1]);
             acc.msm_a_ms += ev_ms(ev[1], ev[2]);
-            // a compact B forks from z (its own gather and sort on B1's stream), not from the shared sort: it may finish before ev[1]
-            hipEvent_t fork_b = pk->b_compact ? ev_z : ev[1];
-            acc.msm_b_g1_ms += ev_ms(fork_b, ev[3]);
-            acc.msm_b_g2_ms += ev_ms(fork_b, ev[4]);
+            // every query forks from the shared sort (ev[1]), a compact one with its sub-list first: no figure is negative
+            acc.msm_b_g1_ms += ev_ms(ev[1], ev[3]);
+            acc.msm_b_g2_ms += ev_ms(ev[1], ev[4]);
             acc.msm_l_ms += ev_ms(ev[1], ev[18]);
             acc.witness_map_ms += ev_ms(ev[5], ev[6]);
             acc.msm_h_ms += ev_ms(ev[6], ev[7]);
