@@ -93,6 +93,33 @@ def synthetic_r1cs(cp, rnd, n_inst, n_free, n_c, two_stage_split=None, nnz=(3, 2
     return cs
 
 
+def with_assignment(cs, z):
+    """A shallow copy of the finalized R1CS `cs` that holds the assignment z (z[0] included) instead of its own: the
+    oracle's prover and committer read the assignment from the constraint system."""
+    import copy
+    assert len(z) == cs.num_instance + cs.num_witness
+    out = copy.copy(cs)
+    out.instance = [x % cs.r for x in z[:cs.num_instance]]
+    out.witness = [x % cs.r for x in z[cs.num_instance:]]
+    return out
+
+
+def oracle_prove(cp, cs, pk, z, kappas, r_, s_):
+    """groth16.prove on the assignment z in place of cs's own, satisfying or not (the prover is a map of z)"""
+    from oracle.pyref import groth16
+    return groth16.prove(cp, with_assignment(cs, z), pk, [], list(kappas), r_, s_)
+
+
+def oracle_commit(cp, cs, pk, stage, w, kappa):
+    """groth16.commit to the stage witness w in place of cs's own"""
+    from oracle.pyref import groth16
+    s0, e0 = cs.stage_ranges[stage]
+    z = cs.full_assignment()
+    assert len(w) == e0 - s0
+    z[cs.num_instance + s0:cs.num_instance + e0] = w
+    return groth16.commit(cp, with_assignment(cs, z), pk, stage, kappa)
+
+
 def pk_upload_from_oracle(ctx, cd, pk, cs):
     """Oracle ProvingKey + finalized R1CS -> hk_pk resident on the device."""
     A, B, C = cs.matrices()
