@@ -6,9 +6,10 @@
 // k_verify_ic (prepared inputs: one lane per proof, one interleaved double-and-add chain over its public inputs),
 // k_verify_tree_lines (first tree level of N independent multi-pairings: the lines of the proofs' B points and the
 // key's PREPARED lines of -gamma / -delta_j, evaluated at the matching G1 points), k_verify_coeffs (the combined inputs
-// of the randomised batch check) and k_verify_verdict.  The rest of the Miller pipeline (k_pair_lines, k_pair_tree,
-// k_pair_horner) and the GT power are the multi-pairing's own (pairing_wave.cuh).  Host orchestration: VerifyRun<P>,
-// explicitly instantiated in hk_<curve>_pair.hip.  DESIGN.md section 4f.
+// of the randomised batch check), k_verify_rand_zero (a zero r_i sends its chunk to the per-proof path) and
+// k_verify_verdict.  The rest of the Miller pipeline (k_pair_lines, k_pair_tree, k_pair_horner) and the GT power are the
+// multi-pairing's own (pairing_wave.cuh).  Host orchestration: VerifyRun<P>, explicitly instantiated in
+// hk_<curve>_pair.hip.  DESIGN.md section 4f.
 #pragma once
 #include "pairing_driver_impl.cuh"
 
@@ -198,6 +199,15 @@ k_verify_coeffs(const Fr* __restrict__ r, const Fr* __restrict__ x, u32 n, u32 n
     coef[k] = Fr::canon(acc);
 }
 
+// zero[0] = 1 when some r_i == 0: its terms drop out of both sides of the batch equation, which would then hold whatever
+// proof i is.  `zero` is the byte after the chunk's point flags, so the host reads both at once.
+template <class Fr>
+__global__ void __launch_bounds__(64)
+k_verify_rand_zero(const Fr* __restrict__ r, u32 n, unsigned char* __restrict__ zero) {
+    u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && ld_vec(&r[i]).is_zero()) *zero = 1;
+}
+
 // verdicts[p] = flags[p] when a point check marked the proof, else got[p] == want[p * want_stride]
 template <class P>
 __global__ void __launch_bounds__(64)
@@ -228,7 +238,8 @@ template <class P>
 size_t VerifyRun<P>::max_private_bytes() {
     typedef typename ScalarOfQ<P>::type Fr;
     const void* ks[] = {(const void*)k_points_check<Fp<P>>, (const void*)k_points_check<Fp2<P>>, (const void*)k_verify_ic<P, Fr>,
-                        (const void*)k_verify_tree_lines<P>, (const void*)k_verify_coeffs<Fr>, (const void*)k_verify_verdict<P>};
+                        (const void*)k_verify_tree_lines<P>, (const void*)k_verify_coeffs<Fr>, (const void*)k_verify_rand_zero<Fr>,
+                        (const void*)k_verify_verdict<P>};
     size_t m = 0;
     for (const void* k : ks) { size_t b = hk_private_bytes_of(k); if (b > m) m = b; }
     return m;
@@ -422,7 +433,7 @@ hk_status VerifyRun<P>::verify_batch(hk_ctx* ctx, const hk_vk* h, const void* a,
         unsigned char* eq = nullptr;
         HK_TRY(L->carve([&](Carve& k) {
             stage_carve(k, io, 7);
-            flag = k.n<unsigned char>(m);
+            flag = k.n<unsigned char>(m + 1);              // one per proof, then "some r_i is zero"
             gst = k.n<Affine<Fq>>((size_t)m * nst);
             lines = k.n<Line6<P>>((size_t)m * S);
             pp0 = k.n<GT>((size_t)m * S * gpp);
@@ -446,7 +457,7 @@ hk_status VerifyRun<P>::verify_batch(hk_ctx* ctx, const hk_vk* h, const void* a,
         const void *ad = io[0].p, *bd = io[1].p, *cd = io[2].p, *dd = io[3].p, *xd = io[4].p, *rd = io[5].p;
         unsigned char* vd = (unsigned char*)io[6].p;
         HK_TRY(stage_upload(L, io, 6));
-        HK_HIP(hipMemsetAsync(flag, 0, m, s));
+        HK_HIP(hipMemsetAsync(flag, 0, m + 1, s));
         bool any_bad = false;
         if (check) {
             hipLaunchKernelGGL((k_points_check<Fq>), dim3((m + 63) / 64), dim3(64), 0, s, (const Affine<Fq>*)ad, m, 1u, flag);
@@ -461,11 +472,14 @@ hk_status VerifyRun<P>::verify_batch(hk_ctx* ctx, const hk_vk* h, const void* a,
         HK_TRY(verify_lines<P>(s, (const Affine<Fq2>*)bd, m, lines));
         bool batch_ok = false;
         if (rand) {
-            // one randomised equation for the chunk; a proof with a bad point sends the chunk to the per-proof path
-            std::vector<unsigned char> fh(m);
-            HK_HIP(hipMemcpyAsync(fh.data(), flag, m, hipMemcpyDeviceToHost, s));
+            // one randomised equation for the chunk; a proof with a bad point, or a zero r_i, sends the chunk to the
+            // per-proof path
+            hipLaunchKernelGGL((k_verify_rand_zero<Fr>), dim3((m + 63) / 64), dim3(64), 0, s, (const Fr*)rd, m, flag + m);
+            HK_HIP(hipGetLastError());
+            std::vector<unsigned char> fh(m + 1);
+            HK_HIP(hipMemcpyAsync(fh.data(), flag, m + 1, hipMemcpyDeviceToHost, s));
             HK_HIP(hipStreamSynchronize(s));
-            for (u32 i = 0; i < m; i++) any_bad = any_bad || fh[i];
+            for (u32 i = 0; i <= m; i++) any_bad = any_bad || fh[i];
         }
         if (rand && !any_bad) {
             // sum r_i, sum r_i x_i -> sum r_i IC_i = (sum r_i) abc[0] + sum_k (sum_i r_i x_ik) abc[k + 1]

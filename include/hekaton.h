@@ -429,7 +429,9 @@ hk_status hk_vk_alpha_beta(const hk_vk* vk, void* gt_out);
  * batch mode: one randomised equation
  *   prod e(r_i A_i, B_i) e(sum r_i IC_i, -gamma) prod_j e(sum r_i D_ij, -delta_j) e(sum r_i C_i, -delta_last)
  *     == e(alpha, beta)^(sum r_i)
- * per chunk of proofs; all verdicts are 1 when it holds, else that chunk is verified per proof.  Batch mode requires
+ * per chunk of proofs; all verdicts are 1 when it holds, else that chunk is verified per proof.  An r_i == 0 would drop
+ * proof i from both sides, so a chunk that holds one is verified per proof as well (the entry looks; no verdict becomes 2).
+ * The r_i must be drawn after the proofs are fixed: a prover who knows them can make wrong proofs cancel.  Batch mode requires
  * HK_VERIFY_CHECK_POINTS (HK_ERR_ARG otherwise).  A pair with a member at infinity contributes 1; infinity passes the
  * point check.  Returns HK_OK whatever the verdicts; n == 0 does nothing. */
 hk_status hk_verify_batch(hk_ctx* ctx, const hk_vk* vk, const void* a_g1, const void* b_g2, const void* c_g1,
