@@ -2,8 +2,11 @@
 tests/test_field_device_gpu.py and tests/test_wave_f12_gpu.py), tests/device_shim/ec_dev_shim.hip (of
 tests/test_ec_device_gpu.py and tests/test_msm_plan_device_gpu.py), tests/device_shim/pair_dev_shim.hip (of
 tests/test_pair_device_gpu.py), tests/device_shim/ntt_dev_shim.hip (of tests/test_ntt_device_gpu.py and
-tests/test_scan_gpu.py) and tests/device_shim/sweep_dev_shim.hip (of tests/test_sweep_device_gpu.py).  The shims run in the
-calling process."""
+tests/test_scan_gpu.py), tests/device_shim/sweep_dev_shim.hip (of tests/test_sweep_device_gpu.py) and
+tests/device_shim/sublist_dev_shim.hip (of tests/test_msm_sublist_gpu.py).  The shims run in the calling process.
+
+A shim is one class: LIBS (variant -> library file), SIGS (the argtypes of its entry points, with a restype where it is not
+int) and USES_ASM (the entry point that tells the variant, where there is one), on the loader of Shim."""
 import ctypes
 import os
 
@@ -36,7 +39,7 @@ FORM_LANE, FORM_QUAD = 0, 1
 
 # ntt_dev_shim.hip
 NTT_VARIANTS = {"asm": "libntt_dev_shim.so", "noasm": "libntt_dev_shim_noasm.so"}
-NTT_REFUSED = 1000           # DSHIM_NTT_REFUSED: arguments outside a kernel's contract, nothing launched
+NTT_REFUSED = 1000           # SHIM_REFUSED of shim_common.cuh: arguments outside a kernel's contract, nothing launched
 FR_BYTES = 32
 
 # sweep_dev_shim.hip: built as shipped only (see the header of tests/device_shim/Makefile)
@@ -44,11 +47,12 @@ SWEEP_LIB = "libsweep_dev_shim.so"
 SPLIT_K_LANE, SPLIT_QUAD = 0, 1
 MUL_PLAIN, MUL_ENDO = 0, 1
 
-_loaded = {}
-_loaded_sweep = []
-_loaded_ec = {}
-_loaded_pair = {}
-_loaded_ntt = {}
+# sublist_dev_shim.hip: integer kernels only, one build
+SUBLIST_LIB = "libsublist_dev_shim.so"
+
+_loaded = {}                 # library file name -> its shim object
+
+vp, ui, up, sz, ci = ctypes.c_char_p, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint), ctypes.c_size_t, ctypes.c_int
 
 
 def pack(elems, nbytes):
@@ -65,17 +69,38 @@ def unpack(buf, nbytes, width=1):
     return [tuple(ints[i:i + width]) for i in range(0, len(ints), width)]
 
 
-class DevShim:
-    def __init__(self, variant):
-        path = os.path.join(ROOT, "hekaton_system_amd", "lib", VARIANTS[variant])
+def check(st, what):
+    """every entry point answers 0, minus a hipError_t, or (> 0) a refusal of the shim's or the product's hk_status"""
+    assert st == 0, "%s: %s %d" % (what, "HIP error" if st < 0 else "status", abs(st))
+
+
+class Shim:
+    LIBS, SIGS, USES_ASM = {}, {}, None
+
+    def __init__(self, variant="asm"):
+        path = os.path.join(ROOT, "hekaton_system_amd", "lib", self.LIBS[variant])
         assert os.path.exists(path), "build the device shim first (python __graft_entry__.py)"
         self.variant = variant
         self.lib = ctypes.CDLL(path)
-        self.lib.dshim_field_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
-                                            ctypes.c_size_t, ctypes.c_int, ctypes.c_int]
-        self.lib.dshim_wave_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
-                                           ctypes.c_size_t, ctypes.c_int]
-        assert self.lib.dshim_uses_asm() == (1 if variant == "asm" else 0)
+        for name, sig in self.SIGS.items():
+            fn = getattr(self.lib, name)
+            if isinstance(sig, tuple):
+                sig, fn.restype = sig
+            fn.argtypes = sig
+        if self.USES_ASM:
+            assert getattr(self.lib, self.USES_ASM)() == (1 if variant == "asm" else 0)
+
+    @classmethod
+    def load(cls, variant="asm"):
+        name = cls.LIBS[variant]
+        if name not in _loaded:
+            _loaded[name] = cls(variant)
+        return _loaded[name]
+
+
+class DevShim(Shim):
+    LIBS, USES_ASM = VARIANTS, "dshim_uses_asm"
+    SIGS = {"dshim_field_op": [ci, ci, vp, vp, vp, sz, ci, ci], "dshim_wave_op": [ci, ci, vp, vp, vp, sz, ci]}
 
     def field_op(self, fid, op, nbytes, a, b=None, raw=0, chain=0):
         """a, b: lists of ints (base fields) or of (c0, c1) tuples (Fq2), as raw limbs -> the same shape back"""
@@ -84,7 +109,7 @@ class DevShim:
         bbuf = None if b is None else pack(b, nbytes)
         out = ctypes.create_string_buffer(len(abuf))
         st = self.lib.dshim_field_op(fid, op, abuf, bbuf, out, len(a), raw, chain)
-        assert st == 0, "dshim_field_op(field %d, op %d): HIP error %d" % (fid, op, st)
+        check(st, "dshim_field_op(field %d, op %d)" % (fid, op))
         return unpack(out.raw, nbytes, width)
 
     def wave_op(self, cid, op, nbytes, a, b=None, alias=ALIAS_NONE):
@@ -93,31 +118,23 @@ class DevShim:
         bbuf = None if b is None else pack(b, nbytes)
         out = ctypes.create_string_buffer(len(a) * 13 * nbytes)
         st = self.lib.dshim_wave_op(cid, op, abuf, bbuf, out, len(a), alias)
-        assert st == 0, "dshim_wave_op(curve %d, op %d, alias %d): HIP error %d" % (cid, op, alias, st)
+        check(st, "dshim_wave_op(curve %d, op %d, alias %d)" % (cid, op, alias))
         return unpack(out.raw, nbytes, 13)
 
 
-def load(variant):
-    if variant not in _loaded:
-        _loaded[variant] = DevShim(variant)
-    return _loaded[variant]
+load = DevShim.load
 
 
-class EcShim:
+class EcShim(Shim):
     """Points travel as slots of four coordinate-field elements (x, y, zz, zzz; an affine point fills the first two), each an
     int (G1) or a (c0, c1) tuple (G2) of RAW limbs: Montgomery values, possibly non-canonical representatives."""
 
+    LIBS, USES_ASM = EC_VARIANTS, "dshim_ec_uses_asm"
+    SIGS = {"dshim_group_op": [ci, ci, vp, vp, vp, sz, ci, ui], "dshim_batch_affine": [ci, vp, vp, sz, ui],
+            "dshim_msm": [ci] + [ui] * 6 + [vp, vp, ci, vp, up]}
+
     def __init__(self, variant):
-        path = os.path.join(ROOT, "hekaton_system_amd", "lib", EC_VARIANTS[variant])
-        assert os.path.exists(path), "build the device shim first (python __graft_entry__.py)"
-        self.variant = variant
-        self.lib = ctypes.CDLL(path)
-        self.lib.dshim_group_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
-                                            ctypes.c_size_t, ctypes.c_int, ctypes.c_uint]
-        self.lib.dshim_batch_affine.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint]
-        self.lib.dshim_msm.argtypes = [ctypes.c_int] + [ctypes.c_uint] * 6 + [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int,
-                                                                               ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint)]
-        assert self.lib.dshim_ec_uses_asm() == (1 if variant == "asm" else 0)
+        super().__init__(variant)
         assert self.lib.dshim_ec_has_msm() == (1 if variant == "asm" else 0)
 
     def built(self, gid, op):
@@ -141,7 +158,7 @@ class EcShim:
 
     def group_op(self, gid, op, nbytes, a, b=None, raw=0, k=0):
         st, slots = self.group_op_status(gid, op, nbytes, a, b, raw, k)
-        assert st == 0, "dshim_group_op(group %d, op %d): HIP error %d" % (gid, op, -st)
+        check(st, "dshim_group_op(group %d, op %d)" % (gid, op))
         return slots
 
     def batch_affine(self, gid, nbytes, pts, chunk):
@@ -150,7 +167,7 @@ class EcShim:
         buf = b"".join(pack(list(slot), nbytes) for slot in pts)
         out = ctypes.create_string_buffer(len(buf) // 2)
         st = self.lib.dshim_batch_affine(gid, buf, out, len(pts), chunk)
-        assert st == 0, "dshim_batch_affine(group %d, n %d, chunk %d): HIP error %d" % (gid, len(pts), chunk, -st)
+        check(st, "dshim_batch_affine(group %d, n %d, chunk %d)" % (gid, len(pts), chunk))
         elems = unpack(out.raw, nbytes, width)
         return [tuple(elems[i:i + 2]) for i in range(0, len(elems), 2)]
 
@@ -168,30 +185,18 @@ class EcShim:
         return st, (out.raw if st == 0 else None), list(plan)
 
 
-def load_ec(variant):
-    if variant not in _loaded_ec:
-        _loaded_ec[variant] = EcShim(variant)
-    return _loaded_ec[variant]
+load_ec = EcShim.load
 
 
-class PairShim:
+class PairShim(Shim):
     """The stages of the multi-pairing pipeline.  f2q_op takes and gives integers (raw limbs in, canonical Montgomery values
     out); the pipeline stages take and give the bytes the kernels read and write (Montgomery, little-endian; nb bytes per Fq):
     an affine G1 point is 2 Fq, a G2 point 4, a raw line 6 (c0, c1, c2 in Fq2), an Fq12 value 12."""
 
-    def __init__(self, variant):
-        path = os.path.join(ROOT, "hekaton_system_amd", "lib", PAIR_VARIANTS[variant])
-        assert os.path.exists(path), "build the device shim first (python __graft_entry__.py)"
-        self.variant = variant
-        self.lib = ctypes.CDLL(path)
-        vp, ui, up = ctypes.c_char_p, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint)
-        self.lib.dshim_f2q_op.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_size_t]
-        self.lib.dshim_pair_lines.argtypes = [ctypes.c_int, ctypes.c_int, vp, ui, ui, vp, up]
-        self.lib.dshim_pair_tree_lines.argtypes = [ctypes.c_int, vp, vp, ui, ui, ui, ui, ui, up, up, ui, vp]
-        self.lib.dshim_pair_tree.argtypes = [ctypes.c_int, vp, ui, ui, ui, vp]
-        self.lib.dshim_pair_horner.argtypes = [ctypes.c_int, vp, ui, vp]
-        self.lib.dshim_pair_steps.restype = ctypes.c_uint
-        assert self.lib.dshim_pair_uses_asm() == (1 if variant == "asm" else 0)
+    LIBS, USES_ASM = PAIR_VARIANTS, "dshim_pair_uses_asm"
+    SIGS = {"dshim_f2q_op": [ci, ci, vp, vp, vp, sz], "dshim_pair_lines": [ci, ci, vp, ui, ui, vp, up],
+            "dshim_pair_tree_lines": [ci, vp, vp, ui, ui, ui, ui, ui, up, up, ui, vp], "dshim_pair_tree": [ci, vp, ui, ui, ui, vp],
+            "dshim_pair_horner": [ci, vp, ui, vp], "dshim_pair_steps": ([ci], ui)}
 
     def steps(self, cid):
         return self.lib.dshim_pair_steps(cid)
@@ -204,7 +209,7 @@ class PairShim:
         bbuf = None if b is None else pack(b, nbytes)
         out = ctypes.create_string_buffer(len(a) * 4 * per * 2 * nbytes)
         st = self.lib.dshim_f2q_op(cid, op, abuf, bbuf, out, len(a))
-        assert st == 0, "dshim_f2q_op(curve %d, op %d): HIP error %d" % (cid, op, -st)
+        check(st, "dshim_f2q_op(curve %d, op %d)" % (cid, op))
         f2 = unpack(out.raw, nbytes, 2)
         if per == 2:
             f2 = [tuple(f2[i:i + 2]) for i in range(0, len(f2), 2)]
@@ -217,7 +222,7 @@ class PairShim:
         out = ctypes.create_string_buffer(n_r * S * n * 6 * nb)
         got_S = ctypes.c_uint(0)
         st = self.lib.dshim_pair_lines(cid, form, bytes(g2), n, n_r, out, ctypes.byref(got_S))
-        assert st == 0, "dshim_pair_lines(curve %d, form %d, n %d, n_r %d): HIP error %d" % (cid, form, n, n_r, -st)
+        check(st, "dshim_pair_lines(curve %d, form %d, n %d, n_r %d)" % (cid, form, n, n_r))
         assert got_S.value == S
         return out.raw, S
 
@@ -231,7 +236,7 @@ class PairShim:
         out = ctypes.create_string_buffer(count * S * ((n + c - 1) // c) * 12 * nb)
         st = self.lib.dshim_pair_tree_lines(cid, bytes(lines), bytes(g1), n, c, n_l, n_r, S, pa, pb, len(pairs) if pairs else 0,
                                             out)
-        assert st == 0, "dshim_pair_tree_lines(curve %d, n %d): HIP error %d" % (cid, n, -st)
+        check(st, "dshim_pair_tree_lines(curve %d, n %d)" % (cid, n))
         return out.raw
 
     def pair_tree(self, cid, nb, vals, n, c, count):
@@ -239,7 +244,7 @@ class PairShim:
         assert len(vals) == count * n * 12 * nb
         out = ctypes.create_string_buffer(count * ((n + c - 1) // c) * 12 * nb)
         st = self.lib.dshim_pair_tree(cid, bytes(vals), n, c, count, out)
-        assert st == 0, "dshim_pair_tree(curve %d, n %d, c %d): HIP error %d" % (cid, n, c, -st)
+        check(st, "dshim_pair_tree(curve %d, n %d, c %d)" % (cid, n, c))
         return out.raw
 
     def pair_horner(self, cid, nb, L, count):
@@ -247,60 +252,51 @@ class PairShim:
         assert len(L) == count * self.steps(cid) * 12 * nb
         out = ctypes.create_string_buffer(count * 12 * nb)
         st = self.lib.dshim_pair_horner(cid, bytes(L), count, out)
-        assert st == 0, "dshim_pair_horner(curve %d, count %d): HIP error %d" % (cid, count, -st)
+        check(st, "dshim_pair_horner(curve %d, count %d)" % (cid, count))
         return out.raw
 
 
-def load_pair(variant):
-    if variant not in _loaded_pair:
-        _loaded_pair[variant] = PairShim(variant)
-    return _loaded_pair[variant]
+load_pair = PairShim.load
 
 
-class NttShim:
+class NttShim(Shim):
     """One launch per call of the Fr transform layer.  Fr vectors travel as bytes: canonical Montgomery values, 32 bytes
     each, little-endian - what the kernels read and write.  `curve` is 0 (BN254 Fr) or 1 (BLS12-381 Fr).  The *_status forms
     give (status, bytes or None): 0, NTT_REFUSED, or minus a hipError_t."""
 
+    LIBS, USES_ASM = NTT_VARIANTS, "dshim_ntt_uses_asm"
+    SIGS = {"dshim_ntt_tables": [ci, ui, vp, vp], "dshim_pow_table": [ci, vp, ui, ui, vp],
+            "dshim_pow_from_tables": [ci, vp, up, ui, ui, vp],
+            "dshim_ntt_pass": [ci, ci, vp, sz, ui, vp, ui, ui, ui, ui, ui, ci, ui, vp, vp, vp, vp],
+            "dshim_scale_pow": [ci, vp, sz, ui, vp, vp, ui, ci, ci], "dshim_bitrev": [ci, vp, ui],
+            "dshim_mul_pointwise": [ci, vp, vp, sz],
+            "dshim_spmv": [ci, ctypes.POINTER(ctypes.c_ulonglong), up, vp, sz, vp, sz, vp, ui, ui, ui],
+            "dshim_scan_u32": [ctypes.c_void_p, ctypes.c_void_p, ui], "dshim_ntt_scan_pad": ([], ui)}
+
     def __init__(self, variant):
-        path = os.path.join(ROOT, "hekaton_system_amd", "lib", NTT_VARIANTS[variant])
-        assert os.path.exists(path), "build the device shim first (python __graft_entry__.py)"
-        self.variant = variant
-        self.lib = ctypes.CDLL(path)
-        vp, ui, sz, ci = ctypes.c_char_p, ctypes.c_uint, ctypes.c_size_t, ctypes.c_int
-        self.lib.dshim_ntt_tables.argtypes = [ci, ui, vp, vp]
-        self.lib.dshim_pow_table.argtypes = [ci, vp, ui, ui, vp]
-        self.lib.dshim_pow_from_tables.argtypes = [ci, vp, ctypes.POINTER(ui), ui, ui, vp]
-        self.lib.dshim_ntt_pass.argtypes = [ci, ci, vp, sz, ui, vp, ui, ui, ui, ui, ui, ci, ui, vp, vp, vp, vp]
-        self.lib.dshim_scale_pow.argtypes = [ci, vp, sz, ui, vp, vp, ui, ci, ci]
-        self.lib.dshim_bitrev.argtypes = [ci, vp, ui]
-        self.lib.dshim_mul_pointwise.argtypes = [ci, vp, vp, sz]
-        self.lib.dshim_spmv.argtypes = [ci, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ui), vp, sz, vp, sz, vp, ui, ui, ui]
-        self.lib.dshim_scan_u32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ui]
-        self.lib.dshim_ntt_scan_pad.restype = ui
+        super().__init__(variant)
         self.scan_pad = self.lib.dshim_ntt_scan_pad()
-        assert self.lib.dshim_ntt_uses_asm() == (1 if variant == "asm" else 0)
 
     def ntt_tables(self, curve, log_table, sq):
         """sq: bytes of log_table entries w^(2^k) -> bytes of the 2^log_table - 1 stage-table entries"""
         assert len(sq) == log_table * FR_BYTES
         out = ctypes.create_string_buffer(((1 << log_table) - 1) * FR_BYTES)
         st = self.lib.dshim_ntt_tables(curve, log_table, bytes(sq), out)
-        assert st == 0, "dshim_ntt_tables(curve %d, log_table %d): status %d" % (curve, log_table, st)
+        check(st, "dshim_ntt_tables(curve %d, log_table %d)" % (curve, log_table))
         return out.raw
 
     def pow_table(self, curve, sq, count, nbits):
         assert len(sq) == nbits * FR_BYTES
         out = ctypes.create_string_buffer(count * FR_BYTES)
         st = self.lib.dshim_pow_table(curve, bytes(sq), count, nbits, out)
-        assert st == 0, "dshim_pow_table(curve %d, count %d, nbits %d): status %d" % (curve, count, nbits, st)
+        check(st, "dshim_pow_table(curve %d, count %d, nbits %d)" % (curve, count, nbits))
         return out.raw
 
     def pow_from_tables(self, curve, pw, js, logn):
         assert len(pw) == 3 * 2048 * FR_BYTES
         out = ctypes.create_string_buffer(len(js) * FR_BYTES)
         st = self.lib.dshim_pow_from_tables(curve, bytes(pw), (ctypes.c_uint * len(js))(*js), len(js), logn, out)
-        assert st == 0, "dshim_pow_from_tables(curve %d, logn %d): status %d" % (curve, logn, st)
+        check(st, "dshim_pow_from_tables(curve %d, logn %d)" % (curve, logn))
         return out.raw
 
     def ntt_pass_status(self, curve, dit, data, stride, batch, tws, logn, lo, nst, cols_bits, threads, post=0, npost=0xffffffff,
@@ -316,29 +312,29 @@ class NttShim:
 
     def ntt_pass(self, curve, dit, data, stride, batch, tws, logn, lo, nst, cols_bits, threads, **ep):
         st, out = self.ntt_pass_status(curve, dit, data, stride, batch, tws, logn, lo, nst, cols_bits, threads, **ep)
-        assert st == 0, "dshim_ntt_pass(curve %d, dit %d, logn %d, lo %d, nst %d, cols_bits %d, threads %d): status %d" % (
-            curve, dit, logn, lo, nst, cols_bits, threads, st)
+        check(st, "dshim_ntt_pass(curve %d, dit %d, logn %d, lo %d, nst %d, cols_bits %d, threads %d)" % (
+            curve, dit, logn, lo, nst, cols_bits, threads))
         return out
 
     def scale_pow(self, curve, data, stride, batch, pw, scale, logn, bitrev_index, use_pow):
         assert len(data) == batch * stride * FR_BYTES
         buf = ctypes.create_string_buffer(bytes(data), len(data))
         st = self.lib.dshim_scale_pow(curve, buf, stride, batch, pw, scale, logn, bitrev_index, use_pow)
-        assert st == 0, "dshim_scale_pow(curve %d, logn %d): status %d" % (curve, logn, st)
+        check(st, "dshim_scale_pow(curve %d, logn %d)" % (curve, logn))
         return buf.raw
 
     def bitrev(self, curve, data, logn):
         assert len(data) == FR_BYTES << logn
         buf = ctypes.create_string_buffer(bytes(data), len(data))
         st = self.lib.dshim_bitrev(curve, buf, logn)
-        assert st == 0, "dshim_bitrev(curve %d, logn %d): status %d" % (curve, logn, st)
+        check(st, "dshim_bitrev(curve %d, logn %d)" % (curve, logn))
         return buf.raw
 
     def mul_pointwise(self, curve, a, b):
         assert len(a) == len(b)
         buf = ctypes.create_string_buffer(bytes(a), len(a))
         st = self.lib.dshim_mul_pointwise(curve, buf, bytes(b), len(a) // FR_BYTES)
-        assert st == 0, "dshim_mul_pointwise(curve %d, m %d): status %d" % (curve, len(a) // FR_BYTES, st)
+        check(st, "dshim_mul_pointwise(curve %d, m %d)" % (curve, len(a) // FR_BYTES))
         return buf.raw
 
     def spmv(self, curve, row_ptr, col, val, z, out, n_copy):
@@ -348,7 +344,7 @@ class NttShim:
         buf = ctypes.create_string_buffer(bytes(out), len(out))
         st = self.lib.dshim_spmv(curve, (ctypes.c_ulonglong * (n_rows + 1))(*row_ptr), (ctypes.c_uint * max(nnz, 1))(*col),
                                  bytes(val), nnz, bytes(z), len(z) // FR_BYTES, buf, n_rows, n_copy, m)
-        assert st == 0, "dshim_spmv(curve %d, n_rows %d, n_copy %d, m %d): status %d" % (curve, n_rows, n_copy, m, st)
+        check(st, "dshim_spmv(curve %d, n_rows %d, n_copy %d, m %d)" % (curve, n_rows, n_copy, m))
         return buf.raw
 
     def scan_u32(self, counts, out):
@@ -357,34 +353,23 @@ class NttShim:
         assert counts.dtype.name == "uint32" and out.dtype.name == "uint32" and len(out) == n + self.scan_pad
         assert counts.flags["C_CONTIGUOUS"] and out.flags["C_CONTIGUOUS"]
         st = self.lib.dshim_scan_u32(counts.ctypes.data if n else None, out.ctypes.data, n)
-        assert st == 0, "dshim_scan_u32(n %d): status %d" % (n, st)
+        check(st, "dshim_scan_u32(n %d)" % n)
 
 
-def load_ntt(variant):
-    if variant not in _loaded_ntt:
-        _loaded_ntt[variant] = NttShim(variant)
-    return _loaded_ntt[variant]
+load_ntt = NttShim.load
 
 
-class SweepShim:
+class SweepShim(Shim):
     """One launch per call of the group sweeps (fixed_base.cuh, endo.cuh).  Everything travels as the bytes the kernels read
     and write: affine points and Fr scalars in memory form (pb bytes per affine point, 32 per scalar), XYZZ results as stored
     (2 pb bytes: x, y, zz, zzz).  `gid`: 0 bn254 G1, 1 bn254 G2, 2 bls G1, 3 bls G2.  The *_status forms give (status, bytes
     or None): 0 or minus a hipError_t."""
 
-    def __init__(self):
-        path = os.path.join(ROOT, "hekaton_system_amd", "lib", SWEEP_LIB)
-        assert os.path.exists(path), "build the device shim first (python __graft_entry__.py)"
-        self.lib = ctypes.CDLL(path)
-        vp, ui, ci = ctypes.c_char_p, ctypes.c_uint, ctypes.c_int
-        self.lib.dshim_fb_table.argtypes = [ci, vp, vp]
-        self.lib.dshim_fb_mul.argtypes = [ci, vp, vp, ci, ui, vp]
-        self.lib.dshim_points_lincomb.argtypes = [ci, vp, vp, ui, ui, vp]
-        self.lib.dshim_scalar_mul.argtypes = [ci, ci, vp, vp, ui, vp]
-        self.lib.dshim_points_fold_endo.argtypes = [ci, vp, vp, vp, ui, ui, vp]
-        self.lib.dshim_points_mul_split.argtypes = [ci, ci, ci, vp, vp, vp, ui, ui, ui, ui, ci, vp]
-        self.lib.dshim_points_sum.argtypes = [ci, vp, ui, vp]
-        self.lib.dshim_points_sum_seg.argtypes = [ci, vp, ui, ui, vp]
+    LIBS = {"asm": SWEEP_LIB}
+    SIGS = {"dshim_fb_table": [ci, vp, vp], "dshim_fb_mul": [ci, vp, vp, ci, ui, vp], "dshim_points_lincomb": [ci, vp, vp, ui, ui, vp],
+            "dshim_scalar_mul": [ci, ci, vp, vp, ui, vp], "dshim_points_fold_endo": [ci, vp, vp, vp, ui, ui, vp],
+            "dshim_points_mul_split": [ci, ci, ci, vp, vp, vp, ui, ui, ui, ui, ci, vp], "dshim_points_sum": [ci, vp, ui, vp],
+            "dshim_points_sum_seg": [ci, vp, ui, ui, vp]}
 
     def sum_threads(self, gid):
         return self.lib.dshim_sweep_sum_threads(gid)
@@ -401,7 +386,7 @@ class SweepShim:
 
     @staticmethod
     def _done(st, what, out):
-        assert st == 0, "%s: HIP error %d" % (what, -st)
+        check(st, what)
         return out.raw
 
     def fb_table(self, gid, pb, base):
@@ -447,8 +432,7 @@ class SweepShim:
 
     def mul_split(self, gid, pb, form, uniform, pts, scalars, n, **kw):
         st, out = self.mul_split_status(gid, pb, form, uniform, pts, scalars, n, **kw)
-        assert st == 0, "dshim_points_mul_split(g%d, form %d, uniform %d, n %d, %r): HIP error %d" % (gid, form, uniform, n,
-                                                                                                     sorted(kw), -st)
+        check(st, "dshim_points_mul_split(g%d, form %d, uniform %d, n %d, %r)" % (gid, form, uniform, n, sorted(kw)))
         return out
 
     def points_sum(self, gid, pb, pts):
@@ -463,7 +447,25 @@ class SweepShim:
                           "dshim_points_sum_seg(g%d, seg %d, batch %d)" % (gid, seg, batch), out)
 
 
-def load_sweep():
-    if not _loaded_sweep:
-        _loaded_sweep.append(SweepShim())
-    return _loaded_sweep[0]
+load_sweep = SweepShim.load
+
+
+class SublistShim(Shim):
+    """MsmSort::sublist on a caller-supplied sorted list (BN254 Fr, WP = 1); the arrays are C-contiguous numpy uint32"""
+    LIBS = {"asm": SUBLIST_LIB}
+    SIGS = {"dshim_sublist_plan": [ui, ui, ui, up], "dshim_msm_sublist": [ui, ui, ui, ui] + [ctypes.c_void_p] * 5}
+
+    def plan(self, c, n, n_dst):
+        """-> W, NB, gshift_src, gshift_dst, sorted stride src, sorted stride dst, tiles per proof"""
+        out = (ctypes.c_uint * 7)()
+        check(self.lib.dshim_sublist_plan(c, n, n_dst, out), "dshim_sublist_plan(c %d, n %d, n_dst %d)" % (c, n, n_dst))
+        return list(out)
+
+    def sublist(self, c, batch, n, n_dst, sorted_src, start_src, rank, sorted_dst, start_dst):
+        """sorted_dst, start_dst: as they lie before the call, changed in place"""
+        arrays = (sorted_src, start_src, rank, sorted_dst, start_dst)
+        assert all(a.dtype.name == "uint32" and a.flags["C_CONTIGUOUS"] for a in arrays)
+        check(self.lib.dshim_msm_sublist(c, batch, n, n_dst, *[a.ctypes.data for a in arrays]), "dshim_msm_sublist")
+
+
+load_sublist = SublistShim.load

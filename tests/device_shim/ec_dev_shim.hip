@@ -5,8 +5,8 @@
 // runs the product's sort, accumulate, level chain and reductions on vectors that no caller-visible plan would give it.
 // Test-only; never part of libhekaton.
 //
-// One translation unit per group (-DEC_SHIM_GROUP=0..3: bn254 G1, bn254 G2, bls12-381 G1, bls12-381 G2, as shim_group_op),
-// linked into one library; group 0's unit also holds the extern "C" entry points.  Built twice by the Makefile next to it:
+// One translation unit per group (-DSHIM_GROUP=0..3: the ladder of shim_common.cuh), linked into one library; group 0's
+// unit also holds the extern "C" entry points.  Built twice by the Makefile next to it:
 // as shipped, and with -DHK_NO_ASM_MUL -DEC_SHIM_NO_MSM (the C++ fallback under the same lazy representation; group law
 // and batch inversion only).  Only forms the product ships are instantiated: ec_madd<F, AccumInlineCorner<F>::value> is
 // the accumulate loop's, so the inlined P == Q corner of a 12-limb G2 does not exist here either.
@@ -14,29 +14,11 @@
 // Operands enter as raw limbs; every HIP status is returned to the caller; the shim allocates and frees its own buffers
 // and never touches an hk_ctx.
 #include "../../hekaton_system_amd/csrc/msm_driver_impl.cuh"
-using namespace hk;
-
-#ifndef EC_SHIM_GROUP
-#error "compile with -DEC_SHIM_GROUP=0..3"
+#ifndef SHIM_GROUP
+#error "compile with -DSHIM_GROUP=0..3"
 #endif
-
-#if EC_SHIM_GROUP == 0
-typedef CurveBn254 ShimCurve;
-typedef CurveBn254::Fq ShimF;
-#define SHIM_FN(name) ec_shim_g0_##name
-#elif EC_SHIM_GROUP == 1
-typedef CurveBn254 ShimCurve;
-typedef CurveBn254::Fq2 ShimF;
-#define SHIM_FN(name) ec_shim_g1_##name
-#elif EC_SHIM_GROUP == 2
-typedef CurveBls381 ShimCurve;
-typedef CurveBls381::Fq ShimF;
-#define SHIM_FN(name) ec_shim_g2_##name
-#else
-typedef CurveBls381 ShimCurve;
-typedef CurveBls381::Fq2 ShimF;
-#define SHIM_FN(name) ec_shim_g3_##name
-#endif
+#define SHIM_PREFIX ec_shim
+#include "shim_common.cuh"
 
 enum GroupOp { G_MADD = 0, G_MADD_NI, G_ADD, G_ADD_NI, G_DBL, G_DBL_NI, G_DBL_AFFINE, G_NEG, G_TO_AFFINE, G_MUL_SMALL,
                G_MUL_LIMBS, G_MADD_CHAIN, G_NOPS };
@@ -45,21 +27,7 @@ enum GroupOp { G_MADD = 0, G_MADD_NI, G_ADD, G_ADD_NI, G_DBL, G_DBL_NI, G_DBL_AF
 // kernels with product names (k_batch_affine<...>, k_msm_*<...>) are the same symbols in all three: what keeps them apart is
 // the -Bsymbolic link of the shim Makefile (a library's launches bind to its own kernel handles) together with a loader
 // that does not merge the libraries' symbols (ctypes: RTLD_LOCAL).  k_group_op exists in the two shim builds only and
-// carries the variant in its name as well, so that a kernel trace tells them apart.
-#if defined(HK_NO_ASM_MUL)
-constexpr int VARIANT = 0;
-#else
-constexpr int VARIANT = 1;
-#endif
-
-template <class P> __device__ __forceinline__ void ld_raw(Fp<P>& f, const u32* p) {
-    HK_UNROLL for (int i = 0; i < P::N; i++) f.v[i] = p[i];
-}
-template <class P> __device__ __forceinline__ void ld_raw(Fp2<P>& f, const u32* p) { ld_raw(f.c0, p); ld_raw(f.c1, p + P::N); }
-template <class P> __device__ __forceinline__ void st_raw(u32* p, const Fp<P>& f) {
-    HK_UNROLL for (int i = 0; i < P::N; i++) p[i] = f.v[i];
-}
-template <class P> __device__ __forceinline__ void st_raw(u32* p, const Fp2<P>& f) { st_raw(p, f.c0); st_raw(p + P::N, f.c1); }
+// carries VARIANT in its name as well, so that a kernel trace tells them apart.
 
 // one lane per case.  a: n XYZZ points (x, y, zz, zzz), b: n slots of the same size - an XYZZ point, an affine point in its
 // first half, or the 8 limbs of a canonical scalar (G_MUL_LIMBS); out: n slots: the XYZZ registers as they stand (raw) or
@@ -109,21 +77,14 @@ k_group_op(const u32* __restrict__ a, const u32* __restrict__ b, u32* __restrict
 // ---- host side ---------------------------------------------------------------------------------------------------
 namespace {
 
-struct DevBufs {
-    void* p[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~DevBufs() { for (void* q : p) if (q) (void)hipFree(q); }
-};
-
-#define SHIM_TRY(e) do { hipError_t st_ = (e); if (st_ != hipSuccess) return -(int)st_; } while (0)
-
 // The C++ fallback of the Montgomery product is several times the size of the assembly, and two flavours of the group law
 // outgrow the code-object bounds with it (tools/kernel_meta.py --check refuses the library): every
 // form that adds two points in 8-limb G2 (ec_add_ni alone is 160 KB there), and the INLINED mixed add of 12-limb G1.  The
 // -DHK_NO_ASM_MUL build leaves those out and answers hipErrorNotSupported for them; the as-shipped build holds every op.
 constexpr bool op_built(int op) {
-#if defined(HK_NO_ASM_MUL) && EC_SHIM_GROUP == 1
+#if defined(HK_NO_ASM_MUL) && SHIM_GROUP == 1
     return op == G_DBL || op == G_DBL_NI || op == G_DBL_AFFINE || op == G_NEG || op == G_TO_AFFINE;
-#elif defined(HK_NO_ASM_MUL) && EC_SHIM_GROUP == 2
+#elif defined(HK_NO_ASM_MUL) && SHIM_GROUP == 2
     return op != G_MADD && op != G_MADD_CHAIN;
 #else
     return op >= 0;
@@ -144,14 +105,11 @@ int group_op(int op, const void* a, const void* b, void* out, size_t n, int raw,
     if (!op_built(op)) return -(int)hipErrorNotSupported;
     size_t bytes = n * sizeof(XYZZ<F>);
     DevBufs d;
-    SHIM_TRY(hipMalloc(&d.p[0], bytes));
-    SHIM_TRY(hipMalloc(&d.p[1], bytes));
-    SHIM_TRY(hipMalloc(&d.p[2], bytes));
-    SHIM_TRY(hipMemcpy(d.p[0], a, bytes, hipMemcpyHostToDevice));
-    SHIM_TRY(hipMemcpy(d.p[1], b ? b : a, bytes, hipMemcpyHostToDevice));
-    SHIM_TRY(hipMemset(d.p[2], 0xA5, bytes));
-    const u32 *da = (const u32*)d.p[0], *db = (const u32*)d.p[1];
-    u32* dout = (u32*)d.p[2];
+    const u32 *da, *db;
+    u32* dout;
+    SHIM_GET(&da, bytes, a);
+    SHIM_GET(&db, bytes, b ? b : a);
+    SHIM_GET(&dout, bytes, nullptr);
     switch (op) {
         case G_MADD: launch_op<F, G_MADD>(da, db, dout, (u32)n, raw, k); break;
         case G_MADD_NI: launch_op<F, G_MADD_NI>(da, db, dout, (u32)n, raw, k); break;
@@ -166,29 +124,22 @@ int group_op(int op, const void* a, const void* b, void* out, size_t n, int raw,
         case G_MUL_LIMBS: launch_op<F, G_MUL_LIMBS>(da, db, dout, (u32)n, raw, k); break;
         default: launch_op<F, G_MADD_CHAIN>(da, db, dout, (u32)n, raw, k); break;
     }
-    SHIM_TRY(hipGetLastError());
-    SHIM_TRY(hipDeviceSynchronize());
-    SHIM_TRY(hipMemcpy(out, d.p[2], bytes, hipMemcpyDeviceToHost));
-    return 0;
+    return finish(out, dout, bytes);
 }
 
 // the product's k_batch_affine with the caller's chunk (MsmRun::batch_affine derives it from n: 1 up to 65 536 points)
 template <class F>
 int batch_affine(const void* in, void* out, size_t n, unsigned chunk) {
     DevBufs d;
-    SHIM_TRY(hipMalloc(&d.p[0], n * sizeof(XYZZ<F>)));
-    SHIM_TRY(hipMalloc(&d.p[1], n * sizeof(Affine<F>)));
-    SHIM_TRY(hipMalloc(&d.p[2], n * sizeof(F)));
-    SHIM_TRY(hipMemcpy(d.p[0], in, n * sizeof(XYZZ<F>), hipMemcpyHostToDevice));
-    SHIM_TRY(hipMemset(d.p[1], 0xA5, n * sizeof(Affine<F>)));
-    SHIM_TRY(hipMemset(d.p[2], 0xA5, n * sizeof(F)));
+    const XYZZ<F>* pts;
+    Affine<F>* aff;
+    F* tmp;
+    SHIM_GET(&pts, n * sizeof(XYZZ<F>), in);
+    SHIM_GET(&aff, n * sizeof(Affine<F>), nullptr);
+    SHIM_GET(&tmp, n * sizeof(F), nullptr);
     u32 lanes = (u32)((n + chunk - 1) / chunk);
-    hipLaunchKernelGGL((k_batch_affine<F>), dim3((lanes + 63) / 64), dim3(64), 0, 0, (const XYZZ<F>*)d.p[0], (Affine<F>*)d.p[1],
-                       (F*)d.p[2], (u32)n, (u32)chunk);
-    SHIM_TRY(hipGetLastError());
-    SHIM_TRY(hipDeviceSynchronize());
-    SHIM_TRY(hipMemcpy(out, d.p[1], n * sizeof(Affine<F>), hipMemcpyDeviceToHost));
-    return 0;
+    hipLaunchKernelGGL((k_batch_affine<F>), dim3((lanes + 63) / 64), dim3(64), 0, 0, pts, aff, tmp, (u32)n, (u32)chunk);
+    return finish(out, aff, n * sizeof(Affine<F>));
 }
 
 #if !defined(EC_SHIM_NO_MSM)
@@ -225,10 +176,8 @@ int msm(unsigned c, unsigned WP, unsigned batch, unsigned n, unsigned n_bases, u
     Carve count;
     carve(count);
     DevBufs d;
-    SHIM_TRY(hipMalloc(&d.p[0], count.off + 256));
-    SHIM_TRY(hipMemset(d.p[0], 0xA5, count.off + 256));            // no stage may rely on cleared scratch
     Carve real;
-    real.base = (char*)d.p[0];
+    SHIM_GET(&real.base, count.off + 256, nullptr);                // 0xA5: no stage may rely on cleared scratch
     carve(real);
     if (n_bases) SHIM_TRY(hipMemcpy(table, bases, (size_t)n_bases * sizeof(Affine<F>), hipMemcpyHostToDevice));
     SHIM_TRY(hipMemcpy(sc, scalars, (size_t)batch * n * sizeof(Fr), hipMemcpyHostToDevice));
@@ -259,7 +208,7 @@ int SHIM_FN(msm)(unsigned c, unsigned WP, unsigned batch, unsigned n, unsigned n
 }
 #endif
 
-#if EC_SHIM_GROUP == 0
+#if SHIM_GROUP == 0
 #define SHIM_DECL(g)                                                                                                        \
     int ec_shim_g##g##_group_op(int, const void*, const void*, void*, size_t, int, unsigned);                              \
     int ec_shim_g##g##_op_built(int);                                                                                      \
@@ -269,7 +218,6 @@ int SHIM_FN(msm)(unsigned c, unsigned WP, unsigned batch, unsigned n, unsigned n
 SHIM_DECL(1) SHIM_DECL(2) SHIM_DECL(3)
 
 extern "C" {
-// 1 when the arithmetic was compiled with the inline assembly of mont_asm.h, 0 for the -DHK_NO_ASM_MUL build
 int dshim_ec_uses_asm(void) { return VARIANT; }
 // 1 when dshim_msm is part of this build
 int dshim_ec_has_msm(void) {
@@ -281,39 +229,21 @@ int dshim_ec_has_msm(void) {
 }
 // 1 when this build holds `op` for `group` (see op_built), else 0
 int dshim_ec_op_built(int group, int op) {
-    if (op < 0 || op >= G_NOPS) return 0;
-    switch (group) {
-        case 0: return ec_shim_g0_op_built(op);
-        case 1: return ec_shim_g1_op_built(op);
-        case 2: return ec_shim_g2_op_built(op);
-        case 3: return ec_shim_g3_op_built(op);
-    }
-    return 0;
+    if (op < 0 || op >= G_NOPS || group < 0 || group > 3) return 0;
+    SHIM_DISPATCH(group, op_built(op))
 }
 // group: 0 bn254 G1, 1 bn254 G2, 2 bls G1, 3 bls G2 (as shim_group_op); op: GroupOp; a, b, out: n slots of 4 coordinate-field
 // elements, raw limbs (see k_group_op); raw: store the registers as they stand instead of through st_vec.
-// Returns 0, or minus the first failing hipError_t.
+// Returns 0, or minus the first failing hipError_t (hipErrorInvalidValue for an unknown group, as every entry point below).
 int dshim_group_op(int group, int op, const void* a, const void* b, void* out, size_t n, int raw, unsigned k) {
     if (op < 0 || op >= G_NOPS || n == 0 || n > (1u << 20) || !a || !out) return -(int)hipErrorInvalidValue;
     if (op == G_MADD_CHAIN && k > 4096) return -(int)hipErrorInvalidValue;
-    switch (group) {
-        case 0: return ec_shim_g0_group_op(op, a, b, out, n, raw, k);
-        case 1: return ec_shim_g1_group_op(op, a, b, out, n, raw, k);
-        case 2: return ec_shim_g2_group_op(op, a, b, out, n, raw, k);
-        case 3: return ec_shim_g3_group_op(op, a, b, out, n, raw, k);
-    }
-    return -(int)hipErrorInvalidValue;
+    SHIM_DISPATCH(group, group_op(op, a, b, out, n, raw, k))
 }
 // in: n XYZZ points as they lie in memory, out: n affine points; chunk: points per lane (one inversion per lane)
 int dshim_batch_affine(int group, const void* in, void* out, size_t n, unsigned chunk) {
     if (n == 0 || n > (1u << 20) || chunk == 0 || chunk > 4096 || !in || !out) return -(int)hipErrorInvalidValue;
-    switch (group) {
-        case 0: return ec_shim_g0_batch_affine(in, out, n, chunk);
-        case 1: return ec_shim_g1_batch_affine(in, out, n, chunk);
-        case 2: return ec_shim_g2_batch_affine(in, out, n, chunk);
-        case 3: return ec_shim_g3_batch_affine(in, out, n, chunk);
-    }
-    return -(int)hipErrorInvalidValue;
+    SHIM_DISPATCH(group, batch_affine(in, out, n, chunk))
 }
 // bases: n_bases affine points (memory form: canonical Montgomery); scalars: batch x n Fr (Montgomery when mont); out: batch
 // affine points.  Returns 0, the product's hk_status (> 0) unchanged, or minus the hipError_t of one of the shim's own calls.
@@ -325,13 +255,7 @@ int dshim_msm(int group, unsigned c, unsigned WP, unsigned batch, unsigned n, un
     if (c < 3 || c > 16 || WP == 0 || batch == 0 || batch > 8 || n == 0 || n > (1u << 20) || n_bases > (1u << 20) ||
         idx_off > (1u << 20) || !scalars || !out || (n_bases && !bases))
         return -(int)hipErrorInvalidValue;
-    switch (group) {
-        case 0: return ec_shim_g0_msm(c, WP, batch, n, n_bases, idx_off, bases, scalars, mont, out, plan_out);
-        case 1: return ec_shim_g1_msm(c, WP, batch, n, n_bases, idx_off, bases, scalars, mont, out, plan_out);
-        case 2: return ec_shim_g2_msm(c, WP, batch, n, n_bases, idx_off, bases, scalars, mont, out, plan_out);
-        case 3: return ec_shim_g3_msm(c, WP, batch, n, n_bases, idx_off, bases, scalars, mont, out, plan_out);
-    }
-    return -(int)hipErrorInvalidValue;
+    SHIM_DISPATCH(group, msm(c, WP, batch, n, n_bases, idx_off, bases, scalars, mont, out, plan_out))
 #endif
 }
 }

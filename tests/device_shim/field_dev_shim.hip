@@ -8,30 +8,14 @@
 // to the caller; the shim allocates and frees its own buffers and never touches an hk_ctx.
 #include "../../hekaton_system_amd/csrc/ec.cuh"
 #include "../../hekaton_system_amd/csrc/pairing_wave.cuh"
-using namespace hk;
+#include "shim_common.cuh"
 
 enum FieldOp { F_ADD = 0, F_SUB, F_MUL, F_SQR, F_NEG, F_DBL, F_HALVE, F_CANON, F_TO_MONT, F_FROM_MONT, F_INV, F_IS_ZERO, F_EQ,
                F_CHAIN, F_NOPS };
 enum WaveOp { W_MUL = 0, W_SQR, W_CYC_SQR, W_CONJ, W_FROB1, W_FROB2, W_FROB3, W_INV, W_NOPS };
 
-// part of every kernel's name: both variants get loaded into one test process, and each must launch its own kernels
-#if defined(HK_NO_ASM_MUL)
-constexpr int VARIANT = 0;
-#else
-constexpr int VARIANT = 1;
-#endif
-
 template <class F> struct IsBase { static constexpr bool value = false; };
 template <class P> struct IsBase<Fp<P>> { static constexpr bool value = true; };
-
-template <class P> __device__ __forceinline__ void ld_raw(Fp<P>& f, const u32* p) {
-    HK_UNROLL for (int i = 0; i < P::N; i++) f.v[i] = p[i];
-}
-template <class P> __device__ __forceinline__ void ld_raw(Fp2<P>& f, const u32* p) { ld_raw(f.c0, p); ld_raw(f.c1, p + P::N); }
-template <class P> __device__ __forceinline__ void st_raw(u32* p, const Fp<P>& f) {
-    HK_UNROLL for (int i = 0; i < P::N; i++) p[i] = f.v[i];
-}
-template <class P> __device__ __forceinline__ void st_raw(u32* p, const Fp2<P>& f) { st_raw(p, f.c0); st_raw(p + P::N, f.c1); }
 
 // one lane per element; a, b, out: n x F::N limbs
 template <class F, int V>
@@ -115,33 +99,22 @@ k_wave_op(int op, const u32* __restrict__ a, const u32* __restrict__ b, u32* __r
 // ---- host side ---------------------------------------------------------------------------------------------------
 namespace {
 
-struct DevBufs {
-    void *a = nullptr, *b = nullptr, *out = nullptr;
-    ~DevBufs() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (out) (void)hipFree(out); }
-};
-
-#define SHIM_TRY(e) do { hipError_t st_ = (e); if (st_ != hipSuccess) return (int)st_; } while (0)
-
 // uploads a and b (in_bytes each), runs launch(da, db, dout), downloads out (out_bytes)
 template <class L>
 int run(const void* a, const void* b, void* out, size_t in_bytes, size_t out_bytes, L launch) {
     DevBufs d;
-    SHIM_TRY(hipMalloc(&d.a, in_bytes));
-    SHIM_TRY(hipMalloc(&d.b, in_bytes));
-    SHIM_TRY(hipMalloc(&d.out, out_bytes));
-    SHIM_TRY(hipMemcpy(d.a, a, in_bytes, hipMemcpyHostToDevice));
-    SHIM_TRY(hipMemcpy(d.b, b ? b : a, in_bytes, hipMemcpyHostToDevice));
-    SHIM_TRY(hipMemset(d.out, 0xA5, out_bytes));
-    launch((const u32*)d.a, (const u32*)d.b, (u32*)d.out);
-    SHIM_TRY(hipGetLastError());
-    SHIM_TRY(hipDeviceSynchronize());
-    SHIM_TRY(hipMemcpy(out, d.out, out_bytes, hipMemcpyDeviceToHost));
-    return 0;
+    const u32 *da, *db;
+    u32* dout;
+    SHIM_GET(&da, in_bytes, a);
+    SHIM_GET(&db, in_bytes, b ? b : a);
+    SHIM_GET(&dout, out_bytes, nullptr);
+    launch(da, db, dout);
+    return finish(out, dout, out_bytes);
 }
 
 template <class F>
 int field_op(int op, const void* a, const void* b, void* out, size_t n, int raw, int chain) {
-    if (!IsBase<F>::value && (op == F_TO_MONT || op == F_FROM_MONT)) return (int)hipErrorInvalidValue;
+    if (!IsBase<F>::value && (op == F_TO_MONT || op == F_FROM_MONT)) return -(int)hipErrorInvalidValue;
     size_t bytes = n * F::N * sizeof(u32);
     return run(a, b, out, bytes, bytes, [&](const u32* da, const u32* db, u32* dout) {
         hipLaunchKernelGGL((k_field_op<F, VARIANT>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, op, da, db, dout, (u32)n, raw, chain);
@@ -160,18 +133,12 @@ int wave_op(int op, const void* a, const void* b, void* out, size_t n, int alias
 
 extern "C" {
 // 1 when the arithmetic was compiled with the inline assembly of mont_asm.h, 0 for the -DHK_NO_ASM_MUL build
-int dshim_uses_asm(void) {
-#if defined(HK_NO_ASM_MUL)
-    return 0;
-#else
-    return 1;
-#endif
-}
+int dshim_uses_asm(void) { return VARIANT; }
 // field: 0 bn254 Fr, 1 bn254 Fq, 2 bls Fr, 3 bls Fq, 4 bn254 Fq2, 5 bls Fq2 (as shim_field_op); op: FieldOp;
 // a, b, out: n elements of raw limbs (b may be null for unary ops); raw: store the registers as they stand instead of through
-// canon(); chain: iterations of F_CHAIN.  Returns 0 or the first failing hipError_t.
+// canon(); chain: iterations of F_CHAIN.  Returns 0 or minus the first failing hipError_t.
 int dshim_field_op(int field, int op, const void* a, const void* b, void* out, size_t n, int raw, int chain) {
-    if (op < 0 || op >= F_NOPS || n == 0 || n > (1u << 24) || chain < 0) return (int)hipErrorInvalidValue;
+    if (op < 0 || op >= F_NOPS || n == 0 || n > (1u << 24) || chain < 0) return -(int)hipErrorInvalidValue;
     switch (field) {
         case 0: return field_op<Fp<Bn254FrP>>(op, a, b, out, n, raw, chain);
         case 1: return field_op<Fp<Bn254FqP>>(op, a, b, out, n, raw, chain);
@@ -180,16 +147,16 @@ int dshim_field_op(int field, int op, const void* a, const void* b, void* out, s
         case 4: return field_op<Fp2<Bn254FqP>>(op, a, b, out, n, raw, chain);
         case 5: return field_op<Fp2<Bls381FqP>>(op, a, b, out, n, raw, chain);
     }
-    return (int)hipErrorInvalidValue;
+    return -(int)hipErrorInvalidValue;
 }
 // curve: 0 bn254, 1 bls12-381; op: WaveOp; a, b: n x 12 Fq raw limbs; out: n x 13 Fq canonical (slot 12 is the padding);
 // alias: 0 dst distinct, 1 dst == a, 2 dst == b (mul), 3 a == b == dst (mul)
 int dshim_wave_op(int curve, int op, const void* a, const void* b, void* out, size_t n, int alias) {
-    if (op < 0 || op >= W_NOPS || n == 0 || n > (1u << 20) || alias < 0 || alias > 3) return (int)hipErrorInvalidValue;
-    if (alias >= 2 && op != W_MUL) return (int)hipErrorInvalidValue;
-    if (alias != 0 && op == W_INV) return (int)hipErrorInvalidValue;
+    if (op < 0 || op >= W_NOPS || n == 0 || n > (1u << 20) || alias < 0 || alias > 3) return -(int)hipErrorInvalidValue;
+    if (alias >= 2 && op != W_MUL) return -(int)hipErrorInvalidValue;
+    if (alias != 0 && op == W_INV) return -(int)hipErrorInvalidValue;
     if (curve == 0) return wave_op<Bn254FqP>(op, a, b, out, n, alias);
     if (curve == 1) return wave_op<Bls381FqP>(op, a, b, out, n, alias);
-    return (int)hipErrorInvalidValue;
+    return -(int)hipErrorInvalidValue;
 }
 }

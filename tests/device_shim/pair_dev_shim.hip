@@ -15,19 +15,11 @@
 // product.  Every HIP status is returned to the caller; the shim allocates and frees its own buffers and never touches an
 // hk_ctx.
 #include "../../hekaton_system_amd/csrc/pairing_driver_impl.cuh"
-using namespace hk;
+#include "shim_common.cuh"
 
 enum F2qOp { Q_MUL = 0, Q_SQR, Q_MUL_BY_CHAR, Q_PSI, Q_NOPS };
 
-#if defined(HK_NO_ASM_MUL)
-constexpr int VARIANT = 0;
-#else
-constexpr int VARIANT = 1;
-#endif
-
-template <class P> __device__ __forceinline__ void ld_raw(Fp<P>& f, const u32* p) {
-    HK_UNROLL for (int i = 0; i < P::N; i++) f.v[i] = p[i];
-}
+// the quad-lane forms of shim_common.cuh's raw access: this shim alone includes endo.cuh's Fp2Q
 template <class P> __device__ __forceinline__ void ld_raw(Fp2Q<P>& f, const u32* p) { ld_raw(f.c0, p); ld_raw(f.c1, p + P::N); }
 template <class P> __device__ __forceinline__ void st_canon(u32* p, const Fp2Q<P>& f) {
     Fp<P> c0 = Fp<P>::canon(f.c0), c1 = Fp<P>::canon(f.c1);
@@ -62,13 +54,6 @@ k_f2q_op(int op, const u32* __restrict__ a, const u32* __restrict__ b, u32* __re
 // ---- host side ---------------------------------------------------------------------------------------------------
 namespace {
 
-struct DevBufs {
-    void* p[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~DevBufs() { for (void* q : p) if (q) (void)hipFree(q); }
-};
-
-#define SHIM_TRY(e) do { hipError_t st_ = (e); if (st_ != hipSuccess) return -(int)st_; } while (0)
-
 template <class P> size_t lds_tree() { return sizeof(WaveArea<P>) + 2 * WV_SLOT * sizeof(Fp<P>); }                 // as PairRun::run
 template <class P> size_t lds_fin() { return sizeof(WaveArea<P>) + WV_FINISH_SLOTS * WV_SLOT * sizeof(Fp<P>); }
 template <class P> PairSteps steps_of() { return pair_steps(PairLoopOf<P>::get(), TowerParams<P>::TWIST_IS_D); }
@@ -78,18 +63,13 @@ int f2q_op(int op, const void* a, const void* b, void* out, size_t n) {
     if (op == Q_MUL_BY_CHAR && !TowerParams<P>::TWIST_IS_D) return -(int)hipErrorInvalidValue;    // ark has it on BN only
     size_t in_bytes = n * 2 * sizeof(Fp<P>), out_bytes = n * 4 * (op >= Q_MUL_BY_CHAR ? 2 : 1) * 2 * sizeof(Fp<P>);
     DevBufs d;
-    SHIM_TRY(hipMalloc(&d.p[0], in_bytes));
-    SHIM_TRY(hipMalloc(&d.p[1], in_bytes));
-    SHIM_TRY(hipMalloc(&d.p[2], out_bytes));
-    SHIM_TRY(hipMemcpy(d.p[0], a, in_bytes, hipMemcpyHostToDevice));
-    SHIM_TRY(hipMemcpy(d.p[1], b ? b : a, in_bytes, hipMemcpyHostToDevice));
-    SHIM_TRY(hipMemset(d.p[2], 0xA5, out_bytes));
-    hipLaunchKernelGGL((k_f2q_op<P, VARIANT>), dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, 0, op, (const u32*)d.p[0],
-                       (const u32*)d.p[1], (u32*)d.p[2], (u32)n);
-    SHIM_TRY(hipGetLastError());
-    SHIM_TRY(hipDeviceSynchronize());
-    SHIM_TRY(hipMemcpy(out, d.p[2], out_bytes, hipMemcpyDeviceToHost));
-    return 0;
+    const u32 *da, *db;
+    u32* dout;
+    SHIM_GET(&da, in_bytes, a);
+    SHIM_GET(&db, in_bytes, b ? b : a);
+    SHIM_GET(&dout, out_bytes, nullptr);
+    hipLaunchKernelGGL((k_f2q_op<P, VARIANT>), dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, 0, op, da, db, dout, (u32)n);
+    return finish(out, dout, out_bytes);
 }
 
 // g2: n_r vectors of n affine G2 points (memory form) -> the raw lines [(b * S + s) * n + i], the grids of PairRun::run
@@ -99,22 +79,18 @@ int pair_lines(int form, const void* g2, unsigned n, unsigned n_r, void* lines_o
     u32 S = (u32)steps_of<P>().n;
     size_t in_bytes = (size_t)n_r * n * sizeof(Affine<Fp2<P>>), out_bytes = (size_t)n_r * S * n * sizeof(Line6<P>);
     DevBufs d;
-    SHIM_TRY(hipMalloc(&d.p[0], in_bytes));
-    SHIM_TRY(hipMalloc(&d.p[1], out_bytes));
-    SHIM_TRY(hipMemcpy(d.p[0], g2, in_bytes, hipMemcpyHostToDevice));
-    SHIM_TRY(hipMemset(d.p[1], 0xA5, out_bytes));                  // a line the kernel does not write is no line
-    Line6<P>* lines = (Line6<P>*)d.p[1];
+    const Affine<Fp2<P>>* pts;
+    Line6<P>* lines;
+    SHIM_GET(&pts, in_bytes, g2);
+    SHIM_GET(&lines, out_bytes, nullptr);                          // 0xA5: a line the kernel does not write is no line
     if (form == 1)
-        hipLaunchKernelGGL((k_pair_lines<Fp2Q<P>>), dim3((4 * n + 63) / 64, n_r), dim3(64), 0, 0,
-                           (const Affine<Fp2Q<P>>*)d.p[0], n, n_r, loop, S, lines);
+        hipLaunchKernelGGL((k_pair_lines<Fp2Q<P>>), dim3((4 * n + 63) / 64, n_r), dim3(64), 0, 0, (const Affine<Fp2Q<P>>*)pts, n,
+                           n_r, loop, S, lines);
     else
-        hipLaunchKernelGGL((k_pair_lines<Fp2<P>>), dim3((n + 63) / 64, n_r), dim3(64), 0, 0, (const Affine<Fp2<P>>*)d.p[0], n, n_r,
-                           loop, S, lines);
-    SHIM_TRY(hipGetLastError());
-    SHIM_TRY(hipDeviceSynchronize());
-    SHIM_TRY(hipMemcpy(lines_out, d.p[1], out_bytes, hipMemcpyDeviceToHost));
-    *S_out = S;
-    return 0;
+        hipLaunchKernelGGL((k_pair_lines<Fp2<P>>), dim3((n + 63) / 64, n_r), dim3(64), 0, 0, pts, n, n_r, loop, S, lines);
+    int st = finish(lines_out, lines, out_bytes);
+    if (st == 0) *S_out = S;
+    return st;
 }
 
 // lines: [n_r][S][n] raw lines, g1: [n_l][n] affine points; out: [count][S][ceil(n / c)] Fq12, count = n_pairs or n_l n_r
@@ -126,18 +102,15 @@ int pair_tree_lines(const void* lines, const void* g1, unsigned n, unsigned c, u
     size_t lb = (size_t)n_r * S * n * sizeof(Line6<P>), gb = (size_t)n_l * n * sizeof(Affine<Fp<P>>);
     size_t ob = (size_t)count * S * groups * sizeof(Fp12<P>);
     DevBufs d;
-    SHIM_TRY(hipMalloc(&d.p[0], lb));
-    SHIM_TRY(hipMalloc(&d.p[1], gb));
-    SHIM_TRY(hipMalloc(&d.p[2], ob));
-    SHIM_TRY(hipMemcpy(d.p[0], lines, lb, hipMemcpyHostToDevice));
-    SHIM_TRY(hipMemcpy(d.p[1], g1, gb, hipMemcpyHostToDevice));
-    SHIM_TRY(hipMemset(d.p[2], 0xA5, ob));
-    hipLaunchKernelGGL((k_pair_tree_lines<P>), dim3(groups, count * S), dim3(64), lds_tree<P>(), 0, (const Line6<P>*)d.p[0],
-                       (const Affine<Fp<P>>*)d.p[1], n, c, n_r, S, pl, (Fp12<P>*)d.p[2]);
-    SHIM_TRY(hipGetLastError());
-    SHIM_TRY(hipDeviceSynchronize());
-    SHIM_TRY(hipMemcpy(out, d.p[2], ob, hipMemcpyDeviceToHost));
-    return 0;
+    const Line6<P>* d_lines;
+    const Affine<Fp<P>>* d_g1;
+    Fp12<P>* d_out;
+    SHIM_GET(&d_lines, lb, lines);
+    SHIM_GET(&d_g1, gb, g1);
+    SHIM_GET(&d_out, ob, nullptr);
+    hipLaunchKernelGGL((k_pair_tree_lines<P>), dim3(groups, count * S), dim3(64), lds_tree<P>(), 0, d_lines, d_g1, n, c, n_r, S, pl,
+                       d_out);
+    return finish(out, d_out, ob);
 }
 
 // in: [count][n] canonical Fq12 -> out: [count][ceil(n / c)]
@@ -146,16 +119,12 @@ int pair_tree(const void* in, unsigned n, unsigned c, unsigned count, void* out)
     u32 groups = (n + c - 1) / c;
     size_t ib = (size_t)count * n * sizeof(Fp12<P>), ob = (size_t)count * groups * sizeof(Fp12<P>);
     DevBufs d;
-    SHIM_TRY(hipMalloc(&d.p[0], ib));
-    SHIM_TRY(hipMalloc(&d.p[1], ob));
-    SHIM_TRY(hipMemcpy(d.p[0], in, ib, hipMemcpyHostToDevice));
-    SHIM_TRY(hipMemset(d.p[1], 0xA5, ob));
-    hipLaunchKernelGGL((k_pair_tree<P>), dim3(groups, count), dim3(64), lds_tree<P>(), 0, (const Fp12<P>*)d.p[0], n, c,
-                       (Fp12<P>*)d.p[1]);
-    SHIM_TRY(hipGetLastError());
-    SHIM_TRY(hipDeviceSynchronize());
-    SHIM_TRY(hipMemcpy(out, d.p[1], ob, hipMemcpyDeviceToHost));
-    return 0;
+    const Fp12<P>* d_in;
+    Fp12<P>* d_out;
+    SHIM_GET(&d_in, ib, in);
+    SHIM_GET(&d_out, ob, nullptr);
+    hipLaunchKernelGGL((k_pair_tree<P>), dim3(groups, count), dim3(64), lds_tree<P>(), 0, d_in, n, c, d_out);
+    return finish(out, d_out, ob);
 }
 
 // L: [count][S] canonical Fq12 (S = the steps of the curve's loop) -> out: [count]
@@ -164,21 +133,17 @@ int pair_horner(const void* L, unsigned count, void* out) {
     PairSteps st = steps_of<P>();
     size_t ib = (size_t)count * st.n * sizeof(Fp12<P>), ob = (size_t)count * sizeof(Fp12<P>);
     DevBufs d;
-    SHIM_TRY(hipMalloc(&d.p[0], ib));
-    SHIM_TRY(hipMalloc(&d.p[1], ob));
-    SHIM_TRY(hipMemcpy(d.p[0], L, ib, hipMemcpyHostToDevice));
-    SHIM_TRY(hipMemset(d.p[1], 0xA5, ob));
-    hipLaunchKernelGGL((k_pair_horner<P>), dim3(count), dim3(64), lds_fin<P>(), 0, (const Fp12<P>*)d.p[0], st, (Fp12<P>*)d.p[1]);
-    SHIM_TRY(hipGetLastError());
-    SHIM_TRY(hipDeviceSynchronize());
-    SHIM_TRY(hipMemcpy(out, d.p[1], ob, hipMemcpyDeviceToHost));
-    return 0;
+    const Fp12<P>* d_in;
+    Fp12<P>* d_out;
+    SHIM_GET(&d_in, ib, L);
+    SHIM_GET(&d_out, ob, nullptr);
+    hipLaunchKernelGGL((k_pair_horner<P>), dim3(count), dim3(64), lds_fin<P>(), 0, d_in, st, d_out);
+    return finish(out, d_out, ob);
 }
 
 }  // namespace
 
 extern "C" {
-// 1 when the arithmetic was compiled with the inline assembly of mont_asm.h, 0 for the -DHK_NO_ASM_MUL build
 int dshim_pair_uses_asm(void) { return VARIANT; }
 // line steps of the curve's Miller loop (the S of the entry points below), 0 for an unknown curve
 unsigned dshim_pair_steps(int curve) {

@@ -6,18 +6,8 @@
 // The shim checks what the kernels take on trust (start monotone and within n W, every index below n, every rank below
 // n_dst, no more kept entries than the sub-list holds) and refuses anything else before a launch; it allocates and frees
 // its own buffers, returns every HIP status, and never touches an hk_ctx.
-#include <vector>
 #include "../../hekaton_system_amd/csrc/msm_driver_impl.cuh"
-using namespace hk;
-
-namespace {
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-#define SHIM_TRY(e) do { hipError_t st_ = (e); if (st_ != hipSuccess) return -(int)st_; } while (0)
-constexpr int SHIM_REFUSED = 1000;
-}  // namespace
+#include "shim_common.cuh"
 
 extern "C" {
 // plan words of the source plan (n scalars, window c, WP = 1, BN254 Fr) and the sub-list plan over n_dst of them:
@@ -69,11 +59,9 @@ int dshim_msm_sublist(unsigned c, unsigned batch, unsigned n, unsigned n_dst, co
     };
     Carve count;
     carve(count);
-    DevBuf d;
-    SHIM_TRY(hipMalloc(&d.p, count.off + 256));
-    SHIM_TRY(hipMemset(d.p, 0xA5, count.off + 256));               // no stage may rely on cleared scratch
+    DevBufs d;
     Carve real;
-    real.base = (char*)d.p;
+    SHIM_GET(&real.base, count.off + 256, nullptr);                // one block, 0xA5: no stage may rely on cleared scratch
     carve(real);
     SHIM_TRY(hipMemcpy(src.sorted, sorted_src, ss * batch * 4, hipMemcpyHostToDevice));
     SHIM_TRY(hipMemcpy(src.start, start_src, st * batch * 4, hipMemcpyHostToDevice));

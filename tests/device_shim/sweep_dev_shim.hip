@@ -5,8 +5,8 @@
 // test hands a kernel the table, the vectors, the form and the launch shape it wants and reads back what the kernel stored.
 // Test-only; never part of libhekaton.
 //
-// One translation unit per group (-DSWEEP_SHIM_GROUP=0..3: bn254 G1, bn254 G2, bls12-381 G1, bls12-381 G2, as
-// ec_dev_shim.hip), linked into one library; group 0's unit also holds the extern "C" entry points.  Built as shipped only
+// One translation unit per group (-DSHIM_GROUP=0..3: the ladder of shim_common.cuh, as ec_dev_shim.hip), linked into one
+// library; group 0's unit also holds the extern "C" entry points.  Built as shipped only
 // (see the header of the Makefile next to it).  The kernels keep their product names: the library is linked -Bsymbolic and
 // loaded RTLD_LOCAL, as the other shims are.
 //
@@ -14,63 +14,15 @@
 // as stored (x, y, zz, zzz; zz = 0: infinity).  Every HIP status is returned to the caller; the shim allocates and frees its
 // own buffers (scratch and outputs start as 0xA5) and never touches an hk_ctx.
 #include "../../hekaton_system_amd/csrc/msm_driver_impl.cuh"
-using namespace hk;
-
-#ifndef SWEEP_SHIM_GROUP
-#error "compile with -DSWEEP_SHIM_GROUP=0..3"
+#ifndef SHIM_GROUP
+#error "compile with -DSHIM_GROUP=0..3"
 #endif
-
-#if SWEEP_SHIM_GROUP == 0
-typedef CurveBn254 ShimCurve;
-typedef CurveBn254::Fq ShimF;
-#define SHIM_FN(name) sweep_shim_g0_##name
-#elif SWEEP_SHIM_GROUP == 1
-typedef CurveBn254 ShimCurve;
-typedef CurveBn254::Fq2 ShimF;
-#define SHIM_FN(name) sweep_shim_g1_##name
-#elif SWEEP_SHIM_GROUP == 2
-typedef CurveBls381 ShimCurve;
-typedef CurveBls381::Fq ShimF;
-#define SHIM_FN(name) sweep_shim_g2_##name
-#else
-typedef CurveBls381 ShimCurve;
-typedef CurveBls381::Fq2 ShimF;
-#define SHIM_FN(name) sweep_shim_g3_##name
-#endif
-typedef ShimCurve::Fr ShimFr;
+#define SHIM_PREFIX sweep_shim
+#include "shim_common.cuh"
 
 namespace {
 
 constexpr size_t SWEEP_MAX_N = 1u << 16;
-
-struct DevBufs {
-    enum { MAX = 8 };
-    void* p[MAX] = {};
-    int used = 0;
-    ~DevBufs() { for (int i = 0; i < used; i++) if (p[i]) (void)hipFree(p[i]); }
-};
-
-#define SHIM_TRY(e) do { hipError_t st_ = (e); if (st_ != hipSuccess) return -(int)st_; } while (0)
-
-// a device buffer of `bytes`: a copy of `src`, or 0xA5 where src is null
-static int dev_buf(DevBufs& d, const void* src, size_t bytes, void** out) {
-    if (d.used == DevBufs::MAX) return -(int)hipErrorInvalidValue;
-    void* q = nullptr;
-    SHIM_TRY(hipMalloc(&q, bytes ? bytes : 16));
-    d.p[d.used++] = q;
-    if (src) SHIM_TRY(hipMemcpy(q, src, bytes, hipMemcpyHostToDevice));
-    else SHIM_TRY(hipMemset(q, 0xA5, bytes ? bytes : 16));
-    *out = q;
-    return 0;
-}
-#define SHIM_BUF(var, type, src, bytes) type var; do { void* q_; int r_ = dev_buf(d, src, bytes, &q_); if (r_) return r_; var = (type)q_; } while (0)
-
-static int finish(void* out, const void* dev, size_t bytes) {
-    SHIM_TRY(hipGetLastError());
-    SHIM_TRY(hipDeviceSynchronize());
-    SHIM_TRY(hipMemcpy(out, dev, bytes, hipMemcpyDeviceToHost));
-    return 0;
-}
 
 template <class F> struct QuadOf { typedef F type; static constexpr bool has = false; };
 template <class P> struct QuadOf<Fp2<P>> { typedef Fp2Q<P> type; static constexpr bool has = true; };
@@ -79,8 +31,10 @@ template <class F>
 int fb_table(const void* base, void* table_out) {
     DevBufs d;
     const size_t tb = sizeof(Affine<F>) * FB_WINDOWS * 256;
-    SHIM_BUF(b, const Affine<F>*, base, sizeof(Affine<F>));
-    SHIM_BUF(t, Affine<F>*, nullptr, tb);
+    const Affine<F>* b;
+    Affine<F>* t;
+    SHIM_GET(&b, sizeof(Affine<F>), base);
+    SHIM_GET(&t, tb, nullptr);
     hipLaunchKernelGGL((k_fb_table<F>), dim3(FB_WINDOWS * 256 / 64), dim3(64), 0, 0, b, t);
     return finish(table_out, t, tb);
 }
@@ -88,9 +42,12 @@ int fb_table(const void* base, void* table_out) {
 template <class Fr, class F>
 int fb_mul(const void* table, const void* scalars, int is_mont, unsigned n, void* out) {
     DevBufs d;
-    SHIM_BUF(t, const Affine<F>*, table, sizeof(Affine<F>) * FB_WINDOWS * 256);
-    SHIM_BUF(s, const Fr*, scalars, (size_t)n * sizeof(Fr));
-    SHIM_BUF(o, XYZZ<F>*, nullptr, (size_t)n * sizeof(XYZZ<F>));
+    const Affine<F>* t;
+    const Fr* s;
+    XYZZ<F>* o;
+    SHIM_GET(&t, sizeof(Affine<F>) * FB_WINDOWS * 256, table);
+    SHIM_GET(&s, (size_t)n * sizeof(Fr), scalars);
+    SHIM_GET(&o, (size_t)n * sizeof(XYZZ<F>), nullptr);
     hipLaunchKernelGGL((k_fb_mul<Fr, F>), dim3((n + 63) / 64), dim3(64), 0, 0, t, s, is_mont, n, o);
     return finish(out, o, (size_t)n * sizeof(XYZZ<F>));
 }
@@ -98,9 +55,12 @@ int fb_mul(const void* table, const void* scalars, int is_mont, unsigned n, void
 template <class Fr, class F>
 int lincomb(const void* vecs, const void* coeffs, unsigned k, unsigned n, void* out) {
     DevBufs d;
-    SHIM_BUF(v, const Affine<F>*, vecs, (size_t)k * n * sizeof(Affine<F>));
-    SHIM_BUF(c, const Fr*, coeffs, (size_t)k * sizeof(Fr));
-    SHIM_BUF(o, XYZZ<F>*, nullptr, (size_t)n * sizeof(XYZZ<F>));
+    const Affine<F>* v;
+    const Fr* c;
+    XYZZ<F>* o;
+    SHIM_GET(&v, (size_t)k * n * sizeof(Affine<F>), vecs);
+    SHIM_GET(&c, (size_t)k * sizeof(Fr), coeffs);
+    SHIM_GET(&o, (size_t)n * sizeof(XYZZ<F>), nullptr);
     LincombVecs<F> lv;
     for (unsigned j = 0; j < (unsigned)LINCOMB_MAX; j++) lv.v[j] = j < k ? v + (size_t)j * n : nullptr;
     hipLaunchKernelGGL((k_points_lincomb<Fr, F>), dim3((n + 63) / 64), dim3(64), 0, 0, lv, c, k, n, o);
@@ -111,13 +71,17 @@ int lincomb(const void* vecs, const void* coeffs, unsigned k, unsigned n, void* 
 template <class Fr, class F>
 int mul_each(int kind, const void* pts, const void* scalars, unsigned n, void* out) {
     DevBufs d;
-    SHIM_BUF(p, const Affine<F>*, pts, (size_t)n * sizeof(Affine<F>));
-    SHIM_BUF(s, const Fr*, scalars, (size_t)n * sizeof(Fr));
-    SHIM_BUF(o, XYZZ<F>*, nullptr, (size_t)n * sizeof(XYZZ<F>));
+    const Affine<F>* p;
+    const Fr* s;
+    XYZZ<F>* o;
+    SHIM_GET(&p, (size_t)n * sizeof(Affine<F>), pts);
+    SHIM_GET(&s, (size_t)n * sizeof(Fr), scalars);
+    SHIM_GET(&o, (size_t)n * sizeof(XYZZ<F>), nullptr);
     if (kind == 0) {
         hipLaunchKernelGGL((k_scalar_mul_each<Fr, F>), dim3((n + 63) / 64), dim3(64), 0, 0, p, s, n, o);
     } else {
-        SHIM_BUF(tab, XYZZ<F>*, nullptr, ((size_t)1 << EndoOf<F>::K) * n * sizeof(XYZZ<F>));
+        XYZZ<F>* tab;
+        SHIM_GET(&tab, ((size_t)1 << EndoOf<F>::K) * n * sizeof(XYZZ<F>), nullptr);
         hipLaunchKernelGGL((k_scalar_mul_endo<Fr, F>), dim3((n + 63) / 64), dim3(64), 0, 0, p, s, n, EndoOf<F>::split(), tab, o);
     }
     return finish(out, o, (size_t)n * sizeof(XYZZ<F>));
@@ -126,11 +90,14 @@ int mul_each(int kind, const void* pts, const void* scalars, unsigned n, void* o
 template <class Fr, class F>
 int fold_endo(const void* lo, const void* hi, const void* coeffs, unsigned neg, unsigned n, void* out) {
     DevBufs d;
-    SHIM_BUF(l, const Affine<F>*, lo, (size_t)n * sizeof(Affine<F>));
-    SHIM_BUF(h, const Affine<F>*, hi, (size_t)n * sizeof(Affine<F>));
-    SHIM_BUF(c, const Fr*, coeffs, (size_t)EndoOf<F>::K * sizeof(Fr));
-    SHIM_BUF(tab, XYZZ<F>*, nullptr, ((size_t)1 << EndoOf<F>::K) * n * sizeof(XYZZ<F>));
-    SHIM_BUF(o, XYZZ<F>*, nullptr, (size_t)n * sizeof(XYZZ<F>));
+    const Affine<F> *l, *h;
+    const Fr* c;
+    XYZZ<F> *tab, *o;
+    SHIM_GET(&l, (size_t)n * sizeof(Affine<F>), lo);
+    SHIM_GET(&h, (size_t)n * sizeof(Affine<F>), hi);
+    SHIM_GET(&c, (size_t)EndoOf<F>::K * sizeof(Fr), coeffs);
+    SHIM_GET(&tab, ((size_t)1 << EndoOf<F>::K) * n * sizeof(XYZZ<F>), nullptr);
+    SHIM_GET(&o, (size_t)n * sizeof(XYZZ<F>), nullptr);
     hipLaunchKernelGGL((k_points_fold_endo<Fr, F>), dim3((n + 63) / 64), dim3(64), 0, 0, l, h, c, neg, n, tab, o);
     return finish(out, o, (size_t)n * sizeof(XYZZ<F>));
 }
@@ -159,12 +126,15 @@ int mul_split(int quad, int uniform, const void* lo, const void* pts, const void
     if (quad && !QuadOf<F>::has) return -(int)hipErrorNotSupported;
     DevBufs d;
     const unsigned n_pts = pts_mod ? pts_mod : n;
-    SHIM_BUF(l, const Affine<F>*, lo, (size_t)vectors * n * sizeof(Affine<F>));
-    SHIM_BUF(p, const Affine<F>*, pts, (size_t)vectors * n_pts * sizeof(Affine<F>));
-    SHIM_BUF(s, const Fr*, scalars, (size_t)(uniform ? (unsigned)EndoOf<F>::K : n) * sizeof(Fr));
-    SHIM_BUF(tab, void*, nullptr, (size_t)vectors * split_tab_bytes<F>(n));
-    SHIM_BUF(o, XYZZ<F>*, nullptr, (size_t)vectors * n * sizeof(XYZZ<F>));
-    if (!lo) l = nullptr;
+    const Affine<F> *l = nullptr, *p;
+    const Fr* s;
+    void* tab;
+    XYZZ<F>* o;
+    if (lo) SHIM_GET(&l, (size_t)vectors * n * sizeof(Affine<F>), lo);
+    SHIM_GET(&p, (size_t)vectors * n_pts * sizeof(Affine<F>), pts);
+    SHIM_GET(&s, (size_t)(uniform ? (unsigned)EndoOf<F>::K : n) * sizeof(Fr), scalars);
+    SHIM_GET(&tab, (size_t)vectors * split_tab_bytes<F>(n), nullptr);
+    SHIM_GET(&o, (size_t)vectors * n * sizeof(XYZZ<F>), nullptr);
     if (quad && uniform) launch_split<Fr, F, Q, true>(l, p, n_pts, s, neg_all, n, pts_mod, vectors, scalars_mont, tab, o);
     else if (quad) launch_split<Fr, F, Q, false>(l, p, n_pts, s, neg_all, n, pts_mod, vectors, scalars_mont, tab, o);
     else if (uniform) launch_split<Fr, F, F, true>(l, p, n_pts, s, neg_all, n, pts_mod, vectors, scalars_mont, tab, o);
@@ -175,8 +145,10 @@ int mul_split(int quad, int uniform, const void* lo, const void* pts, const void
 template <class F>
 int points_sum(const void* in, unsigned n, void* out) {
     DevBufs d;
-    SHIM_BUF(i, const XYZZ<F>*, in, (size_t)n * sizeof(XYZZ<F>));
-    SHIM_BUF(o, XYZZ<F>*, nullptr, sizeof(XYZZ<F>));
+    const XYZZ<F>* i;
+    XYZZ<F>* o;
+    SHIM_GET(&i, (size_t)n * sizeof(XYZZ<F>), in);
+    SHIM_GET(&o, sizeof(XYZZ<F>), nullptr);
     hipLaunchKernelGGL((k_points_sum<F>), dim3(1), dim3(PointsSum<F>::THREADS), 0, 0, i, n, o);
     return finish(out, o, sizeof(XYZZ<F>));
 }
@@ -184,8 +156,10 @@ int points_sum(const void* in, unsigned n, void* out) {
 template <class F>
 int points_sum_seg(const void* in, unsigned seg, unsigned batch, void* out) {
     DevBufs d;
-    SHIM_BUF(i, const XYZZ<F>*, in, (size_t)seg * batch * sizeof(XYZZ<F>));
-    SHIM_BUF(o, XYZZ<F>*, nullptr, (size_t)batch * sizeof(XYZZ<F>));
+    const XYZZ<F>* i;
+    XYZZ<F>* o;
+    SHIM_GET(&i, (size_t)seg * batch * sizeof(XYZZ<F>), in);
+    SHIM_GET(&o, (size_t)batch * sizeof(XYZZ<F>), nullptr);
     hipLaunchKernelGGL((k_points_sum_seg<F>), dim3(batch), dim3(64), 0, 0, i, seg, o);
     return finish(out, o, (size_t)batch * sizeof(XYZZ<F>));
 }
@@ -220,7 +194,7 @@ int SHIM_FN(split_elems)(int quad) {
 int SHIM_FN(split_nd)() { return SplitDigits<ShimF>::ND; }
 int SHIM_FN(split_steps)() { return EndoOf<ShimF>::STEPS; }
 
-#if SWEEP_SHIM_GROUP == 0
+#if SHIM_GROUP == 0
 #define SHIM_DECL(g)                                                                                                        \
     int sweep_shim_g##g##_fb_table(const void*, void*);                                                                    \
     int sweep_shim_g##g##_fb_mul(const void*, const void*, int, unsigned, void*);                                          \
@@ -236,15 +210,6 @@ int SHIM_FN(split_steps)() { return EndoOf<ShimF>::STEPS; }
     int sweep_shim_g##g##_split_nd();                                                                                      \
     int sweep_shim_g##g##_split_steps();
 SHIM_DECL(1) SHIM_DECL(2) SHIM_DECL(3)
-
-#define SHIM_DISPATCH(group, call)                                                                                          \
-    switch (group) {                                                                                                        \
-        case 0: return sweep_shim_g0_##call;                                                                                \
-        case 1: return sweep_shim_g1_##call;                                                                                \
-        case 2: return sweep_shim_g2_##call;                                                                                \
-        case 3: return sweep_shim_g3_##call;                                                                                \
-    }                                                                                                                       \
-    return -(int)hipErrorInvalidValue;
 
 static bool n_ok(unsigned n) { return n != 0 && n <= SWEEP_MAX_N; }
 

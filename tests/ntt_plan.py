@@ -4,7 +4,8 @@ tests/test_ntt_device_gpu.py."""
 import os
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import host_build
+
 DEFAULT_TILE_LOG, DEFAULT_UPPER_MAX = 11, 6
 
 
@@ -12,8 +13,7 @@ def load(build_dir):
     """-> (knobs, plans): knobs[raw tile_log, raw upper_max] = (tile_log, upper_max);
     plans[logn, tile_log, raw upper_max] = (upper_max, [(lo, nst, cols_bits), ...]) in DIT order"""
     exe = os.path.join(str(build_dir), "ntt_plan_driver")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-o", exe,
-                           os.path.join(ROOT, "tests", "host_shim", "ntt_plan_driver.cpp")])
+    host_build.build("ntt_plan_driver.cpp", exe, "-O1", "-Wall", "-Werror")
     knobs, plans = {}, {}
     for line in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines():
         f = line.split()

@@ -16,9 +16,10 @@ import pytest
 from hekaton_system_amd import aggregation, capi, tipa
 from hekaton_system_amd.cp_groth16 import CURVE_PARAMS, FrCodec
 from tests import agg_scalars_cases as cases
+from tests import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM_SRC = os.path.join(ROOT, "tests", "host_shim", "agg_scalars_shim.cpp")
+SHIM_SRC = "agg_scalars_shim.cpp"  # under tests/host_shim
 
 
 def test_symbols_declared_listed_exported():
@@ -236,8 +237,8 @@ def test_prove_helpers_device_by_default_host_under_the_switch(curve, fake_buffe
 def shim(tmp_path_factory):
     """csrc/agg_scalars.cuh compiled for the host (g++) - the source the kernels run."""
     out = str(tmp_path_factory.mktemp("shim") / "agg_scalars_shim.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", out, SHIM_SRC])
-    lib = C.CDLL(out)
+    host_build.build(SHIM_SRC, out, "-O2", *host_build.SHARED)
+    lib = host_build.load(out)
     sz, vp, i = C.c_size_t, C.c_void_p, C.c_int
     lib.shim_scalar_powers.argtypes = [i, vp, sz, sz, vp]
     lib.shim_ipa_quotient.argtypes = [i, vp, sz, vp, vp, sz, vp]
@@ -291,7 +292,7 @@ def test_standalone_program_is_clean_under_the_sanitizers(tmp_path):
     outs = []
     for tag, flags in (("plain", ["-O1"]), ("san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
         exe = str(tmp_path / ("agg_scalars_" + tag))
-        subprocess.check_call(["g++", "-std=c++17", "-DAGG_SCALARS_MAIN"] + flags + ["-o", exe, SHIM_SRC])
+        host_build.build(SHIM_SRC, exe, "-DAGG_SCALARS_MAIN", *flags)
         r = subprocess.run([exe], capture_output=True, text=True)
         assert r.returncode == 0 and r.stderr == "", (tag, r.stderr[-2000:])
         outs.append(r.stdout)

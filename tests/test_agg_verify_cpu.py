@@ -21,9 +21,10 @@ from oracle.pyref import curve as pycurve
 from oracle.pyref.codec import Codec
 from oracle.pyref.params import CURVES as PARAMS
 from tests import class_sums_cases as cases
+from tests import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM_SRC = os.path.join(ROOT, "tests", "host_shim", "class_sums_shim.cpp")
+SHIM_SRC = "class_sums_shim.cpp"  # under tests/host_shim
 
 
 def test_symbol_declared_listed_exported():
@@ -102,8 +103,8 @@ def test_context_wrapper_marshals_its_arguments(curve):
 def shim(tmp_path_factory):
     """csrc/class_sums.cuh compiled for the host (g++) - the source the kernels run."""
     out = str(tmp_path_factory.mktemp("shim") / "class_sums_shim.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", out, SHIM_SRC])
-    lib = C.CDLL(out)
+    host_build.build(SHIM_SRC, out, "-O2", *host_build.SHARED)
+    lib = host_build.load(out)
     lib.shim_class_power_sums.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     lib.shim_class_power_sums.restype = C.c_int
     return lib
@@ -140,7 +141,7 @@ def test_standalone_program_is_clean_under_the_sanitizers(tmp_path):
     outs = []
     for tag, flags in (("plain", ["-O1"]), ("san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
         exe = str(tmp_path / ("class_sums_" + tag))
-        subprocess.check_call(["g++", "-std=c++17", "-DCLASS_SUMS_MAIN"] + flags + ["-o", exe, SHIM_SRC])
+        host_build.build(SHIM_SRC, exe, "-DCLASS_SUMS_MAIN", *flags)
         r = subprocess.run([exe], capture_output=True, text=True)
         assert r.returncode == 0 and r.stderr == "", (tag, r.stderr[-2000:])
         outs.append(r.stdout)

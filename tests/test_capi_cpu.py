@@ -3,7 +3,6 @@ without a GPU (no CPU fallback), and its generated constants agree with the orac
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ from hekaton_system_amd import capi
 from oracle.pyref.params import CURVES
 from oracle.pyref.codec import Codec
 from tests import golden_util as gu
+from tests import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -62,9 +62,8 @@ def test_generated_params_match_oracle():
 def shim(tmp_path_factory):
     """The product's field.cuh / ec.cuh compiled for the host (g++) — same source the kernels run."""
     out = str(tmp_path_factory.mktemp("shim") / "field_shim.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", out,
-                           os.path.join(ROOT, "tests", "host_shim", "field_shim.cpp")])
-    return ctypes.CDLL(out)
+    host_build.build("field_shim.cpp", out, "-O2", *host_build.SHARED)
+    return host_build.load(out)
 
 
 def test_product_field_and_curve_arithmetic_vs_golden(shim):
@@ -133,12 +132,10 @@ def test_msm_window_count_is_the_smallest_that_holds_every_scalar(tmp_path_facto
     SMALLEST such W that is >= the always-sufficient ceil((bits+2)/c) - 1, for every window size either curve can get:
     16 windows at c = 16 on both (BLS12-381's 17th digit would always be zero), and never a W that lets s' overflow."""
     import ctypes
-    import subprocess
     from oracle.pyref.params import CURVES
     out = str(tmp_path_factory.mktemp("shim") / "field_shim.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", out,
-                           os.path.join(ROOT, "tests", "host_shim", "field_shim.cpp")])
-    lib = ctypes.CDLL(out)
+    host_build.build("field_shim.cpp", out, "-O2", *host_build.SHARED)
+    lib = host_build.load(out)
     buf = (ctypes.c_uint * 16)()
     for cid, name, bits in ((0, "bn254", 254), (1, "bls12_381", 255)):
         r = CURVES[name].r

@@ -11,6 +11,8 @@ from hekaton_system_amd.endo import eigenvalue, psi4
 from oracle.pyref import curve
 from oracle.pyref.params import CURVES
 
+from tests import host_build
+
 
 def _f2m(a, b, q):
     return ((a[0] * b[0] - a[1] * b[1]) % q, (a[0] * b[1] + a[1] * b[0]) % q)
@@ -94,15 +96,11 @@ def test_device_side_split_recombines_and_is_short(name, tmp_path_factory):
     and psi (4 parts), sum_j (+-)|k_j| lambda^j = c mod r for edge and random scalars, and the parts fit the kernel's fixed
     chain lengths (131 / 68 doublings)."""
     import ctypes
-    import os
-    import subprocess
     import numpy as np
     from hekaton_system_amd.endo import phi2
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = str(tmp_path_factory.mktemp("shim") / "field_shim.so")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-o", out,
-                           os.path.join(root, "tests", "host_shim", "field_shim.cpp")])
-    lib = ctypes.CDLL(out)
+    host_build.build("field_shim.cpp", out, "-O1", *host_build.SHARED)
+    lib = host_build.load(out)
     lib.shim_endo_decompose.restype = ctypes.c_uint
     cid = 0 if name == "bn254" else 1
     r = CURVES[name].r
@@ -128,15 +126,11 @@ def test_one_lane_of_the_split_kernel_multiplies_correctly(name, tmp_path_factor
     multiple, in G1 (parts up to 131 bits) and G2 (68 bits), for the magnitudes at the digit boundaries (0, 7, 8, 9, 15, 16,
     0x88..8, all-ones) and random ones; infinity in, infinity out."""
     import ctypes
-    import os
-    import subprocess
     import numpy as np
     from oracle.pyref.codec import Codec
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = str(tmp_path_factory.mktemp("shim") / "field_shim.so")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-o", out,
-                           os.path.join(root, "tests", "host_shim", "field_shim.cpp")])
-    lib = ctypes.CDLL(out)
+    host_build.build("field_shim.cpp", out, "-O1", *host_build.SHARED)
+    lib = host_build.load(out)
     cp = CURVES[name]
     cd = Codec(cp)
     rnd = random.Random(31)

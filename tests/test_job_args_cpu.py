@@ -8,6 +8,8 @@ import subprocess
 
 import pytest
 
+from tests import host_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, ARG = "HK_OK", "HK_ERR_ARG"
 
@@ -31,8 +33,7 @@ EXPECTED = {
 
 def _build(tmp, name, *flags):
     out = str(tmp / name)
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", *flags, "-o", out,
-                           os.path.join(ROOT, "tests", "host_shim", "job_args_driver.cpp")])
+    host_build.build("job_args_driver.cpp", out, "-O1", "-g", "-Wall", "-Werror", *flags)
     return out
 
 

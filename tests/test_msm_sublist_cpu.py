@@ -2,12 +2,12 @@
 compiled for the host: tests/host_shim/msm_sublist_driver.cpp).  A sub-list reuses the digits of the assignment's one sort,
 so its plan shares c, W, WP, F, B, NB, K and kconst with plan_z even where a vector of its own length would pick another
 window; n, gshift and the lane counts are its own.  The rank table is the inverse of the index list."""
-import os
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import host_build
+
 NONE = 0xFFFFFFFF
 FIELDS = ("c", "W", "WP", "F", "B", "NB", "K", "n", "gshift", "chunk", "T0", "n_levels", "kconst")
 # (n, n_sub): the default bench class and its A / B lists, the smallest class that compacts, a sub-list far shorter than its
@@ -29,8 +29,7 @@ def pick_c_tables(n, bits=254):
 @pytest.fixture(scope="module")
 def out(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("msm_sublist") / "msm_sublist_driver")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-o", exe,
-                           os.path.join(ROOT, "tests", "host_shim", "msm_sublist_driver.cpp")])
+    host_build.build("msm_sublist_driver.cpp", exe, "-O1", "-Wall", "-Werror")
     args = [str(v) for n, k in SHAPES for v in (n, pick_c_tables(n), k)]
     plans, rules, rank = {}, {}, None
     for line in subprocess.run([exe] + args, capture_output=True, text=True, check=True).stdout.splitlines():

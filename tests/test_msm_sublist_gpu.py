@@ -9,39 +9,22 @@ kept entries as it lay before the call.  n <= 4096 scalars and c = 4 .. 8, so th
 Part 2: hk_prove on a key whose A and B queries both run compacted, and on one where neither meets the rule, against the
 C oracle's proof of the same inputs, byte for byte.
 """
-import ctypes
-import os
-
 import numpy as np
 import pytest
 
+from tests import dev_shim as ds
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NONE = 0xFFFFFFFF
 TILE = 1024
 SENTINEL = 0xA5A5A5A5
-_lib = []
-
-
-def _shim():
-    if not _lib:
-        path = os.path.join(ROOT, "hekaton_system_amd", "lib", "libsublist_dev_shim.so")
-        assert os.path.exists(path), "build the device shim first (python __graft_entry__.py)"
-        lib = ctypes.CDLL(path)
-        up, ui = ctypes.POINTER(ctypes.c_uint), ctypes.c_uint
-        lib.dshim_sublist_plan.argtypes = [ui, ui, ui, up]
-        lib.dshim_msm_sublist.argtypes = [ui, ui, ui, ui] + [ctypes.c_void_p] * 5
-        _lib.append(lib)
-    return _lib[0]
 
 
 class Plan:
     def __init__(self, c, n, n_dst):
-        out = (ctypes.c_uint * 7)()
-        assert _shim().dshim_sublist_plan(c, n, n_dst, out) == 0
         self.c, self.n, self.n_dst = c, n, n_dst
-        self.W, self.NB, self.gs_src, self.gs_dst, self.stride_src, self.stride_dst, self.tiles = list(out)
+        self.W, self.NB, self.gs_src, self.gs_dst, self.stride_src, self.stride_dst, self.tiles = ds.load_sublist().plan(c, n, n_dst)
         assert self.NB == 1 << (c - 1) and self.stride_src == n * self.W + 1 and self.stride_dst == n_dst * self.W + 1
         assert self.tiles == n * self.W // TILE + 1
 
@@ -84,9 +67,7 @@ def run_sublist(plan, lists, rank):
     dst = np.full(batch * plan.stride_dst, SENTINEL, dtype=np.uint32)
     dst_st = np.full(batch * (plan.NB + 1), SENTINEL, dtype=np.uint32)
     rank = np.ascontiguousarray(rank, dtype=np.uint32)
-    rc = _shim().dshim_msm_sublist(plan.c, batch, plan.n, plan.n_dst, src.ctypes.data, st.ctypes.data, rank.ctypes.data,
-                                   dst.ctypes.data, dst_st.ctypes.data)
-    assert rc == 0, "dshim_msm_sublist: status %d" % rc
+    ds.load_sublist().sublist(plan.c, batch, plan.n, plan.n_dst, src, st, rank, dst, dst_st)
     return [(dst[b * plan.stride_dst:(b + 1) * plan.stride_dst], dst_st[b * (plan.NB + 1):(b + 1) * (plan.NB + 1)])
             for b in range(batch)]
 

@@ -3,25 +3,23 @@ source the kernels run; the library itself never runs it on the CPU) against the
 (oracle/pyref/pairing.py): Fq12 ring operations, Frobenius maps, the final-exponentiation chain, and whole
 multi-pairings with infinity members, on both curves."""
 import ctypes
-import os
 import random
-import subprocess
 
 import pytest
 
 from oracle.pyref import curve, pairing
 from oracle.pyref.params import CURVES
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import host_build
+
 CID = {"bn254": 0, "bls12_381": 1}
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("shim") / "field_shim.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", out,
-                           os.path.join(ROOT, "tests", "host_shim", "field_shim.cpp")])
-    lib = ctypes.CDLL(out)
+    host_build.build("field_shim.cpp", out, "-O2", *host_build.SHARED)
+    lib = host_build.load(out)
     lib.shim_multi_pairing.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p]
     return lib
 

@@ -16,10 +16,11 @@ from hekaton_system_amd import capi
 from hekaton_system_amd.ark_serialize import ArkCodec, ProvingKeys, SerializationError
 from hekaton_system_amd.cp_groth16 import CommitterKey, ProvingKey, VerifyingKey
 from oracle.pyref.params import CURVES
+from tests import host_build
 from tests import point_codec_cases as pc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM_SRC = os.path.join(ROOT, "tests", "host_shim", "point_codec_shim.cpp")
+SHIM_SRC = "point_codec_shim.cpp"  # under tests/host_shim
 SYMBOLS = ("hk_field_sqrt", "hk_points_decompress_g1", "hk_points_decompress_g2", "hk_points_compress_g1",
            "hk_points_compress_g2")
 CURVE_ID = {"bn254": 0, "bls12_381": 1}
@@ -103,8 +104,8 @@ def test_point_families_are_what_they_say(curve, group):
 def shim(tmp_path_factory):
     """csrc/point_codec.cuh compiled for the host (g++) - the source the kernels run."""
     out = str(tmp_path_factory.mktemp("shim") / "point_codec_shim.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", out, SHIM_SRC])
-    lib = C.CDLL(out)
+    host_build.build(SHIM_SRC, out, "-O2", *host_build.SHARED)
+    lib = host_build.load(out)
     sz, vp, i = C.c_size_t, C.c_void_p, C.c_int
     lib.shim_field_sqrt.argtypes = [i, i, vp, sz, vp, vp]
     lib.shim_points_decompress.argtypes = [i, i, vp, vp, sz, vp, vp]
@@ -166,7 +167,7 @@ def test_standalone_program_is_clean_under_the_sanitizers(tmp_path):
     outs = []
     for tag, flags in (("plain", ["-O1"]), ("san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])):
         exe = str(tmp_path / ("point_codec_" + tag))
-        subprocess.check_call(["g++", "-std=c++17", "-DPOINT_CODEC_MAIN"] + flags + ["-o", exe, SHIM_SRC])
+        host_build.build(SHIM_SRC, exe, "-DPOINT_CODEC_MAIN", *flags)
         r = subprocess.run([exe], capture_output=True, text=True)
         assert r.returncode == 0 and r.stderr == "", (tag, r.stderr[-2000:])
         outs.append(r.stdout)

@@ -10,14 +10,15 @@ import pytest
 
 from hekaton_system_amd import capi
 
+from tests import host_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("coalesce") / "coalesce_driver")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=thread", "-pthread", "-o", out,
-                           os.path.join(ROOT, "tests", "host_shim", "coalesce_driver.cpp")])
+    host_build.build("coalesce_driver.cpp", out, "-O1", "-g", "-fsanitize=thread", "-pthread")
     return out
 
 

@@ -4,25 +4,21 @@ meets its own condition in discrete logs with exactly the intended output at inf
 directed scalars have the shapes the cases rely on (csrc/endo.cuh's endo_decompose, host-compiled), and the exponent
 reference equals the oracle's MSM-based prover and committer point for point."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle.pyref import groth16
+from tests import host_build
 from tests import prove_edges as pe
 from tests.util import oracle_commit, oracle_prove
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("shim") / "field_shim.so")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-o", out,
-                           os.path.join(ROOT, "tests", "host_shim", "field_shim.cpp")])
-    lib = ctypes.CDLL(out)
+    host_build.build("field_shim.cpp", out, "-O1", *host_build.SHARED)
+    lib = host_build.load(out)
     lib.shim_endo_decompose.restype = ctypes.c_uint
     return lib
 

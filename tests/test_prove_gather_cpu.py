@@ -10,14 +10,13 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import host_build
 
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("gather") / "coalesce_gather_driver")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=thread", "-pthread", "-o", out,
-                           os.path.join(ROOT, "tests", "host_shim", "coalesce_gather_driver.cpp")])
+    host_build.build("coalesce_gather_driver.cpp", out, "-O1", "-g", "-fsanitize=thread", "-pthread")
     return out
 
 

@@ -8,7 +8,6 @@ import hashlib
 import os
 import random
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +15,8 @@ import pytest
 from hekaton_system_amd import capi, sha_circuit
 from hekaton_system_amd.cp_groth16 import FrCodec
 from hekaton_system_amd.sha_circuit import INNER_HASH_SIZE, ShaMerkleJob, iterated_sha256, node_hash_field
+
+from tests import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("hk_sha_tree", "hk_sha_tree_inputs")
@@ -106,9 +107,8 @@ def test_context_sha_tree_inputs_marshals_its_arguments():
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("shim") / "sha256_shim.so")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-o", out,
-                           os.path.join(ROOT, "tests", "host_shim", "sha256_shim.cpp")])
-    return C.CDLL(out)
+    host_build.build("sha256_shim.cpp", out, "-O1", *host_build.SHARED)
+    return host_build.load(out)
 
 
 def _messages(nbytes, seed):

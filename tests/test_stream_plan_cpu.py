@@ -1,20 +1,19 @@
 """CPU: the prove-lane stream plan (hekaton_system_amd/csrc/stream_plan.h).  A context's
 PROVE_COALESCE_RUNNING prove lanes get s = clamp(Q / K, 1, 5) streams each out of the Q hardware queues, and a chunk's five
 roles (main, B1, B2, L, H) fold onto those s streams by a fixed table."""
-import os
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import host_build
+
 ROLES = ("main", "B1", "B2", "L", "H")
 
 
 @pytest.fixture(scope="module")
 def plan(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("stream_plan") / "stream_plan_driver")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-o", exe,
-                           os.path.join(ROOT, "tests", "host_shim", "stream_plan_driver.cpp")])
+    host_build.build("stream_plan_driver.cpp", exe, "-O1", "-Wall", "-Werror")
     s, maps = {}, {}
     for line in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines():
         f = line.split()

@@ -3,16 +3,13 @@ tables make the digit walk double or cancel where intended, the "equal partial s
 the LDS tree, the K-lane form reads a magnitude whole up to 0x77..7 and no further (host mirror of one lane:
 tests/host_shim/field_shim.cpp), and the discrete-log reference agrees with the oracle's own add / mul / msm."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import host_build
 from tests import msm_edges as me
 from tests import sweep_edges as se
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("gid", range(4))
@@ -111,9 +108,8 @@ def test_equal_partial_sums_meet_p_eq_q_at_every_tree_level(gid):
 @pytest.fixture(scope="module")
 def host_shim(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("shim") / "field_shim.so")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", "-o", out,
-                           os.path.join(ROOT, "tests", "host_shim", "field_shim.cpp")])
-    return ctypes.CDLL(out)
+    host_build.build("field_shim.cpp", out, "-O1", *host_build.SHARED)
+    return host_build.load(out)
 
 
 def _split_mul(lib, gid, pb, m):
