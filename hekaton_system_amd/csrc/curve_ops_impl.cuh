@@ -166,7 +166,7 @@ struct Ops final : CurveOps {
     hk_status commit(hk_ctx*, const hk_pk*, size_t, const void*, size_t, const void*, void*) override;
     hk_status commit_batch(hk_ctx*, const hk_pk*, size_t, const void*, size_t, const void*, size_t, void*) override;
     hk_status prove_batch(hk_ctx*, const hk_pk*, size_t, size_t, const ProveRow*, size_t) override;
-    static size_t finish_private_bytes();      // k_finish_ab / k_finish_c
+    static size_t finish_private_bytes();      // k_finish_ab / k_finish_c, and the kernels of h_basis.cuh
     // verify.cuh
     hk_status vk_prepare(hk_ctx* ctx, const hk_vk_desc* d, hk_vk** out) override { return Verify::vk_prepare(ctx, d, out); }
     void vk_free(hk_vk* vk) override { Verify::vk_free(vk); }

@@ -274,6 +274,28 @@ struct QapHost {
         HK_HIP(hipGetLastError());
         return HK_OK;
     }
+    // The map for a key whose H query is held in the coset's evaluation basis (h_basis.cuh): four transforms, no C pass.
+    // ab: 2*m Fr scratch (a | b).  On return a[j] = m^2 a'_j b'_j, j < m in NATURAL order: the unscaled inverse transform
+    // leaves m times the coefficients, the forward transform keeps that factor on each of a' and b', and the key's table
+    // G^ / m^2 takes the m^2 back - no scaling product here.  The C part of h is linear in z and rides the L query.
+    static hk_status run_eval(hipStream_t s, NttTables* T, const CsrDev& A, const CsrDev& B, size_t n_inst, size_t n_c,
+                              const Fr* z, Fr* ab, u32 log_m) {
+        size_t m = (size_t)1 << log_m;
+        const CsrDev* Ms[2] = {&A, &B};
+        for (int k = 0; k < 2; k++)
+            hipLaunchKernelGGL((k_spmv<Fr>), dim3((u32)((m + 255) / 256)), dim3(256), 0, s,
+                               Ms[k]->row_ptr, Ms[k]->col, (const Fr*)Ms[k]->val, z, ab + k * m,
+                               (u32)n_c, k == 0 ? (u32)n_inst : 0u, (u32)m);
+        typename N::Post e1;                                   // ifft (DIF) of a, b with "* g^j", as in run()
+        e1.post = 2;
+        e1.nvec = 2;
+        e1.pw = (const Fr*)T->pw_g;
+        HK_TRY(N::passes(s, ab, m, 2, log_m, (const Fr*)T->tw_inv, 0, e1));
+        HK_TRY(N::passes(s, ab, m, 2, log_m, (const Fr*)T->tw_fwd, 1));       // coset fft (DIT) of a, b
+        hipLaunchKernelGGL((k_mul_pointwise<Fr>), dim3((u32)((m + 255) / 256)), dim3(256), 0, s, ab, ab + m, m);
+        HK_HIP(hipGetLastError());
+        return HK_OK;
+    }
 };
 
 template <class C>

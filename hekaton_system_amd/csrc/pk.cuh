@@ -1,9 +1,11 @@
 // pk.cuh — the device-resident proving key: its tables (shift tables of every query, the compacted A and B queries, the
-// bit-reversed h query, the matrices) and the one-time work that builds them.  Defines Ops<C>::pk_upload (hk_pk_upload) and
+// h query - in the coset's evaluation basis, or bit-reversed in the coefficient basis - the matrices) and the one-time work
+// that builds them.  Defines Ops<C>::pk_upload (hk_pk_upload) and
 // Ops<C>::pk_free (hk_pk_free).
 #pragma once
 #include "ntt_host.cuh"
 #include "csr.cuh"
+#include "h_basis.cuh"
 
 namespace hk {
 
@@ -29,15 +31,19 @@ struct PkImpl {
     u32 *a_rank = nullptr, *b_rank = nullptr;
     MsmPlan plan_a, plan_b;
     Affine<Fq>* l_tab = nullptr;           // [F][l_n]     ck_last | inf | inf | -delta_g | -delta_i ...
-    u32 l_n = 0, l_off = 0;
+    u32 l_n = 0, l_off = 0;                // h_eval: every ext index (l_off = 0, l_n = n_ext), variable k holds -C^_k, a
+                                           // last-stage witness ck_last_k - C^_k (h_basis.cuh)
     bool has_qap = false;
+    // the H query in the coset's evaluation basis (h_basis.cuh; the default for a key with a QAP, HK_H_BASIS=coeff at upload
+    // keeps the coefficient basis): the prover runs QapHost::run_eval - four transforms, no C pass - on 2 m Fr per proof
+    bool h_eval = false;
     u32 log_m = 0;
     MsmPlan plan_h;
-    Affine<Fq>* h_tab = nullptr;           // [F][m]  h_g in bit-reversed order (slot m-1 = inf)
+    Affine<Fq>* h_tab = nullptr;           // [F][m]  h_g in bit-reversed order (slot m-1 = inf); h_eval: G^_j / m^2, natural
     std::vector<MsmPlan> plan_ck;
     std::vector<Affine<Fq>*> ck_tab;       // [F][ck_len + 1]  ck[stage] | last_delta_g
     std::vector<u32> ck_n;
-    Affine<Fq>* consts_g1 = nullptr;       // a_g[0], alpha_g, b_g[0], beta_g
+    Affine<Fq>* consts_g1 = nullptr;       // a_g[0], alpha_g, b_g[0], beta_g, -C^_0 (inf unless h_eval)
     Affine<Fq2>* consts_g2 = nullptr;      // b_h[0], beta_h
     CsrDev csr[3];
     std::vector<void*> owned;              // every hipMalloc of this key
@@ -117,8 +123,15 @@ hk_status Ops<C>::pk_upload(hk_ctx* ctx, const hk_pk_desc* d, hk_pk** out) {
     HK_HIP(hipSetDevice(ctx->device));
     PK* pk = new PK();
     hk_pk* h = new hk_pk{ctx->ops, ctx, pk};
-    void* staging = nullptr;                          // transient device copy of h_g (freed on every exit)
-    auto fail = [&](hk_status st) { if (staging) (void)hipFree(staging); Ops<C>::pk_free(h); return st; };
+    void *staging = nullptr, *hb_tmp = nullptr;       // transient: device copy of h_g; G and -C^ (freed on every exit)
+    auto fail = [&](hk_status st) {
+        if (staging) (void)hipFree(staging);
+        if (hb_tmp) (void)hipFree(hb_tmp);
+        Ops<C>::pk_free(h);
+        return st;
+    };
+    const bool has_qap = d->A && d->B && d->C;
+    pk->h_eval = has_qap && hb_eval_form(getenv("HK_H_BASIS"));
     pk->n_v = (u32)n_v; pk->n_inst = (u32)d->n_inst; pk->n_c = (u32)d->n_constraints;
     pk->n_stages = (u32)d->n_stages;
     u32 k = pk->n_stages - 1;
@@ -226,21 +239,23 @@ hk_status Ops<C>::pk_upload(hk_ctx* ctx, const hk_pk_desc* d, hk_pk** out) {
         PK_TRY(MsmRun<Fq2>::build_tables(s0, pk->b2_tab, pk->b_n, pz.F, shift));
     }
     // --- L table: last-stage committer key, then the negated deltas that fold -rs*delta and -kappa_i*delta_i
+    // (an evaluation-basis key: over every ext index, its variable rows filled and its shift tables built with the QAP below)
     size_t n1 = d->ck_len[k];
-    pk->l_n = (u32)n1 + pk->n_extra;
-    pk->l_off = (u32)(n_v - 1 - n1);                    // ext index of the first last-stage witness
+    const size_t l_rows = pk->h_eval ? n_v - 1 : n1;    // rows in front of r | s | rs | kappa
+    pk->l_n = (u32)l_rows + pk->n_extra;
+    pk->l_off = (u32)(n_v - 1 - l_rows);                // ext index of the table's first row
     if ((st = pk_alloc_table(pk->owned, pk->bytes, pz.F, pk->l_n, &pk->l_tab)) != HK_OK) return fail(st);
     PK_HIP(hipMemset(pk->l_tab, 0, g1 * pk->l_n));
-    if (n1) PK_HIP(hipMemcpy(pk->l_tab, d->ck_stage[k], g1 * n1, h2d_kind(d->ck_stage[k])));
+    if (n1 && !pk->h_eval) PK_HIP(hipMemcpy(pk->l_tab, d->ck_stage[k], g1 * n1, h2d_kind(d->ck_stage[k])));
     {
         std::vector<Affine<Fq>> dh(k + 1);
         PK_HIP(hipMemcpy(dh.data(), deltas, g1 * (k + 1), is_device_ptr(deltas) ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
         std::vector<Affine<Fq>> neg(1 + k);
         neg[0] = dh[k].is_inf() ? dh[k] : ec_neg(dh[k]);                       // -delta_g  (scalar r*s)
         for (u32 i = 0; i < k; i++) neg[1 + i] = dh[i].is_inf() ? dh[i] : ec_neg(dh[i]);   // -delta_i (kappa_i)
-        PK_HIP(hipMemcpy(pk->l_tab + n1 + 2, neg.data(), g1 * (1 + k), hipMemcpyHostToDevice));
+        PK_HIP(hipMemcpy(pk->l_tab + l_rows + 2, neg.data(), g1 * (1 + k), hipMemcpyHostToDevice));
     }
-    PK_TRY(MsmRun<Fq>::build_tables(s0, pk->l_tab, pk->l_n, pz.F, shift));
+    if (!pk->h_eval) PK_TRY(MsmRun<Fq>::build_tables(s0, pk->l_tab, pk->l_n, pz.F, shift));
     // --- per-stage commitment tables: ck[stage] | last_delta_g (scalar kappa)
     for (u32 sidx = 0; sidx < pk->n_stages; sidx++) {
         size_t n = d->ck_len[sidx] + 1;
@@ -257,9 +272,10 @@ hk_status Ops<C>::pk_upload(hk_ctx* ctx, const hk_pk_desc* d, hk_pk** out) {
     // --- constants for the finish kernel
     {
         void* p1; void* p2;
-        PK_HIP(hipMalloc(&p1, g1 * 4)); pk->owned.push_back(p1);
+        PK_HIP(hipMalloc(&p1, g1 * 5)); pk->owned.push_back(p1);
         PK_HIP(hipMalloc(&p2, g2 * 2)); pk->owned.push_back(p2);
         pk->consts_g1 = (Affine<Fq>*)p1; pk->consts_g2 = (Affine<Fq2>*)p2;
+        PK_HIP(hipMemset(pk->consts_g1 + 4, 0, g1));
         PK_HIP(hipMemcpy(pk->consts_g1 + 0, a_g, g1, h2d_kind(a_g)));
         PK_HIP(hipMemcpy(pk->consts_g1 + 1, d->alpha_g, g1, h2d_kind(d->alpha_g)));
         PK_HIP(hipMemcpy(pk->consts_g1 + 2, b_g, g1, h2d_kind(b_g)));
@@ -267,8 +283,8 @@ hk_status Ops<C>::pk_upload(hk_ctx* ctx, const hk_pk_desc* d, hk_pk** out) {
         PK_HIP(hipMemcpy(pk->consts_g2 + 0, b_h, g2, h2d_kind(b_h)));
         PK_HIP(hipMemcpy(pk->consts_g2 + 1, d->beta_h, g2, h2d_kind(d->beta_h)));
     }
-    // --- QAP: matrices + H-query in bit-reversed order
-    if (d->A && d->B && d->C) {
+    // --- QAP: matrices + H-query, in the coset's evaluation basis or bit-reversed in the coefficient basis
+    if (has_qap) {
         if (d->A->n_rows != d->n_constraints || d->B->n_rows != d->n_constraints ||
             d->C->n_rows != d->n_constraints)
             return fail(HK_ERR_LEN);
@@ -306,13 +322,25 @@ hk_status Ops<C>::pk_upload(hk_ctx* ctx, const hk_pk_desc* d, hk_pk** out) {
             PK_HIP(hipMemcpy(staging, d->h_g, g1 * d->h_len, hipMemcpyHostToDevice));
             src = (const Affine<Fq>*)staging;
         }
-        hipLaunchKernelGGL((k_pk_bitrev_copy<Fq>), dim3((u32)((m + 255) / 256)), dim3(256), 0, s0, pk->h_tab,
-                           src, (u32)d->h_len, pk->log_m);
-        PK_HIP(hipDeviceSynchronize());
-        if (staging) { (void)hipFree(staging); staging = nullptr; }
-        PK_TRY(MsmRun<Fq>::build_tables(s0, pk->h_tab, (u32)m, pk->plan_h.F, pk->plan_h.c * pk->plan_h.WP));
         NttTables* T;
         PK_TRY(NttHost<C>::ensure(ctx, pk->log_m, &T));
+        if (pk->h_eval) {
+            // h_tab = G^ / m^2 in natural order; G, then -C^ (+ the last stage's committer key) behind it, are transient
+            PK_HIP(hipMalloc(&hb_tmp, g1 * (m + n_v)));
+            Affine<Fq>*gd = (Affine<Fq>*)hb_tmp, *cd = gd + m;
+            PK_TRY(HBasis<C>::transform(ctx, T, src, (u32)d->h_len, pk->log_m, pk->h_tab, gd));
+            PK_TRY(HBasis<C>::c_columns(ctx, pk->csr[2], n_v, pk->log_m, gd, d->ck_stage[k], n1, cd));
+            if (nq) PK_HIP(hipMemcpy(pk->l_tab, cd + 1, g1 * nq, hipMemcpyDeviceToDevice));
+            PK_HIP(hipMemcpy(pk->consts_g1 + 4, cd, g1, hipMemcpyDeviceToDevice));      // z_0 = 1: -C^_0 joins C's constants
+            (void)hipFree(hb_tmp); hb_tmp = nullptr;
+            PK_TRY(MsmRun<Fq>::build_tables(s0, pk->l_tab, pk->l_n, pz.F, shift));
+        } else {
+            hipLaunchKernelGGL((k_pk_bitrev_copy<Fq>), dim3((u32)((m + 255) / 256)), dim3(256), 0, s0, pk->h_tab,
+                               src, (u32)d->h_len, pk->log_m);
+            PK_HIP(hipDeviceSynchronize());
+        }
+        if (staging) { (void)hipFree(staging); staging = nullptr; }
+        PK_TRY(MsmRun<Fq>::build_tables(s0, pk->h_tab, (u32)m, pk->plan_h.F, pk->plan_h.c * pk->plan_h.WP));
         pk->has_qap = true;
     }
     PK_HIP(hipDeviceSynchronize());

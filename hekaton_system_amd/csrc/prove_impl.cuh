@@ -40,6 +40,8 @@ __global__ void k_prep_ext(Fr* __restrict__ ext, u32 ext_stride, const Fr* __res
 
 // Finish: A = MA + a_g[0] + alpha_g ; B = MB2 + b_h[0] + beta_h ; B1 = MB1 + b_g[0] + beta_g ;
 //         C = s*A + r*B1 + ML' + MH   with ML' = L - rs*delta_g - sum kappa_i*delta_i   (see file header)
+// (an evaluation-basis key, h_basis.cuh: ML' also carries -sum_{k>=1} z_k C^_k, the constant c1[4] = -C^_0 completes it, and
+// MH = sum_j (a'_j b'_j) G^_j: the same C)
 // (prover.rs:135-155 "Finish C" + into_affine, committer.rs:112-114).  Two kernels, so that the variable-base products
 // do not wait for H: k_finish_ab needs only A, B1, B2 and L and leaves C without MH in part_c; k_finish_c adds MH once H is
 // done and normalises C.  The sum is the one the single kernel formed, in the same order, and an affine point is unique.
@@ -125,7 +127,8 @@ __global__ void k_finish_ab(const XYZZ<Fq>* __restrict__ res_g1_all, const XYZZ<
                 Cc.zz = Fq::sqr(sum.z);
                 Cc.zzz = Fq::mul(Cc.zz, sum.z);
             }
-            st_vec(part_c, ec_add_ni(Cc, ld_vec(&res_g1[2])));
+            // c1[4]: -C^_0 of an evaluation-basis key (z_0 = 1 is no ext scalar), infinity otherwise
+            st_vec(part_c, ec_madd_ni(ec_add_ni(Cc, ld_vec(&res_g1[2])), ld_vec(&c1[4])));
         }
     }
 }
@@ -145,7 +148,8 @@ template <class C>
 size_t Ops<C>::finish_private_bytes() {
     size_t ab = hk_private_bytes_of((const void*)k_finish_ab<Fr, Fq, Fq2>);
     size_t c = hk_private_bytes_of((const void*)k_finish_c<Fq>);
-    return ab > c ? ab : c;
+    size_t hb = HBasis<C>::private_bytes();                 // the evaluation-basis key's one-time kernels (h_basis.cuh)
+    return std::max(std::max(ab, c), hb);
 }
 
 template <class C>
@@ -262,6 +266,7 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
     HK_TRY(NttHost<C>::ensure(ctx, pk->log_m, &T));
     const MsmPlan &pz = pk->plan_z, &ph = pk->plan_h, &pa = pk->plan_a, &pb = pk->plan_b;
     const size_t m = (size_t)1 << pk->log_m, fr = sizeof(Fr), rs_stride = 2 + n_kappas;
+    const size_t h_stride = (pk->h_eval ? 2 : 3) * m;                          // a proof's witness-map scratch, in Fr
     std::vector<char> z_dev(batch);
     bool any_host = false;
     for (size_t b = 0; b < batch; b++) {
@@ -298,7 +303,7 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
         oc = c.n<Affine<Fq>>(nb);
         ob = c.n<Affine<Fq2>>(nb);
         pc = c.n<XYZZ<Fq>>(nb);                                               // C without MH (k_finish_ab -> k_finish_c)
-        abc = c.n<Fr>(3 * m * nb);                                            // [nb][a | b | c]
+        abc = c.n<Fr>(h_stride * nb);                                         // [nb][a | b | c], or [nb][a | b] (h_eval)
     };
     // chunk rule (hekaton.h): at most HK_PROVE_BATCH_CHUNK proofs, fewer when that many would not fit in free device memory
     // (the lane's own arena counts as free: reserve() replaces it)
@@ -368,11 +373,15 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
         auto submit_h = [&]() -> hk_status {
             HK_TRY(wait(sH, ev_z, s));
             if (prof) HK_HIP(hipEventRecord(ev[5], sH));
-            for (u32 j = 0; j < nb; j++)                                        // witness map: one chain per proof
-                HK_TRY(Q::run(sH, T, pk->csr[0], pk->csr[1], pk->csr[2], pk->n_inst, pk->n_c, zd[j],
-                              abc + (size_t)j * 3 * m, pk->log_m));
+            for (u32 j = 0; j < nb; j++) {                                      // witness map: one chain per proof
+                if (pk->h_eval)
+                    HK_TRY(Q::run_eval(sH, T, pk->csr[0], pk->csr[1], pk->n_inst, pk->n_c, zd[j], abc + j * h_stride, pk->log_m));
+                else
+                    HK_TRY(Q::run(sH, T, pk->csr[0], pk->csr[1], pk->csr[2], pk->n_inst, pk->n_c, zd[j],
+                                  abc + j * h_stride, pk->log_m));
+            }
             if (prof) HK_HIP(hipEventRecord(ev[6], sH));                       // witness map done
-            HK_TRY(MsmSort<Fr>::run(sH, ph, (const u32*)abc, 1, sbh, true, nb, 3 * m));
+            HK_TRY(MsmSort<Fr>::run(sH, ph, (const u32*)abc, 1, sbh, true, nb, h_stride));
             HK_TRY(MsmRun<Fq>::run(sH, ph, pk->h_tab, (u32)m, 0, sbh, rbh, res1 + 3, prof ? ev[12] : nullptr,
                                    prof ? ev[13] : nullptr, nb, 4));
             HK_HIP(hipEventRecord(ev[7], sH));                                 // H done

@@ -329,7 +329,10 @@ hk_status hk_poseidon_path(hk_ctx* ctx, const void* consts_mont, size_t n_consts
                            const hk_poseidon_desc* node_hash, const void* leaf_mont, const void* siblings_mont,
                            const uint32_t* leaf_index, size_t depth, size_t batch, size_t n_v, size_t col0, void* z_out);
 
-/* ---- proving-key residency -------------------------------------------------------------- */
+/* ---- proving-key residency --------------------------------------------------------------
+ * A key with matrices holds its H query in the coset's evaluation basis (hk_prove then runs four
+ * transforms and no C pass; the upload transforms h_g once, seconds at m = 2^21); HK_H_BASIS=coeff in the environment of the
+ * upload keeps the coefficient basis.  The proofs of the two forms are the same bytes. */
 hk_status hk_pk_upload(hk_ctx* ctx, const hk_pk_desc* desc, hk_pk** out);
 void      hk_pk_free(hk_pk* pk);
 
