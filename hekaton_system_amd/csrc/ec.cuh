@@ -86,7 +86,13 @@ HK_RARE XYZZ<F> ec_dbl_rare(const XYZZ<F>& p) { return ec_dbl(p); }
 // the P == Q corner: an out-of-line call there takes the addresses of `a`/`q`, which forces hipcc to
 // keep copies of them in scratch memory on EVERY iteration of the accumulate loop (rocprofv3 showed
 // 6.3 GB of WRITE_SIZE per 2^21-point MSM from it).
-template <class F, bool INLINE_CORNER = (F::Params::N <= 8)>
+//
+// FUSED_Y: y = R (Q - X3) - Y1 PPP as ONE fused two-product block, F::mulsub (field.cuh mul2: one Montgomery reduction for
+// both products and one negated operand, Y1, which is dead afterwards) - the inlined callers, i.e. the accumulate loops.
+// The out-of-line ec_madd_ni keeps the two products and the subtraction, and so do ec_add, ec_dbl and ec_dbl_affine: in
+// those cold, out-of-line forms the fused block's four live operands cost 16 to 64 B more scratch per lane in every kernel
+// that calls them, which the scratch-ring budget of DESIGN.md section 3c does not have (section 4u).
+template <class F, bool INLINE_CORNER = (F::Params::N <= 8), bool FUSED_Y = true>
 HK_HD XYZZ<F> ec_madd(const XYZZ<F>& a, const Affine<F>& q) {
     if (q.is_inf()) return a;
     if (a.is_inf()) return XYZZ<F>::from_affine(q);
@@ -109,7 +115,8 @@ HK_HD XYZZ<F> ec_madd(const XYZZ<F>& a, const Affine<F>& q) {
         F xx = F::sqr(q.x);
         F m = F::add(F::dbl(xx), xx);
         o.x = F::sub(F::sqr(m), F::dbl(s));
-        o.y = F::sub(F::mul(m, F::sub(s, o.x)), F::mul(w, q.y));
+        if constexpr (FUSED_Y) o.y = F::mulsub(m, F::sub(s, o.x), w, q.y);
+        else o.y = F::sub(F::mul(m, F::sub(s, o.x)), F::mul(w, q.y));
         o.zz = v;
         o.zzz = w;
         return o;
@@ -118,7 +125,8 @@ HK_HD XYZZ<F> ec_madd(const XYZZ<F>& a, const Affine<F>& q) {
     F ppp = F::mul(p, pp);
     F qq = F::mul(a.x, pp);
     o.x = F::sub(F::sub(F::sqr(r), ppp), F::dbl(qq));
-    o.y = F::sub(F::mul(r, F::sub(qq, o.x)), F::mul(a.y, ppp));
+    if constexpr (FUSED_Y) o.y = F::mulsub(r, F::sub(qq, o.x), ppp, a.y);
+    else o.y = F::sub(F::mul(r, F::sub(qq, o.x)), F::mul(a.y, ppp));
     o.zz = F::mul(a.zz, pp);
     o.zzz = F::mul(a.zzz, ppp);
     return o;
@@ -156,7 +164,7 @@ HK_RARE XYZZ<F> ec_add_ni(const XYZZ<F>& a, const XYZZ<F>& b) { return ec_add(a,
 template <class F>
 HK_RARE XYZZ<F> ec_dbl_ni(const XYZZ<F>& a) { return ec_dbl(a); }
 template <class F>
-HK_RARE XYZZ<F> ec_madd_ni(const XYZZ<F>& a, const Affine<F>& b) { return ec_madd(a, b); }
+HK_RARE XYZZ<F> ec_madd_ni(const XYZZ<F>& a, const Affine<F>& b) { return ec_madd<F, (F::Params::N <= 8), false>(a, b); }
 template <class F>
 HK_RARE F f_mul_ni(const F& a, const F& b) { return F::mul(a, b); }
 

@@ -362,6 +362,8 @@ struct Fp2Q {
         r.c1 = B::sub(B::sub(v2, v0), v1);
         return r;
     }
+    // a b - c d, the field interface the fused y of ec_madd asks for (ec.cuh): two quad products, as Fp2::mulsub
+    __device__ __forceinline__ static Fp2Q mulsub(const Fp2Q& a, const Fp2Q& b, const Fp2Q& c, const Fp2Q& d) { return sub(mul(a, b), mul(c, d)); }
     __device__ __forceinline__ static Fp2Q sqr(const Fp2Q& a) {       // lanes 0, 2: (a0 + a1)(a0 - a1); lanes 1, 3: a0 a1
         bool odd = threadIdx.x & 1u;
         B s = B::add(a.c0, a.c1), d = B::sub(a.c0, a.c1);

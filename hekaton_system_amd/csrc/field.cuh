@@ -243,6 +243,48 @@ struct Fp {
         return reduce_once(r);
     }
     HK_HD static Fp sqr(const Fp& a) { return mul(a, a); }
+
+    // (a b + c d) / R with ONE Montgomery reduction (gen_mont_asm.py gen_block2): 3 N^2 mad + addc pairs where two
+    // products run 4 N^2.  Operands up to the representative bound, that bound itself included (see neg_operand): on a
+    // lazy field (a b + c d + m p) / R < (8 p^2 + R p) / R = p (8p / R + 1).  Where 8p + R <= 2R (BLS12-381 Fq: 1.82 p) that
+    // is a lazy representative as it stands; elsewhere (BN254: 2.52 p, about 0.48 R, so it fits the N limbs) one
+    // conditional subtraction of 2p follows - HK_MONT2_FIX_<field>, which the generator decides from the modulus.  On a
+    // canonical field the value is below p (2p / R + 1) < 2p and reduce_once makes it canonical, as after mul.
+    // Without a block (HK_NO_ASM_MUL, host code) it is the sum of two products.
+    HK_HD static Fp mul2(const Fp& a, const Fp& b, const Fp& c, const Fp& d) {
+#if defined(HK_USE_ASM_MUL)
+#define HK_MUL2_CASE(ID, F)                                                                              \
+        if constexpr (P::ASM_ID == ID) {                                                                 \
+            Fp r; HK_MONT2_ASM_##F(r, a, b, c, d);                                                       \
+            if constexpr (!P::LAZY) return reduce_once(r);                                               \
+            else if constexpr (HK_MONT2_FIX_##F) { Fp t; HK_RED_ASM_##F(t, r); return t; }               \
+            else return r;                                                                               \
+        }
+        HK_MUL2_CASE(1, BN254_FR)
+        HK_MUL2_CASE(2, BN254_FQ)
+        if constexpr (P::ASM_ID == 3) { Fp t, r; HK_MONT2_ASM_BLS12_381_FR(t, a, b, c, d); HK_RED_ASM_BLS12_381_FR(r, t); return r; }
+        HK_MUL2_CASE(4, BLS12_381_FQ)
+#undef HK_MUL2_CASE
+#endif
+        return add(mul(a, b), mul(c, d));
+    }
+    // -a as an operand of mul / mul2 ONLY: on a lazy field with a block, 2p - a in (0, 2p] without the zero mask of neg
+    // (2N instructions; 0 maps to 2p, which the products' bounds admit and nothing else does).  Otherwise neg.
+    HK_HD static Fp neg_operand(const Fp& a) {
+#if defined(HK_USE_ASM_MUL)
+        if constexpr (P::LAZY && P::ASM_ID == 1) { Fp r; HK_NEG2P_ASM_BN254_FR(r, a); return r; }
+        if constexpr (P::LAZY && P::ASM_ID == 2) { Fp r; HK_NEG2P_ASM_BN254_FQ(r, a); return r; }
+        if constexpr (P::LAZY && P::ASM_ID == 4) { Fp r; HK_NEG2P_ASM_BLS12_381_FQ(r, a); return r; }
+#endif
+        return neg(a);
+    }
+    // a b - c d: one fused block and one negated operand where the field has the block, else two products and a sub
+    HK_HD static Fp mulsub(const Fp& a, const Fp& b, const Fp& c, const Fp& d) {
+#if defined(HK_USE_ASM_MUL)
+        if constexpr (P::ASM_ID != 0) return mul2(a, b, c, neg_operand(d));
+#endif
+        return sub(mul(a, b), mul(c, d));
+    }
     // a / 2: (a odd ? a + p : a) >> 1 - a Montgomery value halves like its integer.  Lazy input < 2p gives < 1.5p.
     HK_HD static Fp halve(const Fp& a) {
         u32 odd = 0u - (a.v[0] & 1u);
@@ -304,6 +346,10 @@ struct Fp2 {
         r.c1 = B::sub(B::sub(s, v0), v1);
         return r;
     }
+    // a b + c d and a b - c d: two Karatsuba products, as before the base field had its fused block (DESIGN.md §4u on
+    // why the extension does not use it)
+    HK_HD static Fp2 mul2(const Fp2& a, const Fp2& b, const Fp2& c, const Fp2& d) { return add(mul(a, b), mul(c, d)); }
+    HK_HD static Fp2 mulsub(const Fp2& a, const Fp2& b, const Fp2& c, const Fp2& d) { return sub(mul(a, b), mul(c, d)); }
     HK_HD static Fp2 sqr(const Fp2& a) {                     // (a0+a1)(a0-a1), 2 a0 a1
         B t = bmul(a.c0, a.c1);
         Fp2 r;

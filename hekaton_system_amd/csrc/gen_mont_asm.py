@@ -166,6 +166,125 @@ def gen_block_tied(name, p, n):
 """ % dict(name=name, decl=decl, body=body, outs=outs, ins=ins, clob=clob, store=store), len(L)
 
 
+def mul2_needs_correction(p, n):
+    """Whether the fused two-product block (a b + c d) / R needs one conditional subtraction of 2p afterwards, on a lazy
+    field.  With every operand at most 2p and every quotient digit m_j below 2^32 (so m < R), the block's value is
+        (a b + c d + m p) / R  <  (8 p^2 + R p) / R  =  p (8p / R + 1),
+    which stays below 2p exactly when 8p + R <= 2R.  Decided from the modulus, never from a curve's name.  Where it does
+    not, the value is still below 4p <= R (a lazy field has 4p <= R, so 8p/R + 1 <= 3): it fits the n limbs."""
+    R = 1 << (32 * n)
+    return 8 * p + R > 2 * R
+
+
+def gen_block2(name, p, n):
+    """r = (a b + c d) R^-1: the product-scanning columns of gen_block with two operand products per quotient product,
+    column i = sum a_j b_(i-j) + sum c_j d_(i-j) + sum m_j p_(i-j).  One reduction serves both products: 3 n^2 mad + addc
+    pairs where two separate products run 4 n^2.  A column holds at most 3n products below 2^64 plus the carried-in
+    words, far below the 96 bits of the accumulator.
+
+    Every field gets the tied form of gen_block_tied: the a-limbs are read-write operands that receive the result and the
+    quotient digits live in clobbered physical VGPRs.  That is not about the operand count alone.  The untied form (8
+    early-clobber outputs, 32 inputs) compiles for 8 limbs, and hipcc (ROCm 7.2) then gives d-limbs - operands 33 and 36 -
+    the registers of outputs 1 and 4: early-clobber is not honoured against the inputs beyond the 32nd operand, and the
+    mixed add computed a wrong y wherever register pressure made that choice (found by the chain test of
+    tests/test_mul2_gpu.py, read in the disassembly).  The tied form needs no such protection: the only operand registers it
+    writes are t_k = a_k's, in column n + k, and limb k of every operand is last read in column n - 1 + k."""
+    inv = (-pow(p, -1, 1 << 32)) % (1 << 32)
+    limbs = [(p >> (32 * i)) & 0xFFFFFFFF for i in range(n)]
+    A = lambda i: "%%%d" % i                   # "+v": a_i in, t_i out
+    T = A
+    M = lambda i: "v%d" % (M_BASE + i)
+    base = n
+    B = lambda i: "%%%d" % (base + i)
+    C = lambda i: "%%%d" % (base + n + i)
+    D = lambda i: "%%%d" % (base + 2 * n + i)
+    P = lambda i: "s%d" % (SBASE + i)
+    SINV = "s%d" % (SBASE + n)
+    L = []
+    for i, l in enumerate(limbs):
+        L.append("s_mov_b32 %s, 0x%08x" % (P(i), l))
+    L.append("s_mov_b32 %s, 0x%08x" % (SINV, inv))
+    mac, shift, lo = _column_ops(L)
+
+    for i in range(n):
+        for j in range(i):
+            mac(A(j), B(i - j))
+            mac(C(j), D(i - j))
+            mac(M(j), P(i - j))
+        mac(A(i), B(0))
+        mac(C(i), D(0))
+        L.append("v_mul_lo_u32 %s, %s, %s" % (M(i), lo(), SINV))
+        mac(M(i), P(0))
+        shift()
+    for i in range(n, 2 * n):
+        for j in range(i - n + 1, n):
+            mac(A(j), B(i - j))
+            mac(C(j), D(i - j))
+            mac(M(j), P(i - j))
+        L.append("v_mov_b32 %s, %s" % (T(i - n), lo()))      # a_(i-n) and m_(i-n) are dead from this column on
+        if i < 2 * n - 1:
+            shift()
+    body = "\\n\\t".join(L)
+    vec = lambda x: ", ".join('"v"(%s.v[%d])' % (x, i) for i in range(n))
+    outs = ", ".join('"+&v"(t%d)' % i for i in range(n))
+    ins = ", ".join(vec(x) for x in "bcd")
+    decl = "    u32 " + ", ".join("t%d = a.v[%d]" % (i, i) for i in range(n)) + ";"
+    mclob = ["v%d" % (M_BASE + i) for i in range(n)]
+    clob = ", ".join('"%s"' % c for c in ["vcc"] + ACC_CLOBBERS + mclob + ["s%d" % (SBASE + i) for i in range(n + 1)])
+    store = " ".join("r.v[%d] = t%d;" % (i, i) for i in range(n))
+    lazy = 4 * p <= 1 << (32 * n)
+    fix = int(mul2_needs_correction(p, n)) if lazy else 1
+    return """
+// %(name)s: r = (a * b + c * d) * R^-1 mod p, one reduction for both products%(form)s.  Operands up to the
+// representative bound (2p on a lazy field) give r < p (8p / R + 1): %(after)s
+#define HK_MONT2_FIX_%(name)s %(fix)d
+#define HK_MONT2_ASM_%(name)s(r, a, b, c, d)                                             \\
+    do {                                                                                 \\
+    %(decl)s                                                                             \\
+        asm("%(body)s"                                                                   \\
+            : %(outs)s                                                                   \\
+            : %(ins)s                                                                    \\
+            : %(clob)s);                                                                 \\
+        %(store)s                                                                        \\
+    } while (0)
+""" % dict(name=name, decl=decl, body=body, outs=outs, ins=ins, clob=clob, store=store, fix=fix,
+           form=" - tied-operand form",
+           after=("below 2p as it stands" if lazy and not fix else
+                  "one conditional subtraction of %s must follow" % ("2p" if lazy else "p"))), len(L)
+
+
+def gen_neg2p(name, p, n):
+    """r = 2p - a for a lazy representative a in [0, 2p): a value in (0, 2p] congruent to -a, good as an operand of a
+    product block (whose bound takes operands up to 2p) and nowhere else - 0 maps to 2p.  2n instructions; the limbs of
+    2p go through two alternating scratch registers because a carry-chain instruction reads one scalar operand, VCC."""
+    p2 = [((2 * p) >> (32 * i)) & 0xFFFFFFFF for i in range(n)]
+    T = lambda i: "%%%d" % i
+    L = []
+    for i in range(n):
+        s = (ACC_LO, ACC_HI)[i & 1]
+        L.append("v_mov_b32 %s, 0x%08x" % (s, p2[i]))
+        if i == 0:
+            L.append("v_sub_co_u32 %s, vcc, %s, %s" % (T(0), s, T(0)))
+        else:
+            L.append("v_subb_co_u32 %s, vcc, %s, %s, vcc" % (T(i), s, T(i)))
+    decl = "    u32 " + ", ".join("t%d = a.v[%d]" % (i, i) for i in range(n)) + ";"
+    store = " ".join("r.v[%d] = t%d;" % (i, i) for i in range(n))
+    outs = ", ".join('"+&v"(t%d)' % i for i in range(n))
+    clob = ", ".join('"%s"' % c for c in ["vcc", ACC_LO, ACC_HI])
+    return """
+// %(name)s: r = 2p - a in (0, 2p] for a in [0, 2p): a product operand only (0 gives 2p)
+#define HK_NEG2P_ASM_%(name)s(r, a)                                                      \\
+    do {                                                                                 \\
+    %(decl)s                                                                             \\
+        asm("%(body)s"                                                                   \\
+            : %(outs)s                                                                   \\
+            :                                                                            \\
+            : %(clob)s);                                                                 \\
+        %(store)s                                                                        \\
+    } while (0)
+""" % dict(name=name, decl=decl, body="\\n\\t".join(L), outs=outs, clob=clob, store=store), len(L)
+
+
 S_BASE_V = 10                                 # v8.. scratch for the trial subtraction of the lazy add
 
 
@@ -274,6 +393,12 @@ def main(path):
             if True:
                 blk, cnts = gen_addsub("%s_%s" % (cname, fname), p, n)
                 out.append("/* add / dbl / sub: %d / %d / %d instructions */" % cnts)
+                out.append(blk)
+            blk, cnt = gen_block2("%s_%s" % (cname, fname), p, n)
+            out.append("/* fused two-product block: %d instructions */" % cnt)
+            out.append(blk)
+            if 4 * p <= 1 << (32 * n):
+                blk, cnt = gen_neg2p("%s_%s" % (cname, fname), p, n)
                 out.append(blk)
     with open(path, "w") as f:
         f.write("\n".join(out) + "\n")
