@@ -117,7 +117,35 @@ HK_HD u32 endo_decompose(const u32 (&c)[8], const EndoSplit<K>& E, u32 (&mag)[K]
 // the whole wave whenever any lane has the bit: with four images that was four mixed adds per step for every lane
 // (68 x (dbl + 4 madd): 7.5 ms in G2).  Each lane therefore first tabulates the 2^K - 1 subset sums of its images
 // (tab[mask][i] = sum of +-endo^j(P_i) over the bits of mask) and the chain adds ONE table entry per step, picked by the
-// column of the K sub-scalars: 68 x (dbl + add).
+// column of the K sub-scalars: 68 x (dbl + add).  Both one-lane kernels below run these two helpers.
+// tab[mask][i] for every mask whose TOP bit is j: the entry without that bit (already there) plus the image +-endo^j(q)
+template <class F>
+__device__ __forceinline__ void endo_subset_table(Affine<F> q, u32 neg, XYZZ<F>* tab, u32 n, u32 i) {
+    HK_NOUNROLL for (int j = 0; j < EndoOf<F>::K; j++) {
+        if (j) q = EndoOf<F>::apply(q);
+        Affine<F> w = q;
+        if ((neg >> j) & 1u) w.y = F::neg(w.y);
+        st_vec(&tab[((size_t)1 << j) * n + i], XYZZ<F>::from_affine(w));
+        HK_NOUNROLL for (u32 m = 1; m < (1u << j); m++)
+            st_vec(&tab[(((size_t)1 << j) | m) * n + i], ec_madd_ni(ld_vec(&tab[(size_t)m * n + i]), w));
+    }
+}
+// a magnitude seen as its limbs: u32[6] from endo_decompose, or an Fr out of Montgomery form
+__device__ __forceinline__ const u32* limbs_of(const u32 (&m)[6]) { return m; }
+template <class P> __device__ __forceinline__ const u32* limbs_of(const Fp<P>& m) { return m.v; }
+// from bit `top` down: a doubling and the table entry of the K magnitudes' bit column (acc in place: a copy is a frame slot)
+template <class F, class M>
+__device__ __forceinline__ void endo_subset_chain(const M (&mag)[EndoOf<F>::K], int top, const XYZZ<F>* tab, u32 n, u32 i,
+                                                  XYZZ<F>& acc) {
+    acc = XYZZ<F>::inf();
+    HK_NOUNROLL for (int b = top; b >= 0; b--) {
+        acc = ec_dbl_ni(acc);
+        u32 m = 0;
+        HK_UNROLL for (int j = 0; j < EndoOf<F>::K; j++) m |= ((limbs_of(mag[j])[b >> 5] >> (b & 31)) & 1u) << j;
+        if (m) acc = ec_add_ni(acc, ld_vec(&tab[(size_t)m * n + i]));
+    }
+}
+
 template <class Fr, class F>
 __global__ void __launch_bounds__(64)
 k_scalar_mul_endo(const Affine<F>* __restrict__ pts, const Fr* __restrict__ scalars, u32 n,
@@ -132,22 +160,9 @@ k_scalar_mul_endo(const Affine<F>* __restrict__ pts, const Fr* __restrict__ scal
     u32 neg = endo_decompose<K>(c, E, mag);
     Affine<F> q = ld_vec(&pts[i]);
     if (q.is_inf()) { st_vec(&out[i], XYZZ<F>::inf()); return; }
-    HK_NOUNROLL for (int j = 0; j < K; j++) {
-        if (j) q = EndoOf<F>::apply(q);
-        Affine<F> w = q;
-        if ((neg >> j) & 1u) w.y = F::neg(w.y);
-        // every mask whose TOP bit is j: the entry without that bit (already there) plus this image
-        st_vec(&tab[((size_t)1 << j) * n + i], XYZZ<F>::from_affine(w));
-        HK_NOUNROLL for (u32 m = 1; m < (1u << j); m++)
-            st_vec(&tab[(((size_t)1 << j) | m) * n + i], ec_madd_ni(ld_vec(&tab[(size_t)m * n + i]), w));
-    }
-    XYZZ<F> acc = XYZZ<F>::inf();
-    HK_NOUNROLL for (int b = EndoOf<F>::STEPS - 1; b >= 0; b--) {
-        acc = ec_dbl_ni(acc);
-        u32 m = 0;
-        HK_UNROLL for (int j = 0; j < K; j++) m |= ((mag[j][b >> 5] >> (b & 31)) & 1u) << j;
-        if (m) acc = ec_add_ni(acc, ld_vec(&tab[(size_t)m * n + i]));
-    }
+    endo_subset_table(q, neg, tab, n, i);
+    XYZZ<F> acc;
+    endo_subset_chain(mag, EndoOf<F>::STEPS - 1, tab, n, i, acc);
     st_vec(&out[i], acc);
 }
 
@@ -155,7 +170,7 @@ k_scalar_mul_endo(const Affine<F>* __restrict__ pts, const Fr* __restrict__ scal
 // into K magnitudes and a sign mask: the fold of a TIPA round (hk_points_fold_g1 / _g2).  Same table-driven chain as
 // k_scalar_mul_endo - the endomorphism images and their subset sums are built per element inside this launch (no
 // separate image kernel, no image vectors in HBM), one table add per step - then + lo.
-// coeffs: K Montgomery Fr (the magnitudes); steps: bit length of the longest magnitude.
+// coeffs: K Montgomery Fr (the magnitudes); the chain starts at the top set bit of the longest magnitude.
 template <class Fr, class F>
 __global__ void __launch_bounds__(64)
 k_points_fold_endo(const Affine<F>* __restrict__ lo, const Affine<F>* __restrict__ hi, const Fr* __restrict__ coeffs, u32 neg,
@@ -174,20 +189,8 @@ k_points_fold_endo(const Affine<F>* __restrict__ lo, const Affine<F>* __restrict
     Affine<F> q = ld_vec(&hi[i]);
     XYZZ<F> acc = XYZZ<F>::inf();
     if (!q.is_inf()) {
-        HK_NOUNROLL for (int j = 0; j < K; j++) {
-            if (j) q = EndoOf<F>::apply(q);
-            Affine<F> w = q;
-            if ((neg >> j) & 1u) w.y = F::neg(w.y);
-            st_vec(&tab[((size_t)1 << j) * n + i], XYZZ<F>::from_affine(w));
-            HK_NOUNROLL for (u32 m = 1; m < (1u << j); m++)
-                st_vec(&tab[(((size_t)1 << j) | m) * n + i], ec_madd_ni(ld_vec(&tab[(size_t)m * n + i]), w));
-        }
-        HK_NOUNROLL for (int b = top; b >= 0; b--) {
-            acc = ec_dbl_ni(acc);
-            u32 m = 0;
-            HK_UNROLL for (int j = 0; j < K; j++) m |= ((mag[j].v[b >> 5] >> (b & 31)) & 1u) << j;
-            if (m) acc = ec_add_ni(acc, ld_vec(&tab[(size_t)m * n + i]));
-        }
+        endo_subset_table(q, neg, tab, n, i);
+        endo_subset_chain(mag, top, tab, n, i, acc);
     }
     st_vec(&out[i], ec_madd_ni(acc, l));
 }
@@ -315,7 +318,72 @@ HK_HD bool split_mag_fits(const u32* m) {
     return true;
 }
 
+// (X, Y, Z) -> (X, Y, Z^2, Z^3)
+template <class F>
+HK_HD XYZZ<F> jac_to_xyzz(const Jac<F>& p) {
+    XYZZ<F> o = XYZZ<F>::inf();
+    if (!p.is_inf()) {
+        o.x = p.x; o.y = p.y;
+        o.zz = F::sqr(p.z);
+        o.zzz = F::mul(o.zz, p.z);
+    }
+    return o;
+}
+
+// a lane's table, entry k = (k + 1) P: a row in LDS or on the host (inlined, it keeps its address space), or SplitTabStrided
+template <class F> struct SplitTabRow {
+    Jac<F>* row;
+    HK_HD Jac<F> ld(int k) const { return row[k]; }
+    HK_HD void st(int k, const Jac<F>& e) const { row[k] = e; }
+};
+
+// |m| q for ONE lane of a short product, m biased by split_bias: signed 4-bit digits from the top over the table 1P .. 8P,
+// ND x (4 Jacobian doublings + 1 add) into acc (in place: a copy is a frame slot).  q_inf: the lane has no point, no table.
+// On the device the wave votes on skipping leading zero digits, so its lanes stay in step; a lane kept running loses nothing:
+// a doubling of infinity stays is_inf(), jac_add_ni returns its other operand for an infinite one, a zero digit adds nothing.
+template <class F, class Tab>
+HK_HD void split_window_digits(bool q_inf, const u32 (&m)[6], const Tab& tab, Jac<F>& acc) {
+    acc = Jac<F>::inf();
+    HK_NOUNROLL for (int d = SplitDigits<F>::ND - 1; d >= 0; d--) {
+        int dig = split_digit(m, d);
+        bool idle = q_inf || (dig == 0 && acc.is_inf());
+#if defined(__HIP_DEVICE_COMPILE__)
+        if (__all(idle)) continue;
+#else
+        if (idle) continue;
+#endif
+        HK_NOUNROLL for (int r = 0; r < 4; r++) acc = jac_dbl_ni(acc);
+        if (dig != 0 && !q_inf) {
+            Jac<F> e = tab.ld((dig < 0 ? -dig : dig) - 1);
+            if (dig < 0) e.y = F::neg(e.y);
+            acc = jac_add_ni(acc, e);
+        }
+    }
+}
+// q: lane's point, image and sign applied.  Table: 2 = dbl 1, 3 = 2 + P, 4 = dbl 2, 5 = 4 + P, 6 = dbl 3, 7 = 6 + P, 8 = dbl 4
+template <class F, class Tab>
+HK_HD void split_window_chain(const Affine<F>& q, const u32 (&m)[6], const Tab& tab, Jac<F>& acc) {
+    const bool q_inf = q.is_inf();
+    if (!q_inf) {
+        Jac<F> e = Jac<F>::from_affine(q);
+        tab.st(0, e);
+        HK_NOUNROLL for (int k = 2; k <= SPLIT_TABLE; k++) {
+            if (k & 1) e = jac_madd_ni(tab.ld(k - 2), q);
+            else e = jac_dbl_ni(tab.ld(k / 2 - 1));
+            tab.st(k - 1, e);
+        }
+    }
+    split_window_digits(q_inf, m, tab, acc);
+}
+
 #if defined(__HIPCC__)
+template <class F> struct SplitTabStrided {                     // entry k of lane (quad) t at tab[k lanes + t]
+    Jac<F>* __restrict__ tab;
+    size_t lanes, t;
+    __device__ __forceinline__ Jac<F> ld(int k) const { return ld_vec(&tab[(size_t)k * lanes + t]); }
+    __device__ __forceinline__ void st(int k, const Jac<F>& e) const { st_vec(&tab[(size_t)k * lanes + t], e); }
+};
+
 // ---- Fq2 on FOUR lanes -------------------------------------------------------------------------------------------------
 // The lanes of a quad (4 t .. 4 t + 3) hold the SAME Fq2 value; a product is ONE base-field product per lane - lane 0:
 // a0 b0, lane 1: a1 b1, lanes 2, 3: (a0 + a1)(b0 + b1) - quad-broadcast (DPP quad_perm, 3 N moves) and recombined by every
@@ -460,73 +528,34 @@ k_points_mul_split(SplitVecs<F> v, const Fr* __restrict__ scalars, u32 neg_all, 
         if (!q.is_inf()) {
             HK_NOUNROLL for (u32 k = 0; k < j; k++) q = EndoOf<F>::apply(q);
             if (negate) q.y = F::neg(q.y);
-            // 1P .. 8P: 2 = dbl 1, 3 = 2 + P, 4 = dbl 2, 5 = 4 + P, 6 = dbl 3, 7 = 6 + P, 8 = dbl 4
-            Jac<F> e = Jac<F>::from_affine(q);
-            st_vec(&tab[0 * lanes + t], e);
-            HK_NOUNROLL for (int k = 2; k <= SPLIT_TABLE; k++) {
-                if (k & 1) e = jac_madd_ni(ld_vec(&tab[(size_t)(k - 2) * lanes + t]), q);
-                else e = jac_dbl_ni(ld_vec(&tab[(size_t)(k / 2 - 1) * lanes + t]));
-                st_vec(&tab[(size_t)(k - 1) * lanes + t], e);
-            }
         }
-        bool q_inf = q.is_inf();
-        HK_NOUNROLL for (int d = ND - 1; d >= 0; d--) {
-            int dig = split_digit(m, d);
-            bool idle = q_inf || (dig == 0 && acc.is_inf());
-            if (__all(idle)) continue;                           // leading zero digits of the whole wave
-            HK_NOUNROLL for (int r = 0; r < 4; r++) acc = jac_dbl_ni(acc);
-            if (dig != 0 && !q_inf) {
-                u32 a = dig < 0 ? (u32)(-dig) : (u32)dig;
-                Jac<F> e = ld_vec(&tab[(size_t)(a - 1) * lanes + t]);
-                if (dig < 0) e.y = F::neg(e.y);
-                acc = jac_add_ni(acc, e);
-            }
-        }
+        split_window_chain(q, m, SplitTabStrided<F>{tab, lanes, t}, acc);
     }
     sh[tl] = acc;
     __syncthreads();
     if (valid && j == 0) {
         HK_NOUNROLL for (int k = 1; k < K; k++) acc = jac_add_ni(acc, sh[tl + k]);
-        XYZZ<F> o = XYZZ<F>::inf();
-        if (!acc.is_inf()) {
-            o.x = acc.x; o.y = acc.y;
-            o.zz = F::sqr(acc.z);
-            o.zzz = F::mul(o.zz, acc.z);
-        }
+        XYZZ<F> o = jac_to_xyzz(acc);
         if (lo) o = ec_madd_ni(o, ld_vec(&lo[i]));
         st_vec(&out[i], o);
     }
 }
-// out[0] = sum of n XYZZ points: one workgroup, strided partial sums, LDS tree (the tail of a SMALL one-off MSM:
-// hk_msm_g1 / _g2 over caller-supplied bases with n K <= SPLIT_MAX_LANES run as n element-wise products + this sum -
-// without shift tables a Pippenger pass ends in ~254 serial doublings, 3 ms in G1 and 8.5 ms in G2 whatever n)
+// out[g] = sum of in[g * seg .. (g + 1) * seg): one workgroup of T lanes per segment g = blockIdx.x, strided partial sums,
+// LDS tree.  One segment and T = PointsSum<F>::THREADS: the tail of a SMALL one-off MSM (hk_msm_g1 / _g2 over
+// caller-supplied bases with n K <= SPLIT_MAX_LANES run as n element-wise products + this sum - without shift tables a
+// Pippenger pass ends in ~254 serial doublings, 3 ms in G1 and 8.5 ms in G2 whatever n); T = 64: the commitments of
+// hk_commit_batch.
 template <class F> struct PointsSum { static constexpr int THREADS = sizeof(XYZZ<F>) > 256 ? 128 : 256; };   // LDS <= 64 KiB
-template <class F>
-__global__ void __launch_bounds__(PointsSum<F>::THREADS)
-k_points_sum(const XYZZ<F>* __restrict__ in, u32 n, XYZZ<F>* __restrict__ out) {
-    constexpr u32 T = PointsSum<F>::THREADS;
+template <class F, int T>
+__global__ void __launch_bounds__(T)
+k_points_sum_seg(const XYZZ<F>* __restrict__ in, u32 seg, XYZZ<F>* __restrict__ out) {
     __shared__ XYZZ<F> sh[T];
+    const XYZZ<F>* src = in + (size_t)blockIdx.x * seg;
     XYZZ<F> acc = XYZZ<F>::inf();
-    HK_NOUNROLL for (u32 i = threadIdx.x; i < n; i += T) acc = ec_add_ni(acc, ld_vec(&in[i]));
+    HK_NOUNROLL for (u32 i = threadIdx.x; i < seg; i += T) acc = ec_add_ni(acc, ld_vec(&src[i]));
     sh[threadIdx.x] = acc;
     __syncthreads();
     HK_NOUNROLL for (u32 off = T / 2; off > 0; off >>= 1) {
-        if (threadIdx.x < off) { XYZZ<F> t = ec_add_ni(sh[threadIdx.x], sh[threadIdx.x + off]); sh[threadIdx.x] = t; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) st_vec(out, sh[0]);
-}
-// out[g] = sum of in[g * seg .. (g + 1) * seg): one 64-lane workgroup per segment (the commitments of hk_commit_batch)
-template <class F>
-__global__ void __launch_bounds__(64)
-k_points_sum_seg(const XYZZ<F>* __restrict__ in, u32 seg, XYZZ<F>* __restrict__ out) {
-    __shared__ XYZZ<F> sh[64];
-    const XYZZ<F>* src = in + (size_t)blockIdx.x * seg;
-    XYZZ<F> acc = XYZZ<F>::inf();
-    HK_NOUNROLL for (u32 i = threadIdx.x; i < seg; i += 64) acc = ec_add_ni(acc, ld_vec(&src[i]));
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    HK_NOUNROLL for (u32 off = 32; off > 0; off >>= 1) {
         if (threadIdx.x < off) { XYZZ<F> t = ec_add_ni(sh[threadIdx.x], sh[threadIdx.x + off]); sh[threadIdx.x] = t; }
         __syncthreads();
     }

@@ -176,7 +176,7 @@ size_t MsmRun<F>::max_private_bytes() {
                         (const void*)k_msm_reduce_fused<F>, (const void*)k_msm_bucket_reduce<F>,
                         (const void*)k_msm_window_sum<F>, (const void*)k_msm_final<F>, (const void*)k_to_affine<F>,
                         (const void*)k_msm_build_tables<F>, (const void*)k_batch_affine<F>, (const void*)k_fb_table<F>,
-                        (const void*)k_fb_mul<Fr, F>, (const void*)k_scalar_mul_each<Fr, F>, (const void*)k_scalar_mul_endo<Fr, F>, (const void*)k_points_fold_endo<Fr, F>, (const void*)k_points_mul_split<Fr, F, true>, (const void*)k_points_mul_split<Fr, F, false>, (const void*)k_points_sum<F>, (const void*)k_points_sum_seg<F>,
+                        (const void*)k_fb_mul<Fr, F>, (const void*)k_scalar_mul_each<Fr, F>, (const void*)k_scalar_mul_endo<Fr, F>, (const void*)k_points_fold_endo<Fr, F>, (const void*)k_points_mul_split<Fr, F, true>, (const void*)k_points_mul_split<Fr, F, false>, (const void*)k_points_sum_seg<F, PointsSum<F>::THREADS>, (const void*)k_points_sum_seg<F, 64>,
                         (const void*)k_points_lincomb<Fr, F>};
     size_t m = 0;
     for (const void* k : ks) { size_t b = hk_private_bytes_of(k); if (b > m) m = b; }
@@ -263,7 +263,7 @@ hk_status MsmRun<F>::scalar_mul_each(hipStream_t s, const Affine<F>* pts, const 
 }
 
 // sum_i s_i P_i for a SHORT vector without tables: n element-wise products over the endomorphism (k_points_mul_split),
-// then one workgroup's sum (k_points_sum).  scalars: Montgomery (mont != 0) or canonical integers.
+// then one workgroup's sum (k_points_sum_seg over one segment).  scalars: Montgomery (mont != 0) or canonical integers.
 template <class F>
 hk_status MsmRun<F>::small_msm(hipStream_t s, const Affine<F>* bases, const void* scalars, int mont, u32 n, XYZZ<F>* tab,
                                XYZZ<F>* xy, XYZZ<F>* result) {
@@ -273,7 +273,7 @@ hk_status MsmRun<F>::small_msm(hipStream_t s, const Affine<F>* bases, const void
     SplitVecs<F> v = {};
     v.pts[0] = bases;
     launch_mul_split<Fr, typename F::Params, false>(s, v, 1u, (const Fr*)scalars, 0u, n, E, reinterpret_cast<Jac<F>*>(tab), xy, mont ? 1 : 0);
-    hipLaunchKernelGGL((k_points_sum<F>), dim3(1), dim3(PointsSum<F>::THREADS), 0, s, (const XYZZ<F>*)xy, n, result);
+    hipLaunchKernelGGL((k_points_sum_seg<F, PointsSum<F>::THREADS>), dim3(1), dim3(PointsSum<F>::THREADS), 0, s, (const XYZZ<F>*)xy, n, result);
     HK_HIP(hipGetLastError());
     return HK_OK;
 }
@@ -291,7 +291,7 @@ hk_status MsmRun<F>::small_msm_rows(hipStream_t s, const Affine<F>* bases, const
     v.pts[0] = bases;
     v.pts_mod = seg;
     launch_mul_split<Fr, typename F::Params, false>(s, v, 1u, (const Fr*)scalars, 0u, (u32)n, E, reinterpret_cast<Jac<F>*>(tab), xy, 1);
-    hipLaunchKernelGGL((k_points_sum_seg<F>), dim3(batch), dim3(64), 0, s, (const XYZZ<F>*)xy, seg, result);
+    hipLaunchKernelGGL((k_points_sum_seg<F, 64>), dim3(batch), dim3(64), 0, s, (const XYZZ<F>*)xy, seg, result);
     HK_HIP(hipGetLastError());
     return HK_OK;
 }

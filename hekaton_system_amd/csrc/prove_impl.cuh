@@ -70,9 +70,10 @@ __global__ void k_finish_ab(const XYZZ<Fq>* __restrict__ res_g1_all, const XYZZ<
     } else {
         // C = s*A + r*B1 + ML' + MH.  This kernel is the tail of every proof's latency, and its two variable-base products
         // were one lane's chain of 256 doublings + <= 128 additions (Straus over a joint table: 3 ms).  They now run as
-        // the short element-wise sweeps do (endo.cuh): A and B1 are normalised by lanes 0 and 1, then FOUR lanes take one
-        // GLV half each (s = s0 + s1 lambda on A, r = r0 + r1 lambda on B1: <= 131 bits) with a signed 4-bit window over
-        // 1P .. 8P and a Jacobian chain - 34 digits x (4 doublings + 1 add) - and lane 0 joins the four partial products.
+        // the short element-wise sweeps do: A and B1 are normalised by lanes 0 and 1, then FOUR lanes take one GLV half
+        // each (s = s0 + s1 lambda on A, r = r0 + r1 lambda on B1: <= 131 bits) with a table 1P .. 8P, built here straight
+        // in LDS, and the sweeps' digit loop (split_window_digits, endo.cuh: its wave vote counts the lanes that are in
+        // it, those of the four whose base is not at infinity); lane 0 joins the four partial products.
         __shared__ Affine<Fq> base[2];
         __shared__ Jac<Fq> tab[4][SPLIT_TABLE];
         __shared__ Jac<Fq> part[4];
@@ -104,16 +105,7 @@ __global__ void k_finish_ab(const XYZZ<Fq>* __restrict__ res_g1_all, const XYZZ<
                     e = (i & 1) ? jac_madd_ni(prev, q) : jac_dbl_ni(prev);
                     tab[t][i - 1] = e;
                 }
-                HK_NOUNROLL for (int d = ND - 1; d >= 0; d--) {
-                    int dig = split_digit(m, d);
-                    if (dig == 0 && acc.is_inf()) continue;
-                    HK_NOUNROLL for (int r4 = 0; r4 < 4; r4++) acc = jac_dbl_ni(acc);
-                    if (dig != 0) {
-                        Jac<Fq> e2 = tab[t][(dig < 0 ? -dig : dig) - 1];
-                        if (dig < 0) e2.y = Fq::neg(e2.y);
-                        acc = jac_add_ni(acc, e2);
-                    }
-                }
+                split_window_digits(false, m, SplitTabRow<Fq>{tab[t]}, acc);
             }
             part[t] = acc;
         }
@@ -121,14 +113,8 @@ __global__ void k_finish_ab(const XYZZ<Fq>* __restrict__ res_g1_all, const XYZZ<
         if (t == 0) {
             Jac<Fq> sum = part[0];
             HK_NOUNROLL for (int i = 1; i < 4; i++) sum = jac_add_ni(sum, part[i]);
-            XYZZ<Fq> Cc = XYZZ<Fq>::inf();
-            if (!sum.is_inf()) {
-                Cc.x = sum.x; Cc.y = sum.y;
-                Cc.zz = Fq::sqr(sum.z);
-                Cc.zzz = Fq::mul(Cc.zz, sum.z);
-            }
             // c1[4]: -C^_0 of an evaluation-basis key (z_0 = 1 is no ext scalar), infinity otherwise
-            st_vec(part_c, ec_madd_ni(ec_add_ni(Cc, ld_vec(&res_g1[2])), ld_vec(&c1[4])));
+            st_vec(part_c, ec_madd_ni(ec_add_ni(jac_to_xyzz(sum), ld_vec(&res_g1[2])), ld_vec(&c1[4])));
         }
     }
 }

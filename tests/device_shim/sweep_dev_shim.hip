@@ -1,6 +1,6 @@
 // Device-compiled view of the PRODUCT's group sweeps over caller-supplied points, ONE kernel launch per call (hipcc, gfx950):
 // k_fb_table, k_fb_mul, k_points_lincomb, k_scalar_mul_each (fixed_base.cuh), k_scalar_mul_endo, k_points_fold_endo,
-// k_points_mul_split in every form, k_points_sum, k_points_sum_seg (endo.cuh).  Through the library these kernels are
+// k_points_mul_split in every form, k_points_sum_seg at both sizes (endo.cuh).  Through the library these kernels are
 // reached only behind MsmRun's choices (the form by n, the window table from the base, the normalisation behind each); here a
 // test hands a kernel the table, the vectors, the form and the launch shape it wants and reads back what the kernel stored.
 // Test-only; never part of libhekaton.
@@ -142,25 +142,14 @@ int mul_split(int quad, int uniform, const void* lo, const void* pts, const void
     return finish(out, o, (size_t)vectors * n * sizeof(XYZZ<F>));
 }
 
-template <class F>
-int points_sum(const void* in, unsigned n, void* out) {
-    DevBufs d;
-    const XYZZ<F>* i;
-    XYZZ<F>* o;
-    SHIM_GET(&i, (size_t)n * sizeof(XYZZ<F>), in);
-    SHIM_GET(&o, sizeof(XYZZ<F>), nullptr);
-    hipLaunchKernelGGL((k_points_sum<F>), dim3(1), dim3(PointsSum<F>::THREADS), 0, 0, i, n, o);
-    return finish(out, o, sizeof(XYZZ<F>));
-}
-
-template <class F>
+template <class F, int T>
 int points_sum_seg(const void* in, unsigned seg, unsigned batch, void* out) {
     DevBufs d;
     const XYZZ<F>* i;
     XYZZ<F>* o;
     SHIM_GET(&i, (size_t)seg * batch * sizeof(XYZZ<F>), in);
     SHIM_GET(&o, (size_t)batch * sizeof(XYZZ<F>), nullptr);
-    hipLaunchKernelGGL((k_points_sum_seg<F>), dim3(batch), dim3(64), 0, 0, i, seg, o);
+    hipLaunchKernelGGL((k_points_sum_seg<F, T>), dim3(batch), dim3(T), 0, 0, i, seg, o);
     return finish(out, o, (size_t)batch * sizeof(XYZZ<F>));
 }
 
@@ -184,8 +173,8 @@ int SHIM_FN(mul_split)(int quad, int uniform, const void* lo, const void* pts, c
                        unsigned pts_mod, unsigned vectors, int scalars_mont, void* out) {
     return mul_split<ShimFr, ShimF>(quad, uniform, lo, pts, scalars, neg_all, n, pts_mod, vectors, scalars_mont, out);
 }
-int SHIM_FN(points_sum)(const void* in, unsigned n, void* out) { return points_sum<ShimF>(in, n, out); }
-int SHIM_FN(points_sum_seg)(const void* in, unsigned seg, unsigned batch, void* out) { return points_sum_seg<ShimF>(in, seg, batch, out); }
+int SHIM_FN(points_sum)(const void* in, unsigned n, void* out) { return points_sum_seg<ShimF, PointsSum<ShimF>::THREADS>(in, n, 1, out); }
+int SHIM_FN(points_sum_seg)(const void* in, unsigned seg, unsigned batch, void* out) { return points_sum_seg<ShimF, 64>(in, seg, batch, out); }
 int SHIM_FN(sum_threads)() { return PointsSum<ShimF>::THREADS; }
 int SHIM_FN(split_elems)(int quad) {
     if (quad) return QuadOf<ShimF>::has ? 64 / (4 * EndoOf<ShimF>::K) : 0;
@@ -216,7 +205,7 @@ static bool n_ok(unsigned n) { return n != 0 && n <= SWEEP_MAX_N; }
 extern "C" {
 // group: 0 bn254 G1, 1 bn254 G2, 2 bls G1, 3 bls G2 throughout.  Every call returns 0 or minus the first failing hipError_t
 // (hipErrorInvalidValue for arguments outside a kernel's contract: nothing is launched then).
-// PointsSum<F>::THREADS: the workgroup of k_points_sum
+// PointsSum<F>::THREADS: the workgroup of k_points_sum_seg over one segment (the small MSM's sum)
 int dshim_sweep_sum_threads(int group) { SHIM_DISPATCH(group, sum_threads()) }
 // elements per 64-lane workgroup of k_points_mul_split: quad = 0 the K-lane form, 1 the quad form (0 for a G1 group)
 int dshim_sweep_split_elems(int group, int quad) { SHIM_DISPATCH(group, split_elems(quad)) }

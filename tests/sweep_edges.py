@@ -5,7 +5,7 @@ like tests/msm_edges.py, whose groups, pool of bases and `point` cache it shares
 
 Every point is k G with a known k, so every expected value is ONE oracle multiplication of a scalar combination mod r
 (msm_edges.point).  The case lists keep their discrete logs periodic in the element index, so that a vector of 65 elements
-costs a dozen oracle multiplications, not 65.  The walks the kernels make (k_fb_mul's digit walk, k_points_sum's strided loop
+costs a dozen oracle multiplications, not 65.  The walks the kernels make (k_fb_mul's digit walk, k_points_sum_seg's strided loop
 and LDS tree) are modelled here in discrete logs, so that a family can say "this add meets P == Q" and assert it.
 """
 import random
@@ -188,7 +188,7 @@ def sum_family(gid, name, n, slot=0):
 
 
 def sum_walk(logs, T, r):
-    """k_points_sum (T lanes; k_points_sum_seg: T = 64) in discrete logs -> (result log, events of the LDS tree): an event is
+    """k_points_sum_seg (T lanes: PointsSum<F>::THREADS over one segment, or 64) in discrete logs -> (result log, events of the LDS tree): an event is
     (off, 'dbl' | 'cancel') where a tree add met equal or opposite finite operands"""
     acc = [sum(logs[t::T]) % r for t in range(T)]
     events = []

@@ -4,7 +4,7 @@ tests/test_sweep_edges_cpu.py asserts), in all four groups.
 
 Through the library these kernels sit behind MsmRun's choices: the window table always comes from the base, the form of the
 element-wise product from n, and only random vectors reach the sums.  Here a crafted table makes k_fb_mul's mixed add double
-and cancel in mid-walk, equal and opposite points meet at every level of k_points_sum's LDS tree, the trailing add of the
+and cancel in mid-walk, equal and opposite points meet at every level of k_points_sum_seg's LDS tree, the trailing add of the
 split forms meets lo = c hi and lo = -c hi, and every size sits around the workgroup of its kernel (the sizes come from the
 shim's getters).  Every result is compared exactly with the big-int oracle: points are k G with known k, the expected value
 is ((combination of the logs) mod r) G.  Every XYZZ result must also satisfy zz^3 = zzz^2.
@@ -110,7 +110,7 @@ def test_lincomb_cases(gid, k, n, shim):
         _check(got, want, "g%d lincomb %s k=%d n=%d" % (gid, name, k, n))
 
 
-# ---- k_points_sum / k_points_sum_seg ------------------------------------------------------------------------------------------
+# ---- k_points_sum_seg: one segment of PointsSum<F>::THREADS lanes, segments of 64 -----------------------------------------
 @pytest.mark.parametrize("gid", range(4))
 def test_points_sum_around_the_workgroup(gid, shim):
     io = Io(gid)
@@ -119,7 +119,7 @@ def test_points_sum_around_the_workgroup(gid, shim):
         for name in se.SUM_FAMILIES:
             fam = se.sum_family(gid, name, n)
             got = io.from_xyzz(shim.points_sum(gid, io.pb, io.xyzz(fam)))
-            assert got == io.want([sum(k for k, _ in fam)]), "g%d k_points_sum %s n=%d" % (gid, name, n)
+            assert got == io.want([sum(k for k, _ in fam)]), "g%d k_points_sum_seg, one segment, %s n=%d" % (gid, name, n)
 
 
 @pytest.mark.parametrize("gid", range(4))

@@ -1,8 +1,11 @@
 """CPU: every premise tests/sweep_edges.py states - the single-byte scalars have one non-zero window, the crafted fixed-base
 tables make the digit walk double or cancel where intended, the "equal partial sums" vectors meet P == Q at every level of
-the LDS tree, the K-lane form reads a magnitude whole up to 0x77..7 and no further (host mirror of one lane:
-tests/host_shim/field_shim.cpp), and the discrete-log reference agrees with the oracle's own add / mul / msm."""
+the LDS tree, the K-lane form reads a magnitude whole up to 0x77..7 and no further (the kernels' own split_window_chain
+compiled for the host: tests/host_shim/field_shim.cpp; once more, under the sanitizers and over both table layouts, as the
+stand-alone tests/host_shim/split_chain_driver.cpp), and the discrete-log reference agrees with the oracle's own
+add / mul / msm."""
 import ctypes
+import subprocess
 
 import numpy as np
 import pytest
@@ -133,6 +136,31 @@ def test_one_lane_of_the_k_lane_form_reads_a_magnitude_up_to_the_limit(gid, host
         assert dec(_split_mul(host_shim, gid, pb, m)) == me.point(gid, m * k), (gid, hex(m))
     for m in (lim + 1, 1 << 190):
         assert dec(_split_mul(host_shim, gid, pb, m)) != me.point(gid, m * k), (gid, hex(m))
+
+
+def test_window_chain_runs_clean_under_the_sanitizers_and_gives_the_shim_bytes(host_shim, tmp_path):
+    """split_window_chain + jac_to_xyzz as a stand-alone program built with -fsanitize=address,undefined, its tables in a row
+    per lane and in one block strided by lane: 0x77..7 (the largest magnitude split_mag_fits admits), 0, 1 and 8 times a
+    point of each group, and times the point at infinity, exit clean and print shim_split_mul's bytes."""
+    exe = host_build.build("split_chain_driver.cpp", tmp_path / "split_chain_driver", "-O1", "-g", "-Wall", "-Werror",
+                           "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
+    pts = {gid: [se.Io(gid).aff([k]) for k in me.pool_ks(gid)[:4]] for gid in range(4)}
+    text = "".join("%d %s\n" % (gid, b"".join(bytes(p) for p in pts[gid]).hex()) for gid in range(4))
+    run = subprocess.run([exe], input=text, capture_output=True, text=True)
+    assert run.returncode == 0 and run.stderr == "", run.stderr
+    lines = [l.split() for l in run.stdout.splitlines()]
+    assert [(int(g), int(i), int(t)) for g, i, t, _ in lines] == [(g, i, t) for g in range(4) for i in (0, 1) for t in range(4)]
+    for g, inf, t, got in lines:
+        gid, t = int(g), int(t)
+        assert len({bytes(p) for p in pts[gid]}) == 4
+        pb = bytes(len(pts[gid][t])) if int(inf) else bytes(pts[gid][t])
+        m = [se.mag_limit(gid), 0, 1, 8][t]
+        assert bytes.fromhex(got) == _split_mul(host_shim, gid, pb, m), (gid, inf, t)
+        if int(inf) or m == 0:
+            assert bytes.fromhex(got) == bytes(len(pb))
+        elif m in (1, 8):                                    # independent of the shim: the oracle's multiple
+            assert se.Io(gid).dec(bytes.fromhex(got)) == me.point(gid, m * me.pool_ks(gid)[t]), (gid, t)
+            assert m != 1 or bytes.fromhex(got) == pb
 
 
 @pytest.mark.parametrize("gid", range(4))

@@ -30,7 +30,7 @@ Io = se.Io
 @pytest.mark.parametrize("gid", range(4))
 def test_msm_families_on_the_small_path(gid, ctx_bn254, ctx_bls, monkeypatch):
     """the families of test_plain_msm_families_through_the_bucket_pass at n = 300, without HK_MSM_NO_SMALL: k_points_mul_split
-    and k_points_sum see every digit extreme, one base under many scalars, bases that cancel pairwise or are at infinity and
+    and k_points_sum_seg see every digit extreme, one base under many scalars, bases that cancel pairwise or are at infinity and
     all-zero scalars; "one base, one scalar" at n = T and 2 T makes every add of the LDS tree a doubling.  Through hk_msm_g*
     and through a resident set (short: no tables, the same path), in both scalar forms."""
     monkeypatch.delenv("HK_MSM_NO_SMALL", raising=False)
@@ -88,7 +88,7 @@ def _device_bases(io, ctx, ks, tag):
 
 @pytest.mark.parametrize("gid,n", [(0, 32768), (0, 32769), (1, 16384), (1, 16385)])
 def test_msm_on_both_sides_of_the_small_path_boundary(gid, n, ctx_bn254, monkeypatch):
-    """n K = 65 536 is the last size hk_msm_g* runs as element-wise products + k_points_sum; one base more takes the bucket
+    """n K = 65 536 is the last size hk_msm_g* runs as element-wise products + k_points_sum_seg; one base more takes the bucket
     pass.  Both give ((sum s_i k_i) mod r) G."""
     monkeypatch.delenv("HK_MSM_NO_SMALL", raising=False)
     io = Io(gid)
