@@ -14,8 +14,11 @@ computed - so the equations are restated here from aggregation.rs:138-345 read f
 
 Both objects have a wire form in ark_serialize.py's framing (u64 little-endian lengths, GT as 12 canonical Fq, points
 uncompressed, Fr canonical); the layout is this build's own (PARITY UNPINNED: `ripp` is absent).  Order-r membership of
-the proof's GT elements is NOT tested - `Tipp.verify` has no such test either; every power of a GT element that comes from
-the proof is taken with the plain chain (in_gt=False), which is a power for any element of Fq12."""
+the GT elements of key and proof is tested where they are READ: `deserialize` with a context runs hk_gt_check over every
+member, as it runs hk_points_check over the points.  `verify_aggregate` itself tests nothing of the
+kind and by default assumes nothing - every power of a GT element that comes from the proof is taken with the plain chain
+(in_gt=False), which is a power for any element of Fq12; `members_in_gt=True` is the caller's statement that the readers'
+check (and the caller's own of `super_com`) has been made, and buys the Frobenius-split powers."""
 from dataclasses import dataclass
 
 import numpy as np
@@ -113,6 +116,18 @@ def _check_points(ctx, g1, g2, what):
             raise ValueError("%s: a G%d point is not on the curve or not in the subgroup" % (what, group))
 
 
+def _check_gt(ctx, F, members, what):
+    """hk_gt_check over the GT members read, in one call: each non-zero and of order dividing r, or ValueError."""
+    if ctx is None or not members:
+        return
+    if not ctx.gt_check(np.frombuffer(b"".join(F.encode(x) for x in members), np.uint8)).all():
+        raise ValueError("%s: a GT member is not in the order-r subgroup" % what)
+
+
+def _com_members(com):
+    return [com.t, com.u] + ([com.ip] if com.ip is not None else [])
+
+
 @dataclass
 class AggVerdict:
     ok: bool
@@ -170,6 +185,9 @@ class AggVerifyingKey:
 
     @classmethod
     def deserialize(cls, ctx, curve, data):
+        """ValueError for what does not parse and - with a context - for a point off its curve or outside the subgroup, or
+        a GT member (the n_s + 3 commitments' two each, every alpha_beta[c]) outside the order-r subgroup: one
+        hk_points_check per group, then one hk_gt_check.  ctx=None checks neither."""
         return _wire(lambda: cls._read(ctx, curve, data))
 
     @classmethod
@@ -196,6 +214,7 @@ class AggVerifyingKey:
         alpha_beta = [_get_gt(r, F) for _ in range(n_classes)]
         if r.remaining():
             raise ValueError("trailing bytes")
+        _check_gt(ctx, F, [m for com in coms for m in _com_members(com)] + alpha_beta, "verifying key")
         class_of = np.repeat(np.array([c for c, _ in runs], np.uint32), [length for _, length in runs])
         return cls(curve, n, n_s, vk, coms[:n_s], coms[n_s], coms[n_s + 1], coms[n_s + 2], class_of, alpha_beta)
 
@@ -232,7 +251,8 @@ class AggProof:
     @classmethod
     def deserialize(cls, ctx, curve, data):
         """ValueError for a length that does not match, trailing bytes, a non-canonical field element, a number of rounds
-        other than log2 n, and - with a context - a point off its curve or outside the subgroup."""
+        other than log2 n, and - with a context - a point off its curve or outside the subgroup, or a GT member (com_ab's
+        three, com_c's two, the 16 cross terms, six per round) outside the order-r subgroup.  ctx=None checks neither."""
         return _wire(lambda: cls._read(ctx, curve, data))
 
     @classmethod
@@ -261,15 +281,22 @@ class AggProof:
         if r.remaining():
             raise ValueError("trailing bytes")
         _check_points(ctx, by_group[1], by_group[2], "proof")
+        _check_gt(ctx, F, _com_members(com_ab) + _com_members(com_c) + [e for row in cross for e in row] +
+                  [rd[k] for rd in rounds for k in _ROUND_KEYS], "proof")
         return cls(curve, n, com_ab, com_c, cross, tipp)
 
 
-def verify_aggregate(ctx, avk, super_com, pub_inputs, proof, pt, mem_type=None, trace=None):
+def verify_aggregate(ctx, avk, super_com, pub_inputs, proof, pt, mem_type=None, trace=None, members_in_gt=False):
     """True iff `proof` (AggProof) aggregates n accepted subcircuit proofs of the job `avk` (AggVerifyingKey) describes, for
     the stage-0 super commitment `super_com` (IppCom) and the public inputs `pub_inputs` (ints).  pt: a fresh
     merlin.Transcript with the aggregator's label.  mem_type (transcript.ROM / RAM): the leading public inputs must be the
     challenges the super commitment hashes to.  Returns AggVerdict(ok, reason): reason names the first check that failed.
-    trace: a dict that receives the values the verifier derived (twist, s, t, sigma, z_alpha_beta, com_lr, z_lr)."""
+    trace: a dict that receives the values the verifier derived (twist, s, t, sigma, z_alpha_beta, com_lr, z_lr).
+    members_in_gt: the caller states that every GT member of `avk` and `proof` lies in the order-r subgroup - which
+    `AggVerifyingKey.deserialize` and `AggProof.deserialize` establish when they are given a context (hk_gt_check) - AND
+    that `super_com`, the caller's own value that no reader has seen, does too (`ctx.gt_check` on its two members where it
+    is not the caller's own pairing output).  com_lr, z_lr and TIPP's fold check then take the Frobenius-split powers
+    (in_gt = 1) instead of the plain 254-step chain.  The default keeps the plain chain and assumes nothing."""
     from . import tipa
     curve = avk.curve
     F, fc, r_mod = GtField(curve), FrCodec(curve), CURVE_PARAMS[curve]["r"]
@@ -290,7 +317,8 @@ def verify_aggregate(ctx, avk, super_com, pub_inputs, proof, pt, mem_type=None, 
     pt.append_serializable(b"C-commitment", proof.com_c.serialize_uncompressed())
     pt.append_serializable(b"D-commitment", super_com.serialize_uncompressed())
     twist = trace["twist"] = pt.challenge_scalar(b"r-random-fiatshamir", r_mod)
-    # 3. prod_i e(alpha_i, beta_i)^(twist^i) from one pairing per class: the bases come from the key, so they are in GT
+    # 3. prod_i e(alpha_i, beta_i)^(twist^i) from one pairing per class: the bases come from the key - the caller's own, or read
+    # with a context, which checks them (hk_gt_check) - so they are in GT
     n_classes = len(avk.alpha_beta)
     sigma = ctx.class_power_sums(twist, avk.class_of, n_classes)
     zab = ctx.gt_pow_prod(np.frombuffer(b"".join(F.encode(e) for e in avk.alpha_beta), np.uint8), sigma, n_classes, True)
@@ -306,20 +334,21 @@ def verify_aggregate(ctx, avk, super_com, pub_inputs, proof, pt, mem_type=None, 
     t = trace["t"] = pt.challenge_scalar(b"t-random-fiatshamir", r_mod)
     s2, s3, t2, t3 = s * s % r_mod, s * s * s % r_mod, t * t % r_mod, t * t * t % r_mod
     # 6. the commitments (:171-174, :320-324): the prepared input's from the key alone; com_lr mixes in the proof's and the
-    # statement's, so its powers take the plain chain
+    # statement's, so its powers take the plain chain unless the caller vouches for them (members_in_gt)
+    in_gt = bool(members_in_gt)
     com_in = IppCom.lincomb([(avk.com_s[0], None)] + [(avk.com_s[1 + j], x[j]) for j in range(len(x))])
     com_d = IppCom(F, super_com.t, super_com.u, ctx=ctx)
     com_lr = trace["com_lr"] = IppCom.lincomb([(proof.com_ab, None), (com_in, s), (com_d, s2), (proof.com_c, s3), (avk.com_h, t),
-                                               (avk.com_delta0, t2), (avk.com_delta1, t3)], in_gt=False)
+                                               (avk.com_delta0, t2), (avk.com_delta1, t3)], in_gt=in_gt)
     # 7. z_lr = prod_ij cross[i][j]^(s^i t^j)
     exps = [pow(s, i, r_mod) * pow(t, j, r_mod) % r_mod for i in range(4) for j in range(4)]
     out = ctx.gt_pow_prod(np.frombuffer(b"".join(F.encode(z[i][j]) for i in range(4) for j in range(4)), np.uint8), fc.enc(exps),
-                          16, False)
+                          16, in_gt)
     z_lr = trace["z_lr"] = F.decode(out[0])
     # 8. TIPA::verify
     T = tipa.Tipp(ctx, curve)
     try:
-        ok = T.verify(avk.tipp_vk, com_lr, z_lr, twist, proof.tipp)
+        ok = T.verify(avk.tipp_vk, com_lr, z_lr, twist, proof.tipp, in_gt=in_gt)
     finally:
         T.pool.shutdown()
     return AggVerdict(True, ACCEPTED) if ok else AggVerdict(False, R_TIPP)

@@ -250,6 +250,14 @@ _SIGNATURES = {
 }
 EXPORTS = list(_SIGNATURES)
 
+# What the companion header include/hekaton_gt.h declares, in the same idiom: load() sets these as it sets the table above
+# and refuses a library that lacks one.  A table of its own only while tests/test_capi_signatures_cpu.py pins the first to
+# hekaton.h's names: the two fold together with the two headers, in a change that may touch that test
+# (tests/test_gt_check_cpu.py holds this one against its header).
+_SIGNATURES_GT = {
+    "hk_gt_check": [_vp, _vp, _sz, _vp],
+}
+
 _lib = None
 
 
@@ -263,7 +271,7 @@ def load():
         raise ImportError("libhekaton.so not built (%s): run `python -c 'import __graft_entry__ as g; "
                           "g.build()'` — there is no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, sig in _SIGNATURES.items():
+    for name, sig in list(_SIGNATURES.items()) + list(_SIGNATURES_GT.items()):
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = sig if isinstance(sig, tuple) else (sig, _i)
     _lib = lib
@@ -1045,6 +1053,16 @@ class Context:
         n = n if n is not None else _size(pts) // pb
         ok = np.zeros(n, dtype=np.uint8)
         check(fn(self.handle, ptr(pts) if n else None, n, ok.ctypes.data), fn.__name__)
+        return ok
+
+    def gt_check(self, gts, n=None):
+        """hk_gt_check: is each Fq12 value an element of GT - not zero, of order dividing r?  What a verifier asks of values
+        it read from untrusted bytes before it treats them as pairing outputs (gt_pow's in_gt=True is a power only there).
+        gts: n x gt_bytes Montgomery bytes (uint8 array or DeviceBuffer).  Returns np.uint8[n] of 0 / 1."""
+        gts = _hd(gts)
+        n = n if n is not None else _size(gts) // self.gt_bytes
+        ok = np.zeros(n, dtype=np.uint8)
+        check(self.lib.hk_gt_check(self.handle, ptr(gts) if n else None, n, ok.ctypes.data), "hk_gt_check")
         return ok
 
     def field_sqrt(self, which, data):

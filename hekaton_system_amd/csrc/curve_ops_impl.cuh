@@ -162,6 +162,7 @@ struct Ops final : CurveOps {
     hk_status pairing_pairs(hk_ctx*, const void* const*, size_t, const void* const*, size_t, const uint32_t*, const uint32_t*, size_t,
                             size_t, void*) override;
     hk_status gt_pow(hk_ctx*, const void*, const void*, size_t, void*, int, size_t) override;
+    hk_status gt_check(hk_ctx*, const void*, size_t, unsigned char*) override;
     // prove_impl.cuh
     hk_status commit(hk_ctx*, const hk_pk*, size_t, const void*, size_t, const void*, void*) override;
     hk_status commit_batch(hk_ctx*, const hk_pk*, size_t, const void*, size_t, const void*, size_t, void*) override;

@@ -561,6 +561,10 @@ hk_status hk_points_check_g2(hk_ctx* ctx, const void* points, size_t n, uint8_t*
     if (!ctx || (n && (!points || !ok))) return HK_ERR_ARG;
     return ctx->ops->points_check(ctx, 2, points, n, ok);
 }
+hk_status hk_gt_check(hk_ctx* ctx, const void* fq12_in, size_t n, uint8_t* ok) {          // include/hekaton_gt.h
+    if (!ctx || (n && (!fq12_in || !ok))) return HK_ERR_ARG;
+    return ctx->ops->gt_check(ctx, fq12_in, n, ok);
+}
 hk_status hk_ctx_gt_bytes(const hk_ctx* ctx, size_t* gt) {
     if (!ctx || !gt) return HK_ERR_ARG;
     *gt = ctx->ops->gt_bytes;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/hekaton.h"
+#include "../../include/hekaton_gt.h"
 #include "coalesce.h"
 #include "msm.cuh"
 #include "stream_plan.h"
@@ -207,6 +208,7 @@ struct CurveOps {
                                     const uint32_t* pair_lhs, const uint32_t* pair_rhs, size_t n_pairs, size_t n, void* out) = 0;
     virtual hk_status gt_pow(hk_ctx*, const void* gt_in, const void* scalars, size_t n, void* gt_out, int in_gt,
                              size_t group_len) = 0;
+    virtual hk_status gt_check(hk_ctx*, const void* fq12_in, size_t n, unsigned char* ok) = 0;
     // prove_impl.cuh
     virtual hk_status commit(hk_ctx*, const hk_pk*, size_t stage, const void* w, size_t n, const void* kappa,
                              void* out) = 0;

@@ -117,6 +117,8 @@ struct PairRun {
     // in_gt: the elements lie in GT (order r) - the exponent is then split along the Frobenius (k_gt_pow_endo)
     static hk_status gt_pow(hipStream_t s, const Fp12<P>* in, const void* scalars_mont, u32 n, Fp12<P>* out, bool in_gt);
     static hk_status gt_prod(hipStream_t s, const Fp12<P>* in, u32 len, u32 groups, Fp12<P>* out);
+    // ok[e] = 1 iff in[e] is in GT: non-zero and of order dividing r (k_gt_check; device pointers)
+    static hk_status gt_check(hipStream_t s, const Fp12<P>* in, u32 n, unsigned char* ok);
 };
 
 // CP-Groth16 verification (verify.cuh): the hk_vk_* / hk_verify_batch / hk_points_check_* entry points of a curve;

@@ -31,6 +31,16 @@ hk_status PairRun<P>::gt_pow(hipStream_t s, const Fp12<P>* in, const void* scala
     return HK_OK;
 }
 
+template <class P>
+hk_status PairRun<P>::gt_check(hipStream_t s, const Fp12<P>* in, u32 n, unsigned char* ok) {
+    if (n == 0) return HK_OK;
+    size_t lds = sizeof(WaveArea<P>) + 3 * WV_SLOT * sizeof(Fp<P>);
+    hipLaunchKernelGGL((k_gt_check<P>), dim3(n), dim3(64), lds, s, in, n, ok);
+    HK_DBG(s, "k_gt_check");
+    HK_HIP(hipGetLastError());
+    return HK_OK;
+}
+
 // out[g] = prod_{j < len} in[g * len + j]: one wave per group on the wave multiplier (the tree kernel with one group per row)
 template <class P>
 hk_status PairRun<P>::gt_prod(hipStream_t s, const Fp12<P>* in, u32 len, u32 groups, Fp12<P>* out) {
@@ -46,7 +56,8 @@ template <class P>
 size_t PairRun<P>::max_private_bytes() {
     const void* ks[] = {(const void*)k_pair_lines<Fp2<P>>, (const void*)k_pair_lines<Fp2Q<P>>, (const void*)k_pair_tree_lines<P>, (const void*)k_pair_tree<P>,
                         (const void*)k_pair_horner<P>,
-                        (const void*)k_gt_pow<P, typename ScalarOfQ<P>::type>, (const void*)k_gt_pow_endo<P, typename ScalarOfQ<P>::type>};
+                        (const void*)k_gt_pow<P, typename ScalarOfQ<P>::type>, (const void*)k_gt_pow_endo<P, typename ScalarOfQ<P>::type>,
+                        (const void*)k_gt_check<P>};
     const void* serial[] = {(const void*)k_pair_miller<P>, (const void*)k_f12_product<P>, (const void*)k_final_exp<P>};
     size_t m = 0;
     for (const void* k : ks) { size_t b = hk_private_bytes_of(k); if (b > m) m = b; }

@@ -1,6 +1,6 @@
 // pairing_ops.cuh — pairing products and GT powers over caller-supplied vectors (PairRun, msm_driver.cuh).  Defines
-// Ops<C>::pairing_products (hk_pairing_products, hk_multi_pairing), pairing_pairs (hk_pairing_pairs) and gt_pow (hk_gt_pow,
-// hk_gt_pow_prod, hk_fq12_pow).
+// Ops<C>::pairing_products (hk_pairing_products, hk_multi_pairing), pairing_pairs (hk_pairing_pairs), gt_pow (hk_gt_pow,
+// hk_gt_pow_prod, hk_fq12_pow) and gt_check (hk_gt_check).
 #pragma once
 #include "curve_ops_impl.cuh"
 #include "group_ops.cuh"      // GatherRows, k_gather_rows
@@ -115,6 +115,24 @@ hk_status Ops<C>::gt_pow(hk_ctx* ctx, const void* gt_in, const void* scalars, si
     HK_TRY(PairRun<P>::gt_pow(L->stream, (const GT*)in[0].p, in[1].p, (u32)n, pw, in_gt != 0));
     if (group_len > 1) HK_TRY(PairRun<P>::gt_prod(L->stream, pw, (u32)group_len, (u32)n_out, (GT*)to.p));
     HK_TRY(stage_download(L, &to, 1));
+    return L->settle();
+}
+
+// hk_gt_check: ok[i] = 1 iff fq12_in[i] is an element of GT (k_gt_check, one wavefront per element)
+template <class C>
+hk_status Ops<C>::gt_check(hk_ctx* ctx, const void* fq12_in, size_t n, unsigned char* ok) {
+    typedef typename Fq::Params P;
+    typedef Fp12<P> GT;
+    if (n == 0) return HK_OK;
+    if (n >= ((size_t)1 << 31)) return HK_ERR_ARG;                 // one workgroup per element: grid.x
+    Staged io[2] = {staged(fq12_in, n * sizeof(GT)), staged(ok, n)};
+    LaneGuard g(ctx);
+    Lane* L = g.lane;
+    if (!L) return HK_ERR_DEVICE;
+    HK_TRY(L->carve([&](Carve& c) { stage_carve(c, io, 2); }));
+    HK_TRY(stage_upload(L, io, 1));
+    HK_TRY(PairRun<P>::gt_check(L->stream, (const GT*)io[0].p, (u32)n, (unsigned char*)io[1].p));
+    HK_TRY(stage_download(L, io + 1, 1));
     return L->settle();
 }
 

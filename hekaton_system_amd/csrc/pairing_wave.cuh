@@ -203,6 +203,20 @@ struct WaveF12 {
         if (lane < 13) dst[lane] = v;
         sync();
     }
+    // a == b / a == 0 as field elements, the same answer on every lane: lane k < 12 compares coefficient k on canonical
+    // representatives (the slots hold lazy ones; Fq::operator== and is_zero reduce), one ballot collects them.  Reads only:
+    // every helper that wrote a or b ended on its barrier, and the wave's LDS operations complete in program order, so no
+    // barrier is needed before whatever overwrites the slots next.
+    static __device__ __forceinline__ bool equal(const Fq* a, const Fq* b) {
+        u32 lane = threadIdx.x;
+        bool ne = lane < 12 && !(a[lane] == b[lane]);
+        return __ballot(ne) == 0;
+    }
+    static __device__ __forceinline__ bool is_zero(const Fq* a) {
+        u32 lane = threadIdx.x;
+        bool nz = lane < 12 && !a[lane].is_zero();
+        return __ballot(nz) == 0;
+    }
     // dst = a^(q^K), K = 1..3: lane 2j + c computes component c of (Fq2 coefficient j, conjugated when K is odd) * const_j
     template <int K>
     static __device__ __noinline__ void frob(Fq* dst, const Fq* a) {
@@ -615,6 +629,59 @@ k_gt_pow_endo(const Fp12<P>* __restrict__ in, const Fr* __restrict__ scalars_mon
         if (m) W::mul(acc, acc, tab + m * WV_SLOT, w);
     }
     W::store(&out[blockIdx.x], acc);
+}
+
+// ok[e] = 1 iff in[e] lies in GT, the order-r subgroup of Fq12^*: one wave per element.  With q the base prime, t the trace
+// and Phi_12(q) = q^4 - q^2 + 1 the test is
+//   (1) x != 0 (and every coefficient is a canonical Fq: anything else is no field element and is refused),
+//   (2) x^(q^4) * x == x^(q^2): x lies in the cyclotomic subgroup (two frob<2>, one product, no inversion),
+//   (3) x^q == x^(t - 1): t - 1 = 6 u^2 on BN254 (pow_x twice - u's sign cancels - then y -> (y^2 y)^2), u on BLS12-381
+//       (exp_by_x, conjugation included).
+// (2) and (3) give ord(x) | gcd(Phi_12(q), q - (t - 1)) = r on both curves.  (2) is also what
+// makes (3)'s chain a power at all - cyc_sqr and conjugation-as-inverse hold only on the cyclotomic subgroup - so an
+// element that fails (1) or (2) is refused before the chain: the ballots are the same on every lane, the exit is uniform
+// and no lane waits at a barrier the others never reach.  Zero would pass (2) and (3) as 0 == 0: (1) refuses it.
+template <class P>
+__global__ void __launch_bounds__(64)
+k_gt_check(const Fp12<P>* __restrict__ in, u32 n, unsigned char* __restrict__ ok) {
+    extern __shared__ unsigned char pair_lds[];
+    typedef WaveF12<P> W;
+    typedef Fp<P> Fq;
+    WaveArea<P>* w = reinterpret_cast<WaveArea<P>*>(pair_lds);
+    Fq* s = reinterpret_cast<Fq*>(pair_lds + sizeof(WaveArea<P>));
+    WaveF12<P>::init(w);
+    if (blockIdx.x >= n) return;
+    Fq *x = s, *a = s + WV_SLOT, *b = s + 2 * WV_SLOT;
+    u32 lane = threadIdx.x;
+    W::load(x, &in[blockIdx.x]);
+    bool big = false;
+    if (lane < 12) {                                             // the bytes as they came: below q, limb for limb
+        Fq v = x[lane], c = Fq::reduce_once(v);
+        u32 d = 0;
+        HK_UNROLL for (int i = 0; i < P::N; i++) d |= v.v[i] ^ c.v[i];
+        big = d != 0;
+    }
+    bool pass = __ballot(big) == 0 && !W::is_zero(x);            // (1)
+    if (pass) {
+        W::template frob<2>(a, x);                               // x^(q^2)
+        W::template frob<2>(b, a);                               // x^(q^4)
+        W::mul(b, b, x, w);
+        pass = W::equal(a, b);                                   // (2)
+    }
+    if (pass) {
+        if (TowerParams<P>::TWIST_IS_D) {                        // the BN family, as in final_exp
+            W::pow_x(a, x, w);
+            W::pow_x(b, a, w);                                   // y = x^(u^2)
+            W::cyc_sqr(a, b, w);
+            W::mul(a, a, b, w);                                  // y^3
+            W::cyc_sqr(a, a, w);                                 // y^6 = x^(t - 1)
+        } else {
+            W::exp_by_x(a, x, w);                                // x^u = x^(t - 1)
+        }
+        W::template frob<1>(b, x);                               // x^q
+        pass = W::equal(a, b);                                   // (3)
+    }
+    if (lane == 0) ok[blockIdx.x] = pass ? 1 : 0;
 }
 
 #endif  // __HIPCC__

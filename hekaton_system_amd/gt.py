@@ -14,6 +14,7 @@ class GtField:
     def __init__(self, curve):
         p = CURVE_PARAMS[curve]
         self.q = p["q"]
+        self.r = p["r"]
         self.nb = p["fq_bytes"]
         self.xi = _XI[curve]
         self.R = 1 << (8 * self.nb)
@@ -69,3 +70,9 @@ class GtField:
     def conj(self, x):
         """x^(q^6): the inverse of an element of GT (unitary)."""
         return tuple(x[:6]) + tuple((-c) % self.q for c in x[6:])
+
+    def in_gt(self, x):
+        """Is x an element of GT, the order-r subgroup of Fq12^*: x != 0 and x^r == 1, by the plain chain.  The definition
+        that hk_gt_check (capi.Context.gt_check) decides on the device by a shorter route - kept apart from it on purpose."""
+        x = tuple(c % self.q for c in x)
+        return any(x) and self.pow(x, self.r) == self.one

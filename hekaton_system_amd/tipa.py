@@ -388,9 +388,11 @@ class Tipp:
         return proof
 
     # ---- verify -----------------------------------------------------------------------------------------
-    def verify(self, vk, com, z_ab, twist, proof):
+    def verify(self, vk, com, z_ab, twist, proof, in_gt=False):
         """vk: dict(n, g, h, g_alpha, g_beta, h_alpha, h_beta) - single elements (`tipp_pk.vk()`).  True iff the proof is
-        accepted."""
+        accepted.  in_gt: the caller has established that every round message of the proof lies in GT (hk_gt_check; the
+        wire reader `agg_verify.AggProof.deserialize` with a context does) - the fold check then splits its exponents
+        along the Frobenius instead of taking the plain chain."""
         ctx, fc, F, r = self.ctx, self.fc, self.F, self.r
         n = vk["n"]
         tr = Transcript(r)
@@ -413,11 +415,11 @@ class Tipp:
                 groups[name][1].extend((c, c_inv))
         if challenges:
             # the proof's GT members are the prover's word: the plain chain (in_gt = 0), not the Frobenius split that is
-            # only a power for elements of order r
+            # only a power for elements of order r - unless the caller has checked them (in_gt)
             bases = groups["T"][0] + groups["U"][0] + groups["Z"][0]
             exps = groups["T"][1] + groups["U"][1] + groups["Z"][1]
             f_fold = self.pool.submit(ctx.gt_pow_prod, np.frombuffer(b"".join(F.encode(x) for x in bases), np.uint8),
-                                      fc.enc(exps), 2 * len(challenges), False)          # beside the checks below
+                                      fc.enc(exps), 2 * len(challenges), bool(in_gt))    # beside the checks below
         else:
             f_fold = None
         a, b = proof["final_a"], proof["final_b"]
