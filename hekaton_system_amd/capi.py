@@ -168,6 +168,7 @@ _STAGE0 = [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _sz, _vp]
 _SIGNATURES = {
     "hk_status_str": ([_i], C.c_char_p),
     "hk_version": ([], C.c_char_p),
+    "hk_kernel_info": [_sz, _P(C.c_char_p), _P(_sz), _P(C.c_char_p)],
     "hk_ctx_create": [_i, _i, _P(_vp)],
     "hk_ctx_destroy": ([_vp], None),
     "hk_ctx_sync": [_vp],

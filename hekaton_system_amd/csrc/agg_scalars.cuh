@@ -329,9 +329,8 @@ hk_status Ops<C>::scalar_powers(hk_ctx* ctx, const void* x_mont, size_t n, size_
     }));
     hipStream_t s = L->stream;
     HK_HIP(hipMemcpyAsync(tab_d, tab, sizeof(tab), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL((k_powers<Fr>), dim3((n_chunks + 255) / 256, (u32)reps), dim3(256), 0, s, (const Fr*)tab_d, n_chunks, nbits,
-                       (u64)n, (Fr*)to.p);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_powers<Fr>), dim3((n_chunks + 255) / 256, (u32)reps), dim3(256), 0, s, (const Fr*)tab_d, n_chunks, nbits,
+              (u64)n, (Fr*)to.p);
     HK_TRY(stage_download(L, &to, 1));
     return L->settle();                                                     // `tab` is read until here
 }
@@ -374,14 +373,13 @@ hk_status Ops<C>::ipa_quotient(hk_ctx* ctx, const void* challenges_mont, size_t 
     Fr* q = (Fr*)to.p;
     const Fr* tp = tab_d;
     if (fused) {
-        hipLaunchKernelGGL((k_ipaq_tail<Fr>), dim3(1), dim3(AQ_TILE), 0, s, tp, sh, q);
+        HK_LAUNCH((k_ipaq_tail<Fr>), dim3(1), dim3(AQ_TILE), 0, s, tp, sh, q);
     } else {
-        hipLaunchKernelGGL((k_ipaq_chunk<Fr>), dim3(n_tiles), dim3(AQ_TILE), 0, s, tp, sh, part);
-        hipLaunchKernelGGL((k_ipaq_scan_tile<Fr>), dim3(n_tiles), dim3(AQ_TILE), 0, s, tp, part, tops, sh.n_chunks);
-        hipLaunchKernelGGL((k_ipaq_scan_tops<Fr>), dim3(1), dim3(AQ_TOPS_LANES), 0, s, tp, tops, n_tiles);
-        hipLaunchKernelGGL((k_ipaq_walk<Fr>), dim3(n_tiles), dim3(AQ_TILE), 0, s, tp, sh, (const Fr*)part, (const Fr*)tops, q);
+        HK_LAUNCH((k_ipaq_chunk<Fr>), dim3(n_tiles), dim3(AQ_TILE), 0, s, tp, sh, part);
+        HK_LAUNCH((k_ipaq_scan_tile<Fr>), dim3(n_tiles), dim3(AQ_TILE), 0, s, tp, part, tops, sh.n_chunks);
+        HK_LAUNCH((k_ipaq_scan_tops<Fr>), dim3(1), dim3(AQ_TOPS_LANES), 0, s, tp, tops, n_tiles);
+        HK_LAUNCH((k_ipaq_walk<Fr>), dim3(n_tiles), dim3(AQ_TILE), 0, s, tp, sh, (const Fr*)part, (const Fr*)tops, q);
     }
-    HK_HIP(hipGetLastError());
     HK_TRY(stage_download(L, &to, 1));
     return L->settle();                                                     // `tab` is read until here
 }

@@ -148,15 +148,13 @@ hk_status Ops<C>::class_power_sums(hk_ctx* ctx, const void* x_mont, const uint32
     HK_HIP(hipMemcpyAsync(tab_d, tab, sizeof(tab), hipMemcpyHostToDevice, s));
     HK_HIP(hipMemsetAsync(flag, 0, 4, s));
     // the partials and the error word first: nothing touches sums_out before the host has read it (as hk_ram_stage1_witness)
-    hipLaunchKernelGGL((k_cs_chunks<Fr>), dim3(n_wgs, n_groups), dim3(CS_WG), 0, s, (const Fr*)tab_d, (const u32*)in.p, (u64)n,
-                       (u32)n_classes, n_chunks, nbits, part, flag);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_cs_chunks<Fr>), dim3(n_wgs, n_groups), dim3(CS_WG), 0, s, (const Fr*)tab_d, (const u32*)in.p, (u64)n,
+              (u32)n_classes, n_chunks, nbits, part, flag);
     u32 fl = 0;
     HK_HIP(hipMemcpyAsync(&fl, flag, 4, hipMemcpyDeviceToHost, s));
     HK_HIP(hipStreamSynchronize(s));
     if (fl) { HK_TRY(L->settle()); return HK_ERR_ARG; }
-    hipLaunchKernelGGL((k_cs_reduce<Fr>), dim3((u32)n_classes), dim3(CS_WG), 0, s, (const Fr*)part, n_wgs, (Fr*)to.p);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_cs_reduce<Fr>), dim3((u32)n_classes), dim3(CS_WG), 0, s, (const Fr*)part, n_wgs, (Fr*)to.p);
     HK_TRY(stage_download(L, &to, 1));
     return L->settle();                                                     // `tab` is read until here
 }

@@ -73,8 +73,8 @@ static hk_status r1cs_validate(hipStream_t s, const CsrDev D[3], size_t n_cols, 
     for (int k = 0; k < 3; k++) {
         size_t work = D[k].n_rows > D[k].nnz ? D[k].n_rows : D[k].nnz;
         u32 blocks = (u32)std::max<size_t>(std::min<size_t>((work + 255) / 256, 2048), 1);
-        hipLaunchKernelGGL((k_csr_check<0>), dim3(blocks), dim3(256), 0, s, D[k].row_ptr, D[k].col, (u64)D[k].n_rows,
-                           (u64)D[k].nnz, (u32)n_cols, flag);
+        HK_LAUNCH((k_csr_check<0>), dim3(blocks), dim3(256), 0, s, D[k].row_ptr, D[k].col, (u64)D[k].n_rows,
+                  (u64)D[k].nnz, (u32)n_cols, flag);
     }
     u32 h = 0;
     HK_HIP(hipMemcpyAsync(&h, flag, sizeof(u32), hipMemcpyDeviceToHost, s));

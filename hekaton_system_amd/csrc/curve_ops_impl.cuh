@@ -113,20 +113,6 @@ struct Ops final : CurveOps {
         return msm_plain<Fq2>(ctx, bases, n_bases, scalars, n_scalars, mont, checked, out);
     }
 
-    size_t max_private_bytes() override {
-        size_t m = MsmRun<Fq>::max_private_bytes();
-        size_t b = MsmRun<Fq2>::max_private_bytes();
-        if (b > m) m = b;
-        b = PairRun<typename Fq::Params>::max_private_bytes();
-        if (b > m) m = b;
-        b = Verify::max_private_bytes();
-        if (b > m) m = b;
-        b = Codec::max_private_bytes();
-        if (b > m) m = b;
-        b = finish_private_bytes();
-        return b > m ? b : m;
-    }
-
     // ---- defined by the headers named here, in CurveOps's order ----------------------------------------
     // ntt_host.cuh
     hk_status ntt(hk_ctx*, void*, unsigned, int, int) override;
@@ -167,7 +153,6 @@ struct Ops final : CurveOps {
     hk_status commit(hk_ctx*, const hk_pk*, size_t, const void*, size_t, const void*, void*) override;
     hk_status commit_batch(hk_ctx*, const hk_pk*, size_t, const void*, size_t, const void*, size_t, void*) override;
     hk_status prove_batch(hk_ctx*, const hk_pk*, size_t, size_t, const ProveRow*, size_t) override;
-    static size_t finish_private_bytes();      // k_finish_ab / k_finish_c, and the kernels of h_basis.cuh
     // verify.cuh
     hk_status vk_prepare(hk_ctx* ctx, const hk_vk_desc* d, hk_vk** out) override { return Verify::vk_prepare(ctx, d, out); }
     void vk_free(hk_vk* vk) override { Verify::vk_free(vk); }

@@ -263,37 +263,36 @@ hk_status Ops<C>::exec_tree(hk_ctx* ctx, const hk_exec_tree_desc* d, const hk_ex
 
     // (a) running evaluations and leaves
     if (K == 2)
-        hipLaunchKernelGGL((k_et_chunk_prod<Fr, 2>), dim3((n_chunks + 63) / 64, 2), dim3(64), 0, s, tp, ap, (u64)n, n_chunks, ch, prods);
+        HK_LAUNCH((k_et_chunk_prod<Fr, 2>), dim3((n_chunks + 63) / 64, 2), dim3(64), 0, s, tp, ap, (u64)n, n_chunks, ch, prods);
     else
-        hipLaunchKernelGGL((k_et_chunk_prod<Fr, 4>), dim3((n_chunks + 63) / 64, 2), dim3(64), 0, s, tp, ap, (u64)n, n_chunks, ch, prods);
-    hipLaunchKernelGGL((k_et_scan_tile<Fr>), dim3(n_tiles, 2), dim3(ET_SCAN_TILE), 0, s, prods, tops, n_chunks, n_tiles);
-    hipLaunchKernelGGL((k_et_scan_tops<Fr>), dim3(1, 2), dim3(ET_TOPS_LANES), 0, s, tops, n_tiles);
+        HK_LAUNCH((k_et_chunk_prod<Fr, 4>), dim3((n_chunks + 63) / 64, 2), dim3(64), 0, s, tp, ap, (u64)n, n_chunks, ch, prods);
+    HK_LAUNCH((k_et_scan_tile<Fr>), dim3(n_tiles, 2), dim3(ET_SCAN_TILE), 0, s, prods, tops, n_chunks, n_tiles);
+    HK_LAUNCH((k_et_scan_tops<Fr>), dim3(1, 2), dim3(ET_TOPS_LANES), 0, s, tops, n_tiles);
     if (K == 2)
-        hipLaunchKernelGGL((k_et_leaves<Fr, 2>), dim3((ns + 63) / 64, 2), dim3(64), 0, s, tp, ap, (const u32*)off_d, ns, n_chunks,
-                           n_tiles, ch, (const Fr*)prods, (const Fr*)tops, evals, leaves);
+        HK_LAUNCH((k_et_leaves<Fr, 2>), dim3((ns + 63) / 64, 2), dim3(64), 0, s, tp, ap, (const u32*)off_d, ns, n_chunks,
+                  n_tiles, ch, (const Fr*)prods, (const Fr*)tops, evals, leaves);
     else
-        hipLaunchKernelGGL((k_et_leaves<Fr, 4>), dim3((ns + 63) / 64, 2), dim3(64), 0, s, tp, ap, (const u32*)off_d, ns, n_chunks,
-                           n_tiles, ch, (const Fr*)prods, (const Fr*)tops, evals, leaves);
+        HK_LAUNCH((k_et_leaves<Fr, 4>), dim3((ns + 63) / 64, 2), dim3(64), 0, s, tp, ap, (const u32*)off_d, ns, n_chunks,
+                  n_tiles, ch, (const Fr*)prods, (const Fr*)tops, evals, leaves);
 
     // (b) the tree: nodes = leaf digests, then each level, root last
     const PoseidonDesc a = poseidon_desc(d->leaf_hash), b = poseidon_desc(d->node_hash);
     const bool fused_leaves = ns <= ET_WG_STATES;
     if (!fused_leaves)
-        hipLaunchKernelGGL((k_et_leaf_hash<Fr>), dim3((ns + ET_WG_STATES - 1) / ET_WG_STATES), dim3(256), 0, s, cp, a,
-                           (const Fr*)leaves, (u32)nf, ns, nodes);
+        HK_LAUNCH((k_et_leaf_hash<Fr>), dim3((ns + ET_WG_STATES - 1) / ET_WG_STATES), dim3(256), 0, s, cp, a,
+                  (const Fr*)leaves, (u32)nf, ns, nodes);
     u32 w = ns, off = 0;
     while ((w >> 1) > ET_WG_STATES) {
         const u32 w_out = w >> 1;
-        hipLaunchKernelGGL((k_et_level<Fr>), dim3((w_out + ET_WG_STATES - 1) / ET_WG_STATES), dim3(256), 0, s, cp, b,
-                           (const Fr*)(nodes + off), w_out, nodes + off + w);
+        HK_LAUNCH((k_et_level<Fr>), dim3((w_out + ET_WG_STATES - 1) / ET_WG_STATES), dim3(256), 0, s, cp, b,
+                  (const Fr*)(nodes + off), w_out, nodes + off + w);
         off += w;
         w = w_out;
     }
-    hipLaunchKernelGGL((k_et_tree_tail<Fr>), dim3(1), dim3(256), 0, s, cp, a, b, (const Fr*)leaves, (u32)nf, fused_leaves ? 1u : 0u,
-                       w, off, nodes);
+    HK_LAUNCH((k_et_tree_tail<Fr>), dim3(1), dim3(256), 0, s, cp, a, b, (const Fr*)leaves, (u32)nf, fused_leaves ? 1u : 0u,
+              w, off, nodes);
     // (c) the paths
-    hipLaunchKernelGGL((k_et_paths<Fr>), dim3((u32)((n_sub * depth + 255) / 256)), dim3(256), 0, s, (const Fr*)nodes, ns, depth, sibs);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_et_paths<Fr>), dim3((u32)((n_sub * depth + 255) / 256)), dim3(256), 0, s, (const Fr*)nodes, ns, depth, sibs);
 
     struct { void* dst; const Fr* src; size_t count; } outs[] = {
         {o->evals_mont, evals, 2 * n_sub},       {o->leaves_mont, leaves, nf * n_sub}, {o->nodes_mont, nodes, 2 * n_sub - 1},

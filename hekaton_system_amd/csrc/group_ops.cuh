@@ -330,8 +330,7 @@ hk_status Ops<C>::points_fold(hk_ctx* ctx, size_t k, const void* const* lo, cons
         }
         if (ok) {                                                   // the folded vectors go to their windows in one launch
             u32 gx = (gr.vecs[0] + 255) / 256;
-            hipLaunchKernelGGL((k_gather_rows<Fr>), dim3(gx > 1024 ? 1024 : gx, (u32)k), dim3(256), 0, L->stream, gr);
-            HK_HIP(hipGetLastError());
+            HK_LAUNCH((k_gather_rows<Fr>), dim3(gx > 1024 ? 1024 : gx, (u32)k), dim3(256), 0, L->stream, gr);
         } else {
             for (size_t y = 0; y < k; y++)
                 HK_HIP(hipMemcpyAsync(out[y], od + y * n, n * sizeof(Affine<F>),
@@ -379,8 +378,7 @@ hk_status Ops<C>::field_convert(hk_ctx* ctx, int which, const void* in, void* ou
                 sd = t;
             }
             F* dd = out_dev ? dst : u;
-            hipLaunchKernelGGL(k_field_convert<F>, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, L->stream, sd, dd, k, to_mont);
-            HK_HIP(hipGetLastError());
+            HK_LAUNCH(k_field_convert<F>, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, L->stream, sd, dd, k, to_mont);
             if (!out_dev) HK_HIP(hipMemcpyAsync(dst, dd, k * sizeof(F), hipMemcpyDeviceToHost, L->stream));
             HK_TRY(L->settle());
         }

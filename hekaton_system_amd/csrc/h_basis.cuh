@@ -105,15 +105,6 @@ struct HBasis {
     typedef typename C::Fq Fq;
     typedef NttHost<C> N;
 
-    static size_t private_bytes() {
-        size_t m = 0;
-        for (const void* k : {(const void*)k_hb_load<Fr, Fq>, (const void*)k_hb_stage<Fr, Fq>, (const void*)k_hb_ccols<Fr, Fq>}) {
-            size_t b = hk_private_bytes_of(k);
-            if (b > m) m = b;
-        }
-        return m;
-    }
-
     // hat[j] = G^_j / m^2 and g[j] = G_j, j < m, natural order (device, m affine points each) from the key's h_g (device,
     // h_len = m - 1 points)
     static hk_status transform(hk_ctx* ctx, NttTables* T, const Affine<Fq>* h_g, u32 h_len, u32 log_m, Affine<Fq>* hat,
@@ -131,12 +122,11 @@ struct HBasis {
         // the rows c_j as they are: zinv / m^3 on the first vector, zinv / m on the second
         Fr minv = N::size_inv(log_m), zinv = N::vanishing_inv_on_coset(log_m);
         Fr c1 = Fr::mul(zinv, minv), c0 = Fr::mul(c1, Fr::mul(minv, minv));
-        hipLaunchKernelGGL((k_hb_load<Fr, Fq>), dim3((u32)((m + 63) / 64), 2), dim3(64), 0, s, h_g, h_len, log_m,
-                           (const Fr*)T->pw_ginv, c0, c1, E, x);
+        HK_LAUNCH((k_hb_load<Fr, Fq>), dim3((u32)((m + 63) / 64), 2), dim3(64), 0, s, h_g, h_len, log_m,
+                  (const Fr*)T->pw_ginv, c0, c1, E, x);
         for (u32 st = 0; st < log_m; st++)
-            hipLaunchKernelGGL((k_hb_stage<Fr, Fq>), dim3((u32)((m / 2 + 63) / 64), 2), dim3(64), 0, s, x, (const Fr*)T->tw_inv,
-                               st, log_m, E);
-        HK_HIP(hipGetLastError());
+            HK_LAUNCH((k_hb_stage<Fr, Fq>), dim3((u32)((m / 2 + 63) / 64), 2), dim3(64), 0, s, x, (const Fr*)T->tw_inv,
+                      st, log_m, E);
         HK_TRY(MsmRun<Fq>::batch_affine(s, x, hat, pref, (u32)m));
         HK_TRY(MsmRun<Fq>::batch_affine(s, x + m, g, pref + m, (u32)m));
         return L->settle();
@@ -187,10 +177,9 @@ struct HBasis {
         HK_TRY(L->carve([&](Carve& c) { stage_carve(c, in, 6); xy = c.n<XYZZ<Fq>>(n_v); pref = c.n<Fq>(n_v); }));
         HK_TRY(stage_upload(L, in, 6));
         static const EndoSplit<2> E = EndoOf<Fq>::split();
-        hipLaunchKernelGGL((k_hb_ccols<Fr, Fq>), dim3((u32)((n_v + 63) / 64)), dim3(64), 0, L->stream, (const u64*)in[0].p,
-                           (const u32*)in[1].p, (const u32*)in[2].p, (const Fr*)Cm.val, g, (const u32*)in[3].p,
-                           (const Affine<Fq>*)in[4].p, (const Affine<Fq>*)in[5].p, (u32)(n_v - n1), (u32)n_v, E, xy);
-        HK_HIP(hipGetLastError());
+        HK_LAUNCH((k_hb_ccols<Fr, Fq>), dim3((u32)((n_v + 63) / 64)), dim3(64), 0, L->stream, (const u64*)in[0].p,
+                  (const u32*)in[1].p, (const u32*)in[2].p, (const Fr*)Cm.val, g, (const u32*)in[3].p,
+                  (const Affine<Fq>*)in[4].p, (const Affine<Fq>*)in[5].p, (u32)(n_v - n1), (u32)n_v, E, xy);
         HK_TRY(MsmRun<Fq>::batch_affine(L->stream, xy, out, pref, (u32)n_v));
         return L->settle();
     }

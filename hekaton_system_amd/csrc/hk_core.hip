@@ -37,7 +37,7 @@ static uint64_t scratch_limit_bytes() {
     }();
     return v;
 }
-static std::atomic<size_t> g_deepest_frame{0};             // over every curve a context was created for in this process
+static std::atomic<size_t> g_deepest_frame{0};             // over every context created in this process (a switch may differ)
 
 // Ring pre-sizing.  A queue's ring is re-allocated every time a kernel with a deeper frame than it has seen arrives; rings
 // that grow one after another through several sizes fragment the agent's scratch range, and a request can then fail with
@@ -76,14 +76,62 @@ static unsigned hw_queues() {
     return q && atoi(q) > 0 ? (unsigned)atoi(q) : 4u;
 }
 
-hk_status scratch_budget_check(CurveOps* ops, const hipDeviceProp_t& prop, void** presize_out) {
-    // the deepest frame of EVERY curve the library carries, not only this context's: a process that opens a context of the
-    // other curve later (the bench's BLS12-381 leg after its BN254 leg) then finds every queue's ring already at its final
-    // size - no ring ever grows, and the moment the round-3 experiment aborted in (twenty rings wanted at once while the
-    // previous context's were still held) does not arise
-    size_t frame = ops->max_private_bytes();
-    for (CurveOps* o : {curve_ops_bn254(), curve_ops_bls381()})
-        if (o->max_private_bytes() > frame) frame = o->max_private_bytes();
+// ---- the kernels the library launches (launch.h) -------------------------------------------------------------------
+// kernel_registry() read once: one row per kernel (the registry holds one per instantiating translation unit), its name cut
+// out of kernel_pretty()'s spelling.  A kernel launched both behind a switch and without one is ungated.
+struct KernelInfo {
+    const void* fn;
+    std::string name;
+    const char* only_with_env;
+};
+static const std::vector<KernelInfo>& kernels() {
+    static const std::vector<KernelInfo> v = [] {
+        std::vector<KernelInfo> out;
+        std::map<const void*, size_t> at;
+        for (const KernelEntry& e : kernel_registry()) {
+            auto it = at.find(e.fn);
+            if (it != at.end()) {
+                if (!e.only_with_env) out[it->second].only_with_env = nullptr;
+                continue;
+            }
+            // -> "hk::k_name(parameter types)".  This reads clang's spelling of __PRETTY_FUNCTION__; should a compiler spell
+            // it otherwise the whole string stays, and tests/test_kernel_registry_cpu.py fails on the names
+            std::string name = e.pretty;
+            size_t a = name.find("[K = &"), t = name.find(", T = void (*)"), b = name.rfind(']');
+            if (a != std::string::npos && t != std::string::npos && b != std::string::npos && a < t && t < b)
+                name = name.substr(a + 6, t - a - 6) + name.substr(t + 14, b - t - 14);
+            at[e.fn] = out.size();
+            out.push_back({e.fn, name, e.only_with_env});
+        }
+        return out;
+    }();
+    return v;
+}
+
+// private-memory ("scratch") bytes per lane of kernels()[i], as the loaded code object declares them: asked once per process
+// (several hundred handles), 0 where the runtime does not answer
+static size_t private_bytes_of(size_t i) {
+    static const std::vector<size_t> frames = [] {
+        std::vector<size_t> f;
+        for (const KernelInfo& k : kernels()) {
+            hipFuncAttributes fa;
+            if (hipFuncGetAttributes(&fa, k.fn) != hipSuccess) { (void)hipGetLastError(); fa.localSizeBytes = 0; }
+            f.push_back((size_t)fa.localSizeBytes);
+        }
+        return f;
+    }();
+    return frames[i];
+}
+
+hk_status scratch_budget_check(const hipDeviceProp_t& prop, void** presize_out) {
+    // the deepest frame of EVERY kernel the library launches, whatever the curve of this context: a process that opens a
+    // context of the other curve later (the bench's BLS12-381 leg after its BN254 leg) then finds every queue's ring already
+    // at its final size - no ring ever grows, and the moment the round-3 experiment aborted in (twenty rings wanted at once
+    // while the previous context's were still held) does not arise
+    size_t frame = 0;
+    const std::vector<KernelInfo>& ks = kernels();
+    for (size_t i = 0; i < ks.size(); i++)
+        if (!ks[i].only_with_env || getenv(ks[i].only_with_env)) frame = std::max(frame, private_bytes_of(i));
     size_t prev = g_deepest_frame.load();
     while (frame > prev && !g_deepest_frame.compare_exchange_weak(prev, frame)) {}
     frame = g_deepest_frame.load();
@@ -174,7 +222,8 @@ static Lane* new_lane(hk_ctx* ctx, unsigned n, bool prove) {
         return nullptr;
     }
     if (ctx->presize_kernel && !getenv("HK_NO_SCRATCH_PRESIZE")) {
-        // one wave of the deepest frame on each of the lane's streams, in creation order (see k_scratch_presize)
+        // one wave of the deepest frame on each of the lane's streams, in creation order (see k_scratch_presize).  A raw
+        // launch, the only one: this kernel IS the ring sizing, so it must not count towards the frame it is chosen from
         presize_fn k = (presize_fn)ctx->presize_kernel;
         for (unsigned i = 0; i < n; i++) hipLaunchKernelGGL(k, dim3(1), dim3(64), 0, l->stream_at(i), (unsigned*)nullptr, 1u);
         bool okp = true;
@@ -287,6 +336,15 @@ const char* hk_status_str(hk_status s) {
 
 const char* hk_version(void) { return "hekaton-mi355x 0.1 (gfx950)"; }
 
+hk_status hk_kernel_info(size_t i, const char** name, size_t* private_bytes, const char** only_with_env) {
+    const std::vector<hk::KernelInfo>& ks = hk::kernels();
+    if (i >= ks.size()) return HK_ERR_ARG;
+    if (name) *name = ks[i].name.c_str();
+    if (only_with_env) *only_with_env = ks[i].only_with_env;
+    if (private_bytes) *private_bytes = hk::private_bytes_of(i);
+    return HK_OK;
+}
+
 hk_status hk_ctx_create(hk_curve curve, int device_id, hk_ctx** out) {
     if (!out) return HK_ERR_ARG;
     *out = nullptr;
@@ -312,7 +370,7 @@ hk_status hk_ctx_create(hk_curve curve, int device_id, hk_ctx** out) {
     hk::CurveOps* ops = curve == HK_BN254 ? curve_ops_bn254() : curve_ops_bls381();
     // no environment setting may be able to exhaust the runtime's scratch pool (the abort of round 2): refuse here
     void* presize = nullptr;
-    HK_TRY(hk::scratch_budget_check(ops, prop, &presize));
+    HK_TRY(hk::scratch_budget_check(prop, &presize));
     // read once per context, before any thread can be inside hk_prove
     const char* gu = getenv("HK_PROVE_GATHER_US");
     hk_ctx* c = new hk_ctx(gu ? atol(gu) : (long)hk::PROVE_GATHER_US);

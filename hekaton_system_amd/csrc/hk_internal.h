@@ -31,6 +31,8 @@
         if (_s != HK_OK) return _s;        \
     } while (0)
 
+#include "launch.h"
+
 namespace hk {
 
 // ---- curve traits -----------------------------------------------------------------------------
@@ -164,9 +166,6 @@ struct CurveOps {
     // curve_ops_impl.cuh
     virtual hk_status msm(hk_ctx*, int group, const void* bases, size_t n_bases, const void* scalars,
                           size_t n_scalars, int mont, int checked, void* out) = 0;
-    // largest private-memory frame (bytes per lane) among the curve's kernels: sizes the scratch ring the runtime
-    // pins to every hardware queue that ever runs one of them
-    virtual size_t max_private_bytes() = 0;
     // ntt_host.cuh
     virtual hk_status ntt(hk_ctx*, void* data, unsigned log_m, int inverse, int coset) = 0;
     virtual hk_status witness_map(hk_ctx*, const hk_csr* A, const hk_csr* B, const hk_csr* C, size_t n_inst,

@@ -312,16 +312,16 @@ struct KgQap {
         HK_TRY(stage.upload(L, D));
         if (zt_zero) return HK_ERR_ARG;                                  // t in the domain (generator.rs:68 never draws one)
         const u32 nu = (u32)(n_c + n_inst), nv = (u32)n_v;
-        hipLaunchKernelGGL((k_kg_lagrange<Fr>), dim3((nu / KG_CHUNK + 1 + 63) / 64), dim3(64), 0, s, kc_d, nu, u, pref);
+        HK_LAUNCH((k_kg_lagrange<Fr>), dim3((nu / KG_CHUNK + 1 + 63) / 64), dim3(64), 0, s, kc_d, nu, u, pref);
         for (int k = 0; k < 3; k++) {
             const u32 nnz = (u32)D[k].nnz;
             HK_HIP(hipMemsetAsync(cnt, 0, sizeof(u32) * (n_v + 1), s));
-            if (nnz) hipLaunchKernelGGL((k_kg_col_count<0>), dim3((nnz + 255) / 256), dim3(256), 0, s, D[k].col, nnz, cnt);
+            if (nnz) HK_LAUNCH((k_kg_col_count<0>), dim3((nnz + 255) / 256), dim3(256), 0, s, D[k].col, nnz, cnt);
             HK_TRY(scan_u32(s, cnt, st[0], tops, nv + 1));
             HK_HIP(hipMemcpyAsync(cursor, st[0], sizeof(u32) * (n_v + 1), hipMemcpyDeviceToDevice, s));
             if (nnz)
-                hipLaunchKernelGGL((k_kg_scatter<Fr>), dim3((nnz + 255) / 256), dim3(256), 0, s, D[k].row_ptr, (u32)n_c, D[k].col,
-                                   (const Fr*)D[k].val, nnz, (const Fr*)u, cursor, X);
+                HK_LAUNCH((k_kg_scatter<Fr>), dim3((nnz + 255) / 256), dim3(256), 0, s, D[k].row_ptr, (u32)n_c, D[k].col,
+                          (const Fr*)D[k].val, nnz, (const Fr*)u, cursor, X);
             // bounded chunk levels: after each, no column holds more than ceil(bound / KG_SEG) entries
             const u32* start = st[0];
             const Fr* vals = X;
@@ -329,18 +329,17 @@ struct KgQap {
             for (int lvl = 0; bound > KG_SEG; lvl++) {
                 u32* next_start = st[(lvl + 1) & 1];
                 Fr* next = (lvl & 1) ? X : Y;
-                hipLaunchKernelGGL((k_kg_chunk_count<0>), dim3((nv + 1 + 255) / 256), dim3(256), 0, s, start, nv, cnt);
+                HK_LAUNCH((k_kg_chunk_count<0>), dim3((nv + 1 + 255) / 256), dim3(256), 0, s, start, nv, cnt);
                 HK_TRY(scan_u32(s, cnt, next_start, tops, nv + 1));
                 entries = std::min<u64>(entries, entries / KG_SEG + n_v);     // chunks <= entries / KG_SEG + non-empty columns
-                hipLaunchKernelGGL((k_kg_chunk_sum<Fr>), dim3((u32)((entries + 255) / 256)), dim3(256), 0, s, start,
-                                   (const u32*)next_start, nv, vals, next);
+                HK_LAUNCH((k_kg_chunk_sum<Fr>), dim3((u32)((entries + 255) / 256)), dim3(256), 0, s, start,
+                          (const u32*)next_start, nv, vals, next);
                 start = next_start;
                 vals = next;
                 bound = (bound + KG_SEG - 1) / KG_SEG;
             }
-            hipLaunchKernelGGL((k_kg_col_final<Fr>), dim3((nv + 255) / 256), dim3(256), 0, s, start, nv, vals, (const Fr*)u,
-                               (u32)n_c, k == 0 ? (u32)n_inst : 0u, abc + k * n_v);
-            HK_HIP(hipGetLastError());
+            HK_LAUNCH((k_kg_col_final<Fr>), dim3((nv + 255) / 256), dim3(256), 0, s, start, nv, vals, (const Fr*)u,
+                      (u32)n_c, k == 0 ? (u32)n_inst : 0u, abc + k * n_v);
         }
         return HK_OK;
     }
@@ -497,12 +496,11 @@ hk_status Ops<C>::keygen(hk_ctx* ctx, const hk_keygen_desc* d, const hk_keygen_o
     HK_TRY(q.run(L, kc_d, zt_zero, abc));
     if (prof) HK_HIP(hipEventRecord(ev[1], s));
     // (c)
-    hipLaunchKernelGGL((k_kg_scalars<Fr>), dim3((u32)((n_v + 63) / 64)), dim3(64), 0, s, (const Fr*)abc, (const Fr*)kc_d,
-                       (const Fr*)(kc_d + KC_N), (const u32*)begin_d, (u32)n_st, (u32)n_inst, (u32)n_v, sa, sb1, sb2, sgabc, sck);
+    HK_LAUNCH((k_kg_scalars<Fr>), dim3((u32)((n_v + 63) / 64)), dim3(64), 0, s, (const Fr*)abc, (const Fr*)kc_d,
+              (const Fr*)(kc_d + KC_N), (const u32*)begin_d, (u32)n_st, (u32)n_inst, (u32)n_v, sa, sb1, sb2, sgabc, sck);
     if (n_h)
-        hipLaunchKernelGGL((k_kg_hquery<Fr>), dim3((u32)((n_h / KG_CHUNK + 1 + 63) / 64)), dim3(64), 0, s, (const Fr*)kc_d,
-                           (u32)n_h, sh);
-    HK_HIP(hipGetLastError());
+        HK_LAUNCH((k_kg_hquery<Fr>), dim3((u32)((n_h / KG_CHUNK + 1 + 63) / 64)), dim3(64), 0, s, (const Fr*)kc_d,
+                  (u32)n_h, sh);
     if (qap_abc.p)
         HK_HIP(hipMemcpyAsync(qap_abc.p, abc, 3 * n_v * sizeof(Fr), qap_abc.dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
                               s));

@@ -8,13 +8,6 @@
 
 namespace hk {
 
-// private-memory ("scratch") bytes per lane of a kernel, as the loaded code object declares them
-static inline size_t hk_private_bytes_of(const void* kernel) {
-    hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, kernel) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return (size_t)fa.localSizeBytes;
-}
-
 // Every buffer below holds `batch` per-proof slices one fixed stride apart (msm.cuh); a single MSM is a batch of one.
 struct SortBufs {        // device buffers produced by the counting sort
     u32* count;          // [NB]
@@ -89,9 +82,6 @@ struct MsmRun {
                                XYZZ<F>* xy, XYZZ<F>* result);
     static hk_status small_msm_rows(hipStream_t s, const Affine<F>* bases, const void* scalars, u32 seg, u32 batch, XYZZ<F>* tab,
                                     XYZZ<F>* xy, XYZZ<F>* result);
-    // largest private-memory ("scratch") frame per lane among this flavour's kernels, from the loaded code object
-    // (hipFuncGetAttributes): what sizes a hardware queue's scratch ring
-    static size_t max_private_bytes();
 };
 
 // which (lhs vector, rhs vector) pairs a call multiplies out: n = 0 -> every pair, product p = a * n_r + b; else product p
@@ -111,7 +101,6 @@ struct PairRun {
     static hk_status run(hipStream_t s, const Affine<Fp<P>>* g1, const Affine<Fp2<P>>* g2, u32 n, u32 n_l, u32 n_r,
                          Fp12<P>* miller, Fp12<P>* prod, Fp12<P>* out, const PairList* pairs = nullptr);
     static size_t scratch_bytes(u32 n, u32 count, u32 n_r);
-    static size_t max_private_bytes();   // as MsmRun<F>::max_private_bytes, over the pairing / endomorphism kernels
     static u32 steps();          // line-evaluation steps of the Miller loop (the factor of `count` in the tree launches' grid.y)
     // out[e] = in[e]^scalars[e] (GT powers; device pointers)
     // in_gt: the elements lie in GT (order r) - the exponent is then split along the Frobenius (k_gt_pow_endo)
@@ -131,7 +120,6 @@ struct VerifyRun {
     static hk_status verify_batch(hk_ctx*, const hk_vk*, const void* a, const void* b, const void* c, const void* ds,
                                   const void* inputs, size_t n, unsigned flags, const void* rand, unsigned char* verdicts);
     static hk_status points_check(hk_ctx*, int group, const void* pts, size_t n, unsigned char* ok);
-    static size_t max_private_bytes();
 };
 
 // compressed points (point_codec.cuh): the hk_field_sqrt / hk_points_decompress_* / hk_points_compress_* entry points of a
@@ -142,7 +130,6 @@ struct CodecRun {
     static hk_status points_decompress(hk_ctx*, int group, const void* x_canon, const unsigned char* flags, size_t n, int check,
                                        void* points_out, unsigned char* status);
     static hk_status points_compress(hk_ctx*, int group, const void* points, size_t n, void* x_canon_out, unsigned char* flags_out);
-    static size_t max_private_bytes();
 };
 
 }  // namespace hk

@@ -1,23 +1,11 @@
 // msm_driver_impl.cuh — definitions for msm_driver.cuh (see there).
 #pragma once
-#include <hip/hip_ext.h>
 #include "msm_driver.cuh"
 #include "fixed_base.cuh"
 #include "endo.cuh"
 #include "scan.cuh"
 
 namespace hk {
-
-// HK_DEBUG_SYNC=1: synchronise after every launch and name it on stderr (locates a faulting kernel)
-static inline bool hk_dbg_sync() { static const bool on = getenv("HK_DEBUG_SYNC") != nullptr; return on; }
-#define HK_DBG(stream, name)                                                              \
-    do {                                                                                  \
-        if (hk_dbg_sync()) {                                                              \
-            fprintf(stderr, "[hk] launched %s\n", name); fflush(stderr);                  \
-            hipError_t _e = hipStreamSynchronize(stream);                                 \
-            fprintf(stderr, "[hk] finished %s: %s\n", name, hipGetErrorName(_e)); fflush(stderr); \
-        }                                                                                 \
-    } while (0)
 
 template <class Fr>
 void MsmSort<Fr>::alloc(Carve& c, const MsmPlan& p, SortBufs* out, u32 batch) {
@@ -51,17 +39,13 @@ hk_status MsmSort<Fr>::sublist(hipStream_t s, const MsmPlan& src, const SortBufs
     const u32 tiles = msm_sub_tiles(src);
     if ((u64)tiles * batch > 0xffffffffull) return HK_ERR_ARG;
     const dim3 gt((tiles + MSM_SUB_THREADS / 64 - 1) / (MSM_SUB_THREADS / 64), batch);
-    hipLaunchKernelGGL((k_msm_sub_mark<0>), gt, dim3(MSM_SUB_THREADS), 0, s, (const u32*)sb_src.sorted,
-                       (const u32*)sb_src.start, src, rank, sb_dst.mask, sb_dst.tcount);
-    HK_DBG(s, "k_msm_sub_mark");
+    HK_LAUNCH((k_msm_sub_mark<0>), gt, dim3(MSM_SUB_THREADS), 0, s, (const u32*)sb_src.sorted,
+              (const u32*)sb_src.start, src, rank, sb_dst.mask, sb_dst.tcount);
     HK_TRY(scan_u32(s, sb_dst.tcount, sb_dst.toff, sb_dst.tops, tiles * batch));
-    hipLaunchKernelGGL((k_msm_sub_emit<0>), gt, dim3(MSM_SUB_THREADS), 0, s, (const u32*)sb_src.sorted, src, rank,
-                       (const u64*)sb_dst.mask, (const u32*)sb_dst.toff, dst, sb_dst.sorted);
-    HK_DBG(s, "k_msm_sub_emit");
-    hipLaunchKernelGGL((k_msm_sub_starts<0>), dim3((src.NB + 1 + 255) / 256, batch), dim3(256), 0, s,
-                       (const u32*)sb_src.start, src, (const u64*)sb_dst.mask, (const u32*)sb_dst.toff, sb_dst.start);
-    HK_DBG(s, "k_msm_sub_starts");
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_msm_sub_emit<0>), gt, dim3(MSM_SUB_THREADS), 0, s, (const u32*)sb_src.sorted, src, rank,
+              (const u64*)sb_dst.mask, (const u32*)sb_dst.toff, dst, sb_dst.sorted);
+    HK_LAUNCH((k_msm_sub_starts<0>), dim3((src.NB + 1 + 255) / 256, batch), dim3(256), 0, s,
+              (const u32*)sb_src.start, src, (const u64*)sb_dst.mask, (const u32*)sb_dst.toff, sb_dst.start);
     return HK_OK;
 }
 
@@ -74,15 +58,11 @@ hk_status MsmSort<Fr>::run(hipStream_t s, const MsmPlan& p, const u32* scalars_d
     u32 blocks = (p.n + p.chunk - 1) / p.chunk;
     if (blocks == 0) blocks = 1;
     const size_t words = scalar_stride * (sizeof(Fr) / sizeof(u32));
-    hipLaunchKernelGGL((k_msm_hist<Fr>), dim3(blocks, batch), dim3(MSM_SORT_THREADS), 0, s,
-                       scalars_d, words, is_mont, p, sb.count, sb.digits);
-    HK_DBG(s, "k_msm_hist");
-    hipLaunchKernelGGL((k_msm_scan<0>), dim3(batch), dim3(1024), 0, s, sb.count, sb.start, sb.cursor, p.NB);
-    HK_DBG(s, "k_msm_scan");
-    hipLaunchKernelGGL((k_msm_scatter<Fr>), dim3(blocks, batch), dim3(MSM_SORT_THREADS), 0, s,
-                       (const short*)sb.digits, p, sb.cursor, sb.sorted);
-    HK_DBG(s, "k_msm_scatter");
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_msm_hist<Fr>), dim3(blocks, batch), dim3(MSM_SORT_THREADS), 0, s,
+              scalars_d, words, is_mont, p, sb.count, sb.digits);
+    HK_LAUNCH((k_msm_scan<0>), dim3(batch), dim3(1024), 0, s, sb.count, sb.start, sb.cursor, p.NB);
+    HK_LAUNCH((k_msm_scatter<Fr>), dim3(blocks, batch), dim3(MSM_SORT_THREADS), 0, s,
+              (const short*)sb.digits, p, sb.cursor, sb.sorted);
     return HK_OK;
 }
 
@@ -119,84 +99,54 @@ hk_status MsmRun<F>::run(hipStream_t s, const MsmPlan& p0, const Affine<F>* tabl
     const size_t n0 = 2ull * p.T[0], n1 = msm_p1_stride(p);
     // no memset of the buckets (4 - 8 MB per MSM): k_msm_accum0 writes every bucket that has entries and clears the
     // ticket, the reductions skip the empty ones
-    // with profiling on, ev0/ev1 take the kernel's own start/stop timestamps (hipExtLaunchKernelGGL), so
+    // with profiling on, ev0/ev1 take the kernel's own start/stop timestamps, so
     // the figure agrees with rocprofv3's kernel trace even when other lanes share the hardware queues
     dim3 g0((p.T[0] + 63) / 64, batch);
-    if (ev0 && ev1)
-        hipExtLaunchKernelGGL((k_msm_accum0<F>), g0, dim3(64), 0, s, ev0, ev1, 0,
-                              table, n_bases, idx_off, sb.sorted, sb.start, p, b.buckets, b.pkeys[0], b.ppts[0]);
-    else
-        hipLaunchKernelGGL((k_msm_accum0<F>), g0, dim3(64), 0, s,
-                           table, n_bases, idx_off, sb.sorted, sb.start, p, b.buckets, b.pkeys[0], b.ppts[0]);
-    HK_DBG(s, "k_msm_accum0");
+    HK_LAUNCH_TIMED((k_msm_accum0<F>), g0, dim3(64), 0, s, ev0, ev1,
+                    table, n_bases, idx_off, sb.sorted, sb.start, p, b.buckets, b.pkeys[0], b.ppts[0]);
     u32 k = 1;
     for (; k < p.n_levels && p.T[k] > (u32)MSM_TAIL_THREADS; k++) {
         int in = (k - 1) & 1, out = k & 1;
-        hipLaunchKernelGGL((k_msm_accum_lvl<F>), dim3((p.T[k] + 63) / 64, batch), dim3(64), 0, s,
-                           (int)k, b.pkeys[in], b.ppts[in], in ? n1 : n0, sb.start, p, b.buckets, b.pkeys[out], b.ppts[out],
-                           out ? n1 : n0);
-        HK_DBG(s, "k_msm_accum_lvl");
+        HK_LAUNCH((k_msm_accum_lvl<F>), dim3((p.T[k] + 63) / 64, batch), dim3(64), 0, s,
+                  (int)k, b.pkeys[in], b.ppts[in], in ? n1 : n0, sb.start, p, b.buckets, b.pkeys[out], b.ppts[out],
+                  out ? n1 : n0);
     }
     if (k < p.n_levels) {                                   // the remaining levels fit one workgroup each: one launch
-        hipLaunchKernelGGL((k_msm_accum_tail<F>), dim3(batch), dim3(MSM_TAIL_THREADS), 0, s, (int)k, b.pkeys[0], b.ppts[0],
-                           b.pkeys[1], b.ppts[1], sb.start, p, b.buckets);
-        HK_DBG(s, "k_msm_accum_tail");
+        HK_LAUNCH((k_msm_accum_tail<F>), dim3(batch), dim3(MSM_TAIL_THREADS), 0, s, (int)k, b.pkeys[0], b.ppts[0],
+                  b.pkeys[1], b.ppts[1], sb.start, p, b.buckets);
     }
     u32 J = p.B / p.K;
     if (p.WP == 1) {
         u32 blocks = (J + MSM_REDUCE_THREADS - 1) / MSM_REDUCE_THREADS;
-        hipLaunchKernelGGL((k_msm_reduce_fused<F>), dim3(blocks, batch), dim3(MSM_REDUCE_THREADS), 0, s, b.buckets, sb.start, p,
-                           b.red, result_d, res_stride);
-        HK_DBG(s, "k_msm_reduce_fused");
+        HK_LAUNCH((k_msm_reduce_fused<F>), dim3(blocks, batch), dim3(MSM_REDUCE_THREADS), 0, s, b.buckets, sb.start, p,
+                  b.red, result_d, res_stride);
     } else {
         // several windows per group (the HK_MSM_WP experiment only): the three-launch reduction of each proof's slices
         const size_t rs = (size_t)p.WP * J;
         for (u32 pr = 0; pr < batch; pr++) {
             const XYZZ<F>* bk = b.buckets + (size_t)pr * (p.NB + 1);
             const u32* st = sb.start + (size_t)pr * (p.NB + 1);
-            hipLaunchKernelGGL((k_msm_bucket_reduce<F>), dim3((p.WP * J + 63) / 64), dim3(64), 0, s, bk, st, p, b.red + pr * rs);
-            HK_DBG(s, "k_msm_bucket_reduce");
-            hipLaunchKernelGGL((k_msm_window_sum<F>), dim3(p.WP), dim3(MSM_WSUM_THREADS), 0, s, b.red + pr * rs, p,
-                               b.wsum + (size_t)pr * p.WP);
-            HK_DBG(s, "k_msm_window_sum");
-            hipLaunchKernelGGL((k_msm_final<F>), dim3(1), dim3(64), 0, s, b.wsum + (size_t)pr * p.WP, p,
-                               result_d + (size_t)pr * res_stride);
-            HK_DBG(s, "k_msm_final");
+            HK_LAUNCH((k_msm_bucket_reduce<F>), dim3((p.WP * J + 63) / 64), dim3(64), 0, s, bk, st, p, b.red + pr * rs);
+            HK_LAUNCH((k_msm_window_sum<F>), dim3(p.WP), dim3(MSM_WSUM_THREADS), 0, s, b.red + pr * rs, p,
+                      b.wsum + (size_t)pr * p.WP);
+            HK_LAUNCH((k_msm_final<F>), dim3(1), dim3(64), 0, s, b.wsum + (size_t)pr * p.WP, p,
+                      result_d + (size_t)pr * res_stride);
         }
     }
-    HK_HIP(hipGetLastError());
     return HK_OK;
-}
-
-
-template <class F>
-size_t MsmRun<F>::max_private_bytes() {
-    typedef typename ScalarOf<F>::type Fr;
-    const void* ks[] = {(const void*)k_msm_accum0<F>, (const void*)k_msm_accum_lvl<F>, (const void*)k_msm_accum_tail<F>,
-                        (const void*)k_msm_reduce_fused<F>, (const void*)k_msm_bucket_reduce<F>,
-                        (const void*)k_msm_window_sum<F>, (const void*)k_msm_final<F>, (const void*)k_to_affine<F>,
-                        (const void*)k_msm_build_tables<F>, (const void*)k_batch_affine<F>, (const void*)k_fb_table<F>,
-                        (const void*)k_fb_mul<Fr, F>, (const void*)k_scalar_mul_each<Fr, F>, (const void*)k_scalar_mul_endo<Fr, F>, (const void*)k_points_fold_endo<Fr, F>, (const void*)k_points_mul_split<Fr, F, true>, (const void*)k_points_mul_split<Fr, F, false>, (const void*)k_points_sum_seg<F, PointsSum<F>::THREADS>, (const void*)k_points_sum_seg<F, 64>,
-                        (const void*)k_points_lincomb<Fr, F>};
-    size_t m = 0;
-    for (const void* k : ks) { size_t b = hk_private_bytes_of(k); if (b > m) m = b; }
-    return m;
 }
 
 template <class F>
 hk_status MsmRun<F>::build_tables(hipStream_t s, Affine<F>* table, u32 n, u32 groups, u32 shift_bits) {
     if (groups <= 1 || n == 0) return HK_OK;
-    hipLaunchKernelGGL((k_msm_build_tables<F>), dim3((n + 63) / 64), dim3(64), 0, s, table, n, groups,
-                       shift_bits);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_msm_build_tables<F>), dim3((n + 63) / 64), dim3(64), 0, s, table, n, groups,
+              shift_bits);
     return HK_OK;
 }
 
 template <class F>
 hk_status MsmRun<F>::to_affine(hipStream_t s, const XYZZ<F>* in, Affine<F>* out, u32 n) {
-    hipLaunchKernelGGL((k_to_affine<F>), dim3((n + 63) / 64), dim3(64), 0, s, in, out, n);
-    HK_DBG(s, "k_to_affine");
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_to_affine<F>), dim3((n + 63) / 64), dim3(64), 0, s, in, out, n);
     return HK_OK;
 }
 
@@ -206,15 +156,14 @@ hk_status MsmRun<F>::batch_affine(hipStream_t s, const XYZZ<F>* in, Affine<F>* o
     u32 chunk = (n + 65535) / 65536;                       // 1 up to one wave per SIMD, then longer serial runs per lane
     if (chunk > (u32)FB_CHUNK) chunk = FB_CHUNK;
     u32 lanes = (n + chunk - 1) / chunk;
-    hipLaunchKernelGGL((k_batch_affine<F>), dim3((lanes + 63) / 64), dim3(64), 0, s, in, out, pref, n, chunk);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_batch_affine<F>), dim3((lanes + 63) / 64), dim3(64), 0, s, in, out, pref, n, chunk);
     return HK_OK;
 }
 
 // the K-lane sweep (endo.cuh): for G2 with few elements every Fq2 value on a quad of lanes (Fp2Q), else one lane per value
 template <class Fr, class P, bool UNIFORM>
-static inline void launch_mul_split(hipStream_t s, const SplitVecs<Fp2<P>>& v, u32 k, const Fr* scalars, u32 neg_mask, u32 n,
-                                    const EndoSplit<4>& E, Jac<Fp2<P>>* tab, XYZZ<Fp2<P>>* xy, int scalars_mont = 1) {
+static inline hk_status launch_mul_split(hipStream_t s, const SplitVecs<Fp2<P>>& v, u32 k, const Fr* scalars, u32 neg_mask, u32 n,
+                                         const EndoSplit<4>& E, Jac<Fp2<P>>* tab, XYZZ<Fp2<P>>* xy, int scalars_mont = 1) {
     const bool no_quad = getenv("HK_ENDO_NO_QUAD") != nullptr;
     u32 lanes = n * 4;
     if (!no_quad && (size_t)lanes * 4 <= SPLIT_MAX_LANES) {
@@ -222,18 +171,20 @@ static inline void launch_mul_split(hipStream_t s, const SplitVecs<Fp2<P>>& v, u
         SplitVecs<Q> vq;
         for (int y = 0; y < FOLD_MAX; y++) { vq.lo[y] = (const Affine<Q>*)v.lo[y]; vq.pts[y] = (const Affine<Q>*)v.pts[y]; }
         vq.pts_mod = v.pts_mod;
-        hipLaunchKernelGGL((k_points_mul_split<Fr, Q, UNIFORM>), dim3((lanes * 4 + 63) / 64, k), dim3(64), 0, s, vq, scalars,
-                           neg_mask, n, E, (Jac<Q>*)tab, (XYZZ<Q>*)xy, scalars_mont);
+        HK_LAUNCH((k_points_mul_split<Fr, Q, UNIFORM>), dim3((lanes * 4 + 63) / 64, k), dim3(64), 0, s, vq, scalars,
+                  neg_mask, n, E, (Jac<Q>*)tab, (XYZZ<Q>*)xy, scalars_mont);
     } else {
-        hipLaunchKernelGGL((k_points_mul_split<Fr, Fp2<P>, UNIFORM>), dim3((lanes + 63) / 64, k), dim3(64), 0, s, v, scalars,
-                           neg_mask, n, E, tab, xy, scalars_mont);
+        HK_LAUNCH((k_points_mul_split<Fr, Fp2<P>, UNIFORM>), dim3((lanes + 63) / 64, k), dim3(64), 0, s, v, scalars,
+                  neg_mask, n, E, tab, xy, scalars_mont);
     }
+    return HK_OK;
 }
 template <class Fr, class P, bool UNIFORM>
-static inline void launch_mul_split(hipStream_t s, const SplitVecs<Fp<P>>& v, u32 k, const Fr* scalars, u32 neg_mask, u32 n,
-                                    const EndoSplit<2>& E, Jac<Fp<P>>* tab, XYZZ<Fp<P>>* xy, int scalars_mont = 1) {
-    hipLaunchKernelGGL((k_points_mul_split<Fr, Fp<P>, UNIFORM>), dim3((n * 2 + 63) / 64, k), dim3(64), 0, s, v, scalars,
-                       neg_mask, n, E, tab, xy, scalars_mont);
+static inline hk_status launch_mul_split(hipStream_t s, const SplitVecs<Fp<P>>& v, u32 k, const Fr* scalars, u32 neg_mask, u32 n,
+                                         const EndoSplit<2>& E, Jac<Fp<P>>* tab, XYZZ<Fp<P>>* xy, int scalars_mont = 1) {
+    HK_LAUNCH((k_points_mul_split<Fr, Fp<P>, UNIFORM>), dim3((n * 2 + 63) / 64, k), dim3(64), 0, s, v, scalars,
+              neg_mask, n, E, tab, xy, scalars_mont);
+    return HK_OK;
 }
 
 template <class F>
@@ -248,17 +199,16 @@ hk_status MsmRun<F>::scalar_mul_each(hipStream_t s, const Affine<F>* pts, const 
         static const auto E = EndoOf<F>::split();
         SplitVecs<F> v = {};
         v.pts[0] = pts;
-        launch_mul_split<Fr, typename F::Params, false>(s, v, 1u, (const Fr*)scalars_mont, 0u, n, E, reinterpret_cast<Jac<F>*>(tab), xy);
+        HK_TRY((launch_mul_split<Fr, typename F::Params, false>(s, v, 1u, (const Fr*)scalars_mont, 0u, n, E, reinterpret_cast<Jac<F>*>(tab), xy)));
     } else if (tab && !plain) {
         // scalars split on the device along phi / psi: one shared chain of 131 (G1) / 68 (G2) doublings (endo.cuh)
         static const auto E = EndoOf<F>::split();
-        hipLaunchKernelGGL((k_scalar_mul_endo<Fr, F>), dim3((n + 63) / 64), dim3(64), 0, s, pts, (const Fr*)scalars_mont, n, E,
-                           tab, xy);
+        HK_LAUNCH((k_scalar_mul_endo<Fr, F>), dim3((n + 63) / 64), dim3(64), 0, s, pts, (const Fr*)scalars_mont, n, E,
+                  tab, xy);
     } else {
-        hipLaunchKernelGGL((k_scalar_mul_each<Fr, F>), dim3((n + 63) / 64), dim3(64), 0, s, pts, (const Fr*)scalars_mont,
-                           n, xy);
+        HK_LAUNCH((k_scalar_mul_each<Fr, F>), dim3((n + 63) / 64), dim3(64), 0, s, pts, (const Fr*)scalars_mont,
+                  n, xy);
     }
-    HK_HIP(hipGetLastError());
     return batch_affine(s, xy, out, pref, n);
 }
 
@@ -272,9 +222,8 @@ hk_status MsmRun<F>::small_msm(hipStream_t s, const Affine<F>* bases, const void
     static const auto E = EndoOf<F>::split();
     SplitVecs<F> v = {};
     v.pts[0] = bases;
-    launch_mul_split<Fr, typename F::Params, false>(s, v, 1u, (const Fr*)scalars, 0u, n, E, reinterpret_cast<Jac<F>*>(tab), xy, mont ? 1 : 0);
-    hipLaunchKernelGGL((k_points_sum_seg<F, PointsSum<F>::THREADS>), dim3(1), dim3(PointsSum<F>::THREADS), 0, s, (const XYZZ<F>*)xy, n, result);
-    HK_HIP(hipGetLastError());
+    HK_TRY((launch_mul_split<Fr, typename F::Params, false>(s, v, 1u, (const Fr*)scalars, 0u, n, E, reinterpret_cast<Jac<F>*>(tab), xy, mont ? 1 : 0)));
+    HK_LAUNCH((k_points_sum_seg<F, PointsSum<F>::THREADS>), dim3(1), dim3(PointsSum<F>::THREADS), 0, s, (const XYZZ<F>*)xy, n, result);
     return HK_OK;
 }
 
@@ -290,9 +239,8 @@ hk_status MsmRun<F>::small_msm_rows(hipStream_t s, const Affine<F>* bases, const
     SplitVecs<F> v = {};
     v.pts[0] = bases;
     v.pts_mod = seg;
-    launch_mul_split<Fr, typename F::Params, false>(s, v, 1u, (const Fr*)scalars, 0u, (u32)n, E, reinterpret_cast<Jac<F>*>(tab), xy, 1);
-    hipLaunchKernelGGL((k_points_sum_seg<F, 64>), dim3(batch), dim3(64), 0, s, (const XYZZ<F>*)xy, seg, result);
-    HK_HIP(hipGetLastError());
+    HK_TRY((launch_mul_split<Fr, typename F::Params, false>(s, v, 1u, (const Fr*)scalars, 0u, (u32)n, E, reinterpret_cast<Jac<F>*>(tab), xy, 1)));
+    HK_LAUNCH((k_points_sum_seg<F, 64>), dim3(batch), dim3(64), 0, s, (const XYZZ<F>*)xy, seg, result);
     return HK_OK;
 }
 
@@ -307,13 +255,12 @@ hk_status MsmRun<F>::fold_endo(hipStream_t s, u32 k, const Affine<F>* const* lo,
         static const auto E = EndoOf<F>::split();                                // unused by the uniform form
         SplitVecs<F> v = {};
         for (u32 y = 0; y < k; y++) { v.lo[y] = lo[y]; v.pts[y] = hi[y]; }
-        launch_mul_split<Fr, typename F::Params, true>(s, v, k, (const Fr*)coeffs_mont, neg_mask, n, E, reinterpret_cast<Jac<F>*>(tab), xy);
+        HK_TRY((launch_mul_split<Fr, typename F::Params, true>(s, v, k, (const Fr*)coeffs_mont, neg_mask, n, E, reinterpret_cast<Jac<F>*>(tab), xy)));
     } else {
         for (u32 y = 0; y < k; y++)                                              // long vectors: throughput-bound, one after the other
-            hipLaunchKernelGGL((k_points_fold_endo<Fr, F>), dim3((n + 63) / 64), dim3(64), 0, s, lo[y], hi[y], (const Fr*)coeffs_mont,
-                               neg_mask, n, tab, xy + (size_t)y * n);
+            HK_LAUNCH((k_points_fold_endo<Fr, F>), dim3((n + 63) / 64), dim3(64), 0, s, lo[y], hi[y], (const Fr*)coeffs_mont,
+                      neg_mask, n, tab, xy + (size_t)y * n);
     }
-    HK_HIP(hipGetLastError());
     return batch_affine(s, xy, out, pref, k * n);
 }
 
@@ -325,8 +272,7 @@ hk_status MsmRun<F>::lincomb(hipStream_t s, const Affine<F>* const* vecs, const 
     if (k == 0 || k > (u32)LINCOMB_MAX) return HK_ERR_ARG;
     LincombVecs<F> lv;
     for (u32 j = 0; j < (u32)LINCOMB_MAX; j++) lv.v[j] = j < k ? vecs[j] : nullptr;
-    hipLaunchKernelGGL((k_points_lincomb<Fr, F>), dim3((n + 63) / 64), dim3(64), 0, s, lv, (const Fr*)coeffs_mont, k, n, xy);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_points_lincomb<Fr, F>), dim3((n + 63) / 64), dim3(64), 0, s, lv, (const Fr*)coeffs_mont, k, n, xy);
     return batch_affine(s, xy, out, pref, n);
 }
 
@@ -335,10 +281,9 @@ hk_status MsmRun<F>::fixed_base(hipStream_t s, const Affine<F>* base, const void
                                 u32 n, Affine<F>* table, XYZZ<F>* xy, F* pref, Affine<F>* out, bool build_table) {
     typedef typename ScalarOf<F>::type Fr;
     if (n == 0) return HK_OK;
-    if (build_table) hipLaunchKernelGGL((k_fb_table<F>), dim3(FB_WINDOWS * 256 / 64), dim3(64), 0, s, base, table);
-    hipLaunchKernelGGL((k_fb_mul<Fr, F>), dim3((n + 63) / 64), dim3(64), 0, s, table, (const Fr*)scalars,
-                       is_mont, n, xy);
-    HK_HIP(hipGetLastError());
+    if (build_table) HK_LAUNCH((k_fb_table<F>), dim3(FB_WINDOWS * 256 / 64), dim3(64), 0, s, base, table);
+    HK_LAUNCH((k_fb_mul<Fr, F>), dim3((n + 63) / 64), dim3(64), 0, s, table, (const Fr*)scalars,
+              is_mont, n, xy);
     return batch_affine(s, xy, out, pref, n);
 }
 

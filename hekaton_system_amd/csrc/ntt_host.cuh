@@ -90,17 +90,16 @@ struct NttHost {
         HK_HIP(hipMemcpy(d_sq + 64 + NG, gis.data(), sizeof(Fr) * NG, hipMemcpyHostToDevice));
         u32 blocks = (u32)((half + 255) / 256), blocks_full = (u32)((full + 255) / 256);
         // w_M^i for i < M/2 (scratch), regrouped into one contiguous table per butterfly stage
-        hipLaunchKernelGGL((k_pow_table<Fr>), dim3(blocks), dim3(256), 0, 0, tmp, d_sq, (u32)half, L - 1);
-        hipLaunchKernelGGL((k_stage_tables<Fr>), dim3(blocks_full), dim3(256), 0, 0, tf, tmp, L);
-        hipLaunchKernelGGL((k_pow_table<Fr>), dim3(blocks), dim3(256), 0, 0, tmp, d_sq + 32, (u32)half, L - 1);
-        hipLaunchKernelGGL((k_stage_tables<Fr>), dim3(blocks_full), dim3(256), 0, 0, ti, tmp, L);
+        HK_LAUNCH((k_pow_table<Fr>), dim3(blocks), dim3(256), 0, 0, tmp, d_sq, (u32)half, L - 1);
+        HK_LAUNCH((k_stage_tables<Fr>), dim3(blocks_full), dim3(256), 0, 0, tf, tmp, L);
+        HK_LAUNCH((k_pow_table<Fr>), dim3(blocks), dim3(256), 0, 0, tmp, d_sq + 32, (u32)half, L - 1);
+        HK_LAUNCH((k_stage_tables<Fr>), dim3(blocks_full), dim3(256), 0, 0, ti, tmp, L);
         for (u32 lvl = 0; lvl < 3; lvl++) {
-            hipLaunchKernelGGL((k_pow_table<Fr>), dim3(POW_TABLE_SIZE / 256), dim3(256), 0, 0, pg + POW_TABLE_SIZE * lvl,
-                               d_sq + 64 + POW_TABLE_BITS * lvl, (u32)POW_TABLE_SIZE, (u32)POW_TABLE_BITS);
-            hipLaunchKernelGGL((k_pow_table<Fr>), dim3(POW_TABLE_SIZE / 256), dim3(256), 0, 0, pgi + POW_TABLE_SIZE * lvl,
-                               d_sq + 64 + NG + POW_TABLE_BITS * lvl, (u32)POW_TABLE_SIZE, (u32)POW_TABLE_BITS);
+            HK_LAUNCH((k_pow_table<Fr>), dim3(POW_TABLE_SIZE / 256), dim3(256), 0, 0, pg + POW_TABLE_SIZE * lvl,
+                      d_sq + 64 + POW_TABLE_BITS * lvl, (u32)POW_TABLE_SIZE, (u32)POW_TABLE_BITS);
+            HK_LAUNCH((k_pow_table<Fr>), dim3(POW_TABLE_SIZE / 256), dim3(256), 0, 0, pgi + POW_TABLE_SIZE * lvl,
+                      d_sq + 64 + NG + POW_TABLE_BITS * lvl, (u32)POW_TABLE_SIZE, (u32)POW_TABLE_BITS);
         }
-        HK_HIP(hipGetLastError());
         HK_HIP(hipDeviceSynchronize());
         HK_HIP(hipFree(d_sq));
         HK_HIP(hipFree(tmp));
@@ -161,28 +160,25 @@ struct NttHost {
             const Fr& sc = (pp & 1) ? *ep.scale : one;
             const Fr& kc = (pp & 4) ? *ep.kc : one;
             if (dit)
-                hipLaunchKernelGGL((k_ntt_pass4<Fr, 1>), grid, dim3(threads), lds, s, data, stride, tws, logn, p.lo,
-                                   p.nst, p.cols_bits, pp, ep.nvec, sc, ep.pw, ep.sub, kc);
+                HK_LAUNCH((k_ntt_pass4<Fr, 1>), grid, dim3(threads), lds, s, data, stride, tws, logn, p.lo,
+                          p.nst, p.cols_bits, pp, ep.nvec, sc, ep.pw, ep.sub, kc);
             else
-                hipLaunchKernelGGL((k_ntt_pass4<Fr, 0>), grid, dim3(threads), lds, s, data, stride, tws, logn, p.lo,
-                                   p.nst, p.cols_bits, pp, ep.nvec, sc, ep.pw, ep.sub, kc);
+                HK_LAUNCH((k_ntt_pass4<Fr, 0>), grid, dim3(threads), lds, s, data, stride, tws, logn, p.lo,
+                          p.nst, p.cols_bits, pp, ep.nvec, sc, ep.pw, ep.sub, kc);
         }
-        HK_HIP(hipGetLastError());
         return HK_OK;
     }
 
     static hk_status scale(hipStream_t s, Fr* data, size_t stride, u32 batch, u32 logn, const Fr* pw,
                            const Fr& sc, int bitrev_index, int use_pow) {
         size_t n = (size_t)1 << logn;
-        hipLaunchKernelGGL((k_scale_pow<Fr>), dim3((u32)((n + 255) / 256), batch), dim3(256), 0, s, data,
-                           stride, pw, sc, logn, bitrev_index, use_pow);
-        HK_HIP(hipGetLastError());
+        HK_LAUNCH((k_scale_pow<Fr>), dim3((u32)((n + 255) / 256), batch), dim3(256), 0, s, data,
+                  stride, pw, sc, logn, bitrev_index, use_pow);
         return HK_OK;
     }
     static hk_status bitrev(hipStream_t s, Fr* data, u32 logn) {
         size_t n = (size_t)1 << logn;
-        hipLaunchKernelGGL((k_bitrev<Fr>), dim3((u32)((n + 255) / 256)), dim3(256), 0, s, data, logn);
-        HK_HIP(hipGetLastError());
+        HK_LAUNCH((k_bitrev<Fr>), dim3((u32)((n + 255) / 256)), dim3(256), 0, s, data, logn);
         return HK_OK;
     }
 };
@@ -244,9 +240,9 @@ struct QapHost {
         for (int k = 0; k < 3; k++) {
             // every row of the m-element vector is written: matrix rows, the instance copy behind them (a only:
             // a[n_c + j] = z[j]), zeros - no memset of the 3 m x 32 B (a 201 MB fill at m = 2^21)
-            hipLaunchKernelGGL((k_spmv<Fr>), dim3((u32)((m + 255) / 256)), dim3(256), 0, s,
-                               Ms[k]->row_ptr, Ms[k]->col, (const Fr*)Ms[k]->val, z, abc + k * m,
-                               (u32)n_c, k == 0 ? (u32)n_inst : 0u, (u32)m);
+            HK_LAUNCH((k_spmv<Fr>), dim3((u32)((m + 255) / 256)), dim3(256), 0, s,
+                      Ms[k]->row_ptr, Ms[k]->col, (const Fr*)Ms[k]->val, z, abc + k * m,
+                      (u32)n_c, k == 0 ? (u32)n_inst : 0u, (u32)m);
         }
         // With Z constant on the coset (Z(g w^i) = g^m - 1) and the transforms linear,
         //     h = zinv * (coset_ifft(a_coset o b_coset) - ifft(c))
@@ -260,7 +256,7 @@ struct QapHost {
         e1.pw = (const Fr*)T->pw_g;
         HK_TRY(N::passes(s, abc, m, 3, log_m, tinv, 0, e1));
         HK_TRY(N::passes(s, abc, m, 2, log_m, tfwd, 1));       // coset fft (DIT) of a, b
-        hipLaunchKernelGGL((k_mul_pointwise<Fr>), dim3((u32)((m + 255) / 256)), dim3(256), 0, s, abc, abc + m, m);
+        HK_LAUNCH((k_mul_pointwise<Fr>), dim3((u32)((m + 255) / 256)), dim3(256), 0, s, abc, abc + m, m);
         Fr minv = N::size_inv(log_m);
         Fr mm = fp_inv(Fr::mul(minv, minv));                                                    // m^2
         Fr k = Fr::mul(N::vanishing_inv_on_coset(log_m), Fr::mul(minv, Fr::mul(minv, minv)));   // zinv / m^3
@@ -271,7 +267,6 @@ struct QapHost {
         e2.kc = &mm;
         e2.scale = &k;
         HK_TRY(N::passes(s, abc, m, 1, log_m, tinv, 0, e2));
-        HK_HIP(hipGetLastError());
         return HK_OK;
     }
     // The map for a key whose H query is held in the coset's evaluation basis (h_basis.cuh): four transforms, no C pass.
@@ -283,17 +278,16 @@ struct QapHost {
         size_t m = (size_t)1 << log_m;
         const CsrDev* Ms[2] = {&A, &B};
         for (int k = 0; k < 2; k++)
-            hipLaunchKernelGGL((k_spmv<Fr>), dim3((u32)((m + 255) / 256)), dim3(256), 0, s,
-                               Ms[k]->row_ptr, Ms[k]->col, (const Fr*)Ms[k]->val, z, ab + k * m,
-                               (u32)n_c, k == 0 ? (u32)n_inst : 0u, (u32)m);
+            HK_LAUNCH((k_spmv<Fr>), dim3((u32)((m + 255) / 256)), dim3(256), 0, s,
+                      Ms[k]->row_ptr, Ms[k]->col, (const Fr*)Ms[k]->val, z, ab + k * m,
+                      (u32)n_c, k == 0 ? (u32)n_inst : 0u, (u32)m);
         typename N::Post e1;                                   // ifft (DIF) of a, b with "* g^j", as in run()
         e1.post = 2;
         e1.nvec = 2;
         e1.pw = (const Fr*)T->pw_g;
         HK_TRY(N::passes(s, ab, m, 2, log_m, (const Fr*)T->tw_inv, 0, e1));
         HK_TRY(N::passes(s, ab, m, 2, log_m, (const Fr*)T->tw_fwd, 1));       // coset fft (DIT) of a, b
-        hipLaunchKernelGGL((k_mul_pointwise<Fr>), dim3((u32)((m + 255) / 256)), dim3(256), 0, s, ab, ab + m, m);
-        HK_HIP(hipGetLastError());
+        HK_LAUNCH((k_mul_pointwise<Fr>), dim3((u32)((m + 255) / 256)), dim3(256), 0, s, ab, ab + m, m);
         return HK_OK;
     }
 };

@@ -20,14 +20,12 @@ hk_status PairRun<P>::gt_pow(hipStream_t s, const Fp12<P>* in, const void* scala
     const bool plain = !in_gt || getenv("HK_GT_POW_PLAIN") != nullptr;   // the 254-step chain: any Fq12 element (or A/B)
     if (plain) {
         size_t lds = sizeof(WaveArea<P>) + 2 * WV_SLOT * sizeof(Fp<P>);
-        hipLaunchKernelGGL((k_gt_pow<P, Fr>), dim3(n), dim3(64), lds, s, in, (const Fr*)scalars_mont, n, out);
+        HK_LAUNCH((k_gt_pow<P, Fr>), dim3(n), dim3(64), lds, s, in, (const Fr*)scalars_mont, n, out);
     } else {
         static const EndoSplit<4> E = endo_split_g2((const P*)nullptr);
         size_t lds = sizeof(WaveArea<P>) + 16 * WV_SLOT * sizeof(Fp<P>);
-        hipLaunchKernelGGL((k_gt_pow_endo<P, Fr>), dim3(n), dim3(64), lds, s, in, (const Fr*)scalars_mont, n, E, out);
+        HK_LAUNCH((k_gt_pow_endo<P, Fr>), dim3(n), dim3(64), lds, s, in, (const Fr*)scalars_mont, n, E, out);
     }
-    HK_DBG(s, "k_gt_pow");
-    HK_HIP(hipGetLastError());
     return HK_OK;
 }
 
@@ -35,9 +33,7 @@ template <class P>
 hk_status PairRun<P>::gt_check(hipStream_t s, const Fp12<P>* in, u32 n, unsigned char* ok) {
     if (n == 0) return HK_OK;
     size_t lds = sizeof(WaveArea<P>) + 3 * WV_SLOT * sizeof(Fp<P>);
-    hipLaunchKernelGGL((k_gt_check<P>), dim3(n), dim3(64), lds, s, in, n, ok);
-    HK_DBG(s, "k_gt_check");
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_gt_check<P>), dim3(n), dim3(64), lds, s, in, n, ok);
     return HK_OK;
 }
 
@@ -46,25 +42,13 @@ template <class P>
 hk_status PairRun<P>::gt_prod(hipStream_t s, const Fp12<P>* in, u32 len, u32 groups, Fp12<P>* out) {
     if (groups == 0 || len == 0) return HK_OK;
     size_t lds_tree = sizeof(WaveArea<P>) + 2 * WV_SLOT * sizeof(Fp<P>);
-    hipLaunchKernelGGL((k_pair_tree<P>), dim3(1, groups), dim3(64), lds_tree, s, in, len, len, out);
-    HK_DBG(s, "k_pair_tree (gt_prod)");
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_pair_tree<P>), dim3(1, groups), dim3(64), lds_tree, s, in, len, len, out);
     return HK_OK;
 }
 
-template <class P>
-size_t PairRun<P>::max_private_bytes() {
-    const void* ks[] = {(const void*)k_pair_lines<Fp2<P>>, (const void*)k_pair_lines<Fp2Q<P>>, (const void*)k_pair_tree_lines<P>, (const void*)k_pair_tree<P>,
-                        (const void*)k_pair_horner<P>,
-                        (const void*)k_gt_pow<P, typename ScalarOfQ<P>::type>, (const void*)k_gt_pow_endo<P, typename ScalarOfQ<P>::type>,
-                        (const void*)k_gt_check<P>};
-    const void* serial[] = {(const void*)k_pair_miller<P>, (const void*)k_f12_product<P>, (const void*)k_final_exp<P>};
-    size_t m = 0;
-    for (const void* k : ks) { size_t b = hk_private_bytes_of(k); if (b > m) m = b; }
-    if (getenv("HK_PAIR_SERIAL"))            // the one-lane-per-pair debugging path carries the deepest frames (5 KB)
-        for (const void* k : serial) { size_t b = hk_private_bytes_of(k); if (b > m) m = b; }
-    return m;
-}
+// the one-lane-per-pair debugging path: its kernels carry the deepest frames (5 KB) and count towards the scratch budget
+// only when the switch is set (launch.h)
+struct PairSerialGate { static const char* env() { return "HK_PAIR_SERIAL"; } };
 
 template <class P>
 u32 PairRun<P>::steps() {
@@ -95,18 +79,15 @@ hk_status PairRun<P>::run(hipStream_t s, const Affine<Fp<P>>* g1, const Affine<F
     size_t total = (size_t)n * count;
     if (count == 0 || n == 0) return HK_ERR_ARG;
     PairLoop loop = PairLoopOf<P>::get();
-    static const bool serial = getenv("HK_PAIR_SERIAL") != nullptr;      // one lane per pair / per product (A/B, debugging)
+    static const bool serial = getenv(PairSerialGate::env()) != nullptr;     // one lane per pair / per product (A/B, debugging)
     size_t lds_tree = sizeof(WaveArea<P>) + 2 * WV_SLOT * sizeof(Fp<P>);
     size_t lds_fin = sizeof(WaveArea<P>) + WV_FINISH_SLOTS * WV_SLOT * sizeof(Fp<P>);
     if (serial && !pairs) {
-        hipLaunchKernelGGL((k_pair_miller<P>), dim3((u32)((total + 63) / 64)), dim3(64), 0, s, g1, g2, n, n_l, n_r, loop, miller);
-        HK_DBG(s, "k_pair_miller");
-        hipLaunchKernelGGL((k_f12_product<P>), dim3(count), dim3(PAIR_TREE_THREADS), sizeof(Fp12<P>) * PAIR_TREE_THREADS, s,
-                           (const Fp12<P>*)miller, n, prod);
-        HK_DBG(s, "k_f12_product");
-        hipLaunchKernelGGL((k_final_exp<P>), dim3(count), dim3(64), sizeof(Fp12<P>) * PAIR_FEXP_WORDS, s,
-                           (const Fp12<P>*)prod, count, out);
-        HK_DBG(s, "k_final_exp");
+        HK_LAUNCH_GATED(PairSerialGate, (k_pair_miller<P>), dim3((u32)((total + 63) / 64)), dim3(64), 0, s, g1, g2, n, n_l, n_r, loop, miller);
+        HK_LAUNCH_GATED(PairSerialGate, (k_f12_product<P>), dim3(count), dim3(PAIR_TREE_THREADS), sizeof(Fp12<P>) * PAIR_TREE_THREADS, s,
+                        (const Fp12<P>*)miller, n, prod);
+        HK_LAUNCH_GATED(PairSerialGate, (k_final_exp<P>), dim3(count), dim3(64), sizeof(Fp12<P>) * PAIR_FEXP_WORDS, s,
+                        (const Fp12<P>*)prod, count, out);
     } else {
         // pipeline (pairing_wave.cuh): lines -> per-step product trees (wave multiplier) -> Horner + final exponentiation
         PairSteps st = pair_steps(loop, TowerParams<P>::TWIST_IS_D);
@@ -121,27 +102,22 @@ hk_status PairRun<P>::run(hipStream_t s, const Affine<Fp<P>>* g1, const Affine<F
         // few points: a quad of lanes per point (4 n n_r lanes still at most one wave per SIMD)
         const bool quad = (size_t)n * n_r * 4 <= SPLIT_MAX_LANES && getenv("HK_ENDO_NO_QUAD") == nullptr;
         if (quad)
-            hipLaunchKernelGGL((k_pair_lines<Fp2Q<P>>), dim3((4 * n + 63) / 64, n_r), dim3(64), 0, s,
-                               (const Affine<Fp2Q<P>>*)g2, n, n_r, loop, S, lines);
+            HK_LAUNCH((k_pair_lines<Fp2Q<P>>), dim3((4 * n + 63) / 64, n_r), dim3(64), 0, s,
+                      (const Affine<Fp2Q<P>>*)g2, n, n_r, loop, S, lines);
         else
-            hipLaunchKernelGGL((k_pair_lines<Fp2<P>>), dim3((n + 63) / 64, n_r), dim3(64), 0, s, g2, n, n_r, loop, S, lines);
-        HK_DBG(s, "k_pair_lines");
-        hipLaunchKernelGGL((k_pair_tree_lines<P>), dim3(g0, count * S), dim3(64), lds_tree, s, (const Line6<P>*)lines, g1, n, 16u, n_r, S, pl, pp[0]);
-        HK_DBG(s, "k_pair_tree_lines");
+            HK_LAUNCH((k_pair_lines<Fp2<P>>), dim3((n + 63) / 64, n_r), dim3(64), 0, s, g2, n, n_r, loop, S, lines);
+        HK_LAUNCH((k_pair_tree_lines<P>), dim3(g0, count * S), dim3(64), lds_tree, s, (const Line6<P>*)lines, g1, n, 16u, n_r, S, pl, pp[0]);
         u32 m = g0;
         int cur = 0;
         while (m > 1) {
             u32 groups = (m + 15) / 16;
-            hipLaunchKernelGGL((k_pair_tree<P>), dim3(groups, count * S), dim3(64), lds_tree, s, (const Fp12<P>*)pp[cur], m, 16u,
-                               pp[cur ^ 1]);
-            HK_DBG(s, "k_pair_tree");
+            HK_LAUNCH((k_pair_tree<P>), dim3(groups, count * S), dim3(64), lds_tree, s, (const Fp12<P>*)pp[cur], m, 16u,
+                      pp[cur ^ 1]);
             cur ^= 1;
             m = groups;
         }
-        hipLaunchKernelGGL((k_pair_horner<P>), dim3(count), dim3(64), lds_fin, s, (const Fp12<P>*)pp[cur], st, out);
-        HK_DBG(s, "k_pair_horner");
+        HK_LAUNCH((k_pair_horner<P>), dim3(count), dim3(64), lds_fin, s, (const Fp12<P>*)pp[cur], st, out);
     }
-    HK_HIP(hipGetLastError());
     return HK_OK;
 }
 

@@ -77,8 +77,7 @@ hk_status Ops<C>::pairing_pairs(hk_ctx* ctx, const void* const* lhs, size_t n_lh
         if (ok) {
             u32 gx = (most + 255) / 256;
             if (gx > 1024) gx = 1024;
-            hipLaunchKernelGGL((k_gather_rows<Fr>), dim3(gx, (u32)(n_lhs + n_rhs)), dim3(256), 0, s, gr);
-            HK_HIP(hipGetLastError());
+            HK_LAUNCH((k_gather_rows<Fr>), dim3(gx, (u32)(n_lhs + n_rhs)), dim3(256), 0, s, gr);
             packed = true;
         }
     }

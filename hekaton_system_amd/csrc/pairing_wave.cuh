@@ -507,29 +507,6 @@ k_pair_horner(const Fp12<P>* __restrict__ L, PairSteps st, Fp12<P>* __restrict__
     W::store(&out[blockIdx.x], acc);
 }
 
-// One wave per product: the product of its n Miller values (each lane-group of the wave takes a strided share through
-// the wave multiplier: acc *= in[i]), then the final exponentiation.  in: [count][n] canonical Fq12; out: [count].
-template <class P>
-__global__ void __launch_bounds__(64)
-k_pair_finish(const Fp12<P>* __restrict__ in, u32 n, Fp12<P>* __restrict__ out) {
-    extern __shared__ unsigned char pair_lds[];
-    typedef WaveF12<P> W;
-    typedef Fp<P> Fq;
-    WaveArea<P>* w = reinterpret_cast<WaveArea<P>*>(pair_lds);
-    Fq* s = reinterpret_cast<Fq*>(pair_lds + sizeof(WaveArea<P>));
-    WaveF12<P>::init(w);
-    const Fp12<P>* src = in + (size_t)blockIdx.x * n;
-    Fq* acc = s;
-    Fq* cur = s + 9 * WV_SLOT;
-    W::load(acc, &src[0]);
-    for (u32 i = 1; i < n; i++) {
-        W::load(cur, &src[i]);
-        W::mul(acc, acc, cur, w);
-    }
-    W::final_exp(s, w);
-    W::store(&out[blockIdx.x], acc);
-}
-
 // Tree level of the Miller-value product: wave g multiplies in[g*c .. min((g+1)*c, n)) of its product -> out[g].
 // grid = (groups, count); in: [count][n], out: [count][groups].
 template <class P>

@@ -179,7 +179,7 @@ hk_status Ops<C>::pk_upload(hk_ctx* ctx, const hk_pk_desc* d, hk_pk** out) {
         auto select = [&](const Affine<Fq>* staged, bool* compact, u32* n_out, MsmPlan* plan, u32** idx_d, u32** rank_d) -> hk_status {
             std::vector<u32> idx;
             if (nq) {
-                hipLaunchKernelGGL((k_mark_noninf<Fq>), dim3((u32)((nq + 255) / 256)), dim3(256), 0, s0, staged, flags, (u32)nq);
+                HK_LAUNCH((k_mark_noninf<Fq>), dim3((u32)((nq + 255) / 256)), dim3(256), 0, s0, staged, flags, (u32)nq);
                 std::vector<u32> hf(nq);
                 if (hipMemcpy(hf.data(), flags, 4 * nq, hipMemcpyDeviceToHost) != hipSuccess) return HK_ERR_DEVICE;
                 for (size_t i = 0; i < nq; i++) if (hf[i]) idx.push_back((u32)i);
@@ -216,14 +216,14 @@ hk_status Ops<C>::pk_upload(hk_ctx* ctx, const hk_pk_desc* d, hk_pk** out) {
             hipMemset(pk->b2_tab, 0, g2 * pk->b_n) != hipSuccess)
             return tfail(HK_ERR_DEVICE);
         if (pk->a_compact) {
-            hipLaunchKernelGGL((k_gather<Affine<Fq>>), dim3((pk->a_n + 255) / 256), dim3(256), 0, s0, pk->a_tab, (const Affine<Fq>*)sa, (const u32*)a_idx, pk->a_n, (u32)nq);
+            if (HK_LAUNCH_STATUS((k_gather<Affine<Fq>>), dim3((pk->a_n + 255) / 256), dim3(256), 0, s0, pk->a_tab, (const Affine<Fq>*)sa, (const u32*)a_idx, pk->a_n, (u32)nq) != HK_OK) return tfail(HK_ERR_DEVICE);
         } else if (nq) {
             if (hipMemcpy(pk->a_tab, sa, g1 * nq, hipMemcpyDeviceToDevice) != hipSuccess) return tfail(HK_ERR_DEVICE);
         }
         if (pk->b_compact) {
             u32 blocks = (pk->b_n + 255) / 256;
-            hipLaunchKernelGGL((k_gather<Affine<Fq>>), dim3(blocks), dim3(256), 0, s0, pk->b1_tab, (const Affine<Fq>*)sb1, (const u32*)b_idx, pk->b_n, (u32)nq);
-            hipLaunchKernelGGL((k_gather<Affine<Fq2>>), dim3(blocks), dim3(256), 0, s0, pk->b2_tab, (const Affine<Fq2>*)sb2, (const u32*)b_idx, pk->b_n, (u32)nq);
+            if (HK_LAUNCH_STATUS((k_gather<Affine<Fq>>), dim3(blocks), dim3(256), 0, s0, pk->b1_tab, (const Affine<Fq>*)sb1, (const u32*)b_idx, pk->b_n, (u32)nq) != HK_OK) return tfail(HK_ERR_DEVICE);
+            if (HK_LAUNCH_STATUS((k_gather<Affine<Fq2>>), dim3(blocks), dim3(256), 0, s0, pk->b2_tab, (const Affine<Fq2>*)sb2, (const u32*)b_idx, pk->b_n, (u32)nq) != HK_OK) return tfail(HK_ERR_DEVICE);
         } else if (nq) {
             if (hipMemcpy(pk->b1_tab, sb1, g1 * nq, hipMemcpyDeviceToDevice) != hipSuccess) return tfail(HK_ERR_DEVICE);
             if (hipMemcpy(pk->b2_tab, sb2, g2 * nq, hipMemcpyDeviceToDevice) != hipSuccess) return tfail(HK_ERR_DEVICE);
@@ -335,8 +335,8 @@ hk_status Ops<C>::pk_upload(hk_ctx* ctx, const hk_pk_desc* d, hk_pk** out) {
             (void)hipFree(hb_tmp); hb_tmp = nullptr;
             PK_TRY(MsmRun<Fq>::build_tables(s0, pk->l_tab, pk->l_n, pz.F, shift));
         } else {
-            hipLaunchKernelGGL((k_pk_bitrev_copy<Fq>), dim3((u32)((m + 255) / 256)), dim3(256), 0, s0, pk->h_tab,
-                               src, (u32)d->h_len, pk->log_m);
+            PK_TRY(HK_LAUNCH_STATUS((k_pk_bitrev_copy<Fq>), dim3((u32)((m + 255) / 256)), dim3(256), 0, s0, pk->h_tab,
+                                    src, (u32)d->h_len, pk->log_m));
             PK_HIP(hipDeviceSynchronize());
         }
         if (staging) { (void)hipFree(staging); staging = nullptr; }

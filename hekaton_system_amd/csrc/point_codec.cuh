@@ -240,16 +240,6 @@ k_points_compress(const Affine<F>* __restrict__ pts, u32 n, F* __restrict__ x_ca
     flags[i] = fl;
 }
 
-template <class P>
-size_t CodecRun<P>::max_private_bytes() {
-    const void* ks[] = {(const void*)k_field_sqrt<Fp<P>>, (const void*)k_field_sqrt<Fp2<P>>,
-                        (const void*)k_points_decompress<Fp<P>>, (const void*)k_points_decompress<Fp2<P>>,
-                        (const void*)k_points_compress<Fp<P>>, (const void*)k_points_compress<Fp2<P>>};
-    size_t m = 0;
-    for (const void* k : ks) { size_t b = hk_private_bytes_of(k); if (b > m) m = b; }
-    return m;
-}
-
 // One element-wise pass over n elements in chunks: buffer k holds elements of sz[k] bytes, the first n_in are inputs.
 // launch(chunk's device pointers, elements) queues the kernel on the lane's stream.
 template <class Launch>
@@ -265,8 +255,7 @@ static hk_status codec_pass(hk_ctx* ctx, void* const* bufs, const size_t* sz, in
         HK_TRY(stage_upload(L, io, (size_t)n_in));
         void* p[4];
         for (int b = 0; b < n_bufs; b++) p[b] = io[b].p;
-        launch(L->stream, p, (u32)k);
-        HK_HIP(hipGetLastError());
+        HK_TRY(launch(L->stream, p, (u32)k));
         HK_TRY(stage_download(L, io + n_in, (size_t)(n_bufs - n_in)));
         HK_TRY(L->settle());
     }
@@ -280,7 +269,8 @@ hk_status CodecRun<P>::field_sqrt(hk_ctx* ctx, int which, const void* in, size_t
         void* bufs[3] = {(void*)in, out, ok};
         const size_t sz[3] = {sizeof(F), sizeof(F), 1};
         return codec_pass(ctx, bufs, sz, 3, 1, n, [](hipStream_t s, void* const* p, u32 k) {
-            hipLaunchKernelGGL((k_field_sqrt<F>), dim3((k + 63) / 64), dim3(64), 0, s, (const F*)p[0], k, (F*)p[1], (unsigned char*)p[2]);
+            HK_LAUNCH((k_field_sqrt<F>), dim3((k + 63) / 64), dim3(64), 0, s, (const F*)p[0], k, (F*)p[1], (unsigned char*)p[2]);
+            return HK_OK;
         });
     };
     return which == 1 ? run(Fp<P>()) : run(Fp2<P>());
@@ -294,8 +284,9 @@ hk_status CodecRun<P>::points_decompress(hk_ctx* ctx, int group, const void* x_c
         void* bufs[4] = {(void*)x_canon, (void*)flags, points_out, status};
         const size_t sz[4] = {sizeof(F), 1, sizeof(Affine<F>), 1};
         return codec_pass(ctx, bufs, sz, 4, 2, n, [check](hipStream_t s, void* const* p, u32 k) {
-            hipLaunchKernelGGL((k_points_decompress<F>), dim3((k + 63) / 64), dim3(64), 0, s, (const F*)p[0], (const unsigned char*)p[1],
-                               k, check, (Affine<F>*)p[2], (unsigned char*)p[3]);
+            HK_LAUNCH((k_points_decompress<F>), dim3((k + 63) / 64), dim3(64), 0, s, (const F*)p[0], (const unsigned char*)p[1],
+                      k, check, (Affine<F>*)p[2], (unsigned char*)p[3]);
+            return HK_OK;
         });
     };
     return group == 1 ? run(Fp<P>()) : run(Fp2<P>());
@@ -309,8 +300,9 @@ hk_status CodecRun<P>::points_compress(hk_ctx* ctx, int group, const void* point
         void* bufs[3] = {(void*)points, x_canon_out, flags_out};
         const size_t sz[3] = {sizeof(Affine<F>), sizeof(F), 1};
         return codec_pass(ctx, bufs, sz, 3, 1, n, [](hipStream_t s, void* const* p, u32 k) {
-            hipLaunchKernelGGL((k_points_compress<F>), dim3((k + 63) / 64), dim3(64), 0, s, (const Affine<F>*)p[0], k, (F*)p[1],
-                               (unsigned char*)p[2]);
+            HK_LAUNCH((k_points_compress<F>), dim3((k + 63) / 64), dim3(64), 0, s, (const Affine<F>*)p[0], k, (F*)p[1],
+                      (unsigned char*)p[2]);
+            return HK_OK;
         });
     };
     return group == 1 ? run(Fp<P>()) : run(Fp2<P>());

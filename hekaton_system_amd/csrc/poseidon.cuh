@@ -158,13 +158,14 @@ k_poseidon_membership(const Fr* __restrict__ consts, PoseidonDesc leaf_d, Poseid
 // the membership block of every row on stream s: behind the kernels that fill the row's other columns in a job entry (src =
 // index = its rows, stride 2: no table of its own), the whole of hk_poseidon_path (src NULL, stride 1)
 template <class Fr, int NF>
-void poseidon_membership(hipStream_t s, const void* consts, const hk_poseidon_desc* leaf_hash, const hk_poseidon_desc* node_hash,
-                         const void* leaves, const void* siblings, const u32* src, const u32* index, u32 stride, size_t depth,
-                         size_t batch, size_t n_v, size_t col0, void* z_out) {
+hk_status poseidon_membership(hipStream_t s, const void* consts, const hk_poseidon_desc* leaf_hash, const hk_poseidon_desc* node_hash,
+                              const void* leaves, const void* siblings, const u32* src, const u32* index, u32 stride, size_t depth,
+                              size_t batch, size_t n_v, size_t col0, void* z_out) {
     const u32 nb = (u32)batch;
-    hipLaunchKernelGGL((k_poseidon_membership<Fr, NF>), dim3((nb + S1_WG_ROWS - 1) / S1_WG_ROWS), dim3(256), 0, s, (const Fr*)consts,
-                       poseidon_desc(leaf_hash), poseidon_desc(node_hash), (const Fr*)leaves, (const Fr*)siblings, src, index,
-                       stride, (u32)depth, nb, n_v, col0, (Fr*)z_out);
+    HK_LAUNCH((k_poseidon_membership<Fr, NF>), dim3((nb + S1_WG_ROWS - 1) / S1_WG_ROWS), dim3(256), 0, s, (const Fr*)consts,
+              poseidon_desc(leaf_hash), poseidon_desc(node_hash), (const Fr*)leaves, (const Fr*)siblings, src, index,
+              stride, (u32)depth, nb, n_v, col0, (Fr*)z_out);
+    return HK_OK;
 }
 
 }  // namespace hk

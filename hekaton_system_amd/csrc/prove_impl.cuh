@@ -131,14 +131,6 @@ __global__ void __launch_bounds__(64) k_finish_c(const XYZZ<Fq>* __restrict__ pa
 }
 
 template <class C>
-size_t Ops<C>::finish_private_bytes() {
-    size_t ab = hk_private_bytes_of((const void*)k_finish_ab<Fr, Fq, Fq2>);
-    size_t c = hk_private_bytes_of((const void*)k_finish_c<Fq>);
-    size_t hb = HBasis<C>::private_bytes();                 // the evaluation-basis key's one-time kernels (h_basis.cuh)
-    return std::max(std::max(ab, c), hb);
-}
-
-template <class C>
 hk_status Ops<C>::commit(hk_ctx* ctx, const hk_pk* h, size_t stage, const void* w, size_t n,
                          const void* kappa, void* out) {
     if (h->ctx != ctx) return HK_ERR_ARG;                  // a key lives on the context (device) that uploaded it
@@ -347,8 +339,8 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
         HK_HIP(hipMemcpyAsync(small, rsk.data() + b0 * rs_stride * fr, nb * rs_stride * fr, hipMemcpyHostToDevice, s));
         // --- one digit sort per proof for the four assignment-indexed queries: L reads its list as it is, A and B too, or -
         // when they run over their non-infinity bases only - the sub-list of it that their rank table selects
-        hipLaunchKernelGGL((k_prep_ext<Fr>), dim3(64), dim3(256), 0, s, zext + (n_v - 1), pk->n_ext, (const Fr*)small,
-                           (u32)rs_stride, (u32)n_kappas, nb, sb.count, sbh.count, pz.NB * nb, ph.NB * nb);
+        HK_LAUNCH((k_prep_ext<Fr>), dim3(64), dim3(256), 0, s, zext + (n_v - 1), pk->n_ext, (const Fr*)small,
+                  (u32)rs_stride, (u32)n_kappas, nb, sb.count, sbh.count, pz.NB * nb, ph.NB * nb);
         // Fork: the five queries are independent once their scalars exist.  Streams let the latency-bound tails
         // (segmented levels, bucket reduction) of one query hide under the throughput-bound accumulation of another;
         // every launch covers the whole chunk.
@@ -413,15 +405,13 @@ hk_status Ops<C>::prove_batch(hk_ctx* ctx, const hk_pk* h, size_t n_v, size_t n_
         HK_TRY(wait(s, ev[3], sB1));
         HK_TRY(wait(s, ev[4], sB2));
         HK_TRY(wait(s, ev[18], sL));
-        hipLaunchKernelGGL((k_finish_ab<Fr, Fq, Fq2>), dim3(3, nb), dim3(64), 0, s, res1, res2, pk->consts_g1, pk->consts_g2,
-                           (const Fr*)small, (u32)rs_stride, oa, ob, pc, endo_g1);
-        HK_HIP(hipGetLastError());
+        HK_LAUNCH((k_finish_ab<Fr, Fq, Fq2>), dim3(3, nb), dim3(64), 0, s, res1, res2, pk->consts_g1, pk->consts_g2,
+                  (const Fr*)small, (u32)rs_stride, oa, ob, pc, endo_g1);
         if (!h_first) HK_TRY(submit_h());
         // Join H
         HK_TRY(wait(s, ev[7], sH));
         if (prof) HK_HIP(hipEventRecord(ev[19], s));                           // all queries and finish_ab done
-        hipLaunchKernelGGL((k_finish_c<Fq>), dim3(1), dim3(64), 0, s, (const XYZZ<Fq>*)pc, (const XYZZ<Fq>*)res1, oc, nb);
-        HK_HIP(hipGetLastError());
+        HK_LAUNCH((k_finish_c<Fq>), dim3(1), dim3(64), 0, s, (const XYZZ<Fq>*)pc, (const XYZZ<Fq>*)res1, oc, nb);
         HK_HIP(hipMemcpyAsync(ha.data(), oa, nb * sizeof(Affine<Fq>), hipMemcpyDeviceToHost, s));
         HK_HIP(hipMemcpyAsync(hb.data(), ob, nb * sizeof(Affine<Fq2>), hipMemcpyDeviceToHost, s));
         HK_HIP(hipMemcpyAsync(hc.data(), oc, nb * sizeof(Affine<Fq>), hipMemcpyDeviceToHost, s));

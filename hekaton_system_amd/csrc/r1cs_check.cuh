@@ -144,18 +144,17 @@ struct R1csRun {
         Fr* vals_d = want_vals ? (vals_host ? vals_s : (Fr*)bad_vals) : nullptr;
         for (size_t b0 = 0; b0 < batch && n_rows; b0 += 32768) {       // grid.y < 65 536
             const u32 nb = (u32)(batch - b0 < 32768 ? batch - b0 : 32768);
-            hipLaunchKernelGGL((k_r1cs_rows<Fr>), dim3((n_rows + 255) / 256, nb), dim3(256), 0, s, M[0].row_ptr, M[0].col,
-                               (const Fr*)M[0].val, M[1].row_ptr, M[1].col, (const Fr*)M[1].val, M[2].row_ptr, M[2].col,
-                               (const Fr*)M[2].val, z + b0 * n_v, n_v, n_rows, words, bitmap + b0 * words);
+            HK_LAUNCH((k_r1cs_rows<Fr>), dim3((n_rows + 255) / 256, nb), dim3(256), 0, s, M[0].row_ptr, M[0].col,
+                      (const Fr*)M[0].val, M[1].row_ptr, M[1].col, (const Fr*)M[1].val, M[2].row_ptr, M[2].col,
+                      (const Fr*)M[2].val, z + b0 * n_v, n_v, n_rows, words, bitmap + b0 * words);
         }
-        hipLaunchKernelGGL((k_r1cs_compact<0>), dim3((u32)batch), dim3(256), 0, s, (const u64*)bitmap, words, vd, rows_d, (u32)cap);
+        HK_LAUNCH((k_r1cs_compact<0>), dim3((u32)batch), dim3(256), 0, s, (const u64*)bitmap, words, vd, rows_d, (u32)cap);
         if (want_vals) {
             const u32 total = (u32)(batch * cap);
-            hipLaunchKernelGGL((k_r1cs_vals<Fr>), dim3((total + 255) / 256), dim3(256), 0, s, M[0].row_ptr, M[0].col, (const Fr*)M[0].val,
-                               M[1].row_ptr, M[1].col, (const Fr*)M[1].val, M[2].row_ptr, M[2].col, (const Fr*)M[2].val, z, n_v,
-                               (const u32*)rows_d, (u32)cap, total, vals_d);
+            HK_LAUNCH((k_r1cs_vals<Fr>), dim3((total + 255) / 256), dim3(256), 0, s, M[0].row_ptr, M[0].col, (const Fr*)M[0].val,
+                      M[1].row_ptr, M[1].col, (const Fr*)M[1].val, M[2].row_ptr, M[2].col, (const Fr*)M[2].val, z, n_v,
+                      (const u32*)rows_d, (u32)cap, total, vals_d);
         }
-        HK_HIP(hipGetLastError());
         static_assert(sizeof(R1Verdict) == sizeof(hk_r1cs_verdict), "hk_r1cs_verdict is two u32");
         HK_HIP(hipMemcpyAsync(verdicts, vd, batch * sizeof(R1Verdict), hipMemcpyDeviceToHost, s));
         if (rows_host) HK_HIP(hipMemcpyAsync(bad_rows, rows_s, batch * cap * 4, hipMemcpyDeviceToHost, s));

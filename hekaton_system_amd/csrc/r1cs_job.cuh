@@ -100,9 +100,8 @@ hk_status Ops<C>::r1cs_job_trace(hk_ctx* ctx, const hk_r1cs_job_desc* d, void* t
     HK_TRY(stage_upload(L, &in, 1));
     HK_HIP(hipMemcpyAsync(rank_d, d->slot_rank, 4 * S, hipMemcpyHostToDevice, s));
     HK_HIP(hipMemcpyAsync(src_d, d->slot_src, 4 * S, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL((k_rj_trace<Fr>), dim3((u32)((n_fr + 255) / 256)), dim3(256), 0, s, (const Fr*)wit, (const u32*)rank_d,
-                       (const u32*)src_d, (u32)S, d->sets_per_tx, d->tx_stride, (u32)n_fr, out_d);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_rj_trace<Fr>), dim3((u32)((n_fr + 255) / 256)), dim3(256), 0, s, (const Fr*)wit, (const u32*)rank_d,
+              (const u32*)src_d, (u32)S, d->sets_per_tx, d->tx_stride, (u32)n_fr, out_d);
     HK_TRY(stage_download(L, &out, 1));
     return L->settle();
 }
@@ -146,10 +145,9 @@ hk_status Ops<C>::r1cs_job_witness(hk_ctx* ctx, const hk_r1cs_job_desc* d, const
     const u32 per = (u32)(1 + len);                                // <= n_v < 2^31
     for (size_t b0 = 0; b0 < batch; b0 += RJ_GRID_ROWS) {           // a grid's y holds at most 65 535 rows
         const u32 nb = (u32)std::min(batch - b0, (size_t)RJ_GRID_ROWS);
-        hipLaunchKernelGGL((k_rj_body<Fr>), dim3((per + 255) / 256, nb), dim3(256), 0, s, (const Fr*)wit, (const u64*)base_d + b0, per,
-                           n_v, body_col0, (Fr*)z_out + b0 * n_v);
+        HK_LAUNCH((k_rj_body<Fr>), dim3((per + 255) / 256, nb), dim3(256), 0, s, (const Fr*)wit, (const u64*)base_d + b0, per,
+                  n_v, body_col0, (Fr*)z_out + b0 * n_v);
     }
-    HK_HIP(hipGetLastError());
     return L->settle();
 }
 

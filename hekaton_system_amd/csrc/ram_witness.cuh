@@ -278,14 +278,12 @@ hk_status Ops<C>::ram_stage0_witness(hk_ctx* ctx, const uint32_t* offsets, uint3
     RwArgs<Fr> a{(const Fr*)in[0].p, (const Fr*)in[1].p, rows_d, ts32, same, (u32)batch, (u32)K, 70 * K, 0, 0, 0, (Fr*)w_out};
     const u64 n_canon = (u64)batch * (2 * K + 1), n_fill = (u64)batch * 70 * K;
     // the timestamps and the error word first: nothing touches w_out before the host has read it (as hk_ram_stage1_witness)
-    hipLaunchKernelGGL((k_rw_canon<Fr>), dim3((u32)((n_canon + 255) / 256)), dim3(256), 0, s, a, flag);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_rw_canon<Fr>), dim3((u32)((n_canon + 255) / 256)), dim3(256), 0, s, a, flag);
     u32 fl = 0;
     HK_HIP(hipMemcpyAsync(&fl, flag, 4, hipMemcpyDeviceToHost, s));
     HK_HIP(hipStreamSynchronize(s));
     if (fl) { HK_TRY(L->settle()); return HK_ERR_ARG; }
-    hipLaunchKernelGGL((k_rw_stage0<Fr>), dim3((u32)((n_fill + 255) / 256)), dim3(256), 0, s, a);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_rw_stage0<Fr>), dim3((u32)((n_fill + 255) / 256)), dim3(256), 0, s, a);
     return L->settle();
 }
 
@@ -333,23 +331,21 @@ hk_status Ops<C>::ram_stage1_witness(hk_ctx* ctx, const hk_ram_stage1_desc* d, c
     const u32 nb = (u32)batch;
     auto blocks = [](u64 lanes) { return dim3((u32)((lanes + 255) / 256)); };
     // the timestamps and the error word first: nothing touches z_out before the host has read it
-    hipLaunchKernelGGL((k_rw_canon<Fr>), blocks((u64)batch * (2 * K + 1)), dim3(256), 0, s, a, flag);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_rw_canon<Fr>), blocks((u64)batch * (2 * K + 1)), dim3(256), 0, s, a, flag);
     u32 fl = 0;
     HK_HIP(hipMemcpyAsync(&fl, flag, 4, hipMemcpyDeviceToHost, s));
     HK_HIP(hipStreamSynchronize(s));
     if (fl) { HK_TRY(L->settle()); return HK_ERR_ARG; }
     if (d->template_mont)
-        hipLaunchKernelGGL((k_rw_template<Fr>), blocks((u64)batch * n_v), dim3(256), 0, s, (const Fr*)in[7].p, (u64)batch * n_v, n_v,
-                           (Fr*)z_out);
-    hipLaunchKernelGGL((k_rw_fill<Fr>), blocks((u64)batch * (40 + 105 * K)), dim3(256), 0, s, a, ch, (const Fr*)in[6].p);
-    hipLaunchKernelGGL((k_rw_products<Fr>), blocks((u64)batch * 3 * K), dim3(256), 0, s, a, ch);
-    hipLaunchKernelGGL((k_rw_chunk_prod<Fr>), blocks((u64)2 * batch * n_chunks), dim3(256), 0, s, a, ch, n_chunks, prods);
-    hipLaunchKernelGGL((k_rw_chunk_scan<Fr>), dim3((2 * nb + 63) / 64), dim3(64), 0, s, a, (const Fr*)in[3].p, n_chunks, prods);
-    hipLaunchKernelGGL((k_rw_chain_walk<Fr>), blocks((u64)2 * batch * n_chunks), dim3(256), 0, s, a, ch, n_chunks, (const Fr*)prods);
-    poseidon_membership<Fr, 6>(s, in[2].p, d->leaf_hash, d->node_hash, in[4].p, in[5].p, rows_d, rows_d, 2, depth, batch, n_v,
-                               (size_t)d->pos_col0, z_out);
-    HK_HIP(hipGetLastError());
+        HK_LAUNCH((k_rw_template<Fr>), blocks((u64)batch * n_v), dim3(256), 0, s, (const Fr*)in[7].p, (u64)batch * n_v, n_v,
+                  (Fr*)z_out);
+    HK_LAUNCH((k_rw_fill<Fr>), blocks((u64)batch * (40 + 105 * K)), dim3(256), 0, s, a, ch, (const Fr*)in[6].p);
+    HK_LAUNCH((k_rw_products<Fr>), blocks((u64)batch * 3 * K), dim3(256), 0, s, a, ch);
+    HK_LAUNCH((k_rw_chunk_prod<Fr>), blocks((u64)2 * batch * n_chunks), dim3(256), 0, s, a, ch, n_chunks, prods);
+    HK_LAUNCH((k_rw_chunk_scan<Fr>), dim3((2 * nb + 63) / 64), dim3(64), 0, s, a, (const Fr*)in[3].p, n_chunks, prods);
+    HK_LAUNCH((k_rw_chain_walk<Fr>), blocks((u64)2 * batch * n_chunks), dim3(256), 0, s, a, ch, n_chunks, (const Fr*)prods);
+    HK_TRY((poseidon_membership<Fr, 6>(s, in[2].p, d->leaf_hash, d->node_hash, in[4].p, in[5].p, rows_d, rows_d, 2, depth, batch, n_v,
+                                       (size_t)d->pos_col0, z_out)));
     return L->settle();
 }
 

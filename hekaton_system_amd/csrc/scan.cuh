@@ -72,10 +72,9 @@ __global__ void __launch_bounds__(256) k_scan_u32_add(u32* __restrict__ out, con
 static hk_status scan_u32(hipStream_t s, const u32* in, u32* out, u32* tops, u32 n) {
     if (n == 0) return HK_OK;
     u32 nt = (n + SCAN_U32_TILE - 1) / SCAN_U32_TILE;
-    hipLaunchKernelGGL((k_scan_u32_tile<0>), dim3(nt), dim3(256), 0, s, in, out, tops, n);
-    hipLaunchKernelGGL((k_scan_u32_tops<0>), dim3(1), dim3(256), 0, s, tops, nt);
-    hipLaunchKernelGGL((k_scan_u32_add<0>), dim3((n + 255) / 256), dim3(256), 0, s, out, (const u32*)tops, n);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_scan_u32_tile<0>), dim3(nt), dim3(256), 0, s, in, out, tops, n);
+    HK_LAUNCH((k_scan_u32_tops<0>), dim3(1), dim3(256), 0, s, tops, nt);
+    HK_LAUNCH((k_scan_u32_add<0>), dim3((n + 255) / 256), dim3(256), 0, s, out, (const u32*)tops, n);
     return HK_OK;
 }
 

@@ -192,16 +192,15 @@ hk_status Ops<C>::sha_tree(hk_ctx* ctx, const void* leaves, uint32_t n_sub, uint
     const u32 nn = (u32)n;
     const bool fused_leaves = nl + 1 <= ST_WG_NODES;
     if (!fused_leaves)
-        hipLaunchKernelGGL((k_sha_tree_level<0>), dim3((u32)((nl + 1 + ST_LEVEL_LANES - 1) / ST_LEVEL_LANES)), dim3(ST_LEVEL_LANES), 0, s,
-                           lp, dig, nn, ns, 0u);
+        HK_LAUNCH((k_sha_tree_level<0>), dim3((u32)((nl + 1 + ST_LEVEL_LANES - 1) / ST_LEVEL_LANES)), dim3(ST_LEVEL_LANES), 0, s,
+                  lp, dig, nn, ns, 0u);
     u32 w = (u32)(nl / 2);
     for (; w > ST_WG_NODES; w >>= 1)
-        hipLaunchKernelGGL((k_sha_tree_level<0>), dim3(w / ST_LEVEL_LANES), dim3(ST_LEVEL_LANES), 0, s, lp, dig, nn, ns, w);
-    hipLaunchKernelGGL((k_sha_tree_tail<0>), dim3(1), dim3(ST_WG_NODES), 0, s, lp, dig, nn, ns, fused_leaves ? 1u : 0u, w);
+        HK_LAUNCH((k_sha_tree_level<0>), dim3(w / ST_LEVEL_LANES), dim3(ST_LEVEL_LANES), 0, s, lp, dig, nn, ns, w);
+    HK_LAUNCH((k_sha_tree_tail<0>), dim3(1), dim3(ST_WG_NODES), 0, s, lp, dig, nn, ns, fused_leaves ? 1u : 0u, w);
     const u32 total = (u32)(n * np);                               // < 2^28
-    hipLaunchKernelGGL((k_sha_tree_trace<Fr>), dim3((total + 255) / 256), dim3(256), 0, s, (const uint4*)dig, nn, (u32)np, total, time_e,
-                       root);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_sha_tree_trace<Fr>), dim3((total + 255) / 256), dim3(256), 0, s, (const uint4*)dig, nn, (u32)np, total, time_e,
+              root);
     struct { void* dst; const void* src; size_t bytes; } outs[] = {
         {o->digests_out, dig, dig_bytes}, {o->time_entries_mont_out, time_e, time_bytes}, {o->sha_root_mont_out, root, sizeof(Fr)}};
     for (auto& x : outs)
@@ -241,9 +240,8 @@ hk_status Ops<C>::sha_tree_inputs(hk_ctx* ctx, const void* leaves, const void* d
     HK_HIP(hipMemcpyAsync(sub_d, sub_index, 4 * batch, hipMemcpyHostToDevice, s));
     const u32 total = (u32)(batch * n_inputs);
     const unsigned char* p = (const unsigned char*)in.p;
-    hipLaunchKernelGGL((k_sha_tree_inputs<0>), dim3((total + 255) / 256), dim3(256), 0, s, of_leaves ? p : nullptr, of_leaves ? nullptr : p,
-                       (u32)n, n_inputs, (const u32*)sub_d, total, out_d);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_sha_tree_inputs<0>), dim3((total + 255) / 256), dim3(256), 0, s, of_leaves ? p : nullptr, of_leaves ? nullptr : p,
+              (u32)n, n_inputs, (const u32*)sub_d, total, out_d);
     HK_HIP(hipMemcpyAsync(inputs_out, out_d, out_bytes, is_device_ptr(inputs_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
     return L->settle();
 }

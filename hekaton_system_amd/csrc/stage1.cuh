@@ -125,11 +125,10 @@ hk_status Ops<C>::stage1_witness(hk_ctx* ctx, const hk_stage1_desc* d, const uin
     HK_HIP(hipMemcpyAsync(rows_d, rows.data(), 4 * rows.size(), hipMemcpyHostToDevice, s));
     const Fr *tp = (const Fr*)in[0].p, *ap = (const Fr*)in[1].p;
     const u32 nb = (u32)batch, lanes = (u32)((7 + 5 * K) * batch);
-    hipLaunchKernelGGL((k_s1_values<Fr>), dim3((lanes + 255) / 256), dim3(256), 0, s, tp, ap, (const u32*)rows_d, nb, (u32)K, ch,
-                       (const Fr*)in[3].p, (const Fr*)in[6].p, n_v, (size_t)d->inst_col0, (size_t)d->col0, (Fr*)z_out);
-    poseidon_membership<Fr, 4>(s, in[2].p, d->leaf_hash, d->node_hash, in[4].p, in[5].p, rows_d, rows_d, 2, depth, batch, n_v,
-                               (size_t)d->pos_col0, z_out);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_s1_values<Fr>), dim3((lanes + 255) / 256), dim3(256), 0, s, tp, ap, (const u32*)rows_d, nb, (u32)K, ch,
+              (const Fr*)in[3].p, (const Fr*)in[6].p, n_v, (size_t)d->inst_col0, (size_t)d->col0, (Fr*)z_out);
+    HK_TRY((poseidon_membership<Fr, 4>(s, in[2].p, d->leaf_hash, d->node_hash, in[4].p, in[5].p, rows_d, rows_d, 2, depth, batch, n_v,
+                                       (size_t)d->pos_col0, z_out)));
     return L->settle();
 }
 

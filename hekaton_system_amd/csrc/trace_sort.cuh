@@ -265,10 +265,9 @@ hk_status Ops<C>::trace_sort(hk_ctx* ctx, uint32_t entry_fields, const void* tim
     if (n_tiles == 1) {
         u32* perm_s = idx[1] + n;
         if (K == 2)
-            hipLaunchKernelGGL((k_ts_small<Fr, 2>), dim3(1), dim3(256), 0, s, tp, nn, keys[0], keys[1], idx[0], idx[1], flags, sorted, perm_s);
+            HK_LAUNCH((k_ts_small<Fr, 2>), dim3(1), dim3(256), 0, s, tp, nn, keys[0], keys[1], idx[0], idx[1], flags, sorted, perm_s);
         else
-            hipLaunchKernelGGL((k_ts_small<Fr, 4>), dim3(1), dim3(256), 0, s, tp, nn, keys[0], keys[1], idx[0], idx[1], flags, sorted, perm_s);
-        HK_HIP(hipGetLastError());
+            HK_LAUNCH((k_ts_small<Fr, 4>), dim3(1), dim3(256), 0, s, tp, nn, keys[0], keys[1], idx[0], idx[1], flags, sorted, perm_s);
         HK_HIP(hipMemcpyAsync(fl, flags, sizeof(fl), hipMemcpyDeviceToHost, s));
         HK_HIP(hipStreamSynchronize(s));
         if (fl[0]) { HK_TRY(L->settle()); return HK_ERR_ARG; }
@@ -276,10 +275,9 @@ hk_status Ops<C>::trace_sort(hk_ctx* ctx, uint32_t entry_fields, const void* tim
     } else {
         HK_HIP(hipMemcpyAsync(flags, fl, sizeof(fl), hipMemcpyHostToDevice, s));
         if (K == 2)
-            hipLaunchKernelGGL((k_ts_keys<Fr, 2>), dim3((nn + 255) / 256), dim3(256), 0, s, tp, nn, keys[0], idx[0], flags);
+            HK_LAUNCH((k_ts_keys<Fr, 2>), dim3((nn + 255) / 256), dim3(256), 0, s, tp, nn, keys[0], idx[0], flags);
         else
-            hipLaunchKernelGGL((k_ts_keys<Fr, 4>), dim3((nn + 255) / 256), dim3(256), 0, s, tp, nn, keys[0], idx[0], flags);
-        HK_HIP(hipGetLastError());
+            HK_LAUNCH((k_ts_keys<Fr, 4>), dim3((nn + 255) / 256), dim3(256), 0, s, tp, nn, keys[0], idx[0], flags);
         HK_HIP(hipMemcpyAsync(fl, flags, sizeof(fl), hipMemcpyDeviceToHost, s));
         HK_HIP(hipStreamSynchronize(s));                           // the one read-back: the error bit and the varying bits
         if (fl[0]) { HK_TRY(L->settle()); return HK_ERR_ARG; }
@@ -288,22 +286,21 @@ hk_status Ops<C>::trace_sort(hk_ctx* ctx, uint32_t entry_fields, const void* tim
             const u32 word = p >> 2, shift = (p & 3u) * 8;
             if ((((fl[1 + word] & ~fl[4 + word]) >> shift) & 255u) == 0) continue;        // this digit is the same in every key
             const u32 *kin = keys[cur], *iin = idx[cur];
-            hipLaunchKernelGGL((k_ts_hist<0>), dim3(n_tiles), dim3(256), 0, s, kin + (size_t)word * n, nn, shift, n_tiles, hist);
+            HK_LAUNCH((k_ts_hist<0>), dim3(n_tiles), dim3(256), 0, s, kin + (size_t)word * n, nn, shift, n_tiles, hist);
             HK_TRY(scan_u32(s, hist, gbase, tops, n_hist));
             if (W == 2)
-                hipLaunchKernelGGL((k_ts_scatter<2>), dim3(n_tiles), dim3(256), 0, s, kin, iin, keys[cur ^ 1], idx[cur ^ 1], nn, word,
-                                   shift, (const u32*)gbase, n_tiles);
+                HK_LAUNCH((k_ts_scatter<2>), dim3(n_tiles), dim3(256), 0, s, kin, iin, keys[cur ^ 1], idx[cur ^ 1], nn, word,
+                          shift, (const u32*)gbase, n_tiles);
             else
-                hipLaunchKernelGGL((k_ts_scatter<3>), dim3(n_tiles), dim3(256), 0, s, kin, iin, keys[cur ^ 1], idx[cur ^ 1], nn, word,
-                                   shift, (const u32*)gbase, n_tiles);
+                HK_LAUNCH((k_ts_scatter<3>), dim3(n_tiles), dim3(256), 0, s, kin, iin, keys[cur ^ 1], idx[cur ^ 1], nn, word,
+                          shift, (const u32*)gbase, n_tiles);
             cur ^= 1;
         }
         const u32 blocks = (u32)((n * 2 * K + 255) / 256);
         if (K == 2)
-            hipLaunchKernelGGL((k_ts_gather<2>), dim3(blocks), dim3(256), 0, s, (const uint4*)tp, (const u32*)idx[cur], nn, (uint4*)sorted);
+            HK_LAUNCH((k_ts_gather<2>), dim3(blocks), dim3(256), 0, s, (const uint4*)tp, (const u32*)idx[cur], nn, (uint4*)sorted);
         else
-            hipLaunchKernelGGL((k_ts_gather<4>), dim3(blocks), dim3(256), 0, s, (const uint4*)tp, (const u32*)idx[cur], nn, (uint4*)sorted);
-        HK_HIP(hipGetLastError());
+            HK_LAUNCH((k_ts_gather<4>), dim3(blocks), dim3(256), 0, s, (const uint4*)tp, (const u32*)idx[cur], nn, (uint4*)sorted);
         perm = idx[cur];
     }
     HK_HIP(hipMemcpyAsync(addr_out, sorted, bytes, is_device_ptr(addr_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
@@ -338,9 +335,8 @@ hk_status Ops<C>::stage0_witness(hk_ctx* ctx, const uint32_t* offsets, uint32_t 
     const void *te = in[0].p, *ae = in[1].p;
     HK_HIP(hipMemcpyAsync(offs_d, offs.data(), 4 * batch, hipMemcpyHostToDevice, s));
     const u64 total = (u64)batch * 8 * K;                  // < 2^31
-    hipLaunchKernelGGL((k_s0_rows<0>), dim3((u32)((total + 255) / 256)), dim3(256), 0, s, (const uint4*)te, (const uint4*)ae,
-                       (const u32*)offs_d, total, (u32)K, (uint4*)w_out);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_s0_rows<0>), dim3((u32)((total + 255) / 256)), dim3(256), 0, s, (const uint4*)te, (const uint4*)ae,
+              (const u32*)offs_d, total, (u32)K, (uint4*)w_out);
     return L->settle();
 }
 

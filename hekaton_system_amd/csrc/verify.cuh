@@ -235,27 +235,14 @@ struct VkImpl {
 };
 
 template <class P>
-size_t VerifyRun<P>::max_private_bytes() {
-    typedef typename ScalarOfQ<P>::type Fr;
-    const void* ks[] = {(const void*)k_points_check<Fp<P>>, (const void*)k_points_check<Fp2<P>>, (const void*)k_verify_ic<P, Fr>,
-                        (const void*)k_verify_tree_lines<P>, (const void*)k_verify_coeffs<Fr>, (const void*)k_verify_rand_zero<Fr>,
-                        (const void*)k_verify_verdict<P>};
-    size_t m = 0;
-    for (const void* k : ks) { size_t b = hk_private_bytes_of(k); if (b > m) m = b; }
-    return m;
-}
-
-template <class P>
 static hk_status verify_lines(hipStream_t s, const Affine<Fp2<P>>* g2, u32 n, Line6<P>* lines) {
     PairLoop loop = PairLoopOf<P>::get();
     u32 S = PairRun<P>::steps();
     if ((size_t)n * 4 <= SPLIT_MAX_LANES)
-        hipLaunchKernelGGL((k_pair_lines<Fp2Q<P>>), dim3((4 * n + 63) / 64, 1), dim3(64), 0, s, (const Affine<Fp2Q<P>>*)g2, n, 1u,
-                           loop, S, lines);
+        HK_LAUNCH((k_pair_lines<Fp2Q<P>>), dim3((4 * n + 63) / 64, 1), dim3(64), 0, s, (const Affine<Fp2Q<P>>*)g2, n, 1u,
+                  loop, S, lines);
     else
-        hipLaunchKernelGGL((k_pair_lines<Fp2<P>>), dim3((n + 63) / 64, 1), dim3(64), 0, s, g2, n, 1u, loop, S, lines);
-    HK_DBG(s, "k_pair_lines (verify)");
-    HK_HIP(hipGetLastError());
+        HK_LAUNCH((k_pair_lines<Fp2<P>>), dim3((n + 63) / 64, 1), dim3(64), 0, s, g2, n, 1u, loop, S, lines);
     return HK_OK;
 }
 
@@ -271,8 +258,7 @@ static hk_status verify_products(hipStream_t s, const VerifyMembers<P>& vm, u32 
     u32 g = (M + 15) / 16;
     for (u32 r0 = 0; r0 < rows; r0 += 65535u) {
         u32 nr = rows - r0 < 65535u ? rows - r0 : 65535u;
-        hipLaunchKernelGGL((k_verify_tree_lines<P>), dim3(g, nr), dim3(64), lds_tree, s, vm, S, 16u, r0, pp0);
-        HK_DBG(s, "k_verify_tree_lines");
+        HK_LAUNCH((k_verify_tree_lines<P>), dim3(g, nr), dim3(64), lds_tree, s, vm, S, 16u, r0, pp0);
     }
     Fp12<P>* pp[2] = {pp0, pp1};
     int cur = 0;
@@ -280,16 +266,13 @@ static hk_status verify_products(hipStream_t s, const VerifyMembers<P>& vm, u32 
         u32 groups = (g + 15) / 16;
         for (u32 r0 = 0; r0 < rows; r0 += 65535u) {
             u32 nr = rows - r0 < 65535u ? rows - r0 : 65535u;
-            hipLaunchKernelGGL((k_pair_tree<P>), dim3(groups, nr), dim3(64), lds_tree, s, (const Fp12<P>*)pp[cur] + (size_t)r0 * g, g,
-                               16u, pp[cur ^ 1] + (size_t)r0 * groups);
-            HK_DBG(s, "k_pair_tree (verify)");
+            HK_LAUNCH((k_pair_tree<P>), dim3(groups, nr), dim3(64), lds_tree, s, (const Fp12<P>*)pp[cur] + (size_t)r0 * g, g,
+                      16u, pp[cur ^ 1] + (size_t)r0 * groups);
         }
         cur ^= 1;
         g = groups;
     }
-    hipLaunchKernelGGL((k_pair_horner<P>), dim3(count), dim3(64), lds_fin, s, (const Fp12<P>*)pp[cur], st, out);
-    HK_DBG(s, "k_pair_horner (verify)");
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_pair_horner<P>), dim3(count), dim3(64), lds_fin, s, (const Fp12<P>*)pp[cur], st, out);
     return HK_OK;
 }
 
@@ -380,9 +363,8 @@ hk_status VerifyRun<P>::points_check(hk_ctx* ctx, int group, const void* pts, si
         typedef decltype(ftag) F;
         HK_TRY(L->carve([&](Carve& c) { stage_carve(c, io, 2); }));
         HK_TRY(stage_upload(L, io, 1));
-        hipLaunchKernelGGL((k_points_check<F>), dim3((u32)((n + 63) / 64)), dim3(64), 0, L->stream, (const Affine<F>*)io[0].p, (u32)n,
-                           0u, (unsigned char*)io[1].p);
-        HK_HIP(hipGetLastError());
+        HK_LAUNCH((k_points_check<F>), dim3((u32)((n + 63) / 64)), dim3(64), 0, L->stream, (const Affine<F>*)io[0].p, (u32)n,
+                  0u, (unsigned char*)io[1].p);
         HK_TRY(stage_download(L, io + 1, 1));
         return L->settle();
     };
@@ -460,22 +442,19 @@ hk_status VerifyRun<P>::verify_batch(hk_ctx* ctx, const hk_vk* h, const void* a,
         HK_HIP(hipMemsetAsync(flag, 0, m + 1, s));
         bool any_bad = false;
         if (check) {
-            hipLaunchKernelGGL((k_points_check<Fq>), dim3((m + 63) / 64), dim3(64), 0, s, (const Affine<Fq>*)ad, m, 1u, flag);
-            hipLaunchKernelGGL((k_points_check<Fq2>), dim3((m + 63) / 64), dim3(64), 0, s, (const Affine<Fq2>*)bd, m, 1u, flag);
-            hipLaunchKernelGGL((k_points_check<Fq>), dim3((m + 63) / 64), dim3(64), 0, s, (const Affine<Fq>*)cd, m, 1u, flag);
+            HK_LAUNCH((k_points_check<Fq>), dim3((m + 63) / 64), dim3(64), 0, s, (const Affine<Fq>*)ad, m, 1u, flag);
+            HK_LAUNCH((k_points_check<Fq2>), dim3((m + 63) / 64), dim3(64), 0, s, (const Affine<Fq2>*)bd, m, 1u, flag);
+            HK_LAUNCH((k_points_check<Fq>), dim3((m + 63) / 64), dim3(64), 0, s, (const Affine<Fq>*)cd, m, 1u, flag);
             if (nd > 1)
-                hipLaunchKernelGGL((k_points_check<Fq>), dim3((u32)(((size_t)m * (nd - 1) + 63) / 64)), dim3(64), 0, s,
-                                   (const Affine<Fq>*)dd, m * (nd - 1), nd - 1, flag);
-            HK_DBG(s, "k_points_check");
-            HK_HIP(hipGetLastError());
+                HK_LAUNCH((k_points_check<Fq>), dim3((u32)(((size_t)m * (nd - 1) + 63) / 64)), dim3(64), 0, s,
+                          (const Affine<Fq>*)dd, m * (nd - 1), nd - 1, flag);
         }
         HK_TRY(verify_lines<P>(s, (const Affine<Fq2>*)bd, m, lines));
         bool batch_ok = false;
         if (rand) {
             // one randomised equation for the chunk; a proof with a bad point, or a zero r_i, sends the chunk to the
             // per-proof path
-            hipLaunchKernelGGL((k_verify_rand_zero<Fr>), dim3((m + 63) / 64), dim3(64), 0, s, (const Fr*)rd, m, flag + m);
-            HK_HIP(hipGetLastError());
+            HK_LAUNCH((k_verify_rand_zero<Fr>), dim3((m + 63) / 64), dim3(64), 0, s, (const Fr*)rd, m, flag + m);
             std::vector<unsigned char> fh(m + 1);
             HK_HIP(hipMemcpyAsync(fh.data(), flag, m + 1, hipMemcpyDeviceToHost, s));
             HK_HIP(hipStreamSynchronize(s));
@@ -483,10 +462,9 @@ hk_status VerifyRun<P>::verify_batch(hk_ctx* ctx, const hk_vk* h, const void* a,
         }
         if (rand && !any_bad) {
             // sum r_i, sum r_i x_i -> sum r_i IC_i = (sum r_i) abc[0] + sum_k (sum_i r_i x_ik) abc[k + 1]
-            hipLaunchKernelGGL((k_verify_coeffs<Fr>), dim3((nk + 1 + 63) / 64), dim3(64), 0, s, (const Fr*)rd, (const Fr*)xd, m, nk, coef);
-            hipLaunchKernelGGL((k_verify_ic<P, Fr>), dim3(1), dim3(64), 0, s, (const Affine<Fq>*)v->abc, nk + 1, (const Fr*)coef,
-                               (const Affine<Fq>*)nullptr, 1u, bst, 1u);
-            HK_HIP(hipGetLastError());
+            HK_LAUNCH((k_verify_coeffs<Fr>), dim3((nk + 1 + 63) / 64), dim3(64), 0, s, (const Fr*)rd, (const Fr*)xd, m, nk, coef);
+            HK_LAUNCH((k_verify_ic<P, Fr>), dim3(1), dim3(64), 0, s, (const Affine<Fq>*)v->abc, nk + 1, (const Fr*)coef,
+                      (const Affine<Fq>*)nullptr, 1u, bst, 1u);
             // sum r_i D_ij and sum r_i C_i: small MSMs over the proofs' columns
             for (u32 j = 0; j + 1 < nd; j++) {
                 HK_HIP(hipMemcpy2DAsync(col, g1b, (const char*)dd + j * g1b, (nd - 1) * g1b, g1b, m, hipMemcpyDeviceToDevice, s));
@@ -499,9 +477,8 @@ hk_status VerifyRun<P>::verify_batch(hk_ctx* ctx, const hk_vk* h, const void* a,
             VerifyMembers<P> vm = {lines, ra, m, m, v->lines, bst, nst};
             HK_TRY(verify_products<P>(s, vm, 1, qa, qb, one));
             HK_TRY(PairRun<P>::gt_pow(s, v->alpha_beta, coef, 1, want, true));      // e(alpha, beta)^(sum r_i)
-            hipLaunchKernelGGL((k_verify_verdict<P>), dim3(1), dim3(64), 0, s, (const GT*)one, (const GT*)want, 0u, 1u,
-                               (const unsigned char*)nullptr, eq);
-            HK_HIP(hipGetLastError());
+            HK_LAUNCH((k_verify_verdict<P>), dim3(1), dim3(64), 0, s, (const GT*)one, (const GT*)want, 0u, 1u,
+                      (const unsigned char*)nullptr, eq);
             unsigned char eh = 0;
             HK_HIP(hipMemcpyAsync(&eh, eq, 1, hipMemcpyDeviceToHost, s));
             HK_HIP(hipStreamSynchronize(s));
@@ -510,17 +487,15 @@ hk_status VerifyRun<P>::verify_batch(hk_ctx* ctx, const hk_vk* h, const void* a,
         }
         if (!batch_ok) {
             // per-proof: IC_p, then [IC_p, D_p0 .., C_p] side by side against the prepared lines
-            hipLaunchKernelGGL((k_verify_ic<P, Fr>), dim3((m + 63) / 64), dim3(64), 0, s, (const Affine<Fq>*)v->abc + 1, nk, (const Fr*)xd,
-                               (const Affine<Fq>*)v->abc, m, gst, nst);
-            HK_HIP(hipGetLastError());
+            HK_LAUNCH((k_verify_ic<P, Fr>), dim3((m + 63) / 64), dim3(64), 0, s, (const Affine<Fq>*)v->abc + 1, nk, (const Fr*)xd,
+                      (const Affine<Fq>*)v->abc, m, gst, nst);
             if (nd > 1)
                 HK_HIP(hipMemcpy2DAsync(gst + 1, nst * g1b, dd, (nd - 1) * g1b, (nd - 1) * g1b, m, hipMemcpyDeviceToDevice, s));
             HK_HIP(hipMemcpy2DAsync(gst + nd, nst * g1b, cd, g1b, g1b, m, hipMemcpyDeviceToDevice, s));
             VerifyMembers<P> vm = {lines, (const Affine<Fq>*)ad, m, 1, v->lines, gst, nst};
             HK_TRY(verify_products<P>(s, vm, m, pp0, pp1, res));
-            hipLaunchKernelGGL((k_verify_verdict<P>), dim3((m + 63) / 64), dim3(64), 0, s, (const GT*)res, (const GT*)v->alpha_beta, 0u, m,
-                               check ? (const unsigned char*)flag : nullptr, vd);
-            HK_HIP(hipGetLastError());
+            HK_LAUNCH((k_verify_verdict<P>), dim3((m + 63) / 64), dim3(64), 0, s, (const GT*)res, (const GT*)v->alpha_beta, 0u, m,
+                      check ? (const unsigned char*)flag : nullptr, vd);
         }
         HK_TRY(stage_download(L, io + 6, 1));
         HK_TRY(L->settle());

@@ -361,13 +361,12 @@ hk_status Ops<C>::vkd_trace(hk_ctx* ctx, const hk_vkd_desc* d, void* values_out,
     HK_HIP(hipMemcpyAsync(vals_d, d->roots_mont, 2 * fr, hipMemcpyHostToDevice, s));
     const PoseidonDesc a = poseidon_desc(d->leaf_hash), b = poseidon_desc(d->node_hash);
     const u32 nu = (u32)U, seg = (u32)(depth / S);
-    hipLaunchKernelGGL((k_vkd_hash<Fr>), dim3((1 + 3 * nu + 63) / 64), dim3(256), 0, s, (const Fr*)consts, a,
-                       (const unsigned char*)leaves, (const unsigned char*)zeros_d, (const u32*)kinds_d, nu, (u32)S, seg, vals_d, raw_d);
-    hipLaunchKernelGGL((k_vkd_chain<Fr>), dim3((2 * nu + 63) / 64), dim3(256), 0, s, (const Fr*)consts, b, (const Fr*)sibs,
-                       (const u32*)kinds_d, (const u32*)raw_d, nu, (u32)depth, (u32)S, seg, vals_d);
-    hipLaunchKernelGGL((k_vkd_trace<Fr>), dim3((u32)((n_fr + 255) / 256)), dim3(256), 0, s, (const Fr*)vals_d, (const u32*)addr_d,
-                       (const u32*)src_d, (u32)n_fr, out_d);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_vkd_hash<Fr>), dim3((1 + 3 * nu + 63) / 64), dim3(256), 0, s, (const Fr*)consts, a,
+              (const unsigned char*)leaves, (const unsigned char*)zeros_d, (const u32*)kinds_d, nu, (u32)S, seg, vals_d, raw_d);
+    HK_LAUNCH((k_vkd_chain<Fr>), dim3((2 * nu + 63) / 64), dim3(256), 0, s, (const Fr*)consts, b, (const Fr*)sibs,
+              (const u32*)kinds_d, (const u32*)raw_d, nu, (u32)depth, (u32)S, seg, vals_d);
+    HK_LAUNCH((k_vkd_trace<Fr>), dim3((u32)((n_fr + 255) / 256)), dim3(256), 0, s, (const Fr*)vals_d, (const u32*)addr_d,
+              (const u32*)src_d, (u32)n_fr, out_d);
     HK_TRY(stage_download(L, out, 2));
     return L->settle();
 }
@@ -440,19 +439,18 @@ hk_status Ops<C>::vkd_witness(hk_ctx* ctx, const hk_vkd_desc* d, const uint32_t*
     HK_HIP(hipMemcpyAsync(rows_d, rows.data(), sizeof(VkdRow) * batch, hipMemcpyHostToDevice, s));
     const PoseidonDesc a = poseidon_desc(d->leaf_hash), bd = poseidon_desc(d->node_hash);
     const u32 nb = (u32)batch;
-    hipLaunchKernelGGL((k_vkd_one<Fr>), dim3((nb + 255) / 256), dim3(256), 0, s, nb, n_v, (Fr*)z_out);
+    HK_LAUNCH((k_vkd_one<Fr>), dim3((nb + 255) / 256), dim3(256), 0, s, nb, n_v, (Fr*)z_out);
     if (has_hash)
         for (size_t b0 = 0; b0 < batch; b0 += VKD_GRID_ROWS) {
             const u32 n = (u32)std::min(batch - b0, (size_t)VKD_GRID_ROWS);
-            hipLaunchKernelGGL((k_vkd_leaf_bits<Fr>), dim3((8 * VKD_LEAF_BYTES + 255) / 256, n), dim3(256), 0, s,
-                               (const unsigned char*)p[0], (const VkdRow*)rows_d + b0, n_v, (size_t)cols->hash_col0,
-                               (Fr*)z_out + b0 * n_v);
+            HK_LAUNCH((k_vkd_leaf_bits<Fr>), dim3((8 * VKD_LEAF_BYTES + 255) / 256, n), dim3(256), 0, s,
+                      (const unsigned char*)p[0], (const VkdRow*)rows_d + b0, n_v, (size_t)cols->hash_col0,
+                      (Fr*)z_out + b0 * n_v);
         }
     if (n_ch)                                              // padding, write pp, equality: no body columns
-        hipLaunchKernelGGL((k_vkd_body<Fr>), dim3((nb + 63) / 64, n_ch), dim3(256), 0, s, (const Fr*)p[2], a, bd,
-                           (const unsigned char*)p[0], (const Fr*)p[1], (const Fr*)p[3], (const VkdRow*)rows_d, ch, (u32)Lv, nb,
-                           n_v, (Fr*)z_out);
-    HK_HIP(hipGetLastError());
+        HK_LAUNCH((k_vkd_body<Fr>), dim3((nb + 63) / 64, n_ch), dim3(256), 0, s, (const Fr*)p[2], a, bd,
+                  (const unsigned char*)p[0], (const Fr*)p[1], (const Fr*)p[3], (const VkdRow*)rows_d, ch, (u32)Lv, nb,
+                  n_v, (Fr*)z_out);
     return L->settle();
 }
 

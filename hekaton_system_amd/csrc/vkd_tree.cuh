@@ -284,41 +284,40 @@ hk_status Ops<C>::vkd_tree(hk_ctx* ctx, const hk_vkd_tree_desc* d, void* sibling
     unsigned char* status_d = (unsigned char*)out[2].p;
     const PoseidonDesc a = poseidon_desc(d->leaf_hash), b = poseidon_desc(d->node_hash);
     const u32 passes = nd / 8;
-    hipLaunchKernelGGL((k_vt_empty<Fr>), dim3(1), dim3(64), 0, s, consts, a, b, (const unsigned char*)zeros_d, nd, empty);
+    HK_LAUNCH((k_vt_empty<Fr>), dim3(1), dim3(64), 0, s, consts, a, b, (const unsigned char*)zeros_d, nd, empty);
     int ko = 0, lv = 0;                                     // which of key / ord, and of ord / rs / re / node, is current
     if (small) {
-        hipLaunchKernelGGL((k_vt_small<Fr>), dim3(1), dim3(256), 0, s, consts, a, b, leaves0, leaves, (const u32*)kinds_d, nm, ne, nd,
-                           (const Fr*)empty, idx, key[0], key[1], ord[0], ord[1], rs[0], rs[1], re[0], re[1], node[0], node[1], sib_d,
-                           status_d);
+        HK_LAUNCH((k_vt_small<Fr>), dim3(1), dim3(256), 0, s, consts, a, b, leaves0, leaves, (const u32*)kinds_d, nm, ne, nd,
+                  (const Fr*)empty, idx, key[0], key[1], ord[0], ord[1], rs[0], rs[1], re[0], re[1], node[0], node[1], sib_d,
+                  status_d);
         lv = (int)(nd & 1u);                               // node: one swap per level (ord is not read again)
     } else {
-        hipLaunchKernelGGL((k_vt_events<Fr>), dim3((ne + 63) / 64), dim3(256), 0, s, consts, a, leaves0, leaves, nm, ne, nd, idx,
-                           key[0], ord[0], node[0]);
+        HK_LAUNCH((k_vt_events<Fr>), dim3((ne + 63) / 64), dim3(256), 0, s, consts, a, leaves0, leaves, nm, ne, nd, idx,
+                  key[0], ord[0], node[0]);
         for (u32 p = 0; p < passes; p++) {
             const u32 word = p >> 2, shift = (p & 3u) * 8;
             const u32* gb = nullptr;
             if (n_tiles > 1) {
-                hipLaunchKernelGGL((k_ts_hist<0>), dim3(n_tiles), dim3(256), 0, s, (const u32*)key[ko] + (size_t)word * E, ne, shift,
-                                   n_tiles, hist);
+                HK_LAUNCH((k_ts_hist<0>), dim3(n_tiles), dim3(256), 0, s, (const u32*)key[ko] + (size_t)word * E, ne, shift,
+                          n_tiles, hist);
                 HK_TRY(scan_u32(s, hist, gbase, tops, n_hist));
                 gb = gbase;
             }
-            hipLaunchKernelGGL((k_ts_scatter<(int)VT_KEY_WORDS>), dim3(n_tiles), dim3(256), 0, s, (const u32*)key[ko],
-                               (const u32*)ord[ko], key[ko ^ 1], ord[ko ^ 1], ne, word, shift, gb, n_tiles);
+            HK_LAUNCH((k_ts_scatter<(int)VT_KEY_WORDS>), dim3(n_tiles), dim3(256), 0, s, (const u32*)key[ko],
+                      (const u32*)ord[ko], key[ko ^ 1], ord[ko ^ 1], ne, word, shift, gb, n_tiles);
             ko ^= 1;
         }
         // the levels' ord starts where the sort left it; rs / re / node start at 0
-        hipLaunchKernelGGL((k_vt_runs<0>), dim3((ne + 255) / 256), dim3(256), 0, s, (const u32*)key[ko], (const u32*)ord[ko], ne, nm,
-                           leaves0, leaves, (const u32*)kinds_d, rs[0], re[0], status_d);
+        HK_LAUNCH((k_vt_runs<0>), dim3((ne + 255) / 256), dim3(256), 0, s, (const u32*)key[ko], (const u32*)ord[ko], ne, nm,
+                  leaves0, leaves, (const u32*)kinds_d, rs[0], re[0], status_d);
         for (u32 l = 0; l < nd; l++) {
-            hipLaunchKernelGGL((k_vt_level<Fr>), dim3((ne + 63) / 64), dim3(256), 0, s, consts, b, (const u32*)idx, ne, nm, nd, l,
-                               (const u32*)ord[ko], (const u32*)rs[lv], (const u32*)re[lv], (const Fr*)node[lv], (const Fr*)empty,
-                               ord[ko ^ 1], rs[lv ^ 1], re[lv ^ 1], node[lv ^ 1], sib_d);
+            HK_LAUNCH((k_vt_level<Fr>), dim3((ne + 63) / 64), dim3(256), 0, s, consts, b, (const u32*)idx, ne, nm, nd, l,
+                      (const u32*)ord[ko], (const u32*)rs[lv], (const u32*)re[lv], (const Fr*)node[lv], (const Fr*)empty,
+                      ord[ko ^ 1], rs[lv ^ 1], re[lv ^ 1], node[lv ^ 1], sib_d);
             ko ^= 1;
             lv ^= 1;
         }
     }
-    HK_HIP(hipGetLastError());
     Fr* roots_d = (Fr*)out[1].p;
     HK_HIP(hipMemcpyAsync(roots_d, M ? node[lv] + (M - 1) : empty + depth, fr, hipMemcpyDeviceToDevice, s));
     HK_HIP(hipMemcpyAsync(roots_d + 1, node[lv] + (E - 1), fr, hipMemcpyDeviceToDevice, s));

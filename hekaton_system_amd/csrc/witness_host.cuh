@@ -37,12 +37,11 @@ hk_status Ops<C>::assignment_from_bits(hk_ctx* ctx, const void* bits, size_t n_v
     if (!L) return HK_ERR_DEVICE;
     HK_TRY(L->carve([&](Carve& c) { stage_carve(c, in, 3); }));
     HK_TRY(stage_upload(L, in, 3));
-    hipLaunchKernelGGL((k_expand_bits<Fr>), dim3((u32)((n_v + 255) / 256)), dim3(256), 0, L->stream, (const unsigned char*)in[0].p,
-                       n_v, (Fr*)z_out);
+    HK_LAUNCH((k_expand_bits<Fr>), dim3((u32)((n_v + 255) / 256)), dim3(256), 0, L->stream, (const unsigned char*)in[0].p,
+              n_v, (Fr*)z_out);
     if (n_full)
-        hipLaunchKernelGGL((k_scatter_full<Fr>), dim3((u32)((n_full + 63) / 64)), dim3(64), 0, L->stream, (const u32*)in[1].p,
-                           (const Fr*)in[2].p, (u32)n_full, n_v, (Fr*)z_out);
-    HK_HIP(hipGetLastError());
+        HK_LAUNCH((k_scatter_full<Fr>), dim3((u32)((n_full + 63) / 64)), dim3(64), 0, L->stream, (const u32*)in[1].p,
+                  (const Fr*)in[2].p, (u32)n_full, n_v, (Fr*)z_out);
     return L->settle();
 }
 
@@ -132,14 +131,13 @@ hk_status Ops<C>::wprog_run(hk_ctx* ctx, const hk_wprog* h, const uint32_t* inpu
     hipStream_t s = L->stream;
     const void *in_d = in[0].p, *cd = in[1].p, *vd = in[2].p;
     HK_TRY(stage_upload(L, in, 3));
-    hipLaunchKernelGGL((k_word_program<0>), dim3((u32)((batch + 63) / 64)), dim3(64), 0, s, w->ops, w->n_ops, w->refs,
-                       (const u32*)in_d, w->n_inputs, (u32)batch, values);
-    hipLaunchKernelGGL((k_witness_expand<Fr>), dim3((u32)((w->n_v + 255) / 256), (u32)batch), dim3(256), 0, s, w->map, w->n_v,
-                       (const u32*)values, (u32)batch, (Fr*)z_out);
+    HK_LAUNCH((k_word_program<0>), dim3((u32)((batch + 63) / 64)), dim3(64), 0, s, w->ops, w->n_ops, w->refs,
+              (const u32*)in_d, w->n_inputs, (u32)batch, values);
+    HK_LAUNCH((k_witness_expand<Fr>), dim3((u32)((w->n_v + 255) / 256), (u32)batch), dim3(256), 0, s, w->map, w->n_v,
+              (const u32*)values, (u32)batch, (Fr*)z_out);
     if (n_full)
-        hipLaunchKernelGGL((k_scatter_full_batch<Fr>), dim3((u32)((n_full + 63) / 64), (u32)batch), dim3(64), 0, s,
-                           (const u32*)cd, (const Fr*)vd, (u32)n_full, w->n_v, (Fr*)z_out);
-    HK_HIP(hipGetLastError());
+        HK_LAUNCH((k_scatter_full_batch<Fr>), dim3((u32)((n_full + 63) / 64), (u32)batch), dim3(64), 0, s,
+                  (const u32*)cd, (const Fr*)vd, (u32)n_full, w->n_v, (Fr*)z_out);
     return L->settle();
 }
 
@@ -159,9 +157,8 @@ hk_status Ops<C>::assignment_scatter(hk_ctx* ctx, const uint32_t* full_cols, con
     HK_TRY(L->carve([&](Carve& c) { stage_carve(c, in, 2); }));
     const void *cd = in[0].p, *vd = in[1].p;
     HK_TRY(stage_upload(L, in, 2));
-    hipLaunchKernelGGL((k_scatter_full_batch<Fr>), dim3((u32)((n_full + 63) / 64), (u32)batch), dim3(64), 0, L->stream,
-                       (const u32*)cd, (const Fr*)vd, (u32)n_full, n_v, (Fr*)z_out);
-    HK_HIP(hipGetLastError());
+    HK_LAUNCH((k_scatter_full_batch<Fr>), dim3((u32)((n_full + 63) / 64), (u32)batch), dim3(64), 0, L->stream,
+              (const u32*)cd, (const Fr*)vd, (u32)n_full, n_v, (Fr*)z_out);
     return L->settle();
 }
 
@@ -191,8 +188,7 @@ hk_status Ops<C>::poseidon_path(hk_ctx* ctx, const void* consts, size_t n_consts
     const void *cd = in[0].p, *ld = in[1].p, *sd = in[2].p, *id = in[3].p;
     HK_TRY(stage_upload(L, in, 4));
     // row b is its own source: leaf b, path b, direction bits from index[b]
-    poseidon_membership<Fr, 4>(L->stream, cd, lh, nh, ld, sd, nullptr, (const u32*)id, 1, depth, batch, n_v, col0, z_out);
-    HK_HIP(hipGetLastError());
+    HK_TRY((poseidon_membership<Fr, 4>(L->stream, cd, lh, nh, ld, sd, nullptr, (const u32*)id, 1, depth, batch, n_v, col0, z_out)));
     return L->settle();
 }
 

@@ -109,6 +109,13 @@ typedef struct {
 
 const char* hk_status_str(hk_status s);
 const char* hk_version(void);
+/* Diagnostics: entry i of the kernels the library launches - every one of them, since each is launched through one helper
+ * that registers it when the library is loaded.  name: the kernel and its parameter types; only_with_env: NULL, or the
+ * environment switch without which nothing launches it; private_bytes: its private-memory frame per lane, from the loaded
+ * code object - the deepest of them (over the entries whose switch, if any, is set) sizes every hardware queue's scratch
+ * ring.  private_bytes may be NULL: no HIP call is made then, so the list can be read on a machine without a GPU.  The
+ * strings live as long as the library.  HK_ERR_ARG once i is past the end. */
+hk_status hk_kernel_info(size_t i, const char** name, size_t* private_bytes, const char** only_with_env);
 
 /* ---- context ------------------------------------------------------------------------ */
 hk_status hk_ctx_create(hk_curve curve, int device_id, hk_ctx** out);

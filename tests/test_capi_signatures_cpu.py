@@ -29,7 +29,7 @@ def _declarations():
 def test_header_parse():
     decls = _declarations()
     names = [n for _, n, _ in decls]
-    assert len(decls) == 81 and len(set(names)) == 81
+    assert len(decls) == 82 and len(set(names)) == 82
     assert {r for r, _, _ in decls} == set(RESTYPES)
 
 
